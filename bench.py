@@ -10,7 +10,12 @@ GaussianUnknownMean traces already resident in HBM: zero_grad -> InferenceNetwor
 hidden 512, 1 643 583 parameters, fp32. For N > 1 the driver launches one process per GPU
 (torch.distributed.run); per-GPU work is fixed (weak scaling), value = whole-job traces/s.
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps steps and prints the line (metric, value, unit, ms_per_step, config).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy: for the training workloads the loss of that
+step and the parameters and Adam moments after it (that step trains from the engine's initial state, so the files depend on
+the arguments only); for `is` the values and log-weights of the last posterior_results call.
+
+With --full the JSON line also carries
   roofline     : the dominant kernel of the step - the row-panel launch (csrc/panel.hip: the whole forward + backward data
                  path of the minibatch, fp32 MFMA 4x4x1 with weights streamed from L2) - timed live with HIP events on the
                  stream it runs on inside the timed region (every stride-th launch), priced against the fp32-matrix peak
@@ -282,8 +287,45 @@ def committed_profile(name):
     return d, path
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: name -> array as path/<name>.npy, float64 kept, everything else float32. When the arrays together
+    exceed DUMP_BYTES, each one larger than an equal share of it is cut to a fixed, seeded sample of its flattened elements
+    (indices in ascending order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES:
+        share = DUMP_BYTES // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+                arrays[k] = a.reshape(-1)[keep]
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+
+
+def engine_state(eng):
+    """What a training step carries to the next one: parameters, Adam moments and the optimizer's per-tensor counters (the
+    gradients are clear between steps)."""
+    return [eng.params, eng.exp_avg, eng.exp_avg_sq, eng.tensor_step, eng.arrived]
+
+
+def restore_state(eng, snapshot):
+    """Stream-ordered copies of a snapshot of engine_state() back into the engine (after the step before, before the next)."""
+    for t, t_init in zip(engine_state(eng), snapshot):
+        t.copy_(t_init)
+
+
+def engine_outputs(eng, loss):
+    """What a caller of the training step receives: the step's loss, the parameters and the Adam moments after it."""
+    return dict(loss=np.array([float(loss)], np.float32), params=eng.params.cpu().numpy(), exp_avg=eng.exp_avg.cpu().numpy(),
+                exp_avg_sq=eng.exp_avg_sq.cpu().numpy())
+
+
 def api_posterior_bench(lib, device, lstm_dim, particles, calls, warm, program='gum', seed0=7, offset=0, train_traces=None,
-                        prof_class=4):
+                        prof_class=4, full=True, outputs=None):
     """BASELINE.json configs[3] through the drop-in API: Model.learn_inference_network (a short run: the network only has to
     exist and be sane) then `calls` x Model.posterior_results(particles, IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK,
     observe=...) in lock step, the observation cycling through three values. What a timed call runs is reported, not
@@ -291,7 +333,8 @@ def api_posterior_bench(lib, device, lstm_dim, particles, calls, warm, program='
     recordings the call replays three C-ABI calls with the new observation and forward() is NOT run; `plan_replays` counts
     them) - the same loop with PP_IS_PLAN=0, where state.sample / state.observe / Trace.end run on the user's forward() every
     call (pyprob/model.py:47-88, 180-181; state.py:118-155, 203-219), is timed next to it (`noplan`). The Empirical statistics
-    are read back every call either way. Returns (record, seconds, units)."""
+    are read back every call either way. Returns (record, seconds, units). full=False: the wall-time loop only (no
+    instrumented loop, no `noplan` loop); `outputs` (a dict) receives the values and log-weights of the last timed call."""
     import contextlib
     import io
     from pyprob_amd.state import InferenceEngine, InferenceNetwork
@@ -327,14 +370,17 @@ def api_posterior_bench(lib, device, lstm_dim, particles, calls, warm, program='
     # call (~25 statement launches) ~0.5 ms: the wall time is taken from an UN-instrumented loop, the kernel times from a second,
     # instrumented one
     dt, replays, last = timed_loop()
-    lib.pp_prof_arm(prof_class, cap)
-    timed_loop()
-    post = last[0]                                   # the configuration's own observation: its posterior is what is reported
+    if outputs is not None:
+        outputs.update(values=last[(calls - 1) % 3].values_numpy(), log_weights=last[(calls - 1) % 3].log_weights_numpy())
     ms = np.zeros(cap, np.float32)
     fl = np.zeros(cap, np.float64)
     cnt = C.c_int32(0)
-    lib.pp_prof_collect(ms.ctypes.data, cap, C.byref(cnt), fl.ctypes.data)
-    lib.pp_prof_arm(prof_class, 0)
+    if full:
+        lib.pp_prof_arm(prof_class, cap)
+        timed_loop()
+        lib.pp_prof_collect(ms.ctypes.data, cap, C.byref(cnt), fl.ctypes.data)
+        lib.pp_prof_arm(prof_class, 0)
+    post = last[0]                                   # the configuration's own observation: its posterior is what is reported
     plans = getattr(model, '_lockstep_plans', None) or {}
     first_kernel = any(p.get('first') for p in plans.values() if isinstance(p, dict))
     executes = (('launch-plan replay: two C-ABI calls per call (pp_is_first_statement, pp_is_fused), forward() NOT run'
@@ -351,7 +397,7 @@ def api_posterior_bench(lib, device, lstm_dim, particles, calls, warm, program='
                posterior_mean=round(float(post.mean), 4), posterior_stddev=round(float(post.stddev), 4),
                ess=round(float(post.effective_sample_size), 1), control_flow_paths=int(getattr(post, 'num_paths', 1)),
                network_params=model._inference_network._engine.spec.num_parameters())
-    if replays:
+    if full and replays:
         # the same loop with the plan off: forward() runs in every timed call
         old_env = os.environ.get('PP_IS_PLAN')
         os.environ['PP_IS_PLAN'] = '0'
@@ -563,7 +609,14 @@ def main():
     ap.add_argument('--no-is', action='store_true', help='skip the posterior_results sub-record of the default line')
     ap.add_argument('--graph', type=int, default=0, help='replay the step as a captured HIP graph (1) or launch eagerly (0)')
     ap.add_argument('--prewarm-s', type=float, default=0.35, help='untimed steady-state pre-warm before the --warmup steps')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure what the headline does not need: '
+                    'roofline and per-kernel timings, the IS and end-to-end records, the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy')
     args = ap.parse_args()
+    full = args.full
+    if args.dump_outputs and args.workload == 'dropin':
+        # (its timed path is a whole learn_inference_network call: a chain of steps whose end state is not reproducible)
+        ap.error('--dump-outputs: not available for --workload dropin')
     if (args.gpus > 1 or os.environ.get('PP_BENCH_SELF_LAUNCH') == '1') and 'RANK' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start one process per GPU ourselves, the way the reference spawns
         # its own workers (pyprob/model.py:339-406); rank 0 of the children prints the line
@@ -618,8 +671,10 @@ def main():
     if use_dist:
         out['rccl_ranks'] = out_rccl
     K, W = args.steps, args.warmup
+    outputs = {} if args.dump_outputs else None
 
     if args.workload == 'train':
+        initial_state = [t.clone() for t in engine_state(eng)]
         B = args.batch
         per_rank = max(args.dataset // world, B * 8)
         obs, mu, prior = synth_gum_dataset(per_rank, device, seed=1000 + rank)
@@ -661,13 +716,17 @@ def main():
         forced = os.environ.get('PP_BENCH_LOOP', 'auto')
 
         def run_steps(i0, n, native):
+            """Returns the device scalar that will hold the loss of the last of the n steps."""
             if not native:
                 for i in range(i0, i0 + n):
                     step(i)
-                return
+                return eng.loss_buf[:1]
+            last = None
             for c0 in range(0, n, 256):
                 m = min(256, n - c0)
-                eng.train_resident([pick(i0 + c0 + j) for j in range(m)], [lr] * m)
+                losses, _ = eng.train_resident([pick(i0 + c0 + j) for j in range(m)], [lr] * m)
+                last = losses[m - 1:m]
+            return last
 
         def wall(native, n):
             barrier()
@@ -714,15 +773,23 @@ def main():
             os.environ.get('PP_DETERMINISTIC', '0') != '1'
         live_class = 0 if panel_expected else 1
         stride = max(4, K // 50)
-        if not args.graph:
+        if full and not args.graph:
             lib.pp_prof_stride(stride)
             lib.pp_prof_arm(live_class, K // stride + 1)
         barrier()
         t0 = time.perf_counter()
-        run_steps(W, K, native_loop)
+        run_steps(W, K - 1, native_loop)
+        # the last timed step trains from the engine's initial state: the float atomics of the kernels' reductions make the
+        # state a chain of steps arrives at differ in the last bits from run to run, and Adam carries such differences on.
+        # This way the inputs of the step that --dump-outputs writes are the same every run (the copies cost ~0.1 % of the region)
+        restore_state(eng, initial_state)
+        last_loss = run_steps(W + K - 1, 1, native_loop)
         barrier()
         dt = time.perf_counter() - t0
         gc.enable()
+        final_loss = float(last_loss.item())
+        if outputs is not None:
+            outputs.update(engine_outputs(eng, final_loss))
 
         def collect(which, n):
             ms = np.zeros(n, np.float32)
@@ -742,28 +809,29 @@ def main():
             torch.cuda.synchronize()
             return collect(which, n)
 
-        live = eager_pass(live_class, min(K, 50)) if args.graph else collect(live_class, K)
-        lib.pp_prof_stride(1)
-        # per-step times (event pairs between consecutive steps of one more untimed pass): the median next to the mean
-        n_med = min(max(K, 20), 200)
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
-        evs[0].record()
-        for i in range(n_med):
-            step(i)
-            evs[i + 1].record()
-        torch.cuda.synchronize()
-        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
-        out['ms_per_step_median'] = round(per_step[n_med // 2], 4)
-        other = eager_pass(1 - live_class, min(K, 50))
-        first, dominant = (live, other) if live_class == 0 else (other, live)      # class 0 / class 1 samples
-        gather = eager_pass(2, min(K, 50))
-        adam = eager_pass(3, min(K, 50))
-        final_loss = float(eng.loss_buf[0].item())
+        first = dominant = gather = adam = None
+        if full:
+            live = eager_pass(live_class, min(K, 50)) if args.graph else collect(live_class, K)
+            lib.pp_prof_stride(1)
+            # per-step times (event pairs between consecutive steps of one more untimed pass): the median next to the mean
+            n_med = min(max(K, 20), 200)
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_med + 1)]
+            evs[0].record()
+            for i in range(n_med):
+                step(i)
+                evs[i + 1].record()
+            torch.cuda.synchronize()
+            per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(n_med))
+            out['ms_per_step_median'] = round(per_step[n_med // 2], 4)
+            other = eager_pass(1 - live_class, min(K, 50))
+            first, dominant = (live, other) if live_class == 0 else (other, live)      # class 0 / class 1 samples
+            gather = eager_pass(2, min(K, 50))
+            adam = eager_pass(3, min(K, 50))
         units = B * K
         metric, unit = 'ic_train_traces_per_sec', 'traces/s'
         # HBM bytes per launch (PMC passes) and rocprofv3 --kernel-trace --stats averages of this command, committed by
         # tools/profile_round.sh together with the hash of the kernel sources they were measured on: quoted only on a match
-        std_shape = B == 1024 and args.lstm_dim == 512
+        std_shape = full and B == 1024 and args.lstm_dim == 512
         pmc_doc, pmc_file = committed_profile('r06_pmc_traffic.json') if std_shape else (None, 'not the profiled shape')
         pmc = (pmc_doc or {}).get('kernels', {})
         avg_doc, avg_file = committed_profile('r06_kernel_avgs.json') if std_shape else (None, 'not the profiled shape')
@@ -897,7 +965,7 @@ def main():
                       loop_probe_us_per_step={k: round(v * 1e6, 2) for k, v in probe.items()},
                       allreduce_bytes_per_step=(4 * (eng.grads_full.numel() - sum(c for _, c in eng.dp_skip)) if use_dist else 0),
                       dp_exchange=dp_exchange)
-        if world == 1 and not args.no_is:
+        if full and world == 1 and not args.no_is:
             # the other half of BASELINE.json's metric in the same line: particles/s of posterior_results through the API
             # (configs[3] on one GPU; `--workload is` is the full record incl. the control-flow program)
             out['is'] = api_posterior_bench(lib, device, args.lstm_dim, 1000000, 100, 6, 'gum')[0]      # (100 calls: ~7 ms timed)
@@ -914,7 +982,7 @@ def main():
                 out['gumm_lockstep_1m']['statement_kernel'] = {k: g1m['statement_kernel'][k] for k in
                                                                ('achieved', 'frac', 'frac_executed',
                                                                 'us_per_call', 'launches_per_call', 'wall_over_statement_kernels')}
-        if world == 1 and not args.no_is:
+        if full and world == 1 and not args.no_is:
             out['online_e2e'] = online_training_bench(device, args.lstm_dim, B, 2 * 1024 * 1024)
             config['online_e2e_traces_per_sec'] = out['online_e2e']['traces_per_sec']
             try:      # (needs a writable temporary directory for the 40 MB of packed shards)
@@ -925,7 +993,8 @@ def main():
                 out['offline_e2e'] = dict(error=repr(exc))
         # the driver's record keeps the flat scalars of `config` / `roofline` and only the NAMES of nested objects: every
         # number README.md quotes is repeated here as a flat key
-        config['ms_per_step_median'] = out.get('ms_per_step_median')
+        if 'ms_per_step_median' in out:
+            config['ms_per_step_median'] = out['ms_per_step_median']
         for key, flat in (('is', 'is_particles_per_sec'), ('gumm_lockstep', 'gumm_lockstep_particles_per_sec'),
                           ('gumm_lockstep_1m', 'gumm_lockstep_1m_particles_per_sec')):
             if key in out:
@@ -943,7 +1012,7 @@ def main():
         rl = out.get('roofline', {})
         # MFMA utilisation by COUNTER (SQ_VALU_MFMA_BUSY_CYCLES over the launch's SIMD cycles, tools/pmc_kernel.sh; quoted on a
         # source-hash match): what `frac_executed` estimates from the FLOP count
-        mdoc, mnote = committed_profile('r06_mfma_busy.json') if (args.batch == 1024 and args.lstm_dim == 512) else (None, 'not the profiled shape')
+        mdoc, mnote = committed_profile('r06_mfma_busy.json') if (full and args.batch == 1024 and args.lstm_dim == 512) else (None, 'not the profiled shape')
         if mdoc is not None and 'kernel' in rl:
             key = 'panel' if 'panel16' in rl['kernel'] else 'wgrad_group'
             rl['mfma_busy_frac'] = mdoc['kernels'].get(key, {}).get('mfma_busy_frac')
@@ -978,24 +1047,25 @@ def main():
             batches.append(PackedBatch.from_ragged(arr['trace_len'], ids, arr['values'], arr['prior'], arr['obs'],
                                                    len(eng.spec.addresses)).to(device))
         lr = 1e-3 * (world ** 0.5)
+        initial_state = [t.clone() for t in engine_state(eng)]
         for i in range(W):
             eng.train_step(batches[i % nb], lr)
         # the weight-gradient launch timed live: an event pair costs the stream ~5 us (two boundaries around the launch, visible
         # as gaps in profiles/s5v_ragged_step_sequence.csv) - every 4-th launch carries one, as in the default workload
-        lib.pp_prof_stride(4)
-        lib.pp_prof_arm(1, K // 4 + 1)
+        if full:
+            lib.pp_prof_stride(4)
+            lib.pp_prof_arm(1, K // 4 + 1)
         barrier()
         t0 = time.perf_counter()
-        for i in range(K):
+        for i in range(K - 1):
             eng.train_step(batches[(W + i) % nb], lr)
+        restore_state(eng, initial_state)      # (as in the default workload: the dumped step's inputs are the same every run)
+        eng.train_step(batches[(W + K - 1) % nb], lr)
         barrier()
         dt = time.perf_counter() - t0
-        ms = np.zeros(K, np.float32)
-        fl = np.zeros(K, np.float64)
-        cnt = C.c_int32(0)
-        lib.pp_prof_collect(ms.ctypes.data, K, C.byref(cnt), fl.ctypes.data)
-        lib.pp_prof_arm(1, 0)
-        lib.pp_prof_stride(1)
+        final_loss = float(eng.loss_buf[0].item())
+        if outputs is not None:
+            outputs.update(engine_outputs(eng, final_loss))
         units = B * K
         metric, unit = 'ic_train_traces_per_sec', 'traces/s'
         mean_len = float(np.mean([b.mean_length_controlled for b in batches]))
@@ -1003,39 +1073,46 @@ def main():
                                'addresses/heads), LSTM hidden=%d, batch=%d per GPU' % (mean_len, len(addresses),
                                                                                        args.lstm_dim, B),
                       params=eng.spec.num_parameters(), global_batch=B * world, parallelism='dp%d' % world,
-                      final_loss=round(float(eng.loss_buf[0].item()), 4), launch='eager')
-        flops_step = 0.0
-        for b in batches[:1]:
-            n_later = b.n_rows - b.n_traces
-            flops_step = 3.0 * (B * 18496 + b.n_rows * (868352 + 293764 + 8) + n_later * 2097152)
-        out['roofline'] = dict(bound='mfma', achieved=round(flops_step * K / dt / 1e12, 3), peak=FP32_MATRIX_PEAK_TFLOPS,
-                               unit='TFLOP/s', frac=round(flops_step * K / dt / 1e12 / FP32_MATRIX_PEAK_TFLOPS, 4), traffic=None,
-                               kernel='whole step (all GEMM + elementwise kernels), algorithmic FLOPs of SURVEY.md 8(d) x3 for '
-                                      'training / wall-clock step time')
-        # HBM bytes of the WHOLE step (all launches) from the committed PMC passes of this command (tools/profile_round6.sh), quoted
-        # on a source-hash match; algorithmic bytes per step: every parameter read in the forward and the backward
-        # pass, its gradient written, Adam's read of (w, g, m, v) and write of (w, m, v) = 44 B per parameter, + the materialised
-        # LSTM input rows (written, read by the weight gradients) and the per-row gate / hidden / cell rows written forward and
-        # read backward
-        P_ = eng.spec.num_parameters()
-        rows_ = float(np.mean([b.n_rows for b in batches]))
-        H_ = args.lstm_dim
-        alg_bytes = 44.0 * P_ + rows_ * 4.0 * (2 * 68 + 2 * (4 * H_ + 2 * H_) + 2 * (int((H_ + 30) / 2) + 30))
-        gdoc, gnote = committed_profile('r06_gumm_traffic.json') if (B == 1024 and H_ == 512) else (None, 'not the profiled shape')
-        out['roofline']['traffic'] = (gdoc or {}).get('traffic_bytes_per_step')
-        out['roofline']['algorithmic_bytes'] = round(alg_bytes)
-        out['roofline']['traffic_source'] = gnote if gdoc is None else '%s (csrc_sha %s)' % (gnote, gdoc.get('csrc_sha'))
-        if out['roofline']['traffic']:
-            out['roofline']['traffic_ratio'] = round(out['roofline']['traffic'] / alg_bytes, 3)
-        out['roofline']['launches_per_step'] = (gdoc or {}).get('launches_per_step')
-        if cnt.value > 0:
-            avg_ms, flops = float(ms[:cnt.value].mean()), float(fl[:cnt.value].mean())
-            ach = flops / (avg_ms * 1e-3) / 1e12
-            out['roofline']['dominant_kernel'] = dict(
-                bound='mfma', achieved=round(ach, 3), peak=FP32_MATRIX_PEAK_TFLOPS, unit='TFLOP/s',
-                frac=round(ach / FP32_MATRIX_PEAK_TFLOPS, 4), avg_launch_us=round(avg_ms * 1e3, 3), launches_timed=int(cnt.value),
-                flops_per_launch=flops, kernel='grouped weight-gradient launch holding dW_ih / dW_hh of the backward pass '
-                                               '(the head products of the %d addresses ride in the same grouped launches)' % len(addresses))
+                      final_loss=round(final_loss, 4), launch='eager')
+        if full:
+            ms = np.zeros(K, np.float32)
+            fl = np.zeros(K, np.float64)
+            cnt = C.c_int32(0)
+            lib.pp_prof_collect(ms.ctypes.data, K, C.byref(cnt), fl.ctypes.data)
+            lib.pp_prof_arm(1, 0)
+            lib.pp_prof_stride(1)
+            flops_step = 0.0
+            for b in batches[:1]:
+                n_later = b.n_rows - b.n_traces
+                flops_step = 3.0 * (B * 18496 + b.n_rows * (868352 + 293764 + 8) + n_later * 2097152)
+            out['roofline'] = dict(bound='mfma', achieved=round(flops_step * K / dt / 1e12, 3), peak=FP32_MATRIX_PEAK_TFLOPS,
+                                   unit='TFLOP/s', frac=round(flops_step * K / dt / 1e12 / FP32_MATRIX_PEAK_TFLOPS, 4), traffic=None,
+                                   kernel='whole step (all GEMM + elementwise kernels), algorithmic FLOPs of SURVEY.md 8(d) x3 for '
+                                          'training / wall-clock step time')
+            # HBM bytes of the WHOLE step (all launches) from the committed PMC passes of this command (tools/profile_round6.sh), quoted
+            # on a source-hash match; algorithmic bytes per step: every parameter read in the forward and the backward
+            # pass, its gradient written, Adam's read of (w, g, m, v) and write of (w, m, v) = 44 B per parameter, + the materialised
+            # LSTM input rows (written, read by the weight gradients) and the per-row gate / hidden / cell rows written forward and
+            # read backward
+            P_ = eng.spec.num_parameters()
+            rows_ = float(np.mean([b.n_rows for b in batches]))
+            H_ = args.lstm_dim
+            alg_bytes = 44.0 * P_ + rows_ * 4.0 * (2 * 68 + 2 * (4 * H_ + 2 * H_) + 2 * (int((H_ + 30) / 2) + 30))
+            gdoc, gnote = committed_profile('r06_gumm_traffic.json') if (B == 1024 and H_ == 512) else (None, 'not the profiled shape')
+            out['roofline']['traffic'] = (gdoc or {}).get('traffic_bytes_per_step')
+            out['roofline']['algorithmic_bytes'] = round(alg_bytes)
+            out['roofline']['traffic_source'] = gnote if gdoc is None else '%s (csrc_sha %s)' % (gnote, gdoc.get('csrc_sha'))
+            if out['roofline']['traffic']:
+                out['roofline']['traffic_ratio'] = round(out['roofline']['traffic'] / alg_bytes, 3)
+            out['roofline']['launches_per_step'] = (gdoc or {}).get('launches_per_step')
+            if cnt.value > 0:
+                avg_ms, flops = float(ms[:cnt.value].mean()), float(fl[:cnt.value].mean())
+                ach = flops / (avg_ms * 1e-3) / 1e12
+                out['roofline']['dominant_kernel'] = dict(
+                    bound='mfma', achieved=round(ach, 3), peak=FP32_MATRIX_PEAK_TFLOPS, unit='TFLOP/s',
+                    frac=round(ach / FP32_MATRIX_PEAK_TFLOPS, 4), avg_launch_us=round(avg_ms * 1e3, 3), launches_timed=int(cnt.value),
+                    flops_per_launch=flops, kernel='grouped weight-gradient launch holding dW_ih / dW_hh of the backward pass '
+                                                   '(the head products of the %d addresses ride in the same grouped launches)' % len(addresses))
     elif args.workload == 'dropin':
         # What a pyprob user gets after binding.install(): the executors pyprob_amd/pyprob_host.py routes pyprob.Model through,
         # end to end (trace generation, layer creation, bookkeeping included) - measured here through pyprob_amd.Model, the host
@@ -1047,28 +1124,30 @@ def main():
         dt, units = rec['seconds'], rec['traces']
         K = units // B
         metric, unit = 'ic_train_traces_per_sec', 'traces/s'
-        old_env = os.environ.get('PP_IS_PLAN')
-        os.environ['PP_IS_PLAN'] = '0'
-        try:
-            isr = api_posterior_bench(lib, device, args.lstm_dim, args.particles, 20, 3, 'gum')[0]
-            gm = api_posterior_bench(lib, device, args.lstm_dim, 200000, 5, 2, 'gumm', prof_class=5)[0]
-        finally:
-            if old_env is None:
-                os.environ.pop('PP_IS_PLAN', None)
-            else:
-                os.environ['PP_IS_PLAN'] = old_env
-        gmm = online_training_bench(device, args.lstm_dim, B, 256 * B, 'gumm')
-        off = offline_training_bench(device, args.lstm_dim, B, args.dataset)
-        out['offline_e2e'] = off
         config = dict(workload='drop-in paths end to end (pyprob_host executors through pyprob_amd.Model): GaussianUnknownMean online '
                                'IC training incl. prior generation, LSTM hidden=%d, batch=%d' % (args.lstm_dim, B),
                       parallelism='dp1', online_e2e_traces_per_sec=rec['traces_per_sec'],
-                      online_e2e_bookkept_traces_per_sec=rec['bookkept_traces_per_sec'], online_final_loss=rec['final_loss'],
-                      gumm_online_e2e_traces_per_sec=gmm['traces_per_sec'],
-                      offline_e2e_traces_per_sec=off['traces_per_sec'], offline_traces_on_disk=off['traces'],
-                      save_dataset_traces_per_sec=off['save_dataset_traces_per_sec'],
-                      is_noplan_particles_per_sec=isr['particles_per_sec'], is_noplan_ms_per_call=isr['ms_per_call'],
-                      gumm_lockstep_particles_per_sec=gm['particles_per_sec'], api=rec['api'])
+                      online_e2e_bookkept_traces_per_sec=rec['bookkept_traces_per_sec'], online_final_loss=rec['final_loss'])
+        if full:
+            old_env = os.environ.get('PP_IS_PLAN')
+            os.environ['PP_IS_PLAN'] = '0'
+            try:
+                isr = api_posterior_bench(lib, device, args.lstm_dim, args.particles, 20, 3, 'gum')[0]
+                gm = api_posterior_bench(lib, device, args.lstm_dim, 200000, 5, 2, 'gumm', prof_class=5)[0]
+            finally:
+                if old_env is None:
+                    os.environ.pop('PP_IS_PLAN', None)
+                else:
+                    os.environ['PP_IS_PLAN'] = old_env
+            gmm = online_training_bench(device, args.lstm_dim, B, 256 * B, 'gumm')
+            off = offline_training_bench(device, args.lstm_dim, B, args.dataset)
+            out['offline_e2e'] = off
+            config.update(gumm_online_e2e_traces_per_sec=gmm['traces_per_sec'],
+                          offline_e2e_traces_per_sec=off['traces_per_sec'], offline_traces_on_disk=off['traces'],
+                          save_dataset_traces_per_sec=off['save_dataset_traces_per_sec'],
+                          is_noplan_particles_per_sec=isr['particles_per_sec'], is_noplan_ms_per_call=isr['ms_per_call'],
+                          gumm_lockstep_particles_per_sec=gm['particles_per_sec'])
+        config['api'] = rec['api']
         out['roofline'] = dict(bound='host', achieved=None, peak=None, unit='traces/s', frac=None, traffic=None,
                                note='an end-to-end rate through the host API: see the default workload for the kernels\' rooflines')
     else:
@@ -1076,19 +1155,21 @@ def main():
         # the data path: distinct Philox counter ranges per rank)
         n = args.particles // world
         del eng
-        rec, dt, units = api_posterior_bench(lib, device, args.lstm_dim, n, K, max(W, 3), 'gum', offset=rank * n)
+        rec, dt, units = api_posterior_bench(lib, device, args.lstm_dim, n, K, max(W, 3), 'gum', offset=rank * n, full=full,
+                                             outputs=outputs)
         metric, unit = 'is_posterior_particles_per_sec', 'particles/s'
         pk = rec.pop('particle_kernels', None)
-        out['roofline'] = pk if pk else dict(bound='hbm', achieved=None, peak=HBM_PEAK_GBS, unit='GB/s', frac=None, traffic=None)
-        out['roofline'].setdefault('traffic', None)
+        if full:
+            out['roofline'] = pk if pk else dict(bound='hbm', achieved=None, peak=HBM_PEAK_GBS, unit='GB/s', frac=None, traffic=None)
+            out['roofline'].setdefault('traffic', None)
         config = dict(workload='GaussianUnknownMean posterior_results IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK through '
                                'Model.posterior_results on the user program, LSTM hidden=%d, %d particles per call per GPU'
                                % (args.lstm_dim, n), parallelism='particles sharded x%d' % world, **rec)
-        if world == 1:      # the N-row network step: a program with stochastic control flow in lock step
+        if full and world == 1:      # the N-row network step: a program with stochastic control flow in lock step
             g, _, _ = api_posterior_bench(lib, device, args.lstm_dim, 200000, max(3, K // 10), 2, 'gumm', prof_class=5)
             out['gumm_lockstep'] = g
 
-    if use_dist and args.workload == 'train' and eng.native_dp and not args.graph:
+    if full and use_dist and args.workload == 'train' and eng.native_dp and not args.graph:
         # the exchange of a step, by HIP event pairs (a short pass of its own: a record costs the stream ~1.5 us): the early
         # ranges' all-reduce on the side stream, the rest's on the step's stream, and what the step then still waited for the side
         # stream. exposed = rest + wait (what sits between the backward pass and Adam); PP_DP_OVERLAP=0: one collective, all of it
@@ -1127,12 +1208,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = units * world / dt
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         line = dict(metric=metric, value=round(value, 1), unit=unit, n_gpus=world, steps=K, warmup=W,
                     ms_per_step=round(dt / K * 1e3, 4), higher_is_better=True, scaling='weak', vs_baseline=None,
                     dtype='f32', data='synthetic', config=config)
         line.update(out)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             # the live reference where it can be imported (kind "reference"); on the GPU box the torch port of the step
             # (the stronger of the two ports) with the reference's recorded figures next to it
             live = cpu_baseline_reference(args.lstm_dim, args.batch, args.workload)

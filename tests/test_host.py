@@ -232,6 +232,23 @@ def test_bench_stdout_carries_only_the_json_line():
     assert 'banner written by a C library' in r.stderr and 'python chatter' in r.stderr
 
 
+def test_bench_dump_outputs_keeps_float64_and_samples_to_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 arrays stay float64, everything else is written as float32; past the byte budget an
+    array larger than its share becomes a seeded sample of its elements, the same on every run."""
+    import bench
+    big = np.arange(3000, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / 'a'), dict(loss=np.array([1.5], np.float32), big=big, lw=np.arange(4.0), n=np.arange(3)))
+    assert np.load(tmp_path / 'a' / 'lw.npy').dtype == np.float64 and np.load(tmp_path / 'a' / 'n.npy').dtype == np.float32
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'big.npy'), big)
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4096)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), dict(loss=np.array([1.5], np.float32), big=big))
+    s = np.load(tmp_path / 'b' / 'big.npy')
+    assert s.size == 2048 // 4 and np.all(np.diff(s) > 0) and np.isin(s, big).all()
+    np.testing.assert_array_equal(s, np.load(tmp_path / 'c' / 'big.npy'))
+    np.testing.assert_array_equal(np.load(tmp_path / 'b' / 'loss.npy'), [1.5])
+
+
 # ---- host logic of the streaming weight-gradient launch (csrc/wgrad_t1.hip), no device work -----------------------------
 def _wgrad_plan(products, zero_blocks=None):
     """products: dicts M, N, K, lda, ldb, ldc [, gather] -> list of problems {M, N, K, S, ks, gather, first, c_off, a_off, b_off}."""

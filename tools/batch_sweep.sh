@@ -5,7 +5,7 @@ OUT=gpurun_out; mkdir -p $OUT
 LOG=$OUT/${TAG}_batch_sweep.log; : > $LOG
 for H in 512 1024; do
 for B in 1024 2048 4096 8192 16384; do
-  timeout 60 python bench.py --batch $B --lstm-dim $H --steps 100 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 60 python bench.py --batch $B --lstm-dim $H --steps 100 --warmup 10 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.read().strip().splitlines()[-1])

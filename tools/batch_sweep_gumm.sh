@@ -3,7 +3,7 @@ TAG=${1:-r02}
 OUT=gpurun_out; mkdir -p $OUT
 LOG=$OUT/${TAG}_batch_sweep_gumm.log; : > $LOG
 for B in 1024 2048 4096 8192; do
-  timeout 90 python bench.py --workload train_gumm --batch $B --steps 60 --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 90 python bench.py --workload train_gumm --batch $B --steps 60 --warmup 10 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -9,7 +9,7 @@ for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BU
   n=$((n+1))
   [ $n -gt ${PASSES:-5} ] && break
   rm -rf $OUT/fp_pmc_$n
-  rocprofv3 --kernel-trace --pmc $set -d $OUT/fp_pmc_$n -o p -- python $OUT/../bench.py "$@" --no-cpu-baseline --prewarm-s 0 > $OUT/${TAG}_pmc_$n.log 2>&1
+  rocprofv3 --kernel-trace --pmc $set -d $OUT/fp_pmc_$n -o p -- python $OUT/../bench.py "$@" --full --no-cpu-baseline --prewarm-s 0 > $OUT/${TAG}_pmc_$n.log 2>&1
   python $OUT/../tools/pmc_summary.py $OUT/fp_pmc_$n/p_results.db $OUT/${TAG}_pmc_$n.csv 0
   grep "$KERNEL" $OUT/${TAG}_pmc_$n.csv | cut -d, -f2- | cut -c1-120
   rm -rf $OUT/fp_pmc_$n

@@ -7,10 +7,10 @@ TAG=${1:-s5a}
 REPO=$PWD; OUT=$PWD/gpurun_out; mkdir -p $OUT
 # the driver's command FIRST, in the fresh session (a bench line measured right after a profiled or test run of the same box
 # session shows every memory-latency-bound kernel ~1.6x slower); it quotes no rocprof / PMC figures yet
-python $REPO/bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_20_5_fresh.json 2> $OUT/${TAG}_bench_20_5_fresh.err
+python $REPO/bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_20_5_fresh.json 2> $OUT/${TAG}_bench_20_5_fresh.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/fp_ks
-rocprofv3 --kernel-trace --stats -d $OUT/fp_ks -o p -- python $REPO/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-is > $OUT/${TAG}_ks.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/fp_ks -o p -- python $REPO/bench.py --steps 200 --warmup 20 --full --no-cpu-baseline --no-is > $OUT/${TAG}_ks.log 2>&1
 python $REPO/tools/rocprof_summary.py $OUT/fp_ks/p_results.db $OUT/${TAG}_train_kernel_stats.csv > /dev/null
 python - <<P
 import sys; sys.path.insert(0, '$REPO/tools')
@@ -20,15 +20,15 @@ P
 rm -rf $OUT/fp_ks
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf $OUT/fp_pmc_$c
-  rocprofv3 --kernel-trace --pmc $c -d $OUT/fp_pmc_$c -o p -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-is > $OUT/${TAG}_pmc_$c.log 2>&1
+  rocprofv3 --kernel-trace --pmc $c -d $OUT/fp_pmc_$c -o p -- python $REPO/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-is > $OUT/${TAG}_pmc_$c.log 2>&1
   python $REPO/tools/pmc_summary.py $OUT/fp_pmc_$c/p_results.db $OUT/${TAG}_train_pmc_$c.csv 0
   rm -rf $OUT/fp_pmc_$c
 done
 cd $REPO
 python tools/profile_json.py $TAG $OUT/${TAG}_train_kernel_stats.csv $OUT/${TAG}_train_pmc_FETCH_SIZE.csv $OUT/${TAG}_train_pmc_WRITE_SIZE.csv
 cp profiles/r06_kernel_avgs.json $OUT/${TAG}_r06_kernel_avgs.json; cp profiles/r06_pmc_traffic.json $OUT/${TAG}_r06_pmc_traffic.json
-python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_20_5.json 2> $OUT/${TAG}_bench_20_5.err
-python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+python bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_20_5.json 2> $OUT/${TAG}_bench_20_5.err
+python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 tail -c 600 $OUT/${TAG}_bench_20_5.json; echo; python -c "
 import json
 for f in ('20_5', 'default'):
