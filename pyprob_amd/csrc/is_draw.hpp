@@ -5,19 +5,11 @@
 // proposal_poisson_truncated_normal_mixture.py).
 #pragma once
 #include "common.hpp"
+#include "head_math.hpp"
 
 #include <math.h>
 
 namespace pp {
-
-constexpr int MAXK = 16;
-constexpr float kFp32Eps = 1.1920928955078125e-07f;
-constexpr float kHalfLog2Pi = 0.91893853320467274178f;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kSqrt2 = 1.41421356237309504880f;
-constexpr float kTwoPi = 6.28318530717958647692f;
-
-__device__ __forceinline__ float std_cdf(float x) { return 0.5f * (1.0f + erff(x * kInvSqrt2)); }
 
 // ---- Philox4x32-10 (Salmon et al. 2011), counter = particle index, key = seed ----------------------------
 struct Philox {
@@ -52,9 +44,7 @@ __device__ __forceinline__ float box_muller_fast(float u1, float u2) {
     return __builtin_amdgcn_sqrtf(-2.0f * __logf(u1)) * __builtin_amdgcn_cosf(u2);
 }
 
-// One particle of a mixture head. KIND 0: Normal mixture around a Normal prior (pa, pb) = (mean, stddev); KIND 1:
-// TruncatedNormal mixture inside a Uniform prior (low, high); KIND 2: the Poisson head (TruncatedNormal mixture on [0, 40],
-// stddev = exp(y)). y = the 3K head outputs of the particle (means | scales | logits). Draws v (Philox counter `ctr`,
+// One particle of a mixture head (KIND 0 / 1 / 2: head_math.hpp). y = the 3K head outputs of the particle (means | scales | logits). Draws v (Philox counter `ctr`,
 // stream 0x1C) unless has_value, returns log q(v) in lp.
 template <int KIND>
 __device__ __forceinline__ void mixture_particle(const float* __restrict__ y, const float pa, const float pb, const int K,
@@ -83,14 +73,9 @@ __device__ __forceinline__ void mixture_particle(const float* __restrict__ y, co
     for (int k = 0; k < MAXK; ++k)
         if (k < K) {
             p[k] = p[k] / ps;
-            if (KIND == 0) {
-                mu[k] = pa + y[k] * pb;
-                sd[k] = expf(y[K + k]) * pb;
-            } else {
-                const float rng = pb - pa;
-                mu[k] = pa + sigmoidf_(y[k]) * rng;
-                sd[k] = KIND == 2 ? expf(y[K + k]) : rng / 1000.0f + sigmoidf_(y[K + k]) * rng * 10.0f;
-            }
+            const HeadComp c = head_component<KIND>(y[k], y[K + k], pa, pb);
+            mu[k] = c.mu;
+            sd[k] = c.sd;
         }
     float v;
     if (has_value) {
@@ -130,20 +115,11 @@ __device__ __forceinline__ void mixture_particle(const float* __restrict__ y, co
     }
     // log q(v)   (Mixture.log_prob, distributions/mixture.py:42-44)
     float a[MAXK], amax = -INFINITY;
-    const bool inside = (KIND == 0) || (v >= pa && v <= pb);
 #pragma unroll
     for (int k = 0; k < MAXK; ++k)
         if (k < K) {
-            const float lpk = logf(fminf(fmaxf(p[k], kFp32Eps), 1.0f - kFp32Eps));
-            const float t = (v - mu[k]) / sd[k];
-            float comp;
-            if (KIND == 0) {
-                comp = -0.5f * t * t - logf(sd[k]) - kHalfLog2Pi;
-            } else {
-                const float Z = std_cdf((pb - mu[k]) / sd[k]) - std_cdf((pa - mu[k]) / sd[k]);
-                comp = (inside ? 0.0f : -INFINITY) + (-0.5f * t * t - kHalfLog2Pi) - logf(sd[k] * Z);
-            }
-            a[k] = lpk + comp;
+            float t, alpha, beta, Z;
+            a[k] = log_clamped(p[k]) + component_logpdf<KIND>(v, mu[k], sd[k], pa, pb, t, alpha, beta, Z);
             amax = fmaxf(amax, a[k]);
         }
     float lp = amax;

@@ -43,16 +43,9 @@ __global__ __launch_bounds__(256) void is_mixture_shared_kernel(const float* __r
         for (int j = 0; j <= k && j < K; ++j) cum += (expf(y[2 * K + j] - zmax) / zs) / ps;
         if (k < K) {
             const float pk = (expf(y[2 * K + k] - zmax) / zs) / ps;
-            float mu, sd;
-            if (KIND == 0) {
-                mu = pa + y[k] * pb;
-                sd = expf(y[K + k]) * pb;
-            } else {
-                const float rng = pb - pa;
-                mu = pa + sigmoidf_(y[k]) * rng;
-                sd = KIND == 2 ? expf(y[K + k]) : rng / 1000.0f + sigmoidf_(y[K + k]) * rng * 10.0f;
-            }
-            const float lpk = logf(fminf(fmaxf(pk, kFp32Eps), 1.0f - kFp32Eps));
+            const HeadComp c = head_component<KIND>(y[k], y[K + k], pa, pb);
+            const float mu = c.mu, sd = c.sd;
+            const float lpk = log_clamped(pk);
             s_mu[k] = mu;
             s_sd[k] = sd;
             s_inv[k] = 1.0f / sd;
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(256) void is_categorical_kernel(const float* __rest
     }
     const float pv = (expf(y[vi] - zmax) / zs + 1e-8f) / S;
     value_out[i] = (float)vi;
-    logq_out[i] = logf(fminf(fmaxf(pv, kFp32Eps), 1.0f - kFp32Eps));
+    logq_out[i] = log_clamped(pv);
 }
 
 // Bernoulli proposal (proposal_bernoulli_bernoulli.py:16-20): probs = sigmoid(y) + 1e-8; value ~ Bernoulli(probs),
@@ -1255,16 +1248,9 @@ __global__ __launch_bounds__(256, 4) void is_fused_kernel(const float* __restric
                 if (j <= k) cum += rj;
             }
             if (k < K) {
-                float mu, sd;
-                if (KIND == 0) {
-                    mu = pa + y[k] * pb;
-                    sd = expf(y[K + k]) * pb;
-                } else {
-                    const float rng = pb - pa;
-                    mu = pa + sigmoidf_(y[k]) * rng;
-                    sd = KIND == 2 ? expf(y[K + k]) : rng / 1000.0f + sigmoidf_(y[K + k]) * rng * 10.0f;
-                }
-                const float lpk = logf(fminf(fmaxf(pk, kFp32Eps), 1.0f - kFp32Eps));
+                const HeadComp c = head_component<KIND>(y[k], y[K + k], pa, pb);
+                const float mu = c.mu, sd = c.sd;
+                const float lpk = log_clamped(pk);
                 s_mu[k] = mu; s_sd[k] = sd; s_inv[k] = 1.0f / sd; s_cum[k] = cum;
                 if (KIND == 0) {
                     s_c[k] = lpk - logf(sd) - kHalfLog2Pi;

@@ -40,11 +40,6 @@ namespace {
 constexpr int FR = 32;   // particles per workgroup
 constexpr int FW = 8;    // waves per workgroup
 
-// sigmoid / tanh on v_exp_f32 / v_rcp_f32 (~1 ulp each; absolute error of the results ~1e-7, asserted by
-// tests/test_gpu_is_step_fused.py against the float64 oracle)
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
 // reductions over the 16 lanes of a DPP row (lanes 16 q .. 16 q + 15): every lane ends with the result
 __device__ __forceinline__ float row16_max(float v) {
     v = fmaxf(v, dpp_mov<0x128>(v));   // row_ror:8
@@ -607,15 +602,8 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
         float p = comp ? expf(z - zmax) : 0.0f;
         p = p / row16_sum(p);
         p = p / row16_sum(p);
-        float mu, sd;
-        if (KIND == 0) {
-            mu = pa + (comp ? y[k] : 0.0f) * pb;
-            sd = expf(comp ? y[K + k] : 0.0f) * pb;
-        } else {
-            const float rng = pb - pa;
-            mu = pa + sigmoidf_(comp ? y[k] : 0.0f) * rng;
-            sd = KIND == 2 ? expf(comp ? y[K + k] : 0.0f) : rng / 1000.0f + sigmoidf_(comp ? y[K + k] : 0.0f) * rng * 10.0f;
-        }
+        const HeadComp hc = head_component<KIND>(comp ? y[k] : 0.0f, comp ? y[K + k] : 0.0f, pa, pb);
+        const float mu = hc.mu, sd = hc.sd;
         float ca = 0.0f, cb = 1.0f;
         if (KIND != 0) {
             ca = std_cdf((pa - mu) / sd);
@@ -657,12 +645,9 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
             }
         }
         // log q(v) = logsumexp_k (log p_k + log f_k(v))   (mixture.py:42-44)
-        const bool inside = (KIND == 0) || (v >= pa && v <= pb);
-        const float lpk = logf(fminf(fmaxf(p, kFp32Eps), 1.0f - kFp32Eps));
-        const float tt = (v - mu) / sd;
-        float term;
-        if (KIND == 0) term = -0.5f * tt * tt - logf(sd) - kHalfLog2Pi;
-        else term = (inside ? 0.0f : -INFINITY) + (-0.5f * tt * tt - kHalfLog2Pi) - logf(sd * (cb - ca));
+        const float lpk = log_clamped(p);
+        float tt;
+        const float term = component_logpdf<KIND>(v, mu, sd, pa, pb, cb - ca, tt);
         const float ak = comp ? lpk + term : -INFINITY;
         const float amax = row16_max(ak);
         float lp = amax;

@@ -37,9 +37,6 @@ constexpr int RING = 3;     // k-slabs of gate fragments in flight per wave
 // workgroups per CU overlap their phases, where one workgroup of eight waves ran them one after the other)
 constexpr int rows_per_block(int ubk) { return (ubk == 1 || ubk == 2) ? 64 : 32; }
 
-__device__ __forceinline__ float fast_sigmoid_s(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh_s(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-
 struct SmallPrepArgs {
     const float* P;
     const int64_t* at;
@@ -315,11 +312,11 @@ void is_step_small_kernel(const SmallArgs a) {
         // gates (torch.nn.LSTM order i, f, g, o) in place, then the barrier: every wave has read the tile and the old rows
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float gi = fast_sigmoid_s(acc[0][r]);
-            const float gg = fast_tanh_s(acc[2][r]);
+            const float gi = fast_sigmoid(acc[0][r]);
+            const float gg = fast_tanh(acc[2][r]);
             acc[0][r] = gi * gg;
-            acc[1][r] = fast_sigmoid_s(acc[1][r]);
-            acc[3][r] = fast_sigmoid_s(acc[3][r]);
+            acc[1][r] = fast_sigmoid(acc[1][r]);
+            acc[3][r] = fast_sigmoid(acc[3][r]);
         }
         SMALL_STAMP();      // 3 + 4 l: K loop + gates
         __syncthreads();
@@ -328,7 +325,7 @@ void is_step_small_kernel(const SmallArgs a) {
         for (int r = 0; r < 16; ++r) {
             const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
             const float cn = acc[1][r] * cp[r] + acc[0][r];
-            const float hn = acc[3][r] * fast_tanh_s(cn);
+            const float hn = acc[3][r] * fast_tanh(cn);
             if (m0 + row < a.n) {
                 const int64_t off = l * a.layer_stride + (int64_t)sRow[row] * H + u;
                 a.c[off] = cn;

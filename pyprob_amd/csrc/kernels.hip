@@ -3,6 +3,7 @@
 // embedding-table gradients, flat Adam. All fp32, gfx950 wave64.
 #include "common.hpp"
 #include "gather.hpp"
+#include "head_math.hpp"
 #include "aux_jobs.hpp"
 
 #include <math.h>
@@ -532,24 +533,12 @@ int lstm_cell_bwd(float* G, const float* c_prev, const float* c, const float* dh
 // ------------------------------------------------------------------------------------------------------
 // Proposal heads: transforms + log_prob + d log_prob / d y, one row per lane, loss reduced per wavefront.
 // ------------------------------------------------------------------------------------------------------
-constexpr int MAXK = 16;
-constexpr float kFp32Eps = 1.1920928955078125e-07f;   // torch.finfo(float32).eps (util.clamp_probs)
-constexpr float kHalfLog2Pi = 0.91893853320467274178f;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
-constexpr float kLogEps = -18.420680743952367f;        // log(1e-8), pyprob/util.py:35
-
-__device__ __forceinline__ float std_cdf(float x) { return 0.5f * (1.0f + erff(x * kInvSqrt2)); }
-__device__ __forceinline__ float std_pdf(float x) { return kInvSqrt2Pi * expf(-0.5f * x * x); }
-
 struct MixtureParams {
     float mu[MAXK], sd[MAXK], pi[MAXK], p[MAXK];
     float pisum;
 };
 
-// KIND 0: Normal components around a Normal prior; KIND 1: TruncatedNormal components inside a Uniform prior
-// (stddev = range/1000 + sigmoid(y) 10 range); KIND 2: the Poisson head - TruncatedNormal components on the fixed
-// interval [pa, pb] = [0, 40] with stddev = exp(y) (proposal_poisson_truncated_normal_mixture.py:19-37).
+// KIND 0 / 1 / 2: the mixture heads of head_math.hpp
 template <int KIND>
 __device__ __forceinline__ void mixture_params(const float* __restrict__ y, int K, float pa, float pb,
                                                MixtureParams& m, float sm[MAXK], float ss[MAXK]) {
@@ -576,16 +565,11 @@ __device__ __forceinline__ void mixture_params(const float* __restrict__ y, int 
     for (int k = 0; k < MAXK; ++k)
         if (k < K) {
             m.p[k] = m.pi[k] / ps;
-            if (KIND == 0) {
-                m.mu[k] = pa + y[k] * pb;
-                m.sd[k] = expf(y[K + k]) * pb;
-            } else {
-                const float rng = pb - pa;
-                sm[k] = sigmoidf_(y[k]);
-                ss[k] = sigmoidf_(y[K + k]);
-                m.mu[k] = pa + sm[k] * rng;
-                m.sd[k] = KIND == 2 ? expf(y[K + k]) : rng / 1000.0f + ss[k] * rng * 10.0f;
-            }
+            const HeadComp c = head_component<KIND>(y[k], y[K + k], pa, pb);
+            m.mu[k] = c.mu;
+            m.sd[k] = c.sd;
+            sm[k] = c.sm;
+            ss[k] = c.ss;
         }
 }
 
@@ -594,21 +578,11 @@ template <int KIND>
 __device__ __forceinline__ float mixture_logprob(const MixtureParams& m, int K, float v, float low, float high,
                                                  float a[MAXK]) {
     float amax = -INFINITY;
-    const bool inside = (KIND == 0) || (v >= low && v <= high);
 #pragma unroll
     for (int k = 0; k < MAXK; ++k)
         if (k < K) {
-            const float lpk = logf(fminf(fmaxf(m.p[k], kFp32Eps), 1.0f - kFp32Eps));
-            const float t = (v - m.mu[k]) / m.sd[k];
-            float comp;
-            if (KIND == 0) {
-                comp = -0.5f * t * t - logf(m.sd[k]) - kHalfLog2Pi;
-            } else {
-                const float alpha = (low - m.mu[k]) / m.sd[k], beta = (high - m.mu[k]) / m.sd[k];
-                const float Z = std_cdf(beta) - std_cdf(alpha);
-                comp = (inside ? 0.0f : -INFINITY) + (-0.5f * t * t - kHalfLog2Pi) - logf(m.sd[k] * Z);
-            }
-            a[k] = lpk + comp;
+            float t, alpha, beta, Z;
+            a[k] = log_clamped(m.p[k]) + component_logpdf<KIND>(v, m.mu[k], m.sd[k], low, high, t, alpha, beta, Z);
             amax = fmaxf(amax, a[k]);
         }
     if (!(amax > -INFINITY)) return amax;  // -inf (or NaN)
@@ -669,21 +643,16 @@ __global__ __launch_bounds__(64) void head_mixture_kernel(const float* __restric
                 for (int k = 0; k < MAXK; ++k)
                     if (k < K) {
                         const float t = (v - m.mu[k]) / m.sd[k];
-                        float dmu, dsd;
-                        if (KIND == 0) {
-                            dmu = resp[k] * t / m.sd[k];
-                            dsd = resp[k] * (t * t - 1.0f) / m.sd[k];
+                        if (KIND == 0) {   // (in another order than component_grad's lane form)
+                            const float dmu = resp[k] * t / m.sd[k];
+                            const float dsd = resp[k] * (t * t - 1.0f) / m.sd[k];
                             dy[k] = grad_scale * dmu * pb;
                             dy[K + k] = grad_scale * dsd * m.sd[k];
                         } else {
-                            const float rng = pb - pa;
                             const float alpha = (pa - m.mu[k]) / m.sd[k], beta = (pb - m.mu[k]) / m.sd[k];
                             const float Z = std_cdf(beta) - std_cdf(alpha);
-                            const float fa = std_pdf(alpha), fb = std_pdf(beta);
-                            dmu = resp[k] * (t / m.sd[k] - (fa - fb) / (m.sd[k] * Z));
-                            dsd = resp[k] * ((t * t - 1.0f) / m.sd[k] - (alpha * fa - beta * fb) / (m.sd[k] * Z));
-                            dy[k] = grad_scale * dmu * rng * sm[k] * (1.0f - sm[k]);
-                            dy[K + k] = grad_scale * dsd * (KIND == 2 ? m.sd[k] : rng * 10.0f * ss[k] * (1.0f - ss[k]));
+                            component_grad<KIND>(resp[k], grad_scale, HeadComp{m.mu[k], m.sd[k], sm[k], ss[k]}, t, alpha, beta,
+                                                 Z, pa, pb, dy[k], dy[K + k]);
                         }
                         dy[2 * K + k] = grad_scale * m.pi[k] * (dp[k] - dpipi);
                     }
@@ -723,7 +692,7 @@ __global__ __launch_bounds__(64) void head_categorical_kernel(const float* __res
         }
         const float piv = expf(y[vi] - zmax) / zs;
         const float pv = (piv + 1e-8f) / S;
-        const float lp = pv == pv ? logf(fminf(fmaxf(pv, kFp32Eps), 1.0f - kFp32Eps)) : pv;   // (clamp would drop a NaN)
+        const float lp = pv == pv ? log_clamped(pv) : pv;   // (clamp would drop a NaN)
         if (lp_out) lp_out[r] = lp;
         bad = !isfinite(lp);
         contrib = -lp;
@@ -956,38 +925,10 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const TailJobs jobs, int
         PP_STAMP(3);
         // one mixture component per lane
         const float v = value[r], pa = prior[2 * r], pb = prior[2 * r + 1];
-        const float zmax = wave_max(yz);
-        const float e = comp ? expf(yz - zmax) : 0.0f;
-        const float pi = e / wave_sum(e);
-        const float ps = wave_sum(pi);
-        const float p = pi / ps;
-        float mu, sd, sm = 0.f, ss = 0.f, rng = pb - pa;
-        if (KIND == 0) {
-            mu = pa + ymu * pb;
-            sd = expf(ysd) * pb;
-        } else {
-            sm = sigmoidf_(ymu);
-            ss = sigmoidf_(ysd);
-            mu = pa + sm * rng;
-            sd = KIND == 2 ? expf(ysd) : rng / 1000.0f + ss * rng * 10.0f;
-        }
-        const float tt = (v - mu) / sd;
-        float cl, alpha = 0.f, beta = 0.f, Z = 1.f;
-        if (KIND == 0) {
-            cl = -0.5f * tt * tt - logf(sd) - kHalfLog2Pi;
-        } else {
-            alpha = (pa - mu) / sd;
-            beta = (pb - mu) / sd;
-            Z = std_cdf(beta) - std_cdf(alpha);
-            const bool inside = v >= pa && v <= pb;
-            cl = (inside ? 0.0f : -INFINITY) + (-0.5f * tt * tt - kHalfLog2Pi) - logf(sd * Z);
-        }
-        const float a = comp ? logf(fminf(fmaxf(p, kFp32Eps), 1.0f - kFp32Eps)) + cl : -INFINITY;
-        const float amax = wave_max(a);
-        float lp = amax;
-        if (amax > -INFINITY) lp = amax + logf(wave_sum(comp ? expf(a - amax) : 0.0f));
-        // NaN in any component poisons the result like the reference's logsumexp would
-        if (wave_sum((comp && a != a) ? 1.0f : 0.0f) > 0.0f) lp = NAN;
+        const auto red_sum = [](float x) { return wave_sum(x); };
+        const auto red_max = [](float x) { return wave_max(x); };
+        LaneMixture hm;
+        const float lp = lane_mixture_logprob<KIND>(comp, ymu, ysd, yz, v, pa, pb, red_sum, red_max, hm);
         PP_STAMP(4);
         if (lp_out && lane == 0) lp_out[r] = lp;
         const bool rescued = (lp == -INFINITY);
@@ -995,29 +936,9 @@ __global__ __launch_bounds__(256) void head_tail_kernel(const TailJobs jobs, int
         bad_any |= bad;
         if (lane == 0) loss_local += rescued ? -kLogEps : -lp;
         if (!bwd) continue;
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
         const bool live = !(rescued || bad);
-        {
-            const float resp = (comp && live) ? expf(a - lp) : 0.0f;
-            const bool in = (p >= kFp32Eps) && (p <= 1.0f - kFp32Eps);
-            float dp = (comp && in) ? resp / p : 0.0f;
-            const float dpp = wave_sum(dp * p);
-            dp = comp ? (dp - dpp) / ps : 0.0f;
-            const float dpipi = wave_sum(dp * pi);
-            if (comp && live) {
-                if (KIND == 0) {
-                    d0 = grad_scale * resp * tt / sd * pb;
-                    d1 = grad_scale * resp * (tt * tt - 1.0f);
-                } else {
-                    const float fa = std_pdf(alpha), fb = std_pdf(beta);
-                    const float dmu = resp * (tt / sd - (fa - fb) / (sd * Z));
-                    const float dsd = resp * ((tt * tt - 1.0f) / sd - (alpha * fa - beta * fb) / (sd * Z));
-                    d0 = grad_scale * dmu * rng * sm * (1.0f - sm);
-                    d1 = grad_scale * dsd * (KIND == 2 ? sd : rng * 10.0f * ss * (1.0f - ss));
-                }
-                d2 = grad_scale * pi * (dp - dpipi);
-            }
-        }
+        float d0, d1, d2;
+        lane_mixture_grad<KIND>(hm, comp, live, lp, pa, pb, grad_scale, red_sum, d0, d1, d2);
         if (comp) {
             float* dy = DY + (int64_t)i * lddy;
             dy[lane] = d0; dy[K + lane] = d1; dy[2 * K + lane] = d2;

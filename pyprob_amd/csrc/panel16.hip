@@ -37,6 +37,7 @@
 #include "common.hpp"
 #include "panel16.hpp"
 #include "handoff.hpp"
+#include "head_math.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -88,17 +89,6 @@ struct P16 {
     static constexpr int B1 = 0, B2 = B1 + F1, B3 = B2 + F2, B4 = B3 + F3, B5 = B4 + F4, FU = F5 + F6, FT = B5 + UTW * FU;
     static constexpr int RING = HH == 512 ? 24 : 16;
 };
-
-constexpr float kFp32Eps = 1.1920928955078125e-07f;
-constexpr float kHalfLog2Pi = 0.91893853320467274178f;
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
-constexpr float kLogEps = -18.420680743952367f;
-
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-__device__ __forceinline__ float std_cdf_(float x) { return 0.5f * (1.0f + erff(x * kInvSqrt2)); }
-__device__ __forceinline__ float std_pdf_(float x) { return kInvSqrt2Pi * expf(-0.5f * x * x); }
 
 __device__ __forceinline__ void wave_sync_lds() {   // order this wave's LDS writes before its LDS reads
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -498,38 +488,10 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
             yz = m_b2z + yof(2 * K + c);
         }
         const float v = m_v, pa = m_pa, pb = m_pb;
-        const float zmax = row_max(yz);
-        const float ex = comp ? expf(yz - zmax) : 0.0f;
-        const float pi = ex / row_sum(ex);
-        const float ps = row_sum(pi);
-        const float p = pi / ps;
-        float mu, sd, sm = 0.f, ss = 0.f;
-        const float rng = pb - pa;
-        if (KIND == 0) {
-            mu = pa + ymu * pb;
-            sd = expf(ysd) * pb;
-        } else {
-            sm = sigmoidf_(ymu);
-            ss = sigmoidf_(ysd);
-            mu = pa + sm * rng;
-            sd = KIND == 2 ? expf(ysd) : rng / 1000.0f + ss * rng * 10.0f;
-        }
-        const float tt = (v - mu) / sd;
-        float cl, alpha = 0.f, beta = 0.f, Z = 1.f;
-        if (KIND == 0) {
-            cl = -0.5f * tt * tt - logf(sd) - kHalfLog2Pi;
-        } else {
-            alpha = (pa - mu) / sd;
-            beta = (pb - mu) / sd;
-            Z = std_cdf_(beta) - std_cdf_(alpha);
-            const bool inside = v >= pa && v <= pb;
-            cl = (inside ? 0.0f : -INFINITY) + (-0.5f * tt * tt - kHalfLog2Pi) - logf(sd * Z);
-        }
-        const float al = comp ? logf(fminf(fmaxf(p, kFp32Eps), 1.0f - kFp32Eps)) + cl : -INFINITY;
-        const float amax = row_max(al);
-        float lp = amax;
-        if (amax > -INFINITY) lp = amax + logf(row_sum(comp ? expf(al - amax) : 0.0f));
-        if (row_sum((comp && al != al) ? 1.0f : 0.0f) > 0.0f) lp = NAN;   // NaN in a component poisons the logsumexp
+        const auto red_sum = [](float x) { return row_sum(x); };
+        const auto red_max = [](float x) { return row_max(x); };
+        LaneMixture hm;
+        const float lp = lane_mixture_logprob<KIND>(comp, ymu, ysd, yz, v, pa, pb, red_sum, red_max, hm);
         const bool rescued = (lp == -INFINITY);
         const bool bad = !rescued && !isfinite(lp);
         if (mine && c == 0) {
@@ -537,29 +499,9 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
             atomicAdd(a.loss_acc + 32 * ((blockIdx.x * 4 + g) & 63), rescued ? -kLogEps : -lp);
             if (bad) atomicOr(a.flag, 1);
         }
-        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
         const bool live = rowok && !(rescued || bad);
-        {
-            const float resp = (comp && live) ? expf(al - lp) : 0.0f;
-            const bool in = (p >= kFp32Eps) && (p <= 1.0f - kFp32Eps);
-            float dp = (comp && in) ? resp / p : 0.0f;
-            const float dpp = row_sum(dp * p);
-            dp = comp ? (dp - dpp) / ps : 0.0f;
-            const float dpipi = row_sum(dp * pi);
-            if (comp && live) {
-                if (KIND == 0) {
-                    d0 = a.grad_scale * resp * tt / sd * pb;
-                    d1 = a.grad_scale * resp * (tt * tt - 1.0f);
-                } else {
-                    const float fa = std_pdf_(alpha), fb = std_pdf_(beta);
-                    const float dmu = resp * (tt / sd - (fa - fb) / (sd * Z));
-                    const float dsd = resp * ((tt * tt - 1.0f) / sd - (alpha * fa - beta * fb) / (sd * Z));
-                    d0 = a.grad_scale * dmu * rng * sm * (1.0f - sm);
-                    d1 = a.grad_scale * dsd * (KIND == 2 ? sd : rng * 10.0f * ss * (1.0f - ss));
-                }
-                d2 = a.grad_scale * pi * (dp - dpipi);
-            }
-        }
+        float d0, d1, d2;
+        lane_mixture_grad<KIND>(hm, comp, live, lp, pa, pb, a.grad_scale, red_sum, d0, d1, d2);
         if (comp) {
             sDY[r * PDY + c] = d0; sDY[r * PDY + K + c] = d1; sDY[r * PDY + 2 * K + c] = d2;
             if (mine) {
