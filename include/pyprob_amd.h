@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 14
+#define PP_ABI_VERSION 15
 #define PP_MAX_OBS 8
 #define PP_MAX_LSTM_DEPTH 4
 #define PP_MAX_OBS_DEPTH 4
@@ -514,6 +514,57 @@ int pp_axpy(float scale, const float* term, float* lw, int32_t n, void* stream);
  * one-workgroup combine); `scratch` dev >= PP_IS_STATS_SCRATCH doubles. */
 #define PP_IS_STATS_SCRATCH 6144
 int pp_is_stats(const float* lw, const float* x, int32_t n, double* out, double* scratch, void* stream);
+
+/* (ABI 15) Every distribution family of pyprob v1.5.0 on the device: log-densities and draws for the prior-proposal engine
+ * (state.sample's prior branch pyprob/state.py:191-201 and its uncontrolled draws :218-221), the likelihoods of state.observe
+ * (:118-155) and pyprob.factor (:113-115, distributions/factor.py). Kinds 0-5 are those of pp_logweight_accumulate; the
+ * log-densities are evaluated in fp32 like the torch.distributions classes behind pyprob/distributions/<family>.py:
+ *    0 Normal(p0 mean, p1 stddev)                 normal.py
+ *    1 Uniform(p0 low, p1 high), support [low, high)        uniform.py
+ *    2 Factor: the value x itself (log_prob given)          factor.py
+ *    3 Poisson(p0 rate)  4 Bernoulli(p0 probs)              poisson.py, bernoulli.py
+ *    5 Categorical: p0 = probs row(s), p_stride[0] = row stride (0 = one shared row), p_stride[1] = C   categorical.py
+ *    6 Exponential(p0 rate)                                 exponential.py
+ *    7 Gamma(p0 concentration, p1 rate)                     gamma.py
+ *    8 Beta(p0 concentration1, p1 concentration0, p2 low, p3 high): torch Beta.log_prob of (x - low) / (high - low),
+ *      WITHOUT the -log(high - low) Jacobian, as pyprob's beta.py:38-40 evaluates it
+ *    9 LogNormal(p0 loc, p1 scale)                          log_normal.py
+ *   10 Weibull(p0 scale, p1 concentration)                  weibull.py
+ *   11 Binomial(p0 total_count, p1 logits)                  binomial.py (torch evaluates it from the logits)
+ *   12 VonMises(p0 loc, p1 concentration)                   von_mises.py (torch's polynomial log I0)
+ *   13 TruncatedNormal(p0 mean, p1 stddev, p2 low, p3 high), closed support: truncated_normal.py:40-45
+ * A parameter is a pointer + a stride (0: one shared value, 1: one per particle). A value outside the family's support
+ * gives -inf (the particle is then discarded like any non-finite weight, pyprob/model.py:63-65). */
+#define PP_DIST_MAX_KIND 13
+#define PP_DIST_MAX_TERMS 8
+#define PP_DIST_MAX_ROUNDS 64
+typedef struct pp_dist {
+    int32_t kind;
+    int32_t p_stride[4];
+    const float* p[4];
+} pp_dist;
+typedef struct pp_dist_term {
+    pp_dist d;
+    const float* x; int32_t x_stride;   /* the value scored; x_stride 0 = one shared value (an observation) */
+    float scale;                          /* likelihood_importance for an observe (state.py:147-149), 1 for a prior */
+} pp_dist_term;
+
+/* The log-weight pass of a lock-step run (state.py:147-149, 211; trace.py:123-125):
+ *     lw[r] += sum_t scale_t * log p_t(x_t[r])    for r = rows[j], j < m (rows: dev int64 ascending), or rows NULL: r < n
+ * At most PP_DIST_MAX_TERMS terms of any kind in one launch. lw may be NULL; lp_out (dev [n], count == 1 only) receives
+ * log p(x[r]) unscaled at r. Rows that are not listed are not touched. */
+int pp_dist_logweight(const pp_dist_term* terms, int32_t count, float* lw /*dev [n]*/, float* lp_out, const int64_t* rows,
+                      int32_t m, int32_t n, void* stream);
+
+/* Draws of a family: out[r] ~ family(params_r) for r = rows[j], j < m, or rows NULL: r < n (out is full-width, dev [n];
+ * other rows are not touched). Philox4x32-10: key = seed, counter = offset + r, stream_id per statement - the counter
+ * scheme of pp_prior_draw, so a particle's draw does not depend on how particles were split into paths or shards; kinds
+ * 0 / 1 are bit-identical to pp_prior_draw. Rejection samplers (Gamma: Marsaglia-Tsang with the alpha < 1 boost in log
+ * space; Beta: G1 / (G1 + G2) in log space; Poisson: multiplication / PTRS; Binomial: inversion / BTRS; VonMises:
+ * Best-Fisher; TruncatedNormal: inverse CDF, redrawn when the fp32 value leaves [low, high]) take fresh Philox words per
+ * round and stop after PP_DIST_MAX_ROUNDS rounds: such a lane writes NaN. Kind 2 (Factor) has no draw. */
+int pp_dist_draw(const pp_dist* d, const int64_t* rows, int32_t m, int32_t n, uint64_t seed, uint64_t offset, uint32_t stream_id,
+                 float* out /*dev [n]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Individual kernels (used by the whole-path entry points; exported for unit parity tests and profiling)

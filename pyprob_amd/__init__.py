@@ -7,7 +7,7 @@ __version__ = '0.1.0'
 def __getattr__(name):
     """Lazy pyprob-style top level: pyprob_amd.sample / observe / Model / InferenceEngine / PriorInflation ... (importing the package
     must not require torch or a GPU)."""
-    if name in ('sample', 'observe', 'TraceMode', 'InferenceEngine', 'PriorInflation', 'InferenceNetwork', 'LearningRateScheduler',
+    if name in ('sample', 'observe', 'factor', 'TraceMode', 'InferenceEngine', 'PriorInflation', 'InferenceNetwork', 'LearningRateScheduler',
                 'Optimizer'):
         from . import state
         value = getattr(state, name)

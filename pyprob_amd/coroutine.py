@@ -25,6 +25,7 @@ import warnings
 import numpy as np
 import torch
 
+from .distributions import DIST_PARAMS
 from .packed import distribution_params
 
 
@@ -46,6 +47,7 @@ class _Params:
     """Per-particle parameter columns of one statement group, in the duck type ISRunner.dist_term reads."""
     FIELDS = {'Normal': ('mean', 'stddev'), 'Uniform': ('low', 'high'), 'Poisson': ('rate',), 'Bernoulli': ('probs',),
               'Categorical': ('probs',)}
+    FIELDS.update(DIST_PARAMS)          # the families of pp_dist_logweight (is_engine.DIST_PARAMS)
 
     @classmethod
     def from_columns(cls, name, columns):
@@ -76,6 +78,9 @@ class _Params:
         elif name == 'Categorical':
             self.num_categories = int(dists[0].num_categories)
             self.probs = np.stack([np.asarray(d.probs.detach().reshape(-1).tolist(), np.float32) for d in dists])
+        elif name in DIST_PARAMS:
+            for k in DIST_PARAMS[name]:
+                setattr(self, k, np.array([float(getattr(d, k)) for d in dists], np.float32))
         else:
             raise RuntimeError('Distribution currently unsupported: {}'.format(name))
 

@@ -12,6 +12,16 @@ import numpy as np
 import torch
 
 
+# pp_dist kinds of the families beyond the five the inference network proposes for (include/pyprob_amd.h, ABI 15), and the
+# attributes their parameters are read from, in p0..p3 order (pyprob/distributions/<family>.py)
+DIST_KINDS = {'Factor': 2, 'Exponential': 6, 'Gamma': 7, 'Beta': 8, 'LogNormal': 9, 'Weibull': 10, 'Binomial': 11, 'VonMises': 12,
+              'TruncatedNormal': 13}
+DIST_PARAMS = {'Exponential': ('rate',), 'Gamma': ('concentration', 'rate'),
+               'Beta': ('concentration1', 'concentration0', 'low', 'high'), 'LogNormal': ('loc', 'scale'),
+               'Weibull': ('scale', 'concentration'), 'Binomial': ('total_count', 'logits'), 'VonMises': ('loc', 'concentration'),
+               'TruncatedNormal': ('mean_non_truncated', 'stddev_non_truncated', 'low', 'high')}
+
+
 def _t(x):
     return x if torch.is_tensor(x) else torch.as_tensor(x, dtype=torch.float32)
 
@@ -176,6 +186,335 @@ class Bernoulli(Distribution):
     @property
     def probs(self):
         return self._torch_dist.probs
+
+
+class _Family(Distribution):
+    """A family whose parameters are kept as they were given (float32 tensors; per-particle ParticleTensors of a lock-step run
+    are not broadcast or validated: stale entries of particles off the current path may be anything). log_prob is torch's,
+    with -inf outside the support like the device kernels (pp_dist_logweight)."""
+    _params = ()
+
+    def __init__(self, name, address_suffix, *params):
+        with torch._C.DisableTorchFunctionSubclass():
+            self._p = tuple(v if (torch.is_tensor(v) and v.dtype == torch.float32) else _t(v).float() for v in params)
+        super().__init__(name, address_suffix)
+
+    def _device(self):
+        return self._p[0].device
+
+    def _in_support(self, value):
+        return torch.ones_like(value, dtype=torch.bool)
+
+    def log_prob(self, value, sum=False):
+        value = _t(value).float().to(self._device())
+        lp = self._torch_dist.log_prob(value)
+        lp = torch.where(self._in_support(value), lp, torch.full_like(lp, float('-inf')))
+        return torch.sum(lp) if sum else lp
+
+    def __repr__(self):
+        return '{}({})'.format(self.name, ', '.join('{}={}'.format(n, p.tolist()) for n, p in zip(self._params, self._p)))
+
+
+class Exponential(_Family):
+    """pyprob/distributions/exponential.py"""
+    _params = ('rate',)
+
+    def __init__(self, rate):
+        super().__init__('Exponential', 'Exponential', rate)
+
+    def _make_torch_dist(self):
+        return torch.distributions.Exponential(self._p[0], validate_args=False)
+
+    def _in_support(self, value):
+        return value >= 0
+
+    @property
+    def rate(self):
+        return self._p[0]
+
+
+class Gamma(_Family):
+    """pyprob/distributions/gamma.py"""
+    _params = ('concentration', 'rate')
+
+    def __init__(self, concentration, rate):
+        super().__init__('Gamma', 'Gamma', concentration, rate)
+
+    def _make_torch_dist(self):
+        return torch.distributions.Gamma(self._p[0], self._p[1], validate_args=False)
+
+    def _in_support(self, value):
+        return value >= 0
+
+    @property
+    def concentration(self):
+        return self._p[0]
+
+    @property
+    def rate(self):
+        return self._p[1]
+
+
+class Beta(_Family):
+    """pyprob/distributions/beta.py: Beta(concentration1, concentration0) stretched onto [low, high]. log_prob is that of
+    the unit-interval Beta at (x - low) / (high - low), without the -log(high - low) Jacobian, as pyprob computes it."""
+    _params = ('concentration1', 'concentration0', 'low', 'high')
+
+    def __init__(self, concentration1, concentration0, low=0, high=1):
+        super().__init__('Beta', 'Beta', concentration1, concentration0, low, high)
+
+    def _make_torch_dist(self):
+        return torch.distributions.Beta(self._p[0], self._p[1], validate_args=False)
+
+    def _unit(self, value):
+        return (value - self._p[2]) / (self._p[3] - self._p[2])
+
+    def _in_support(self, value):
+        y = self._unit(value)
+        return (y >= 0) & (y <= 1)
+
+    def log_prob(self, value, sum=False):
+        value = _t(value).float().to(self._device())
+        y = self._unit(value)
+        lp = self._torch_dist.log_prob(y)
+        lp = torch.where((y >= 0) & (y <= 1), lp, torch.full_like(lp, float('-inf')))
+        return torch.sum(lp) if sum else lp
+
+    def sample(self):
+        return self._p[2] + self._torch_dist.sample() * (self._p[3] - self._p[2])
+
+    @property
+    def concentration1(self):
+        return self._p[0]
+
+    @property
+    def concentration0(self):
+        return self._p[1]
+
+    @property
+    def low(self):
+        return self._p[2]
+
+    @property
+    def high(self):
+        return self._p[3]
+
+    @property
+    def mean(self):
+        return self._p[2] + self._torch_dist.mean * (self._p[3] - self._p[2])
+
+    @property
+    def variance(self):
+        r = self._p[3] - self._p[2]
+        return self._torch_dist.variance * r * r
+
+
+class LogNormal(_Family):
+    """pyprob/distributions/log_normal.py"""
+    _params = ('loc', 'scale')
+
+    def __init__(self, loc, scale):
+        super().__init__('LogNormal', 'LogNormal', loc, scale)
+
+    def _make_torch_dist(self):
+        return torch.distributions.LogNormal(self._p[0], self._p[1], validate_args=False)
+
+    def _in_support(self, value):
+        return value > 0
+
+    @property
+    def loc(self):
+        return self._p[0]
+
+    @property
+    def scale(self):
+        return self._p[1]
+
+
+class Weibull(_Family):
+    """pyprob/distributions/weibull.py"""
+    _params = ('scale', 'concentration')
+
+    def __init__(self, scale, concentration):
+        super().__init__('Weibull', 'Weibull', scale, concentration)
+
+    def _make_torch_dist(self):
+        return torch.distributions.Weibull(self._p[0], self._p[1], validate_args=False)
+
+    def _in_support(self, value):
+        return value > 0
+
+    @property
+    def scale(self):
+        return self._p[0]
+
+    @property
+    def concentration(self):
+        return self._p[1]
+
+
+class Binomial(_Family):
+    """pyprob/distributions/binomial.py: total_count with probs or logits; the log-density is torch's, from the logits."""
+    _params = ('total_count', 'logits')
+
+    def __init__(self, total_count=1, probs=None, logits=None):
+        if (probs is None) == (logits is None):
+            raise ValueError('Either `probs` or `logits` must be specified, but not both.')
+        if logits is None:
+            with torch._C.DisableTorchFunctionSubclass():
+                p = _t(probs).float()
+                eps = torch.finfo(torch.float32).eps
+                pc = p.clamp(eps, 1 - eps)
+                logits = torch.log(pc) - torch.log1p(-pc)         # torch's probs_to_logits (is_binary)
+        self._probs = None if probs is None else _t(probs).float()
+        super().__init__('Binomial', 'Binomial', total_count, logits)
+
+    def _make_torch_dist(self):
+        return torch.distributions.Binomial(total_count=self._p[0], logits=self._p[1], validate_args=False)
+
+    def _in_support(self, value):
+        return (value >= 0) & (value <= self._p[0]) & (value == torch.floor(value))
+
+    @property
+    def total_count(self):
+        return self._p[0]
+
+    @property
+    def logits(self):
+        return self._p[1]
+
+    @property
+    def probs(self):
+        return self._probs if self._probs is not None else torch.sigmoid(self._p[1])
+
+
+class VonMises(_Family):
+    """pyprob/distributions/von_mises.py"""
+    _params = ('loc', 'concentration')
+
+    def __init__(self, loc, concentration):
+        super().__init__('VonMises', 'VonMises', loc, concentration)
+
+    def _make_torch_dist(self):
+        return torch.distributions.VonMises(self._p[0], self._p[1], validate_args=False)
+
+    def _in_support(self, value):
+        return torch.isfinite(value)
+
+    @property
+    def loc(self):
+        return self._p[0]
+
+    @property
+    def concentration(self):
+        return self._p[1]
+
+
+def _std_cdf(x):
+    return 0.5 * (1 + torch.erf(x / math.sqrt(2)))
+
+
+class TruncatedNormal(_Family):
+    """pyprob/distributions/truncated_normal.py: a Normal restricted to [low, high]; log_prob scores the closed interval
+    (:40-45), sample draws by the inverse CDF between Phi(alpha) and Phi(beta) (:94-112). clamp_mean_between_low_high
+    moves the mean into [low, high] at construction, as pyprob does."""
+    _params = ('mean_non_truncated', 'stddev_non_truncated', 'low', 'high')
+
+    def __init__(self, mean_non_truncated, stddev_non_truncated, low, high, clamp_mean_between_low_high=False):
+        super().__init__('TruncatedNormal', 'TruncatedNormal', mean_non_truncated, stddev_non_truncated, low, high)
+        if clamp_mean_between_low_high:
+            with torch._C.DisableTorchFunctionSubclass():
+                m = torch.max(torch.min(self._p[0], self._p[3]), self._p[2])
+            self._p = (m,) + self._p[1:]
+
+    def _ab(self):
+        mu, sd, low, high = self._p
+        return (low - mu) / sd, (high - mu) / sd
+
+    def _Z(self):
+        a, b = self._ab()
+        return _std_cdf(b) - _std_cdf(a)
+
+    def log_prob(self, value, sum=False):
+        mu, sd, low, high = self._p
+        value = _t(value).float().to(self._device())
+        z = (value - mu) / sd
+        lp = -(z * z) / 2 - 0.5 * math.log(2 * math.pi) - torch.log(sd * self._Z())
+        lp = torch.where((value >= low) & (value <= high), lp, torch.full_like(lp, float('-inf')))
+        return torch.sum(lp) if sum else lp
+
+    def sample(self):
+        """The inverse CDF between Phi(alpha) and Phi(beta) in float64 on the parameters' device (torch.special.ndtr / ndtri keep
+        the tails that 2 p - 1 in fp32 loses); an element that rounds outside [low, high] is redrawn, the others are kept."""
+        mu, sd, low, high = (t.double() for t in self._p)
+        shape = torch.broadcast_shapes(mu.shape, sd.shape, low.shape, high.shape)
+        mu, sd, low, high = (t.expand(shape) for t in (mu, sd, low, high))
+        ca, cb = torch.special.ndtr((low - mu) / sd), torch.special.ndtr((high - mu) / sd)
+        out = torch.full(shape, float('nan'), dtype=torch.float64, device=mu.device)
+        todo = torch.ones(shape, dtype=torch.bool, device=mu.device)
+        for _ in range(64):
+            u = torch.rand(shape, dtype=torch.float64, device=mu.device)
+            v = (torch.special.ndtri(ca + u * (cb - ca)) * sd + mu).float().double()
+            ok = todo & (v >= low) & (v <= high)
+            out = torch.where(ok, v, out)
+            todo = todo & ~ok
+            if not bool(todo.any()):
+                return out.float()
+        raise RuntimeError('TruncatedNormal.sample: no draw inside [low, high]')
+
+    @property
+    def mean_non_truncated(self):
+        return self._p[0]
+
+    @property
+    def stddev_non_truncated(self):
+        return self._p[1]
+
+    @property
+    def low(self):
+        return self._p[2]
+
+    @property
+    def high(self):
+        return self._p[3]
+
+    def _pdf_ab(self):
+        a, b = self._ab()
+        c = 1 / math.sqrt(2 * math.pi)
+        return a, b, c * torch.exp(-0.5 * a * a), c * torch.exp(-0.5 * b * b)
+
+    @property
+    def mean(self):
+        a, b, pa, pb = self._pdf_ab()
+        return self._p[0] + self._p[1] * (pa - pb) / self._Z()
+
+    @property
+    def variance(self):
+        a, b, pa, pb = self._pdf_ab()
+        Z = self._Z()
+        return self._p[1] ** 2 * (1 + (a * pa - b * pb) / Z - ((pa - pb) / Z) ** 2)
+
+
+class Factor(Distribution):
+    """pyprob/distributions/factor.py: the pseudo-distribution behind pyprob.factor - its log_prob is the given log-density
+    (or log_prob_func(value)); it has no sample."""
+
+    def __init__(self, log_prob=None, log_prob_func=None):
+        if (log_prob is None) == (log_prob_func is None):
+            raise RuntimeError('Expecting one of log_prob, log_prob_func' if log_prob is None else
+                               'Expecting only one of log_prob, log_prob_func')
+        self._log_prob = None if log_prob is None else (log_prob if torch.is_tensor(log_prob) else _t(log_prob).float())
+        self._log_prob_func = log_prob_func
+        super().__init__('Factor', 'Factor')
+
+    def log_prob(self, value=None, sum=False):
+        return self._log_prob if self._log_prob is not None else self._log_prob_func(value)
+
+    def sample(self):
+        return None
+
+    def __repr__(self):
+        return 'Factor()'
 
 
 class Empirical:

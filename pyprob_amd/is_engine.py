@@ -15,10 +15,284 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .distributions import DIST_KINDS, DIST_PARAMS
 from .ops import ops
 
 
-class ISRunner:
+class DistRunner:
+    """The network-free half of a lock-step importance-sampling run: per-particle log-weight terms of every distribution family,
+    draws from the prior, control-flow partitions, result copies and the importance statistics - everything the prior-proposal
+    engine needs (posterior_results(IMPORTANCE_SAMPLING, lock_step=True): state.sample's prior branch, pyprob/state.py:191-201).
+    ISRunner adds the inference network on top."""
+
+    def __init__(self, device, lib=None):
+        self.lib = lib if lib is not None else L.load()
+        self.dev = torch.device(device)
+        self.n = 0
+        self.offset = 0
+        self._consts = {}
+        self._stats = torch.zeros(8, dtype=torch.float64, device=self.dev)
+        self._st = None
+        self._stats_scratch = torch.zeros(L.PP_IS_STATS_SCRATCH, dtype=torch.float64, device=self.dev)
+        self.prev_value = None
+        self.last_value = None
+
+    def _const(self, v):
+        """1-element device tensor holding v (cached: no allocation / H2D copy in the steady state)."""
+        t = self._consts.get(v)
+        if t is None:
+            if len(self._consts) > 4096:      # (observed values of many posterior calls: keep the cache bounded)
+                self._consts.clear()
+            t = torch.tensor([v], dtype=torch.float32, device=self.dev)
+            self._consts[v] = t
+        return t
+
+    def begin(self, n, offset=0):
+        """Start n particles (network-free: no LSTM state)."""
+        self.n = n
+        self.offset = int(offset)
+        self.prev_value = None
+        self.last_value = None
+        if self.dev.type == 'cuda':
+            if torch.cuda.current_device() != (self.dev.index or 0):
+                torch.cuda.set_device(self.dev)
+            self._st = L.stream_ptr()
+        else:
+            self._st = None
+
+    # ---- log-weight terms ---------------------------------------------------------------------------------
+    def dist_term(self, distribution, n=None):
+        """(kind, p0, p0_stride, p1, p1_stride) of pp_logweight_accumulate for a prior / likelihood distribution object
+        (duck-typed: .name and the parameter attributes of pyprob/distributions/*.py); None if the family has no device
+        kernel. Parameters may be shared (one element) or per particle (n elements)."""
+        with torch._C.DisableTorchFunctionSubclass():     # (metadata only: no Python dispatch per attribute of a ParticleTensor)
+            return self._dist_term(distribution)
+
+    def _dist_term(self, distribution):
+        dev = self.dev
+
+        def t(v):
+            if isinstance(v, (int, float)) or (torch.is_tensor(v) and v.device.type == 'cpu' and v.numel() == 1):
+                return self._const(float(v))          # cached device scalar: no host-to-device copy per statement
+            if torch.is_tensor(v) and v.dtype == torch.float32 and v.device == dev and v.dim() == 1 and v.is_contiguous():
+                return v.as_subclass(torch.Tensor)    # (per-particle parameters of a lock-step run: one call, not five)
+            return torch.as_tensor(v, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(dev).contiguous()
+
+        def s(v):
+            return 0 if v.numel() == 1 else 1
+        name = distribution.name
+        if name == 'Normal':
+            p0, p1 = t(distribution.mean), t(distribution.stddev)
+            return 0, p0, s(p0), p1, s(p1)
+        if name == 'Uniform':
+            p0, p1 = t(distribution.low), t(distribution.high)
+            return 1, p0, s(p0), p1, s(p1)
+        if name == 'Poisson':
+            p0 = t(distribution.rate)
+            return 3, p0, s(p0), None, 0
+        if name == 'Bernoulli':
+            p0 = t(distribution.probs)
+            return 4, p0, s(p0), None, 0
+        if name == 'Categorical':
+            C_ = int(distribution.num_categories)
+            p0 = t(distribution.probs)
+            return 5, p0, (0 if p0.numel() == C_ else C_), None, C_
+        kind = DIST_KINDS.get(name)
+        if kind is None:
+            return None
+        if kind == 2:           # Factor: the term is the value itself (the caller passes the log-density as x)
+            return (2, None, 0, None, 0, None, 0, None, 0)
+        ps = [t(getattr(distribution, a)) for a in DIST_PARAMS[name]]
+        ps += [None] * (4 - len(ps))
+        out = [kind]
+        for q in ps:
+            out += [q, 0 if q is None else s(q)]
+        return tuple(out)       # (kind, p0, s0, p1, s1, p2, s2, p3, s3): a pp_dist term (pp_dist_logweight / pp_dist_draw)
+
+    def dist_spec(self, distribution):
+        """(kind, [p0..p3], [s0..s3]) of pp_dist for any family (kinds 0-5 included: the prior draws of the prior-proposal
+        engine); None if the family has no device kernel."""
+        term = self.dist_term(distribution)
+        if term is None:
+            return None
+        if len(term) == 5:
+            kind, p0, s0, p1, s1 = term
+            if kind == 5:
+                return kind, [p0, None, None, None], [s0, s1, 0, 0]
+            return kind, [p0, p1, None, None], [s0, s1, 0, 0]
+        return term[0], list(term[1::2]), list(term[2::2])
+
+    def draw(self, distribution, values, rows, seed, stream_id):
+        """values[r] ~ distribution for the particles r of `rows` (None: all of them), in place (pp_dist_draw: Philox key
+        `seed`, counter offset + r, `stream_id` per statement)."""
+        spec = self.dist_spec(distribution)
+        if spec is None or spec[0] == 2:
+            raise RuntimeError('lock-step execution has no device sampler for {}'.format(distribution.name))
+        kind, ps, ss = spec
+        for q in ps:
+            if q is not None and kind != 5 and q.numel() not in (1, values.numel()):
+                raise RuntimeError('lock-step draw of {}: parameters of 1 or n elements'.format(distribution.name))
+        ops.dist_draw(int(kind), ps, [int(v) for v in ss], rows, values, int(seed), self.offset, int(stream_id))
+        torch.autograd.graph.increment_version(values)      # (written by the kernel: memoised results of it are stale)
+        return values
+
+    def dist_accumulate(self, lw, term, x, rows, scale):
+        """lw[r] += scale * log p(x[r]) for a pp_dist term (dist_term's 9-tuple) on the particles of `rows` (None: all)."""
+        x = x.as_subclass(torch.Tensor) if type(x) is not torch.Tensor else x
+        if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
+            x = x.to(self.dev, torch.float32).contiguous()
+        x = x.reshape(-1)
+        ps, ss = list(term[1::2]), [int(v) for v in term[2::2]]
+        ops.dist_logweight(lw, [int(term[0])], ps, ss, [x], [float(scale)], rows, None, lw.numel())
+
+    def log_prob(self, term, x, n=None):
+        """log_prob(dist; x) per particle as a device tensor [n] (no accumulation)."""
+        if len(term) == 9:      # a pp_dist term (pp_dist_logweight's lp_out)
+            n = int(x.numel()) if n is None else n
+            lp = torch.empty(n, dtype=torch.float32, device=self.dev)
+            x = x.as_subclass(torch.Tensor).to(self.dev, torch.float32).reshape(-1).contiguous()
+            ops.dist_logweight(None, [int(term[0])], list(term[1::2]), [int(v) for v in term[2::2]], [x], [1.0], None, lp, n)
+            return lp
+        kind, p0, s0, p1, s1 = term
+        n = int(x.numel()) if n is None else n
+        return ops.log_prob(int(kind), p0, int(s0), p1, int(s1), x, n)
+
+    def _term_accumulate(self, term, x, scale, lw):
+        kind, p0, s0, p1, s1 = term
+        ops.logweight_terms(lw, [int(kind)], [p0], [int(s0)], [p1], [int(s1)], [x], [float(scale)], False)
+
+    def accumulate_masked(self, lw, kind, p0, p1, x, active, scale=1.0, term=None):
+        """accumulate() for the active particles of a diverged path: the term is evaluated for every particle (stale
+        entries of inactive particles may be anything) and added where `active` (None = everywhere)."""
+        if term is None:
+            term = (kind, p0, 0 if p0.numel() == 1 else 1, p1, 0 if p1.numel() == 1 else 1)
+        if active is None:
+            return self._term_accumulate(term, x, scale, lw)
+        lp = self.log_prob(term, x, lw.numel())
+        lw.add_(torch.where(active, lp, torch.zeros_like(lp)), alpha=float(scale))
+
+    # ---- the particles of a control-flow path as a row list (LockStepState.by_rows): direct C-ABI calls ------------------------
+    def partition_launch(self, cond, rows, m):
+        """A branch: split the path's rows (None: particles 0..m-1) by the bool [n] condition - the launches only; the counts
+        are read by partition_read (the one synchronisation of a branch)."""
+        buf = torch.empty(2 * max(m, 1), dtype=torch.int64, device=self.dev)
+        need = (m + 1023) // 1024 + 1
+        scratch = getattr(self, '_part_scratch', None)
+        if scratch is None or scratch.numel() < need:
+            scratch = self._part_scratch = torch.empty(max(need, 1024), dtype=torch.int32, device=self.dev)
+        if m > 0 and self.dev.type == 'cuda' and os.environ.get('PP_IS_PART_POLL', '1') != '0':
+            # the decision comes back through PINNED host memory the kernel writes in place (counts, then a sequence word behind a
+            # system-scope fence) and the host polls: no 8-byte device-to-host copy, whose blocking call cost every branch ~45 us
+            ring = getattr(self, '_part_ring', None)
+            if ring is None:
+                self._part_pin = torch.zeros(64 * 4, dtype=torch.int32).pin_memory()
+                ring = self._part_ring = self._part_pin.numpy().reshape(64, 4)
+                self._part_seq = 0
+            self._part_seq = self._part_seq % 0x3fffffff + 1
+            slot = self._part_seq & 63          # (nested paths keep a few partitions in flight: one slot each)
+            ring[slot, 2] = 0
+            L.check(self.lib.pp_partition_rows_polled(cond.data_ptr(), L.ptr(rows), int(m), buf.data_ptr(), buf.data_ptr() + 8 * m,
+                                                      self._part_pin.data_ptr() + 16 * slot, self._part_seq, scratch.data_ptr(),
+                                                      self._st), 'pp_partition_rows_polled')
+            return buf, (ring[slot], self._part_seq), m, cond, rows
+        counts = torch.empty(2, dtype=torch.int32, device=self.dev)
+        L.check(self.lib.pp_partition_rows(cond.data_ptr(), L.ptr(rows), int(m), buf.data_ptr(), buf.data_ptr() + 8 * m,
+                                           counts.data_ptr(), scratch.data_ptr(), self._st), 'pp_partition_rows')
+        return buf, counts, m, cond, rows      # (cond / rows stay alive until the kernels have run)
+
+    def partition_read(self, handle):
+        """(rows where the condition holds, the other rows, their counts) - ascending int64 device vectors."""
+        buf, counts, m = handle[:3]
+        if isinstance(counts, tuple):
+            slot, seq = counts
+            spins, deadline = 0, None
+            while slot[2] != seq:
+                spins += 1
+                if spins > 4000:                 # a long statement kernel is still running: yield between polls, bounded by time
+                    now = time.perf_counter()
+                    if deadline is None:
+                        deadline = now + 30.0
+                    elif now > deadline:
+                        torch.cuda.synchronize(self.dev)
+                        if slot[2] != seq:
+                            raise L.HipLibraryError('pp_partition_rows_polled: the counts never arrived in host memory')
+                    time.sleep(0)
+            n_true, n_false = int(slot[0]), int(slot[1])
+        else:
+            n_true, n_false = counts.tolist()
+        return buf[:n_true], buf[m:m + n_false], n_true, n_false
+
+    def partition(self, cond, rows, m):
+        return self.partition_read(self.partition_launch(cond, rows, m))
+
+    def accumulate_rows(self, lw, term, x, rows, scale):
+        """lw[rows] += scale * log_prob(term; x[rows]) - one launch on the path's rows (pp_logweight_accumulate_rows)."""
+        kind, p0, s0, p1, s1 = term
+        x = x.as_subclass(torch.Tensor) if type(x) is not torch.Tensor else x
+        if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
+            x = x.to(self.dev, torch.float32).contiguous()
+        for t in (p0, p1, x):
+            if t is not None and t.numel() not in (1, lw.numel()):
+                raise RuntimeError('lock-step log-weight term: tensors of 1 or n elements')
+        L.check(self.lib.pp_logweight_accumulate_rows(int(kind), L.ptr(p0), int(s0), L.ptr(p1), int(s1), x.data_ptr(),
+                                                      0 if x.numel() == 1 else 1, float(scale), lw.data_ptr(), rows.data_ptr(),
+                                                      int(rows.numel()), self._st), 'pp_logweight_accumulate_rows')
+
+    def copy_rows(self, src, dst, rows):
+        """dst[rows] = src[rows] (src: n values or one shared value), in place (pp_copy_rows)."""
+        src = src.as_subclass(torch.Tensor) if type(src) is not torch.Tensor else src
+        if src.dtype != torch.float32 or src.device != self.dev or not src.is_contiguous():
+            src = src.to(self.dev, torch.float32).contiguous()
+        if src.numel() not in (1, dst.numel()):
+            raise RuntimeError('copy_rows: a source of 1 or n elements')
+        L.check(self.lib.pp_copy_rows(src.data_ptr(), 0 if src.numel() == 1 else 1, dst.data_ptr(), rows.data_ptr(), int(rows.numel()),
+                                      self._st), 'pp_copy_rows')
+        torch.autograd.graph.increment_version(dst)       # written by the kernel: memoised results of it are stale
+
+    def accumulate(self, lw, kind, p0, p1, x, scale=1.0, term=None):
+        """lw += scale * log_prob(dist(p0, p1); x); p0/p1/x are device tensors of 1 (broadcast) or n elements."""
+        if term is None:
+            term = (kind, p0, 0 if p0.numel() == 1 else 1, p1, 0 if p1.numel() == 1 else 1)
+        self._term_accumulate(term, x, scale, lw)
+
+    def accumulate_terms(self, lw, terms, overwrite=False):
+        """One pass for up to four terms; terms = [(kind, p0, p1, x, scale)] (kind 2 = the tensor x itself) or
+        [(dist_term(...), x, scale)]."""
+        def s(t):
+            return 0 if (t is None or t.numel() == 1) else 1
+        kinds, p0s, s0s, p1s, s1s, xs, scales = [], [], [], [], [], [], []
+        for item in terms:
+            if len(item) == 3:          # (dist_term tuple, x, scale)
+                (kind, p0, s0, p1, s1), x, scale = item
+            else:
+                kind, p0, p1, x, scale = item
+                s0, s1 = s(p0), s(p1)
+            kinds.append(int(kind)); p0s.append(p0); s0s.append(int(s0)); p1s.append(p1); s1s.append(int(s1))
+            xs.append(x); scales.append(float(scale))
+        ops.logweight_terms(lw, kinds, p0s, s0s, p1s, s1s, xs, scales, bool(overwrite))
+
+    def axpy(self, lw, scale, term):
+        """lw += scale * term (e.g. -log q)."""
+        ops.logweight_terms(lw, [2], [None], [0], [None], [0], [term], [float(scale)], False)
+
+    def stats(self, lw, x=None):
+        """Importance statistics (Empirical.finalize / expectation / effective_sample_size,
+        pyprob/distributions/empirical.py:298-309, 451-466, 758-766) reduced on the device in float64."""
+        self._stats = ops.is_stats(lw, x, self._stats_scratch)
+        return self._stats_dict(self._stats)
+
+    @staticmethod
+    def _stats_dict(stats):
+        m, sw, sw2, swx, swx2, cnt = (float(v) for v in stats[:6]) if isinstance(stats, np.ndarray) else stats.tolist()[:6]
+        mean = swx / sw if sw > 0 else float('nan')
+        var = swx2 / sw - mean * mean if sw > 0 else float('nan')
+        return dict(max_lw=m, sum_w=sw, sum_w2=sw2, sum_wx=swx, sum_wx2=swx2, count=cnt,
+                    ess=(sw * sw / sw2) if sw2 > 0 else 0.0, mean=mean, var=var,
+                    log_evidence=m + np.log(sw / max(cnt, 1)) if sw > 0 else float('-inf'))
+
+
+
+class ISRunner(DistRunner):
     def __init__(self, engine):
         self.eng = engine
         self.lib = engine.lib
@@ -48,16 +322,6 @@ class ISRunner:
         if getattr(self, '_stats_np', None) is None:
             self._stats_pin = torch.zeros(8, dtype=torch.float64).pin_memory()
             self._stats_np = self._stats_pin.numpy()
-
-    def _const(self, v):
-        """1-element device tensor holding v (cached: no allocation / H2D copy in the steady state)."""
-        t = self._consts.get(v)
-        if t is None:
-            if len(self._consts) > 4096:      # (observed values of many posterior calls: keep the cache bounded)
-                self._consts.clear()
-            t = torch.tensor([v], dtype=torch.float32, device=self.dev)
-            self._consts[v] = t
-        return t
 
     def _ensure_ws(self, n):
         need = self.lib.pp_is_workspace_bytes(C.byref(self.eng.net), n)
@@ -370,185 +634,6 @@ class ISRunner:
         self.h.index_copy_(1, rows, h)
         self.c.index_copy_(1, rows, c)
         return value, logq
-
-    # ---- log-weight terms ---------------------------------------------------------------------------------
-    def dist_term(self, distribution, n=None):
-        """(kind, p0, p0_stride, p1, p1_stride) of pp_logweight_accumulate for a prior / likelihood distribution object
-        (duck-typed: .name and the parameter attributes of pyprob/distributions/*.py); None if the family has no device
-        kernel. Parameters may be shared (one element) or per particle (n elements)."""
-        with torch._C.DisableTorchFunctionSubclass():     # (metadata only: no Python dispatch per attribute of a ParticleTensor)
-            return self._dist_term(distribution)
-
-    def _dist_term(self, distribution):
-        dev = self.dev
-
-        def t(v):
-            if isinstance(v, (int, float)) or (torch.is_tensor(v) and v.device.type == 'cpu' and v.numel() == 1):
-                return self._const(float(v))          # cached device scalar: no host-to-device copy per statement
-            if torch.is_tensor(v) and v.dtype == torch.float32 and v.device == dev and v.dim() == 1 and v.is_contiguous():
-                return v.as_subclass(torch.Tensor)    # (per-particle parameters of a lock-step run: one call, not five)
-            return torch.as_tensor(v, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(dev).contiguous()
-
-        def s(v):
-            return 0 if v.numel() == 1 else 1
-        name = distribution.name
-        if name == 'Normal':
-            p0, p1 = t(distribution.mean), t(distribution.stddev)
-            return 0, p0, s(p0), p1, s(p1)
-        if name == 'Uniform':
-            p0, p1 = t(distribution.low), t(distribution.high)
-            return 1, p0, s(p0), p1, s(p1)
-        if name == 'Poisson':
-            p0 = t(distribution.rate)
-            return 3, p0, s(p0), None, 0
-        if name == 'Bernoulli':
-            p0 = t(distribution.probs)
-            return 4, p0, s(p0), None, 0
-        if name == 'Categorical':
-            C_ = int(distribution.num_categories)
-            p0 = t(distribution.probs)
-            return 5, p0, (0 if p0.numel() == C_ else C_), None, C_
-        return None
-
-    def log_prob(self, term, x, n=None):
-        """log_prob(dist; x) per particle as a device tensor [n] (no accumulation)."""
-        kind, p0, s0, p1, s1 = term
-        n = int(x.numel()) if n is None else n
-        return ops.log_prob(int(kind), p0, int(s0), p1, int(s1), x, n)
-
-    def _term_accumulate(self, term, x, scale, lw):
-        kind, p0, s0, p1, s1 = term
-        ops.logweight_terms(lw, [int(kind)], [p0], [int(s0)], [p1], [int(s1)], [x], [float(scale)], False)
-
-    def accumulate_masked(self, lw, kind, p0, p1, x, active, scale=1.0, term=None):
-        """accumulate() for the active particles of a diverged path: the term is evaluated for every particle (stale
-        entries of inactive particles may be anything) and added where `active` (None = everywhere)."""
-        if term is None:
-            term = (kind, p0, 0 if p0.numel() == 1 else 1, p1, 0 if p1.numel() == 1 else 1)
-        if active is None:
-            return self._term_accumulate(term, x, scale, lw)
-        lp = self.log_prob(term, x, lw.numel())
-        lw.add_(torch.where(active, lp, torch.zeros_like(lp)), alpha=float(scale))
-
-    # ---- the particles of a control-flow path as a row list (LockStepState.by_rows): direct C-ABI calls ------------------------
-    def partition_launch(self, cond, rows, m):
-        """A branch: split the path's rows (None: particles 0..m-1) by the bool [n] condition - the launches only; the counts
-        are read by partition_read (the one synchronisation of a branch)."""
-        buf = torch.empty(2 * max(m, 1), dtype=torch.int64, device=self.dev)
-        need = (m + 1023) // 1024 + 1
-        scratch = getattr(self, '_part_scratch', None)
-        if scratch is None or scratch.numel() < need:
-            scratch = self._part_scratch = torch.empty(max(need, 1024), dtype=torch.int32, device=self.dev)
-        if m > 0 and self.dev.type == 'cuda' and os.environ.get('PP_IS_PART_POLL', '1') != '0':
-            # the decision comes back through PINNED host memory the kernel writes in place (counts, then a sequence word behind a
-            # system-scope fence) and the host polls: no 8-byte device-to-host copy, whose blocking call cost every branch ~45 us
-            ring = getattr(self, '_part_ring', None)
-            if ring is None:
-                self._part_pin = torch.zeros(64 * 4, dtype=torch.int32).pin_memory()
-                ring = self._part_ring = self._part_pin.numpy().reshape(64, 4)
-                self._part_seq = 0
-            self._part_seq = self._part_seq % 0x3fffffff + 1
-            slot = self._part_seq & 63          # (nested paths keep a few partitions in flight: one slot each)
-            ring[slot, 2] = 0
-            L.check(self.lib.pp_partition_rows_polled(cond.data_ptr(), L.ptr(rows), int(m), buf.data_ptr(), buf.data_ptr() + 8 * m,
-                                                      self._part_pin.data_ptr() + 16 * slot, self._part_seq, scratch.data_ptr(),
-                                                      self._st), 'pp_partition_rows_polled')
-            return buf, (ring[slot], self._part_seq), m, cond, rows
-        counts = torch.empty(2, dtype=torch.int32, device=self.dev)
-        L.check(self.lib.pp_partition_rows(cond.data_ptr(), L.ptr(rows), int(m), buf.data_ptr(), buf.data_ptr() + 8 * m,
-                                           counts.data_ptr(), scratch.data_ptr(), self._st), 'pp_partition_rows')
-        return buf, counts, m, cond, rows      # (cond / rows stay alive until the kernels have run)
-
-    def partition_read(self, handle):
-        """(rows where the condition holds, the other rows, their counts) - ascending int64 device vectors."""
-        buf, counts, m = handle[:3]
-        if isinstance(counts, tuple):
-            slot, seq = counts
-            spins, deadline = 0, None
-            while slot[2] != seq:
-                spins += 1
-                if spins > 4000:                 # a long statement kernel is still running: yield between polls, bounded by time
-                    now = time.perf_counter()
-                    if deadline is None:
-                        deadline = now + 30.0
-                    elif now > deadline:
-                        torch.cuda.synchronize(self.dev)
-                        if slot[2] != seq:
-                            raise L.HipLibraryError('pp_partition_rows_polled: the counts never arrived in host memory')
-                    time.sleep(0)
-            n_true, n_false = int(slot[0]), int(slot[1])
-        else:
-            n_true, n_false = counts.tolist()
-        return buf[:n_true], buf[m:m + n_false], n_true, n_false
-
-    def partition(self, cond, rows, m):
-        return self.partition_read(self.partition_launch(cond, rows, m))
-
-    def accumulate_rows(self, lw, term, x, rows, scale):
-        """lw[rows] += scale * log_prob(term; x[rows]) - one launch on the path's rows (pp_logweight_accumulate_rows)."""
-        kind, p0, s0, p1, s1 = term
-        x = x.as_subclass(torch.Tensor) if type(x) is not torch.Tensor else x
-        if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
-            x = x.to(self.dev, torch.float32).contiguous()
-        for t in (p0, p1, x):
-            if t is not None and t.numel() not in (1, lw.numel()):
-                raise RuntimeError('lock-step log-weight term: tensors of 1 or n elements')
-        L.check(self.lib.pp_logweight_accumulate_rows(int(kind), L.ptr(p0), int(s0), L.ptr(p1), int(s1), x.data_ptr(),
-                                                      0 if x.numel() == 1 else 1, float(scale), lw.data_ptr(), rows.data_ptr(),
-                                                      int(rows.numel()), self._st), 'pp_logweight_accumulate_rows')
-
-    def copy_rows(self, src, dst, rows):
-        """dst[rows] = src[rows] (src: n values or one shared value), in place (pp_copy_rows)."""
-        src = src.as_subclass(torch.Tensor) if type(src) is not torch.Tensor else src
-        if src.dtype != torch.float32 or src.device != self.dev or not src.is_contiguous():
-            src = src.to(self.dev, torch.float32).contiguous()
-        if src.numel() not in (1, dst.numel()):
-            raise RuntimeError('copy_rows: a source of 1 or n elements')
-        L.check(self.lib.pp_copy_rows(src.data_ptr(), 0 if src.numel() == 1 else 1, dst.data_ptr(), rows.data_ptr(), int(rows.numel()),
-                                      self._st), 'pp_copy_rows')
-        torch.autograd.graph.increment_version(dst)       # written by the kernel: memoised results of it are stale
-
-    def accumulate(self, lw, kind, p0, p1, x, scale=1.0, term=None):
-        """lw += scale * log_prob(dist(p0, p1); x); p0/p1/x are device tensors of 1 (broadcast) or n elements."""
-        if term is None:
-            term = (kind, p0, 0 if p0.numel() == 1 else 1, p1, 0 if p1.numel() == 1 else 1)
-        self._term_accumulate(term, x, scale, lw)
-
-    def accumulate_terms(self, lw, terms, overwrite=False):
-        """One pass for up to four terms; terms = [(kind, p0, p1, x, scale)] (kind 2 = the tensor x itself) or
-        [(dist_term(...), x, scale)]."""
-        def s(t):
-            return 0 if (t is None or t.numel() == 1) else 1
-        kinds, p0s, s0s, p1s, s1s, xs, scales = [], [], [], [], [], [], []
-        for item in terms:
-            if len(item) == 3:          # (dist_term tuple, x, scale)
-                (kind, p0, s0, p1, s1), x, scale = item
-            else:
-                kind, p0, p1, x, scale = item
-                s0, s1 = s(p0), s(p1)
-            kinds.append(int(kind)); p0s.append(p0); s0s.append(int(s0)); p1s.append(p1); s1s.append(int(s1))
-            xs.append(x); scales.append(float(scale))
-        ops.logweight_terms(lw, kinds, p0s, s0s, p1s, s1s, xs, scales, bool(overwrite))
-
-    def axpy(self, lw, scale, term):
-        """lw += scale * term (e.g. -log q)."""
-        ops.logweight_terms(lw, [2], [None], [0], [None], [0], [term], [float(scale)], False)
-
-    def stats(self, lw, x=None):
-        """Importance statistics (Empirical.finalize / expectation / effective_sample_size,
-        pyprob/distributions/empirical.py:298-309, 451-466, 758-766) reduced on the device in float64."""
-        self._stats = ops.is_stats(lw, x, self._stats_scratch)
-        return self._stats_dict(self._stats)
-
-    @staticmethod
-    def _stats_dict(stats):
-        m, sw, sw2, swx, swx2, cnt = (float(v) for v in stats[:6]) if isinstance(stats, np.ndarray) else stats.tolist()[:6]
-        mean = swx / sw if sw > 0 else float('nan')
-        var = swx2 / sw - mean * mean if sw > 0 else float('nan')
-        return dict(max_lw=m, sum_w=sw, sum_w2=sw2, sum_wx=swx, sum_wx2=swx2, count=cnt,
-                    ess=(sw * sw / sw2) if sw2 > 0 else 0.0, mean=mean, var=var,
-                    log_evidence=m + np.log(sw / max(cnt, 1)) if sw > 0 else float('-inf'))
-
 
 def gum_posterior(engine, num_particles, obs=(8.0, 9.0), prior_mean=1.0, prior_stddev=5.0 ** 0.5,
                   likelihood_stddev=2.0 ** 0.5, seed=0, offset=0, runner=None, return_particles=False):

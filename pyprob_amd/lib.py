@@ -6,7 +6,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libpyprob_amd.so')
 
-PP_ABI_VERSION = 14
+PP_ABI_VERSION = 15
 PP_MAX_OBS = 8
 PP_MAX_LSTM_DEPTH = 4
 PP_MAX_OBS_DEPTH = 4
@@ -63,6 +63,18 @@ class pp_batch(C.Structure):
 class pp_lw_term(C.Structure):
     _fields_ = [('kind', i32), ('p0_stride', i32), ('p1_stride', i32), ('x_stride', i32),
                 ('p0', vp), ('p1', vp), ('x', vp), ('scale', C.c_float)]
+
+
+PP_DIST_MAX_TERMS = 8
+PP_DIST_MAX_ROUNDS = 64
+
+
+class pp_dist(C.Structure):
+    _fields_ = [('kind', i32), ('p_stride', i32 * 4), ('p', vp * 4)]
+
+
+class pp_dist_term(C.Structure):
+    _fields_ = [('d', pp_dist), ('x', vp), ('x_stride', i32), ('scale', C.c_float)]
 
 
 class pp_gemm_args(C.Structure):
@@ -141,6 +153,8 @@ PROTOTYPES = {
     'pp_logweight_terms': (C.c_int, [C.POINTER(pp_lw_term), i32, vp, i32, i32, vp]),
     'pp_axpy': (C.c_int, [C.c_float, vp, vp, i32, vp]),
     'pp_is_stats': (C.c_int, [vp, vp, i32, vp, vp, vp]),
+    'pp_dist_logweight': (C.c_int, [C.POINTER(pp_dist_term), i32, vp, vp, vp, i32, i32, vp]),
+    'pp_dist_draw': (C.c_int, [C.POINTER(pp_dist), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_gemm_f32': (C.c_int, [C.POINTER(pp_gemm_args), vp]),
     'pp_gemm_f32_grouped': (C.c_int, [C.POINTER(pp_gemm_args), i32, vp]),
     'pp_colsum_f32': (C.c_int, [vp, i64, vp, i32, i32, vp, vp, vp]),

@@ -147,16 +147,72 @@ class Model:
         same = (ls.final_stats is not None and values is not None and
                 getattr(ls, 'final_stats_of', None) == (values.data_ptr(), values.numel()))
         stats = ls.final_stats if same else runner.stats(all_lw, values)
+        emp = self._lockstep_empirical(runner, ls, values, stats, num_traces, n_paths)
+        if plan_key is not None:
+            self._record_lockstep_plan(plan_key, ls, n_paths, all_values, same, observe)
+        return emp
+
+    def _traces_prior_lockstep(self, num_traces, observe, seed=0, offset=0, likelihood_importance=1., device=None, *args,
+                               **kwargs):
+        """posterior_results(IMPORTANCE_SAMPLING, lock_step=True): the reference's per-trace loop (pyprob/model.py:47-88 with
+        state.sample's prior branch, state.py:191-201) for all particles at once. Every sample statement is a device draw
+        from its prior (pp_dist_draw, counter = offset + particle: a particle's values do not depend on how the call is
+        split), every observe / factor a device log-weight term; control flow diverges into paths as in
+        _traces_lockstep_on_device. The weight of a particle is its likelihood."""
+        from .is_engine import DistRunner
+        dev = torch.device(device) if device is not None else (
+            torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu'))
+        runner = self.__dict__.get('_prior_is_runner')
+        if runner is None or runner.dev != dev:
+            runner = self._prior_is_runner = DistRunner(dev)
+        ls = state.PriorISState(runner, num_traces, seed, offset)
+        state._init_traces(func=self.forward, trace_mode=TraceMode.POSTERIOR, inference_engine=InferenceEngine.IMPORTANCE_SAMPLING,
+                           observe=observe, likelihood_importance=likelihood_importance, lock_step=ls)
+        runner.begin(num_traces, offset=offset)
+        values = None
+        n_paths = 0
+
+        def run_path():
+            nonlocal values, n_paths
+            state._begin_trace()
+            result = self.forward(*args, **kwargs)
+            n_paths += 1
+            if not torch.is_tensor(result):
+                raise RuntimeError('lock-step importance sampling: forward() must return a per-particle tensor')
+            result = result.as_subclass(torch.Tensor).reshape(-1).to(runner.dev, torch.float32)
+            if result.numel() not in (1, num_traces):
+                raise RuntimeError('lock-step importance sampling: forward() must return one value per particle')
+            if ls.rows is None:
+                values = result.clone() if result.numel() == num_traces else result.expand(num_traces).clone()
+            else:
+                if values is None:
+                    values = torch.zeros(num_traces, dtype=torch.float32, device=runner.dev)
+                runner.copy_rows(result.contiguous(), values, ls.rows)
+
+        try:
+            while True:
+                run_path()
+                if not ls.next_path():
+                    break
+        finally:
+            state._lock_step = None
+            state._current_trace = None
+            ls.memo = None
+        return self._lockstep_empirical(runner, ls, values, runner.stats(ls.lw, values), num_traces, n_paths)
+
+    @staticmethod
+    def _lockstep_empirical(runner, ls, values, stats, num_traces, n_paths):
+        """The Empirical of a lock-step call (both engines): non-finite log-weights are discarded like Model._traces does
+        (model.py:64-66), the full vectors stay attached (the distributed gather needs fixed sizes)."""
+        all_values, all_lw = values, ls.lw
         lw = all_lw
-        if int(stats['count']) != num_traces:      # non-finite log-weights are discarded like Model._traces does (model.py:64-66)
+        if int(stats['count']) != num_traces:
             values, lw = _drop_non_finite(values, all_lw)
             stats = runner.stats(lw, values)
         emp = Empirical.from_device(values, lw, stats)      # (host arrays are made on demand, not per call)
-        emp._all_values, emp._all_log_weights = all_values, all_lw     # (full shard: the distributed gather needs fixed sizes)
+        emp._all_values, emp._all_log_weights = all_values, all_lw
         emp.num_paths = n_paths
         emp.statement_log = ls.log       # per statement index: {address: (values [n], address id)} - what each path drew
-        if plan_key is not None:
-            self._record_lockstep_plan(plan_key, ls, n_paths, all_values, same, observe)
         return emp
 
     # ---- launch plan of a static lock-step program ---------------------------------------------------------------------
@@ -750,6 +806,11 @@ class Model:
                 post = self._traces_coroutines(num_traces, observe, trace_result, seed, offset, likelihood_importance,
                                                *args, **kwargs)
             post.rename('Posterior, IC, traces: {:,}, ESS: {:,.2f}'.format(post.length, post.effective_sample_size))
+        elif lock_step is True and inference_engine == InferenceEngine.IMPORTANCE_SAMPLING:
+            # the prior-proposal engine with all particles in lock step on the device
+            post = self._traces_prior_lockstep(num_traces, observe, seed=seed, offset=offset,
+                                               likelihood_importance=likelihood_importance, *args, **kwargs)
+            post.rename('Posterior, IS, traces: {:,}, ESS: {:,.2f}'.format(post.length, post.effective_sample_size))
         else:
             post = self._traces(num_traces, TraceMode.POSTERIOR, inference_engine, None, trace_result, observe,
                                 likelihood_importance, *args, **kwargs)

@@ -16,6 +16,8 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_step_rows   (the same for the rows of a diverged path, state in place)
                                                                      pyprob/state.py:207-212
     log_prob     prior / likelihood log_prob terms of the log-weight pyprob/state.py:211, 147-149
+    dist_logweight  the log-weight terms of every distribution family   pyprob/state.py:113-115, 147-149, 211
+    dist_draw       draws of every distribution family (Philox)       pyprob/state.py:191-201, 218-221
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -61,6 +63,10 @@ _lib.define('log_prob(int kind, Tensor p0, int p0_stride, Tensor? p1, int p1_str
 _lib.define('logweight_terms(Tensor(a!) lw, int[] kinds, Tensor?[] p0, int[] p0_strides, Tensor?[] p1, int[] p1_strides, '
             'Tensor[] x, float[] scales, bool overwrite) -> ()')
 _lib.define('is_stats(Tensor lw, Tensor? x, Tensor(a!) scratch) -> Tensor')
+_lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
+            'Tensor(b!)? lp_out, int n) -> ()')
+_lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
+            'int stream_id) -> ()')
 
 # ---- network registry -------------------------------------------------------------------------------------------
 _NETS = {}
@@ -412,6 +418,73 @@ def _logweight_terms_hip(lw, kinds, p0, p0_strides, p1, p1_strides, x, scales, o
     L.check(rc, 'pp_logweight_terms')
 
 
+def _dist_fill(d, kind, params, strides, q, n, what):
+    """pp_dist `d` from the 4 parameters / strides of term q (include/pyprob_amd.h: pointer + stride 0 shared / 1 per particle;
+    Categorical: p0 = probability row(s) with the row stride in strides[0] and C in strides[1])."""
+    d.kind = int(kind)
+    for k in range(4):
+        t, st = params[4 * q + k], int(strides[4 * q + k])
+        if t is not None:
+            _f32(t, '%s p%d' % (what, k))
+            need = 1 if st == 0 else (n * st if kind == 5 else n)
+            if kind == 5 and k == 0:
+                need = int(strides[4 * q + 1]) if st == 0 else n * st
+            if t.numel() < need:
+                raise RuntimeError('pyprob_hip::%s: term %d parameter %d has %d elements, %d needed' % (what, q, k, t.numel(), need))
+        d.p[k] = L.ptr(t)
+        d.p_stride[k] = st
+
+
+def _rows_arg(rows, n, what):
+    if rows is None:
+        return None, n
+    if rows.dtype != torch.int64 or not rows.is_contiguous() or rows.dim() != 1:
+        raise RuntimeError('pyprob_hip::%s: rows must be a contiguous int64 vector' % what)
+    return rows.data_ptr(), rows.numel()
+
+
+def _dist_logweight_hip(lw, kinds, params, strides, x, scales, rows, lp_out, n):
+    lib = L.load()
+    count = len(kinds)
+    if not 1 <= count <= L.PP_DIST_MAX_TERMS or len(params) != 4 * count or len(strides) != 4 * count or len(x) != count \
+            or len(scales) != count:
+        raise RuntimeError('pyprob_hip::dist_logweight: 1..%d terms, 4 parameters and strides per term' % L.PP_DIST_MAX_TERMS)
+    ref = lw if lw is not None else lp_out
+    if ref is None:
+        raise RuntimeError('pyprob_hip::dist_logweight: lw or lp_out is needed')
+    for t, name in ((lw, 'lw'), (lp_out, 'lp_out')):
+        if t is not None and (_f32(t, name).numel() != n):
+            raise RuntimeError('pyprob_hip::dist_logweight: %s must have n = %d elements' % (name, n))
+    _same_device(ref, lw, lp_out, rows, *params, *x)
+    arr = (L.pp_dist_term * count)()
+    for q in range(count):
+        _dist_fill(arr[q].d, kinds[q], params, strides, q, n, 'dist_logweight')
+        if _f32(x[q], 'x').numel() not in (1, n):
+            raise RuntimeError('pyprob_hip::dist_logweight: x of term %d must have 1 or n elements' % q)
+        arr[q].x = x[q].data_ptr()
+        arr[q].x_stride = 0 if x[q].numel() == 1 else 1
+        arr[q].scale = float(scales[q])
+    rp, m = _rows_arg(rows, n, 'dist_logweight')
+    with torch.cuda.device(ref.device):
+        rc = lib.pp_dist_logweight(arr, count, L.ptr(lw), L.ptr(lp_out), rp, int(m), int(n), _stream(ref))
+    L.check(rc, 'pp_dist_logweight')
+
+
+def _dist_draw_hip(kind, params, strides, rows, out, seed, offset, stream_id):
+    lib = L.load()
+    if len(params) != 4 or len(strides) != 4:
+        raise RuntimeError('pyprob_hip::dist_draw: 4 parameters and 4 strides')
+    n = _f32(out, 'out').numel()
+    _same_device(out, rows, *params)
+    d = L.pp_dist()
+    _dist_fill(d, kind, params, strides, 0, n, 'dist_draw')
+    rp, m = _rows_arg(rows, n, 'dist_draw')
+    with torch.cuda.device(out.device):
+        rc = lib.pp_dist_draw(C.byref(d), rp, int(m), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), int(stream_id) & 0xFFFFFFFF,
+                              out.data_ptr(), _stream(out))
+    L.check(rc, 'pp_dist_draw')
+
+
 def _is_stats_hip(lw, x, scratch):
     lib = L.load()
     _same_device(lw, x, scratch)
@@ -438,5 +511,7 @@ _lib.impl('prior_draw', _prior_draw_hip, 'CUDA')
 _lib.impl('log_prob', _log_prob_hip, 'CUDA')
 _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')
+_lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
+_lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 
 ops = getattr(torch.ops, NAMESPACE)

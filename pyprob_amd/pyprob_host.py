@@ -62,6 +62,27 @@ def convert(distribution):
             return D.Categorical(distribution._probs if hasattr(distribution, '_probs') else distribution.probs)
         if name == 'Bernoulli':
             return D.Bernoulli(_shared(distribution._probs if hasattr(distribution, '_probs') else distribution.probs))
+        if name == 'Exponential':
+            return D.Exponential(_shared(distribution.rate))
+        if name == 'Gamma':
+            return D.Gamma(_shared(distribution.concentration), _shared(distribution.rate))
+        if name == 'Beta':
+            return D.Beta(_shared(distribution.concentration1), _shared(distribution.concentration0), _shared(distribution.low),
+                          _shared(distribution.high))
+        if name == 'LogNormal':
+            return D.LogNormal(_shared(distribution.loc), _shared(distribution.scale))
+        if name == 'Weibull':
+            return D.Weibull(_shared(distribution.scale), _shared(distribution.concentration))
+        if name == 'Binomial':      # the device reads the logits, as torch's Binomial.log_prob does
+            return D.Binomial(total_count=_shared(distribution._torch_dist.total_count), logits=_shared(distribution._torch_dist.logits))
+        if name == 'VonMises':
+            return D.VonMises(_shared(distribution.loc), _shared(distribution.concentration))
+        if name == 'TruncatedNormal':      # (pyprob applied clamp_mean_between_low_high at construction)
+            return D.TruncatedNormal(_shared(distribution.mean_non_truncated), _shared(distribution.stddev_non_truncated),
+                                     _shared(distribution.low), _shared(distribution.high))
+        if name == 'Factor':
+            return D.Factor(log_prob=distribution._log_prob) if distribution._log_prob is not None else \
+                D.Factor(log_prob_func=distribution._log_prob_func)
     raise NotImplementedError('no batched executor for distribution {}'.format(name))
 
 
@@ -75,7 +96,11 @@ def _hip_observe(distribution, value=None, name=None, address=None):
 
 
 def _refuse(*args, **kwargs):
-    raise NotImplementedError('pyprob.tag / pyprob.factor have no batched executor')
+    raise NotImplementedError('pyprob.tag has no batched executor')
+
+
+def _hip_factor(log_prob=None, log_prob_func=None, name=None, address=None):
+    return S.factor(log_prob=log_prob, log_prob_func=log_prob_func, name=name, address=address)
 
 
 def _to_tensor_in_place(value, dtype=torch.float32):
@@ -118,7 +143,7 @@ def forwarded(device):
     if saved['tag'] is not None:
         pyprob.tag = _refuse
     if saved['factor'] is not None:
-        pyprob.factor = _refuse
+        pyprob.factor = _hip_factor
     _pp_util.to_tensor = _to_tensor_in_place
     saved['trace'] = _pp_state._current_trace
     _pp_state._current_trace = _NoDirectCalls()

@@ -483,6 +483,30 @@ class LockStepState(PathExecutor):
         self.decisions.append(decision)
         return decision
 
+    prior_is = False          # True: the prior-proposal engine (every sample statement draws from its prior)
+
+    def prior_statement(self, address, distribution):
+        """A sample statement drawn from its prior for the particles of this path (pp_dist_draw: key = the call's seed,
+        counter = offset + particle, one stream per statement index), recorded in the statement log like any statement;
+        no weight term."""
+        j = self.statement
+        self.statement += 1
+        if j < self.replay_statements:
+            values = self.log[j][address][0]
+        else:
+            self.flush()          # a deferred draw may be a parameter of this one
+            self.plan_ok = False
+            while len(self.log) <= j:
+                self.log.append({})
+            entry = self.log[j].get(address)
+            values = entry[0] if entry is not None else torch.empty(self.n, dtype=torch.float32, device=self.dev)
+            self.runner.draw(distribution, values, self.rows, self.seed, 0x10000 + j)
+            self.log[j][address] = (values, None)
+        w = self.wrappers.get(id(values))
+        if w is None or w[0] is not values:
+            w = self.wrappers[id(values)] = (values, ParticleTensor.wrap(values))
+        return w[1]
+
     @property
     def lw(self):
         """The per-particle log-weight accumulator; eager accumulation paths see a zero-initialised vector."""
@@ -531,6 +555,22 @@ class LockStepState(PathExecutor):
             self.final_stats = out
             self.final_stats_of = (stats_x.data_ptr(), stats_x.numel())     # what the statistics were reduced over
         return out
+
+
+class PriorISState(LockStepState):
+    """Lock-step execution of the prior-proposal engine (InferenceEngine.IMPORTANCE_SAMPLING, state.py:191-201): every
+    sample statement draws from its prior on the device, observes and factors add their likelihood terms. Branches, row
+    lists, replay prefixes and the statistics are LockStepState's; there is no network and no fused pass (the runner is an
+    is_engine.DistRunner)."""
+    prior_is = True
+
+    def __init__(self, runner, n, seed, offset):
+        super().__init__(runner, n, seed, offset)
+        self.fused = False
+        self.plan_ok = False
+
+    def flush(self, final=False):
+        return None
 
 
 def _inflate(distribution):
@@ -789,6 +829,17 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
     term = ls.runner.dist_term(distribution)
     if term is None:
         raise RuntimeError('lock-step importance sampling has no device likelihood for {}'.format(distribution.name))
+    _lock_step_term(ls, term, v, obs_name)
+
+
+def _lock_step_term(ls, term, v, obs_name=None):
+    """One likelihood term of the active particles: kinds 0-5 join the fused pass (or the rows kernel); the other families and
+    factor's value term go through pp_dist_logweight on the path's rows."""
+    if len(term) == 9:
+        ls.plan_ok = False
+        ls.flush()
+        ls.runner.dist_accumulate(ls.lw, term, v, ls.rows, _likelihood_importance)
+        return
     if ls.fused and ls.rows is None:       # full width: joins the next fused pass (with the draw, if one is pending)
         ls.defer_term(term, v, _likelihood_importance, source=('obs', obs_name) if (obs_name is not None and v.numel() == 1) else None)
         return
@@ -798,6 +849,29 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
         ls.runner.accumulate_rows(ls.lw, term, v, ls.rows, _likelihood_importance)
     else:
         ls.runner.accumulate_masked(ls.lw, None, None, None, v, ls.active, scale=_likelihood_importance, term=term)
+
+
+def factor(log_prob=None, log_prob_func=None, name=None, address=None):
+    """state.factor, pyprob/state.py:113-115: an observe of a Factor, whose log-density (scaled by likelihood_importance)
+    joins the log-weight. In lock step it is a term of the value itself (pp_dist kind 2)."""
+    from .distributions import Factor
+    observe(Factor(log_prob=log_prob, log_prob_func=log_prob_func), name=name, address=address)
+
+
+def _lock_step_factor(distribution, value):
+    ls = _lock_step
+    ls.observes += 1
+    if ls.observes <= ls.replay_observes:
+        return
+    lp = distribution.log_prob(value)
+    with torch._C.DisableTorchFunctionSubclass():
+        if not torch.is_tensor(lp) or (lp.device.type == 'cpu' and lp.numel() == 1):
+            x = ls.runner._const(float(lp))
+        else:
+            x = lp.as_subclass(torch.Tensor).to(ls.runner.dev, torch.float32).reshape(-1).contiguous()
+    if x.numel() not in (1, ls.width):
+        raise RuntimeError('lock-step factor: one log-density per particle (or one shared value), got {}'.format(x.numel()))
+    _lock_step_term(ls, ls.runner.dist_term(distribution), x)
 
 
 def observe(distribution, value=None, name=None, address=None):
@@ -822,13 +896,19 @@ def observe(distribution, value=None, name=None, address=None):
         _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
                                     log_prob=None, log_importance_weight=None, observed=True, name=name))
         return value
+    is_factor = getattr(distribution, 'name', None) == 'Factor'
+    if _lock_step is not None and is_factor:
+        _lock_step_factor(distribution, value)
+        _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
+                                    log_prob=None, log_importance_weight=None, observed=True, name=name))
+        return value
     if _lock_step is not None and value is not None:
         _lock_step_likelihood(distribution, value, obs_name=name if name in _current_trace_observed_variables else None)
         variable = Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
                             log_prob=None, log_importance_weight=None, observed=True, name=name)
         _current_trace.add(variable)
         return value
-    if value is None:
+    if value is None and not is_factor:
         observed, log_prob, lw = False, None, None
     else:
         observed = True
@@ -886,6 +966,18 @@ def sample(distribution, name=None, address=None, control=True):
         value = _lock_step.sample_statement(addr, distribution, control)
         _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
                                     control=control, name=name))     # (instance counting of the next statements)
+        return value
+    if _lock_step is not None and (_lock_step.prior_is or (_trace_mode == TraceMode.POSTERIOR and not control)):
+        # the prior-proposal engine (state.py:191-201), or an uncontrolled sample of an IC run (:218-221): a draw from the
+        # prior on the device, no weight term
+        ls = _lock_step
+        value = ls.prior_statement(addr, distribution)
+        variable = Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
+                            log_prob=None, control=control, name=name)
+        _current_trace.add(variable)
+        hist = getattr(ls, 'history', None)
+        if hist is not None:
+            hist.append((variable, ls.log[ls.statement - 1][addr][0], None, value))
         return value
     if _lock_step is not None:
         if not ic:
