@@ -10,6 +10,7 @@ PP_ABI_VERSION = 15
 PP_MAX_OBS = 8
 PP_MAX_LSTM_DEPTH = 4
 PP_MAX_OBS_DEPTH = 4
+PP_MAX_MIXTURE_COMPONENTS = 16    # MAXK of csrc/head_math.hpp: the mixture heads hold at most 16 components
 PP_ADDR_TABLE_COLS = 8
 PP_HEAD_NORMAL_MIXTURE, PP_HEAD_TRUNCNORMAL_MIXTURE, PP_HEAD_CATEGORICAL, PP_HEAD_POISSON_TN_MIXTURE = 0, 1, 2, 3
 PP_HEAD_BERNOULLI = 4

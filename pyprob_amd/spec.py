@@ -68,7 +68,11 @@ class NetSpec:
         self.dtype_dim = distribution_type_embedding_dim
         self.lstm_dim = 0 if self.feedforward else lstm_dim
         self.head_in = self.e_obs if self.feedforward else lstm_dim       # input width of the proposal layers
-        self.K = proposal_mixture_components
+        K = proposal_mixture_components
+        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= L.PP_MAX_MIXTURE_COMPONENTS:
+            raise ValueError('proposal_mixture_components must be an integer in 1..%d (MAXK of csrc/head_math.hpp), got %r'
+                             % (L.PP_MAX_MIXTURE_COMPONENTS, K))
+        self.K = int(K)
         self.lstm_in = 0 if self.feedforward else self.e_obs + self.smp_dim + 2 * (self.addr_dim + self.dtype_dim)
         self.addresses = []          # AddressInfo, index = address id
         self.address_id = {}

@@ -97,6 +97,43 @@ def synthetic_gum_arrays(n, seed=0):
     return dict(trace_len=np.ones(n, np.int32), addr_idx=np.zeros(n, np.int32), values=mu, prior=prior, obs=obs)
 
 
+def synthetic_cat_arrays(n, C, seed=0):
+    """Categorical-then-Normal traces at any width C (the `cat` golden's program, tests/golden/make_golden.py
+    CategoricalThenNormal, has C = 3): c ~ U{0..C-1} with every category present (n >= C), mu under the prior
+    N(4 c / (C - 1) - 1, 1.5) (= 2 c - 1 at C = 3) but drawn twice as wide, two observations N(mu, 0.8).
+    Returns arrays + address list."""
+    assert n >= C
+    rng = np.random.default_rng(seed)
+    c = rng.integers(0, C, n)
+    c[rng.permutation(n)[:C]] = np.arange(C)
+    m = 4.0 * c / max(C - 1, 1) - 1.0
+    mu = m + 3.0 * rng.standard_normal(n)
+    obs = mu[:, None] + 0.8 * rng.standard_normal((n, 2))
+    prior = np.zeros((2 * n, 2), np.float32)
+    prior[1::2, 0], prior[1::2, 1] = m, 1.5
+    addresses = ['c__Categorical(len_probs:%d)__1' % C, 'mu__Normal__1']
+    return dict(trace_len=np.full(n, 2, np.int32), addr_idx=np.tile(np.array([0, 1], np.int32), n),
+                values=np.stack([c, mu], 1).reshape(-1).astype(np.float32), prior=prior, obs=obs.astype(np.float32)), addresses
+
+
+def chi2_p(counts, probs):
+    """Pearson chi-square p-value of category counts against probabilities; categories expected fewer than 5 times are
+    pooled into one bin."""
+    import torch
+    n = counts.sum()
+    e = probs * n
+    keep = e >= 5
+    obs = np.append(counts[keep], counts[~keep].sum())
+    exp = np.append(e[keep], n - e[keep].sum())
+    if exp[-1] < 5:
+        obs, exp = obs[:-1], exp[:-1]
+        obs[-1] += counts[~keep].sum()
+        exp[-1] = n - exp[:-1].sum()
+    chi2 = float(((obs - exp) ** 2 / exp).sum())
+    df = len(obs) - 1
+    return float(torch.special.gammaincc(torch.tensor(df / 2, dtype=torch.float64), torch.tensor(chi2 / 2, dtype=torch.float64)))
+
+
 def synthetic_gumm_arrays(n, seed=0, max_iter=6):
     """GaussianUnknownMeanMarsaglia traces (tests/test_inference.py:252-275): pairs x,y ~ U(-1,1) until
     x^2+y^2 < 1; addresses alternate x_k, y_k with k the loop iteration. Returns arrays + address list."""
@@ -123,3 +160,31 @@ def synthetic_gumm_arrays(n, seed=0, max_iter=6):
     addresses = ['a%d__%s__Uniform__%d' % (i, 'xy'[i % 2], i // 2 + 1) for i in range(n_addr)]
     return dict(trace_len=np.array(trace_len, np.int32), addr_idx=np.array(addr_idx, np.int32),
                 values=np.array(values, np.float32), prior=prior, obs=np.array(obs, np.float32)), addresses
+
+
+KINK_MARGIN = 2e-6
+
+
+def away_from_relu_kinks(eng, arrays, addresses, dist_names, n):
+    """The first n traces of `arrays` whose proposal layer-0 pre-activations all lie further than KINK_MARGIN (relative to
+    the sum of |terms|) from the ReLU kink in float64. Nearer, the fp32 summation order decides the ReLU mask, and a flipped
+    unit moves every gradient upstream of it by the unit's whole contribution: measured on MI355X with trained-looking
+    weights, one unit at a margin of 9e-9 in 277 000 put the head's dW0 3e-3 off on every path (tiles, both panels,
+    PP_DETERMINISTIC=1) - a property of the data, not of a kernel."""
+    from oracle import ic_oracle as O
+    params = {k: v.numpy() for k, v in eng.state_dict().items()}
+    net = O.Net(params, [o[0] for o in eng.spec.obs], K=eng.spec.K)
+    out = O.loss_and_grads(net, arrays, addresses, dist_names, want_grads=False)
+    off = np.concatenate([[0], np.cumsum(arrays['trace_len'])])
+    bad = np.zeros(len(arrays['trace_len']), bool)
+    for sb, hs in zip(out['sub_batches'], out['lstm_out']):
+        sb = np.asarray(sb)
+        for t in range(hs.shape[0]):
+            Ws, bs = net.ff('_layers_proposal.%s._ff' % addresses[arrays['addr_idx'][off[sb[0]] + t]])
+            z = hs[t] @ Ws[0].T + bs[0]
+            bad[sb[(np.abs(z) < KINK_MARGIN * (np.abs(hs[t]) @ np.abs(Ws[0]).T + np.abs(bs[0]))).any(1)]] = True
+    keep = np.nonzero(~bad)[0][:n]
+    assert len(keep) == n, (len(keep), n)
+    rows = np.concatenate([np.arange(off[b], off[b + 1]) for b in keep])
+    return dict(trace_len=arrays['trace_len'][keep], addr_idx=arrays['addr_idx'][rows], values=arrays['values'][rows],
+                prior=arrays['prior'][rows], obs=arrays['obs'][keep])

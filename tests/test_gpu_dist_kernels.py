@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from helpers import chi2_p
 
 pytestmark = pytest.mark.gpu
 
@@ -273,21 +274,6 @@ def test_continuous_sampler_ks_and_moments(ops, name, p):
             assert float(v.double().var()) == pytest.approx(var, rel=0.02, abs=1e-12), (name, p)
 
 
-def _chi2_p(counts, probs):
-    n = counts.sum()
-    e = probs * n
-    keep = e >= 5
-    obs = np.append(counts[keep], counts[~keep].sum())
-    exp = np.append(e[keep], n - e[keep].sum())
-    if exp[-1] < 5:
-        obs, exp = obs[:-1], exp[:-1]
-        obs[-1] += counts[~keep].sum()
-        exp[-1] = n - exp[:-1].sum()
-    chi2 = float(((obs - exp) ** 2 / exp).sum())
-    df = len(obs) - 1
-    return float(torch.special.gammaincc(torch.tensor(df / 2, dtype=torch.float64), torch.tensor(chi2 / 2, dtype=torch.float64)))
-
-
 DISCRETE = [('Poisson', (0.3,)), ('Poisson', (4.0,)), ('Poisson', (25.0,)), ('Poisson', (3000.0,)),
             ('Binomial', (10.0, 0.3)), ('Binomial', (1000.0, 0.005)), ('Binomial', (200.0, 0.4)), ('Binomial', (5000.0, 0.97)),
             ('Bernoulli', (0.3,))]
@@ -318,7 +304,7 @@ def test_discrete_sampler_chi_square_and_moments(ops, name, p):
         m, var = p[0], p[0] * (1 - p[0])
     counts = np.bincount(v.long().numpy(), minlength=len(k)).astype(np.float64)
     full = pmf / pmf.sum() if name == 'Bernoulli' else pmf
-    assert _chi2_p(counts, full) > 1e-5, (name, p)
+    assert chi2_p(counts, full) > 1e-5, (name, p)
     n = v.numel()
     assert abs(float(v.mean()) - m) < 6 * math.sqrt(var / n), (name, p)
     assert float(v.var()) == pytest.approx(var, rel=0.02), (name, p)
@@ -330,7 +316,7 @@ def test_categorical_draws(ops):
     ops.dist_draw(5, [probs, None, None, None], [0, 4, 0, 0], None, out, 3, 0, 9)
     counts = np.bincount(out.long().cpu().numpy(), minlength=4).astype(np.float64)
     assert len(counts) == 4
-    assert _chi2_p(counts, np.array([0.2, 0.5, 0.1, 0.2])) > 1e-5
+    assert chi2_p(counts, np.array([0.2, 0.5, 0.1, 0.2])) > 1e-5
 
 
 # ---- counters ---------------------------------------------------------------------------------------------------------

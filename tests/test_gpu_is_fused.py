@@ -2,10 +2,13 @@
 importance statistics in ONE pass over the particles, state.LockStepState.flush) against the one-kernel-per-term path
 (PP_IS_FUSED=0) through the drop-in API Model.posterior_results: same Philox stream -> bit-identical values, equal
 log-weights and statistics; host-side Empirical reductions equal the device statistics."""
+import math
+
 import numpy as np
 import pytest
 
 from models import GaussianWithUnknownMean, GaussianWithUnknownMeanMarsagliaLockStep
+from oracle import ic_oracle as O
 from pyprob_amd.state import InferenceEngine, InferenceNetwork
 
 pytestmark = pytest.mark.gpu
@@ -33,6 +36,18 @@ def gumm():
     return model
 
 
+@pytest.fixture(scope='module', params=[1, 16], ids=['k1', 'k16'])
+def gum_k(request):
+    """A fresh GUM network with one or sixteen mixture components: pp_is_fused draws through is_fused_kernel with a run-time
+    K (only K = 10 has its own instantiation)."""
+    torch.manual_seed(6)
+    model = GaussianWithUnknownMean()
+    model.learn_inference_network(inference_network=InferenceNetwork.LSTM, num_traces=4096, observe_embeddings=EMB, batch_size=128,
+                                  lstm_dim=64, proposal_mixture_components=request.param, seed=7)
+    assert model._inference_network._engine.spec.K == request.param
+    return model
+
+
 def _both(model, n, monkeypatch, observe, seed):
     monkeypatch.setenv('PP_IS_FUSED', '1')
     fused = model.posterior_results(n, IC, observe=observe, lock_step=True, seed=seed)
@@ -41,9 +56,8 @@ def _both(model, n, monkeypatch, observe, seed):
     return fused, eager
 
 
-@pytest.mark.parametrize('n', [1000, 65537, 1000000])
-def test_fused_pass_equals_the_per_term_kernels(gum, monkeypatch, n):
-    fused, eager = _both(gum, n, monkeypatch, OBS, seed=11)
+def _fused_equals_the_per_term_kernels(model, monkeypatch, n):
+    fused, eager = _both(model, n, monkeypatch, OBS, seed=11)
     vf, ve = fused._all_values.cpu().numpy(), eager._all_values.cpu().numpy()
     assert np.array_equal(vf, ve)                              # the same Philox stream, the same draw arithmetic
     lf, le = fused._all_log_weights.cpu().numpy(), eager._all_log_weights.cpu().numpy()
@@ -58,7 +72,32 @@ def test_fused_pass_equals_the_per_term_kernels(gum, monkeypatch, n):
     assert abs(float(np.sum(w * v)) - mean_dev) < 1e-6 * max(1.0, abs(mean_dev))
     assert abs(1.0 / float(np.sum(w * w)) - ess_dev) < 1e-6 * ess_dev
     assert abs(fused.mean - mean_dev) < 1e-6 and abs(fused.stddev - std_dev) < 1e-6
+    return fused
+
+
+@pytest.mark.parametrize('n', [1000, 65537, 1000000])
+def test_fused_pass_equals_the_per_term_kernels(gum, monkeypatch, n):
+    fused = _fused_equals_the_per_term_kernels(gum, monkeypatch, n)
     assert abs(fused.mean - 7.25) < 0.75
+
+
+@pytest.mark.parametrize('n', [1000, 65537])
+def test_fused_pass_at_other_mixture_sizes(gum_k, monkeypatch, n):
+    """K = 1 and K = 16: the fused pass equals the per-term kernels, and every particle's log-weight equals the float64
+    oracle's re-scoring at that K (log p - log q of the drawn mu + both Normal observe terms)."""
+    fused = _fused_equals_the_per_term_kernels(gum_k, monkeypatch, n)
+    eng = gum_k._inference_network._engine
+    params = {k: v.numpy() for k, v in eng.state_dict().items()}
+    net = O.Net(params, ['obs0', 'obs1'], K=eng.spec.K)
+    v = fused._all_values.cpu().numpy().astype(np.float64)
+    lw = fused._all_log_weights.cpu().numpy().astype(np.float64)
+    steps = [dict(address=eng.spec.addresses[0].address, dist_name='Normal', values=v, prior=np.array([[1.0, math.sqrt(5)]]))]
+    _, lw_ref = O.is_rescore_lockstep(net, [float(OBS['obs0']), float(OBS['obs1'])], steps, n, chunk=1 << 18)
+    lw_ref = lw_ref + sum(np.asarray(O.normal_log_prob(float(y), v, math.sqrt(2)), np.float32).astype(np.float64)
+                          for y in OBS.values())
+    assert np.isfinite(lw_ref).all()
+    err = np.abs(lw - lw_ref) / np.maximum(1.0, np.abs(lw_ref))
+    assert err.max() < 1e-4, (err.max(), int(err.argmax()))
 
 
 def test_fused_pass_in_a_program_with_control_flow(gumm, monkeypatch):

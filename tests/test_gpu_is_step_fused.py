@@ -29,12 +29,17 @@ def _force_fused(monkeypatch, request):
     return request.param
 
 
-def _engine(H, seed=0, depth=1, emb=None):
+def _addrs(ncat=7):
+    """ADDRS with a Categorical(ncat) head at a_cat."""
+    return [(a, d, ncat if d == 'Categorical' else c) for a, d, c in ADDRS]
+
+
+def _engine(H, seed=0, depth=1, emb=None, K=10, addrs=ADDRS):
     from pyprob_amd.engine import ICEngine
     from pyprob_amd.is_engine import ISRunner
-    spec = NetSpec(emb or EMB, lstm_dim=H, lstm_depth=depth)
+    spec = NetSpec(emb or EMB, lstm_dim=H, lstm_depth=depth, proposal_mixture_components=K)
     eng = ICEngine(spec, device='cuda:0', seed=seed)
-    eng.add_addresses(ADDRS)
+    eng.add_addresses(addrs)
     rng = np.random.default_rng(seed + 1)
     # trained-looking weights: larger than the default initialisation so that gates and mixtures are not near-uniform
     sd = {k: (v.numpy() * (3.0 if ('lstm' in k or 'proposal' in k) else 1.0)).astype(np.float32) for k, v in eng.state_dict().items()}
@@ -47,10 +52,10 @@ def _engine(H, seed=0, depth=1, emb=None):
     return eng, run, sd
 
 
-def _oracle_statement(sd, H, observe, prev, cur, prev_val, h0, c0, values, prior, depth=1, emb=None):
+def _oracle_statement(sd, H, observe, prev, cur, prev_val, h0, c0, values, prior, depth=1, emb=None, K=10, addrs=ADDRS):
     """One `_infer_step` for n particles in float64: returns (h, c, log q, head outputs y); depth > 1: (h0, c0) and the returned
     states are [depth, n, H] (nn.LSTM(I, H, depth): layer k reads the new hidden rows of layer k - 1)."""
-    net = O.Net(sd, list(emb or EMB), K=10)
+    net = O.Net(sd, list(emb or EMB), K=K)
     a_prev, d_prev = prev
     a_cur, d_cur = cur
     n = len(prev_val)
@@ -59,7 +64,7 @@ def _oracle_statement(sd, H, observe, prev, cur, prev_val, h0, c0, values, prior
     x = np.zeros((n, W_ih.shape[1]))
     col = E.shape[1]
     x[:, :col] = E[0]
-    cat = 7 if d_prev == 'Categorical' else None
+    cat = {a: c for a, d, c in addrs}[a_prev] if d_prev == 'Categorical' else None
     s, _ = O.sample_embedding(net, a_prev, d_prev, prev_val, cat)
     S, Ed, Ea = s.shape[1], 8, 64
     x[:, col:col + S] = s
@@ -99,9 +104,12 @@ def _prior_for(dist, n, rng):
     return np.zeros((n, 2), np.float32)
 
 
-def _prev_values(dist, n, rng):
+def _prev_values(dist, n, rng, ncat=7):
     if dist == 'Categorical':
-        return rng.integers(0, 7, n).astype(np.float32)
+        v = rng.integers(0, ncat, n)
+        if ncat > 7:
+            v[:min(n, ncat)] = np.arange(min(n, ncat))      # every category, ncat - 1 included
+        return v.astype(np.float32)
     return rng.normal(0, 1.5, n).astype(np.float32)
 
 
@@ -109,7 +117,7 @@ def _ids(eng, name):
     return eng.spec.address_id[name]
 
 
-@pytest.mark.parametrize('H,n,prev,cur,depth', [
+STATEMENT_CASES = [
     (512, 1000, ('a_normal', 'Normal'), ('a_uniform', 'Uniform'), 1),        # TruncatedNormal mixture, ragged last panel
     (512, 32, ('a_uniform', 'Uniform'), ('a_normal', 'Normal'), 1),          # exactly one panel
     (512, 4133, ('a_cat', 'Categorical'), ('a_normal', 'Normal'), 1),        # one-hot sample embedding of the previous value
@@ -144,17 +152,44 @@ def _ids(eng, name):
     # shapes without a fused kernel: the chain of GEMM launches, same oracle
     (48, 200, ('a_uniform', 'Uniform'), ('a_normal', 'Normal'), 1),
     (512, 150, ('a_normal', 'Normal'), ('a_uniform', 'Uniform'), 2),
-])
-def test_fused_statement_against_the_oracle(H, n, prev, cur, depth):
+]
+# other mixture sizes and categorical widths: (H, n, prev, cur, depth, K, categories of a_cat). n_out = 3 K or C above 32 takes
+# the chain of GEMM launches (is_kernels.hip); K = 1 / 5 / 10 and C = 32 the fused, split or small statement
+STATEMENT_CASES_KC = [
+    pytest.param(512, 1000, ('a_normal', 'Normal'), ('a_uniform', 'Uniform'), 1, 1, 7, id='k1-512-1000-uniform'),
+    pytest.param(512, 1000, ('a_uniform', 'Uniform'), ('a_normal', 'Normal'), 1, 5, 7, id='k5-512-1000-normal'),
+    pytest.param(1024, 1000, ('a_uniform', 'Uniform'), ('a_normal', 'Normal'), 1, 1, 7, id='k1-1024-1000-normal'),
+    pytest.param(64, 500, ('a_normal', 'Normal'), ('a_uniform', 'Uniform'), 2, 1, 7, id='k1-64x2-500-uniform'),
+    pytest.param(64, 500, ('a_uniform', 'Uniform'), ('a_normal', 'Normal'), 2, 10, 7, id='k10-64x2-500-normal'),
+    pytest.param(128, 500, ('a_normal', 'Normal'), ('a_uniform', 'Uniform'), 1, 16, 7, id='k16-128-500-uniform'),
+    pytest.param(512, 1000, ('a_uniform', 'Uniform'), ('a_normal', 'Normal'), 1, 16, 7, id='k16-512-1000-normal'),
+    pytest.param(512, 257, ('a_normal', 'Normal'), ('a_poisson', 'Poisson'), 1, 16, 7, id='k16-512-257-poisson'),
+    pytest.param(1024, 1000, ('a_normal', 'Normal'), ('a_uniform', 'Uniform'), 1, 16, 7, id='k16-1024-1000-uniform'),
+    pytest.param(512, 300, ('a_normal', 'Normal'), ('a_cat', 'Categorical'), 1, 10, 32, id='c32-512-300-cat'),
+    pytest.param(512, 300, ('a_normal', 'Normal'), ('a_cat', 'Categorical'), 1, 10, 33, id='c33-512-300-cat'),
+    pytest.param(512, 300, ('a_normal', 'Normal'), ('a_cat', 'Categorical'), 1, 10, 100, id='c100-512-300-cat'),
+    # Categorical(100) as the PREVIOUS address: a one-hot input of width 100 into the fused, small and chain LSTM inputs
+    pytest.param(512, 1000, ('a_cat', 'Categorical'), ('a_normal', 'Normal'), 1, 10, 100, id='c100prev-512-1000-normal'),
+    pytest.param(64, 500, ('a_cat', 'Categorical'), ('a_uniform', 'Uniform'), 1, 10, 100, id='c100prev-64-500-uniform'),
+    pytest.param(48, 200, ('a_cat', 'Categorical'), ('a_normal', 'Normal'), 1, 10, 100, id='c100prev-48-200-normal'),
+]
+
+
+@pytest.mark.parametrize('H,n,prev,cur,depth,K,ncat',
+                         [pytest.param(*c, 10, 7, id='%d-%d-prev%d-cur%d-%d' % (c[0], c[1], i, i, c[4])) for i, c in enumerate(STATEMENT_CASES)]
+                         + STATEMENT_CASES_KC)
+def test_fused_statement_against_the_oracle(H, n, prev, cur, depth, K, ncat):
     from pyprob_amd.ops import ops
-    eng, run, sd = _engine(H, depth=depth)
+    addrs = _addrs(ncat)
+    eng, run, sd = _engine(H, depth=depth, K=K, addrs=addrs)
     # (the fixture forces the fused statement at any n; by default H = 1024 takes it from 2 049 particles on)
-    fused = (H in (512, 1024) and depth == 1) or (H % 32 == 0 and H <= 256)
+    n_out = eng.spec.head_dims(eng.spec.addresses[_ids(eng, cur[0])])[0]
+    fused = ((H in (512, 1024) and depth == 1) or (H % 32 == 0 and H <= 256)) and n_out <= 32
     assert eng.lib.pp_is_step_fused_supported(C.byref(eng.net), _ids(eng, cur[0]), n) == (1 if fused else 0)
     rng = np.random.default_rng(5)
     h0 = (0.5 * rng.standard_normal((depth, n, H))).astype(np.float32).clip(-0.99, 0.99)
     c0 = rng.standard_normal((depth, n, H)).astype(np.float32)
-    pv = _prev_values(prev[1], n, rng)
+    pv = _prev_values(prev[1], n, rng, ncat)
     prior = _prior_for(cur[1], n, rng)
     dev = eng.device
     h = torch.from_numpy(h0.copy()).to(dev).contiguous()
@@ -173,8 +208,10 @@ def test_fused_statement_against_the_oracle(H, n, prev, cur, depth):
     if cur[1] == 'Uniform':
         assert np.all((v >= prior[:, 0]) & (v < prior[:, 1]))
     o_h0, o_c0 = (h0[0], c0[0]) if depth == 1 else (h0, c0)
+    if cur[1] == 'Categorical':
+        assert np.all((v >= 0) & (v < ncat) & (v == np.floor(v)))
     href, cref, lq_ref, _ = _oracle_statement(sd, H, [8.0, 9.0], prev, cur, pv, o_h0, o_c0, v.astype(np.float64), prior.astype(np.float64),
-                                              depth=depth)
+                                              depth=depth, K=K, addrs=addrs)
     # the LSTM cell on v_exp_f32 / v_rcp_f32 sigmoid / tanh: absolute error of (h, c) asserted here
     eh = np.abs(h.cpu().numpy().reshape(np.shape(href)) - href).max()
     ec = np.abs(c.cpu().numpy().reshape(np.shape(cref)) - cref).max()
@@ -392,9 +429,15 @@ def _mixture_cdf(x, params, dist, lo=None, hi=None):
     return (z * p).sum(1)
 
 
-@pytest.mark.parametrize('cur,H,depth', [(('a_normal', 'Normal'), 512, 1), (('a_uniform', 'Uniform'), 512, 1), (('a_uniform', 'Uniform'), 1024, 1),
-                                         (('a_normal', 'Normal'), 64, 2), (('a_uniform', 'Uniform'), 32, 1)])
-def test_the_drawn_values_follow_the_proposal(cur, H, depth):
+DRAW_CASES = [(('a_normal', 'Normal'), 512, 1), (('a_uniform', 'Uniform'), 512, 1), (('a_uniform', 'Uniform'), 1024, 1),
+              (('a_normal', 'Normal'), 64, 2), (('a_uniform', 'Uniform'), 32, 1)]
+
+
+@pytest.mark.parametrize('cur,H,depth,K', [pytest.param(*c, 10, id='cur%d-%d-%d' % (i, c[1], c[2])) for i, c in enumerate(DRAW_CASES)] + [
+    pytest.param(('a_normal', 'Normal'), 512, 1, 1, id='k1-normal-512'),          # one component: the fused draw
+    pytest.param(('a_normal', 'Normal'), 512, 1, 16, id='k16-normal-512'),        # n_out 48: the chain sampler (is_draw.hpp)
+    pytest.param(('a_uniform', 'Uniform'), 128, 1, 16, id='k16-uniform-128')])
+def test_the_drawn_values_follow_the_proposal(cur, H, depth, K):
     """The N-row draw itself (sixteen lanes per particle: component pick by the inclusive prefix of the clamped weights, then
     the component's Normal / inverse-CDF TruncatedNormal draw - is_step_fused.hip's tail, is_draw.hpp): re-scoring proves
     log q AT the drawn value, not that the value is drawn FROM q. Here every particle gets the same
@@ -404,7 +447,7 @@ def test_the_drawn_values_follow_the_proposal(cur, H, depth):
     from pyprob_amd.ops import ops
     n = 40000
     prev = ('a_uniform', 'Uniform') if cur[1] == 'Normal' else ('a_normal', 'Normal')
-    eng, run, sd = _engine(H, seed=3, depth=depth)
+    eng, run, sd = _engine(H, seed=3, depth=depth, K=K)
     rng = np.random.default_rng(11)
     h0 = np.tile((0.5 * rng.standard_normal((depth, 1, H))).astype(np.float32).clip(-0.99, 0.99), (1, n, 1))
     c0 = np.tile(rng.standard_normal((depth, 1, H)).astype(np.float32), (1, n, 1))
@@ -420,8 +463,8 @@ def test_the_drawn_values_follow_the_proposal(cur, H, depth):
     v = value.cpu().numpy().astype(np.float64)
     assert np.all(np.isfinite(v)) and len(np.unique(v)) > 0.99 * n          # distinct Philox counters per particle
     href, _, _, y = _oracle_statement(sd, H, [8.0, 9.0], prev, cur, pv[:1], h0[0, :1] if depth == 1 else h0[:, :1],
-                                       c0[0, :1] if depth == 1 else c0[:, :1], None, None, depth=depth)
-    net = O.Net(sd, list(EMB), K=10)
+                                       c0[0, :1] if depth == 1 else c0[:, :1], None, None, depth=depth, K=K)
+    net = O.Net(sd, list(EMB), K=K)
     y_all = np.broadcast_to(y[:1], (n, y.shape[1]))
     lq_ref, _, params = O.head_forward(net, cur[0], cur[1], None, prior.astype(np.float64), v, y=y_all)
     one = tuple(np.asarray(a)[0] for a in params)
@@ -445,6 +488,42 @@ def test_the_drawn_values_follow_the_proposal(cur, H, depth):
     se = w.std() / np.sqrt(n)
     assert abs(w.mean() - 1.0) < 4.0 * se + 1e-3, (w.mean(), se)
     # (3) the device's log q at its own draws
+    assert np.abs(logq.cpu().numpy() - lq_ref).max() < 1e-4 * max(1.0, np.abs(lq_ref).max())
+
+
+@pytest.mark.parametrize('ncat', [2, 100])
+def test_the_drawn_categories_follow_the_proposal(ncat):
+    """The categorical draw under one shared proposal (every particle the same state and previous value): Pearson chi-square of
+    the counts of 40 000 draws against the oracle's category probabilities, and log q of the device at its draws. ncat = 2: the
+    fused / split statement; ncat = 100 (n_out > 32): the chain."""
+    from helpers import chi2_p
+    from pyprob_amd.ops import ops
+    n, H = 40000, 512
+    addrs = _addrs(ncat)
+    eng, run, sd = _engine(H, seed=3, addrs=addrs)
+    assert eng.lib.pp_is_step_fused_supported(C.byref(eng.net), _ids(eng, 'a_cat'), n) == (1 if ncat <= 32 else 0)
+    rng = np.random.default_rng(13)
+    h0 = np.tile((0.5 * rng.standard_normal((1, 1, H))).astype(np.float32).clip(-0.99, 0.99), (1, n, 1))
+    c0 = np.tile(rng.standard_normal((1, 1, H)).astype(np.float32), (1, n, 1))
+    pv = np.full(n, 0.37, np.float32)
+    dev = eng.device
+    h = torch.from_numpy(h0.copy()).to(dev).contiguous()
+    c = torch.from_numpy(c0.copy()).to(dev).contiguous()
+    run._ensure_ws(n)
+    value, logq = ops.is_step(eng.params, run.ws, eng.net_handle, _ids(eng, 'a_cat'), _ids(eng, 'a_normal'), n, run.e_obs,
+                              torch.from_numpy(pv).to(dev), None, h, c, n, None, 4243, 0)
+    torch.cuda.synchronize()
+    v = value.cpu().numpy().astype(np.float64)
+    assert np.all((v >= 0) & (v < ncat) & (v == np.floor(v)))
+    cur = ('a_cat', 'Categorical')
+    _, _, _, y = _oracle_statement(sd, H, [8.0, 9.0], ('a_normal', 'Normal'), cur, pv[:1], h0[0, :1], c0[0, :1], None, None,
+                                   addrs=addrs)
+    net = O.Net(sd, list(EMB), K=10)
+    lq_ref, _, (p,) = O.head_forward(net, cur[0], cur[1], None, None, v, y=np.broadcast_to(y[:1], (n, ncat)))
+    probs = p[0]
+    assert probs.max() < 0.9 and (probs > 1.0 / n).sum() >= 2          # a proposal that is not (nearly) one category
+    counts = np.bincount(v.astype(np.int64), minlength=ncat).astype(np.float64)
+    assert chi2_p(counts, probs) > 1e-4, (chi2_p(counts, probs), counts[:8], probs[:8] * n)
     assert np.abs(logq.cpu().numpy() - lq_ref).max() < 1e-4 * max(1.0, np.abs(lq_ref).max())
 
 

@@ -291,9 +291,8 @@ def test_lstm_cell_forward_backward(env, n, H):
     assert torch.isfinite(dG3).all() and float(dG3[:, H:2 * H].abs().max()) == 0.0
 
 
-def _head_case(kind, n, K, rng):
+def _head_case(kind, n, K, rng, Cn=7):
     if kind == 2:
-        Cn = 7
         y = rng.normal(0, 2, (n, Cn))
         v = rng.integers(0, Cn, n).astype(np.float64)
         prior = np.zeros((n, 2))
@@ -314,12 +313,22 @@ def _head_case(kind, n, K, rng):
 
 
 @pytest.mark.parametrize('kind', [0, 1, 2])
-@pytest.mark.parametrize('K', [10, 3, 16])
+@pytest.mark.parametrize('K', [10, 3, 16, 1])
 def test_head_logprob_and_gradient(env, kind, K):
+    _check_head(env, kind, K, 7)
+
+
+@pytest.mark.parametrize('Cn', [1, 33, 100])
+def test_head_logprob_and_gradient_categorical_widths(env, Cn):
+    """The categorical head at one category (log_prob 0, no gradient) and at widths above the fused statements' 32 outputs."""
+    _check_head(env, 2, 10, Cn)
+
+
+def _check_head(env, kind, K, Cn):
     L, lib, device = env
-    rng = np.random.default_rng(kind * 10 + K)
+    rng = np.random.default_rng(kind * 10 + K + (Cn if Cn != 7 else 0))
     n = 777
-    y, v, prior, lp_ref, dy_ref, n_out = _head_case(kind, n, K, rng)
+    y, v, prior, lp_ref, dy_ref, n_out = _head_case(kind, n, K, rng, Cn)
     ldy = ((n_out + 3) // 4) * 4
     Y = np.zeros((n, ldy), np.float32)
     Y[:, :n_out] = y
@@ -348,9 +357,13 @@ def test_head_logprob_and_gradient(env, kind, K):
     np.testing.assert_allclose(got_lp[fin], lp_ref[fin], rtol=1e-4, atol=2e-5)
     dy_ref = np.where(fin[:, None], dy_ref, 0.0) * gs
     scale = np.abs(dy_ref).max()
-    assert np.abs(dyo.cpu().numpy()[:, :n_out] - dy_ref).max() / scale < 2e-4
     loss_ref = -(np.where(fin, lp_ref, O.LOG_EPSILON)).sum()
-    assert abs(float(acc.item()) - loss_ref) / abs(loss_ref) < 1e-5
+    if n_out == 1:          # one category: log_prob 0 (clamped to log(1 - eps)), dy 0
+        assert scale == 0 and np.abs(dyo.cpu().numpy()).max() == 0
+        assert abs(float(acc.item()) - loss_ref) < 1e-4
+    else:
+        assert np.abs(dyo.cpu().numpy()[:, :n_out] - dy_ref).max() / scale < 2e-4
+        assert abs(float(acc.item()) - loss_ref) / abs(loss_ref) < 1e-5
     assert int(flag.item()) == 0
 
 

@@ -18,25 +18,37 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPT = r'''
 import sys, numpy as np, torch
 sys.path.insert(0, %(repo)r); sys.path.insert(0, %(repo)r + '/tests')
-from helpers import synthetic_gum_arrays
+from helpers import away_from_relu_kinks, synthetic_gum_arrays
 from pyprob_amd.engine import ICEngine
 from pyprob_amd.packed import PackedBatch
 from pyprob_amd.spec import NetSpec
 out = {}
-for name, B, dist in (('gum1024', 1024, 'Normal'), ('gum1003', 1003, 'Normal'), ('uni777', 777, 'Uniform'), ('nan64', 64, 'Normal'),
-                      ('gum2048', 2048, 'Normal'), ('gum2041', 2041, 'Normal'), ('gum4096', 4096, 'Normal'),
-                      ('wide1024', 1024, 'Normal'), ('wide1003', 1003, 'Normal'), ('wideuni500', 500, 'Uniform')):
-    # (wide*: LSTM hidden 1024 - BASELINE.json configs[4]'s per-rank network; the 16-row kernel only)
-    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=1024 if name.startswith('wide') else 512)
+for name, B, dist, K in (('gum1024', 1024, 'Normal', 10), ('gum1003', 1003, 'Normal', 10), ('uni777', 777, 'Uniform', 10),
+                         ('nan64', 64, 'Normal', 10), ('gum2048', 2048, 'Normal', 10), ('gum2041', 2041, 'Normal', 10),
+                         ('gum4096', 4096, 'Normal', 10), ('wide1024', 1024, 'Normal', 10), ('wide1003', 1003, 'Normal', 10),
+                         ('wideuni500', 500, 'Uniform', 10), ('k1gum1003', 1003, 'Normal', 1), ('k5uni777', 777, 'Uniform', 5),
+                         ('k15gum1003', 1003, 'Normal', 15), ('k15uni777', 777, 'Uniform', 15), ('k16gum1003', 1003, 'Normal', 16),
+                         ('k16uni777', 777, 'Uniform', 16), ('widek1gum1003', 1003, 'Normal', 1)):
+    # (wide*: LSTM hidden 1024 - BASELINE.json configs[4]'s per-rank network; the 16-row kernel only. k*: other mixture sizes -
+    # K = 11..15 the 8-row kernel in both panel modes (n_out > 30); K = 16 needs 167 KB of the 8-row kernel's LDS (160 KB):
+    # tiles + head tail in every mode. The k* batches keep their traces away from the head's ReLU kink
+    # (helpers.away_from_relu_kinks): unfiltered, a K = 5 batch of 777 rows had one unit at 1e-8 of its sum of |terms| whose
+    # mask flipped on the 8-row kernel and moved the head's layer-0 gradient by 1e-3)
+    kcase = name.startswith(('k', 'widek'))
+    n0 = B + 64 if kcase else B
+    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=1024 if name.startswith('wide') else 512,
+                   proposal_mixture_components=K)
     spec.add_address('mu', dist)
-    arr = synthetic_gum_arrays(B, seed=3 + B)
+    arr = synthetic_gum_arrays(n0, seed=3 + B)
     if dist == 'Uniform':       # prior U(-4, 6); a few values outside the support (log_prob -inf -> rescued rows)
-        arr['prior'] = np.tile(np.array([[-4.0, 6.0]], np.float32), (B, 1))
+        arr['prior'] = np.tile(np.array([[-4.0, 6.0]], np.float32), (n0, 1))
         arr['values'] = np.clip(arr['values'], -3.9, 5.9).astype(np.float32)
         arr['values'][::97] = 7.5
     if name == 'nan64':
         arr['obs'][5, 1] = np.nan
     eng = ICEngine(spec, device='cuda:0', seed=5)
+    if kcase:
+        arr = away_from_relu_kinks(eng, arr, ['mu'], [dist], B)
     pb = PackedBatch.from_ragged(arr['trace_len'], arr['addr_idx'], arr['values'], arr['prior'], arr['obs'], 1).to(eng.device)
     l, lp = eng.loss(pb, backward=True, keep_lp=True)
     torch.cuda.synchronize()
@@ -45,9 +57,12 @@ for name, B, dist in (('gum1024', 1024, 'Normal'), ('gum1003', 1003, 'Normal'), 
     out[name + '_status'] = eng.status_buf[:1].cpu().numpy()
     out[name + '_grads'] = eng.grads.cpu().numpy()
     # a second, different minibatch through the same workspace (stale buffers of the first must not leak)
-    arr2 = synthetic_gum_arrays(B, seed=77 + B)
+    arr2 = synthetic_gum_arrays(n0, seed=77 + B)
     if dist == 'Uniform':
-        arr2['prior'] = arr['prior']; arr2['values'] = np.clip(arr2['values'], -3.9, 5.9).astype(np.float32)
+        arr2['prior'] = np.tile(np.array([[-4.0, 6.0]], np.float32), (n0, 1))
+        arr2['values'] = np.clip(arr2['values'], -3.9, 5.9).astype(np.float32)
+    if kcase:
+        arr2 = away_from_relu_kinks(eng, arr2, ['mu'], [dist], B)
     pb2 = PackedBatch.from_ragged(arr2['trace_len'], arr2['addr_idx'], arr2['values'], arr2['prior'], arr2['obs'], 1).to(eng.device)
     l2 = eng.loss(pb2, backward=True)
     torch.cuda.synchronize()
@@ -168,24 +183,37 @@ def test_panel_kernel_equals_the_tile_path(tmp_path, tile_run, mode):
 
 def test_panel_kernel_against_the_oracle():
     """GUM, H = 512, B = 256 with the panel kernel on: loss and every gradient against the float64 oracle."""
-    from helpers import synthetic_gum_arrays
+    _panel_against_the_oracle(10)
+
+
+@pytest.mark.parametrize('K', [15, 16])
+def test_panel_kernel_against_the_oracle_at_more_components(K):
+    """The same at K = 15 - the 8-row kernel, the only panel for K = 11..15 - and at K = 16, which falls back to the tiles and
+    the head tail."""
+    _panel_against_the_oracle(K)
+
+
+def _panel_against_the_oracle(K):
+    from helpers import away_from_relu_kinks, synthetic_gum_arrays
     from oracle import ic_oracle as O
     from pyprob_amd.engine import ICEngine
     from pyprob_amd.packed import PackedBatch
     from pyprob_amd.spec import NetSpec
     assert os.environ.get('PP_PANEL', '2') != '0'
-    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=512)
+    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=512, proposal_mixture_components=K)
     spec.add_address('mu', 'Normal')
     eng = ICEngine(spec, device='cuda:0', seed=11)
     arr = synthetic_gum_arrays(250, seed=21)
+    if K != 10:
+        arr = away_from_relu_kinks(eng, synthetic_gum_arrays(250 + 32, seed=21), ['mu'], ['Normal'], 250)
     pb = PackedBatch.from_ragged(arr['trace_len'], arr['addr_idx'], arr['values'], arr['prior'], arr['obs'], 1).to(eng.device)
     loss, lp = eng.loss(pb, backward=True, keep_lp=True)
     torch.cuda.synchronize()
     P = {k: v.numpy().astype(np.float64) for k, v in eng.state_dict().items()}
-    net = O.Net(P, ['obs0', 'obs1'], K=10)
+    net = O.Net(P, ['obs0', 'obs1'], K=K)
     ref = O.loss_and_grads(net, arr, ['mu'], ['Normal'])
     assert abs(float(loss.item()) - ref['loss']) <= 2e-5 * abs(ref['loss'])
     g = eng.grad_dict()
     for n in spec.tensors:
         if np.abs(ref['grads'][n]).max() > 1e-7:
-            grad_check('panel_h512_b250/%s' % n, g[n], ref['grads'][n], 5e-6)      # measured 4.6e-7
+            grad_check('panel_h512_b250%s/%s' % ('' if K == 10 else '_k%d' % K, n), g[n], ref['grads'][n], 5e-6)      # measured 4.6e-7

@@ -2,11 +2,15 @@
 C ABI, against (a) the golden vectors recorded from the reference and (b) the numpy oracle at benchmark sizes, plus
 size-independent properties. Tolerance: north_star asks 1e-4 relative on log-weights; most checks are tighter."""
 
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
-from conftest import load_golden
-from helpers import (engine_from_golden, grad_check, packed_from_golden, rel_err, synthetic_gum_arrays,
+from conftest import REPO, load_golden
+from helpers import (away_from_relu_kinks, engine_from_golden, grad_check, packed_from_golden, rel_err, synthetic_gum_arrays,
                      synthetic_gumm_arrays)
 from oracle import ic_oracle as O
 
@@ -15,6 +19,16 @@ pytestmark = pytest.mark.gpu
 # 8.6e-7 relative on the single-statement shapes; 5.0e-9 ABSOLUTE on the ragged ones, whose gradients are ~1e-6)
 GRAD_BAR = 1e-5
 GRAD_ABS_RAGGED = 5e-8
+# absolute floors of the trained-looking cases with TruncatedNormal heads, whose head gradients are sums over ~1 000 rows that
+# cancel. Largest absolute error of a tensor beyond 1e-5 of its max |gradient|, measured on MI355X on the tile path
+# (PP_PANEL=0) / with PP_DETERMINISTIC=1 / on the default path - the same on every path, so fp32 summation order:
+#   single statements (GRAD_ABS_UNIFORM_TRAINED): K = 3 2.3e-8 / 2.1e-8 / 2.2e-8 (dW2 of the head, max 5e-5);
+#     K = 15 5.8e-9 / 5.9e-9 / 5.5e-9; K = 16 5.4e-9 / 6.1e-9 / 5.4e-9
+#   ragged GUMM (GRAD_ABS_RAGGED_TRAINED): H = 512 K = 1 5.2e-8 / 5.1e-8 / 5.2e-8 (dW2 of a head, max 5e-5);
+#     H = 512 K = 16 8.1e-9 / 9.4e-9 / 8.1e-9; H = 256 depth 2 K = 16 4.6e-9 / 4.7e-9 / 4.6e-9
+# (the ragged FeedForward cases keep GRAD_ABS_RAGGED: K = 1 3.8e-8, K = 16 1.3e-8 on all three paths)
+GRAD_ABS_UNIFORM_TRAINED = 5e-8
+GRAD_ABS_RAGGED_TRAINED = 1.5e-7
 torch = pytest.importorskip('torch')
 
 
@@ -65,13 +79,29 @@ def _oracle_run(spec, params, arrays, addresses, dist_names, want_grads=True):
     return O.loss_and_grads(net, arrays, addresses, dist_names, want_grads=want_grads)
 
 
-def _fresh_engine(lstm_dim, addresses, dist, seed=0):
+def _fresh_engine(lstm_dim, addresses, dist, seed=0, K=10, lstm_depth=1, network='lstm', extra=()):
+    """extra: (address, dist, num_categories) added after `addresses`."""
     from pyprob_amd.engine import ICEngine
     from pyprob_amd.spec import NetSpec
-    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=lstm_dim)
+    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=lstm_dim, proposal_mixture_components=K,
+                   network=network, lstm_depth=lstm_depth)
     for a in addresses:
         spec.add_address(a, dist)
+    for a, d, ncat in extra:
+        spec.add_address(a, d, ncat)
     return ICEngine(spec, seed=seed)
+
+
+def _trained_looking(eng, seed):
+    """LSTM and proposal weights x3 plus noisy biases (as test_gpu_is_step_fused._engine): the mixtures are far from uniform,
+    so a wrong component index moves log_prob and not only the gradients."""
+    rng = np.random.default_rng(seed)
+    sd = {k: (v.numpy() * (3.0 if ('lstm' in k or 'proposal' in k) else 1.0)).astype(np.float32) for k, v in eng.state_dict().items()}
+    for k in sd:
+        if k.endswith('bias') or 'bias_' in k:
+            sd[k] = (sd[k] + 0.1 * rng.standard_normal(sd[k].shape)).astype(np.float32)
+    eng.load_state_dict(sd)
+    return eng
 
 
 def _packed(arrays, spec):
@@ -80,24 +110,114 @@ def _packed(arrays, spec):
                                    arrays['obs'], len(spec.addresses))
 
 
-@pytest.mark.parametrize('H', [512])
-def test_benchmark_size_gum_against_oracle(H):
-    """config 2 shape: GUM, batch 1024, LSTM hidden 512 (1 643 583 parameters)."""
-    eng = _fresh_engine(H, ['mu'], 'Normal')
-    assert eng.spec.num_parameters() == 1643583
-    arrays = synthetic_gum_arrays(1024, seed=3)
-    pb = _packed(arrays, eng.spec).to(eng.device)
-    l, lp = eng.loss(pb, backward=True, keep_lp=True)
-    torch.cuda.synchronize()
-    params = {k: v.numpy() for k, v in eng.state_dict().items()}
-    out = _oracle_run(eng.spec, params, arrays, ['mu'], ['Normal'])
-    assert abs(float(l.item()) - out['loss']) <= 2e-5 * abs(out['loss'])
-    lp_tm = _unpack_lp(pb, lp.cpu().numpy(), arrays)
-    np.testing.assert_allclose(lp_tm, out['lp'][0], rtol=1e-4, atol=1e-4)
+def _single_statement_arrays(B, dist, seed):
+    """One statement per trace, values spread wider than the prior: Normal N(1, 2 sqrt5) under the prior N(1, sqrt5); Uniform
+    U(-4, 6) with every 97th value outside the support (log_prob -inf -> rescued row); Poisson counts 0..40 (the head's
+    TruncatedNormal mixture on the fixed [0, 40], pyprob_amd.packed.POISSON_LOW_HIGH)."""
+    from pyprob_amd.packed import POISSON_LOW_HIGH
+    arr = synthetic_gum_arrays(B, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    if dist == 'Normal':
+        arr['values'] = (1.0 + 2.0 * np.sqrt(5.0) * rng.standard_normal(B)).astype(np.float32)
+    elif dist == 'Uniform':
+        arr['prior'] = np.tile(np.array([[-4.0, 6.0]], np.float32), (B, 1))
+        arr['values'] = rng.uniform(-4.0, 6.0, B).astype(np.float32)
+        arr['values'][::97] = 7.5
+    else:
+        arr['prior'] = np.tile(np.array([POISSON_LOW_HIGH], np.float32), (B, 1))
+        arr['values'] = rng.integers(0, 41, B).astype(np.float32)
+    return arr
+
+
+def _oracle_lp_rows(out, arrays):
+    """The oracle's log_prob lists (one per sub-batch and time step) -> one value per row of the trace-major arrays."""
+    off = np.concatenate([[0], np.cumsum(arrays['trace_len'])])
+    ref = np.full(int(off[-1]), np.nan)
+    k = 0
+    for sb in out['sub_batches']:
+        sb = np.asarray(sb)
+        for t in range(int(arrays['trace_len'][sb[0]])):
+            ref[off[sb] + t] = out['lp'][k]
+            k += 1
+    assert k == len(out['lp']) and not np.isnan(ref).any()
+    return ref
+
+
+def _check_lp(lp_tm, ref, label):
+    fin = np.isfinite(ref)
+    assert np.array_equal(np.isfinite(lp_tm), fin), label
+    np.testing.assert_allclose(lp_tm[fin], ref[fin], rtol=1e-4, atol=1e-4, err_msg=label)
+
+
+def _check_grads(label, eng, out, abs_floor=0.0):
     g = eng.grad_dict()
     for n in eng.spec.tensors:
         if np.abs(out['grads'][n]).max() >= 1e-7:
-            grad_check('gum_h%d_b1024/%s' % (H, n), g[n], out['grads'][n], GRAD_BAR)
+            grad_check('%s/%s' % (label, n), g[n], out['grads'][n], GRAD_BAR, abs_floor)
+        elif not np.any(out['grads'][n]):
+            assert not np.any(g[n]), (label, n)        # a tensor the batch does not touch
+
+
+# (H, B, dist, K, extra addresses). The first case is config 2's shape on a fresh network; the others run other mixture sizes
+# on trained-looking weights and spread values. In brackets the path MI355X takes by default (spec.head_dims: n_out = 3 K,
+# head hidden = (H + n_out) / 2).
+GUM_CASES = [
+    pytest.param(512, 1024, 'Normal', 10, (), id='512'),
+    pytest.param(512, 1003, 'Normal', 1, (), id='h512_b1003_normal_k1'),           # [16-row panel]
+    pytest.param(512, 1003, 'Normal', 2, (), id='h512_b1003_normal_k2'),           # [16-row panel]
+    pytest.param(512, 1003, 'Normal', 5, (), id='h512_b1003_normal_k5'),           # [16-row panel]
+    pytest.param(512, 1003, 'Uniform', 3, (), id='h512_b1003_uniform_k3'),         # [16-row panel, TruncatedNormal mixture]
+    pytest.param(512, 1003, 'Poisson', 7, (), id='h512_b1003_poisson_k7'),         # [16-row panel, Poisson TN mixture]
+    pytest.param(512, 1003, 'Normal', 11, (), id='h512_b1003_normal_k11'),         # [8-row panel: n_out 33 > 30]
+    pytest.param(512, 1003, 'Normal', 15, (), id='h512_b1003_normal_k15'),         # [8-row panel: its largest K]
+    pytest.param(512, 1003, 'Uniform', 15, (), id='h512_b1003_uniform_k15'),       # [8-row panel]
+    # (K = 16: 167 KB of LDS, over the 8-row panel's 160 KB, panel.hip panel_t1_supported)
+    pytest.param(512, 1003, 'Normal', 16, (), id='h512_b1003_normal_k16'),         # [tiles + head tail]
+    pytest.param(512, 1003, 'Uniform', 16, (), id='h512_b1003_uniform_k16'),       # [tiles + head tail]
+    pytest.param(512, 2049, 'Normal', 15, (), id='h512_b2049_normal_k15'),         # [tiles + head tail: 257 eight-row panels > 256]
+    pytest.param(1024, 300, 'Normal', 1, (), id='h1024_b300_normal_k1'),           # [16-row panel]
+    pytest.param(1024, 300, 'Normal', 16, (), id='h1024_b300_normal_k16'),         # [tiles + head tail, hid 536]
+    pytest.param(1536, 256, 'Normal', 10, (), id='h1536_b256_normal_k10'),         # [head tail, hid 783: 16 columns per lane]
+    pytest.param(1536, 256, 'Normal', 16, (), id='h1536_b256_normal_k16'),         # [unfused chain: hid 792 breaks the LDS budget]
+    # a batch of the Normal address of a network that also holds a Categorical(100) head: the workspace strides come from the
+    # wider head (hid4 308, out4 100), so the panels step aside and the head tail runs with lda1 = 308 and lddy = 100
+    pytest.param(512, 1024, 'Normal', 10, (('c100', 'Categorical', 100),), id='h512_b1024_normal_k10_next_to_cat100'),
+]
+
+
+@pytest.mark.parametrize('H,B,dist,K,extra', GUM_CASES)
+def test_benchmark_size_gum_against_oracle(H, B, dist, K, extra):
+    """config 2 shape: GUM, batch 1024, LSTM hidden 512 (1 643 583 parameters); and single-statement batches at every
+    mixture-head path: K = 1..16, Normal / Uniform / Poisson heads, H = 512 / 1024 / 1536."""
+    first = (H, B, dist, K, extra) == (512, 1024, 'Normal', 10, ())
+    eng = _fresh_engine(H, ['mu'], dist, K=K, extra=extra)
+    if first:
+        assert eng.spec.num_parameters() == 1643583
+        arrays = synthetic_gum_arrays(1024, seed=3)
+    else:
+        assert eng.spec.head_dims(eng.spec.addresses[0])[0] == 3 * K
+        _trained_looking(eng, seed=K + H)
+        arrays = away_from_relu_kinks(eng, _single_statement_arrays(B + 64, dist, seed=B + K), ['mu'], [dist], B)
+    pb = _packed(arrays, eng.spec).to(eng.device)
+    l, lp = eng.loss(pb, backward=True, keep_lp=True)
+    torch.cuda.synchronize()
+    assert int(eng.status_buf[0].item()) == 0
+    params = {k: v.numpy() for k, v in eng.state_dict().items()}
+    out = _oracle_run(eng.spec, params, arrays, ['mu'], [dist])
+    assert abs(float(l.item()) - out['loss']) <= 2e-5 * abs(out['loss'])
+    lp_tm = _unpack_lp(pb, lp.cpu().numpy(), arrays)
+    if first:
+        np.testing.assert_allclose(lp_tm, out['lp'][0], rtol=1e-4, atol=1e-4)
+    else:
+        _check_lp(lp_tm, out['lp'][0], 'lp')
+    if first:
+        g = eng.grad_dict()
+        for n in eng.spec.tensors:
+            if np.abs(out['grads'][n]).max() >= 1e-7:
+                grad_check('gum_h%d_b1024/%s' % (H, n), g[n], out['grads'][n], GRAD_BAR)
+    else:
+        _check_grads('gum_h%d_b%d_%s_k%d%s' % (H, B, dist, K, '_cat100' if extra else ''), eng, out,
+                     GRAD_ABS_UNIFORM_TRAINED if dist == 'Uniform' else 0.0)
 
 
 @pytest.mark.parametrize('B', [300, 1024])
@@ -119,33 +239,53 @@ def test_hidden_1024_against_oracle(B):
             grad_check('gum_h1024_b%d/%s' % (B, n), g[n], out['grads'][n], GRAD_BAR)
 
 
-def test_benchmark_size_gumm_ragged_against_oracle():
-    """config 3 shape: GUMM (variable-length traces, one head per address), batch 1024, hidden 512."""
-    arrays, addresses = synthetic_gumm_arrays(1024, seed=4, max_iter=6)
-    eng = _fresh_engine(512, addresses, 'Uniform')
+def _gumm_ragged_against_oracle(H, depth, B, K, trained):
+    arrays, addresses = synthetic_gumm_arrays(B + 64 if trained else B, seed=4, max_iter=6)
+    eng = _fresh_engine(H, addresses, 'Uniform', K=K, lstm_depth=depth)
+    if trained:
+        _trained_looking(eng, seed=K)
+        arrays['values'][::53] = 1.25           # outside U(-1, 1): rescued rows (the addresses stay those of the drawn pairs)
+        arrays = away_from_relu_kinks(eng, arrays, addresses, ['Uniform'] * len(addresses), B)
     pb = _packed(arrays, eng.spec).to(eng.device)
     l, lp = eng.loss(pb, backward=True, keep_lp=True)
     torch.cuda.synchronize()
     params = {k: v.numpy() for k, v in eng.state_dict().items()}
     out = _oracle_run(eng.spec, params, arrays, addresses, ['Uniform'] * len(addresses))
     assert abs(float(l.item()) - out['loss']) <= 2e-5 * abs(out['loss'])
+    label = 'gumm_ragged_h%d_b%d' % (H, B) + ('_d%d_k%d' % (depth, K) if trained else '')
+    _check_lp(_unpack_lp(pb, lp.cpu().numpy(), arrays), _oracle_lp_rows(out, arrays), label + '/lp')
+    if trained:
+        _check_grads(label, eng, out, GRAD_ABS_RAGGED_TRAINED)
+        return
     g = eng.grad_dict()
     for n in eng.spec.tensors:
         if np.abs(out['grads'][n]).max() > 1e-7:
-            grad_check('gumm_ragged_h512_b1024/%s' % n, g[n], out['grads'][n], GRAD_BAR, GRAD_ABS_RAGGED)
+            grad_check('%s/%s' % (label, n), g[n], out['grads'][n], GRAD_BAR, GRAD_ABS_RAGGED)
 
 
-def test_feedforward_network_benchmark_size_against_oracle():
-    """InferenceNetworkFeedForward (inference_network_feedforward.py:68-98) at batch 1024 on ragged GUMM traces: the
-    gradient of the observe embedding sums over each trace's time steps, one head per address."""
+def test_benchmark_size_gumm_ragged_against_oracle():
+    """config 3 shape: GUMM (variable-length traces, one head per address), batch 1024, hidden 512."""
+    _gumm_ragged_against_oracle(512, 1, 1024, 10, trained=False)
+
+
+@pytest.mark.parametrize('H,depth,B,K', [(512, 1, 1024, 1), (512, 1, 1024, 16), (256, 2, 300, 16)])
+def test_gumm_ragged_mixture_sizes_against_oracle(H, depth, B, K):
+    """The ragged GUMM batch with one- and sixteen-component TruncatedNormal mixtures [LSTM tail + head tail] on trained-looking
+    weights, every 53rd value outside the support."""
+    _gumm_ragged_against_oracle(H, depth, B, K, trained=True)
+
+
+def _feedforward_against_oracle(K, trained):
     from pyprob_amd.engine import ICEngine
     from pyprob_amd.spec import NetSpec
     arrays, addresses = synthetic_gumm_arrays(1024, seed=8, max_iter=6)
-    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, network='feedforward')
+    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, network='feedforward', proposal_mixture_components=K)
     for a in addresses:
         spec.add_address(a, 'Uniform')
     assert spec.lstm_dim == 0 and not any(n.startswith('_layers_lstm') for n in spec.tensors)
     eng = ICEngine(spec, seed=2)
+    if trained:
+        _trained_looking(eng, seed=K)
     pb = _packed(arrays, eng.spec).to(eng.device)
     l, lp = eng.loss(pb, backward=True, keep_lp=True)
     fwd = eng.loss(pb).clone()                       # forward-only entry point: same loss
@@ -156,15 +296,63 @@ def test_feedforward_network_benchmark_size_against_oracle():
     out = O.loss_and_grads_feedforward(net, arrays, addresses, ['Uniform'] * len(addresses))
     assert abs(float(l.item()) - out['loss']) <= 2e-5 * abs(out['loss'])
     assert abs(float(fwd.item()) - out['loss']) <= 2e-5 * abs(out['loss'])
+    _check_lp(_unpack_lp(pb, lp.cpu().numpy(), arrays), _oracle_lp_rows(out, arrays), 'ff_k%d/lp' % K)
     g = eng.grad_dict()
     for n in eng.spec.tensors:
         if np.abs(out['grads'][n]).max() > 1e-7:
-            grad_check('ff_ragged_b1024/%s' % n, g[n], out['grads'][n], GRAD_BAR, GRAD_ABS_RAGGED)
+            grad_check('ff_ragged_b1024%s/%s' % ('_k%d' % K if trained else '', n), g[n], out['grads'][n], GRAD_BAR, GRAD_ABS_RAGGED)
+    return eng, pb, l
+
+
+def test_feedforward_network_benchmark_size_against_oracle():
+    """InferenceNetworkFeedForward (inference_network_feedforward.py:68-98) at batch 1024 on ragged GUMM traces: the
+    gradient of the observe embedding sums over each trace's time steps, one head per address."""
+    eng, pb, l = _feedforward_against_oracle(10, trained=False)
     # a few Adam steps reduce the loss
     first = float(l.item())
     for _ in range(30):
         last = eng.train_step(pb, 1e-3)
     assert float(last.item()) < first
+
+
+@pytest.mark.parametrize('K', [1, 16])
+def test_feedforward_mixture_sizes_against_oracle(K):
+    """The FeedForward network's ragged batch with one- and sixteen-component heads, trained-looking weights."""
+    _feedforward_against_oracle(K, trained=True)
+
+
+@pytest.mark.parametrize('C', [2, 32, 33, 100])
+def test_categorical_then_normal_against_oracle(C):
+    """Categorical(C) then Normal (the `cat` golden's program at other widths), H = 512, B = 1024: the categorical head with
+    C outputs at t = 0 and the one-hot sample embedding of width C as the LSTM input of t = 1 (gather.hpp) with its weight
+    gradient (kernels.hip sample_embed_bwd*). Every category occurs, C - 1 included."""
+    from helpers import synthetic_cat_arrays
+    arrays, addresses = synthetic_cat_arrays(1024 + 64, C, seed=40 + C)
+    eng = _fresh_engine(512, [], None, extra=((addresses[0], 'Categorical', C), (addresses[1], 'Normal', None)))
+    _trained_looking(eng, seed=C)
+    arrays = away_from_relu_kinks(eng, arrays, addresses, ['Categorical', 'Normal'], 1024)
+    pb = _packed(arrays, eng.spec).to(eng.device)
+    l, lp = eng.loss(pb, backward=True, keep_lp=True)
+    torch.cuda.synchronize()
+    assert int(eng.status_buf[0].item()) == 0
+    params = {k: v.numpy() for k, v in eng.state_dict().items()}
+    out = _oracle_run(eng.spec, params, arrays, addresses, ['Categorical', 'Normal'])
+    assert abs(float(l.item()) - out['loss']) <= 2e-5 * abs(out['loss'])
+    lp_tm = _unpack_lp(pb, lp.cpu().numpy(), arrays)
+    assert len(out['lp']) == 2                       # one sub-batch, two time steps
+    _check_lp(lp_tm[0::2], out['lp'][0], 'lp_t0')
+    _check_lp(lp_tm[1::2], out['lp'][1], 'lp_t1')
+    assert np.array_equal(np.unique(arrays['values'][0::2]), np.arange(C))
+    _check_grads('cat%d_h512_b1024' % C, eng, out)
+
+
+def test_categorical_sample_embedding_deterministic_path():
+    """C = 100 again with PP_DETERMINISTIC=1 (read once per process, hence the subprocess): the one-hot weight gradient runs
+    through sample_embed_bwd_det instead of the scatter with float atomics."""
+    r = subprocess.run([sys.executable, '-m', 'pytest', '-q', '-p', 'no:cacheprovider',
+                        os.path.abspath(__file__) + '::test_categorical_then_normal_against_oracle[100]'],
+                       cwd=REPO, env=dict(os.environ, PP_DETERMINISTIC='1'), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and '1 passed' in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
 
 
 def test_resident_loop_matches_the_per_step_calls():

@@ -13,9 +13,11 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (name, lstm_dim, lstm_depth, batch, max Marsaglia iterations): a team takes 8 rows per step, so the tail starts at the
-# first step with <= teams * 8 traces left - at step 1 for the small batches (the whole recurrence in the two launches)
-CASES = (('h512', 512, 1, 1024, 6), ('h512_small', 512, 1, 40, 5), ('h256_d2', 256, 2, 300, 5), ('h1024', 1024, 1, 64, 4))
+# (name, lstm_dim, lstm_depth, batch, max Marsaglia iterations, mixture components): a team takes 8 rows per step, so the tail
+# starts at the first step with <= teams * 8 traces left - at step 1 for the small batches (the whole recurrence in the two
+# launches); K = 1 / 16: the head tail's one- and sixteen-component instantiations behind the LSTM tail
+CASES = (('h512', 512, 1, 1024, 6, 10), ('h512_small', 512, 1, 40, 5, 10), ('h256_d2', 256, 2, 300, 5, 10), ('h1024', 1024, 1, 64, 4, 10),
+         ('h512_k1', 512, 1, 1024, 6, 1), ('h512_k16', 512, 1, 1024, 6, 16), ('h256_d2_k16', 256, 2, 300, 5, 16))
 
 SCRIPT = r'''
 import sys, numpy as np, torch
@@ -25,10 +27,10 @@ from pyprob_amd.engine import ICEngine
 from pyprob_amd.packed import PackedBatch
 from pyprob_amd.spec import NetSpec
 out = {}
-for name, H, depth, B, iters in %(cases)r:
+for name, H, depth, B, iters, K in %(cases)r:
     arrs = [synthetic_gumm_arrays(B, seed=11 + s, max_iter=iters) for s in range(4)]
     addresses = arrs[0][1]
-    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=H, lstm_depth=depth)
+    spec = NetSpec({'obs0': {'dim': 32}, 'obs1': {'dim': 32}}, lstm_dim=H, lstm_depth=depth, proposal_mixture_components=K)
     for a in addresses: spec.add_address(a, 'Uniform')
     eng = ICEngine(spec, device='cuda:0', seed=5)
     def packed(arr, ad):
@@ -60,7 +62,7 @@ def _run(tmp_path, tag, **env):
 def test_tail_kernels_equal_the_per_step_path(tmp_path):
     tail = _run(tmp_path, 'tail', PP_LSTM_TAIL='1')
     plain = _run(tmp_path, 'plain', PP_LSTM_TAIL='0')
-    for name, H, depth, B, iters in CASES:
+    for name, H, depth, B, iters, K in CASES:
         nact = tail[name + '_nact']
         assert int(tail[name + '_tmax'][0]) >= 4 and nact[-1] <= 8, (name, nact)   # the case does reach the tail path
         assert abs(float(tail[name + '_loss'][0]) - float(plain[name + '_loss'][0])) <= 2e-6 * abs(float(plain[name + '_loss'][0])), name

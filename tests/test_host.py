@@ -89,6 +89,22 @@ def test_survey_parameter_counts():
     assert s.num_parameters() == 2968878   # GUMM notebook, 10 addresses
 
 
+def test_netspec_rejects_mixture_sizes_the_heads_cannot_hold():
+    """proposal_mixture_components must be an integer in 1..16 (MAXK of csrc/head_math.hpp): 0, 17 and 2.5 used to give
+    n_out = 0, 51 and 7.5 and failed only inside the first device call."""
+    from pyprob_amd import lib as L
+    from pyprob_amd.spec import NetSpec
+    obs = {'obs0': {'dim': 32}}
+    assert L.PP_MAX_MIXTURE_COMPONENTS == 16
+    for K in (0, -1, 17, 2.5, 10.0, '10', None, True):
+        with pytest.raises(ValueError, match='1..16'):
+            NetSpec(obs, lstm_dim=64, proposal_mixture_components=K)
+    for K in (1, 5, 16, np.int64(16)):
+        s = NetSpec(obs, lstm_dim=64, proposal_mixture_components=K)
+        s.add_address('a', 'Normal')
+        assert s.K == K and type(s.K) is int and s.head_dims(s.addresses[0])[0] == 3 * K
+
+
 def test_packed_batch_structure(golden):
     case, meta, params, batch, loss, isr = golden
     spec = spec_from_golden(meta, params)
