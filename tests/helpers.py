@@ -1,4 +1,5 @@
-"""Shared helpers of the parity tests: build an ICEngine / PackedBatch from the golden vectors."""
+"""Shared helpers of the parity tests: build an ICEngine / PackedBatch from the golden vectors, the importance-sampling test
+engine and the term matrix of the fused posterior pass (pp_is_fused)."""
 import numpy as np
 
 from pyprob_amd.spec import NetSpec
@@ -188,3 +189,287 @@ def away_from_relu_kinks(eng, arrays, addresses, dist_names, n):
     rows = np.concatenate([np.arange(off[b], off[b + 1]) for b in keep])
     return dict(trace_len=arrays['trace_len'][keep], addr_idx=arrays['addr_idx'][rows], values=arrays['values'][rows],
                 prior=arrays['prior'][rows], obs=arrays['obs'][keep])
+
+
+# ---- the importance-sampling test network (tests/test_gpu_is_step_fused.py, tests/test_gpu_is_fused_kernel.py) -----------------
+IS_EMB = {'obs0': {'dim': 32}, 'obs1': {'dim': 32}}
+IS_ADDRS = [('a_normal', 'Normal', None), ('a_uniform', 'Uniform', None), ('a_cat', 'Categorical', 7), ('a_poisson', 'Poisson', None),
+            ('a_bern', 'Bernoulli', None)]
+
+
+def is_engine(H, seed=0, depth=1, emb=None, K=10, addrs=IS_ADDRS, device='cuda:0'):
+    """(engine, ISRunner, state dict) of a network with one address per proposal head and trained-looking weights.
+    device='cpu': the engine's buffers on the host (tests/oracle_ops.py CpuBufferEngine; the operators are then the oracle-backed
+    stand-ins) - the initialisation is numpy's, the weights are the same on either device."""
+    from pyprob_amd.is_engine import ISRunner
+    spec = NetSpec(emb or IS_EMB, lstm_dim=H, lstm_depth=depth, proposal_mixture_components=K)
+    if device == 'cpu':
+        import oracle_ops
+        eng = oracle_ops.CpuBufferEngine(spec, seed=seed)
+    else:
+        from pyprob_amd.engine import ICEngine
+        eng = ICEngine(spec, device=device, seed=seed)
+    eng.add_addresses(addrs)
+    rng = np.random.default_rng(seed + 1)
+    # trained-looking weights: larger than the default initialisation so that gates and mixtures are not near-uniform
+    sd = {k: (v.numpy() * (3.0 if ('lstm' in k or 'proposal' in k) else 1.0)).astype(np.float32) for k, v in eng.state_dict().items()}
+    for k in sd:
+        if k.endswith('bias') or 'bias_' in k:
+            sd[k] = (sd[k] + 0.1 * rng.standard_normal(sd[k].shape)).astype(np.float32)
+    eng.load_state_dict(sd)
+    run = ISRunner(eng)
+    run.init([8.0, 9.0])
+    return eng, run, sd
+
+
+# ---- the term matrix of pp_is_fused ------------------------------------------------------------------------------------------------
+# A term on the host: dict(kind, p0, s0, p1, s1, x, scale, flags, out, label) - float32 arrays (None where the flag word says "the
+# particle's value": the product passes no pointer there), strides as the C ABI reads them (Categorical: s0 = row stride, s1 = C),
+# `out` = the particles PLANTED outside the term's support (the bookkeeping the reference is checked against).
+# Per-term tolerance of tests/test_gpu_logweight.py::test_prior_log_prob_kernels_against_oracle (rtol = atol; Poisson 2e-5).
+FUSED_TERM_TOL = {0: 1e-5, 1: 1e-5, 2: 1e-5, 3: 2e-5, 4: 1e-5, 5: 1e-5}
+FUSED_SCALES = (1.0, -1.0, 0.37, -2.5)
+FUSED_CAT = 12             # categories: a value in [5, 9] is a legal index (flag 4 on a Categorical term)
+FUSED_PLANT_MIN_N = 128    # smaller runs carry no planted particles
+
+
+def fused_values(n, rng):
+    """The particles' values: positive, one sign, away from 0 (they also serve as sigma under flag 2)."""
+    return rng.uniform(5.0, 9.0, n).astype(np.float32)
+
+
+def fused_term(kind, n, rng, value, flags=0, per_p=0, per_x=0, scale=1.0, slot=0, per_p1=None, plant=True):
+    """One term of kind 0 Normal / 1 Uniform / 2 identity / 3 Poisson / 4 Bernoulli / 5 Categorical. per_p / per_x: parameters / x
+    per particle (stride 1; Categorical: n probability rows) or shared (stride 0); per_p1: the second parameter on its own.
+    flags bit 1 / 2 / 4: p0 / p1 / x IS the particle's value. slot: moves the planted particles (and the shared constants) so
+    that the terms of one call differ."""
+    f32 = np.float32
+    per_p1 = per_p if per_p1 is None else per_p1
+
+    def vec(lo, hi):
+        return rng.uniform(lo, hi, n).astype(f32)
+
+    def one(v):
+        return np.array([v], f32)
+    assert not (flags & 3) or kind in (0, 1)
+    p0 = p1 = x = None
+    s0 = s1 = 0
+    out = np.zeros(n, bool)
+    base = 7 + 11 * slot
+    planting = plant and n >= FUSED_PLANT_MIN_N
+    if kind == 0:
+        p0, s0 = (vec(5.5, 8.5), 1) if per_p else (one(6.5 + 0.125 * slot), 0)
+        p1, s1 = (vec(1.0, 3.0), 1) if per_p1 else (one(1.3 + 0.2 * slot), 0)      # sigma positive and away from 0
+        x = vec(5.0, 9.0) if per_x else one(7.25 - 0.25 * slot)
+    elif kind == 1:
+        assert (flags & 3) != 3, 'low = high = value: an empty interval'
+        # low < x < high whichever of them is the particle's value (in [5, 9])
+        xl, xh = (9.25, 9.9) if flags & 1 else ((3.5, 4.9) if flags & 2 else (4.0, 9.5))
+        p0, s0 = (vec(0.0, 3.0), 1) if per_p else (one(2.0), 0)
+        p1, s1 = (vec(10.0, 14.0), 1) if per_p1 else (one(12.0), 0)
+        x = vec(xl, xh) if per_x else one(0.5 * (xl + xh))
+        if (flags & 6) == 6:
+            out[:] = True      # x = high = value: outside [low, high) everywhere
+        elif planting:
+            # x == low (inside), x == high (outside), x > high (outside): written into whichever side is a per-particle array
+            def eff(a, s, bit):
+                return value if flags & bit else (a if s else np.full(n, a[0], f32))
+            lo_e, hi_e, x_e = eff(p0, s0, 1), eff(p1, s1, 2), eff(x, per_x, 4)
+            x_mod, lo_mod, hi_mod = per_x and not flags & 4, s0 == 1 and not flags & 1, s1 == 1 and not flags & 2
+            i = base
+            if x_mod:
+                x[i] = lo_e[i]
+            elif lo_mod:
+                p0[i] = x_e[i]
+            i = base + 1
+            if x_mod:
+                x[i], out[i] = hi_e[i], True
+            elif hi_mod and x_e[i] > lo_e[i]:
+                p1[i], out[i] = x_e[i], True
+            i = base + 2
+            if x_mod:
+                x[i], out[i] = hi_e[i] + f32(1.5), True
+            elif hi_mod and x_e[i] > lo_e[i]:
+                mid = f32(0.5) * (lo_e[i] + x_e[i])
+                if lo_e[i] < mid < x_e[i]:
+                    p1[i], out[i] = mid, True
+    elif kind == 2:
+        x = vec(-3.0, 3.0) if per_x else one(0.75 + slot)
+    elif kind == 3:
+        p0, s0 = (vec(0.2, 9.0), 1) if per_p else (one(4.2), 0)
+        if per_x:      # counts and reals, zeros among them
+            x = np.where(rng.random(n) < 0.5, rng.poisson(4.0, n), rng.uniform(0.0, 12.0, n)).astype(f32)
+            x[::7] = 0.0
+        else:
+            x = one(3.0)
+    elif kind == 4:
+        p0, s0 = (vec(0.0, 1.0), 1) if per_p else (one(0.3), 0)
+        if per_p and n >= 3:
+            p0[:3] = [0.0, 1.0, 0.5]      # clamped to [eps, 1 - eps]
+        x = (rng.random(n) < 0.5).astype(f32) if per_x else one(1.0)
+    elif kind == 5:
+        C = FUSED_CAT
+        s1 = C
+        p0, s0 = (rng.uniform(0.01, 1.0, (n, C)).astype(f32).reshape(-1), C) if per_p else (rng.uniform(0.01, 1.0, C).astype(f32), 0)
+        if per_x:
+            x = rng.integers(0, C, n).astype(f32)
+            x[1::5] += f32(0.4)           # the index is the truncated value
+            if planting and not flags & 4:
+                x[base], out[base] = C, True
+                x[base + 1], out[base + 1] = -1.0, True
+                x[base + 2], out[base + 2] = C + 0.5, True
+                x[base + 3] = C - 1
+        else:
+            x = one(3.0)
+    else:
+        raise ValueError(kind)
+    if flags & 1:
+        p0, s0 = None, 0
+    if flags & 2:
+        p1, s1 = None, 0
+    if flags & 4:
+        x = None
+    label = 'kind%d flags%d p%s%s x%s scale%g' % (kind, flags, 'n' if per_p else '1', 'n' if per_p1 else '1',
+                                                   'v' if flags & 4 else ('n' if per_x else '1'), scale)
+    return dict(kind=kind, p0=p0, s0=s0, p1=p1, s1=s1, x=x, scale=float(f32(scale)), flags=flags, out=out, label=label)
+
+
+def fused_single_term_cases(n, rng, value):
+    """Every term kind x parameters shared / per particle x `x` shared / per particle / the value x every legal flag word:
+    bit 4 on all kinds, bits 1 and 2 on Normal and Uniform (not both on a Uniform: low = high = value is an empty interval, which
+    torch's Uniform rejects and whose float64 log-density is log 0 - log 0). Scales cycle through FUSED_SCALES."""
+    cases = []
+    for kind in range(6):
+        flag_words = range(8) if kind == 0 else ((0, 1, 2, 4, 5, 6) if kind == 1 else (0, 4))
+        for flags in flag_words:
+            for per_p in (0, 1):
+                for per_x in (0, 1):
+                    if (flags & 4 and per_x) or (kind == 2 and per_p) or ((flags & 3) == 3 and per_p):
+                        continue      # (the array would not be read)
+                    cases.append(fused_term(kind, n, rng, value, flags, per_p, per_x, FUSED_SCALES[len(cases) % 4], slot=len(cases) % 8))
+    return cases
+
+
+def fused_mixed_sets(n, rng, value):
+    """Calls of eight terms (the ABI's maximum). The first seven terms of `lean`, `general_poisson` and `general_sigma` are the
+    SAME Normal / identity terms (one scale per term for all particles: the LEAN instantiation takes them); the eighth makes the
+    call all-LEAN or general, so both instantiations evaluate the same Normal terms. `all_kinds`: every kind, per-particle
+    sigma, sigma = value, Uniform bounds = value, planted out-of-support particles (at different particles per term)."""
+    def common():
+        r = np.random.default_rng(11)      # the same seven terms in every set
+        return [fused_term(0, n, r, value, 0, per_p=1, per_x=0, scale=1.0, slot=0, per_p1=0),
+                fused_term(0, n, r, value, 1, per_p=0, per_x=0, scale=1.0, slot=1),          # an observe: Normal(value, s), y
+                fused_term(0, n, r, value, 4, per_p=0, per_x=0, scale=-1.0, slot=2),         # a prior: Normal(m, s) at the value
+                fused_term(0, n, r, value, 0, per_p=1, per_x=1, scale=0.37, slot=3, per_p1=0),
+                fused_term(0, n, r, value, 1, per_p=0, per_x=1, scale=-2.5, slot=4),
+                fused_term(2, n, r, value, 0, per_x=1, scale=-1.0, slot=5),                  # - log q of an earlier statement
+                fused_term(0, n, r, value, 4, per_p=1, per_x=0, scale=1.0, slot=6, per_p1=0)]
+    sets = {
+        'lean': common() + [fused_term(2, n, rng, value, 0, per_x=0, scale=0.37, slot=7)],
+        'general_poisson': common() + [fused_term(3, n, rng, value, 0, per_p=1, per_x=1, scale=1.0, slot=7)],
+        'general_sigma': common() + [fused_term(0, n, rng, value, 0, per_p=1, per_x=1, scale=1.0, slot=7)],
+        'all_kinds': [fused_term(0, n, rng, value, 0, per_p=1, per_x=1, scale=1.0, slot=0),
+                      fused_term(0, n, rng, value, 2, per_p=0, per_x=1, scale=0.37, slot=1),
+                      fused_term(1, n, rng, value, 1, per_p=1, per_x=1, scale=1.0, slot=2),
+                      fused_term(1, n, rng, value, 4, per_p=1, per_x=0, scale=1.0, slot=3),
+                      fused_term(3, n, rng, value, 4, per_p=1, per_x=0, scale=-1.0, slot=4),
+                      fused_term(4, n, rng, value, 0, per_p=1, per_x=1, scale=-2.5, slot=5),
+                      fused_term(5, n, rng, value, 0, per_p=1, per_x=1, scale=-1.0, slot=6),
+                      fused_term(2, n, rng, value, 4, scale=1.0, slot=7)],
+    }
+    for name in ('lean', 'general_poisson', 'general_sigma'):
+        lean = all(t['kind'] == 2 or (t['kind'] == 0 and not t['flags'] & 2 and t['s1'] == 0) for t in sets[name])
+        assert lean == (name == 'lean'), name      # pp_is_fused's own rule for the LEAN instantiation
+        assert sum(not (t['kind'] == 2 or (t['kind'] == 0 and not t['flags'] & 2 and t['s1'] == 0)) for t in sets[name]) <= 1
+    return sets
+
+
+def fused_term_refs(terms, value):
+    """Float64 log-density of every term at every particle: oracle_ops._term (the CPU stand-in's restatement on the oracle) on the
+    fp32 inputs, the flagged arguments replaced by the particles' values. Asserts the out-of-support bookkeeping: the
+    reference is -inf exactly at the planted particles and finite everywhere else."""
+    import torch
+    import oracle_ops
+    n = len(value)
+    tv = torch.from_numpy(value)
+    refs = []
+    for t in terms:
+        f = t['flags']
+        a0, s0 = (tv, 1) if f & 1 else (None if t['p0'] is None else torch.from_numpy(t['p0']), t['s0'])
+        a1, s1 = (tv, 1) if f & 2 else (None if t['p1'] is None else torch.from_numpy(t['p1']), t['s1'])
+        xx = tv if f & 4 else torch.from_numpy(t['x'])
+        with np.errstate(divide='ignore'):
+            r = np.asarray(oracle_ops._term(t['kind'], a0, s0, a1, s1, xx, n), np.float64).reshape(n)
+        assert np.array_equal(np.isneginf(r), t['out']), (t['label'], np.nonzero(np.isneginf(r) != t['out'])[0][:8])
+        assert np.isfinite(r[~t['out']]).all(), t['label']
+        refs.append(r)
+    return refs
+
+
+def fused_sum_ref(terms, value, lw0, overwrite):
+    """(float64 log-weight, tolerance) per particle: lw0 (unless overwritten) + sum_t scale_t ref_t, the tolerance of a sum =
+    sum_t |scale_t| x the per-term tolerance tol_t (1 + |ref_t|) (non-finite terms add none: their pattern is compared)."""
+    n = len(value)
+    ref = np.zeros(n) if overwrite else lw0.astype(np.float64)
+    tol = np.zeros(n)
+    for t, r in zip(terms, fused_term_refs(terms, value)):
+        with np.errstate(invalid='ignore'):
+            ref = ref + t['scale'] * r
+        tol += abs(t['scale']) * FUSED_TERM_TOL[t['kind']] * (1.0 + np.where(np.isfinite(r), np.abs(r), 0.0))
+    assert not np.isnan(ref).any()
+    return ref, tol
+
+
+def _t(a, dev):
+    import torch
+    return None if a is None else torch.tensor(a, dtype=torch.float32, device=dev)
+
+
+def fused_device_terms(terms, dev):
+    """The host terms as ISRunner.fused reads them: [((kind, p0, s0, p1, s1), x, scale, flags)] on `dev`."""
+    return [((t['kind'], _t(t['p0'], dev), t['s0'], _t(t['p1'], dev), t['s1']), _t(t['x'], dev), t['scale'], t['flags']) for t in terms]
+
+
+def run_fused_terms(run, terms, value, lw0, overwrite):
+    """pp_is_fused with the values given (no draw): returns the log-weights; the values must come back bit-unchanged."""
+    n = len(value)
+    run.begin(n)
+    tv, tl = _t(value, run.dev), _t(lw0, run.dev)
+    run.fused(None, None, fused_device_terms(terms, run.dev), tv, tl, overwrite)
+    assert np.array_equal(tv.cpu().numpy().view(np.uint32), value.view(np.uint32))
+    return tl.cpu().numpy()
+
+
+def run_per_term_kernels(run, terms, value, lw0, overwrite):
+    """The same terms through pp_logweight_terms in calls of at most four (it has no flag word: the value vector is passed
+    where a flag says so)."""
+    tv, tl = _t(value, run.dev), _t(lw0, run.dev)
+    for lo in range(0, len(terms), 4):
+        items = []
+        for t in terms[lo:lo + 4]:
+            f = t['flags']
+            p0, s0 = (tv, 1) if f & 1 else (_t(t['p0'], run.dev), t['s0'])
+            p1, s1 = (tv, 1) if f & 2 else (_t(t['p1'], run.dev), t['s1'])
+            items.append(((t['kind'], p0, s0, p1, s1), tv if f & 4 else _t(t['x'], run.dev), t['scale']))
+        run.accumulate_terms(tl, items, overwrite=overwrite and lo == 0)
+    return tl.cpu().numpy()
+
+
+def check_fused_terms(run, terms, value, rng, label=''):
+    """One call of pp_is_fused (values given) with `terms`, overwriting and accumulating onto a random lw, against the float64
+    sum of the terms and against the per-term kernels (rtol = atol = 1e-5, tests/test_gpu_is_fused.py). Infinite results must
+    sit exactly where the reference has them."""
+    n = len(value)
+    lw0 = (3.0 * rng.standard_normal(n)).astype(np.float32)
+    for overwrite in (True, False):
+        ref, tol = fused_sum_ref(terms, value, lw0, overwrite)
+        got = run_fused_terms(run, terms, value, lw0, overwrite)
+        what = (label, [t['label'] for t in terms], 'overwrite' if overwrite else 'accumulate')
+        assert np.array_equal(np.isneginf(got), np.isneginf(ref)) and np.array_equal(np.isposinf(got), np.isposinf(ref)), what
+        assert not np.isnan(got).any(), what
+        ok = np.isfinite(ref)
+        err = np.abs(got[ok].astype(np.float64) - ref[ok])
+        assert (err <= tol[ok]).all(), what + (float((err / tol[ok]).max()), int(np.nonzero(ok)[0][(err / tol[ok]).argmax()]))
+        per_term = run_per_term_kernels(run, terms, value, lw0, overwrite)
+        assert np.array_equal(np.isneginf(per_term), np.isneginf(ref)) and np.array_equal(np.isposinf(per_term), np.isposinf(ref)), what
+        np.testing.assert_allclose(got[ok], per_term[ok], rtol=1e-5, atol=1e-5, err_msg=str(what))

@@ -288,7 +288,11 @@ def _term(kind, p0, s0, p1, s1, x, n):
         C = s1
         probs = p0.numpy().astype(DT).reshape(-1, C)
         probs = np.tile(probs[:1], (n, 1)) if s0 == 0 else probs[:n]
-        return O.categorical_log_prob(xv, probs)
+        idx = xv.astype(np.int64)               # the index is the truncated value; outside [0, C): -inf (term_log_prob)
+        bad = (idx < 0) | (idx >= C)
+        lp = np.asarray(O.categorical_log_prob(np.where(bad, 0, idx), probs), DT).copy()
+        lp[bad] = -np.inf
+        return lp
     a = col(p0, s0)
     if kind == 3:
         return O.poisson_log_prob(xv, a)

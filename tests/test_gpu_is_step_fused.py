@@ -8,16 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from helpers import IS_ADDRS as ADDRS, IS_EMB as EMB, is_engine as _engine
 from oracle import ic_oracle as O
 from pyprob_amd import lib as L
-from pyprob_amd.spec import NetSpec
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
-
-EMB = {'obs0': {'dim': 32}, 'obs1': {'dim': 32}}
-ADDRS = [('a_normal', 'Normal', None), ('a_uniform', 'Uniform', None), ('a_cat', 'Categorical', 7), ('a_poisson', 'Poisson', None),
-         ('a_bern', 'Bernoulli', None)]
 
 
 @pytest.fixture(autouse=True, params=['2', '3'], ids=['one_kernel', 'split'])
@@ -32,24 +28,6 @@ def _force_fused(monkeypatch, request):
 def _addrs(ncat=7):
     """ADDRS with a Categorical(ncat) head at a_cat."""
     return [(a, d, ncat if d == 'Categorical' else c) for a, d, c in ADDRS]
-
-
-def _engine(H, seed=0, depth=1, emb=None, K=10, addrs=ADDRS):
-    from pyprob_amd.engine import ICEngine
-    from pyprob_amd.is_engine import ISRunner
-    spec = NetSpec(emb or EMB, lstm_dim=H, lstm_depth=depth, proposal_mixture_components=K)
-    eng = ICEngine(spec, device='cuda:0', seed=seed)
-    eng.add_addresses(addrs)
-    rng = np.random.default_rng(seed + 1)
-    # trained-looking weights: larger than the default initialisation so that gates and mixtures are not near-uniform
-    sd = {k: (v.numpy() * (3.0 if ('lstm' in k or 'proposal' in k) else 1.0)).astype(np.float32) for k, v in eng.state_dict().items()}
-    for k in sd:
-        if k.endswith('bias') or 'bias_' in k:
-            sd[k] = (sd[k] + 0.1 * rng.standard_normal(sd[k].shape)).astype(np.float32)
-    eng.load_state_dict(sd)
-    run = ISRunner(eng)
-    run.init([8.0, 9.0])
-    return eng, run, sd
 
 
 def _oracle_statement(sd, H, observe, prev, cur, prev_val, h0, c0, values, prior, depth=1, emb=None, K=10, addrs=ADDRS):

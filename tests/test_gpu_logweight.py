@@ -151,33 +151,103 @@ def _score_in_groups(case, eng, isr, addresses):
         np.testing.assert_allclose(lw.cpu().numpy(), isr['lw'][members], rtol=1e-4, atol=1e-4)
 
 
+STAT_TILE, STAT_BLOCKS = 256 * 16, 256      # is_kernels.hip: particles per tile (256 x STAT_PER_THREAD), workgroups at most
+
+
+def _check_stats(run, lw, x, what):
+    """pp_is_stats on (lw, x) against the float64 definitions: ess and mean 1e-9 relative, var 1e-7, max and count exact."""
+    st = run.stats(torch.tensor(lw, device=run.dev), None if x is None else torch.tensor(x, device=run.dev))
+    ok = np.isfinite(lw)
+    assert st['count'] == ok.sum(), what
+    if not ok.any():
+        assert st['max_lw'] == -np.inf and st['sum_w'] == 0.0 and st['sum_w2'] == 0.0 and st['ess'] == 0.0, (what, st)
+        return st
+    l64 = lw[ok].astype(np.float64)
+    x64 = np.zeros(ok.sum()) if x is None else x[ok].astype(np.float64)
+    ess = O.effective_sample_size(l64)
+    w = np.exp(l64 - O.logsumexp(l64, axis=0))
+    mean = float((w * x64).sum())
+    var = float((w * x64 * x64).sum() - mean * mean)
+    assert abs(st['ess'] - ess) <= 1e-9 * ess, (what, st['ess'], ess)
+    assert abs(st['mean'] - mean) <= 1e-9 * abs(mean), (what, st['mean'], mean)
+    assert abs(st['var'] - var) <= 1e-7 * max(var, 1e-12) + 1e-12, (what, st['var'], var)
+    assert abs(st['max_lw'] - l64.max()) == 0.0, what
+    assert np.isfinite(st['sum_w']) and np.isfinite(st['sum_w2']), what
+    return st
+
+
 def test_importance_statistics_match_float64_oracle():
     """pp_is_stats (Empirical.finalize / expectation / effective_sample_size, empirical.py:298-309, 451-466, 758-766)
     against the float64 definitions on the same log-weights: ESS = 1 / sum softmax(lw)^2 (util.py:398-399), weighted
-    mean and variance."""
+    mean and variance. One sweep of the grid covers STAT_BLOCKS x STAT_TILE = 2^20 particles: the sizes from 2^20 + 1 on give a
+    workgroup several tiles - the running maximum of a workgroup then rises (or not) from tile to tile, a tile or a whole
+    workgroup may hold no finite weight."""
     from pyprob_amd.engine import ICEngine   # noqa: F401  (loads the library)
     from pyprob_amd.is_engine import ISRunner
     meta, params, batch, loss, isr = load_golden('gum')
     run = ISRunner(engine_from_golden(meta, params))
     rng = np.random.default_rng(3)
-    for n in (1, 7, 4096, 300001):
+    assert STAT_TILE * STAT_BLOCKS == 2 ** 20
+    for n in (1, 7, 4096, 300001, 2 ** 20, 2 ** 20 + 1, 3 * 2 ** 20 + 5):
         lw = (rng.standard_normal(n) * 3.0 - 40.0).astype(np.float32)
         x = rng.standard_normal(n).astype(np.float32) + 7.0
         if n > 16:
             lw[5] = -np.inf       # dropped like Model._traces drops them (model.py:64-66)
             lw[11] = np.nan
-        st = run.stats(torch.tensor(lw, device=run.dev), torch.tensor(x, device=run.dev))
-        ok = np.isfinite(lw)
-        l64, x64 = lw[ok].astype(np.float64), x[ok].astype(np.float64)
-        ess = O.effective_sample_size(l64)
-        w = np.exp(l64 - O.logsumexp(l64, axis=0))
-        mean = float((w * x64).sum())
-        var = float((w * x64 * x64).sum() - mean * mean)
-        assert st['count'] == ok.sum()
-        assert abs(st['ess'] - ess) <= 1e-9 * ess, (n, st['ess'], ess)
-        assert abs(st['mean'] - mean) <= 1e-9 * abs(mean), (n, st['mean'], mean)
-        assert abs(st['var'] - var) <= 1e-7 * max(var, 1e-12) + 1e-12, (n, st['var'], var)
-        assert abs(st['max_lw'] - l64.max()) == 0.0
+        _check_stats(run, lw, x, (n, 'random'))
+        if n < 2 ** 20:
+            continue
+        tile = np.arange(n) // STAT_TILE
+        sweep, group = tile // STAT_BLOCKS, tile % STAT_BLOCKS
+        n_sweeps = int(sweep.max()) + 1
+        # tile maxima ascending in sweep order: a workgroup's later tiles carry weights 50 to 700 higher than its earlier ones
+        # (every tile rescales what the workgroup has accumulated); descending: no tile after the first one does
+        shift = np.array([0.0, 50.0, 300.0, 700.0], np.float32)
+        _check_stats(run, lw + shift[sweep], x, (n, 'ascending'))
+        _check_stats(run, lw + shift[n_sweeps - 1 - sweep], x, (n, 'descending'))
+        # ... and by a few units, so that the rescaled earlier tiles still carry weight at the 1e-9 bar
+        _check_stats(run, lw + np.float32(1.5) * sweep.astype(np.float32), x, (n, 'ascending, small steps'))
+        _check_stats(run, lw - np.float32(1.5) * sweep.astype(np.float32), x, (n, 'descending, small steps'))
+        if n_sweeps > 1:          # a whole tile of a second sweep without a finite weight
+            b = STAT_BLOCKS + 3 if n >= (STAT_BLOCKS + 4) * STAT_TILE else STAT_BLOCKS
+            hole = lw.copy()
+            hole[tile == b] = np.where(np.arange((tile == b).sum()) % 2 == 0, -np.inf, np.nan)
+            st = _check_stats(run, hole, x, (n, 'tile %d non-finite' % b))
+            assert st['count'] == np.isfinite(hole).sum() < np.isfinite(lw).sum()
+        dead = lw.copy()          # a workgroup whose every tile is non-finite
+        dead[group == 5] = -np.inf
+        _check_stats(run, dead, x, (n, 'workgroup 5 non-finite'))
+        nothing = np.where(np.arange(n) % 3 == 0, np.nan, np.where(np.arange(n) % 3 == 1, -np.inf, np.inf)).astype(np.float32)
+        st = _check_stats(run, nothing, x, (n, 'all non-finite'))
+        assert st['count'] == 0 and st['max_lw'] == -np.inf and not np.isnan(st['sum_w'])
+        st = _check_stats(run, lw + np.float32(1.5) * sweep.astype(np.float32), None, (n, 'x = None'))
+        assert st['mean'] == 0.0 and st['var'] == 0.0
+
+
+@pytest.mark.parametrize('n', [1, 257, 100003])
+def test_axpy_against_numpy(n):
+    """pp_axpy: lw += scale * term with a negative scale. The compiler contracts the kernel's `lw[i] += scale * t[i]` into a fused
+    multiply-add (v_fmac_f32 in the gfx950 code object: one rounding instead of two), so the result is not the fp32 expression
+    lw + float32(scale) * term bit for bit: it differs from it by the rounding of the product - at most one ulp of the larger
+    of |lw|, |scale * term| and the result (the larger operand's ulp where the sum cancels) - and lies within one ulp of the
+    exact sum."""
+    from pyprob_amd import lib as L
+    lib = L.load()
+    rng = np.random.default_rng(n)
+    lw = (3.0 * rng.standard_normal(n)).astype(np.float32)
+    term = (5.0 * rng.standard_normal(n)).astype(np.float32)
+    scale = np.float32(-0.7)
+    d_lw, d_term = torch.tensor(lw, device='cuda:0'), torch.tensor(term, device='cuda:0')
+    L.check(lib.pp_axpy(float(scale), d_term.data_ptr(), d_lw.data_ptr(), n, L.stream_ptr()), 'pp_axpy')
+    got = d_lw.cpu().numpy()
+    prod = scale * term
+    ref = lw + prod
+    assert ref.dtype == np.float32
+    ulp = np.spacing(np.maximum(np.maximum(np.abs(lw), np.abs(prod)), np.abs(ref)))
+    assert (np.abs(got.astype(np.float64) - ref.astype(np.float64)) <= ulp).all()
+    exact = lw.astype(np.float64) + float(scale) * term.astype(np.float64)      # (the product of two fp32 numbers is exact in fp64)
+    assert (np.abs(got.astype(np.float64) - exact) <= ulp).all()
+    assert np.array_equal(d_term.cpu().numpy(), term)
 
 
 def test_prior_log_prob_kernels_against_oracle():
