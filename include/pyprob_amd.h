@@ -110,7 +110,40 @@ typedef struct pp_net {
      * layer l of observable o is obs_w[o][l] / obs_b[o][l] (_layers_observe_embedding.<name>._layers.<l>). */
     int32_t obs_depth[PP_MAX_OBS];
     int64_t obs_w[PP_MAX_OBS][PP_MAX_OBS_DEPTH], obs_b[PP_MAX_OBS][PP_MAX_OBS_DEPTH];
+    /* ObserveEmbedding.CNN2D5C (EmbeddingCNN2D5C, pyprob/nn/embedding_cnn_2d_5c.py; inference_network.py:119-120). Added
+     * without a new ABI number: the fields trail the struct and zero means what the struct meant before.
+     * obs_kind[o] = 0 is read as FEEDFORWARD (everything above). obs_kind[o] = PP_OBS_CNN2D5C: the observable is an image
+     * obs_shape[o] = [C, H, W] (C in 1..4, H and W >= 20) of obs_in[o] = C*H*W floats in (c, y, x) order; five 3x3
+     * convolutions obs_conv_w[o][l] ([Cout, Cin, 3, 3], _conv<l+1>.weight) / obs_conv_b[o][l] with two 2x2 max-pools
+     * give obs_feat[o] = 128 * h5 * w5 features, flattened in (c, y, x) order; _lin1 [dim, F] / _lin2 [dim, dim] are
+     * obs_w[o][0..1] / obs_b[o][0..1] with obs_depth[o] = 2 and obs_hid[o] = obs_out[o] = dim. */
+    int32_t obs_kind[PP_MAX_OBS];
+    int32_t obs_shape[PP_MAX_OBS][3];
+    int32_t obs_feat[PP_MAX_OBS];
+    int32_t _pad3;
+    int64_t obs_conv_w[PP_MAX_OBS][5], obs_conv_b[PP_MAX_OBS][5];
 } pp_net;
+
+#define PP_OBS_FEEDFORWARD 0
+#define PP_OBS_CNN2D5C     1
+#define PP_PROF_CNN_FWD 32   /* kernel classes of the in-stream timing (pp_prof_arm below) */
+#define PP_PROF_CNN_BWD 48
+
+/* ------------------------------------------------------------------------------------------------------
+ * The convolution stack of a CNN2D5C observable on its own (csrc/cnn2d.hip), for tests and timing. It replaces
+ * EmbeddingCNN2D5C.forward up to the flatten (pyprob/nn/embedding_cnn_2d_5c.py:32-44: conv1 .. conv5 with ReLU, two
+ * max-pools, view(batch, -1)) and autograd's backward through the same lines; _lin1 / _lin2 are ordinary linear layers.
+ * x: dev [n_images, C*H*W]; features_out: dev [n_images, F]. The workspace (pp_cnn2d5c_workspace_bytes, 256-byte
+ * aligned) keeps the activations: pp_cnn2d5c_backward must follow a pp_cnn2d5c_forward with the same net, o, params,
+ * n_images and workspace. d_features: dev [n_images, F]; the gradients of conv1 .. conv5 (weights in the reference's
+ * [Cout, Cin, 3, 3]) are ADDED to `grads` (flat buffer laid out like params). flags must be 0. The split-K partial
+ * weight gradients are stored and added in a fixed order: results are bit-identical from run to run in every mode.
+ * ---------------------------------------------------------------------------------------------------- */
+size_t pp_cnn2d5c_workspace_bytes(const pp_net* net, int32_t o, int32_t n_images);
+int pp_cnn2d5c_forward(const pp_net* net, int32_t o, const float* params, const float* x, int32_t n_images,
+                       float* features_out, void* workspace, size_t workspace_bytes, void* stream);
+int pp_cnn2d5c_backward(const pp_net* net, int32_t o, const float* params, const float* d_features, int32_t n_images,
+                        float* grads, void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
 
 /* columns of the device address table */
 #define PP_ADDR_TABLE_COLS 8
@@ -636,6 +669,9 @@ int pp_head_logprob(int32_t kind, const float* y, int64_t ldy, const int32_t* ro
  *                                                                    product and both head layers per particle)
  *   6  the device chain of a posterior call's first statement: every launch from pp_is_init to the end of pp_is_fused
  *      (observe embedding, the one-row network, the pass over the particles with its statistics)   work = 0
+ *   PP_PROF_CNN_FWD + k, k = 0..7: the launches of pp_cnn2d5c_forward (weight images, conv1, conv2, pool 1, conv3, conv4,
+ *      conv5, pool 2); PP_PROF_CNN_BWD + k, k = 0..10: those of pp_cnn2d5c_backward (pool 2, dW5, dZ4, dW4, dZ3, dW3, dP1,
+ *      pool 1, dW2, dZ1, dW1; a dW class covers the split-K launch and its reduction). work = FLOPs executed (0: a copy)
  * pp_prof_collect returns the elapsed milliseconds and the work of every recorded launch (flops_out).
  * ---------------------------------------------------------------------------------------------------- */
 /* Host-side plan of the streaming weight-gradient launch (csrc/wgrad_t1.hip) for `count` queued products dW += A^T B (both

@@ -13,6 +13,10 @@ def __getattr__(name):
         value = getattr(state, name)
         globals()[name] = value          # (resolved once: `pyprob.sample(...)` in a program runs per statement and per path)
         return value
+    if name == 'ObserveEmbedding':
+        from .spec import ObserveEmbedding
+        globals()[name] = ObserveEmbedding
+        return ObserveEmbedding
     if name == 'Model':
         from .model import Model
         globals()[name] = Model

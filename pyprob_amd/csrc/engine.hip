@@ -6,6 +6,7 @@
 #include "panel.hpp"
 #include "panel16.hpp"
 #include "wgrad_t1.hpp"
+#include "cnn2d.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -157,6 +158,10 @@ struct Workspace {
     bool compact;              // LSTM input rows are [E | s_prev] (i4 = round4(e_obs + smp_dim)), the table columns a bias
     int xc;                    // columns of an LSTM input row: e_obs + smp_dim (compact) or lstm_in
     int64_t e4, i4, hid4, out4, ohid4[PP_MAX_OBS], maxohid4;
+    // CNN2D5C observables (cnn2d.hip): features [B, f4] in front of _lin1, their gradient, the convolution stack's workspace
+    // (saved activations, gradient ping-pong, weight images, split-K partials)
+    float* cnn_feat[PP_MAX_OBS]; float* cnn_dfeat[PP_MAX_OBS]; void* cnn_ws[PP_MAX_OBS]; size_t cnn_ws_bytes[PP_MAX_OBS];
+    int64_t f4[PP_MAX_OBS];
     size_t bytes;
 };
 
@@ -258,6 +263,16 @@ static void carve(const pp_net* net, int B, int R, void* p, size_t cap, Workspac
         panel16_image_sizes(H, hid, net->e_obs, w.p16.frags);
         for (int i = 0; i < 6; ++i) w.p16.img[i] = c.take<float>(w.p16.frags[i] * 256);
     }
+    for (int o = 0; o < PP_MAX_OBS; ++o) {      // (last: a network without an image observable is carved as before)
+        w.cnn_feat[o] = w.cnn_dfeat[o] = nullptr; w.cnn_ws[o] = nullptr; w.cnn_ws_bytes[o] = 0; w.f4[o] = 0;
+        if (o < net->n_obs && net->obs_kind[o] == PP_OBS_CNN2D5C) {
+            w.f4[o] = round4(net->obs_feat[o]);
+            w.cnn_feat[o] = c.take<float>((int64_t)B * w.f4[o]);
+            w.cnn_dfeat[o] = c.take<float>((int64_t)B * w.f4[o]);
+            w.cnn_ws_bytes[o] = cnn_workspace_bytes(net, o, B);
+            w.cnn_ws[o] = c.take<char>((int64_t)w.cnn_ws_bytes[o]);
+        }
+    }
     w.bytes = c.off + 256;
 }
 
@@ -273,6 +288,15 @@ static int check_net(const pp_net* net) {
     }
     PP_CHECK_ARG(net->n_addr == 0 || net->addrs, "pp_net: addrs is null");
     PP_CHECK_ARG(net->lstm_depth >= 0 && net->lstm_depth <= PP_MAX_LSTM_DEPTH, "pp_net: lstm_depth %d out of range", net->lstm_depth);
+    for (int o = 0; o < net->n_obs; ++o) {
+        if (net->obs_kind[o] == PP_OBS_FEEDFORWARD) continue;
+        CnnGeom g;
+        PP_CHECK_ARG(net->obs_kind[o] == PP_OBS_CNN2D5C && cnn_geom(net, o, g) && g.F == net->obs_feat[o] &&
+                         net->obs_in[o] == g.C * g.H * g.W && net->obs_depth[o] == 2,
+                     "pp_net: observable %d: not a valid CNN2D5C description (kind %d, shape [%d, %d, %d], obs_feat %d, obs_in %d)", o,
+                     net->obs_kind[o], net->obs_shape[o][0], net->obs_shape[o][1], net->obs_shape[o][2], net->obs_feat[o],
+                     net->obs_in[o]);
+    }
     return 0;
 }
 
@@ -351,7 +375,7 @@ static int linear_dgrad(const float* dz, int64_t lddz, const float* W, float* dx
 }
 
 static int observe_embedding_fwd(const pp_net* net, const float* P, const float* obs, int64_t ldobs, int B, Workspace& w,
-                                 hipStream_t st) {
+                                 hipStream_t st, bool bwd = true) {
     if (obs_fused_supported(net))   // small embeddings: one fused launch (obs_embed.hip)
         return obs_embed_fwd_fused(net, P, obs, B, w.obs_h, w.cat, w.f1, w.E, st);
     int ci = 0, co = 0;
@@ -361,6 +385,11 @@ static int observe_embedding_fwd(const pp_net* net, const float* P, const float*
         const float* x = obs + ci;
         int64_t ldx = ldobs;
         int in = net->obs_in[o];
+        if (net->obs_kind[o] == PP_OBS_CNN2D5C) {
+            // EmbeddingCNN2D5C (embedding_cnn_2d_5c.py:32-44): the convolution stack, then _lin1 / _lin2 read its features
+            PP_TRY(cnn_forward(net, o, P, x, ldx, B, w.cnn_feat[o], w.f4[o], w.cnn_ws[o], w.cnn_ws_bytes[o], bwd, st));
+            x = w.cnn_feat[o]; ldx = w.f4[o]; in = net->obs_feat[o];
+        }
         for (int l = 0; l < depth; ++l) {
             const bool last = l == depth - 1;
             const int out = last ? net->obs_out[o] : net->obs_hid[o];
@@ -486,7 +515,7 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
             rb.n_small = n_clear;
             PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb));
         } else {
-            PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st));
+            PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, bwd));
         }
         if (in_place) {
             heads_in = w.E;
@@ -528,7 +557,7 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
         PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb, compact ? &abias : nullptr,
                                    panel ? &ptr : nullptr));
     } else {
-        PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st));
+        PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, bwd));
         // (also clears the loss slots and, for a backward pass, dX: see the kernel)
         PP_TRY(lstm_input_gather(net, P, w.E, w.e4, bt->trace, bt->value, bt->addr, bt->prev_row, -1, -1, R, w.X, w.i4, st,
                                  bwd ? w.dX : nullptr, reinterpret_cast<float*>(w.loss_acc), n_clear, w.xc,
@@ -1045,10 +1074,11 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
         int64_t lddz = w.e4;
         float* scratch[2] = {w.dObsH, w.dObsH2};
         for (int l = depth - 1; l >= 0; --l) {
+            const bool cnn = net->obs_kind[o] == PP_OBS_CNN2D5C;      // layer 0 (_lin1) reads the convolution stack's features
             const int out = l == depth - 1 ? net->obs_out[o] : net->obs_hid[o];
-            const int in = l == 0 ? net->obs_in[o] : net->obs_hid[o];
-            const float* x = l == 0 ? bt->obs + ci : w.obs_hl[o][l - 1];
-            const int64_t ldx = l == 0 ? bt->obs_width : w.ohid4[o];
+            const int in = l == 0 ? (cnn ? net->obs_feat[o] : net->obs_in[o]) : net->obs_hid[o];
+            const float* x = l == 0 ? (cnn ? w.cnn_feat[o] : bt->obs + ci) : w.obs_hl[o][l - 1];
+            const int64_t ldx = l == 0 ? (cnn ? w.f4[o] : bt->obs_width) : w.ohid4[o];
             const int64_t wl = net->obs_depth[o] ? net->obs_w[o][l] : (l == 0 ? net->obs_w0[o] : net->obs_w1[o]);
             const int64_t bl = net->obs_depth[o] ? net->obs_b[o][l] : (l == 0 ? net->obs_b0[o] : net->obs_b1[o]);
             PP_TRY(linear_wgrad(dz, lddz, x, ldx, nullptr, grads + wl, grads + bl, nullptr, B, in, out, st));
@@ -1057,6 +1087,11 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
                 PP_TRY(linear_dgrad(dz, lddz, P + wl, dprev, w.ohid4[o], nullptr, x, ldx, B, in, out, false, st));
                 dz = dprev;
                 lddz = w.ohid4[o];
+            } else if (cnn) {
+                // the image is data, its features are not: dFeatures = dz W_lin1 (no mask here: the pool backward applies
+                // conv5's), then back through the stack
+                PP_TRY(linear_dgrad(dz, lddz, P + wl, w.cnn_dfeat[o], w.f4[o], nullptr, nullptr, 0, B, in, out, false, st));
+                PP_TRY(cnn_backward(net, o, w.cnn_dfeat[o], w.f4[o], B, grads, w.cnn_ws[o], w.cnn_ws_bytes[o], st));
             }
         }
         ci += net->obs_in[o];

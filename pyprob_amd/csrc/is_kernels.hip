@@ -7,6 +7,7 @@
 #include "is_draw.hpp"
 #include "is_step_fused.hpp"
 #include "obs_embed.hpp"
+#include "cnn2d.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -545,6 +546,9 @@ __global__ __launch_bounds__(256) void first_row_all_kernel(const ObsFusedArgs a
 struct IsWorkspace {
     float *X, *G, *A1, *Y, *rec, *c0;
     float *obs_h, *cat, *f1;
+    float* cnn_feat[PP_MAX_OBS];   // CNN2D5C observables: the [1, F] feature row and the convolution stack's workspace for one image
+    void* cnn_ws[PP_MAX_OBS];
+    size_t cnn_ws_bytes[PP_MAX_OBS];
     int64_t i4, hid4, out4, e4, maxohid4;
     IsFusedBuffers fz;   // operand images of the fused statement kernel (is_step_fused.hip)
     float* ticket;       // arrival counter of first_row_head_kernel (a 32-bit word: zero when the workspace is allocated, left at
@@ -562,6 +566,15 @@ static void is_carve(const pp_net* net, int n, void* p, IsWorkspace& w) {
         return q;
     };
     w.ticket = take(64);   // FIRST: a fixed place whatever n is (the scratch of an n-row call must never run over it)
+    // the image scratch of pp_is_init (one observation per posterior call) next: a fixed place and size whatever n is
+    for (int o = 0; o < PP_MAX_OBS; ++o) {
+        w.cnn_feat[o] = nullptr; w.cnn_ws[o] = nullptr; w.cnn_ws_bytes[o] = 0;
+        if (o < net->n_obs && net->obs_kind[o] == PP_OBS_CNN2D5C) {
+            w.cnn_feat[o] = take(round4(net->obs_feat[o]));
+            w.cnn_ws_bytes[o] = cnn_workspace_bytes(net, o, 1);
+            w.cnn_ws[o] = take((int64_t)(w.cnn_ws_bytes[o] + 3) / 4);
+        }
+    }
     const int H = net->lstm_dim;
     w.i4 = round4(net->lstm_in);
     w.e4 = round4(net->e_obs);
@@ -648,6 +661,10 @@ int is_init(const pp_net* net, const float* P, const float* obs, float* e_out, v
         const float* x = obs + ci;
         int64_t ldx = width;
         int in = net->obs_in[o];
+        if (net->obs_kind[o] == PP_OBS_CNN2D5C) {      // the image goes through the convolution stack; _lin1 / _lin2 read its features
+            PP_TRY(cnn_forward(net, o, P, x, ldx, 1, w.cnn_feat[o], round4(net->obs_feat[o]), w.cnn_ws[o], w.cnn_ws_bytes[o], false, st));
+            x = w.cnn_feat[o]; ldx = round4(net->obs_feat[o]); in = net->obs_feat[o];
+        }
         for (int l = 0; l < depth; ++l) {
             const bool last = l == depth - 1;
             const int out = last ? net->obs_out[o] : net->obs_hid[o];

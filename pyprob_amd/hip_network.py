@@ -58,10 +58,15 @@ class _HipNetworkMixin:
     def _hip_obs_spec(self):
         obs = {}
         for name, layer in self._layers_observe_embedding.items():
+            if type(layer).__name__ == 'EmbeddingCNN2D5C':       # _conv1 .. _conv5, _lin1, _lin2 (embedding_cnn_2d_5c.py)
+                from .spec import ObserveEmbedding
+                obs[name] = dict(reshape=[int(x) for x in layer._input_shape], dim=int(layer._output_dim),
+                                 embedding=ObserveEmbedding.CNN2D5C)
+                continue
             layers = getattr(layer, '_layers', None)
             if type(layer).__name__ != 'EmbeddingFeedForward' or layers is None or not 1 <= len(layers) <= L.PP_MAX_OBS_DEPTH:
-                raise NotImplementedError('the HIP engine embeds observations with ObserveEmbedding.FEEDFORWARD of depth '
-                                          '1..{} (observable {}: {})'.format(L.PP_MAX_OBS_DEPTH, name, type(layer).__name__))
+                raise NotImplementedError('the HIP engine embeds observations with ObserveEmbedding.CNN2D5C or FEEDFORWARD of '
+                                          'depth 1..{} (observable {}: {})'.format(L.PP_MAX_OBS_DEPTH, name, type(layer).__name__))
             obs[name] = dict(input_dim=int(layer._input_dim), dim=int(layer._output_dim), depth=len(layers))
         return obs
 

@@ -14,6 +14,8 @@ PP_MAX_MIXTURE_COMPONENTS = 16    # MAXK of csrc/head_math.hpp: the mixture head
 PP_ADDR_TABLE_COLS = 8
 PP_HEAD_NORMAL_MIXTURE, PP_HEAD_TRUNCNORMAL_MIXTURE, PP_HEAD_CATEGORICAL, PP_HEAD_POISSON_TN_MIXTURE = 0, 1, 2, 3
 PP_HEAD_BERNOULLI = 4
+PP_OBS_FEEDFORWARD, PP_OBS_CNN2D5C = 0, 1
+PP_PROF_CNN_FWD, PP_PROF_CNN_BWD = 32, 48      # pp_prof_arm classes of the CNN2D5C launches
 PP_LOSS_BACKWARD, PP_LOSS_ZERO_GRADS, PP_LOSS_KEEP_LP = 1, 2, 4
 PP_ADAM_ZERO_GRADS = 1
 PP_ADAM_SCRATCH = 1056          # int32 per tensor (include/pyprob_amd.h)
@@ -51,7 +53,11 @@ class pp_net(C.Structure):
                 ('lstm_w_ih', i64 * PP_MAX_LSTM_DEPTH), ('lstm_w_hh', i64 * PP_MAX_LSTM_DEPTH),
                 ('lstm_b_ih', i64 * PP_MAX_LSTM_DEPTH), ('lstm_b_hh', i64 * PP_MAX_LSTM_DEPTH),
                 ('obs_depth', i32 * PP_MAX_OBS),
-                ('obs_w', (i64 * PP_MAX_OBS_DEPTH) * PP_MAX_OBS), ('obs_b', (i64 * PP_MAX_OBS_DEPTH) * PP_MAX_OBS)]
+                ('obs_w', (i64 * PP_MAX_OBS_DEPTH) * PP_MAX_OBS), ('obs_b', (i64 * PP_MAX_OBS_DEPTH) * PP_MAX_OBS),
+                # CNN2D5C observables (zero = FEEDFORWARD, the struct as it was)
+                ('obs_kind', i32 * PP_MAX_OBS), ('obs_shape', (i32 * 3) * PP_MAX_OBS), ('obs_feat', i32 * PP_MAX_OBS),
+                ('_pad3', i32),
+                ('obs_conv_w', (i64 * 5) * PP_MAX_OBS), ('obs_conv_b', (i64 * 5) * PP_MAX_OBS)]
 
 
 class pp_batch(C.Structure):
@@ -121,6 +127,9 @@ PROTOTYPES = {
     'pp_pack_indexed': (C.c_int, [vp, i32, vp, vp, i32, i32, i32, vp, i64, vp]),
     'pp_pack_words': (i64, [i32, i64, i32, i32, i32]),
     'pp_pack_ragged': (C.c_int, [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, i64, vp]),
+    'pp_cnn2d5c_workspace_bytes': (C.c_size_t, [C.POINTER(pp_net), i32, i32]),
+    'pp_cnn2d5c_forward': (C.c_int, [C.POINTER(pp_net), i32, vp, vp, i32, vp, vp, C.c_size_t, vp]),
+    'pp_cnn2d5c_backward': (C.c_int, [C.POINTER(pp_net), i32, vp, vp, i32, vp, vp, C.c_size_t, i32, vp]),
     'pp_abi_version': (C.c_int, []),
     'pp_last_error': (C.c_char_p, []),
     'pp_device_count': (C.c_int, []),

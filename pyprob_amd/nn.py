@@ -87,7 +87,8 @@ class ProposalSample:
 
 
 class InferenceNetworkLSTM:
-    # observe_embeddings example: {'obs1': {'dim': 32}}   (FEEDFORWARD, depth 2)
+    # observe_embeddings example: {'obs1': {'dim': 32}} (FEEDFORWARD, depth 2);
+    # {'img': {'dim': 32, 'reshape': [1, 28, 28], 'embedding': ObserveEmbedding.CNN2D5C}}
     _network = 'lstm'           # NetSpec(network=...): 'lstm' | 'feedforward' (class InferenceNetworkFeedForward below)
     _engine_factory = ICEngine  # (spec, device=, seed=) -> engine; the CPU tests of the training loop put buffers on the host
 
@@ -134,7 +135,8 @@ class InferenceNetworkLSTM:
 
     # ---- layer creation ------------------------------------------------------------------------------------
     def _init_layers_observe_embedding(self, observe_embeddings, example_trace):
-        """inference_network.py:80-130 for FEEDFORWARD embeddings: input width from the example trace."""
+        """inference_network.py:80-130: the input width (FEEDFORWARD) or shape (CNN2D5C without 'reshape') from the example
+        trace; 'embedding' / 'reshape' / 'depth' / 'dim' go to NetSpec as given."""
         if len(observe_embeddings) == 0:
             raise ValueError('At least one observe embedding is needed to initialize inference network.')
         if isinstance(observe_embeddings, set):
@@ -144,6 +146,8 @@ class InferenceNetworkLSTM:
             v = dict(value)
             variable = example_trace.named_variables[name]
             v['input_dim'] = int(np.prod(v['reshape'])) if 'reshape' in v else int(torch.as_tensor(variable.value).numel())
+            if 'reshape' not in v:      # "reshape not specified, using shape ..." (inference_network.py:96-97): what CNN2D5C reads
+                v['shape'] = [int(x) for x in torch.as_tensor(variable.value).shape]
             if 'dim' not in v:
                 print('Observable {}: embedding dim not specified, using the default 256.'.format(name))
             obs[name] = v

@@ -8,6 +8,7 @@ checkpoints interchange. Every tensor lives in ONE flat fp32 buffer (padded to 1
 gradient all-reduce and the Adam update are single kernels over contiguous HBM.
 """
 import ctypes as C
+import enum
 import math
 from collections import OrderedDict
 
@@ -20,6 +21,19 @@ CHUNK = 1024
 DIST_KIND = {'Normal': L.PP_HEAD_NORMAL_MIXTURE, 'Uniform': L.PP_HEAD_TRUNCNORMAL_MIXTURE,
              'Categorical': L.PP_HEAD_CATEGORICAL, 'Poisson': L.PP_HEAD_POISSON_TN_MIXTURE,
              'Bernoulli': L.PP_HEAD_BERNOULLI}
+
+
+class ObserveEmbedding(enum.Enum):
+    """pyprob.ObserveEmbedding (pyprob/util.py:62-64): the same members and values."""
+    FEEDFORWARD = 0
+    CNN2D5C = 1
+    CNN3D5C = 2
+
+
+def cnn2d5c_feature_shape(shape):
+    """[C, H, W] -> (h5, w5): five valid 3x3 convolutions with 2x2 floor pools after the second and the fifth
+    (embedding_cnn_2d_5c.py:22-30); the flattened feature width is F = 128 * h5 * w5."""
+    return tuple(((int(s) - 4) // 2 - 6) // 2 for s in shape[1:])
 
 
 class AddressInfo:
@@ -46,17 +60,44 @@ class NetSpec:
         self.lstm_depth = 1 if network == 'feedforward' else int(lstm_depth)
         self.network = network
         self.feedforward = network == 'feedforward'
-        # observe_embeddings: ordered {name: {'dim': D, 'input_dim': d_in}}  (FEEDFORWARD, depth 2 only)
+        # observe_embeddings: ordered {name: {'dim': D, 'input_dim': d_in, 'depth': n}} (FEEDFORWARD) or
+        # {name: {'dim': D, 'reshape': [C, H, W], 'embedding': ObserveEmbedding.CNN2D5C}} (inference_network.py:88-123)
         self.obs = []
         self.obs_depth = {}
+        self.obs_kind = {}       # name -> L.PP_OBS_FEEDFORWARD | L.PP_OBS_CNN2D5C
+        self.obs_shape = {}      # CNN2D5C: name -> (C, H, W)
+        self.obs_feat = {}       # CNN2D5C: name -> F, the input width of _lin1
         for name, v in observe_embeddings.items():
+            embedding = v.get('embedding', ObserveEmbedding.FEEDFORWARD)
+            d_out = int(v.get('dim', 256))          # default 256, inference_network.py:103
+            if embedding == ObserveEmbedding.CNN2D5C:
+                # ('depth' is not read for this embedding, inference_network.py:119-120)
+                shape = tuple(int(x) for x in v['reshape']) if 'reshape' in v else tuple(int(x) for x in v.get('shape', ()))
+                if len(shape) != 3:
+                    raise ValueError('Observable %s: CNN2D5C needs a [channels, height, width] shape, got %r' % (name, list(shape)))
+                if not 1 <= shape[0] <= 4:
+                    raise ValueError('Observable %s: CNN2D5C takes 1..4 channels here, got %d' % (name, shape[0]))
+                if min(shape[1:]) < 20:
+                    raise ValueError('Observable %s: CNN2D5C needs height and width >= 20 (five 3x3 convolutions and two '
+                                     'pools leave nothing of a smaller image), got %r' % (name, list(shape)))
+                h5, w5 = cnn2d5c_feature_shape(shape)
+                self.obs.append((name, int(np.prod(shape)), d_out, d_out))
+                self.obs_depth[name] = 2             # _lin1, _lin2
+                self.obs_kind[name] = L.PP_OBS_CNN2D5C
+                self.obs_shape[name] = shape
+                self.obs_feat[name] = 128 * h5 * w5
+                continue
+            if embedding == ObserveEmbedding.CNN3D5C:
+                raise NotImplementedError('ObserveEmbedding.CNN3D5C is not built (DESIGN.md section 7)')
+            if embedding != ObserveEmbedding.FEEDFORWARD:
+                raise ValueError('Unknown embedding: {}'.format(embedding))
             depth = int(v.get('depth', 2))          # default 2, inference_network.py:116
             if not 1 <= depth <= L.PP_MAX_OBS_DEPTH:
                 raise ValueError('observe embedding depth must be 1..%d' % L.PP_MAX_OBS_DEPTH)
-            d_in = int(v.get('input_dim', 1))
-            d_out = int(v.get('dim', 256))          # default 256, inference_network.py:103
+            d_in = int(v['input_dim']) if 'input_dim' in v else int(np.prod(v['reshape'])) if 'reshape' in v else 1
             self.obs.append((name, d_in, int((d_in + d_out) / 2), d_out))
             self.obs_depth[name] = depth
+            self.obs_kind[name] = L.PP_OBS_FEEDFORWARD
         if not self.obs:
             raise ValueError('At least one observe embedding is needed to initialize inference network.')
         if len(self.obs) > L.PP_MAX_OBS:
@@ -81,6 +122,15 @@ class NetSpec:
         self.n_params = 0
         H, I, e = lstm_dim, self.lstm_in, self.e_obs
         for name, d_in, hid, d_out in self.obs:
+            if self.obs_kind[name] == L.PP_OBS_CNN2D5C:                         # embedding_cnn_2d_5c.py:14-21
+                p = '_layers_observe_embedding.%s.' % name
+                chans = (self.obs_shape[name][0], 64, 64, 128, 128, 128)
+                for l in range(5):
+                    self._add(p + '_conv%d.weight' % (l + 1), (chans[l + 1], chans[l], 3, 3))
+                    self._add(p + '_conv%d.bias' % (l + 1), (chans[l + 1],))
+                self._add(p + '_lin1.weight', (d_out, self.obs_feat[name])); self._add(p + '_lin1.bias', (d_out,))
+                self._add(p + '_lin2.weight', (d_out, d_out)); self._add(p + '_lin2.bias', (d_out,))
+                continue
             p = '_layers_observe_embedding.%s._layers.' % name
             for l, (rows, cols) in enumerate(self.obs_layer_shapes(name)):      # embedding_feedforward.py:22-33
                 self._add(p + '%d.weight' % l, (rows, cols)); self._add(p + '%d.bias' % l, (rows,))
@@ -94,9 +144,17 @@ class NetSpec:
                 self._add('_layers_lstm.bias_ih_l%d' % k, (4 * H,)); self._add('_layers_lstm.bias_hh_l%d' % k, (4 * H,))
         self.n_core_tensors = len(self.tensors)
 
+    def obs_layer_names(self, name):
+        """State-dict prefixes of the Linear layers of observable `name`, in the order of obs_layer_shapes."""
+        if self.obs_kind[name] == L.PP_OBS_CNN2D5C:
+            return ['_layers_observe_embedding.%s._lin%d.' % (name, l) for l in (1, 2)]
+        return ['_layers_observe_embedding.%s._layers.%d.' % (name, l) for l in range(self.obs_depth[name])]
+
     def obs_layer_shapes(self, name):
         """[(out, in)] of the Linear layers of observable `name` (EmbeddingFeedForward(num_layers = depth))."""
         _, d_in, hid, d_out = [o for o in self.obs if o[0] == name][0]
+        if self.obs_kind[name] == L.PP_OBS_CNN2D5C:      # _lin1, _lin2 behind the convolution stack
+            return [(d_out, self.obs_feat[name]), (d_out, d_out)]
         depth = self.obs_depth[name]
         if depth == 1:
             return [(d_out, d_in)]
@@ -157,8 +215,8 @@ class NetSpec:
 
     # ---- initial values (PyTorch defaults the reference relies on) --------------------------------------
     def init_tensor(self, name, rng):
-        """nn.Linear / nn.LSTM default init (U(-1/sqrt(fan), 1/sqrt(fan))) and N(0,1) embeddings
-        (inference_network_lstm.py:43,47)."""
+        """nn.Linear / nn.Conv2d / nn.LSTM default init (U(-1/sqrt(fan), 1/sqrt(fan)); a convolution's fan is Cin * 9) and
+        N(0,1) embeddings (inference_network_lstm.py:43,47)."""
         _, shape = self.tensors[name]
         if name.startswith('_layers_address_embedding.') or name.startswith('_layers_distribution_type_embedding.'):
             return rng.standard_normal(shape).astype(np.float32)
@@ -166,10 +224,8 @@ class NetSpec:
             k = 1.0 / math.sqrt(self.lstm_dim)
             return rng.uniform(-k, k, shape).astype(np.float32)
         # Linear: fan_in = weight.shape[1]; the bias uses the same bound
-        if name.endswith('.weight'):
-            fan_in = shape[1]
-        else:
-            fan_in = self.tensors[name[:-len('bias')] + 'weight'][1][1]
+        wshape = shape if name.endswith('.weight') else self.tensors[name[:-len('bias')] + 'weight'][1]
+        fan_in = int(np.prod(wshape[1:]))
         k = 1.0 / math.sqrt(fan_in)
         return rng.uniform(-k, k, shape).astype(np.float32)
 
@@ -250,15 +306,24 @@ class NetSpec:
         net = L.pp_net()
         net.n_obs = len(self.obs)
         for o, (name, d_in, hid, d_out) in enumerate(self.obs):
-            p = '_layers_observe_embedding.%s._layers.' % name
             net.obs_in[o], net.obs_hid[o], net.obs_out[o] = d_in, hid, d_out
             depth = self.obs_depth[name]
             net.obs_depth[o] = depth
+            layers = self.obs_layer_names(name)
             for l in range(depth):
-                net.obs_w[o][l], net.obs_b[o][l] = self.offset(p + '%d.weight' % l), self.offset(p + '%d.bias' % l)
+                net.obs_w[o][l], net.obs_b[o][l] = self.offset(layers[l] + 'weight'), self.offset(layers[l] + 'bias')
             if depth == 2:
-                net.obs_w0[o], net.obs_b0[o] = self.offset(p + '0.weight'), self.offset(p + '0.bias')
-                net.obs_w1[o], net.obs_b1[o] = self.offset(p + '1.weight'), self.offset(p + '1.bias')
+                net.obs_w0[o], net.obs_b0[o] = net.obs_w[o][0], net.obs_b[o][0]
+                net.obs_w1[o], net.obs_b1[o] = net.obs_w[o][1], net.obs_b[o][1]
+            if self.obs_kind[name] == L.PP_OBS_CNN2D5C:
+                net.obs_kind[o] = L.PP_OBS_CNN2D5C
+                net.obs_feat[o] = self.obs_feat[name]
+                p = '_layers_observe_embedding.%s.' % name
+                for k in range(3):
+                    net.obs_shape[o][k] = self.obs_shape[name][k]
+                for l in range(5):
+                    net.obs_conv_w[o][l] = self.offset(p + '_conv%d.weight' % (l + 1))
+                    net.obs_conv_b[o][l] = self.offset(p + '_conv%d.bias' % (l + 1))
         net.e_obs, net.smp_dim, net.addr_dim, net.dtype_dim = self.e_obs, self.smp_dim, self.addr_dim, self.dtype_dim
         p = '_layers_observe_embedding_final._layers.'
         net.fin_w0, net.fin_b0 = self.offset(p + '0.weight'), self.offset(p + '0.bias')

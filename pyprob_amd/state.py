@@ -819,10 +819,27 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
     else:
         v = torch.as_tensor(value, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(ls.runner.dev)
     if v.numel() not in (1, ls.width):
-        # a vector-valued observation (k != n values): the device terms read one value per particle - refuse instead of
-        # scoring element i against particle i (the coroutine executor, lock_step=False, sums vector observes on the host)
-        raise RuntimeError('lock-step importance sampling scores one observed value per particle (or one shared value); '
-                           'got {} values for {} particles - run this program with lock_step=False'.format(v.numel(), ls.width))
+        # A vector-valued observation (an image: k values shared by all particles, the one pp_is_init embedded once for the
+        # call). The device terms read one value per particle, so the observation joins the weights as ONE term per particle:
+        # its log-density summed over the k elements (trace.py:123-125 sums an observed variable's log_prob the same way),
+        # entered like a factor's value (pp_dist kind 2). The parameters are shared ([k] or one element) or per particle
+        # ([n, k]: e.g. a template image selected by a sampled index).
+        ls.observes += 1
+        if ls.observes <= ls.replay_observes:
+            return
+        from .distributions import Factor
+        lp = distribution.log_prob(v.reshape(torch.as_tensor(value).shape))
+        with torch._C.DisableTorchFunctionSubclass():
+            lp = lp.as_subclass(torch.Tensor).to(ls.runner.dev, torch.float32)
+            if lp.numel() == v.numel():
+                x = lp.sum().reshape(1)
+            elif lp.numel() == ls.width * v.numel():
+                x = lp.reshape(ls.width, -1).sum(1).contiguous()
+            else:
+                raise RuntimeError('lock-step importance sampling: an observation of {} values gave {} log-densities for {} '
+                                   'particles - run this program with lock_step=False'.format(v.numel(), lp.numel(), ls.width))
+        _lock_step_term(ls, ls.runner.dist_term(Factor(log_prob=x)), x)
+        return
     ls.observes += 1
     if ls.observes <= ls.replay_observes:
         return
