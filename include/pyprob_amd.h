@@ -599,6 +599,33 @@ int pp_dist_logweight(const pp_dist_term* terms, int32_t count, float* lw /*dev 
 int pp_dist_draw(const pp_dist* d, const int64_t* rows, int32_t m, int32_t n, uint64_t seed, uint64_t offset, uint32_t stream_id,
                  float* out /*dev [n]*/, void* stream);
 
+/* Mixture(distributions, probs) (pyprob/distributions/mixture.py) as a prior or likelihood of a program: K = 1..16 scalar
+ * components (kinds 0, 1, 3, 4, 6-13, families may differ; Factor, Categorical and nested mixtures are not components) and K
+ * unnormalised weights >= 0, one shared row or one row per particle. */
+#define PP_MIX_MAX_COMPONENTS 16
+typedef struct pp_mixture {
+    int32_t count;            /* K, 1..16 */
+    int32_t probs_stride;     /* 0: one shared row of K weights; K: row r at probs + r*K */
+    const float* probs;       /* unnormalised, >= 0 */
+    pp_dist comp[PP_MIX_MAX_COMPONENTS];
+} pp_mixture;
+
+/* Mixture.log_prob (mixture.py:8-16, 38-45; util.clamp_probs) as a log-weight term:
+ *     lp[r] = logsumexp_k( log clamp(w[r,k] / sum_k w[r,k], eps, 1 - eps) + log p_k(x[r]) ),  eps = 2^-23
+ *     lw[r] += scale * lp[r], lp_out[r] = lp[r]   for r = rows[j], j < m, or rows NULL: r < n (m, n, rows as pp_dist_logweight)
+ * The row of weights is summed on the device in index order. -inf when x is outside every component's support; a NaN
+ * parameter gives NaN. lw or lp_out may be NULL (not both). */
+int pp_mix_logweight(const pp_mixture* mix, const float* x, int32_t x_stride, float scale, float* lw /*dev [n]*/, float* lp_out,
+                     const int64_t* rows, int32_t m, int32_t n, void* stream);
+
+/* Mixture.sample (mixture.py:47-63): out[r] ~ component k_r, k_r ~ Categorical(w[r,:]) on the unclamped weights (the rule of
+ * pp_dist_draw kind 5: the first k with u * sum < cumulative weight, else K - 1). The selection uniform is the first word of
+ * Philox(seed, offset + r, stream_id | 0x80000000); the component's draw uses Philox(seed, offset + r, stream_id) - exactly
+ * pp_dist_draw's stream, so a mixture of K = 1 or of K identical components is bit-identical to pp_dist_draw of the family.
+ * stream_id must leave the top bit clear. One launch per distinct kind among the components; rows, m, n as pp_dist_draw. */
+int pp_mix_draw(const pp_mixture* mix, const int64_t* rows, int32_t m, int32_t n, uint64_t seed, uint64_t offset,
+                uint32_t stream_id, float* out /*dev [n]*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Individual kernels (used by the whole-path entry points; exported for unit parity tests and profiling)
  * ---------------------------------------------------------------------------------------------------- */

@@ -34,28 +34,7 @@ __device__ __forceinline__ float dist_log_prob(const DistTerm& d, int64_t r) {
         if (!(x >= 0.0f) || k >= C || (float)k != x) return -INFINITY;
         return logf(fminf(fmaxf(p[k] / sum, kFp32Eps), 1.0f - kFp32Eps));
     }
-    const float a = d.p[0][r * d.s[0]];
-    switch (d.kind) {
-        case 0: return lp_normal(a, d.p[1][r * d.s[1]], x);
-        case 1: {
-            const float b = d.p[1][r * d.s[1]];
-            return (x >= a && x < b) ? -logf(b - a) : -INFINITY;
-        }
-        case 3: return (x >= 0.0f && x == floorf(x)) ? (x == 0.0f ? 0.0f : x * logf(a)) - a - lgammaf(x + 1.0f) : -INFINITY;
-        case 4: {
-            if (!(x == 0.0f || x == 1.0f)) return -INFINITY;
-            const float q = fminf(fmaxf(a, kFp32Eps), 1.0f - kFp32Eps);
-            return x * logf(q) + (1.0f - x) * log1pf(-q);
-        }
-        case 6: return lp_exponential(a, x);
-        case 7: return lp_gamma(a, d.p[1][r * d.s[1]], x);
-        case 8: return lp_beta(a, d.p[1][r * d.s[1]], d.p[2][r * d.s[2]], d.p[3][r * d.s[3]], x);
-        case 9: return lp_lognormal(a, d.p[1][r * d.s[1]], x);
-        case 10: return lp_weibull(a, d.p[1][r * d.s[1]], x);
-        case 11: return lp_binomial(a, d.p[1][r * d.s[1]], x);
-        case 12: return lp_vonmises(a, d.p[1][r * d.s[1]], x);
-        default: return lp_truncnormal(a, d.p[1][r * d.s[1]], d.p[2][r * d.s[2]], d.p[3][r * d.s[3]], x);
-    }
+    return scalar_log_prob(d.kind, d.p, d.s, r, x);
 }
 
 // lw[r] += sum_t scale_t log p_t(x_t[r]); r = rows[j] (rows != NULL) or j; lp_out[r] = the single term's log p
@@ -101,52 +80,8 @@ __global__ __launch_bounds__(256) void dist_draw_kernel(DistTerm d, const int64_
         } else {
             const float a = d.p[0][r * d.s[0]];
             const float b = KIND == 3 || KIND == 4 || KIND == 6 ? 0.0f : d.p[1][r * d.s[1]];
-            uint32_t w[4];
-            switch (KIND) {
-                case 0:
-                    rng.next(w);
-                    v = a + b * sqrtf(-2.0f * logf(u01(w[0]))) * cosf(kTwoPi * u01(w[1]));
-                    break;
-                case 1:
-                    rng.next(w);
-                    v = a + (b - a) * (((float)(w[0] >> 8)) * (1.0f / 16777216.0f));
-                    v = v < b ? v : a;
-                    break;
-                case 3: v = poisson_draw(a, rng); break;
-                case 4:
-                    rng.next(w);
-                    v = u01(w[0]) < a ? 1.0f : 0.0f;
-                    break;
-                case 6:
-                    rng.next(w);
-                    v = -logf(u01(w[0])) / a;
-                    break;
-                case 7: v = (a > 0.0f && b > 0.0f) ? expf(log_gamma_draw(a, rng) - logf(b)) : NAN; break;
-                case 8: {
-                    float y = NAN;
-                    if (a > 0.0f && b > 0.0f) {
-                        const float g1 = log_gamma_draw(a, rng), g0 = log_gamma_draw(b, rng);
-                        // G1 / (G1 + G0) from the logs: the smaller share s = e / (1 + e), e = exp(-|g1 - g0|), stays > 0 down
-                        // to the denormals, and y = 1 - s near 1 is rounded once
-                        const float e = expf(-fabsf(g1 - g0)), s = e / (1.0f + e);
-                        y = g1 >= g0 ? 1.0f - s : s;
-                    }
-                    const float lo = d.p[2][r * d.s[2]], hi = d.p[3][r * d.s[3]];
-                    v = lo + y * (hi - lo);
-                    break;
-                }
-                case 9:
-                    rng.next(w);
-                    v = expf(a + b * normal_from(w[0], w[1]));
-                    break;
-                case 10:
-                    rng.next(w);
-                    v = a * powf(-logf(u01(w[0])), 1.0f / b);
-                    break;
-                case 11: v = binomial_draw(a, b, rng); break;
-                case 12: v = vonmises_draw(a, b, rng); break;
-                default: v = truncnormal_draw(a, b, d.p[2][r * d.s[2]], d.p[3][r * d.s[3]], rng); break;
-            }
+            const bool four = KIND == 8 || KIND == 13;
+            v = draw_one<KIND>(a, b, four ? d.p[2][r * d.s[2]] : 0.0f, four ? d.p[3][r * d.s[3]] : 0.0f, rng);
         }
         out[r] = v;
     }
@@ -189,6 +124,131 @@ static DistTerm dist_term(const pp_dist& d, const float* x, int sx, float scale)
     t.sx = sx;
     t.scale = scale;
     return t;
+}
+
+// ---- Mixture (pyprob/distributions/mixture.py): K scalar components of any kinds, K weights per particle or shared -------------
+struct MixComp {
+    int kind, s[4];
+    const float* p[4];
+};
+struct MixArgs {
+    int count, sp;              // K; row stride of probs (0: one shared row)
+    const float* probs;
+    MixComp c[PP_MIX_MAX_COMPONENTS];
+};
+
+// lp[r] = logsumexp_k( log clamp(w[r,k] / sum_k w[r,k]) + log p_k(x[r]) ) (mixture.py:15-16, 38-45; util.clamp_probs); lw[r] += scale lp,
+// lp_out[r] = lp. The component loop runs on the argument block (k is wave-uniform); the log-sum-exp keeps a running maximum, so
+// no per-component array exists: -inf when every component gives -inf, NaN as soon as one term is NaN.
+__global__ __launch_bounds__(256) void mix_logweight_kernel(MixArgs M, const float* __restrict__ xs, int sx, float scale,
+                                                            float* __restrict__ lw, float* __restrict__ lp_out,
+                                                            const int64_t* __restrict__ rows, int m) {
+    const int K = M.count;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
+        const int64_t r = rows ? rows[j] : (int64_t)j;
+        const float x = xs[r * sx];
+        const float* w = M.probs + r * M.sp;
+        float sum = 0.0f;
+        for (int k = 0; k < K; ++k) sum += w[k];
+        float mx = -INFINITY, acc = 0.0f;
+        bool nan = false;
+        for (int k = 0; k < K; ++k) {
+            const float q = w[k] / sum;
+            const float lq = q == q ? logf(fminf(fmaxf(q, kFp32Eps), 1.0f - kFp32Eps)) : NAN;
+            const float t = lq + scalar_log_prob(M.c[k].kind, M.c[k].p, M.c[k].s, r, x);
+            if (t != t) {
+                nan = true;
+            } else if (t > mx) {
+                acc = acc * expf(mx - t) + 1.0f;
+                mx = t;
+            } else if (t > -INFINITY) {
+                acc += t == mx ? 1.0f : expf(t - mx);
+            }
+        }
+        const float lp = nan ? NAN : (mx > -INFINITY ? mx + logf(acc) : -INFINITY);
+        if (lp_out) lp_out[r] = lp;
+        if (lw) lw[r] += scale * lp;
+    }
+}
+
+// out[r] ~ Mixture for the lanes whose selected component has kind KIND (the host launches one instance per distinct kind of
+// the mixture). Selection: first word of Philox(seed, offset + r, stream_id | 0x80000000), dist_draw_kernel<5>'s rule on the
+// unclamped weights (Categorical(probs).sample(), mixture.py:47-50). Draw: Philox(seed, offset + r, stream_id) - dist_draw_kernel's
+// stream, so K = 1 or K identical components give pp_dist_draw's values. The selected component's parameters are picked in a
+// wave-uniform loop over the argument block under the lane mask (no per-lane index into it).
+template <int KIND>
+__global__ __launch_bounds__(256) void mix_draw_kernel(MixArgs M, const int64_t* __restrict__ rows, int m, uint64_t seed,
+                                                       uint64_t offset, uint32_t stream_id, float* __restrict__ out) {
+    const int K = M.count;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
+        const int64_t r = rows ? rows[j] : (int64_t)j;
+        Philox pick(seed, offset + (uint64_t)r, stream_id | 0x80000000u);
+        uint32_t w[4];
+        pick.next(w);
+        const float* p = M.probs + r * M.sp;
+        float sum = 0.0f;
+        for (int k = 0; k < K; ++k) sum += p[k];
+        const float target = u01(w[0]) * sum;
+        float cum = 0.0f;
+        int sel = K - 1;
+        for (int k = 0; k < K; ++k) {
+            cum += p[k];
+            if (target < cum) { sel = k; break; }
+        }
+        float a = 0.0f, b = 0.0f, c = 0.0f, d = 0.0f;
+        bool mine = false;
+        for (int k = 0; k < K; ++k) {
+            if (M.c[k].kind != KIND) continue;       // wave-uniform
+            if (k == sel) {
+                mine = true;
+                a = M.c[k].p[0][r * M.c[k].s[0]];
+                if (!(KIND == 3 || KIND == 4 || KIND == 6)) b = M.c[k].p[1][r * M.c[k].s[1]];
+                if (KIND == 8 || KIND == 13) {
+                    c = M.c[k].p[2][r * M.c[k].s[2]];
+                    d = M.c[k].p[3][r * M.c[k].s[3]];
+                }
+            }
+        }
+        if (mine) {
+            Philox rng(seed, offset + (uint64_t)r, stream_id);
+            out[r] = draw_one<KIND>(a, b, c, d, rng);
+        }
+    }
+}
+
+static bool mix_ok(const pp_mixture* mx, const char* what) {
+    if (!mx || mx->count < 1 || mx->count > PP_MIX_MAX_COMPONENTS) {
+        set_error("%s: a mixture has 1..%d components", what, PP_MIX_MAX_COMPONENTS);
+        return false;
+    }
+    if (!mx->probs || (mx->probs_stride != 0 && mx->probs_stride != mx->count)) {
+        set_error("%s: probs is one shared row (probs_stride 0) or one row of K per particle (probs_stride K)", what);
+        return false;
+    }
+    for (int k = 0; k < mx->count; ++k) {
+        const pp_dist& d = mx->comp[k];
+        if (d.kind == 2 || d.kind == 5) {
+            set_error("%s: component %d: Factor and Categorical are not mixture components", what, k);
+            return false;
+        }
+        if (!dist_ok(d, what)) return false;
+    }
+    return true;
+}
+
+static MixArgs mix_args(const pp_mixture& mx) {
+    MixArgs M{};
+    M.count = mx.count;
+    M.sp = mx.probs_stride;
+    M.probs = mx.probs;
+    for (int k = 0; k < mx.count; ++k) {
+        M.c[k].kind = mx.comp[k].kind;
+        for (int q = 0; q < 4; ++q) {
+            M.c[k].s[q] = mx.comp[k].p_stride[q];
+            M.c[k].p[q] = mx.comp[k].p[q];
+        }
+    }
+    return M;
 }
 
 }  // namespace pp
@@ -243,5 +303,45 @@ int pp_dist_draw(const pp_dist* d, const int64_t* rows, int32_t m, int32_t n, ui
     }
 #undef PP_DIST_DRAW
     PP_LAUNCH_CHECK("pp_dist_draw");
+    return 0;
+}
+
+int pp_mix_logweight(const pp_mixture* mx, const float* x, int32_t x_stride, float scale, float* lw, float* lp_out,
+                     const int64_t* rows, int32_t m, int32_t n, void* stream) {
+    if (!x || x_stride < 0 || (!lw && !lp_out) || n < 0 || m < 0 || (!rows && m != n) || m > n) {
+        pp::set_error("pp_mix_logweight: bad argument (a value, lw or lp_out, m = n without a row list)");
+        return PP_EINVAL;
+    }
+    if (!pp::mix_ok(mx, "pp_mix_logweight")) return PP_EINVAL;
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(pp::mix_logweight_kernel, dim3(std::min(2048, pp::cdiv(m, 256))), dim3(256), 0, pp::as_stream(stream),
+                       pp::mix_args(*mx), x, x_stride, scale, lw, lp_out, rows, m);
+    PP_LAUNCH_CHECK("pp_mix_logweight");
+    return 0;
+}
+
+int pp_mix_draw(const pp_mixture* mx, const int64_t* rows, int32_t m, int32_t n, uint64_t seed, uint64_t offset,
+                uint32_t stream_id, float* out, void* stream) {
+    if (!out || n < 0 || m < 0 || (!rows && m != n) || m > n) {
+        pp::set_error("pp_mix_draw: bad argument (m = n without a row list)");
+        return PP_EINVAL;
+    }
+    if (stream_id & 0x80000000u) {
+        pp::set_error("pp_mix_draw: the top bit of stream_id belongs to the component selection");
+        return PP_EINVAL;
+    }
+    if (!pp::mix_ok(mx, "pp_mix_draw")) return PP_EINVAL;
+    if (m == 0) return 0;
+    const dim3 grid(std::min(2048, pp::cdiv(m, 256))), block(256);
+    hipStream_t st = pp::as_stream(stream);
+    const pp::MixArgs M = pp::mix_args(*mx);
+    uint32_t kinds = 0;          // one launch per distinct kind of the mixture
+    for (int k = 0; k < mx->count; ++k) kinds |= 1u << mx->comp[k].kind;
+#define PP_MIX_DRAW(K) \
+    if (kinds & (1u << K)) hipLaunchKernelGGL(pp::mix_draw_kernel<K>, grid, block, 0, st, M, rows, m, seed, offset, stream_id, out)
+    PP_MIX_DRAW(0); PP_MIX_DRAW(1); PP_MIX_DRAW(3); PP_MIX_DRAW(4); PP_MIX_DRAW(6); PP_MIX_DRAW(7); PP_MIX_DRAW(8);
+    PP_MIX_DRAW(9); PP_MIX_DRAW(10); PP_MIX_DRAW(11); PP_MIX_DRAW(12); PP_MIX_DRAW(13);
+#undef PP_MIX_DRAW
+    PP_LAUNCH_CHECK("pp_mix_draw");
     return 0;
 }

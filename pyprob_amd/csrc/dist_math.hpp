@@ -98,6 +98,33 @@ __device__ __forceinline__ float lp_truncnormal(float mu, float sd, float low, f
     return -(z * z) / 2.0f - kHalfLog2Pi - logf(sd * Z);
 }
 
+// log p(x) of a scalar family (kinds 0, 1, 3, 4, 6-13) at particle r: parameter q is p[q][r * s[q]]. `kind` comes from a kernel
+// argument block, so every lane of a wave takes the same branch; shared by dist_logweight_kernel and mix_logweight_kernel.
+__device__ __forceinline__ float scalar_log_prob(int kind, const float* const* p, const int* s, int64_t r, float x) {
+    const float a = p[0][r * s[0]];
+    switch (kind) {
+        case 0: return lp_normal(a, p[1][r * s[1]], x);
+        case 1: {
+            const float b = p[1][r * s[1]];
+            return (x >= a && x < b) ? -logf(b - a) : -INFINITY;
+        }
+        case 3: return (x >= 0.0f && x == floorf(x)) ? (x == 0.0f ? 0.0f : x * logf(a)) - a - lgammaf(x + 1.0f) : -INFINITY;
+        case 4: {
+            if (!(x == 0.0f || x == 1.0f)) return -INFINITY;
+            const float q = fminf(fmaxf(a, kFp32Eps), 1.0f - kFp32Eps);
+            return x * logf(q) + (1.0f - x) * log1pf(-q);
+        }
+        case 6: return lp_exponential(a, x);
+        case 7: return lp_gamma(a, p[1][r * s[1]], x);
+        case 8: return lp_beta(a, p[1][r * s[1]], p[2][r * s[2]], p[3][r * s[3]], x);
+        case 9: return lp_lognormal(a, p[1][r * s[1]], x);
+        case 10: return lp_weibull(a, p[1][r * s[1]], x);
+        case 11: return lp_binomial(a, p[1][r * s[1]], x);
+        case 12: return lp_vonmises(a, p[1][r * s[1]], x);
+        default: return lp_truncnormal(a, p[1][r * s[1]], p[2][r * s[2]], p[3][r * s[3]], x);
+    }
+}
+
 // ---- samplers --------------------------------------------------------------------------------------------------------
 // A lane's stream: the first block is drawn by the caller's Philox; every further round calls rng.next() again.
 
@@ -312,6 +339,59 @@ __device__ __forceinline__ float truncnormal_draw(float mu, float sd, float low,
         }
     }
     return NAN;
+}
+
+// One draw of scalar family KIND from the lane's stream (parameters a..d = p0..p3 of include/pyprob_amd.h; the kinds with
+// fewer parameters ignore the rest): the body of dist_draw_kernel<KIND>, shared with mix_draw_kernel<KIND>.
+template <int KIND>
+__device__ __forceinline__ float draw_one(float a, float b, float c, float d, Philox& rng) {
+    uint32_t w[4];
+    float v;
+    switch (KIND) {
+        case 0:
+            rng.next(w);
+            v = a + b * sqrtf(-2.0f * logf(u01(w[0]))) * cosf(kTwoPi * u01(w[1]));
+            break;
+        case 1:
+            rng.next(w);
+            v = a + (b - a) * (((float)(w[0] >> 8)) * (1.0f / 16777216.0f));
+            v = v < b ? v : a;
+            break;
+        case 3: v = poisson_draw(a, rng); break;
+        case 4:
+            rng.next(w);
+            v = u01(w[0]) < a ? 1.0f : 0.0f;
+            break;
+        case 6:
+            rng.next(w);
+            v = -logf(u01(w[0])) / a;
+            break;
+        case 7: v = (a > 0.0f && b > 0.0f) ? expf(log_gamma_draw(a, rng) - logf(b)) : NAN; break;
+        case 8: {
+            float y = NAN;
+            if (a > 0.0f && b > 0.0f) {
+                const float g1 = log_gamma_draw(a, rng), g0 = log_gamma_draw(b, rng);
+                // G1 / (G1 + G0) from the logs: the smaller share s = e / (1 + e), e = exp(-|g1 - g0|), stays > 0 down
+                // to the denormals, and y = 1 - s near 1 is rounded once
+                const float e = expf(-fabsf(g1 - g0)), s = e / (1.0f + e);
+                y = g1 >= g0 ? 1.0f - s : s;
+            }
+            v = c + y * (d - c);
+            break;
+        }
+        case 9:
+            rng.next(w);
+            v = expf(a + b * normal_from(w[0], w[1]));
+            break;
+        case 10:
+            rng.next(w);
+            v = a * powf(-logf(u01(w[0])), 1.0f / b);
+            break;
+        case 11: v = binomial_draw(a, b, rng); break;
+        case 12: v = vonmises_draw(a, b, rng); break;
+        default: v = truncnormal_draw(a, b, c, d, rng); break;
+    }
+    return v;
 }
 
 }  // namespace pp

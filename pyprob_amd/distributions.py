@@ -5,6 +5,7 @@ uniform,categorical,empirical}.py): thin objects carrying `name`, parameters, `s
 `log_prob(value, sum=False)`. They are evaluated on the host like in the reference; the
 proposal distributions themselves (Mixture / TruncatedNormal) live in the HIP kernels.
 """
+import copy
 import math
 import warnings
 
@@ -493,6 +494,154 @@ class TruncatedNormal(_Family):
         a, b, pa, pb = self._pdf_ab()
         Z = self._Z()
         return self._p[1] ** 2 * (1 + (a * pa - b * pb) / Z - ((pa - pb) / Z) ** 2)
+
+
+def _plain(t):
+    return t.as_subclass(torch.Tensor) if type(t) is not torch.Tensor else t
+
+
+def _draw_n(d, n):
+    """n draws of a scalar family, one per particle: independent draws for shared parameters, elementwise for per-particle ones."""
+    if isinstance(d, _Family):
+        c = copy.copy(d)
+        with torch._C.DisableTorchFunctionSubclass():
+            c._p = tuple(_plain(q).reshape(-1).expand(n) if q.numel() == 1 else _plain(q).reshape(-1) for q in d._p)
+        c._td = None
+        return c.sample().reshape(-1).float()
+    td = d._torch_dist
+    batch = td.batch_shape.numel() if len(td.batch_shape) else 1
+    return _plain(td.sample((n,)) if batch == 1 else td.sample()).reshape(-1).float()
+
+
+def _moved(d, device):
+    """A copy of a scalar family with every tensor attribute on `device`."""
+    c = copy.copy(d)
+    for k, v in list(c.__dict__.items()):
+        if torch.is_tensor(v):
+            c.__dict__[k] = v.to(device)
+        elif isinstance(v, tuple) and v and all(torch.is_tensor(q) for q in v):
+            c.__dict__[k] = tuple(q.to(device) for q in v)
+    if c._td is not None:
+        c._td = None
+        if d.name == 'Poisson':
+            c._td = torch.distributions.Poisson(d.rate.to(device), validate_args=False)
+        elif d.name == 'Bernoulli':
+            c._td = torch.distributions.Bernoulli(probs=d.probs.to(device), validate_args=False)
+    return c
+
+
+# the families a Mixture may hold (the scalar kinds of pp_mixture: every family but Factor, Categorical and Mixture itself)
+MIXTURE_COMPONENT_KINDS = dict(DIST_KINDS, Normal=0, Uniform=1, Poisson=3, Bernoulli=4)
+del MIXTURE_COMPONENT_KINDS['Factor']
+
+
+class Mixture(Distribution):
+    """pyprob/distributions/mixture.py: K component distributions and K weights, one row (1-D probs) or one row per batch element
+    / particle (2-D probs). log_prob is logsumexp_k(log clamp(probs_k / sum probs) + log p_k(x)) with the clamp of
+    util.clamp_probs; sample picks a component from Categorical(probs), then draws from it. The weights are kept as they were
+    given (a device tensor or a per-particle ParticleTensor is neither read nor copied here: the device kernels normalise a
+    row themselves, pp_mix_logweight / pp_mix_draw); `probs` is the normalised tensor, made on first use."""
+
+    def __init__(self, distributions, probs=None):
+        self._distributions = list(distributions)
+        self.length = len(self._distributions)
+        if self.length < 1:
+            raise ValueError('Expecting at least one component distribution.')
+        with torch._C.DisableTorchFunctionSubclass():
+            if probs is None:
+                raw = torch.full((self.length,), 1. / self.length)
+            else:
+                raw = probs if (torch.is_tensor(probs) and probs.dtype == torch.float32) else _t(probs).float()
+            if raw.dim() == 1:
+                self._batch_length = 0
+            elif raw.dim() == 2:
+                self._batch_length = raw.size(0)
+            else:
+                raise ValueError('Expecting a 1d or 2d (batched) mixture probabilities.')
+            if raw.size(-1) != self.length:
+                raise ValueError('Expecting one probability per component distribution.')
+        self._raw_probs = raw
+        self._probs = None
+        self._mean = None
+        self._variance = None
+        super().__init__('Mixture', 'Mixture({})'.format(', '.join(d._address_suffix for d in self._distributions)))
+
+    def __repr__(self):
+        return 'Mixture(distributions=[{}], probs={})'.format(', '.join(repr(d) for d in self._distributions),
+                                                             self.probs.detach().cpu().numpy().tolist())
+
+    def __len__(self):
+        return self.length
+
+    def _device(self):
+        return self._raw_probs.device
+
+    @property
+    def probs(self):
+        if self._probs is None:
+            raw = _plain(self._raw_probs)
+            self._probs = raw / raw.sum(-1, keepdim=True)
+        return self._probs
+
+    @property
+    def distributions(self):
+        return self._distributions
+
+    def _log_probs(self):
+        eps = torch.finfo(torch.float32).eps
+        return torch.log(self.probs.clamp(min=eps, max=1 - eps))        # util.clamp_probs
+
+    def log_prob(self, value, sum=False):
+        value = _plain(_t(value).float())
+        lw = self._log_probs()
+        if self._batch_length == 0:
+            value = value.squeeze()
+            lps = torch.stack(torch.broadcast_tensors(*[_plain(d.log_prob(value)).to(lw.device) for d in self._distributions]))
+            lp = torch.logsumexp(lw.reshape((self.length,) + (1,) * (lps.dim() - 1)) + lps, dim=0)
+        else:
+            value = value.reshape(self._batch_length)
+            lps = torch.stack([_plain(d.log_prob(value)).to(lw.device).reshape(-1).expand(self._batch_length)
+                               for d in self._distributions], 1)
+            lp = torch.logsumexp(lw + lps, dim=1)
+        return torch.sum(lp) if sum else lp
+
+    def sample(self):
+        if self._batch_length == 0:
+            i = int(torch.distributions.Categorical(probs=self.probs).sample())
+            return self._distributions[i].sample()
+        return self.sample_n(self._batch_length)
+
+    def sample_n(self, n):
+        """One draw per particle / batch element, vectorised: the component index of every row, then a gather from the components' draws."""
+        p = _plain(self._raw_probs).reshape(-1, self.length)
+        idx = torch.multinomial(p.expand(n, self.length) if p.size(0) == 1 else p, 1)
+        draws = torch.stack([_draw_n(d, n).to(idx.device) for d in self._distributions], 1)
+        return draws.gather(1, idx).reshape(-1)
+
+    @property
+    def mean(self):
+        if self._mean is None:
+            means = torch.stack(torch.broadcast_tensors(*[_plain(_t(d.mean)).float() for d in self._distributions]))
+            if self._batch_length == 0:
+                self._mean = torch.tensordot(self.probs, means, dims=([0], [0]))
+            else:
+                self._mean = (self.probs * means.reshape(self.length, -1).t()).sum(1)
+        return self._mean
+
+    @property
+    def variance(self):
+        if self._variance is None:
+            m = self.mean
+            var = torch.stack(torch.broadcast_tensors(*[(_plain(_t(d.mean)).float() - m).pow(2) + _plain(_t(d.variance)).float()
+                                                        for d in self._distributions]))
+            if self._batch_length == 0:
+                self._variance = torch.tensordot(self.probs, var, dims=([0], [0]))
+            else:
+                self._variance = (self.probs * var.reshape(self.length, -1).t()).sum(1)
+        return self._variance
+
+    def to(self, device):
+        return Mixture([_moved(d, device) for d in self._distributions], probs=self._raw_probs.to(device))
 
 
 class Factor(Distribution):

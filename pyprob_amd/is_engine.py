@@ -97,6 +97,8 @@ class DistRunner:
             C_ = int(distribution.num_categories)
             p0 = t(distribution.probs)
             return 5, p0, (0 if p0.numel() == C_ else C_), None, C_
+        if name == 'Mixture':
+            return self._mix_term(distribution, t)
         kind = DIST_KINDS.get(name)
         if kind is None:
             return None
@@ -109,12 +111,47 @@ class DistRunner:
             out += [q, 0 if q is None else s(q)]
         return tuple(out)       # (kind, p0, s0, p1, s1, p2, s2, p3, s3): a pp_dist term (pp_dist_logweight / pp_dist_draw)
 
+    def _mix_term(self, distribution, t):
+        """('Mixture', kinds [K], parameters [4 K], strides [4 K], probs, K): a pp_mixture term (pp_mix_logweight / pp_mix_draw).
+        Every component is a scalar family with parameters of 1 or n elements; probs holds K (shared) or n K (per particle)
+        unnormalised weights. None if a component has no place in a mixture (Categorical, Factor, a nested Mixture)."""
+        comps = distribution.distributions
+        K = len(comps)
+        if not 1 <= K <= L.PP_MIX_MAX_COMPONENTS:
+            return None
+        kinds, ps, ss = [], [], []
+        for d in comps:
+            if d.name in ('Mixture', 'Categorical', 'Factor'):
+                return None
+            sub = self._dist_term(d)
+            if sub is None:
+                return None
+            if len(sub) == 5:
+                sub = (sub[0], sub[1], sub[2], sub[3], sub[4], None, 0, None, 0)
+            kinds.append(int(sub[0]))
+            ps += list(sub[1::2])
+            ss += [int(v) for v in sub[2::2]]
+        raw = getattr(distribution, '_raw_probs', None)
+        raw = distribution.probs if raw is None else raw
+        if torch.is_tensor(raw) and raw.dtype == torch.float32 and raw.device == self.dev and raw.is_contiguous():
+            probs = raw.as_subclass(torch.Tensor).reshape(-1)
+        else:
+            probs = torch.as_tensor(raw, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(self.dev).contiguous()
+        return ('Mixture', kinds, ps, ss, probs, K)
+
+    def _mix_check(self, term, n):
+        _, kinds, ps, ss, probs, K = term
+        if probs.numel() not in (K, n * K) or any(q is not None and q.numel() not in (1, n) for q in ps):
+            raise RuntimeError('lock-step Mixture: component parameters of 1 or n elements, probs of K or n K elements')
+
     def dist_spec(self, distribution):
         """(kind, [p0..p3], [s0..s3]) of pp_dist for any family (kinds 0-5 included: the prior draws of the prior-proposal
         engine); None if the family has no device kernel."""
         term = self.dist_term(distribution)
         if term is None:
             return None
+        if len(term) == 6:       # a mixture term: drawn by pp_mix_draw
+            return term
         if len(term) == 5:
             kind, p0, s0, p1, s1 = term
             if kind == 5:
@@ -128,6 +165,11 @@ class DistRunner:
         spec = self.dist_spec(distribution)
         if spec is None or spec[0] == 2:
             raise RuntimeError('lock-step execution has no device sampler for {}'.format(distribution.name))
+        if len(spec) == 6:      # Mixture: the selection stream is stream_id | 0x80000000, the component's draw stream_id
+            self._mix_check(spec, values.numel())
+            ops.mix_draw(spec[1], spec[2], spec[3], spec[4], rows, values, int(seed), self.offset, int(stream_id))
+            torch.autograd.graph.increment_version(values)
+            return values
         kind, ps, ss = spec
         for q in ps:
             if q is not None and kind != 5 and q.numel() not in (1, values.numel()):
@@ -142,15 +184,23 @@ class DistRunner:
         if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
             x = x.to(self.dev, torch.float32).contiguous()
         x = x.reshape(-1)
+        if len(term) == 6:      # Mixture (pp_mix_logweight)
+            self._mix_check(term, lw.numel())
+            ops.mix_logweight(lw, term[1], term[2], term[3], term[4], x, float(scale), rows, None, lw.numel())
+            return
         ps, ss = list(term[1::2]), [int(v) for v in term[2::2]]
         ops.dist_logweight(lw, [int(term[0])], ps, ss, [x], [float(scale)], rows, None, lw.numel())
 
     def log_prob(self, term, x, n=None):
         """log_prob(dist; x) per particle as a device tensor [n] (no accumulation)."""
-        if len(term) == 9:      # a pp_dist term (pp_dist_logweight's lp_out)
+        if len(term) in (6, 9):      # a pp_dist / pp_mixture term (lp_out of pp_dist_logweight / pp_mix_logweight)
             n = int(x.numel()) if n is None else n
             lp = torch.empty(n, dtype=torch.float32, device=self.dev)
             x = x.as_subclass(torch.Tensor).to(self.dev, torch.float32).reshape(-1).contiguous()
+            if len(term) == 6:
+                self._mix_check(term, n)
+                ops.mix_logweight(None, term[1], term[2], term[3], term[4], x, 1.0, None, lp, n)
+                return lp
             ops.dist_logweight(None, [int(term[0])], list(term[1::2]), [int(v) for v in term[2::2]], [x], [1.0], None, lp, n)
             return lp
         kind, p0, s0, p1, s1 = term

@@ -84,6 +84,13 @@ class pp_dist_term(C.Structure):
     _fields_ = [('d', pp_dist), ('x', vp), ('x_stride', i32), ('scale', C.c_float)]
 
 
+PP_MIX_MAX_COMPONENTS = 16
+
+
+class pp_mixture(C.Structure):
+    _fields_ = [('count', i32), ('probs_stride', i32), ('probs', vp), ('comp', pp_dist * PP_MIX_MAX_COMPONENTS)]
+
+
 class pp_gemm_args(C.Structure):
     _fields_ = [('A', vp), ('lda', i64), ('a_idx', vp),
                 ('B', vp), ('ldb', i64), ('b_idx', vp),
@@ -165,6 +172,8 @@ PROTOTYPES = {
     'pp_is_stats': (C.c_int, [vp, vp, i32, vp, vp, vp]),
     'pp_dist_logweight': (C.c_int, [C.POINTER(pp_dist_term), i32, vp, vp, vp, i32, i32, vp]),
     'pp_dist_draw': (C.c_int, [C.POINTER(pp_dist), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
+    'pp_mix_logweight': (C.c_int, [C.POINTER(pp_mixture), vp, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
+    'pp_mix_draw': (C.c_int, [C.POINTER(pp_mixture), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_gemm_f32': (C.c_int, [C.POINTER(pp_gemm_args), vp]),
     'pp_gemm_f32_grouped': (C.c_int, [C.POINTER(pp_gemm_args), i32, vp]),
     'pp_colsum_f32': (C.c_int, [vp, i64, vp, i32, i32, vp, vp, vp]),

@@ -324,6 +324,8 @@ class InferenceNetworkLSTM:
         then lw += log p(v) - log q(v) (state.py:211-217). A statement inside the replayed prefix of a path returns the
         values recorded when a superset of these particles executed it. Returns a ParticleTensor [n]."""
         from .state import ParticleTensor
+        if distribution.name == 'Mixture':      # no proposal layer exists for it (inference_network_lstm.py:68)
+            raise RuntimeError('Distribution currently unsupported: {}'.format(distribution.name))
         spec = self._engine.spec
         runner = ls.runner
         j = ls.statement

@@ -18,6 +18,8 @@ kernels for these operators from tests/, to execute the host logic above them wi
     log_prob     prior / likelihood log_prob terms of the log-weight pyprob/state.py:211, 147-149
     dist_logweight  the log-weight terms of every distribution family   pyprob/state.py:113-115, 147-149, 211
     dist_draw       draws of every distribution family (Philox)       pyprob/state.py:191-201, 218-221
+    mix_logweight   Mixture.log_prob as a log-weight term               pyprob/distributions/mixture.py:38-45
+    mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -66,6 +68,10 @@ _lib.define('is_stats(Tensor lw, Tensor? x, Tensor(a!) scratch) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
+            'int stream_id) -> ()')
+_lib.define('mix_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor probs, Tensor x, float scale, '
+            'Tensor? rows, Tensor(b!)? lp_out, int n) -> ()')
+_lib.define('mix_draw(int[] kinds, Tensor?[] params, int[] strides, Tensor probs, Tensor? rows, Tensor(a!) out, int seed, int offset, '
             'int stream_id) -> ()')
 
 # ---- network registry -------------------------------------------------------------------------------------------
@@ -485,6 +491,60 @@ def _dist_draw_hip(kind, params, strides, rows, out, seed, offset, stream_id):
     L.check(rc, 'pp_dist_draw')
 
 
+def _mix_fill(kinds, params, strides, probs, n, what):
+    """pp_mixture from the K components' kinds, 4 K parameters / strides and the weights (K: one shared row, n K: one per particle)."""
+    K = len(kinds)
+    if not 1 <= K <= L.PP_MIX_MAX_COMPONENTS or len(params) != 4 * K or len(strides) != 4 * K:
+        raise RuntimeError('pyprob_hip::%s: 1..%d components, 4 parameters and strides per component' % (what, L.PP_MIX_MAX_COMPONENTS))
+    if _f32(probs, 'probs').numel() not in (K, n * K):
+        raise RuntimeError('pyprob_hip::%s: probs must have K = %d or n K = %d elements' % (what, K, n * K))
+    mx = L.pp_mixture()
+    mx.count = K
+    mx.probs_stride = 0 if probs.numel() == K else K      # (n = 1: either reading is the same row)
+    mx.probs = probs.data_ptr()
+    for k in range(K):
+        if int(kinds[k]) in (2, 5):
+            raise RuntimeError('pyprob_hip::%s: component %d: Factor and Categorical are not mixture components' % (what, k))
+        for q in range(4):
+            if params[4 * k + q] is not None and int(strides[4 * k + q]) not in (0, 1):
+                raise RuntimeError('pyprob_hip::%s: component %d: a parameter stride is 0 or 1' % (what, k))
+        _dist_fill(mx.comp[k], int(kinds[k]), params, strides, k, n, what)
+    return mx
+
+
+def _mix_logweight_hip(lw, kinds, params, strides, probs, x, scale, rows, lp_out, n):
+    lib = L.load()
+    ref = lw if lw is not None else lp_out
+    if ref is None:
+        raise RuntimeError('pyprob_hip::mix_logweight: lw or lp_out is needed')
+    for t, name in ((lw, 'lw'), (lp_out, 'lp_out')):
+        if t is not None and (_f32(t, name).numel() != n):
+            raise RuntimeError('pyprob_hip::mix_logweight: %s must have n = %d elements' % (name, n))
+    _same_device(ref, lw, lp_out, rows, probs, x, *params)
+    mx = _mix_fill(kinds, params, strides, probs, n, 'mix_logweight')
+    if _f32(x, 'x').numel() not in (1, n):
+        raise RuntimeError('pyprob_hip::mix_logweight: x must have 1 or n elements')
+    rp, m = _rows_arg(rows, n, 'mix_logweight')
+    with torch.cuda.device(ref.device):
+        rc = lib.pp_mix_logweight(C.byref(mx), x.data_ptr(), 0 if x.numel() == 1 else 1, float(scale), L.ptr(lw), L.ptr(lp_out), rp,
+                                  int(m), int(n), _stream(ref))
+    L.check(rc, 'pp_mix_logweight')
+
+
+def _mix_draw_hip(kinds, params, strides, probs, rows, out, seed, offset, stream_id):
+    lib = L.load()
+    n = _f32(out, 'out').numel()
+    _same_device(out, rows, probs, *params)
+    mx = _mix_fill(kinds, params, strides, probs, n, 'mix_draw')
+    if int(stream_id) & ~0x7FFFFFFF:
+        raise RuntimeError('pyprob_hip::mix_draw: stream_id must leave the top bit clear (it marks the selection stream)')
+    rp, m = _rows_arg(rows, n, 'mix_draw')
+    with torch.cuda.device(out.device):
+        rc = lib.pp_mix_draw(C.byref(mx), rp, int(m), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), int(stream_id),
+                             out.data_ptr(), _stream(out))
+    L.check(rc, 'pp_mix_draw')
+
+
 def _is_stats_hip(lw, x, scratch):
     lib = L.load()
     _same_device(lw, x, scratch)
@@ -513,5 +573,7 @@ _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
+_lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
+_lib.impl('mix_draw', _mix_draw_hip, 'CUDA')
 
 ops = getattr(torch.ops, NAMESPACE)

@@ -80,6 +80,8 @@ def convert(distribution):
         if name == 'TruncatedNormal':      # (pyprob applied clamp_mean_between_low_high at construction)
             return D.TruncatedNormal(_shared(distribution.mean_non_truncated), _shared(distribution.stddev_non_truncated),
                                      _shared(distribution.low), _shared(distribution.high))
+        if name == 'Mixture':      # (the weights as pyprob normalised them; the components recursively)
+            return D.Mixture([convert(d) for d in distribution.distributions], probs=distribution._probs)
         if name == 'Factor':
             return D.Factor(log_prob=distribution._log_prob) if distribution._log_prob is not None else \
                 D.Factor(log_prob_func=distribution._log_prob_func)

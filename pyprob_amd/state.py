@@ -640,6 +640,8 @@ class PriorLockStep(PathExecutor):
 
     def _draw(self, distribution, stream_id):
         """One value per particle of this execution from `distribution` (prior inflation applied by the caller)."""
+        if distribution.name == 'Mixture':
+            return self._draw_mixture(distribution, stream_id)
         if self.dev.type != 'cpu' and distribution.name in ('Normal', 'Uniform'):
             from .ops import ops
             if distribution.name == 'Normal':
@@ -650,6 +652,24 @@ class PriorLockStep(PathExecutor):
                 # counters: particle index inside this execution; the path id separates re-run paths of one chunk
                 return ops.prior_draw(kind, p0, p1, self.width, self.seed, self.path_id << 32, stream_id)
         return _vector_draw(distribution, self.width).to(self.dev)
+
+    def _draw_mixture(self, distribution, stream_id):
+        """A Mixture on the device through pp_mix_draw (the key / counter / stream scheme of the Normal and Uniform draws); on
+        the CPU device a vectorised torch route: the component index of every particle, then a gather."""
+        if self.dev.type == 'cpu':
+            return distribution.sample_n(self.width)
+        from .is_engine import DistRunner
+        from .ops import ops
+        runner = self.__dict__.get('_mix_runner')
+        if runner is None:
+            runner = self._mix_runner = DistRunner(self.dev)
+        term = runner.dist_term(distribution)
+        if term is None:
+            raise RuntimeError('lock-step execution has no device sampler for this Mixture')
+        runner._mix_check(term, self.width)
+        out = torch.empty(self.width, dtype=torch.float32, device=self.dev)
+        ops.mix_draw(term[1], term[2], term[3], term[4], None, out, self.seed, self.path_id << 32, int(stream_id))
+        return out
 
     def start_path(self, active, decisions, statements_done, observes_done):
         super().start_path(active, decisions, statements_done, observes_done)
@@ -851,8 +871,8 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
 
 def _lock_step_term(ls, term, v, obs_name=None):
     """One likelihood term of the active particles: kinds 0-5 join the fused pass (or the rows kernel); the other families and
-    factor's value term go through pp_dist_logweight on the path's rows."""
-    if len(term) == 9:
+    factor's value term go through pp_dist_logweight, a Mixture through pp_mix_logweight, on the path's rows."""
+    if len(term) in (6, 9):          # (6: a Mixture term, pp_mix_logweight)
         ls.plan_ok = False
         ls.flush()
         ls.runner.dist_accumulate(ls.lw, term, v, ls.rows, _likelihood_importance)
@@ -900,10 +920,11 @@ def observe(distribution, value=None, name=None, address=None):
         value = _current_trace_observed_variables[name]
     elif value is not None:
         value = torch.as_tensor(value, dtype=torch.float32)
-    elif _trace_mode == TraceMode.PRIOR_FOR_INFERENCE_NETWORK and distribution is not None:
+    elif _trace_mode == TraceMode.PRIOR_FOR_INFERENCE_NETWORK and distribution is not None and not (
+            _lock_step is not None and _lock_step.mode == 'prior' and distribution.name == 'Mixture'):
         value = distribution.sample()
     else:
-        value = None
+        value = None          # (a Mixture of a lock-step prior run: one draw per particle by the executor, PriorLockStep._draw)
     if _lock_step is not None and _lock_step.mode == 'prior':
         given = _current_trace_observed_variables.get(name) if name in _current_trace_observed_variables else (
             None if value is None else value)
