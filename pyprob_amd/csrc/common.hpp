@@ -172,6 +172,26 @@ __device__ __forceinline__ void stage_to_lds(float* __restrict__ lds, const floa
     }
 }
 
+// ---- write-through result stores (PP_STORE_WT) --------------------------------------------------------------------------
+// A plain store leaves its line dirty in the writing XCD's L2; the lines are written back when the kernel ends, before the
+// dependent launch may start. Every result of the training step is consumed by the NEXT launch, whose workgroups sit on all
+// eight XCDs, so the writer's L2 copy serves nobody: a 16-byte `sc1` store costs what a plain one does and leaves nothing
+// behind (narrower sc1 stores are one fabric write each, 2.7x - 6x the time per byte: 16 bytes per lane only).
+// `base` and `bytes` must be wave-uniform (kernel arguments): they become the buffer descriptor; `byte_off` is per lane,
+// 32 bits (every buffer of the step is far below 4 GB; the descriptor's range check drops a store beyond `bytes`).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store16_wt(float* base, uint32_t bytes, uint32_t byte_off, f32x4 v) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v),
+                                           __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000), (int)byte_off, 0,
+                                           /*aux: sc1*/ 16);
+}
+// PP_STORE_WT (default 1; 0 = plain stores, for the A/B and the parity tests): read per call, the tests flip it inside
+// one process
+static inline int store_wt_mode() {
+    const char* e = getenv("PP_STORE_WT");
+    return e ? (atoi(e) != 0) : 1;
+}
+
 struct LossFinalize {   // loss = sum of the 64 accumulator slots / B, status = non-finite flag (see loss_finalize_kernel)
     const float* acc; const int32_t* flag; float inv_b; float* loss_out; int32_t* status_out;
 };

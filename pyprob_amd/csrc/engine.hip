@@ -542,6 +542,7 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
             ptr.n_blocks = panel_transpose_blocks(H, ad.hid);
             if (panel16_go) {      // the job writes the six fragment images instead (one thread per fragment lane)
                 ptr.mode16 = 1;
+                ptr.wt = store_wt_mode();
                 ptr.p16.W2 = P + ad.w2; ptr.p16.n_out = ad.n_out;
                 ptr.p16.im = w.p16;
                 panel16_image_sizes(H, ad.hid, net->e_obs, ptr.p16.im.frags);      // (this address's head; the buffers hold the widest)

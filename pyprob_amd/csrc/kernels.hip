@@ -1147,8 +1147,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
                                                    int n_chunks, const float* __restrict__ active,
                                                    int32_t* __restrict__ tensor_step, int32_t* __restrict__ scratch, float lr,
                                                    float beta1, float beta2, float eps, float wd, float gscale,
-                                                   int zero_grads, const int32_t* __restrict__ skip) {
+                                                   int zero_grads, const int32_t* __restrict__ skip, int wt) {
+    // wt (PP_STORE_WT): the chunk's results are stored write-through (common.hpp store16_wt) - the next launch reads them
+    // from all eight XCDs, nothing of this kernel reads them again
     __shared__ float s_corr[2];
+    const uint32_t buf_bytes = (uint32_t)n_chunks * 4096u, wo = ((uint32_t)blockIdx.x * 1024u + threadIdx.x * 4u) * 4u;
+    const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
     const int b = blockIdx.x;
     // the loss of this step was not finite: the reference skips the batch (inference_network_lstm.py:216-217, no
     // optimizer step); checked on the device so that the host does not have to synchronise every iteration
@@ -1156,7 +1160,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
     const int t = chunk_tensor[b];
     if (t < 0 || !(active[t] > 0.0f)) return;   // workgroup-uniform; every chunk of a tensor takes the same branch
     if (skipped) {   // no update, no step count; the (non-finite) gradients are still cleared for the next step
-        if (zero_grads) *reinterpret_cast<f32x4*>(Gr + (int64_t)b * 1024 + threadIdx.x * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (zero_grads) {
+            if (wt) store16_wt(Gr, buf_bytes, wo, zero4);
+            else *reinterpret_cast<f32x4*>(Gr + (int64_t)b * 1024 + threadIdx.x * 4) = zero4;
+        }
         return;
     }
     int32_t* const sc = scratch + (int64_t)t * PP_ADAM_SCRATCH;
@@ -1238,10 +1245,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
             const float denom = sqrtf(v[e]) * inv_sqrt_bc2 + eps;
             p[e] -= step_size * (m[e] / denom);
         }
-        *reinterpret_cast<f32x4*>(P + o) = p;
-        *reinterpret_cast<f32x4*>(M + o) = m;
-        *reinterpret_cast<f32x4*>(V + o) = v;
-        if (zero_grads) *reinterpret_cast<f32x4*>(Gr + o) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (wt) {
+            store16_wt(P, buf_bytes, wo, p);
+            store16_wt(M, buf_bytes, wo, m);
+            store16_wt(V, buf_bytes, wo, v);
+            if (zero_grads) store16_wt(Gr, buf_bytes, wo, zero4);
+        } else {
+            *reinterpret_cast<f32x4*>(P + o) = p;
+            *reinterpret_cast<f32x4*>(M + o) = m;
+            *reinterpret_cast<f32x4*>(V + o) = v;
+            if (zero_grads) *reinterpret_cast<f32x4*>(Gr + o) = zero4;
+        }
     }
     if (threadIdx.x == 0 && ticket == quota - 1) {
         __atomic_store_n(sc + 32 * k, 0, __ATOMIC_RELAXED);
@@ -1261,8 +1275,10 @@ int adam_step(float* params, float* grads, float* m, float* v, int64_t n_params,
     PP_CHECK_ARG(n_params % 1024 == 0, "pp_adam_step: n_params must be a multiple of 1024 (padded tensors)");
     if (n_tensors <= 0 || n_params == 0) return 0;
     const int n_chunks = (int)(n_params / 1024);
+    // (the write-through stores address the buffers with 32-bit byte offsets)
+    const int wt = store_wt_mode() && n_params < ((int64_t)1 << 30) ? 1 : 0;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, params, grads, m, v, chunk_tensor, n_chunks,
-                       active, tensor_step, scratch, lr, beta1, beta2, eps, wd, gscale, (flags & PP_ADAM_ZERO_GRADS) ? 1 : 0, skip);
+                       active, tensor_step, scratch, lr, beta1, beta2, eps, wd, gscale, (flags & PP_ADAM_ZERO_GRADS) ? 1 : 0, skip, wt);
     PP_LAUNCH_CHECK("pp_adam_step");
     return 0;
 }

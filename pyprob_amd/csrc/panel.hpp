@@ -52,12 +52,13 @@ struct PanelTranspose {
     int tiles_ih, first_block, n_blocks;           // 3 H / 64 tiles of W_ih; first workgroup of the job in its launch
     int mode16;                                    // 1: the job writes the 16-row kernel's fragment images (p16) instead
     Panel16Prep p16;
+    int wt;                                        // PP_STORE_WT: write-through image stores (mode 16 only)
 };
 static inline int panel_transpose_blocks(int H, int hid) { return 3 * H / 64 + ((hid + 63) / 64) * (H / 64); }
 
 __device__ __forceinline__ void panel_transpose_block(const PanelTranspose& tr, int b, float* lds /* >= 64 * 65 floats */) {
     if (tr.mode16) {
-        panel16_image_block(tr.Wih, tr.ldw, tr.W1, tr.H, tr.hid, tr.e, tr.p16, b);
+        panel16_image_block(tr.Wih, tr.ldw, tr.W1, tr.H, tr.hid, tr.e, tr.p16, b, tr.wt);
         return;
     }
     const int tid = threadIdx.x;       // 256 threads

@@ -84,6 +84,8 @@ struct P16 {
     static constexpr int L_OIMG = L_DZ;                        // observe-embedding weight image of the tail: over sDZ + sDG
     static_assert(L_END - L_OIMG >= 10240 + 8, "the embedding image must fit the dead buffers");
     static_assert(L_END * 4 <= 160 * 1024, "LDS");
+    static_assert(L_H % 4 == 0 && L_Z % 4 == 0 && L_DY % 4 == 0 && L_DZ % 4 == 0 && L_DG % 4 == 0 && PH % 4 == 0 && PZ % 4 == 0,
+                  "the result tiles leave LDS as 16-byte reads (WT)");
     // the fragment stream of a wave: phase 1 | 2 | 3 | 4 | per unit tile: 5, 6
     static constexpr int F1 = 3 * KE * UTW, F2 = KL * TPW + UTW, F3 = (2 * NT + NWV - 1) / NWV, F4 = 2 * TPW + 2, F5 = NT, F6 = 3 * KE;
     static constexpr int B1 = 0, B2 = B1 + F1, B3 = B2 + F2, B4 = B3 + F3, B5 = B4 + F4, FU = F5 + F6, FT = B5 + UTW * FU;
@@ -165,7 +167,11 @@ struct FragPtrs {
 // workgroup's xz slot: [0, 8) the tile sums of phase 2, [8, 12) the last tile's elements, [16, 24) the dX sums). A consumer wave
 // polls the flags of the partner waves of ITS index (they wrote what it needs), then loads the payloads: half the bytes, two
 // dependent round trips instead of one (tools/micro/handoff_probe.hip: +0.2 us median per exchange in isolation).
-template <int HH_, int KIND, bool OBS, bool FLAGS = false>
+// WT (PP_STORE_WT, the default): the results Hs, A1, dZ1, DY and G leave as 16-byte write-through stores (common.hpp
+// store16_wt) read back from the tile that sits in LDS anyway, right behind the barrier that completes it, instead of one plain
+// dword store per lane and element from the registers: the next launch reads them on every XCD, nothing in this kernel does. The
+// same values to the same addresses; rows at or beyond B stay unwritten either way.
+template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false>
 __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, const PanelObs oin) {
     using T = P16<HH_>;
     constexpr int HH = T::HH, UT = T::UT, UTW = T::UTW, NT = T::NT, TPW = T::TPW, ZK = T::ZK, ZT = T::ZT, PH = T::PH, PZ = T::PZ;
@@ -214,6 +220,18 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
     float* const sDZ = smem + T::L_DZ;
     float* const sDGw = smem + T::L_DG + wave * (3 * PR * PG);
     float* const sXP = smem + T::L_XP;
+    // WT: rows [4 q, 4 q + 4) of an LDS tile [16][pitch] -> columns [0, min(cols, ld)) of the panel's rows of dst [B][ld]
+    // (ld % 4 == 0, checked on the host); columns the tile does not have are zeros (the pad columns of DY)
+    auto rows_out = [&](float* dst, int ld, const float* tile, int pitch, int cols, int have) {
+        const int c4 = min(cols, ld) >> 2;
+        const uint32_t bytes = (uint32_t)a.B * (uint32_t)ld * 4u;
+        for (int idx = tid; idx < 4 * c4; idx += 512) {
+            const int rr = idx / c4, r = 4 * q + rr, col = 4 * (idx - rr * c4);
+            f32x4 v = {0, 0, 0, 0};
+            if (col < have) v = *reinterpret_cast<const f32x4*>(tile + r * pitch + col);
+            if (m0 + r < a.B) store16_wt(dst, bytes, ((uint32_t)(m0 + r) * (uint32_t)ld + col) * 4u, v);
+        }
+    };
     const int dbg_slot = (bx == 0 ? 0 : (bx == 77 ? 1 : -1));
 #define P16_STAMP(k)                                                                                            \
     do {                                                                                                        \
@@ -300,12 +318,24 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
                 const float h = vo * tcv;
                 gi[j][i] = vi; gg[j][i] = vg; go[j][i] = vo; tc[j][i] = tcv;
                 sH[r * PH + 16 * (UTW * wave + j) + c] = h;
-                if (m0 + r < a.B) a.Hs[(int64_t)(m0 + r) * HH + 16 * (ut0 + j) + c] = h;
+                if constexpr (!WT) {
+                    if (m0 + r < a.B) a.Hs[(int64_t)(m0 + r) * HH + 16 * (ut0 + j) + c] = h;
+                }
             }
     }
     P16_STAMP(2);
     __syncthreads();     // the workgroup's h tile [16][H / 4] is complete
     P16_STAMP(3);
+    if constexpr (WT) {      // all 16 rows of the workgroup's units
+        constexpr int C4 = T::UW / 4;
+        const uint32_t bytes = (uint32_t)a.B * (uint32_t)HH * 4u;
+#pragma unroll
+        for (int idx0 = 0; idx0 < PR * C4; idx0 += 512) {
+            const int idx = idx0 + tid, r = idx / C4, col = 4 * (idx % C4);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(sH + r * PH + col);
+            if (m0 + r < a.B) store16_wt(a.Hs, bytes, ((uint32_t)(m0 + r) * HH + T::UW * q + col) * 4u, v);
+        }
+    }
 
     // ---------------- phase 2: partial z1 = h[:, own units] W1^T; tiles wave + 8 t (all K), the last tile (own units) ----------------
     float zt[TPW][4];    // z1 of (row 4 g + i, column 16 (wave + 8 t) + c); the last tile's z1 lives in sZ
@@ -435,20 +465,25 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
                     const float z = relu_keep_nan(four(acc[bt + tt][i], xs[0][e], xs[1][e], xs[2][e]) + b1v[bt + tt]);      // (j < ZT < hid)
                     zt[bt + tt][i] = z;
                     sZ[r * PZ + j] = z;
-                    if (g == q && m0 + r < a.B) a.A1[(int64_t)(m0 + r) * a.lda1 + j] = z;
+                    if constexpr (!WT) {
+                        if (g == q && m0 + r < a.B) a.A1[(int64_t)(m0 + r) * a.lda1 + j] = z;
+                    }
                 }
             }
             if (bt == 0 && tid < 256) {
                 const int j = ZT + ec;
                 const float z = j < hid ? relu_keep_nan(four(own16, xs[0][8], xs[1][8], xs[2][8]) + b16) : 0.0f;
                 sZ[er * PZ + j] = z;
-                if ((er >> 2) == q && m0 + er < a.B && j < a.lda1) a.A1[(int64_t)(m0 + er) * a.lda1 + j] = z;
+                if constexpr (!WT) {
+                    if ((er >> 2) == q && m0 + er < a.B && j < a.lda1) a.A1[(int64_t)(m0 + er) * a.lda1 + j] = z;
+                }
             }
         });
         P16_STAMP(6);
     }
     __syncthreads();     // z1 [16][ZK] complete
     P16_STAMP(7);
+    if constexpr (WT) rows_out(a.A1, a.lda1, sZ, PZ, ZK, ZK);      // (before sXP overlays the tile)
 
     // ---------------- phase 3: y = z1 W2^T; item wave + 8 f of the 2 NT (unit, tile) pairs: this wave's tile is wave & 1 ----------------
     {
@@ -504,16 +539,21 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
         lane_mixture_grad<KIND>(hm, comp, live, lp, pa, pb, a.grad_scale, red_sum, d0, d1, d2);
         if (comp) {
             sDY[r * PDY + c] = d0; sDY[r * PDY + K + c] = d1; sDY[r * PDY + 2 * K + c] = d2;
-            if (mine) {
-                float* dy = a.DY + (int64_t)gr * a.lddy;
-                dy[c] = d0; dy[K + c] = d1; dy[2 * K + c] = d2;
+            if constexpr (!WT) {
+                if (mine) {
+                    float* dy = a.DY + (int64_t)gr * a.lddy;
+                    dy[c] = d0; dy[K + c] = d1; dy[2 * K + c] = d2;
+                }
             }
         }
-        if (mine)      // pad columns of the row's dy
-            for (int o = n_out + c; o < a.lddy; o += 16) a.DY[(int64_t)gr * a.lddy + o] = 0.0f;
+        if constexpr (!WT) {
+            if (mine)      // pad columns of the row's dy
+                for (int o = n_out + c; o < a.lddy; o += 16) a.DY[(int64_t)gr * a.lddy + o] = 0.0f;
+        }
     }
     __syncthreads();
     P16_STAMP(9);
+    if constexpr (WT) rows_out(a.DY, a.lddy, sDY, PDY, a.lddy, PDY);      // (columns [n_out, PDY) of sDY are zero since the staging)
 
     // ---------------- phase 4: dz1 = (dy W2) * [z1 > 0] on the tiles of phase 2 ----------------
     {
@@ -538,12 +578,15 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
                 const float zv = t < TPW ? zt[t < TPW ? t : 0][i] : sZ[r * PZ + j];
                 const float d = (j < hid && zv > 0.0f) ? acc[t][i] : 0.0f;
                 sDZ[r * PZ + j] = d;
-                if (g == q && m0 + r < a.B && j < a.lda1) a.dZ1[(int64_t)(m0 + r) * a.lda1 + j] = d;
+                if constexpr (!WT) {
+                    if (g == q && m0 + r < a.B && j < a.lda1) a.dZ1[(int64_t)(m0 + r) * a.lda1 + j] = d;
+                }
             }
         }
     }
     __syncthreads();     // dz1 [16][ZK] complete
     P16_STAMP(10);
+    if constexpr (WT) rows_out(a.dZ1, a.lda1, sDZ, PZ, ZK, ZK);      // (phase 5 only reads the tile)
 
     // observe-embedding backward (tail): its weights and the masks of this lane's outputs are fetched behind phase 6
     constexpr int ONB = 2;
@@ -593,9 +636,11 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
             sDGw[(0 * PR + r) * PG + c] = d_i;
             sDGw[(1 * PR + r) * PG + c] = d_g;
             sDGw[(2 * PR + r) * PG + c] = d_o;
-            if (m0 + r < a.B) {
-                float* gp = a.G + (int64_t)(m0 + r) * 4 * HH;
-                gp[u] = d_i; gp[2 * HH + u] = d_g; gp[3 * HH + u] = d_o;
+            if constexpr (!WT) {
+                if (m0 + r < a.B) {
+                    float* gp = a.G + (int64_t)(m0 + r) * 4 * HH;
+                    gp[u] = d_i; gp[2 * HH + u] = d_g; gp[3 * HH + u] = d_o;
+                }
             }
         }
         // column sums of dG over the panel's rows (this address's slot of gsum: LSTM bias and table-column gradients follow
@@ -608,6 +653,16 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
             atomicAdd(a.gsum + 3 * HH + u, gs_o);
         }
         wave_sync_lds();     // this wave's dG tiles (A operand of phase 6) are its own
+        if constexpr (WT) {      // 16 rows x 16 units per gate: lane = (row, four units)
+            const int r = lane >> 2, x4 = 4 * (lane & 3);
+            const uint32_t bytes = (uint32_t)a.B * (uint32_t)(4 * HH) * 4u;
+#pragma unroll
+            for (int y = 0; y < 3; ++y) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(sDGw + (y * PR + r) * PG + x4);
+                if (m0 + r < a.B)
+                    store16_wt(a.G, bytes, ((uint32_t)(m0 + r) * (4 * HH) + (y == 0 ? 0 : y + 1) * HH + 16 * (ut0 + j) + x4) * 4u, v);
+            }
+        }
         if constexpr (j == 0) {
             P16_STAMP(11);
             if (OBS) {
@@ -791,12 +846,12 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
 #undef P16_ISSUE
 }
 
-template <int HH_, int KIND, bool OBS, bool FLAGS = false>
+template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false>
 static int panel16_launch(const Panel16Args& a, const PanelObs& po, hipStream_t st) {
     constexpr size_t lds = (size_t)P16<HH_>::L_END * sizeof(float);
     static thread_local bool configured = false;   // > 64 KB of dynamic LDS needs the opt-in once per kernel
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel16_kernel<HH_, KIND, OBS, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)panel16_kernel<HH_, KIND, OBS, FLAGS, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             set_error("panel16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
             return (int)e;
@@ -804,7 +859,7 @@ static int panel16_launch(const Panel16Args& a, const PanelObs& po, hipStream_t 
         configured = true;
     }
     const int panels = cdiv(a.a.B, PR);
-    hipLaunchKernelGGL((panel16_kernel<HH_, KIND, OBS, FLAGS>), dim3(8 * SS * cdiv(panels, 8)), dim3(512), lds, st, a, po);
+    hipLaunchKernelGGL((panel16_kernel<HH_, KIND, OBS, FLAGS, WT>), dim3(8 * SS * cdiv(panels, 8)), dim3(512), lds, st, a, po);
     return 0;
 }
 
@@ -865,20 +920,27 @@ int panel16(int kind, const Panel16Args& a, hipStream_t st, const PanelObs* obs)
     // wave instead of {value, tag} granules - the kernel with the observe-embedding tail, H = 512 only (the benchmarked instantiations)
     const char* hv = getenv("PP_PANEL_HANDOFF");
     const bool flags = hv && hv[0] == 'f' && obs && p.H == 512;
-#define PP_P16_GO(HH_, KIND)                                                                       \
-    do {                                                                                           \
-        if (obs && flags && HH_ == 512) PP_TRY((panel16_launch<512, KIND, true, true>(a, *obs, st)));  \
-        else if (obs) PP_TRY((panel16_launch<HH_, KIND, true>(a, *obs, st)));                      \
-        else PP_TRY((panel16_launch<HH_, KIND, false>(a, none, st)));                              \
+    // PP_STORE_WT (read per call as well): 16-byte write-through result stores; they need 16-byte aligned rows and address
+    // their buffers with 32-bit byte offsets - anything else keeps the plain stores
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const bool wt = store_wt_mode() && p.lda1 % 4 == 0 && p.lddy % 4 == 0 && al16(p.Hs) && al16(p.G) && al16(p.A1) && al16(p.dZ1) &&
+                    al16(p.DY) && (int64_t)p.B * 16 * p.H < ((int64_t)1 << 32) && (int64_t)p.B * 4 * std::max(p.lda1, p.lddy) < ((int64_t)1 << 32);
+#define PP_P16_GO(HH_, KIND, WT_)                                                                            \
+    do {                                                                                                     \
+        if (obs && flags && HH_ == 512) PP_TRY((panel16_launch<512, KIND, true, true, WT_>(a, *obs, st)));  \
+        else if (obs) PP_TRY((panel16_launch<HH_, KIND, true, false, WT_>(a, *obs, st)));                    \
+        else PP_TRY((panel16_launch<HH_, KIND, false, false, WT_>(a, none, st)));                            \
     } while (0)
-#define PP_P16_KIND(HH_)                                                  \
-    do {                                                                  \
-        if (kind == PP_HEAD_NORMAL_MIXTURE) PP_P16_GO(HH_, 0);            \
-        else if (kind == PP_HEAD_TRUNCNORMAL_MIXTURE) PP_P16_GO(HH_, 1);  \
-        else PP_P16_GO(HH_, 2);                                           \
+#define PP_P16_KIND(HH_, WT_)                                                  \
+    do {                                                                       \
+        if (kind == PP_HEAD_NORMAL_MIXTURE) PP_P16_GO(HH_, 0, WT_);            \
+        else if (kind == PP_HEAD_TRUNCNORMAL_MIXTURE) PP_P16_GO(HH_, 1, WT_);  \
+        else PP_P16_GO(HH_, 2, WT_);                                           \
     } while (0)
-    if (p.H == 512) PP_P16_KIND(512);
-    else PP_P16_KIND(1024);
+    if (p.H == 512 && wt) PP_P16_KIND(512, true);
+    else if (p.H == 512) PP_P16_KIND(512, false);
+    else if (wt) PP_P16_KIND(1024, true);
+    else PP_P16_KIND(1024, false);
 #undef PP_P16_KIND
 #undef PP_P16_GO
     PP_LAUNCH_CHECK("panel16");
