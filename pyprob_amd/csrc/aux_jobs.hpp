@@ -17,7 +17,7 @@ struct ColsumJob {
 
 constexpr int AUX_MAX_COLSUM = 48;   // (48 x 72 bytes of kernel arguments; with GroupedParams ~7.5 KB per launch)
 constexpr int AUX_COLSUM_ROWS = 64;    // rows per column-sum workgroup
-constexpr int AUX_OUTER_ROWS = 16;     // rows of dW_ih per workgroup of the outer-product job
+constexpr int AUX_OUTER_ROWS = 64;     // rows of dW_ih per workgroup of the outer-product job
 constexpr int AUX_TABLE_ROWS = 128;    // rows of W_ih per workgroup of the table-gradient job
 constexpr int AUX_DBSUM_ROWS = 256;
 
@@ -152,40 +152,57 @@ __device__ __forceinline__ void aux_colsum_block(const ColsumJob& jbin, int loca
 }
 
 __device__ __forceinline__ void aux_outer_block(const AuxJobs& j, int local) {
-    const int tid = threadIdx.x;
-    if (tid >= 256) return;
-    const int n = local * AUX_OUTER_ROWS + (tid >> 4), kq = tid & 15;
-    if (n >= j.N) return;
+    // 16 threads per row of dW_ih (16 consecutive columns per store), two rows per thread with their loads side by side:
+    // a 512-thread workgroup covers its 64 rows in one trip, every thread busy (16 rows per workgroup used half the threads
+    // of 128 workgroups for the benchmark's 2 048 rows); a 256-thread workgroup takes two trips
+    const int tid = threadIdx.x, kq = tid & 15, rpp = blockDim.x >> 4;
     constexpr int MAXJ = 16;   // 2 ne <= 256 columns
-    float acc[MAXJ];
-#pragma unroll
-    for (int q = 0; q < MAXJ; ++q) acc[q] = 0.0f;
     const int ne = j.ne, nd = j.nd, N = j.N, n_addr = j.n_addr, ncol = 2 * ne;
     const float* const gsum = j.gsum;
     const float* const params = j.params;
     const int64_t* const at = j.at;
-    for (int a = 0; a < n_addr; ++a) {
-        if (!aux_present(j, a)) continue;
-        const float* gs = gsum + (int64_t)a * 2 * N;
-        const float g0 = gs[n], g1 = gs[N + n];
-        const float* dt = params + at[a * PP_ADDR_TABLE_COLS + PP_AT_DTYPE_EMB];
-        const float* ad = params + at[a * PP_ADDR_TABLE_COLS + PP_AT_ADDR_EMB];
+    for (int rb = tid >> 4; rb < AUX_OUTER_ROWS; rb += 2 * rpp) {
+        const int na = local * AUX_OUTER_ROWS + rb, nb = na + rpp;
+        if (na >= N) return;
+        const bool vb = rb + rpp < AUX_OUTER_ROWS && nb < N;
+        const int nbc = vb ? nb : na;
+        // columns [c2, c2 + ne) and [c4, c4 + ne) are adjacent (c4 == c2 + ne): one run of 2 ne columns, single writer.
+        // The sums start from the words they are added to: those loads depend on nothing and leave with the first trip
+        // (behind the sums they were a fourth dependent trip to memory: the job was the last workgroup of the launch)
+        float* rowa = j.dW + (int64_t)na * j.ldw + j.c2;
+        float* rowb = j.dW + (int64_t)nbc * j.ldw + j.c2;
+        float acc[2][MAXJ];
+#pragma unroll
+        for (int q = 0; q < MAXJ; ++q) {
+            const int col = kq + 16 * q;
+            acc[0][q] = col < ncol ? rowa[col] : 0.0f;
+            acc[1][q] = col < ncol ? rowb[col] : 0.0f;
+        }
+        for (int a = 0; a < n_addr; ++a) {
+            if (!aux_present(j, a)) continue;
+            const float* gs = gsum + (int64_t)a * 2 * N;
+            const float g0a = gs[na], g1a = gs[N + na], g0b = gs[nbc], g1b = gs[N + nbc];
+            const float* dt = params + at[a * PP_ADDR_TABLE_COLS + PP_AT_DTYPE_EMB];
+            const float* ad = params + at[a * PP_ADDR_TABLE_COLS + PP_AT_ADDR_EMB];
+#pragma unroll
+            for (int q = 0; q < MAXJ; ++q) {
+                const int col = kq + 16 * q;
+                if (col < ncol) {
+                    const int k = col < ne ? col : col - ne;
+                    const float e = k < nd ? dt[k] : ad[k - nd];
+                    acc[0][q] += (col < ne ? g1a : g0a) * e;
+                    acc[1][q] += (col < ne ? g1b : g0b) * e;
+                }
+            }
+        }
 #pragma unroll
         for (int q = 0; q < MAXJ; ++q) {
             const int col = kq + 16 * q;
             if (col < ncol) {
-                const int k = col < ne ? col : col - ne;
-                const float e = k < nd ? dt[k] : ad[k - nd];
-                acc[q] += (col < ne ? g1 : g0) * e;
+                rowa[col] = acc[0][q];
+                if (vb) rowb[col] = acc[1][q];
             }
         }
-    }
-    // columns [c2, c2 + ne) and [c4, c4 + ne) are adjacent (c4 == c2 + ne): one run of 2 ne columns, single writer
-    float* row = j.dW + (int64_t)n * j.ldw + j.c2;
-#pragma unroll
-    for (int q = 0; q < MAXJ; ++q) {
-        const int col = kq + 16 * q;
-        if (col < ncol) row[col] += acc[q];
     }
 }
 

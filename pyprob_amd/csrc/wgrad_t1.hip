@@ -16,7 +16,7 @@
 // one launch instead of two, step 0.555 -> 0.519 ms; what bounds it there: DESIGN.md 8.2 (the float atomics).
 //
 // The reduction jobs of the backward pass (aux_jobs.hpp: column sums, table-column gradients, bias gradients, the loss) ride
-// behind the tiles as before.
+// behind the tiles as before (in a launch of one round: the derived jobs first, wgrad_t1()).
 #include "wgrad_t1.hpp"
 
 #include <stdlib.h>
@@ -118,7 +118,10 @@ __global__ __launch_bounds__(512, 4) void wgrad_t1_kernel(const WgradT1Args g, c
     const int aux_lo = g.aux_first ? 0 : g.n_blocks;
     const int bx = (int)blockIdx.x - (g.aux_first ? aux.n_blocks : 0);
     if ((int)blockIdx.x >= aux_lo && (int)blockIdx.x < aux_lo + aux.n_blocks) {
-        aux_job_run(aux, (int)blockIdx.x - aux_lo, lds);
+        // (behind the tiles the list is rotated: the jobs derived from the group sums first, the column sums last - wgrad_t1())
+        int jb = (int)blockIdx.x - aux_lo + g.aux_rot;
+        if (jb >= aux.n_blocks) jb -= aux.n_blocks;
+        aux_job_run(aux, jb, lds);
         if (g.trace && threadIdx.x == 0) {
             long long* tr = g.trace + 8 * blockIdx.x;
             tr[0] = t_start; tr[1] = wall_clock64(); tr[2] = 100; tr[3] = 0;
@@ -334,6 +337,16 @@ int wgrad_t1(const WgradT1Args& a, const AuxJobs* aux, hipStream_t st) {
     const int blocks = a.n_blocks + (aux ? j.n_blocks : 0);
     WgradT1Args t = a;
     t.aux_first = (aux && a.n_blocks > 512) ? 1 : 0;      // 2 workgroups x 256 CUs = one round
+    // A launch of one round, jobs included: in the per-workgroup timeline of the benchmark's step
+    // (tools/wg_trace_wgrad_single.py) workgroup id >= 256 shares its CU with workgroup id - 256, and a table-gradient job next to a full tile costs both ~3 us - with
+    // the list in its own order those pairs are the last workgroups of the launch. Rotated, the outer / table / bias jobs come
+    // first and land on the CUs that get no second workgroup or next to the short tiles the launch starts with; the column
+    // sums follow. A placement heuristic, not a guarantee: the pairing is the dispatcher's and was observed, and the gain was
+    // measured on the benchmark's shapes (H = 512 and 1024, B = 1024; 219 tiles + 281 jobs at H = 512) only - other one-round launches
+    // (small batches, PP_PANEL=0) run the same jobs in another order, checked for results, not for time.
+    // PP_WGRAD_JOBROT=0: the list's own order (read per call, for the A/B and the parity test).
+    const char* const env_rot = getenv("PP_WGRAD_JOBROT");
+    if (aux && blocks <= 512 && !(env_rot && atoi(env_rot) == 0)) t.aux_rot = j.cs_first[j.n_colsum];
     if (g_wgtrace && g_wgtrace_mode == 1 && blocks <= g_wgtrace_cap) t.trace = g_wgtrace;
     hipLaunchKernelGGL(wgrad_t1_kernel, dim3(blocks), dim3(512), 0, st, t, j);
     PP_LAUNCH_CHECK("wgrad_t1");

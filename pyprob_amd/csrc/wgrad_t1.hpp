@@ -25,6 +25,7 @@ struct WgradT1Args {
     WgradT1Prob p[WGRAD_T1_MAX];
     int n_prob, n_blocks;     // problems; workgroups of all tiles
     int aux_first;            // workgroups of the reduction jobs in front of the tiles (launches with more than one round of tiles) or behind
+    int aux_rot;              // the job that the first reduction workgroup runs (the list rotated; 0 = as laid out)
     long long* trace;         // debug (pp_debug_wgtrace, mode 1): per workgroup {start, end, problem, split, K loop done} wall-clock ticks
 };
 
