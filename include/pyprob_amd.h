@@ -538,6 +538,24 @@ int pp_is_fused(const pp_net* net, int32_t addr_id, int32_t n, const float* prio
 int pp_prior_draw(int32_t kind, const float* p0, int32_t p0_stride, const float* p1, int32_t p1_stride, int32_t n, uint64_t seed,
                   uint64_t offset, uint32_t stream_id, float* out /*dev [n]*/, void* stream);
 
+/* Observation blocks of vectorised trace generation (pyprob/nn/dataset.py:50-62 with the observe branch of pyprob/state.py,
+ * which draws distribution.sample() for every observe of a PRIOR_FOR_INFERENCE_NETWORK trace): one row of k values per trace,
+ *   out[r * k + e] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1),   r < n, e < k,
+ * p0 read at p0[r * p0_row_stride + e * p0_elem_stride], p1 likewise. Strides are element counts: (row, elem) = (0, 0) a scalar,
+ * (0, 1) one row shared by all traces (an image), (1, 0) one value per trace, (k, 1) a full [n, k] block; no caller materialises a
+ * parameter to [n, k]. Any k >= 1 and any 4-byte aligned `out`; nothing is written outside out[0 .. n * k - 1].
+ * Counter scheme (part of the ABI): element group q = e >> 2 of row r takes the Philox4x32-10 block with key `seed` and counter
+ * words (lo(offset + r), hi(offset + r), stream_id, q). Uniform element e uses word e & 3 of its group's block with
+ * pp_prior_draw's arithmetic (a + (b - a) * (word >> 8) * 2^-24, folded back to a where it rounds up to b). Normal elements
+ * 4q and 4q + 1 are the cosine and the sine branch of Box-Muller on words (0, 1), elements 4q + 2 and 4q + 3 the cosine and the
+ * sine branch on words (2, 3) (sqrtf / logf / cosf / sinf as in pp_prior_draw). Hence k = 1 is bit-identical to pp_prior_draw,
+ * element 0 of any k is pp_prior_draw's value of that row, and a row depends on (seed, offset + r, stream_id) only - not on n,
+ * nor on how rows were split into paths or chunks. Returns nonzero without a launch for kind not in {0, 1}, k < 1, n < 0, or a
+ * NULL p0 / p1 / out when n > 0; n == 0 returns 0 without a launch. */
+int pp_obs_draw(int32_t kind, const float* p0, int64_t p0_row_stride, int32_t p0_elem_stride, const float* p1, int64_t p1_row_stride,
+                int32_t p1_elem_stride, int32_t n, int32_t k, uint64_t seed, uint64_t offset, uint32_t stream_id,
+                float* out /*dev [n, k] contiguous*/, void* stream);
+
 /* lw[i] += scale * term[i] (e.g. -log q). */
 int pp_axpy(float scale, const float* term, float* lw, int32_t n, void* stream);
 

@@ -567,6 +567,15 @@ class PackedTraceDataset:
         return tr
 
 
+def default_chunk_traces(batch_size, obs_widths):
+    """Traces per chunk of online training when the caller names none: max(64 batches, 16384) traces, capped so that the chunk's
+    observation matrix stays within PP_PRIOR_CHUNK_BYTES (default 256 MiB; 16384 traces of a 3x224x224 image would be 9.8 GB) -
+    a multiple of the batch size, never below one batch. Scalar observables stay far below the cap."""
+    chunk = max(64 * batch_size, 16384)
+    cap = int(os.environ.get('PP_PRIOR_CHUNK_BYTES', str(256 << 20))) // (4 * max(int(sum(obs_widths or [])), 1))
+    return chunk if chunk <= cap else max(cap // batch_size, 1) * batch_size
+
+
 class VectorisedOnlineDataset:
     """OnlineDataset (pyprob/nn/dataset.py:50-62) without the one-forward()-per-trace loop: chunks of `chunk_traces`
     prior traces are generated in lock step (Model.prior_traces_packed) and served as an in-memory PackedTraceDataset;
@@ -605,7 +614,11 @@ class VectorisedOnlineDataset:
         if cols is None:
             return self._ds, resident
         self._single_path = resident is not None
-        return PackedTraceDataset.from_columns(self.obs_names, None, *cols), resident
+        widths = getattr(self._model, '_last_prior_obs_widths', None)      # values per name (an image: its element count)
+        first = self.__dict__.setdefault('_widths', widths)
+        if widths != first:
+            raise RuntimeError('observation widths {} of this chunk differ from the first chunk\'s {}'.format(widths, first))
+        return PackedTraceDataset.from_columns(self.obs_names, widths, *cols), resident
 
     def refresh(self):
         """Serve the next chunk of fresh prior traces (the one `start_prefetch` prepared, if any)."""
@@ -679,8 +692,9 @@ def save_dataset(model, dataset_dir, num_traces, num_traces_per_file, obs_names=
         path = os.path.join(dataset_dir, 'pyprob_traces_packed_{:06d}_{}'.format(shard, n))
         with PackedTraceWriter(path, names) as w:
             if vectorised:
-                w.add_columns(*model.prior_traces_packed(n, names, *args, return_types=True,
-                                                         prior_inflation=prior_inflation, **kwargs))
+                cols = model.prior_traces_packed(n, names, *args, return_types=True, prior_inflation=prior_inflation, **kwargs)
+                w.obs_widths = [int(k) for k in model._last_prior_obs_widths]      # (add_columns alone can only guess an equal split)
+                w.add_columns(*cols)
             else:
                 for _ in range(n):
                     w.add_trace(next(gen))

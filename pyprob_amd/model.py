@@ -224,7 +224,7 @@ class Model:
             return None
 
     # attributes the Model base class itself keeps on the instance (never read by a program as constants)
-    _BASE_ATTRS = frozenset(('_inference_network', '_lockstep_plans', '_lock_step_ok', '_last_prior_resident', '_plan_code_cache',
+    _BASE_ATTRS = frozenset(('_inference_network', '_lockstep_plans', '_lock_step_ok', '_last_prior_resident', '_last_prior_obs_widths', '_plan_code_cache',
                              '_plan_key_cache', '_plan_indirect_cache', '_plan_indirect_pairs'))
 
     @staticmethod
@@ -730,7 +730,9 @@ class Model:
         self._last_prior_resident = ls.columns_device(obs_names)      # (device chunks of single-statement programs)
         if resident_only and self._last_prior_resident is not None:
             return None          # the caller trains from the device columns: no host copy of the chunk
-        return ls.columns(obs_names, return_types)
+        cols = ls.columns(obs_names, return_types)
+        self._last_prior_obs_widths = list(ls.obs_widths)      # values per observe name: W = their sum (images, k-vectors)
+        return cols
 
     def _lock_step_safe(self, observe, *args, **kwargs):
         """Can this program run with all particles in lock step? Decided once per model by a probe of 4 particles: a
@@ -864,11 +866,13 @@ class Model:
             try:
                 self.prior_traces_packed(8, list(observe_embeddings.keys()))
                 import os
+                from .dataset import default_chunk_traces
+                chunk = prior_chunk_traces or default_chunk_traces(batch_size, self._last_prior_obs_widths)
                 # the chunk is drawn on the training device when there is one (pp_prior_draw; PP_PRIOR_DEVICE=0: host draws)
                 gen_dev = device if (str(device).startswith('cuda') and torch.cuda.is_available() and
                                      os.environ.get('PP_PRIOR_DEVICE', '1') != '0') else 'cpu'
                 dataset = VectorisedOnlineDataset(self, list(observe_embeddings.keys()),
-                                                  chunk_traces=prior_chunk_traces or max(64 * batch_size, 16384),
+                                                  chunk_traces=chunk,
                                                   prior_inflation=prior_inflation, device=gen_dev)
             except Exception as exc:   # noqa: BLE001 - any failure of the probe means "not lock-step safe"
                 if vectorised_prior:

@@ -19,6 +19,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     dist_logweight  the log-weight terms of every distribution family   pyprob/state.py:113-115, 147-149, 211
     dist_draw       draws of every distribution family (Philox)       pyprob/state.py:191-201, 218-221
     mix_logweight   Mixture.log_prob as a log-weight term               pyprob/distributions/mixture.py:38-45
+    obs_draw        the synthetic observation block of n prior traces   pyprob/nn/dataset.py:50-62, state.py observe branch
     mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -61,6 +62,7 @@ _lib.define('is_fused(Tensor(a!) workspace, int net, int addr_id, Tensor? prior,
             'Tensor?[] p1, int[] p1_strides, Tensor?[] x, float[] scales, int[] flags, Tensor(b!) value, Tensor(c!) lw, '
             'bool overwrite, int seed, int offset, Tensor(d!)? stats_scratch) -> Tensor')
 _lib.define('prior_draw(int kind, Tensor p0, Tensor p1, int n, int seed, int offset, int stream_id) -> Tensor')
+_lib.define('obs_draw(int kind, Tensor p0, Tensor p1, int n, int k, int seed, int offset, int stream_id) -> Tensor')
 _lib.define('log_prob(int kind, Tensor p0, int p0_stride, Tensor? p1, int p1_stride, Tensor x, int n) -> Tensor')
 _lib.define('logweight_terms(Tensor(a!) lw, int[] kinds, Tensor?[] p0, int[] p0_strides, Tensor?[] p1, int[] p1_strides, '
             'Tensor[] x, float[] scales, bool overwrite) -> ()')
@@ -396,6 +398,38 @@ def _prior_draw_hip(kind, p0, p1, n, seed, offset, stream_id):
     return out
 
 
+def obs_draw_strides(t, n, k, name='p'):
+    """(row stride, element stride) with which pp_obs_draw reads a parameter of n rows of k values: a scalar (one element) ->
+    (0, 0); [k] or [1, k] - one row shared by all traces -> (0, 1); [n] or [n, 1] - one value per trace -> (1, 0); [n, k] ->
+    (k, 1). A 1-D tensor of k elements is the shared row also when n == k (callers pass per-trace values as [n, 1])."""
+    shape = tuple(t.shape)
+    if t.numel() == 1:
+        return 0, 0
+    if shape in ((k,), (1, k)):
+        return 0, 1
+    if shape in ((n,), (n, 1)):
+        return 1, 0
+    if shape == (n, k):
+        return k, 1
+    raise RuntimeError('pyprob_hip::obs_draw: %s must be a scalar, [k], [n], [n, 1] or [n, k] (n = %d, k = %d), got %s'
+                       % (name, n, k, list(shape)))
+
+
+def _obs_draw_hip(kind, p0, p1, n, k, seed, offset, stream_id):
+    lib = L.load()
+    _same_device(p0, p1)
+    n, k = int(n), int(k)
+    if n < 0 or k < 1:
+        raise RuntimeError('pyprob_hip::obs_draw: n >= 0 rows of k >= 1 values, got n = %d, k = %d' % (n, k))
+    (r0, e0), (r1, e1) = obs_draw_strides(_f32(p0, 'p0'), n, k, 'p0'), obs_draw_strides(_f32(p1, 'p1'), n, k, 'p1')
+    out = torch.empty((n, k), dtype=torch.float32, device=p0.device)
+    with torch.cuda.device(p0.device):
+        rc = lib.pp_obs_draw(int(kind), p0.data_ptr(), r0, e0, p1.data_ptr(), r1, e1, n, k, int(seed), int(offset),
+                             int(stream_id) & 0xFFFFFFFF, out.data_ptr(), _stream(p0))
+    L.check(rc, 'pp_obs_draw')
+    return out
+
+
 def _log_prob_hip(kind, p0, p0_stride, p1, p1_stride, x, n):
     lib = L.load()
     _same_device(x, p0, p1)
@@ -568,6 +602,7 @@ _lib.impl('is_statement_rows', _is_statement_rows_hip, 'CUDA')
 _lib.impl('is_step_net', _is_step_net_hip, 'CUDA')
 _lib.impl('is_fused', _is_fused_hip, 'CUDA')
 _lib.impl('prior_draw', _prior_draw_hip, 'CUDA')
+_lib.impl('obs_draw', _obs_draw_hip, 'CUDA')
 _lib.impl('log_prob', _log_prob_hip, 'CUDA')
 _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')

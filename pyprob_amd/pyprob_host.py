@@ -392,7 +392,7 @@ def optimize_online(net, dataset, num_traces, batch_size, learning_rate_init, le
                     save_file_name_prefix, save_every_sec, stop_with_bad_loss, optimizer_type, momentum):
     """`InferenceNetwork.optimize` for an OnlineDataset with Adam and no learning-rate schedule, validation set, log file or
     process group (those take pyprob's own loop). Returns False when the program's prior cannot be generated in lock step."""
-    from .dataset import VectorisedOnlineDataset
+    from .dataset import VectorisedOnlineDataset, default_chunk_traces
     from pyprob import PriorInflation
     if not net._layers_initialized:                                                          # inference_network.py:382-385
         net._init_layers_observe_embedding(net._observe_embeddings, example_trace=dataset.__getitem__(0))
@@ -409,8 +409,9 @@ def optimize_online(net, dataset, num_traces, batch_size, learning_rate_init, le
         except Exception:   # noqa: BLE001 - any failure of the probe means "not lock-step safe"
             return False
         gen_dev = net._hip_device if str(net._hip_device).startswith('cuda') and os.environ.get('PP_PRIOR_DEVICE', '1') != '0' else 'cpu'
-        vds = VectorisedOnlineDataset(ad, obs_names, chunk_traces=max(64 * batch_size, 16384), prior_inflation=inflation,
-                                      device=gen_dev)
+        # (the probe left the observables' widths: an image observable is chunked by bytes as well as by traces)
+        vds = VectorisedOnlineDataset(ad, obs_names, chunk_traces=default_chunk_traces(batch_size, ad._last_prior_obs_widths),
+                                      prior_inflation=inflation, device=gen_dev)
         _run_view_optimize(net, vds, None, num_traces, batch_size, learning_rate_init, learning_rate_end, weight_decay, num_traces_end,
                            save_file_name_prefix, save_every_sec, stop_with_bad_loss, optimizer_type, momentum,
                            pyprob.LearningRateScheduler.NONE, None, None, None)

@@ -615,7 +615,19 @@ class PriorLockStep(PathExecutor):
     """n PRIOR traces generated together (trace mode PRIOR_FOR_INFERENCE_NETWORK, pyprob/nn/dataset.py:50-62 run n
     times): every `sample` draws from the prior for the particles of the current control-flow path, every `observe`
     draws the synthetic observation; per path the statement list is recorded, so the traces come out directly as the
-    ragged columns a minibatch is packed from (no Trace objects)."""
+    ragged columns a minibatch is packed from (no Trace objects).
+
+    An observe records one ROW per particle: k values, k = 1 for a scalar observable, k = the element count of an image or
+    vector observable. k and the role of every distribution parameter follow one rule:
+      * a ParticleTensor whose leading dimension is the execution's width is PER PARTICLE, its trailing dimensions are the event;
+      * a plain tensor or a Python number is SHARED by all particles and its whole shape is the event;
+      * the one exception: a 1-D tensor of `width` elements, of either type, is one scalar per particle;
+      * k = the element count of the events' broadcast shape. Events that do not broadcast raise RuntimeError, and so does a plain
+        tensor of two or more dimensions whose leading dimension equals the width next to a per-particle parameter (shared and per
+        particle are both plausible readings and give different observations) - the caller's probe then generates per trace.
+    A name keeps its k in every path of a chunk. Records of k > 1 are [n, k]; on a device their Normal / Uniform rows are drawn by
+    pp_obs_draw from the parameters where they lie (no [n, k] copy of a shared image or a per-particle scalar), other families
+    and the CPU device draw with torch. Scalar records and their draws are what they were before rows existed."""
     mode = 'prior'
     compact = True      # a re-run path draws and computes for its own particles only (GUMM: 1.3 n instead of 8 n work)
 
@@ -626,6 +638,8 @@ class PriorLockStep(PathExecutor):
         # step reads them; the key comes from torch's generator, so pyprob.seed / torch.manual_seed reproduce a chunk
         self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self._consts = {}
+        self.obs_k = {}               # observe name -> values per particle (the same in every path)
+        self.obs_widths = None        # [k per name of obs_names], set by columns()
         super().__init__(n, torch.device(device))
 
     def _param(self, v):
@@ -677,18 +691,18 @@ class PriorLockStep(PathExecutor):
         self._active_rows = None
 
     def _store(self, full, new):
-        """Write this execution's (active) elements of `new` [width] into the full-size record `full` [n] (None: create;
+        """Write this execution's (active) rows of `new` [width] or [width, k] into the full-size record `full` [n] / [n, k] (None: create;
         elements of particles that never execute the statement stay uninitialised and are never read)."""
         new = new.to(self.dev)
         if self.base is None and self.active is None:
             return new
-        if new.dim() and new.stride(0) == 0:      # one value for every particle (e.g. the bounds of Uniform(-1, 1))
+        if new.dim() and new.stride(0) == 0:      # one value (or one row) for every particle (e.g. the bounds of Uniform(-1, 1))
             if full is None:
-                return new[:1].expand(self.n)
-            if full.stride(0) == 0 and bool(full[0] == new[0]):
+                return new[:1].expand((self.n,) + tuple(new.shape[1:]))
+            if full.stride(0) == 0 and torch.equal(full[0], new[0]):
                 return full
         if full is None:
-            full = torch.empty(self.n, dtype=new.dtype, device=self.dev)
+            full = torch.empty((self.n,) + tuple(new.shape[1:]), dtype=new.dtype, device=self.dev)
         elif full.dim() and full.stride(0) == 0:
             full = full.contiguous()              # (a broadcast parameter recorded by an earlier path)
         if self.active is None:
@@ -731,20 +745,127 @@ class PriorLockStep(PathExecutor):
             self.seq.append((j, address))
         return ParticleTensor.wrap(draw)
 
+    def _obs_event(self, name, distribution):
+        """(event shape, [(parameter as a plain tensor, per particle?, its event shape)]) of an observe by the class rule; the
+        parameter list is None for families other than Normal / Uniform (their torch distribution carries the parameters)."""
+        if distribution.name == 'Normal':
+            raw = (distribution._loc, distribution._scale)
+        elif distribution.name == 'Uniform':
+            raw = (distribution._low, distribution._high)
+        else:     # the family's parameters as torch broadcast them: a leading `width` reads as per particle
+            shape = tuple(distribution._torch_dist.batch_shape)
+            per = len(shape) >= 1 and shape[0] == self.width
+            return (shape[1:] if per else shape), None
+        roles = []
+        with torch._C.DisableTorchFunctionSubclass():
+            for p in raw:
+                particle = isinstance(p, ParticleTensor)
+                t = p.as_subclass(torch.Tensor) if torch.is_tensor(p) else torch.as_tensor(p, dtype=torch.float32)
+                if t.numel() == 1:
+                    roles.append((t.reshape(()), False, ()))
+                elif t.dim() == 1 and t.shape[0] == self.width:
+                    roles.append((t, True, ()))
+                elif particle and t.shape[0] == self.width:
+                    roles.append((t, True, tuple(t.shape[1:])))
+                else:
+                    roles.append((t, False, tuple(t.shape)))
+        if any(per for _, per, _ in roles):
+            for t, per, ev in roles:
+                if not per and len(ev) >= 2 and ev[0] == self.width:
+                    raise RuntimeError('observe {!r}: a plain tensor of shape {} next to a per-particle parameter can be read as '
+                                       'shared or as one row per particle ({} particles)'.format(name, list(ev), self.width))
+        try:
+            event = tuple(torch.broadcast_shapes(*[ev for _, _, ev in roles]))
+        except RuntimeError:
+            raise RuntimeError('observe {!r}: the event shapes {} of the distribution parameters do not broadcast'.format(
+                name, [list(ev) for _, _, ev in roles])) from None
+        return event, roles
+
+    def _draw_rows(self, name, distribution, stream_id, event, roles):
+        """[width, k] synthetic observations, k = the element count of `event` > 1."""
+        k = 1
+        for d in event:
+            k *= int(d)
+        w = self.width
+        if roles is None:       # other families: torch, with the parameters as the program built them
+            td = distribution._torch_dist
+            draw = td.sample((w,)) if tuple(td.batch_shape) == event else td.sample()
+            if draw.numel() != w * k:
+                raise RuntimeError('observe {!r}: {} values drawn for {} particles of {} values'.format(name, draw.numel(), w, k))
+            return draw.as_subclass(torch.Tensor).reshape(w, k).float().to(self.dev)
+        if self.dev.type != 'cpu':
+            from .ops import ops
+            ps = []
+            for t, per, ev in roles:
+                t = t.to(self.dev, torch.float32)
+                if t.numel() == 1:
+                    t = self._param(t) if t.device.type == 'cpu' else t.reshape(1)
+                elif per and not ev:
+                    t = t.reshape(w, 1)                                  # one value per particle: row stride 1, element stride 0
+                elif per:       # [w, k] where the event is the full one (a partial broadcast such as [w, 4, 1] is expanded)
+                    t = t.expand((w,) + event).reshape(w, k) if tuple(ev) != event else t.reshape(w, k)
+                else:           # one shared row of k values
+                    t = t.expand(event).reshape(1, k)
+                ps.append(t.contiguous())
+            return ops.obs_draw(0 if distribution.name == 'Normal' else 1, ps[0], ps[1], w, k, self.seed, self.path_id << 32, stream_id)
+        ps = []
+        for t, per, ev in roles:
+            t = t.to(self.dev, torch.float32)
+            ps.append(t.reshape((w,) + (1,) * (len(event) - len(ev)) + tuple(ev)) if per else t)
+        cls = torch.distributions.Normal if distribution.name == 'Normal' else torch.distributions.Uniform
+        td = cls(ps[0], ps[1], validate_args=False)
+        draw = td.sample() if any(per for _, per, _ in roles) else td.sample((w,))
+        return draw.expand((w,) + event).reshape(w, k).float()
+
+    def _obs_width(self, name, k):
+        if self.obs_k.setdefault(name, k) != k:
+            raise RuntimeError('observe {!r}: {} values per trace on this control-flow path, {} on an earlier one'.format(
+                name, k, self.obs_k[name]))
+
     def observe_statement(self, name, distribution, value):
+        """`value`: what the program (value=) or the caller (observe={..}) fixed, else None: the observation is drawn."""
         i = self.observes
         self.observes += 1
+        scalar_sample = value is None and distribution is not None and distribution.name != 'Mixture'
         if i >= self.replay_observes:
             while len(self.obs_log) <= i:
                 self.obs_log.append({})
-            if value is None:
-                draw = self._draw(distribution, 0x4000 + i)
+            event, roles = self._obs_event(name, distribution) if distribution is not None and distribution.name != 'Mixture' else ((), None)
+            k = 1
+            for d in event:
+                k *= int(d)
+            if value is not None:
+                v = torch.as_tensor(value, dtype=torch.float32).as_subclass(torch.Tensor)
+                if k == 1 and v.numel() not in (1, self.width):
+                    event, k = tuple(v.shape), v.numel()          # (a fixed vector under scalar parameters)
+            if k == 1:
+                if value is not None:
+                    draw = v.reshape(-1).to(self.dev).expand(self.width)
+                elif scalar_sample:
+                    # the scalar route as it always was: one sample() of the program's distribution object (torch's generator)
+                    draw = torch.as_tensor(distribution.sample(), dtype=torch.float32).reshape(-1).to(self.dev).expand(self.width)
+                else:
+                    draw = self._draw(distribution, 0x4000 + i)
+                shaped = draw
             else:
-                draw = torch.as_tensor(value, dtype=torch.float32).reshape(-1).to(self.dev).expand(self.width)
+                if value is None:
+                    draw = self._draw_rows(name, distribution, 0x4000 + i, event, roles)
+                elif v.numel() == k:                              # one shared row (stride 0)
+                    draw = v.reshape(1, k).to(self.dev).expand(self.width, k)
+                elif v.numel() == self.width * k:
+                    draw = v.reshape(self.width, k).to(self.dev)
+                else:
+                    raise RuntimeError('observe {!r}: a value of {} elements for {} particles of {} values'.format(
+                        name, v.numel(), self.width, k))
+                shaped = draw.reshape((self.width,) + event)
+            self._obs_width(name, k)
             self.obs_log[i][name] = self._store(self.obs_log[i].get(name), draw)
-            out = draw
+            out = shaped
         else:
-            out = self._view(self.obs_log[i][name])
+            rec = self.obs_log[i][name]
+            if scalar_sample and rec.dim() == 1:
+                distribution.sample()     # (the scalar route draws on every execution, replays included: chunks keep their bits)
+            out = self._view(rec)
         if name is not None:
             self.obs_seq.append((i, name))
         return ParticleTensor.wrap(out)
@@ -783,8 +904,9 @@ class PriorLockStep(PathExecutor):
 
     def columns(self, obs_names, return_types=False):
         """(trace_len [n], address table [(address, distribution, n_categories)], address ids [R], values [R],
-        prior [R, 2], obs [n, W]) as numpy arrays; traces are grouped by control-flow path. return_types appends
-        (type index per trace, [address-id sequence per type]): every path is one trace type."""
+        prior [R, 2], obs [n, W]) as numpy arrays; traces are grouped by control-flow path. W = the sum of the names' widths in
+        `obs_names` order, which are left in `self.obs_widths`. return_types appends (type index per trace, [address-id sequence
+        per type]): every path is one trace type."""
         import numpy as np
         table, ids_of = [], {}
         lens, ids, vals, pri, obs = [], [], [], [], []
@@ -821,10 +943,18 @@ class PriorLockStep(PathExecutor):
             vals.append(v.reshape(-1))
             pri.append(p.reshape(-1, 2))
             by_name = dict((name, i) for i, name in obs_seq)
-            o = np.empty((m, len(obs_names)), np.float32)
-            for k, name in enumerate(obs_names):
-                o[:, k] = column(self.obs_log[by_name[name]][name])
+            widths = [self.obs_k[name] if name in by_name else 1 for name in obs_names]
+            o = np.empty((m, sum(widths)), np.float32)
+            c = 0
+            for name, w in zip(obs_names, widths):
+                rec = self.obs_log[by_name[name]][name]
+                if rec.dim() == 1:
+                    o[:, c] = column(rec)
+                else:             # rows of w values; a row shared by all particles is copied to the host once
+                    o[:, c:c + w] = rec[0].cpu().numpy() if rec.stride(0) == 0 else rec[rows].cpu().numpy()
+                c += w
             obs.append(o)
+            self.obs_widths = widths
         out = (np.concatenate(lens), table, np.concatenate(ids), np.concatenate(vals).astype(np.float32),
                np.concatenate(pri).astype(np.float32), np.concatenate(obs).astype(np.float32))
         return out + ((np.concatenate(type_of), seqs),) if return_types else out
@@ -920,15 +1050,14 @@ def observe(distribution, value=None, name=None, address=None):
         value = _current_trace_observed_variables[name]
     elif value is not None:
         value = torch.as_tensor(value, dtype=torch.float32)
-    elif _trace_mode == TraceMode.PRIOR_FOR_INFERENCE_NETWORK and distribution is not None and not (
-            _lock_step is not None and _lock_step.mode == 'prior' and distribution.name == 'Mixture'):
+    elif _lock_step is not None and _lock_step.mode == 'prior':
+        value = None          # (a lock-step prior run: one draw per particle by the executor, PriorLockStep.observe_statement)
+    elif _trace_mode == TraceMode.PRIOR_FOR_INFERENCE_NETWORK and distribution is not None:
         value = distribution.sample()
     else:
-        value = None          # (a Mixture of a lock-step prior run: one draw per particle by the executor, PriorLockStep._draw)
+        value = None
     if _lock_step is not None and _lock_step.mode == 'prior':
-        given = _current_trace_observed_variables.get(name) if name in _current_trace_observed_variables else (
-            None if value is None else value)
-        return _lock_step.observe_statement(name, distribution, given)
+        return _lock_step.observe_statement(name, distribution, value)
     if _coroutine is not None and value is not None and _trace_mode == TraceMode.POSTERIOR:
         _coroutine.observe(distribution, value)       # the weight term joins the next round's likelihood kernels
         _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
