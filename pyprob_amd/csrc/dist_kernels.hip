@@ -25,14 +25,12 @@ struct DistTerms {
 __device__ __forceinline__ float dist_log_prob(const DistTerm& d, int64_t r) {
     const float x = d.x[r * d.sx];
     if (d.kind == 2) return x;
-    if (d.kind == 5) {       // Categorical: row r * s[0] of C = s[1] probabilities (is_kernels.hip's term_log_prob)
+    if (d.kind == 5) {       // Categorical: row r * s[0] of C = s[1] probabilities; a fractional index is outside the support
         const float* p = d.p[0] + r * d.s[0];
-        const int C = d.s[1];
+        const int C = d.s[1], k = (int)x;
         float sum = 0.0f;
         for (int c = 0; c < C; ++c) sum += p[c];
-        const int k = (int)x;
-        if (!(x >= 0.0f) || k >= C || (float)k != x) return -INFINITY;
-        return logf(fminf(fmaxf(p[k] / sum, kFp32Eps), 1.0f - kFp32Eps));
+        return (!(x >= 0.0f) || k >= C || (float)k != x) ? -INFINITY : categorical_lp(p, sum, k);
     }
     return scalar_log_prob(d.kind, d.p, d.s, r, x);
 }
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(256) void dist_logweight_kernel(DistTerms T, float*
 }
 
 // out[r] ~ family(params_r). Philox key = seed, counter = offset + r, stream id per statement (prior_draw_kernel's scheme);
-// kinds 0 / 1 are prior_draw_kernel's arithmetic on the same first block, so the values are bit-identical to pp_prior_draw.
+// kinds 0 / 1 call prior_draw_kernel's normal_draw / uniform_draw on the same first block: pp_prior_draw's values, bit for bit.
 // One instance per kind: the rejection samplers' registers do not weigh on the transform samplers' occupancy.
 template <int KIND>
 __global__ __launch_bounds__(256) void dist_draw_kernel(DistTerm d, const int64_t* __restrict__ rows, int m, uint64_t seed,
@@ -62,20 +60,15 @@ __global__ __launch_bounds__(256) void dist_draw_kernel(DistTerm d, const int64_
         const int64_t r = rows ? rows[j] : (int64_t)j;
         Philox rng(seed, offset + (uint64_t)r, stream_id);
         float v;
-        if (KIND == 5) {          // Categorical: the first c whose cumulative probability exceeds u * sum
+        if (KIND == 5) {          // Categorical: row r * s[0] of C = s[1] probabilities
             const float* p = d.p[0] + r * d.s[0];
             const int C = d.s[1];
             uint32_t w[4];
             rng.next(w);
             float sum = 0.0f;
             for (int c = 0; c < C; ++c) sum += p[c];
-            const float target = u01(w[0]) * sum;
-            float cum = 0.0f;
-            int k = C - 1;
-            for (int c = 0; c < C; ++c) {
-                cum += p[c];
-                if (target < cum) { k = c; break; }
-            }
+            int k;
+            categorical_pick(p, C, u01(w[0]) * sum, k);
             v = (float)k;
         } else {
             const float a = d.p[0][r * d.s[0]];
@@ -154,7 +147,7 @@ __global__ __launch_bounds__(256) void mix_logweight_kernel(MixArgs M, const flo
         bool nan = false;
         for (int k = 0; k < K; ++k) {
             const float q = w[k] / sum;
-            const float lq = q == q ? logf(fminf(fmaxf(q, kFp32Eps), 1.0f - kFp32Eps)) : NAN;
+            const float lq = q == q ? log_clamped(q) : NAN;
             const float t = lq + scalar_log_prob(M.c[k].kind, M.c[k].p, M.c[k].s, r, x);
             if (t != t) {
                 nan = true;
@@ -172,7 +165,7 @@ __global__ __launch_bounds__(256) void mix_logweight_kernel(MixArgs M, const flo
 }
 
 // out[r] ~ Mixture for the lanes whose selected component has kind KIND (the host launches one instance per distinct kind of
-// the mixture). Selection: first word of Philox(seed, offset + r, stream_id | 0x80000000), dist_draw_kernel<5>'s rule on the
+// the mixture). Selection: first word of Philox(seed, offset + r, stream_id | 0x80000000), dist_draw_kernel<5>'s categorical_pick on the
 // unclamped weights (Categorical(probs).sample(), mixture.py:47-50). Draw: Philox(seed, offset + r, stream_id) - dist_draw_kernel's
 // stream, so K = 1 or K identical components give pp_dist_draw's values. The selected component's parameters are picked in a
 // wave-uniform loop over the argument block under the lane mask (no per-lane index into it).
@@ -188,13 +181,8 @@ __global__ __launch_bounds__(256) void mix_draw_kernel(MixArgs M, const int64_t*
         const float* p = M.probs + r * M.sp;
         float sum = 0.0f;
         for (int k = 0; k < K; ++k) sum += p[k];
-        const float target = u01(w[0]) * sum;
-        float cum = 0.0f;
-        int sel = K - 1;
-        for (int k = 0; k < K; ++k) {
-            cum += p[k];
-            if (target < cum) { sel = k; break; }
-        }
+        int sel;
+        categorical_pick(p, K, u01(w[0]) * sum, sel);
         float a = 0.0f, b = 0.0f, c = 0.0f, d = 0.0f;
         bool mine = false;
         for (int k = 0; k < K; ++k) {

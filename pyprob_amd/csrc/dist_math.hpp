@@ -18,7 +18,7 @@ constexpr float kPi = 3.14159265358979323846f;
 // torch.xlogy(a, x): 0 where a == 0 (x not NaN), a * log(x) otherwise
 __device__ __forceinline__ float xlogyf(float a, float x) { return (a == 0.0f && x == x) ? 0.0f : a * logf(x); }
 
-// ---- log-densities (kinds 6-13; 0-5 are is_kernels.hip's term_log_prob, restated here for the one-launch pass) ----------
+// ---- log-densities (kinds 6-13; the formulas of kinds 0-5 are is_draw.hpp's, shared with is_kernels.hip's term_log_prob) ------
 
 // 6 Exponential(rate): log(rate) - rate x, support [0, inf)
 __device__ __forceinline__ float lp_exponential(float rate, float x) { return x >= 0.0f ? logf(rate) - rate * x : -INFINITY; }
@@ -37,17 +37,11 @@ __device__ __forceinline__ float lp_beta(float c1, float c0, float low, float hi
     return (xlogyf(c1 - 1.0f, y) + xlogyf(c0 - 1.0f, 1.0f - y)) + lgammaf(c1 + c0) - (lgammaf(c1) + lgammaf(c0));
 }
 
-// torch Normal.log_prob
-__device__ __forceinline__ float lp_normal(float loc, float scale, float x) {
-    const float t = x - loc;
-    return -(t * t) / (2.0f * (scale * scale)) - logf(scale) - kHalfLog2Pi;
-}
-
 // 9 LogNormal(loc, scale): Normal.log_prob(log x) - log x (ExpTransform's Jacobian), support (0, inf)
 __device__ __forceinline__ float lp_lognormal(float loc, float scale, float x) {
     if (!(x > 0.0f)) return -INFINITY;
     const float y = logf(x);
-    return lp_normal(loc, scale, y) - y;
+    return normal_lp(loc, scale, y) - y;
 }
 
 // 10 Weibull(scale l, concentration k) = Exponential(1) pushed through x -> x^(1/k) -> l x (torch's TransformedDistribution):
@@ -103,17 +97,10 @@ __device__ __forceinline__ float lp_truncnormal(float mu, float sd, float low, f
 __device__ __forceinline__ float scalar_log_prob(int kind, const float* const* p, const int* s, int64_t r, float x) {
     const float a = p[0][r * s[0]];
     switch (kind) {
-        case 0: return lp_normal(a, p[1][r * s[1]], x);
-        case 1: {
-            const float b = p[1][r * s[1]];
-            return (x >= a && x < b) ? -logf(b - a) : -INFINITY;
-        }
-        case 3: return (x >= 0.0f && x == floorf(x)) ? (x == 0.0f ? 0.0f : x * logf(a)) - a - lgammaf(x + 1.0f) : -INFINITY;
-        case 4: {
-            if (!(x == 0.0f || x == 1.0f)) return -INFINITY;
-            const float q = fminf(fmaxf(a, kFp32Eps), 1.0f - kFp32Eps);
-            return x * logf(q) + (1.0f - x) * log1pf(-q);
-        }
+        case 0: return normal_lp(a, p[1][r * s[1]], x);
+        case 1: return uniform_lp(a, p[1][r * s[1]], x);
+        case 3: return (x >= 0.0f && x == floorf(x)) ? poisson_lp(a, x) : -INFINITY;      // (guarded here: is_draw.hpp)
+        case 4: return (x == 0.0f || x == 1.0f) ? bernoulli_lp(a, x) : -INFINITY;
         case 6: return lp_exponential(a, x);
         case 7: return lp_gamma(a, p[1][r * s[1]], x);
         case 8: return lp_beta(a, p[1][r * s[1]], p[2][r * s[2]], p[3][r * s[3]], x);
@@ -350,12 +337,11 @@ __device__ __forceinline__ float draw_one(float a, float b, float c, float d, Ph
     switch (KIND) {
         case 0:
             rng.next(w);
-            v = a + b * sqrtf(-2.0f * logf(u01(w[0]))) * cosf(kTwoPi * u01(w[1]));
+            v = normal_draw(a, b, w[0], w[1]);
             break;
         case 1:
             rng.next(w);
-            v = a + (b - a) * (((float)(w[0] >> 8)) * (1.0f / 16777216.0f));
-            v = v < b ? v : a;
+            v = uniform_draw(a, b, w[0]);
             break;
         case 3: v = poisson_draw(a, rng); break;
         case 4:

@@ -34,6 +34,55 @@ struct Philox {
 };
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
+// ---- the five network families (kinds 0, 1, 3, 4, 5 of include/pyprob_amd.h): ONE definition per formula, as torch evaluates
+// them in fp32. Every log-weight and draw kernel of is_kernels.hip, dist_kernels.hip (through dist_math.hpp) and obs_draw.hip
+// calls these, so the values of the entry points agree bit for bit by construction.
+// SUPPORT GUARDS are not part of the Poisson, Bernoulli and Categorical forms: they stay at the call sites and differ.
+// term_log_prob (pp_logweight_*, pp_is_fused) scores Poisson and Bernoulli unguarded and truncates the Categorical index;
+// scalar_log_prob / dist_log_prob (pp_dist_logweight, pp_mix_logweight) give -inf for a negative or fractional Poisson value, a
+// Bernoulli value outside {0, 1} and a fractional Categorical index.
+
+// torch.distributions.Normal.log_prob
+__device__ __forceinline__ float normal_lp(float loc, float scale, float x) {
+    const float t = x - loc;
+    return -(t * t) / (2.0f * scale * scale) - logf(scale) - kHalfLog2Pi;
+}
+// Uniform(low, high), support [low, high)
+__device__ __forceinline__ float uniform_lp(float low, float high, float x) {
+    return (x >= low && x < high) ? -logf(high - low) : -INFINITY;
+}
+// Poisson(rate) at a count v: xlogy(v, rate) - rate - lgamma(v + 1)
+__device__ __forceinline__ float poisson_lp(float rate, float v) {
+    return (v == 0.0f ? 0.0f : v * logf(rate)) - rate - lgammaf(v + 1.0f);
+}
+// Bernoulli(probs) at v in {0, 1}: probs clamped to [eps, 1 - eps] (probs_to_logits), v log p + (1 - v) log(1 - p)
+__device__ __forceinline__ float bernoulli_lp(float probs, float v) {
+    const float q = fminf(fmaxf(probs, kFp32Eps), 1.0f - kFp32Eps);
+    return v * logf(q) + (1.0f - v) * log1pf(-q);
+}
+// Categorical over unnormalised weights p[0..C) whose sum the caller has taken (the plain loop stays at the call sites:
+// as a function of its own it compiled to another loop form in the log-weight kernels): entry k scores
+// log(clamp(p[k] / sum, eps, 1 - eps)) ...
+__device__ __forceinline__ float categorical_lp(const float* p, float sum, int k) { return log_clamped(p[k] / sum); }
+// ... and the draw for target = u * sum is k = the first c whose cumulative weight exceeds it (the last entry if rounding leaves
+// none). (k by reference, not returned: the form that leaves every draw kernel's instructions as they were.)
+__device__ __forceinline__ void categorical_pick(const float* p, int C, float target, int& k) {
+    float cum = 0.0f;
+    k = C - 1;
+    for (int c = 0; c < C; ++c) {
+        cum += p[c];
+        if (target < cum) { k = c; break; }
+    }
+}
+// Normal(a, b) from two Philox words (Box-Muller, the cos branch); Uniform[a, b) from one (torch.distributions.Uniform's support)
+__device__ __forceinline__ float normal_draw(float a, float b, uint32_t w0, uint32_t w1) {
+    return a + b * sqrtf(-2.0f * logf(u01(w0))) * cosf(kTwoPi * u01(w1));
+}
+__device__ __forceinline__ float uniform_draw(float a, float b, uint32_t w0) {
+    const float v = a + (b - a) * (((float)(w0 >> 8)) * (1.0f / 16777216.0f));
+    return v < b ? v : a;
+}
+
 // Standard normal deviate of the SHARED-proposal kernels (the first statement of a lock-step run: is_mixture_shared_kernel and
 // is_fused_kernel, one draw per particle, 10^6 particles per call): sqrt(-2 ln u1) cos(2 pi u2) on the hardware log2 / cos /
 // sqrt (v_log_f32, v_cos_f32 takes its argument in revolutions, v_sqrt_f32: ~1e-6 absolute on a deviate of unit scale, ~60

@@ -923,37 +923,25 @@ int is_step(const pp_net* net, const float* P, int addr_id, int prev_addr_id, in
     return 0;
 }
 
-// log_prob of the prior / likelihood families state.sample and state.observe score (state.py:211, 147-149), as torch
-// evaluates them in fp32:
-//   0 Normal(mean a, stddev b)       torch.distributions.Normal.log_prob
-//   1 Uniform(low a, high b)         support [low, high)
-//   3 Poisson(rate a)                xlogy(v, rate) - rate - lgamma(v + 1)
-//   4 Bernoulli(probs a)             probs clamped to [eps, 1 - eps] (probs_to_logits), v log p + (1 - v) log(1 - p)
-//   5 Categorical(probs row p0[i * s0 .. + C), C = s1)   log(clamp(p[v] / sum p, eps, 1 - eps))
+// log_prob of the prior / likelihood families state.sample and state.observe score (state.py:211, 147-149), by the formulas
+// of is_draw.hpp:
+//   0 Normal(mean a, stddev b)   1 Uniform(low a, high b)   3 Poisson(rate a)   4 Bernoulli(probs a)
+//   5 Categorical(probs row p0[i * s0 .. + C), C = s1)
 __device__ __forceinline__ float term_log_prob(int kind, const float* __restrict__ p0, int s0, const float* __restrict__ p1,
                                                int s1, float v, int64_t i) {
-    if (kind == 5) {
+    if (kind == 5) {         // (the index is the truncated value)
         const float* p = p0 + i * s0;
-        const int C = s1;
+        const int C = s1, k = (int)v;
         float sum = 0.0f;
         for (int c = 0; c < C; ++c) sum += p[c];
-        const int k = (int)v;
         if (k < 0 || k >= C) return -INFINITY;
-        const float q = fminf(fmaxf(p[k] / sum, kFp32Eps), 1.0f - kFp32Eps);
-        return logf(q);
+        return categorical_lp(p, sum, k);
     }
     const float a = p0[i * s0];
-    if (kind == 3) return (v == 0.0f ? 0.0f : v * logf(a)) - a - lgammaf(v + 1.0f);
-    if (kind == 4) {
-        const float q = fminf(fmaxf(a, kFp32Eps), 1.0f - kFp32Eps);
-        return v * logf(q) + (1.0f - v) * log1pf(-q);
-    }
+    if (kind == 3) return poisson_lp(a, v);          // (no support test on the value here, nor for Bernoulli: is_draw.hpp)
+    if (kind == 4) return bernoulli_lp(a, v);
     const float b = p1[i * s1];
-    if (kind == 0) {
-        const float t = v - a;
-        return -(t * t) / (2.0f * b * b) - logf(b) - kHalfLog2Pi;
-    }
-    return (v >= a && v < b) ? -logf(b - a) : -INFINITY;
+    return kind == 0 ? normal_lp(a, b, v) : uniform_lp(a, b, v);
 }
 
 // lw[i] += scale * log_prob(dist(p0_i, p1_i); x_i)
@@ -1379,10 +1367,10 @@ __global__ __launch_bounds__(256, 4) void is_fused_kernel(const float* __restric
                     if (s_tcok[t]) {      // constant scale: - log b - log sqrt(2 pi) and 1 / (2 b^2) once per thread
                         lp = s_tc0[t] - d * d * s_tc1[t];
                     } else {
-                        lp = -(d * d) / (2.0f * pb_ * pb_) - logf(pb_) - kHalfLog2Pi;
+                        lp = normal_lp(pa_, pb_, x);
                     }
                 } else {
-                    lp = (x >= pa_ && x < pb_) ? -logf(pb_ - pa_) : -INFINITY;
+                    lp = uniform_lp(pa_, pb_, x);
                 }
             } else {
                 lp = term_log_prob(T.kind, T.p0, T.s0, T.p1, T.s1, x, i);
@@ -1437,14 +1425,7 @@ __global__ __launch_bounds__(256) void prior_draw_kernel(int kind, const float* 
         uint32_t r[4];
         rng.next(r);
         const float a = p0[(int64_t)i * s0], b = p1[(int64_t)i * s1];
-        float v;
-        if (kind == 0) {
-            v = a + b * sqrtf(-2.0f * logf(u01(r[0]))) * cosf(kTwoPi * u01(r[1]));
-        } else {
-            v = a + (b - a) * (((float)(r[0] >> 8)) * (1.0f / 16777216.0f));      // [a, b): torch.distributions.Uniform's support
-            v = v < b ? v : a;
-        }
-        out[i] = v;
+        out[i] = kind == 0 ? normal_draw(a, b, r[0], r[1]) : uniform_draw(a, b, r[0]);
     }
 }
 

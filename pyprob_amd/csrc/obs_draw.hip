@@ -58,8 +58,7 @@ __global__ __launch_bounds__(256) void obs_draw_kernel(int kind, const float* __
             for (int t = 0; t < 4; ++t) {
                 if (t < m) {
                     const float a = a_row[(int64_t)(e + t) * e0], b = b_row[(int64_t)(e + t) * e1];
-                    float u = a + (b - a) * (((float)(w[t] >> 8)) * (1.0f / 16777216.0f));      // [a, b)
-                    v[t] = u < b ? u : a;
+                    v[t] = uniform_draw(a, b, w[t]);
                 } else {
                     v[t] = 0.0f;
                 }

@@ -10,6 +10,7 @@ fused prior/likelihood log-prob kernels that accumulate the per-particle log-wei
 import ctypes as C
 import os
 import time
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -17,6 +18,64 @@ import torch
 from . import lib as L
 from .distributions import DIST_KINDS, DIST_PARAMS
 from .ops import ops
+
+
+# ---- a log-weight term: what lw += scale * log p(x) needs to know about p. DistRunner.dist_term builds them; nothing else does.
+class ScalarTerm(NamedTuple):
+    """Kinds 0-5 (the inference network's families; Categorical: p0 = probability rows, s0 = the row stride, s1 = C): the shape
+    pp_lw_term and the fused pass take."""
+    kind: int
+    p0: Any
+    s0: int
+    p1: Any
+    s1: int
+    fused = True        # may join LockStepState's fused pass (pp_is_fused)
+
+    @property
+    def params(self):
+        return [self.p0, self.p1]
+
+    def wide(self):
+        """The same term with pp_dist's four parameter slots (pp_dist_draw)."""
+        return DistTerm(*self, None, 0, None, 0)
+
+
+class DistTerm(NamedTuple):
+    """A pp_dist: any family's kind with four parameter slots (None: unused) and their strides (0 shared, 1 per particle);
+    Factor (kind 2) has no parameters, its term is the value itself."""
+    kind: int
+    p0: Any
+    s0: int
+    p1: Any
+    s1: int
+    p2: Any
+    s2: int
+    p3: Any
+    s3: int
+    fused = False
+
+    def wide(self):
+        return self
+
+    @property
+    def params(self):
+        return [self.p0, self.p1, self.p2, self.p3]
+
+    @property
+    def strides(self):
+        return [int(self.s0), int(self.s1), int(self.s2), int(self.s3)]
+
+
+class MixTerm(NamedTuple):
+    """A pp_mixture: K scalar components (kinds [K], parameters and strides [4 K]) and K (shared) or n K (per particle)
+    unnormalised weights. tag == 'Mixture'."""
+    tag: str
+    kinds: list
+    params: list
+    strides: list
+    probs: Any
+    K: int
+    fused = False
 
 
 class DistRunner:
@@ -62,9 +121,9 @@ class DistRunner:
 
     # ---- log-weight terms ---------------------------------------------------------------------------------
     def dist_term(self, distribution, n=None):
-        """(kind, p0, p0_stride, p1, p1_stride) of pp_logweight_accumulate for a prior / likelihood distribution object
-        (duck-typed: .name and the parameter attributes of pyprob/distributions/*.py); None if the family has no device
-        kernel. Parameters may be shared (one element) or per particle (n elements)."""
+        """The ScalarTerm, DistTerm or MixTerm of a prior / likelihood distribution object (duck-typed: .name and the parameter
+        attributes of pyprob/distributions/*.py); None if the family has no device kernel. Parameters may be shared (one
+        element) or per particle (n elements)."""
         with torch._C.DisableTorchFunctionSubclass():     # (metadata only: no Python dispatch per attribute of a ParticleTensor)
             return self._dist_term(distribution)
 
@@ -83,38 +142,35 @@ class DistRunner:
         name = distribution.name
         if name == 'Normal':
             p0, p1 = t(distribution.mean), t(distribution.stddev)
-            return 0, p0, s(p0), p1, s(p1)
+            return ScalarTerm(0, p0, s(p0), p1, s(p1))
         if name == 'Uniform':
             p0, p1 = t(distribution.low), t(distribution.high)
-            return 1, p0, s(p0), p1, s(p1)
+            return ScalarTerm(1, p0, s(p0), p1, s(p1))
         if name == 'Poisson':
             p0 = t(distribution.rate)
-            return 3, p0, s(p0), None, 0
+            return ScalarTerm(3, p0, s(p0), None, 0)
         if name == 'Bernoulli':
             p0 = t(distribution.probs)
-            return 4, p0, s(p0), None, 0
+            return ScalarTerm(4, p0, s(p0), None, 0)
         if name == 'Categorical':
             C_ = int(distribution.num_categories)
             p0 = t(distribution.probs)
-            return 5, p0, (0 if p0.numel() == C_ else C_), None, C_
+            return ScalarTerm(5, p0, (0 if p0.numel() == C_ else C_), None, C_)
         if name == 'Mixture':
             return self._mix_term(distribution, t)
         kind = DIST_KINDS.get(name)
         if kind is None:
             return None
         if kind == 2:           # Factor: the term is the value itself (the caller passes the log-density as x)
-            return (2, None, 0, None, 0, None, 0, None, 0)
+            return DistTerm(2, None, 0, None, 0, None, 0, None, 0)
         ps = [t(getattr(distribution, a)) for a in DIST_PARAMS[name]]
         ps += [None] * (4 - len(ps))
-        out = [kind]
-        for q in ps:
-            out += [q, 0 if q is None else s(q)]
-        return tuple(out)       # (kind, p0, s0, p1, s1, p2, s2, p3, s3): a pp_dist term (pp_dist_logweight / pp_dist_draw)
+        return DistTerm(kind, *[f for q in ps for f in (q, 0 if q is None else s(q))])
 
     def _mix_term(self, distribution, t):
-        """('Mixture', kinds [K], parameters [4 K], strides [4 K], probs, K): a pp_mixture term (pp_mix_logweight / pp_mix_draw).
-        Every component is a scalar family with parameters of 1 or n elements; probs holds K (shared) or n K (per particle)
-        unnormalised weights. None if a component has no place in a mixture (Categorical, Factor, a nested Mixture)."""
+        """The MixTerm of a Mixture (pp_mix_logweight / pp_mix_draw). Every component is a scalar family with parameters of 1 or n
+        elements; probs holds K (shared) or n K (per particle) unnormalised weights. None if a component has no place in a
+        mixture (Categorical, Factor, a nested Mixture)."""
         comps = distribution.distributions
         K = len(comps)
         if not 1 <= K <= L.PP_MIX_MAX_COMPONENTS:
@@ -126,100 +182,91 @@ class DistRunner:
             sub = self._dist_term(d)
             if sub is None:
                 return None
-            if len(sub) == 5:
-                sub = (sub[0], sub[1], sub[2], sub[3], sub[4], None, 0, None, 0)
-            kinds.append(int(sub[0]))
-            ps += list(sub[1::2])
-            ss += [int(v) for v in sub[2::2]]
+            sub = sub.wide()
+            kinds.append(int(sub.kind))
+            ps += sub.params
+            ss += sub.strides
         raw = getattr(distribution, '_raw_probs', None)
         raw = distribution.probs if raw is None else raw
         if torch.is_tensor(raw) and raw.dtype == torch.float32 and raw.device == self.dev and raw.is_contiguous():
             probs = raw.as_subclass(torch.Tensor).reshape(-1)
         else:
             probs = torch.as_tensor(raw, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(self.dev).contiguous()
-        return ('Mixture', kinds, ps, ss, probs, K)
+        return MixTerm('Mixture', kinds, ps, ss, probs, K)
 
-    def _mix_check(self, term, n):
-        _, kinds, ps, ss, probs, K = term
-        if probs.numel() not in (K, n * K) or any(q is not None and q.numel() not in (1, n) for q in ps):
-            raise RuntimeError('lock-step Mixture: component parameters of 1 or n elements, probs of K or n K elements')
-
-    def dist_spec(self, distribution):
-        """(kind, [p0..p3], [s0..s3]) of pp_dist for any family (kinds 0-5 included: the prior draws of the prior-proposal
-        engine); None if the family has no device kernel."""
-        term = self.dist_term(distribution)
-        if term is None:
-            return None
-        if len(term) == 6:       # a mixture term: drawn by pp_mix_draw
-            return term
-        if len(term) == 5:
-            kind, p0, s0, p1, s1 = term
-            if kind == 5:
-                return kind, [p0, None, None, None], [s0, s1, 0, 0]
-            return kind, [p0, p1, None, None], [s0, s1, 0, 0]
-        return term[0], list(term[1::2]), list(term[2::2])
-
-    def draw(self, distribution, values, rows, seed, stream_id):
-        """values[r] ~ distribution for the particles r of `rows` (None: all of them), in place (pp_dist_draw: Philox key
-        `seed`, counter offset + r, `stream_id` per statement)."""
-        spec = self.dist_spec(distribution)
-        if spec is None or spec[0] == 2:
-            raise RuntimeError('lock-step execution has no device sampler for {}'.format(distribution.name))
-        if len(spec) == 6:      # Mixture: the selection stream is stream_id | 0x80000000, the component's draw stream_id
-            self._mix_check(spec, values.numel())
-            ops.mix_draw(spec[1], spec[2], spec[3], spec[4], rows, values, int(seed), self.offset, int(stream_id))
-            torch.autograd.graph.increment_version(values)
-            return values
-        kind, ps, ss = spec
-        for q in ps:
-            if q is not None and kind != 5 and q.numel() not in (1, values.numel()):
-                raise RuntimeError('lock-step draw of {}: parameters of 1 or n elements'.format(distribution.name))
-        ops.dist_draw(int(kind), ps, [int(v) for v in ss], rows, values, int(seed), self.offset, int(stream_id))
-        torch.autograd.graph.increment_version(values)      # (written by the kernel: memoised results of it are stale)
-        return values
-
-    def dist_accumulate(self, lw, term, x, rows, scale):
-        """lw[r] += scale * log p(x[r]) for a pp_dist term (dist_term's 9-tuple) on the particles of `rows` (None: all)."""
+    def _flat(self, x):
+        """x as a plain float32 contiguous flat tensor on the runner's device."""
         x = x.as_subclass(torch.Tensor) if type(x) is not torch.Tensor else x
         if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
             x = x.to(self.dev, torch.float32).contiguous()
-        x = x.reshape(-1)
-        if len(term) == 6:      # Mixture (pp_mix_logweight)
-            self._mix_check(term, lw.numel())
-            ops.mix_logweight(lw, term[1], term[2], term[3], term[4], x, float(scale), rows, None, lw.numel())
-            return
-        ps, ss = list(term[1::2]), [int(v) for v in term[2::2]]
-        ops.dist_logweight(lw, [int(term[0])], ps, ss, [x], [float(scale)], rows, None, lw.numel())
+        return x.reshape(-1)
+
+    def _check(self, term, x, n):
+        """The sizes the kernels rely on: x (if given) and every parameter hold 1 or n elements - Categorical: one probability
+        row or n rows, a Mixture's weights: K or n K."""
+        sized = [x]             # what holds 1 or n elements
+        if type(term) is ScalarTerm and term.kind == 5:
+            if term.p0.numel() not in (term.s1, n * term.s1):
+                raise RuntimeError('lock-step Categorical: one row of C probabilities or n rows')
+        else:
+            sized += term.params
+            if type(term) is MixTerm and term.probs.numel() not in (term.K, n * term.K):
+                raise RuntimeError('lock-step Mixture: probs of K or n K elements')
+        if any(q is not None and q.numel() not in (1, n) for q in sized):
+            raise RuntimeError('lock-step term: parameters and values of 1 or n elements')
+
+    def draw(self, distribution, values, rows, seed, stream_id):
+        """values[r] ~ distribution for the particles r of `rows` (None: all of them), in place (pp_dist_draw / pp_mix_draw:
+        Philox key `seed`, counter offset + r, `stream_id` per statement)."""
+        term = self.dist_term(distribution)
+        if term is None or (type(term) is DistTerm and term.kind == 2):
+            raise RuntimeError('lock-step execution has no device sampler for {}'.format(distribution.name))
+        self._check(term, None, values.numel())
+        if type(term) is MixTerm:      # the selection stream is stream_id | 0x80000000, the component's draw stream_id
+            ops.mix_draw(term.kinds, term.params, term.strides, term.probs, rows, values, int(seed), self.offset, int(stream_id))
+        else:
+            term = term.wide()
+            ops.dist_draw(int(term.kind), term.params, term.strides, rows, values, int(seed), self.offset, int(stream_id))
+        torch.autograd.graph.increment_version(values)      # (written by the kernel: memoised results of it are stale)
+        return values
+
+    def accumulate(self, lw, term, x, scale=1.0, rows=None, mask=None):
+        """lw[r] += scale * log p(x[r]) for the particles r of a control-flow path: all of them, or - a path kept as a row list
+        (LockStepState.by_rows) - the ascending int64 indices `rows`, or - a path kept as a mask - the bool [n] `mask`, next to
+        which `rows` are the same particles as the state holds them. One launch per term type (pp_logweight_terms /
+        pp_logweight_accumulate_rows, pp_dist_logweight, pp_mix_logweight); a ScalarTerm under a mask is evaluated for every
+        particle (stale entries of the others may be anything) and added where the mask is set."""
+        n = lw.numel()
+        x = self._flat(x)
+        self._check(term, x, n)
+        if type(term) is MixTerm:
+            ops.mix_logweight(lw, term.kinds, term.params, term.strides, term.probs, x, float(scale), rows, None, n)
+        elif type(term) is DistTerm:
+            ops.dist_logweight(lw, [int(term.kind)], term.params, term.strides, [x], [float(scale)], rows, None, n)
+        elif mask is not None:
+            lp = ops.log_prob(int(term.kind), term.p0, int(term.s0), term.p1, int(term.s1), x, n)
+            lw.add_(torch.where(mask, lp, torch.zeros_like(lp)), alpha=float(scale))
+        elif rows is not None:
+            L.check(self.lib.pp_logweight_accumulate_rows(int(term.kind), L.ptr(term.p0), int(term.s0), L.ptr(term.p1), int(term.s1),
+                                                          x.data_ptr(), 0 if x.numel() == 1 else 1, float(scale), lw.data_ptr(),
+                                                          rows.data_ptr(), int(rows.numel()), self._st), 'pp_logweight_accumulate_rows')
+        else:
+            self.accumulate_terms(lw, [(term, x, scale)])
 
     def log_prob(self, term, x, n=None):
         """log_prob(dist; x) per particle as a device tensor [n] (no accumulation)."""
-        if len(term) in (6, 9):      # a pp_dist / pp_mixture term (lp_out of pp_dist_logweight / pp_mix_logweight)
-            n = int(x.numel()) if n is None else n
-            lp = torch.empty(n, dtype=torch.float32, device=self.dev)
-            x = x.as_subclass(torch.Tensor).to(self.dev, torch.float32).reshape(-1).contiguous()
-            if len(term) == 6:
-                self._mix_check(term, n)
-                ops.mix_logweight(None, term[1], term[2], term[3], term[4], x, 1.0, None, lp, n)
-                return lp
-            ops.dist_logweight(None, [int(term[0])], list(term[1::2]), [int(v) for v in term[2::2]], [x], [1.0], None, lp, n)
-            return lp
-        kind, p0, s0, p1, s1 = term
+        x = self._flat(x)
         n = int(x.numel()) if n is None else n
-        return ops.log_prob(int(kind), p0, int(s0), p1, int(s1), x, n)
-
-    def _term_accumulate(self, term, x, scale, lw):
-        kind, p0, s0, p1, s1 = term
-        ops.logweight_terms(lw, [int(kind)], [p0], [int(s0)], [p1], [int(s1)], [x], [float(scale)], False)
-
-    def accumulate_masked(self, lw, kind, p0, p1, x, active, scale=1.0, term=None):
-        """accumulate() for the active particles of a diverged path: the term is evaluated for every particle (stale
-        entries of inactive particles may be anything) and added where `active` (None = everywhere)."""
-        if term is None:
-            term = (kind, p0, 0 if p0.numel() == 1 else 1, p1, 0 if p1.numel() == 1 else 1)
-        if active is None:
-            return self._term_accumulate(term, x, scale, lw)
-        lp = self.log_prob(term, x, lw.numel())
-        lw.add_(torch.where(active, lp, torch.zeros_like(lp)), alpha=float(scale))
+        self._check(term, x, n)
+        if type(term) is ScalarTerm:
+            kind, p0, s0, p1, s1 = term
+            return ops.log_prob(int(kind), p0, int(s0), p1, int(s1), x, n)
+        lp = torch.empty(n, dtype=torch.float32, device=self.dev)      # (lp_out of pp_dist_logweight / pp_mix_logweight)
+        if type(term) is MixTerm:
+            ops.mix_logweight(None, term.kinds, term.params, term.strides, term.probs, x, 1.0, None, lp, n)
+        else:
+            ops.dist_logweight(None, [int(term.kind)], term.params, term.strides, [x], [1.0], None, lp, n)
+        return lp
 
     # ---- the particles of a control-flow path as a row list (LockStepState.by_rows): direct C-ABI calls ------------------------
     def partition_launch(self, cond, rows, m):
@@ -275,19 +322,6 @@ class DistRunner:
     def partition(self, cond, rows, m):
         return self.partition_read(self.partition_launch(cond, rows, m))
 
-    def accumulate_rows(self, lw, term, x, rows, scale):
-        """lw[rows] += scale * log_prob(term; x[rows]) - one launch on the path's rows (pp_logweight_accumulate_rows)."""
-        kind, p0, s0, p1, s1 = term
-        x = x.as_subclass(torch.Tensor) if type(x) is not torch.Tensor else x
-        if x.dtype != torch.float32 or x.device != self.dev or not x.is_contiguous():
-            x = x.to(self.dev, torch.float32).contiguous()
-        for t in (p0, p1, x):
-            if t is not None and t.numel() not in (1, lw.numel()):
-                raise RuntimeError('lock-step log-weight term: tensors of 1 or n elements')
-        L.check(self.lib.pp_logweight_accumulate_rows(int(kind), L.ptr(p0), int(s0), L.ptr(p1), int(s1), x.data_ptr(),
-                                                      0 if x.numel() == 1 else 1, float(scale), lw.data_ptr(), rows.data_ptr(),
-                                                      int(rows.numel()), self._st), 'pp_logweight_accumulate_rows')
-
     def copy_rows(self, src, dst, rows):
         """dst[rows] = src[rows] (src: n values or one shared value), in place (pp_copy_rows)."""
         src = src.as_subclass(torch.Tensor) if type(src) is not torch.Tensor else src
@@ -299,20 +333,14 @@ class DistRunner:
                                       self._st), 'pp_copy_rows')
         torch.autograd.graph.increment_version(dst)       # written by the kernel: memoised results of it are stale
 
-    def accumulate(self, lw, kind, p0, p1, x, scale=1.0, term=None):
-        """lw += scale * log_prob(dist(p0, p1); x); p0/p1/x are device tensors of 1 (broadcast) or n elements."""
-        if term is None:
-            term = (kind, p0, 0 if p0.numel() == 1 else 1, p1, 0 if p1.numel() == 1 else 1)
-        self._term_accumulate(term, x, scale, lw)
-
     def accumulate_terms(self, lw, terms, overwrite=False):
-        """One pass for up to four terms; terms = [(kind, p0, p1, x, scale)] (kind 2 = the tensor x itself) or
-        [(dist_term(...), x, scale)]."""
+        """One pass for up to four terms; terms = [(ScalarTerm, x, scale)] or, the strides worked out here,
+        [(kind, p0, p1, x, scale)] (kind 2 = the tensor x itself)."""
         def s(t):
             return 0 if (t is None or t.numel() == 1) else 1
         kinds, p0s, s0s, p1s, s1s, xs, scales = [], [], [], [], [], [], []
         for item in terms:
-            if len(item) == 3:          # (dist_term tuple, x, scale)
+            if len(item) == 3:          # (ScalarTerm, x, scale)
                 (kind, p0, s0, p1, s1), x, scale = item
             else:
                 kind, p0, p1, x, scale = item

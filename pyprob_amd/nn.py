@@ -354,12 +354,9 @@ class InferenceNetworkLSTM:
                 # statement and the path like the proposal draws) - a host draw of n values + an upload per statement was
                 # 0.7 ms + 0.05 ms at n = 200 000 (profiles/r04c_gumm_cprofile.txt)
                 from .ops import ops
-                a0, a1 = (distribution.mean, distribution.stddev) if distribution.name == 'Normal' else (distribution.low, distribution.high)
-                p0 = torch.as_tensor(a0, dtype=torch.float32).reshape(-1).to(runner.dev)
-                p1 = torch.as_tensor(a1, dtype=torch.float32).reshape(-1).to(runner.dev)
-                if p0.numel() in (1, ls.n) and p1.numel() in (1, ls.n):
-                    draw = ops.prior_draw(0 if distribution.name == 'Normal' else 1, p0, p1, ls.n,
-                                          ls.seed + 7919 * j + 104729 * ls.path_id, ls.offset, 0x50)
+                term = runner.dist_term(distribution)
+                if term.p0.numel() in (1, ls.n) and term.p1.numel() in (1, ls.n):
+                    draw = ops.prior_draw(term.kind, term.p0, term.p1, ls.n, ls.seed + 7919 * j + 104729 * ls.path_id, ls.offset, 0x50)
             if draw is None:
                 draw = distribution.sample()
                 draw = torch.as_tensor(draw, dtype=torch.float32).reshape(-1)
@@ -448,10 +445,7 @@ class InferenceNetworkLSTM:
                 lp = torch.where(ls.active, lp, torch.zeros_like(lp))
             ls.runner.axpy(ls.lw, 1.0, lp)
             return
-        if getattr(ls, 'by_rows', False) and ls.rows is not None:
-            ls.runner.accumulate_rows(ls.lw, term, value, ls.rows, 1.0)
-        else:
-            ls.runner.accumulate_masked(ls.lw, None, None, None, value, ls.active, term=term)
+        ls.runner.accumulate(ls.lw, term, value, rows=ls.rows, mask=ls.path_mask)
 
     def _validation_loss(self, dataset_valid, batch_size):
         """Mean `_loss` over the minibatches of a packed validation dataset, forward only (inference_network.py:538-543);

@@ -454,6 +454,11 @@ class LockStepState(PathExecutor):
     def active(self, mask):
         self._mask = mask
 
+    @property
+    def path_mask(self):
+        """The mask of a path that is KEPT as a mask (PP_IS_ROWS=0); None for all particles and for a path kept as its row list."""
+        return None if self.by_rows else self._mask
+
     def branch(self, cond):
         if not self.by_rows:
             return super().branch(cond)
@@ -637,20 +642,13 @@ class PriorLockStep(PathExecutor):
         # device chunks: Normal / Uniform columns are drawn by pp_prior_draw (Philox, csrc/is_kernels.hip) where the training
         # step reads them; the key comes from torch's generator, so pyprob.seed / torch.manual_seed reproduce a chunk
         self.seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self._consts = {}
+        self.runner = None            # device chunks: the terms (cached device constants) and the Mixture draws
+        if torch.device(device).type != 'cpu':
+            from .is_engine import DistRunner
+            self.runner = DistRunner(device)
         self.obs_k = {}               # observe name -> values per particle (the same in every path)
         self.obs_widths = None        # [k per name of obs_names], set by columns()
         super().__init__(n, torch.device(device))
-
-    def _param(self, v):
-        """A distribution parameter as a float32 device vector (scalars cached: no host-to-device copy per statement)."""
-        if not torch.is_tensor(v) or (v.device.type == 'cpu' and v.numel() == 1):
-            key = float(v)
-            t = self._consts.get(key)
-            if t is None:
-                t = self._consts[key] = torch.tensor([key], dtype=torch.float32, device=self.dev)
-            return t
-        return v.as_subclass(torch.Tensor).reshape(-1).to(self.dev, torch.float32).contiguous()
 
     def _draw(self, distribution, stream_id):
         """One value per particle of this execution from `distribution` (prior inflation applied by the caller)."""
@@ -658,13 +656,10 @@ class PriorLockStep(PathExecutor):
             return self._draw_mixture(distribution, stream_id)
         if self.dev.type != 'cpu' and distribution.name in ('Normal', 'Uniform'):
             from .ops import ops
-            if distribution.name == 'Normal':
-                kind, p0, p1 = 0, self._param(distribution.mean), self._param(distribution.stddev)
-            else:
-                kind, p0, p1 = 1, self._param(distribution.low), self._param(distribution.high)
-            if p0.numel() in (1, self.width) and p1.numel() in (1, self.width):
+            term = self.runner.dist_term(distribution)      # (scalar parameters: cached device constants, no copy per statement)
+            if term.p0.numel() in (1, self.width) and term.p1.numel() in (1, self.width):
                 # counters: particle index inside this execution; the path id separates re-run paths of one chunk
-                return ops.prior_draw(kind, p0, p1, self.width, self.seed, self.path_id << 32, stream_id)
+                return ops.prior_draw(term.kind, term.p0, term.p1, self.width, self.seed, self.path_id << 32, stream_id)
         return _vector_draw(distribution, self.width).to(self.dev)
 
     def _draw_mixture(self, distribution, stream_id):
@@ -672,18 +667,8 @@ class PriorLockStep(PathExecutor):
         the CPU device a vectorised torch route: the component index of every particle, then a gather."""
         if self.dev.type == 'cpu':
             return distribution.sample_n(self.width)
-        from .is_engine import DistRunner
-        from .ops import ops
-        runner = self.__dict__.get('_mix_runner')
-        if runner is None:
-            runner = self._mix_runner = DistRunner(self.dev)
-        term = runner.dist_term(distribution)
-        if term is None:
-            raise RuntimeError('lock-step execution has no device sampler for this Mixture')
-        runner._mix_check(term, self.width)
-        out = torch.empty(self.width, dtype=torch.float32, device=self.dev)
-        ops.mix_draw(term[1], term[2], term[3], term[4], None, out, self.seed, self.path_id << 32, int(stream_id))
-        return out
+        self.runner.begin(self.width, self.path_id << 32)
+        return self.runner.draw(distribution, torch.empty(self.width, dtype=torch.float32, device=self.dev), None, self.seed, stream_id)
 
     def start_path(self, active, decisions, statements_done, observes_done):
         super().start_path(active, decisions, statements_done, observes_done)
@@ -734,8 +719,8 @@ class PriorLockStep(PathExecutor):
         draw = self._draw(_inflate(distribution) or distribution, j)
         if self.dev.type != 'cpu' and distribution.name in ('Normal', 'Uniform'):
             # cached device constants: a host-to-device copy here would wait for every training step in flight on the stream
-            pp = (distribution.mean, distribution.stddev) if distribution.name == 'Normal' else (distribution.low, distribution.high)
-            p0, p1 = (self._param(q).expand(self.width) if self._param(q).numel() == 1 else self._param(q) for q in pp)
+            term = self.runner.dist_term(distribution)
+            p0, p1 = (q.expand(self.width) if q.numel() == 1 else q for q in (term.p0, term.p1))
         else:
             p0, p1 = _vector_params(distribution, self.width, self.dev)
         o = (None, None, None) if old is None else old
@@ -799,7 +784,7 @@ class PriorLockStep(PathExecutor):
             for t, per, ev in roles:
                 t = t.to(self.dev, torch.float32)
                 if t.numel() == 1:
-                    t = self._param(t) if t.device.type == 'cpu' else t.reshape(1)
+                    t = t.reshape(1)
                 elif per and not ev:
                     t = t.reshape(w, 1)                                  # one value per particle: row stride 1, element stride 0
                 elif per:       # [w, k] where the event is the full one (a partial broadcast such as [w, 4, 1] is expanded)
@@ -1000,22 +985,14 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
 
 
 def _lock_step_term(ls, term, v, obs_name=None):
-    """One likelihood term of the active particles: kinds 0-5 join the fused pass (or the rows kernel); the other families and
-    factor's value term go through pp_dist_logweight, a Mixture through pp_mix_logweight, on the path's rows."""
-    if len(term) in (6, 9):          # (6: a Mixture term, pp_mix_logweight)
-        ls.plan_ok = False
-        ls.flush()
-        ls.runner.dist_accumulate(ls.lw, term, v, ls.rows, _likelihood_importance)
-        return
-    if ls.fused and ls.rows is None:       # full width: joins the next fused pass (with the draw, if one is pending)
+    """One likelihood term of the active particles: a term that can (kinds 0-5) joins the fused pass at full width; otherwise
+    it is one launch on the path's particles (DistRunner.accumulate)."""
+    if term.fused and ls.fused and ls.rows is None:       # joins the next fused pass (with the draw, if one is pending)
         ls.defer_term(term, v, _likelihood_importance, source=('obs', obs_name) if (obs_name is not None and v.numel() == 1) else None)
         return
     ls.plan_ok = False
     ls.flush()
-    if getattr(ls, 'by_rows', False) and ls.rows is not None:
-        ls.runner.accumulate_rows(ls.lw, term, v, ls.rows, _likelihood_importance)
-    else:
-        ls.runner.accumulate_masked(ls.lw, None, None, None, v, ls.active, scale=_likelihood_importance, term=term)
+    ls.runner.accumulate(ls.lw, term, v, _likelihood_importance, rows=ls.rows, mask=ls.path_mask)
 
 
 def factor(log_prob=None, log_prob_func=None, name=None, address=None):

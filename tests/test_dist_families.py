@@ -131,7 +131,7 @@ def test_abi_15_exports_the_distribution_entry_points():
 
 
 def test_runner_maps_every_family_to_its_kind():
-    from pyprob_amd.is_engine import DistRunner
+    from pyprob_amd.is_engine import DistRunner, DistTerm, ScalarTerm
     r = DistRunner.__new__(DistRunner)
     r.dev = torch.device('cpu')
     r._consts = {}
@@ -142,10 +142,12 @@ def test_runner_maps_every_family_to_its_kind():
     for name, k in kinds.items():
         term = r.dist_term(_make(name, [float(v) for v in g[name + '_params'][0]]))
         assert len(term) == 9 and term[0] == k
-        spec = r.dist_spec(_make(name, [float(v) for v in g[name + '_params'][0]]))
-        assert spec[0] == k and len(spec[1]) == 4
+        assert type(term) is DistTerm and not term.fused and term.kind == k and len(term.params) == 4 and term.wide() is term
     assert r.dist_term(D.Factor(log_prob=0.0))[0] == 2
-    assert len(r.dist_term(D.Normal(0.0, 1.0))) == 5      # the five keep their pp_logweight_* route
+    normal = r.dist_term(D.Normal(0.0, 1.0))
+    assert len(normal) == 5 and type(normal) is ScalarTerm and normal.fused      # the five keep their pp_logweight_* route
+    wide = normal.wide()       # ... and draw through pp_dist_draw with four parameter slots
+    assert type(wide) is DistTerm and wide.kind == 0 and len(wide.params) == 4 and wide.params[2:] == [None, None]
 
 
 def test_coroutine_params_take_the_new_families():

@@ -222,8 +222,8 @@ def cpu_doubles():
     MC.register_mix_cpu_doubles()
 
 
-def test_runner_builds_the_mixture_term():
-    from pyprob_amd.is_engine import DistRunner
+def test_runner_builds_the_mixture_term(cpu_doubles):
+    from pyprob_amd.is_engine import DistRunner, MixTerm
     r = DistRunner.__new__(DistRunner)
     r.dev = torch.device('cpu')
     r._consts = {}
@@ -234,10 +234,13 @@ def test_runner_builds_the_mixture_term():
     assert len(term) == 6 and term[0] == 'Mixture' and term[1] == [0, 13, 6] and term[5] == 3
     assert len(term[2]) == 12 and term[3] == [1, 1, 0, 0] + [0] * 4 + [0] * 4      # (the shared stddev comes broadcast)
     assert term[2][0].numel() == n and term[2][9] is None and term[4].numel() == 3 * n
-    r._mix_check(term, n)
-    with pytest.raises(RuntimeError):
-        r._mix_check(term, n + 1)
-    assert r.dist_spec(mix) is term or r.dist_spec(mix)[0] == 'Mixture'
+    assert type(term) is MixTerm and not term.fused
+    assert (term.tag, term.kinds, term.K) == ('Mixture', [0, 13, 6], 3) and term.params is term[2] and term.probs is term[4]
+    r.accumulate(torch.zeros(n), term, torch.zeros(n))
+    with pytest.raises(RuntimeError, match='lock-step Mixture'):        # the size check of every route: the weights hold n rows
+        r.accumulate(torch.zeros(n + 1), term, torch.zeros(n + 1))
+    with pytest.raises(RuntimeError, match='lock-step Mixture'):
+        r.draw(mix, torch.zeros(n + 1), None, 1, 7)
     # Categorical, Factor and nested mixtures are no components
     assert r.dist_term(D.Mixture([D.Categorical([0.5, 0.5])])) is None
     assert r.dist_term(D.Mixture([D.Mixture([D.Normal(0.0, 1.0)])])) is None
@@ -279,3 +282,83 @@ def test_controlled_mixture_sample_is_refused_with_the_reference_wording():
             return z
     with pytest.raises(RuntimeError, match='Distribution currently unsupported: Mixture'):
         Controlled().prior_traces_packed(8, ['y'])
+
+
+# ---- the one host route of a log-weight term (DistRunner.accumulate) on the CPU doubles -------------------------------------------
+ROUTE_N = 37
+ROUTE_ROWS = [0, 3, 4, 9, 15, 16, 22, 28, 31, 35, 36]       # 11 ascending particles, the first and the last among them
+
+
+def _route_case(name):
+    """(mirror distribution with at least one per-particle parameter, values [n]) of one term shape; deterministic per name."""
+    n = ROUTE_N
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    u, z = (lambda: torch.rand(n, generator=g)), (lambda: torch.randn(n, generator=g))
+    if name == 'Normal':
+        return D.Normal(z(), 1.7), z()
+    if name == 'Uniform':
+        return D.Uniform(-1.0 - u(), 2.0), 6.0 * u() - 3.0                    # (values on both sides of the support)
+    if name == 'Poisson':
+        return D.Poisson(0.5 + 3.0 * u()), torch.floor(8.0 * u())
+    if name == 'Bernoulli':
+        return D.Bernoulli(0.1 + 0.8 * u()), (u() < 0.5).float()
+    if name == 'Categorical':
+        return D.Categorical(0.1 + torch.rand(n, 3, generator=g)), torch.floor(3.0 * u())
+    if name == 'Exponential':
+        return D.Exponential(0.5 + u()), 3.0 * u()
+    if name == 'Gamma':
+        return D.Gamma(1.0 + 2.0 * u(), 1.5), 0.1 + 3.0 * u()
+    if name == 'Beta':
+        return D.Beta(1.0 + 2.0 * u(), 2.0, low=-1.0, high=3.0), -1.0 + 4.0 * (0.05 + 0.9 * u())
+    if name == 'LogNormal':
+        return D.LogNormal(0.3 * z(), 0.8), 0.1 + 3.0 * u()
+    if name == 'Weibull':
+        return D.Weibull(1.0 + u(), 1.5), 0.1 + 3.0 * u()
+    if name == 'Binomial':
+        return D.Binomial(total_count=12, logits=z()), torch.floor(13.0 * u())
+    if name == 'VonMises':
+        return D.VonMises(z(), 2.0), z()
+    if name == 'TruncatedNormal':
+        return D.TruncatedNormal(z(), 1.0, -2.0, 3.0), -2.0 + 5.0 * u()
+    if name == 'Factor':
+        x = z()
+        return D.Factor(log_prob=x), x                                        # (the term is the value itself)
+    assert name == 'Mixture'
+    return D.Mixture([D.Normal(z(), 1.0), D.TruncatedNormal(0.0, 1.0, -1.0, 2.0), D.Exponential(2.0)], probs=0.1 + torch.rand(n, 3, generator=g)), 1.5 * u()
+
+
+ROUTE_CASES = ['Normal', 'Uniform', 'Poisson', 'Bernoulli', 'Categorical'] + sorted(D.DIST_KINDS) + ['Mixture']
+
+
+@pytest.mark.parametrize('route', ['full', 'path'])
+@pytest.mark.parametrize('name', ROUTE_CASES)
+def test_accumulate_adds_the_mirror_log_prob_on_every_route(cpu_doubles, name, route):
+    """DistRunner.accumulate for every term shape - the five ScalarTerm kinds, every DistTerm family and Factor, a 3-component
+    MixTerm - at full width and on a path of 11 of 37 particles: exactly the path's particles gain scale * log_prob of the
+    mirror class, the others keep their bits. A path reaches the DistTerm / MixTerm launches as its row list; the ScalarTerm
+    rows kernel has no CPU double, so a ScalarTerm takes the mask route here (tests/test_gpu_rows.py compares the two).
+    Tolerance: the doubles evaluate in float64 (the five) or with the mirror classes themselves and round once to fp32, the mirror
+    evaluates in fp32 (a few ulp of a log-density below ~20: < 1e-5), and lw + scale * lp rounds once more at |lw| < ~10."""
+    from pyprob_amd.is_engine import DistRunner, DistTerm, MixTerm, ScalarTerm
+    r = DistRunner.__new__(DistRunner)
+    r.dev = torch.device('cpu')
+    r._consts = {}
+    r._const = lambda v: torch.tensor([v], dtype=torch.float32)
+    n, scale = ROUTE_N, 0.5
+    dist, x = _route_case(name)
+    term = r.dist_term(dist)
+    assert type(term) is (MixTerm if name == 'Mixture' else DistTerm if name in D.DIST_KINDS else ScalarTerm)
+    ref = (x if name == 'Factor' else dist.log_prob(x)).reshape(-1).float()
+    assert ref.numel() == n and bool(torch.isfinite(ref).any())
+    rows = torch.tensor(ROUTE_ROWS, dtype=torch.int64)
+    touched = torch.ones(n, dtype=torch.bool) if route == 'full' else torch.zeros(n, dtype=torch.bool).index_fill_(0, rows, True)
+    lw0 = torch.randn(n, generator=torch.Generator().manual_seed(1))
+    lw = lw0.clone()
+    if route == 'full':
+        r.accumulate(lw, term, x, scale)
+    else:
+        r.accumulate(lw, term, x, scale, rows=rows, mask=touched if type(term) is ScalarTerm else None)
+    assert torch.equal(lw[~touched], lw0[~touched])
+    torch.testing.assert_close(lw[touched], (lw0 + scale * ref)[touched], rtol=1e-5, atol=1e-5)
+    lp = r.log_prob(term, x, n)                       # the same dispatch without accumulation
+    torch.testing.assert_close(lp, ref, rtol=1e-5, atol=1e-5)
