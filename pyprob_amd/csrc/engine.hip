@@ -165,21 +165,32 @@ struct Workspace {
     size_t bytes;
 };
 
+// Switches of the training step (A/B measurements, tests; all default 1), read together, once per process, as
+// deterministic_mode() is: at the first workspace-size query or step, whichever comes first (carve needs PP_ADDR_BIAS)
+struct StepEnv {
+    int addr_bias, dx_partials, fuse_cell_bwd, fuse_cell, gemm_holes, cell_lean, fuse_cell_rec, dh_partials, aux_colsum;
+};
+static int env_flag(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static const StepEnv& step_env() {
+    static const StepEnv env{env_flag("PP_ADDR_BIAS", 1),     env_flag("PP_DX_PARTIALS", 1),   env_flag("PP_FUSE_CELL_BWD", 1),
+                             env_flag("PP_FUSE_CELL", 1),     env_flag("PP_GEMM_HOLES", 1),    env_flag("PP_CELL_LEAN", 1),
+                             env_flag("PP_FUSE_CELL_REC", 1), env_flag("PP_DH_PARTIALS", 1),   env_flag("PP_AUX_COLSUM", 1)};
+    return env;
+}
+
 // The address terms of the LSTM input as a per-address bias (gather.hpp): the default for LSTM networks whose dimensions
 // allow 16-byte pieces; PP_ADDR_BIAS=0 and the deterministic mode keep the full-width rows (A/B measurements, tests).
 static bool compact_rows(const pp_net* net) {
-    static const int env = getenv("PP_ADDR_BIAS") ? atoi(getenv("PP_ADDR_BIAS")) : 1;
-    if (!env || deterministic_mode() || net->lstm_dim == 0) return false;
+    if (!step_env().addr_bias || deterministic_mode() || net->lstm_dim == 0) return false;
     const int c2 = net->e_obs + net->smp_dim, ne = net->dtype_dim + net->addr_dim;
     return net->lstm_in % 4 == 0 && c2 % 4 == 0 && net->lstm_dim % 16 == 0 && ne >= 2 && ne % 2 == 0 && ne <= 128 && net->n_addr >= 1 &&
            net->n_addr <= 1024 && net->addr_table != nullptr;
 }
 constexpr int DX_SPLITS = 16;
 constexpr int DH_SPLITS = 8;
-static int env_flag(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 
 static void carve(const pp_net* net, int B, int R, void* p, size_t cap, Workspace& w) {
     Carver c(p, cap);
@@ -313,8 +324,6 @@ static int linear_fwd(const float* x, int64_t ldx, const int32_t* x_idx, const f
     return gemm_f32(&g, st, hole);
 }
 
-// dW[out, in] += dz^T x  (dz [n, out] (lddz), x [n, in] (ldx, optional k-gather x_idx)): queued; all weight-gradient
-// products of a backward pass are leaves of the dependency graph and run as one grouped launch (gemm_f32_grouped)
 // the weight-gradient leaves of the backward pass, one grouped launch (timed as kernel class 1 when armed)
 static int launch_wgrads(std::vector<pp_gemm_args>& wq, hipStream_t st, const std::vector<GemmHole>* holes = nullptr,
                          bool timed = true, const AuxJobs* aux = nullptr, bool t1 = false) {
@@ -327,11 +336,13 @@ static int launch_wgrads(std::vector<pp_gemm_args>& wq, hipStream_t st, const st
     if (t1 && wgrad_t1_build(wq.data(), holes && holes->size() == wq.size() ? holes->data() : nullptr, (int)wq.size(), wa))
         PP_TRY(wgrad_t1(wa, aux, st));
     else
-    PP_TRY(gemm_f32_grouped(wq.data(), (int)wq.size(), st, holes ? holes->data() : nullptr, nullptr, aux));
+        PP_TRY(gemm_f32_grouped(wq.data(), (int)wq.size(), st, holes ? holes->data() : nullptr, nullptr, aux));
     if (timed) prof_end(1, flops, st);
     return 0;
 }
 
+// dW[out, in] += dz^T x  (dz [n, out] (lddz), x [n, in] (ldx, optional k-gather x_idx)): queued; all weight-gradient
+// products of a backward pass are leaves of the dependency graph and run as one grouped launch (gemm_f32_grouped)
 static void queue_wgrad(std::vector<pp_gemm_args>& q, const float* dz, int64_t lddz, const float* x, int64_t ldx,
                         const int32_t* x_idx, float* dW, int n, int in, int out, std::vector<GemmHole>* holes = nullptr,
                         GemmHole hole = GemmHole{}) {
@@ -374,31 +385,42 @@ static int linear_dgrad(const float* dz, int64_t lddz, const float* W, float* dx
     return gemm_f32(&g, st, hole);
 }
 
-static int observe_embedding_fwd(const pp_net* net, const float* P, const float* obs, int64_t ldobs, int B, Workspace& w,
-                                 hipStream_t st, bool bwd = true) {
-    if (obs_fused_supported(net))   // small embeddings: one fused launch (obs_embed.hip)
-        return obs_embed_fwd_fused(net, P, obs, B, w.obs_h, w.cat, w.f1, w.E, st);
+// Layer l of observable o's EmbeddingFeedForward(num_layers = depth), ReLU after every layer (embedding_feedforward.py:35-48):
+// y[out] = relu(W[out, in] x + b), w / b offsets into the flat parameter (and gradient) buffer. A CNN2D5C observable's layers
+// are _lin1 / _lin2 behind its convolution stack: layer 0 reads the stack's features
+struct ObsLin { int in, out; int64_t w, b; };
+static int obs_layers(const pp_net* net, int o) { return net->obs_depth[o] ? net->obs_depth[o] : 2; }
+static ObsLin obs_lin(const pp_net* net, int o, int l) {
+    const bool cnn = net->obs_kind[o] == PP_OBS_CNN2D5C, deep = net->obs_depth[o] != 0;
+    ObsLin r;
+    r.in = l == 0 ? (cnn ? net->obs_feat[o] : net->obs_in[o]) : net->obs_hid[o];
+    r.out = l == obs_layers(net, o) - 1 ? net->obs_out[o] : net->obs_hid[o];
+    r.w = deep ? net->obs_w[o][l] : (l == 0 ? net->obs_w0[o] : net->obs_w1[o]);
+    r.b = deep ? net->obs_b[o][l] : (l == 0 ? net->obs_b0[o] : net->obs_b1[o]);
+    return r;
+}
+
+// the observe embedding on its own: small embeddings (`fused`) in one launch (obs_embed.hip), else layer by layer
+static int observe_embedding_fwd(const pp_net* net, const float* P, const float* obs, int64_t ldobs, int B, const Workspace& w,
+                                 hipStream_t st, bool bwd, bool fused) {
+    if (fused) return obs_embed_fwd_fused(net, P, obs, B, w.obs_h, w.cat, w.f1, w.E, st);
     int ci = 0, co = 0;
     for (int o = 0; o < net->n_obs; ++o) {
-        // EmbeddingFeedForward(num_layers = depth), ReLU after every layer (embedding_feedforward.py:35-48)
-        const int depth = net->obs_depth[o] ? net->obs_depth[o] : 2;
+        const int depth = obs_layers(net, o);
         const float* x = obs + ci;
         int64_t ldx = ldobs;
-        int in = net->obs_in[o];
         if (net->obs_kind[o] == PP_OBS_CNN2D5C) {
             // EmbeddingCNN2D5C (embedding_cnn_2d_5c.py:32-44): the convolution stack, then _lin1 / _lin2 read its features
             PP_TRY(cnn_forward(net, o, P, x, ldx, B, w.cnn_feat[o], w.f4[o], w.cnn_ws[o], w.cnn_ws_bytes[o], bwd, st));
-            x = w.cnn_feat[o]; ldx = w.f4[o]; in = net->obs_feat[o];
+            x = w.cnn_feat[o]; ldx = w.f4[o];
         }
         for (int l = 0; l < depth; ++l) {
+            const ObsLin ly = obs_lin(net, o, l);
             const bool last = l == depth - 1;
-            const int out = last ? net->obs_out[o] : net->obs_hid[o];
             float* y = last ? w.cat + co : w.obs_hl[o][l];
             const int64_t ldy = last ? w.e4 : w.ohid4[o];
-            const int64_t wl = net->obs_depth[o] ? net->obs_w[o][l] : (l == 0 ? net->obs_w0[o] : net->obs_w1[o]);
-            const int64_t bl = net->obs_depth[o] ? net->obs_b[o][l] : (l == 0 ? net->obs_b0[o] : net->obs_b1[o]);
-            PP_TRY(linear_fwd(x, ldx, nullptr, P + wl, P + bl, y, ldy, B, in, out, true, nullptr, st));
-            x = y; ldx = ldy; in = out;
+            PP_TRY(linear_fwd(x, ldx, nullptr, P + ly.w, P + ly.b, y, ldy, B, ly.in, ly.out, true, nullptr, st));
+            x = y; ldx = ldy;
         }
         ci += net->obs_in[o];
         co += net->obs_out[o];
@@ -407,6 +429,805 @@ static int observe_embedding_fwd(const pp_net* net, const float* P, const float*
                       nullptr, st));
     PP_TRY(linear_fwd(w.f1, w.e4, nullptr, P + net->fin_w1, P + net->fin_b1, w.E, w.e4, B, net->e_obs, net->e_obs, true,
                       nullptr, st));
+    return 0;
+}
+
+// ---- the training step (ic_loss): switches, plan, phases ------------------------------------------------------------
+// What ic_loss decides, all of it before the first launch (plan_step): the phases below only read it.
+struct StepPlan {
+    bool ff, det, bwd;             // FeedForward network (inference_network_feedforward.py:68-98); deterministic mode; backward pass
+    int B, R, T, H, L, I;          // traces, rows, time steps, hidden width (FF: e_obs), LSTM layers (FF: 0), lstm_in
+    // columns of an LSTM input row [E | s_prev | d_prev | a_prev | d_cur | a_cur] (gather.hpp): c1 = e_obs, the sample embedding
+    // starts there, the table columns at c2, the current statement's at c4; ne = dtype_dim + addr_dim
+    int c1, c2, c3, c4, c5, ne;
+    // single-statement batches have no previous statement at all: the sample-embedding columns are zero in every row
+    int nx;                        // columns of the compact input product: e_obs (T == 1) or c2
+    uint32_t present[32];          // compact rows: bit a = address a occurs in the batch (current or previous statement)
+    int n_present, only_addr;
+    bool fused_obs;                // small embeddings: one fused launch per direction (obs_embed.hip)
+    bool compact;                  // LSTM input rows are [E | s_prev], the table columns a per-address bias (gather.hpp)
+    // Single-statement batch: dX = dG W_ih[:, :e_obs] has ONE consumer, the observe-embedding backward kernel; its K splits
+    // store their partial tiles and that kernel adds them - no float atomics (6-8 us per 64 x 64 tile, tools/wg_trace.py)
+    // and no cleared dX
+    bool dx_partials;
+    int dx_splits;                 // K splits of dX that the observe-embedding backward adds (1: complete rows)
+    // (see GemmExt::lean) the cell backward of a single-statement, single-layer batch runs in the dH epilogue, and with the
+    // zero blocks on neither dX nor dW_ih read the forget gate's columns of first-step rows
+    // (H a multiple of 64: the zero blocks then cover the forget gate's tiles and slabs exactly; and dX as stored split
+    // partials: that product then runs on the async tiles, which skip the forget gate's K range)
+    bool lean_cell;
+    // Single-statement batch, one LSTM layer: every row is a trace's only time step, so the cell backward needs nothing
+    // but dh from the heads - it runs in the epilogue of the dH product (gemm_tile_direct), which also adds each tile's
+    // column sums of dG to its address's group sums; the loss is finalised by the jobs behind the weight-gradient tiles.
+    bool fused_bwd;
+    // Row-panel kernel (panel.hip): a single-statement batch with ONE address keeps input product + cell, head layer 1, the
+    // head tail, dz1, dH + cell backward and dX in one launch (rows of the one address group are the batch rows in order)
+    bool panel;
+    bool panel16_go;               // the 16-row kernel (panel16.hip) instead of the 8-row one (panel.hip)
+    bool obs_tail;                 // training: the observe-embedding backward of the rows rides in the panel kernel's tail
+    ObsFusedArgs obs_args;         // ... with these layer descriptions
+    // ragged batches: the time steps t >= tail_t0 (few rows each) of every LSTM layer run in one launch per direction
+    int tail_t0, tail_teams;
+    // FeedForward, single-statement batch: row r IS trace r, the heads read E in place and the embedding kernel clears the
+    // loss slots - one launch less
+    bool in_place;
+    const float* heads_in;         // input rows of the proposal layers: LSTM outputs, or observe embeddings (FF)
+    int64_t heads_ld;
+    // deterministic mode: the heads write the per-row log_prob only; the loss is a fixed-order sum over the rows and the
+    // kernels of the backward pass get no loss slots to fold
+    float* lp_rows;
+    float* loss_slots;
+    const float* fin_acc;
+    LossFinalize fin;              // folds the loss slots: carried by exactly one launch of a backward pass
+};
+
+static StepPlan plan_step(const pp_net* net, const pp_batch* bt, int flags, float* lp_out, float* loss_out, int32_t* status_out,
+                          const Workspace& w) {
+    const StepEnv& env = step_env();
+    StepPlan p{};
+    p.bwd = flags & PP_LOSS_BACKWARD;
+    p.ff = net->lstm_dim == 0;
+    p.det = deterministic_mode();
+    p.B = bt->n_traces; p.R = bt->n_rows; p.T = bt->t_max; p.H = p.ff ? net->e_obs : net->lstm_dim; p.I = net->lstm_in;
+    // nn.LSTM(I, H, depth), inference_network_lstm.py:31,186-188: layer k reads the hidden states of layer k - 1
+    p.L = p.ff ? 0 : std::max(1, (int)net->lstm_depth);
+    const int B = p.B, R = p.R, T = p.T, H = p.H;
+    p.fused_obs = obs_fused_supported(net);
+    p.tail_t0 = T;
+    if (!p.ff) lstm_tail_plan(bt->n_active, T, H, &p.tail_t0, &p.tail_teams);
+    p.compact = w.compact;
+    p.c1 = net->e_obs; p.c2 = p.c1 + net->smp_dim; p.c3 = p.c2 + net->dtype_dim; p.c4 = p.c3 + net->addr_dim;
+    p.c5 = p.c4 + net->dtype_dim; p.ne = net->dtype_dim + net->addr_dim;
+    p.nx = (T == 1) ? net->e_obs : p.c2;
+    p.dx_partials = p.compact && p.bwd && T == 1 && env.dx_partials && p.fused_obs;
+    p.lean_cell = p.compact && p.bwd && T == 1 && p.L == 1 && H % 64 == 0 && env.fuse_cell_bwd && env.fuse_cell &&
+                  env.gemm_holes == 1 && env.cell_lean && p.dx_partials;
+    if (p.compact)
+        for (int a = 0; a < net->n_addr; ++a)
+            if (bt->grp_off[a + 1] > bt->grp_off[a] || bt->nxt_off[a + 1] > bt->nxt_off[a]) {
+                p.present[a >> 5] |= 1u << (a & 31);
+                ++p.n_present;
+                p.only_addr = a;
+            }
+    if (p.lean_cell && p.n_present == 1 && p.fused_obs && bt->grp_off[p.only_addr] == 0 && bt->grp_off[p.only_addr + 1] == R) {
+        const pp_addr& ad = net->addrs[p.only_addr];
+        const bool shape_ok = head_tail_supported(ad.kind, ad.hid, ad.n_out) &&
+                              w.hid4 <= ((ad.hid + 15) & ~15) && w.out4 <= 64 && (flags & PP_LOSS_KEEP_LP ? lp_out != nullptr : true);
+        p.panel16_go = shape_ok && w.p16.img[0] && panel16_supported(ad.kind, H, ad.hid, ad.n_out, net->e_obs, R);
+        if (p.panel16_go && p.bwd) p.panel16_go = obs_fused_args(net, w.obs_h, p.obs_args) && panel16_obs_ok(p.obs_args);
+        p.panel = p.panel16_go || (shape_ok && panel_t1_supported(ad.kind, H, ad.hid, ad.n_out, net->e_obs) && panel_t1_split(R, H) == 2);
+        if (p.panel)
+            p.obs_tail = p.bwd && (p.panel16_go || panel_obs_tail_ok(net, H, ad.hid, ad.n_out, net->e_obs)) &&
+                         obs_fused_args(net, w.obs_h, p.obs_args);
+    }
+    p.fused_bwd = p.compact && T == 1 && p.L == 1 && env.fuse_cell_bwd;
+    // (panel: complete rows, written by the panel launch; else ~3 slabs per split - the K loop is short either way; more
+    // splits = more workgroups streaming dG)
+    p.dx_splits = (p.dx_partials && !p.panel) ? std::max(1, std::min(DX_SPLITS, (4 * H / 32) / 4)) : 1;
+    p.in_place = p.ff && p.fused_obs && T == 1;
+    p.heads_in = p.in_place ? w.E : w.Hs;
+    p.heads_ld = p.in_place ? w.e4 : H;
+    p.lp_rows = p.det ? (((flags & PP_LOSS_KEEP_LP) && lp_out) ? lp_out : w.lp_rows) : ((flags & PP_LOSS_KEEP_LP) ? lp_out : nullptr);
+    p.loss_slots = p.det ? nullptr : w.loss_acc;
+    p.fin_acc = p.det ? nullptr : w.loss_acc;
+    p.fin = LossFinalize{p.fin_acc, w.flag, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, status_out};
+    return p;
+}
+
+// what every phase works on
+struct Step {
+    const pp_net* net; const pp_batch* bt; const float* P; float* grads;
+    const Workspace& w; const StepPlan& p;
+    hipStream_t st;
+    float* lp_out; int flags;      // (loss_out / status_out: p.fin)
+};
+// Leaves of the backward pass, queued by its phases and launched once, at its end (reduce_and_flush): the weight-gradient
+// products with their zero blocks (paired by index) and the column sums (bias / table gradients). Their ORDER is the order
+// of the tiles and of the reduction jobs in that launch.
+// (a second stream for these leaves with fork / join events was measured twice and lost both times - 0.157 -> 0.166 ms
+// on config 2, 183 vs 170 us with two grouped launches: a cross-queue event wait costs ~5 us - and is gone)
+struct GradQueue {
+    std::vector<pp_gemm_args> wq;
+    std::vector<GemmHole> holes;
+    std::vector<ColsumJob> cs;
+};
+struct LstmLayer { int64_t w_ih, w_hh, b_ih, b_hh; };   // parameter offsets of layer l of nn.LSTM(I, H, depth)
+static LstmLayer lstm_layer(const pp_net* net, int l) {
+    if (l == 0) return LstmLayer{net->w_ih, net->w_hh, net->b_ih, net->b_hh};
+    return LstmLayer{net->lstm_w_ih[l], net->lstm_w_hh[l], net->lstm_b_ih[l], net->lstm_b_hh[l]};
+}
+
+// compact rows: the step's first launch computes the per-address bias vectors of the LSTM input (reads W_ih[:, c2:I] per
+// present address, writes 2 x 4H, clears the group sums)
+static AddrBias addr_bias(const Step& s) {
+    const pp_net* net = s.net; const Workspace& w = s.w; const StepPlan& p = s.p;
+    AddrBias ab{};
+    ab.AB = w.AB; ab.gsum = w.gsum; ab.step_epoch = w.epoch;
+    ab.W = s.P + net->w_ih; ab.b_ih = s.P + net->b_ih; ab.b_hh = s.P + net->b_hh;
+    ab.params = s.P; ab.at = net->addr_table; ab.ldw = p.I;
+    ab.N = 4 * p.H; ab.c2 = p.c2; ab.c3 = p.c3; ab.c4 = p.c4; ab.c5 = p.c5; ab.I = p.I; ab.n_addr = net->n_addr;
+    for (int q = 0; q < 32; ++q) ab.present[q] = p.present[q];
+    return ab;
+}
+// ... and the jobs behind its weight-gradient tiles turn the group sums of dG into the table-column gradients
+static void aux_derived(const Step& s, AuxJobs& aux) {
+    const pp_net* net = s.net; const StepPlan& p = s.p;
+    aux.gsum = s.w.gsum; aux.W = s.P + net->w_ih; aux.dW = s.grads + net->w_ih; aux.ldw = p.I;
+    aux.params = s.P; aux.grads = s.grads; aux.at = net->addr_table;
+    aux.N = 4 * p.H; aux.c2 = p.c2; aux.c4 = p.c4; aux.nd = net->dtype_dim; aux.ne = p.ne; aux.n_addr = net->n_addr;
+    for (int q = 0; q < 32; ++q) aux.present[q] = p.present[q];
+    aux.all_present = 0;
+}
+
+// the k-major weight copies (8-row kernel) or the six fragment images (16-row kernel) of the panel launch: extra workgroups
+// of the first launch
+static PanelTranspose panel_transpose_job(const Step& s) {
+    const pp_net* net = s.net; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const pp_addr& ad = net->addrs[p.only_addr];
+    const int H = p.H;
+    PanelTranspose ptr{};
+    ptr.Wih = s.P + net->w_ih; ptr.ldw = p.I; ptr.WihT = w.WihT;
+    ptr.W1 = s.P + ad.w1; ptr.W1T = w.W1T; ptr.ld1T = 64 * ((ad.hid + 63) / 64);
+    ptr.H = H; ptr.hid = ad.hid; ptr.e = net->e_obs;
+    ptr.tiles_ih = 3 * H / 64;
+    ptr.n_blocks = panel_transpose_blocks(H, ad.hid);
+    if (p.panel16_go) {      // the job writes the six fragment images instead (one thread per fragment lane)
+        ptr.mode16 = 1;
+        ptr.wt = store_wt_mode();
+        ptr.p16.W2 = s.P + ad.w2; ptr.p16.n_out = ad.n_out;
+        ptr.p16.im = w.p16;
+        panel16_image_sizes(H, ad.hid, net->e_obs, ptr.p16.im.frags);      // (this address's head; the buffers hold the widest)
+        int nb = 0;
+        for (int i = 0; i < 6; ++i) {
+            ptr.p16.blocks_before[i] = nb;
+            nb += cdiv(ptr.p16.im.frags[i] * 64, 256);
+        }
+        ptr.p16.blocks_before[6] = nb;
+        ptr.n_blocks = nb;
+    }
+    return ptr;
+}
+
+// First launch: observe embedding; for small embeddings the same launch assembles the LSTM input rows of its traces
+// and clears the loss slots and (backward) dX. Otherwise embedding GEMMs + the stand-alone gather kernel.
+static int first_launch(const Step& s) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const float* P = s.P; hipStream_t st = s.st;
+    const int B = p.B, R = p.R, T = p.T, H = p.H;
+    const int n_clear = PP_LOSS_SLOTS_FLOATS;
+    // kernel class 2 of the in-stream timing: observe embedding + LSTM input rows (the gather path). Algorithmic bytes:
+    // observations and per-row (value, address, previous row) in; X rows, E / cat / f1 and the observables' hidden
+    // activations out (SURVEY.md 8d: 4 I per trace-step written, 4 n_obs per trace read)
+    double gather_bytes = 4.0 * B * bt->obs_width + 12.0 * R + 4.0 * (p.ff ? 0.0 : (double)R * w.xc) + 3.0 * 4.0 * B * net->e_obs;
+    if (!p.ff && p.bwd) gather_bytes += 4.0 * R * w.xc;   // the same launch clears dX
+    AddrBias abias{};
+    if (p.compact) {
+        abias = addr_bias(s);
+        gather_bytes += (double)p.n_present * (4.0 * 4 * H * (2.0 * p.ne) + 4.0 * 4.0 * 4 * H);
+    }
+    for (int o = 0; o < net->n_obs; ++o) gather_bytes += 4.0 * B * net->obs_hid[o];
+    prof_begin(2, st);
+    if (p.ff) {
+        // every time step's proposal layer reads the observe embedding of its trace (:72,85): Hs rows = E[trace]
+        if (p.fused_obs) {
+            RowBuild rb{};
+            rb.zero_small = p.in_place ? w.loss_acc : nullptr;
+            rb.n_small = n_clear;
+            PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb));
+        } else {
+            PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, p.bwd, false));
+        }
+        if (!p.in_place) PP_TRY(embedding_rows(w.E, w.e4, bt->trace, R, net->e_obs, w.Hs, H, w.loss_acc, n_clear, st));
+    } else if (p.fused_obs && T <= 2) {   // (long traces: a wave would write all rows of its trace serially - separate gather)
+        RowBuild rb{};
+        rb.d = GatherDims{net->e_obs, net->smp_dim, net->dtype_dim, net->addr_dim, net->lstm_in};
+        rb.params = P; rb.at = net->addr_table; rb.row_off = bt->row_off_dev; rb.t_max = T;
+        rb.value = bt->value; rb.addr = bt->addr; rb.prev_row = bt->prev_row;
+        rb.X = w.X; rb.ldx = w.i4; rb.xcols = w.xc;
+        rb.zero_like = (p.bwd && !p.dx_partials) ? w.dX : nullptr;
+        rb.zero_small = w.loss_acc; rb.n_small = n_clear;
+        PanelTranspose ptr{};
+        if (p.panel) ptr = panel_transpose_job(s);
+        PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb, p.compact ? &abias : nullptr,
+                                   p.panel ? &ptr : nullptr));
+    } else {
+        PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, p.bwd, p.fused_obs));
+        // (also clears the loss slots and, for a backward pass, dX: see the kernel)
+        PP_TRY(lstm_input_gather(net, P, w.E, w.e4, bt->trace, bt->value, bt->addr, bt->prev_row, -1, -1, R, w.X, w.i4, st,
+                                 p.bwd ? w.dX : nullptr, w.loss_acc, n_clear, w.xc, p.compact ? &abias : nullptr));
+    }
+    prof_end(2, gather_bytes, st);
+    return 0;
+}
+
+// Second launch of the panel step: everything between the LSTM input rows and dX (and, training, the observe-embedding
+// backward in its tail)
+static int panel_launch(const Step& s) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const float* P = s.P; hipStream_t st = s.st;
+    const int B = p.B, R = p.R, H = p.H;
+    const pp_addr& ad = net->addrs[p.only_addr];
+    PanelArgs pa{};
+    pa.B = R; pa.H = H; pa.hid = ad.hid; pa.n_out = ad.n_out; pa.K = ad.n_out / 3; pa.e = net->e_obs;
+    pa.ldx = (int)w.i4; pa.lda1 = (int)w.hid4; pa.lddy = (int)w.out4; pa.ldw = p.I;
+    pa.X = w.X; pa.Wih = P + net->w_ih; pa.AB = w.AB + (int64_t)p.only_addr * 2 * 4 * H;
+    pa.WihT = w.WihT; pa.W1T = w.W1T;
+    pa.xz = w.xz; pa.xd = w.xd; pa.epoch = w.epoch;
+    pa.W1 = P + ad.w1; pa.b1 = P + ad.b1; pa.W2 = P + ad.w2; pa.b2 = P + ad.b2;
+    pa.value = bt->value; pa.prior = bt->prior;
+    pa.Hs = w.Hl[0]; pa.G = w.Gl[0]; pa.A1 = w.A1; pa.DY = w.DY; pa.dZ1 = w.dZ1; pa.dX = w.dX;
+    pa.gsum = w.gsum + (int64_t)p.only_addr * 2 * 4 * H;
+    pa.lp_out = (s.flags & PP_LOSS_KEEP_LP) ? s.lp_out : nullptr;
+    pa.loss_acc = w.loss_acc; pa.flag = w.flag; pa.grad_scale = -1.0f / (float)B;
+    pa.dbg = g_timeline;
+    PanelObs po{};
+    if (p.obs_tail) {
+        po.a = p.obs_args;
+        po.P = P; po.cat = w.cat; po.f1 = w.f1;
+        po.dE = w.dE; po.dF1 = w.dF1; po.dCat = w.dCat; po.dHo0 = w.dObsH;
+        po.dh_stride = (int64_t)B * w.maxohid4;
+    }
+    prof_begin(0, st);
+    if (p.panel16_go) {
+        Panel16Args p16{};
+        p16.a = pa;
+        for (int i = 0; i < 6; ++i) p16.img[i] = w.p16.img[i];
+        PP_TRY(panel16(ad.kind, p16, st, p.obs_tail ? &po : nullptr));
+    } else {
+        PP_TRY(panel_t1(ad.kind, pa, st, p.obs_tail ? &po : nullptr));
+    }
+    // executed data-path FLOPs of the launch: forward + backward products of the 8-row panels
+    prof_end(0, 2.0 * R * (2.0 * 3.0 * H * net->e_obs + 2.0 * (double)H * ad.hid + 2.0 * (double)ad.hid * ad.n_out), st);
+    return 0;
+}
+
+// Input product of layer 0 over compact rows: G = [E | s_prev] W_ih[:, :c2]^T + cur[addr] + prev[previous addr] (gather.hpp);
+// first-step rows have no previous statement: their sample-embedding columns are zero too. *cell_done: the first time
+// step's cell ran in the product's epilogue
+static int lstm_input_compact(const Step& s, bool* cell_done) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const int B = p.B, R = p.R, T = p.T, H = p.H;
+    pp_gemm_args g{};
+    g.A = w.X; g.lda = w.i4;
+    g.B = s.P + net->w_ih; g.ldb = p.I;
+    g.C = w.Gl[0]; g.ldc = 4 * H;
+    g.M = R; g.N = 4 * H; g.K = p.nx;
+    GemmExt x{};
+    x.rb = w.AB; x.rb_addr = bt->addr; x.rb_prev = T > 1 ? bt->prev_row : nullptr;
+    if (T == 1 && p.n_present == 1) {   // one address in a single-statement batch: the bias is one vector
+        x.rb = w.AB + (int64_t)p.only_addr * 2 * 4 * H;
+        x.rb_addr = nullptr;
+    }
+    if (step_env().fuse_cell) {   // gate-interleaved tiles, LSTM cell of the first time step in the epilogue
+        x.cell_H = H; x.cell_rows = B; x.cell_c = w.Cl[0]; x.cell_h = w.Hl[0];
+        x.lean = p.lean_cell ? 1 : 0;
+        *cell_done = true;
+    }
+    GemmHole zc{};
+    zc.b[0] = GemmBlock{0, B, 0, 4 * H, net->e_obs, p.nx};
+    if (lstm_input_fast_ok(g, x)) PP_TRY(lstm_input_fast(g, x, s.st));      // (lstm_input.hip; the zero block is zeros in X)
+    else PP_TRY(gemm_f32(&g, s.st, &zc, &x));
+    prof_end(0, 2.0 * R * (double)p.nx * 4.0 * H, s.st);
+    return 0;
+}
+
+// the time steps of layer l behind its input product: G_t += h_{t-1} W_hh^T, then the cell
+static int lstm_recurrence(const Step& s, int l, bool cell_done) {
+    const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const int T = p.T, H = p.H;
+    const float* Whh = s.P + lstm_layer(s.net, l).w_hh;
+    const bool fuse_rec = step_env().fuse_cell_rec && !p.ff && !p.det;   // (float4 stores, and no fixed order is at stake)
+    for (int t = 0; t < T; ++t) {
+        if (p.tail_teams && t == p.tail_t0)   // all remaining time steps of this layer: one launch (lstm_tail.hip)
+            return lstm_tail_fwd(w.Gl[l], w.Cl[l], w.Hl[l], Whh, bt->row_off_dev, p.tail_t0, T, H, p.tail_teams, w.xch_f, w.xch_b,
+                                 w.flag, s.st);
+        const int n = bt->n_active[t], r0 = bt->row_off[t];
+        float* Gt = w.Gl[l] + (int64_t)r0 * 4 * H;
+        const float* c_prev = nullptr;
+        if (t > 0) {
+            const int rp = bt->row_off[t - 1];
+            pp_gemm_args g{};
+            g.A = w.Hl[l] + (int64_t)rp * H; g.lda = H;
+            g.B = Whh; g.ldb = H;
+            g.C = Gt; g.ldc = 4 * H;
+            g.M = n; g.N = 4 * H; g.K = H;
+            c_prev = w.Cl[l] + (int64_t)rp * H;
+            // Recurrent product with the cell in its epilogue (gate-interleaved tiles; one workgroup per tile walks all of
+            // K = H, the pre-activations are read instead of accumulated into): no lstm_cell_fwd launch, no round trip of
+            // G. Needs enough tiles to fill the chip without a K split: n >= 64 rows x 4H / 64 column tiles.
+            if (fuse_rec && H % 16 == 0 && n >= 64) {
+                GemmExt x{};
+                x.cell_H = H; x.cell_rows = n; x.cell_c = w.Cl[l] + (int64_t)r0 * H; x.cell_h = w.Hl[l] + (int64_t)r0 * H;
+                x.cell_cprev = c_prev;
+                PP_TRY(gemm_f32(&g, s.st, nullptr, &x));
+                continue;
+            }
+            g.accumulate = 1;
+            g.split_k = 1;   // few rows late in a ragged batch: spread K over workgroups (accumulation into G)
+            PP_TRY(gemm_f32(&g, s.st));
+        }
+        if (t == 0 && cell_done) continue;
+        PP_TRY(lstm_cell_fwd(Gt, c_prev, w.Cl[l] + (int64_t)r0 * H, w.Hl[l] + (int64_t)r0 * H, n, H, s.st));
+    }
+    return 0;
+}
+
+static int lstm_forward(const Step& s) {
+    const pp_net* net = s.net; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const int B = p.B, R = p.R, H = p.H;
+    for (int l = 0; l < p.L; ++l) {
+        bool cell_done = false;
+        if (l == 0) prof_begin(0, s.st);
+        if (l == 0 && p.compact) {
+            PP_TRY(lstm_input_compact(s, &cell_done));
+        } else {
+            const LstmLayer ly = lstm_layer(net, l);
+            const float* in = l == 0 ? w.X : w.Hl[l - 1];
+            const int64_t in_ld = l == 0 ? w.i4 : H;
+            const int in_w = l == 0 ? p.I : H;
+            // a trace's first time step has no previous variable: columns [e_obs, c4) of its LSTM input row are zero
+            // (inference_network_lstm.py:159-162) - rows [0, B) of the step-major layout, layer 0 -
+            // ... and no previous cell state in any layer: its forget gate multiplies c_{-1} = 0, so columns [H, 2H) of its
+            // pre-activations are never looked at (lstm_cell_fwd/bwd with c_prev == NULL) - not computed at all
+            GemmHole zero{};
+            zero.b[1] = GemmBlock{0, B, H, 2 * H, 0, in_w};
+            if (l == 0) zero.b[0] = GemmBlock{0, B, 0, 4 * H, p.c1, p.c4};
+            PP_TRY(linear_fwd(in, in_ld, nullptr, s.P + ly.w_ih, s.P + ly.b_ih, w.Gl[l], 4 * H, R, in_w, 4 * H, false, s.P + ly.b_hh,
+                              s.st, &zero));
+            if (l == 0) prof_end(0, 2.0 * R * (double)p.I * 4.0 * H, s.st);
+        }
+        PP_TRY(lstm_recurrence(s, l, cell_done));
+    }
+    return 0;
+}
+
+// bias gradients of one address group's proposal layers (rows [h0, h0 + m) of the group-compact buffers) by the
+// low-contention column-sum jobs
+static void queue_head_bias_sums(const Step& s, GradQueue& q, const pp_addr& ad, int h0, int m) {
+    const Workspace& w = s.w;
+    q.cs.push_back(ColsumJob{w.DY + (int64_t)h0 * w.out4, w.out4, nullptr, m, ad.n_out, s.grads + ad.b2, nullptr});
+    q.cs.push_back(ColsumJob{w.dZ1 + (int64_t)h0 * w.hid4, w.hid4, nullptr, m, ad.hid, s.grads + ad.b1, nullptr});
+}
+
+// Heads: first FF layer of EVERY address group in one grouped launch (rows gathered by address: the dispatch gather),
+// then the fused tails, grouped by (kind, shape)
+static int heads_forward(const Step& s, GradQueue& q) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const float* P = s.P; hipStream_t st = s.st;
+    const int H = p.H;
+    const float gscale = -1.0f / (float)p.B;
+    {
+        std::vector<pp_gemm_args> hq;
+        for (int a = 0; a < net->n_addr; ++a) {
+            const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
+            if (n <= 0) continue;
+            const pp_addr& ad = net->addrs[a];
+            pp_gemm_args g{};
+            g.A = p.heads_in; g.lda = p.heads_ld; g.a_idx = bt->grp_rows + g0;
+            g.B = P + ad.w1; g.ldb = H;
+            g.C = w.A1 + (int64_t)g0 * w.hid4; g.ldc = w.hid4;
+            g.M = n; g.N = ad.hid; g.K = H;
+            g.bias = P + ad.b1; g.relu = 1;
+            hq.push_back(g);
+        }
+        PP_TRY(gemm_f32_grouped(hq.data(), (int)hq.size(), st));
+    }
+    std::vector<char> done(net->n_addr, 0);
+    for (int a = 0; a < net->n_addr; ++a) {
+        const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
+        if (n <= 0 || done[a]) continue;
+        const pp_addr& ad = net->addrs[a];
+        if (head_tail_supported(ad.kind, ad.hid, ad.n_out)) {
+            // fused tail (layer 2 + log_prob + loss [+ dy, dz1]) for this and every later group of the same head shape
+            std::vector<TailJob> tj;
+            for (int b = a; b < net->n_addr; ++b) {
+                const pp_addr& bd = net->addrs[b];
+                const int h0 = bt->grp_off[b], m = bt->grp_off[b + 1] - h0;
+                if (m <= 0 || done[b] || bd.kind != ad.kind || bd.hid != ad.hid || bd.n_out != ad.n_out) continue;
+                done[b] = 1;
+                tj.push_back(TailJob{w.A1 + (int64_t)h0 * w.hid4, P + bd.w2, P + bd.b2, bt->grp_rows + h0,
+                                     p.bwd ? w.DY + (int64_t)h0 * w.out4 : nullptr, w.dZ1 + (int64_t)h0 * w.hid4, m});
+                if (p.bwd) queue_head_bias_sums(s, q, bd, h0, m);
+            }
+            PP_TRY(head_tail_multi(ad.kind, tj.data(), (int)tj.size(), w.hid4, ad.hid, ad.n_out, bt->value, bt->prior, gscale,
+                                   p.lp_rows, w.out4, w.hid4, p.loss_slots, w.flag, st));
+            continue;
+        }
+        done[a] = 1;
+        float* A1 = w.A1 + (int64_t)g0 * w.hid4;
+        float* Y = w.Y + (int64_t)g0 * w.out4;
+        PP_TRY(linear_fwd(A1, w.hid4, nullptr, P + ad.w2, P + ad.b2, Y, w.out4, n, ad.hid, ad.n_out, false, nullptr, st));
+        PP_TRY(head_logprob(ad.kind, Y, w.out4, bt->grp_rows + g0, bt->value, bt->prior, n, ad.n_out, gscale, p.lp_rows,
+                            p.bwd ? w.DY + (int64_t)g0 * w.out4 : nullptr, p.loss_slots, w.flag, st));
+    }
+    return 0;
+}
+
+// weight gradients of address a's two proposal layers
+static void queue_head_wgrads(const Step& s, GradQueue& q, int a) {
+    const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const pp_addr& ad = s.net->addrs[a];
+    const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
+    queue_wgrad(q.wq, w.DY + (int64_t)g0 * w.out4, w.out4, w.A1 + (int64_t)g0 * w.hid4, w.hid4, nullptr, s.grads + ad.w2, n, ad.hid,
+                ad.n_out);
+    // (panel kernel: one group that covers all rows in order - no gather, the product can take the streaming kernel)
+    queue_wgrad(q.wq, w.dZ1 + (int64_t)g0 * w.hid4, w.hid4, p.heads_in, p.heads_ld, p.panel ? nullptr : bt->grp_rows + g0,
+                s.grads + ad.w1, n, p.H, ad.hid);
+}
+
+// Heads backward: what the fused tails left undone, then dH = dZ1 W1 of every address group in one grouped launch
+static int heads_backward(const Step& s, GradQueue& q) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const float* P = s.P; float* grads = s.grads; hipStream_t st = s.st;
+    const int H = p.H;
+    std::vector<pp_gemm_args> dq;   // per-address data gradients into dH
+    for (int a = 0; a < net->n_addr; ++a) {
+        const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
+        if (n <= 0) continue;
+        const pp_addr& ad = net->addrs[a];
+        const float* A1 = w.A1 + (int64_t)g0 * w.hid4;
+        const float* DY = w.DY + (int64_t)g0 * w.out4;
+        float* dZ1 = w.dZ1 + (int64_t)g0 * w.hid4;
+        queue_head_wgrads(s, q, a);
+        if (!head_tail_supported(ad.kind, ad.hid, ad.n_out)) {   // (else dz1 was produced by the forward tail)
+            PP_TRY(colsum_f32(DY, w.out4, nullptr, n, ad.n_out, grads + ad.b2, nullptr, st));
+            PP_TRY(linear_dgrad(DY, w.out4, P + ad.w2, dZ1, w.hid4, nullptr, A1, w.hid4, n, ad.hid, ad.n_out, false, st,
+                                p.det ? nullptr : grads + ad.b1));   // db1 = colsum(dZ1) fused into the epilogue
+            if (p.det) q.cs.push_back(ColsumJob{dZ1, w.hid4, nullptr, n, ad.hid, grads + ad.b1, nullptr});
+        }
+        pp_gemm_args g{};   // dH[rows of this address] = dZ1 W1
+        g.A = dZ1; g.lda = w.hid4;
+        g.B = P + ad.w1; g.ldb = H; g.b_kmajor = 1;
+        g.C = w.dH; g.ldc = H; g.c_idx = bt->grp_rows + g0;
+        g.M = n; g.N = H; g.K = ad.hid;
+        if (p.fused_bwd) g.colsum = w.gsum + (int64_t)a * 2 * 4 * H;   // group sums of dG (current-address slot)
+        dq.push_back(g);
+    }
+    if (p.fused_bwd) {   // ... with the cell backward in its epilogue
+        GemmExt x{};
+        x.bw_G = w.Gl[0]; x.bw_C = w.Cl[0]; x.bw_H = H; x.lean = p.lean_cell ? 1 : 0;
+        return gemm_f32_grouped(dq.data(), (int)dq.size(), st, nullptr, &x);
+    }
+    return gemm_f32_grouped(dq.data(), (int)dq.size(), st);
+}
+
+// Parameter gradients of LSTM layer l (leaves, grouped with every head's weight gradients). First-time-step rows give
+// nothing to the forget-gate rows (dG[:, H:2H] = 0 where c_{t-1} = 0) and, in layer 0, nothing to the previous-variable
+// columns of dW_ih (their inputs are zero there)
+static void queue_lstm_wgrads(const Step& s, GradQueue& q, int l) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const int B = p.B, R = p.R, H = p.H;
+    const LstmLayer ly = lstm_layer(net, l);
+    GemmHole wh{};
+    if (l == 0 && p.compact) {   // dW_ih[:, :c2] = dG^T [E | s_prev]; the table columns follow from the group sums (aux jobs)
+        wh.b[1] = GemmBlock{H, 2 * H, 0, p.nx, 0, B};
+        wh.b[0] = GemmBlock{0, 4 * H, p.c1, p.nx, 0, B};
+        queue_wgrad(q.wq, w.Gl[0], 4 * H, w.X, w.i4, nullptr, s.grads + net->w_ih, R, p.nx, 4 * H, &q.holes, wh);
+        q.wq.back().ldc = p.I;
+    } else {
+        const float* in = l == 0 ? w.X : w.Hl[l - 1];
+        const int64_t in_ld = l == 0 ? w.i4 : H;
+        const int in_w = l == 0 ? p.I : H;
+        wh.b[1] = GemmBlock{H, 2 * H, 0, in_w, 0, B};
+        if (l == 0) wh.b[0] = GemmBlock{0, 4 * H, p.c1, p.c4, 0, B};
+        queue_wgrad(q.wq, w.Gl[l], 4 * H, in, in_ld, nullptr, s.grads + ly.w_ih, R, in_w, 4 * H, &q.holes, wh);
+    }
+    if (p.T > 1) {
+        const int r1 = bt->row_off[1];
+        queue_wgrad(q.wq, w.Gl[l] + (int64_t)r1 * 4 * H, 4 * H, w.Hl[l], H, bt->prev_row + r1, s.grads + ly.w_hh, R - r1, H, 4 * H);
+    }
+}
+
+// the time steps of layer l, last to first: cell backward (bias gradients fused), dh_{t-1} += dG_t W_hh
+static int lstm_backward_steps(const Step& s, int l, float* dH_cur) {
+    const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const int B = p.B, T = p.T, H = p.H;
+    const LstmLayer ly = lstm_layer(s.net, l);
+    const float* Whh = s.P + ly.w_hh;
+    float* db_ih = p.det ? nullptr : s.grads + ly.b_ih;
+    float* db_hh = p.det ? nullptr : s.grads + ly.b_hh;
+    // the top layer's first cell launch folds the loss slots (the tail launch when there is one)
+    LossFinalize fin = p.fin;
+    if (l != p.L - 1) fin.acc = nullptr;
+    int dh_parts = 0;   // K splits of dG_{t+1} W_hh waiting in w.dHp for the cell backward of step t
+    for (int t = T - 1; t >= 0; --t) {
+        if (p.tail_teams && t >= p.tail_t0) {   // steps T-1 .. tail_t0 in one launch; it leaves dh / dc of step tail_t0 - 1
+            PP_TRY(lstm_tail_bwd(w.Gl[l], w.Cl[l], dH_cur, w.dC, Whh, bt->row_off_dev, p.tail_t0, T, H, p.tail_teams, w.xch_f,
+                                 w.xch_b, w.flag, db_ih, db_hh, fin, s.st));
+            t = p.tail_t0;
+            continue;
+        }
+        const int n = bt->n_active[t], r0 = bt->row_off[t];
+        const int n_next = (t + 1 < T) ? bt->n_active[t + 1] : 0;
+        float* Gt = w.Gl[l] + (int64_t)r0 * 4 * H;
+        const float* c_prev = t > 0 ? w.Cl[l] + (int64_t)bt->row_off[t - 1] * H : nullptr;
+        PP_TRY(lstm_cell_bwd(Gt, c_prev, w.Cl[l] + (int64_t)r0 * H, dH_cur + (int64_t)r0 * H, w.dC, n, n_next, H, db_ih, db_hh, s.st,
+                             t == T - 1 ? fin.acc : nullptr, w.flag, B, fin.loss_out, fin.status_out, w.dHp, dh_parts,
+                             (int64_t)B * H));   // + the stored partials of dG_{t+1} W_hh
+        dh_parts = 0;
+        if (t == 0) break;
+        // dh_{t-1} += dG_t W_hh as K-split partial tiles that the NEXT cell-backward launch adds (rows [0, n) of step t - 1
+        // are the same traces): no float atomics (6 us per 64 x 64 tile), no read-modify-write of dH
+        const int tiles = cdiv(n, 64) * cdiv(H, 64), nslab = 4 * H / 32;
+        const int splits = std::max(1, std::min({DH_SPLITS, cdiv(256, tiles), nslab / 2}));
+        if (step_env().dh_partials && !p.det && splits > 1 && H % 4 == 0) {
+            pp_gemm_args g{};
+            g.A = Gt; g.lda = 4 * H;
+            g.B = Whh; g.ldb = H; g.b_kmajor = 1;
+            g.C = w.dHp; g.ldc = H;
+            g.M = n; g.N = H; g.K = 4 * H;
+            GemmExt x{};
+            x.split_stride = (int64_t)B * H;
+            x.force_splits = splits;
+            PP_TRY(gemm_f32(&g, s.st, nullptr, &x));
+            dh_parts = splits;
+        } else {
+            PP_TRY(linear_dgrad(Gt, 4 * H, Whh, dH_cur + (int64_t)bt->row_off[t - 1] * H, H, nullptr, nullptr, 0, n, H, 4 * H, true,
+                                s.st));
+        }
+    }
+    return 0;
+}
+
+static int lstm_backward(const Step& s, GradQueue& q) {
+    const Workspace& w = s.w; const StepPlan& p = s.p;
+    const int B = p.B, R = p.R, H = p.H;
+    float* dH_cur = w.dH;          // gradient into the hidden states of the layer being processed (top: from the heads)
+    float* dH_other = w.dH2;
+    for (int l = p.L - 1; l >= 0; --l) {
+        const LstmLayer ly = lstm_layer(s.net, l);
+        if (!p.fused_bwd) PP_TRY(lstm_backward_steps(s, l, dH_cur));   // (else dG is already in place)
+        if (p.det)   // bias gradients = column sums of the complete dG of this layer, by the single-writer kernel
+            q.cs.push_back(ColsumJob{w.Gl[l], 4 * H, nullptr, R, 4 * H, s.grads + ly.b_ih, s.grads + ly.b_hh});
+        queue_lstm_wgrads(s, q, l);
+        if (l > 0) {   // gradient into the hidden states of the layer below: dH_{l-1} = dG_l W_ih_l (the forget-gate part of
+            GemmHole dh{};                                         // the sum is zero for first-time-step rows)
+            dh.b[0] = GemmBlock{0, B, 0, H, H, 2 * H};
+            PP_TRY(linear_dgrad(w.Gl[l], 4 * H, s.P + ly.w_ih, dH_other, H, nullptr, nullptr, 0, R, H, 4 * H, false, s.st, nullptr,
+                                &dh));
+            std::swap(dH_cur, dH_other);
+        }
+    }
+    return 0;
+}
+
+// Layer 0's data gradient dX = dG W_ih, then scatter into the embedding tables / sample embeddings (the observe embedding
+// follows). Nobody reads the previous-variable columns of first-time-step rows (no previous variable, no parameter behind
+// them). The forget-gate part of the summation over the gates is zero for those rows.
+static int input_backward(const Step& s, GradQueue& q) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const float* P = s.P; float* grads = s.grads; hipStream_t st = s.st;
+    const int B = p.B, R = p.R, T = p.T, H = p.H;
+    if (p.compact) {
+        // dX[:, :c2] = dG W_ih[:, :c2] (observe-embedding and sample-embedding columns; the table columns need no per-row
+        // gradient: their parameter gradients follow from the column sums of dG per address group)
+        const GemmHole dx_unused{{{0, B, p.c1, p.nx, 0, 4 * H}, {0, B, 0, p.nx, H, 2 * H}}};
+        pp_gemm_args g{};
+        g.A = w.G; g.lda = 4 * H;
+        g.B = P + net->w_ih; g.ldb = p.I; g.b_kmajor = 1;
+        g.C = w.dX; g.ldc = w.i4;
+        g.M = R; g.N = p.nx; g.K = 4 * H;
+        if (p.dx_partials) {
+            GemmExt x{};
+            x.split_stride = (int64_t)R * w.i4;
+            x.force_splits = p.dx_splits;
+            PP_TRY(gemm_f32(&g, st, &dx_unused, &x));
+        } else {
+            g.accumulate = 1;   // dX was cleared by the gather kernel
+            g.split_k = 1;
+            PP_TRY(gemm_f32(&g, st, &dx_unused));
+        }
+        if (!p.fused_bwd)   // group sums of dG by current / previous address (the fused dH epilogue produced the former)
+            for (int a = 0; a < net->n_addr; ++a) {
+                const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
+                if (n > 0) q.cs.push_back(ColsumJob{w.G, 4 * H, bt->grp_rows + g0, n, 4 * H, w.gsum + (int64_t)a * 2 * 4 * H, nullptr});
+                const int q0 = bt->nxt_off[a], m = bt->nxt_off[a + 1] - q0;
+                if (m > 0)
+                    q.cs.push_back(ColsumJob{w.G, 4 * H, bt->nxt_rows + q0, m, 4 * H, w.gsum + ((int64_t)a * 2 + 1) * 4 * H, nullptr});
+            }
+    } else {
+        const GemmHole dx_unused{{{0, B, p.c1, p.c4, 0, 4 * H}, {0, B, 0, p.I, H, 2 * H}}};
+        PP_TRY(linear_dgrad(w.G, 4 * H, P + net->w_ih, w.dX, w.i4, nullptr, nullptr, 0, R, p.I, 4 * H, true, st, nullptr,
+                            &dx_unused));   // dX was cleared by the gather kernel
+        for (int a = 0; a < net->n_addr; ++a) {   // table columns of dX -> the embedding vectors
+            const pp_addr& ad = net->addrs[a];
+            const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
+            if (n > 0) {  // rows where `a` is the current address
+                q.cs.push_back(ColsumJob{w.dX + p.c4, w.i4, bt->grp_rows + g0, n, net->dtype_dim, grads + ad.dtype_emb, nullptr});
+                q.cs.push_back(ColsumJob{w.dX + p.c5, w.i4, bt->grp_rows + g0, n, net->addr_dim, grads + ad.addr_emb, nullptr});
+            }
+            const int q0 = bt->nxt_off[a], m = bt->nxt_off[a + 1] - q0;
+            if (m > 0) {  // rows whose previous variable has address `a`
+                q.cs.push_back(ColsumJob{w.dX + p.c2, w.i4, bt->nxt_rows + q0, m, net->dtype_dim, grads + ad.dtype_emb, nullptr});
+                q.cs.push_back(ColsumJob{w.dX + p.c3, w.i4, bt->nxt_rows + q0, m, net->addr_dim, grads + ad.addr_emb, nullptr});
+            }
+        }
+    }
+    if (T > 1 && p.det)
+        PP_TRY(sample_embed_bwd_det(net, P, bt->value, bt->prev_row, bt->nxt_rows, bt->nxt_off, w.dX, w.i4, grads, st));
+    else if (T > 1)
+        PP_TRY(sample_embed_bwd(net, P, bt->value, bt->addr, bt->prev_row, bt->row_off[1], R, w.dX, w.i4, grads, st));
+    return 0;
+}
+
+// Launches the queued weight-gradient leaves as one grouped launch, `aux` behind its tiles.
+static int flush_wgrads(const Step& s, GradQueue& q, const AuxJobs* aux = nullptr) {
+    std::vector<pp_gemm_args>& wq = q.wq;
+    std::vector<GemmHole>& wholes = q.holes;
+    wholes.resize(wq.size(), GemmHole{});
+    // data parallel with an overlap range (dp.hip): the products that complete the range - the LSTM layer's weight
+    // gradients - and the reduction jobs go first; the range's all-reduce starts on the side stream behind them and the
+    // remaining products (proposal layers, observe embedding) run under it
+    int64_t lo = 0, hi = 0;
+    if (dp_overlap_hull(&lo, &hi) && wq.size() > 1) {
+        std::vector<pp_gemm_args> qa, qb;
+        std::vector<GemmHole> ha, hb;
+        for (size_t i = 0; i < wq.size(); ++i) {
+            const bool in = wq[i].C >= s.grads + lo && wq[i].C < s.grads + hi;
+            (in ? qa : qb).push_back(wq[i]);
+            (in ? ha : hb).push_back(wholes[i]);
+        }
+        if (!qa.empty() && !qb.empty()) {
+            PP_TRY(launch_wgrads(qa, s.st, &ha, true, aux, true));
+            PP_TRY(dp_bucket0_issue(s.grads, s.st));
+            PP_TRY(launch_wgrads(qb, s.st, &hb, false, nullptr, true));
+            wq.clear();
+            wholes.clear();
+            return 0;
+        }
+    }
+    PP_TRY(launch_wgrads(wq, s.st, &wholes, true, aux, true));
+    wq.clear();
+    wholes.clear();
+    return 0;
+}
+
+// the live column-sum jobs as jobs behind the weight-gradient tiles; false (nothing copied): more than the job table holds
+static bool colsums_ride(const std::vector<ColsumJob>& cs, AuxJobs& aux) {
+    int n_live = 0;
+    for (const auto& j : cs) n_live += (j.n_rows > 0 && j.n_cols > 0) ? 1 : 0;
+    if (n_live > AUX_MAX_COLSUM) return false;
+    for (const auto& j : cs)
+        if (j.n_rows > 0 && j.n_cols > 0) aux.cs[aux.n_colsum++] = j;
+    return true;
+}
+
+// Column sums + weight-gradient leaves. Compact rows: the jobs that turn the group sums of dG into the table-column
+// gradients (and, after the fused cell backward, the LSTM bias gradients and the loss) ride behind the tiles of the
+// grouped weight-gradient launch; for a single-statement batch so do the column sums themselves (nothing in the
+// launch depends on anything else in it), which removes the separate column-sum launch.
+static int reduce_and_flush(const Step& s, GradQueue& q) {
+    const pp_net* net = s.net; const StepPlan& p = s.p;
+    const bool ride = step_env().aux_colsum;
+    AuxJobs aux{};
+    if (!p.compact) {
+        // FeedForward network: no column sum depends on another launch's group sums, so they all ride behind the
+        // weight-gradient tiles (and the loss is finalised there): one launch less per step
+        if (p.ff && !p.det && ride && !q.wq.empty() && colsums_ride(q.cs, aux)) {
+            aux.fin = p.fin;
+            aux_layout(aux, false);
+            return flush_wgrads(s, q, &aux);
+        }
+        if (p.ff)   // (LSTM: the first cell launch of the backward pass finalises the loss)
+            PP_TRY(colsum_multi(q.cs.data(), (int)q.cs.size(), s.st, p.fin_acc, s.w.flag, p.B, p.fin.loss_out, p.fin.status_out));
+        else
+            PP_TRY(colsum_multi(q.cs.data(), (int)q.cs.size(), s.st));
+        return flush_wgrads(s, q);
+    }
+    if (!(p.fused_bwd && ride && colsums_ride(q.cs, aux))) PP_TRY(colsum_multi(q.cs.data(), (int)q.cs.size(), s.st));
+    aux_derived(s, aux);
+    if (p.fused_bwd) {
+        aux.db_ih = s.grads + net->b_ih; aux.db_hh = s.grads + net->b_hh;
+        aux.fin = p.fin;
+    }
+    aux_layout(aux, true);
+    return flush_wgrads(s, q, &aux);
+}
+
+// the gradient of the observe embedding is summed over the time steps from dX[:, :e_obs] (LSTM) / from dH (FF)
+static const float* obs_grad_rows(const Step& s, int64_t* ld) {
+    *ld = s.p.ff ? s.p.H : s.w.i4;
+    return s.p.ff ? s.w.dH : s.w.dX;
+}
+
+// Fused observe-embedding backward: dE (sum over the trace's time steps of dX, masked by the last ReLU) and the data
+// gradients of the whole stack in one launch ...
+static int obs_dgrad_fused(const Step& s) {
+    const Workspace& w = s.w; const StepPlan& p = s.p;
+    int64_t ldxs;
+    const float* dXs = obs_grad_rows(s, &ldxs);
+    return obs_embed_dgrad_fused(s.net, s.P, p.B, w.obs_h, w.cat, w.f1, dXs, ldxs, s.bt->row_off_dev, p.T, w.E, w.dE, w.dF1, w.dCat,
+                                 w.dObsH, (int64_t)p.B * w.maxohid4, s.st, p.dx_splits, (int64_t)p.R * w.i4);
+}
+// ... its weight gradients join the grouped MFMA launch; bias gradients are column sums of the same buffers
+static void queue_obs_grads_fused(const Step& s, GradQueue& q) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w;
+    float* grads = s.grads;
+    const int B = s.p.B, e = net->e_obs;
+    const int64_t dhs = (int64_t)B * w.maxohid4;
+    queue_wgrad(q.wq, w.dE, w.e4, w.f1, w.e4, nullptr, grads + net->fin_w1, B, e, e);
+    queue_wgrad(q.wq, w.dF1, w.e4, w.cat, w.e4, nullptr, grads + net->fin_w0, B, e, e);
+    q.cs.push_back(ColsumJob{w.dE, w.e4, nullptr, B, e, grads + net->fin_b1, nullptr});
+    q.cs.push_back(ColsumJob{w.dF1, w.e4, nullptr, B, e, grads + net->fin_b0, nullptr});
+    int ci = 0, co = 0;
+    for (int o = 0; o < net->n_obs; ++o) {
+        const int in = net->obs_in[o], hid = net->obs_hid[o], out = net->obs_out[o];
+        float* dHo = w.dObsH + (int64_t)o * dhs;
+        queue_wgrad(q.wq, w.dCat + co, w.e4, w.obs_h[o], w.ohid4[o], nullptr, grads + net->obs_w1[o], B, hid, out);
+        // dW0[:, k] = sum_b dh[b, :] obs[b, k]: a handful of input columns -> weighted column sums, not a GEMM
+        for (int k = 0; k < in; ++k)
+            q.cs.push_back(ColsumJob{dHo, w.ohid4[o], nullptr, B, hid, grads + net->obs_w0[o] + k, nullptr, bt->obs + ci + k,
+                                     bt->obs_width, in});
+        q.cs.push_back(ColsumJob{w.dCat + co, w.e4, nullptr, B, out, grads + net->obs_b1[o], nullptr});
+        q.cs.push_back(ColsumJob{dHo, w.ohid4[o], nullptr, B, hid, grads + net->obs_b0[o], nullptr});
+        ci += in;
+        co += out;
+    }
+}
+
+// Generic observe-embedding backward (any depth, CNN2D5C): behind the step's grouped launch, layer by layer
+static int obs_backward_generic(const Step& s, GradQueue& q) {
+    const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
+    const float* P = s.P; float* grads = s.grads; hipStream_t st = s.st;
+    const int B = p.B, e = net->e_obs;
+    int64_t ldxs;
+    const float* dXs = obs_grad_rows(s, &ldxs);
+    PP_TRY(obs_grad(dXs, ldxs, bt->row_off_dev, p.T, B, e, w.E, w.e4, w.dE, w.e4, st));   // dE, ReLU mask applied
+    PP_TRY(reduce_and_flush(s, q));
+    PP_TRY(linear_wgrad(w.dE, w.e4, w.f1, w.e4, nullptr, grads + net->fin_w1, grads + net->fin_b1, nullptr, B, e, e, st));
+    PP_TRY(linear_dgrad(w.dE, w.e4, P + net->fin_w1, w.dF1, w.e4, nullptr, w.f1, w.e4, B, e, e, false, st,
+                        p.det ? nullptr : grads + net->fin_b0));
+    if (p.det) PP_TRY(colsum_f32(w.dF1, w.e4, nullptr, B, e, grads + net->fin_b0, nullptr, st));
+    PP_TRY(linear_wgrad(w.dF1, w.e4, w.cat, w.e4, nullptr, grads + net->fin_w0, nullptr, nullptr, B, e, e, st));
+    PP_TRY(linear_dgrad(w.dF1, w.e4, P + net->fin_w0, w.dCat, w.e4, nullptr, w.cat, w.e4, B, e, e, false, st));
+    int ci = 0, co = 0;
+    for (int o = 0; o < net->n_obs; ++o) {
+        // backward through EmbeddingFeedForward(num_layers = depth): dz of layer l (ReLU mask already applied) gives
+        // dW_l = dz^T x_l, db_l = colsum dz, and dz of layer l - 1 = (dz W_l) * [x_l > 0]
+        const bool cnn = net->obs_kind[o] == PP_OBS_CNN2D5C;      // layer 0 (_lin1) reads the convolution stack's features
+        const float* dz = w.dCat + co;
+        int64_t lddz = w.e4;
+        float* scratch[2] = {w.dObsH, w.dObsH2};
+        for (int l = obs_layers(net, o) - 1; l >= 0; --l) {
+            const ObsLin ly = obs_lin(net, o, l);
+            const float* x = l == 0 ? (cnn ? w.cnn_feat[o] : bt->obs + ci) : w.obs_hl[o][l - 1];
+            const int64_t ldx = l == 0 ? (cnn ? w.f4[o] : bt->obs_width) : w.ohid4[o];
+            PP_TRY(linear_wgrad(dz, lddz, x, ldx, nullptr, grads + ly.w, grads + ly.b, nullptr, B, ly.in, ly.out, st));
+            if (l > 0) {
+                float* dprev = scratch[l & 1];
+                PP_TRY(linear_dgrad(dz, lddz, P + ly.w, dprev, w.ohid4[o], nullptr, x, ldx, B, ly.in, ly.out, false, st));
+                dz = dprev;
+                lddz = w.ohid4[o];
+            } else if (cnn) {
+                // the image is data, its features are not: dFeatures = dz W_lin1 (no mask here: the pool backward applies
+                // conv5's), then back through the stack
+                PP_TRY(linear_dgrad(dz, lddz, P + ly.w, w.cnn_dfeat[o], w.f4[o], nullptr, nullptr, 0, B, ly.in, ly.out, false, st));
+                PP_TRY(cnn_backward(net, o, w.cnn_dfeat[o], w.f4[o], B, grads, w.cnn_ws[o], w.cnn_ws_bytes[o], st));
+            }
+        }
+        ci += net->obs_in[o];
+        co += net->obs_out[o];
+    }
     return 0;
 }
 
@@ -426,679 +1247,46 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
     }
     const bool bwd = flags & PP_LOSS_BACKWARD;
     PP_CHECK_ARG(!bwd || grads, "pp_ic_loss: PP_LOSS_BACKWARD needs a gradient buffer");
-    const bool ff = net->lstm_dim == 0;   // FeedForward network (inference_network_feedforward.py:68-98)
-    const int B = bt->n_traces, R = bt->n_rows, T = bt->t_max, H = ff ? net->e_obs : net->lstm_dim, I = net->lstm_in;
     Workspace w;
-    carve(net, B, R, ws, ws_bytes, w);
+    carve(net, bt->n_traces, bt->n_rows, ws, ws_bytes, w);
     if (w.bytes > ws_bytes) {
         set_error("pp_ic_loss: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
         return PP_ENOSPACE;
     }
     if (bwd && (flags & PP_LOSS_ZERO_GRADS)) (void)hipMemsetAsync(grads, 0, (size_t)net->n_params * sizeof(float), st);
-
-    // ---------------- forward ----------------
-    // First kernel: observe embedding; for small embeddings the same launch assembles the LSTM input rows of its traces
-    // and clears the loss slots and (backward) dX. Otherwise embedding GEMMs + the stand-alone gather kernel.
-    const bool fused_obs = obs_fused_supported(net);
-    // ragged batches: the time steps t >= tail_t0 (few rows each) of every LSTM layer run in one launch per direction
-    int tail_t0 = T, tail_teams = 0;
-    if (!ff) lstm_tail_plan(bt->n_active, T, H, &tail_t0, &tail_teams);
-    const int n_clear = PP_LOSS_SLOTS_FLOATS;
-    const float* heads_in = w.Hs;     // input rows of the proposal layers: LSTM outputs, or observe embeddings (FF)
-    int64_t heads_ld = H;
-    // kernel class 2 of the in-stream timing: observe embedding + LSTM input rows (the gather path). Algorithmic bytes:
-    // observations and per-row (value, address, previous row) in; X rows, E / cat / f1 and the observables' hidden
-    // activations out (SURVEY.md 8d: 4 I per trace-step written, 4 n_obs per trace read)
-    double gather_bytes = 4.0 * B * bt->obs_width + 12.0 * R + 4.0 * (ff ? 0.0 : (double)R * w.xc) + 3.0 * 4.0 * B * net->e_obs;
-    if (!ff && (flags & PP_LOSS_BACKWARD)) gather_bytes += 4.0 * R * w.xc;   // the same launch clears dX
-    // compact rows: the same launch computes the per-address bias vectors of the LSTM input (reads W_ih[:, c2:I] per
-    // present address, writes 2 x 4H, clears the group sums)
-    const bool compact = w.compact;
-    const int c2x = net->e_obs + net->smp_dim, ne_x = net->dtype_dim + net->addr_dim;
-    // single-statement batches have no previous statement at all: the sample-embedding columns are zero in every row
-    const int nx = (T == 1) ? net->e_obs : c2x;
-    // Single-statement batch: dX = dG W_ih[:, :e_obs] has ONE consumer, the observe-embedding backward kernel; its K splits
-    // store their partial tiles and that kernel adds them - no float atomics (6-8 us per 64 x 64 tile, tools/wg_trace.py)
-    // and no cleared dX
-    static const int dx_partials_env = env_flag("PP_DX_PARTIALS", 1);
-    const bool dx_partials = compact && bwd && T == 1 && dx_partials_env && obs_fused_supported(net);
-    // (see GemmExt::lean) the cell backward of a single-statement, single-layer batch runs in the dH epilogue, and with the
-    // zero blocks on neither dX nor dW_ih read the forget gate's columns of first-step rows
-    // (H a multiple of 64: the zero blocks then cover the forget gate's tiles and slabs exactly)
-    static const bool lean_env = env_flag("PP_FUSE_CELL_BWD", 1) && env_flag("PP_FUSE_CELL", 1) && env_flag("PP_GEMM_HOLES", 1) == 1 &&
-                                 env_flag("PP_CELL_LEAN", 1);
-    // (and dX as stored split partials: that product then runs on the async tiles, which skip the forget gate's K range)
-    const bool lean_cell = compact && bwd && T == 1 && std::max(1, (int)net->lstm_depth) == 1 && H % 64 == 0 && lean_env &&
-                           dx_partials;
-    AddrBias abias{};
-    int n_present = 0, only_addr = 0;   // addresses that occur in the batch
-    if (compact) {
-        abias.AB = w.AB; abias.gsum = w.gsum; abias.step_epoch = w.epoch;
-        abias.W = P + net->w_ih; abias.b_ih = P + net->b_ih; abias.b_hh = P + net->b_hh;
-        abias.params = P; abias.at = net->addr_table; abias.ldw = I;
-        abias.N = 4 * H; abias.c2 = c2x; abias.c3 = c2x + net->dtype_dim; abias.c4 = c2x + ne_x;
-        abias.c5 = abias.c4 + net->dtype_dim; abias.I = I; abias.n_addr = net->n_addr;
-        for (int q = 0; q < 32; ++q) abias.present[q] = 0u;
-        for (int a = 0; a < net->n_addr; ++a)
-            if (bt->grp_off[a + 1] > bt->grp_off[a] || bt->nxt_off[a + 1] > bt->nxt_off[a]) {
-                abias.present[a >> 5] |= 1u << (a & 31);
-                ++n_present;
-                only_addr = a;
-            }
-        gather_bytes += (double)n_present * (4.0 * 4 * H * (2.0 * ne_x) + 4.0 * 4.0 * 4 * H);
+    const StepPlan p = plan_step(net, bt, flags, lp_out, loss_out, status_out, w);
+    const Step s{net, bt, P, grads, w, p, st, lp_out, flags};
+    GradQueue q;
+    PP_TRY(first_launch(s));
+    if (p.panel) {
+        // The headline step, four launches with Adam: the first one also wrote the panel kernel's weight images; the panel
+        // launch left dG, the group sums, dz1, dy and dX (and, with obs_tail, the embedding's data gradients) - what
+        // remains is to queue the leaves in the general path's order and to launch them.
+        // (panel implies lean_cell, which implies bwd, compact rows, T == 1 and one LSTM layer: no forward-only call gets here)
+        PP_TRY(panel_launch(s));
+        const pp_addr& ad = net->addrs[p.only_addr];
+        queue_head_bias_sums(s, q, ad, 0, p.R);
+        queue_head_wgrads(s, q, p.only_addr);
+        queue_lstm_wgrads(s, q, 0);
+        if (!p.obs_tail) PP_TRY(obs_dgrad_fused(s));
+        queue_obs_grads_fused(s, q);
+        return reduce_and_flush(s, q);
     }
-    for (int o = 0; o < net->n_obs; ++o) gather_bytes += 4.0 * B * net->obs_hid[o];
-    // Row-panel kernel (panel.hip): a single-statement batch with ONE address keeps input product + cell, head layer 1, the
-    // head tail, dz1, dH + cell backward and dX in one launch (rows of the one address group are the batch rows in order)
-    bool panel = false, obs_tail = false;
-    bool panel16_go = false;      // the 16-row kernel (panel16.hip) instead of the 8-row one (panel.hip)
-    if (lean_cell && n_present == 1 && fused_obs && bt->grp_off[only_addr] == 0 && bt->grp_off[only_addr + 1] == R) {
-        const pp_addr& ad = net->addrs[only_addr];
-        const bool shape_ok = head_tail_supported(ad.kind, ad.hid, ad.n_out) &&
-                              w.hid4 <= ((ad.hid + 15) & ~15) && w.out4 <= 64 && (flags & PP_LOSS_KEEP_LP ? lp_out != nullptr : true);
-        panel16_go = shape_ok && w.p16.img[0] && panel16_supported(ad.kind, H, ad.hid, ad.n_out, net->e_obs, R);
-        if (panel16_go && bwd) {
-            ObsFusedArgs oa;
-            panel16_go = obs_fused_supported(net) && obs_fused_args(net, w.obs_h, oa) && panel16_obs_ok(oa);
-        }
-        panel = panel16_go || (shape_ok && panel_t1_supported(ad.kind, H, ad.hid, ad.n_out, net->e_obs) && panel_t1_split(R, H) == 2);
-    }
-    prof_begin(2, st);
-    if (ff) {
-        // every time step's proposal layer reads the observe embedding of its trace (:72,85): Hs rows = E[trace]
-        // (single-statement batches: row r IS trace r, the heads read E in place and the embedding kernel clears the
-        // loss slots - one launch less)
-        const bool in_place = fused_obs && T == 1;
-        if (fused_obs) {
-            RowBuild rb{};
-            rb.zero_small = in_place ? reinterpret_cast<float*>(w.loss_acc) : nullptr;
-            rb.n_small = n_clear;
-            PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb));
-        } else {
-            PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, bwd));
-        }
-        if (in_place) {
-            heads_in = w.E;
-            heads_ld = w.e4;
-        } else {
-            PP_TRY(embedding_rows(w.E, w.e4, bt->trace, R, net->e_obs, w.Hs, H, reinterpret_cast<float*>(w.loss_acc),
-                                  n_clear, st));
-        }
-    } else if (fused_obs && T <= 2) {   // (long traces: a wave would write all rows of its trace serially - separate gather)
-        RowBuild rb{};
-        rb.d = GatherDims{net->e_obs, net->smp_dim, net->dtype_dim, net->addr_dim, net->lstm_in};
-        rb.params = P; rb.at = net->addr_table; rb.row_off = bt->row_off_dev; rb.t_max = T;
-        rb.value = bt->value; rb.addr = bt->addr; rb.prev_row = bt->prev_row;
-        rb.X = w.X; rb.ldx = w.i4; rb.xcols = w.xc;
-        rb.zero_like = (bwd && !dx_partials) ? w.dX : nullptr;
-        rb.zero_small = reinterpret_cast<float*>(w.loss_acc); rb.n_small = n_clear;
-        PanelTranspose ptr{};
-        if (panel) {
-            const pp_addr& ad = net->addrs[only_addr];
-            ptr.Wih = P + net->w_ih; ptr.ldw = I; ptr.WihT = w.WihT;
-            ptr.W1 = P + ad.w1; ptr.W1T = w.W1T; ptr.ld1T = 64 * ((ad.hid + 63) / 64);
-            ptr.H = H; ptr.hid = ad.hid; ptr.e = net->e_obs;
-            ptr.tiles_ih = 3 * H / 64;
-            ptr.n_blocks = panel_transpose_blocks(H, ad.hid);
-            if (panel16_go) {      // the job writes the six fragment images instead (one thread per fragment lane)
-                ptr.mode16 = 1;
-                ptr.wt = store_wt_mode();
-                ptr.p16.W2 = P + ad.w2; ptr.p16.n_out = ad.n_out;
-                ptr.p16.im = w.p16;
-                panel16_image_sizes(H, ad.hid, net->e_obs, ptr.p16.im.frags);      // (this address's head; the buffers hold the widest)
-                int nb = 0;
-                for (int i = 0; i < 6; ++i) {
-                    ptr.p16.blocks_before[i] = nb;
-                    nb += cdiv(ptr.p16.im.frags[i] * 64, 256);
-                }
-                ptr.p16.blocks_before[6] = nb;
-                ptr.n_blocks = nb;
-            }
-        }
-        PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb, compact ? &abias : nullptr,
-                                   panel ? &ptr : nullptr));
-    } else {
-        PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, bwd));
-        // (also clears the loss slots and, for a backward pass, dX: see the kernel)
-        PP_TRY(lstm_input_gather(net, P, w.E, w.e4, bt->trace, bt->value, bt->addr, bt->prev_row, -1, -1, R, w.X, w.i4, st,
-                                 bwd ? w.dX : nullptr, reinterpret_cast<float*>(w.loss_acc), n_clear, w.xc,
-                                 compact ? &abias : nullptr));
-    }
-    prof_end(2, gather_bytes, st);
-    // nn.LSTM(I, H, depth), inference_network_lstm.py:31,186-188: layer k reads the hidden states of layer k - 1
-    const int L = ff ? 0 : std::max(1, (int)net->lstm_depth);
-    const bool compact_ok_dims = !ff && !deterministic_mode();   // (fused epilogues use float4 stores and no fixed order is at stake)
-    auto lw_ih = [&](int l) { return l == 0 ? net->w_ih : net->lstm_w_ih[l]; };
-    auto lw_hh = [&](int l) { return l == 0 ? net->w_hh : net->lstm_w_hh[l]; };
-    auto lb_ih = [&](int l) { return l == 0 ? net->b_ih : net->lstm_b_ih[l]; };
-    auto lb_hh = [&](int l) { return l == 0 ? net->b_hh : net->lstm_b_hh[l]; };
-    for (int l = 0; l < L; ++l) {
-        const float* in = l == 0 ? w.X : w.Hl[l - 1];
-        const int64_t in_ld = l == 0 ? w.i4 : H;
-        const int in_w = l == 0 ? I : H;
-        // a trace's first time step has no previous variable: columns [e_obs, c4) of its LSTM input row are zero
-        // (inference_network_lstm.py:159-162) - rows [0, B) of the step-major layout, layer 0 -
-        // ... and no previous cell state in any layer: its forget gate multiplies c_{-1} = 0, so columns [H, 2H) of its
-        // pre-activations are never looked at (lstm_cell_fwd/bwd with c_prev == NULL) - not computed at all
-        GemmHole zero{};
-        zero.b[1] = GemmBlock{0, B, H, 2 * H, 0, in_w};
-        if (l == 0) zero.b[0] = GemmBlock{0, B, 0, 4 * H, net->e_obs, net->e_obs + net->smp_dim + net->dtype_dim + net->addr_dim};
-        if (l == 0) prof_begin(0, st);
-        bool cell_done = false;   // the first time step's cell ran in the product's epilogue
-        if (l == 0 && compact) {
-            // G = [E | s_prev] W_ih[:, :c2]^T + cur[addr] + prev[previous addr] (gather.hpp); first-step rows have no previous
-            // statement: their sample-embedding columns are zero too
-            pp_gemm_args g{};
-            g.A = w.X; g.lda = w.i4;
-            g.B = P + net->w_ih; g.ldb = I;
-            g.C = w.Gl[0]; g.ldc = 4 * H;
-            g.M = R; g.N = 4 * H; g.K = nx;
-            GemmExt x{};
-            x.rb = w.AB; x.rb_addr = bt->addr; x.rb_prev = T > 1 ? bt->prev_row : nullptr;
-            if (T == 1 && n_present == 1) {   // one address in a single-statement batch: the bias is one vector
-                x.rb = w.AB + (int64_t)only_addr * 2 * 4 * H;
-                x.rb_addr = nullptr;
-            }
-            static const int fuse_cell = env_flag("PP_FUSE_CELL", 1);
-            if (fuse_cell) {   // gate-interleaved tiles, LSTM cell of the first time step in the epilogue
-                x.cell_H = H; x.cell_rows = B; x.cell_c = w.Cl[0]; x.cell_h = w.Hl[0];
-                x.lean = lean_cell ? 1 : 0;
-                cell_done = true;
-            }
-            GemmHole zc{};
-            zc.b[0] = GemmBlock{0, B, 0, 4 * H, net->e_obs, nx};
-            if (panel) {
-                const pp_addr& ad = net->addrs[only_addr];
-                PanelArgs pa{};
-                pa.B = R; pa.H = H; pa.hid = ad.hid; pa.n_out = ad.n_out; pa.K = ad.n_out / 3; pa.e = net->e_obs;
-                pa.ldx = (int)w.i4; pa.lda1 = (int)w.hid4; pa.lddy = (int)w.out4; pa.ldw = I;
-                pa.X = w.X; pa.Wih = P + net->w_ih; pa.AB = w.AB + (int64_t)only_addr * 2 * 4 * H;
-                pa.WihT = w.WihT; pa.W1T = w.W1T;
-                pa.xz = w.xz; pa.xd = w.xd; pa.epoch = w.epoch;
-                pa.W1 = P + ad.w1; pa.b1 = P + ad.b1; pa.W2 = P + ad.w2; pa.b2 = P + ad.b2;
-                pa.value = bt->value; pa.prior = bt->prior;
-                pa.Hs = w.Hl[0]; pa.G = w.Gl[0]; pa.A1 = w.A1; pa.DY = w.DY; pa.dZ1 = w.dZ1; pa.dX = w.dX;
-                pa.gsum = w.gsum + (int64_t)only_addr * 2 * 4 * H;
-                pa.lp_out = (flags & PP_LOSS_KEEP_LP) ? lp_out : nullptr;
-                pa.loss_acc = w.loss_acc; pa.flag = w.flag; pa.grad_scale = -1.0f / (float)B;
-                pa.dbg = g_timeline;
-                // training: the observe-embedding backward of the rows rides in the kernel's tail (one launch less)
-                PanelObs po{};
-                obs_tail = bwd && (panel16_go || panel_obs_tail_ok(net, H, ad.hid, ad.n_out, net->e_obs)) && obs_fused_args(net, w.obs_h, po.a);
-                if (obs_tail) {
-                    po.P = P; po.cat = w.cat; po.f1 = w.f1;
-                    po.dE = w.dE; po.dF1 = w.dF1; po.dCat = w.dCat; po.dHo0 = w.dObsH;
-                    po.dh_stride = (int64_t)B * w.maxohid4;
-                }
-                if (panel16_go) {
-                    Panel16Args p16{};
-                    p16.a = pa;
-                    for (int i = 0; i < 6; ++i) p16.img[i] = w.p16.img[i];
-                    PP_TRY(panel16(ad.kind, p16, st, obs_tail ? &po : nullptr));
-                } else {
-                    PP_TRY(panel_t1(ad.kind, pa, st, obs_tail ? &po : nullptr));
-                }
-                cell_done = true;
-                // executed data-path FLOPs of the launch: forward + backward products of the 8-row panels
-                prof_end(0, 2.0 * R * (2.0 * 3.0 * H * net->e_obs + 2.0 * (double)H * ad.hid + 2.0 * (double)ad.hid * ad.n_out), st);
-            } else {
-            if (lstm_input_fast_ok(g, x)) PP_TRY(lstm_input_fast(g, x, st));      // (lstm_input.hip; the zero block is zeros in X)
-            else PP_TRY(gemm_f32(&g, st, &zc, &x));
-            prof_end(0, 2.0 * R * (double)nx * 4.0 * H, st);
-            }
-        } else {
-        PP_TRY(linear_fwd(in, in_ld, nullptr, P + lw_ih(l), P + lb_ih(l), w.Gl[l], 4 * H, R, in_w, 4 * H, false, P + lb_hh(l), st,
-                          &zero));
-        if (l == 0) prof_end(0, 2.0 * R * (double)I * 4.0 * H, st);
-        }
-        for (int t = 0; t < T; ++t) {
-            if (tail_teams && t == tail_t0) {   // all remaining time steps of this layer: one launch (lstm_tail.hip)
-                PP_TRY(lstm_tail_fwd(w.Gl[l], w.Cl[l], w.Hl[l], P + lw_hh(l), bt->row_off_dev, tail_t0, T, H, tail_teams,
-                                     w.xch_f, w.xch_b, w.flag, st));
-                break;
-            }
-            const int n = bt->n_active[t], r0 = bt->row_off[t];
-            float* Gt = w.Gl[l] + (int64_t)r0 * 4 * H;
-            const float* c_prev = nullptr;
-            if (t > 0) {
-                const int rp = bt->row_off[t - 1];
-                pp_gemm_args g{};
-                g.A = w.Hl[l] + (int64_t)rp * H; g.lda = H;
-                g.B = P + lw_hh(l); g.ldb = H;
-                g.C = Gt; g.ldc = 4 * H;
-                g.M = n; g.N = 4 * H; g.K = H;
-                c_prev = w.Cl[l] + (int64_t)rp * H;
-                // Recurrent product with the cell in its epilogue (gate-interleaved tiles; one workgroup per tile walks all of
-                // K = H, the pre-activations are read instead of accumulated into): no lstm_cell_fwd launch, no round trip of
-                // G. Needs enough tiles to fill the chip without a K split: n >= 64 rows x 4H / 64 column tiles.
-                static const int fuse_rec = env_flag("PP_FUSE_CELL_REC", 1);
-                if (fuse_rec && compact_ok_dims && H % 16 == 0 && n >= 64) {
-                    GemmExt x{};
-                    x.cell_H = H; x.cell_rows = n; x.cell_c = w.Cl[l] + (int64_t)r0 * H; x.cell_h = w.Hl[l] + (int64_t)r0 * H;
-                    x.cell_cprev = c_prev;
-                    PP_TRY(gemm_f32(&g, st, nullptr, &x));
-                    continue;
-                }
-                g.accumulate = 1;
-                g.split_k = 1;   // few rows late in a ragged batch: spread K over workgroups (accumulation into G)
-                PP_TRY(gemm_f32(&g, st));
-            }
-            if (t == 0 && cell_done) continue;
-            PP_TRY(lstm_cell_fwd(Gt, c_prev, w.Cl[l] + (int64_t)r0 * H, w.Hl[l] + (int64_t)r0 * H, n, H, st));
-        }
-    }
-    const float gscale = -1.0f / (float)B;
-    std::vector<ColsumJob> cs;
-    // deterministic mode: the heads write the per-row log_prob only; the loss is a fixed-order sum over the rows
-    const bool det = deterministic_mode();
-    float* const lp_rows = det ? (((flags & PP_LOSS_KEEP_LP) && lp_out) ? lp_out : w.lp_rows)
-                               : ((flags & PP_LOSS_KEEP_LP) ? lp_out : nullptr);
-    float* const loss_slots = det ? nullptr : w.loss_acc;
-    // heads: first FF layer of EVERY address group in one grouped launch (rows gathered by address: the dispatch
-    // gather), then the fused tails, grouped by (kind, shape)
-    {
-        std::vector<pp_gemm_args> hq;
-        for (int a = 0; a < net->n_addr; ++a) {
-            const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
-            if (n <= 0) continue;
-            const pp_addr& ad = net->addrs[a];
-            pp_gemm_args g{};
-            g.A = heads_in; g.lda = heads_ld; g.a_idx = bt->grp_rows + g0;
-            g.B = P + ad.w1; g.ldb = H;
-            g.C = w.A1 + (int64_t)g0 * w.hid4; g.ldc = w.hid4;
-            g.M = n; g.N = ad.hid; g.K = H;
-            g.bias = P + ad.b1; g.relu = 1;
-            hq.push_back(g);
-        }
-        if (!panel) PP_TRY(gemm_f32_grouped(hq.data(), (int)hq.size(), st));
-    }
-    std::vector<char> done(net->n_addr, 0);
-    for (int a = 0; a < net->n_addr; ++a) {
-        const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
-        if (n <= 0 || done[a]) continue;
-        const pp_addr& ad = net->addrs[a];
-        if (head_tail_supported(ad.kind, ad.hid, ad.n_out)) {
-            // fused tail (layer 2 + log_prob + loss [+ dy, dz1]) for this and every later group of the same head shape
-            std::vector<TailJob> tj;
-            for (int b = a; b < net->n_addr; ++b) {
-                const pp_addr& bd = net->addrs[b];
-                const int h0 = bt->grp_off[b], m = bt->grp_off[b + 1] - h0;
-                if (m <= 0 || done[b] || bd.kind != ad.kind || bd.hid != ad.hid || bd.n_out != ad.n_out) continue;
-                done[b] = 1;
-                tj.push_back(TailJob{w.A1 + (int64_t)h0 * w.hid4, P + bd.w2, P + bd.b2, bt->grp_rows + h0,
-                                     bwd ? w.DY + (int64_t)h0 * w.out4 : nullptr, w.dZ1 + (int64_t)h0 * w.hid4, m});
-                if (bwd) {   // bias gradients by the low-contention column-sum kernel (multi-job launches below)
-                    cs.push_back(ColsumJob{w.DY + (int64_t)h0 * w.out4, w.out4, nullptr, m, bd.n_out, grads + bd.b2, nullptr});
-                    cs.push_back(ColsumJob{w.dZ1 + (int64_t)h0 * w.hid4, w.hid4, nullptr, m, bd.hid, grads + bd.b1, nullptr});
-                }
-            }
-            if (!panel)
-                PP_TRY(head_tail_multi(ad.kind, tj.data(), (int)tj.size(), w.hid4, ad.hid, ad.n_out, bt->value, bt->prior, gscale,
-                                       lp_rows, w.out4, w.hid4, loss_slots, w.flag, st));
-            continue;
-        }
-        done[a] = 1;
-        float* A1 = w.A1 + (int64_t)g0 * w.hid4;
-        float* Y = w.Y + (int64_t)g0 * w.out4;
-        PP_TRY(linear_fwd(A1, w.hid4, nullptr, P + ad.w2, P + ad.b2, Y, w.out4, n, ad.hid, ad.n_out, false, nullptr, st));
-        PP_TRY(head_logprob(ad.kind, Y, w.out4, bt->grp_rows + g0, bt->value, bt->prior, n, ad.n_out, gscale,
-                            lp_rows, bwd ? w.DY + (int64_t)g0 * w.out4 : nullptr, loss_slots, w.flag, st));
-    }
-    if (det) PP_TRY(loss_from_rows(lp_rows, R, B, w.flag, loss_out, status_out, st));
+    PP_TRY(lstm_forward(s));
+    PP_TRY(heads_forward(s, q));
+    if (p.det) PP_TRY(loss_from_rows(p.lp_rows, p.R, p.B, w.flag, loss_out, status_out, st));
     if (!bwd) {
-        if (!det) PP_TRY(loss_finalize(w.loss_acc, w.flag, B, loss_out, status_out, st));
+        if (!p.det) PP_TRY(loss_finalize(w.loss_acc, w.flag, p.B, loss_out, status_out, st));
         return 0;
     }
-    // (deterministic mode: the loss is final; the kernels below get no loss slots to fold)
-    const float* const fin_acc = det ? nullptr : w.loss_acc;
-    // (with a backward pass the loss slots are folded by the first LSTM-cell launch below)
-    // (the bias / table column sums queued in `cs` are launched once, at the end of the backward pass)
-
-    // ---------------- backward ----------------
-    // Weight-gradient leaves: queued and flushed as ONE grouped launch at the end of the backward pass.
-    // (a second stream for these leaves with fork / join events was measured twice and lost both times - 0.157 -> 0.166 ms
-    // on config 2, 183 vs 170 us with two grouped launches: a cross-queue event wait costs ~5 us - and is gone)
-    std::vector<pp_gemm_args> wq;
-    std::vector<GemmHole> wholes;
-    auto flush_wgrads = [&](hipStream_t stream, bool timed, const AuxJobs* aux = nullptr) -> int {
-        wholes.resize(wq.size(), GemmHole{});
-        // data parallel with an overlap range (dp.hip): the products that complete the range - the LSTM layer's weight
-        // gradients - and the reduction jobs go first; the range's all-reduce starts on the side stream behind them and the
-        // remaining products (proposal layers, observe embedding) run under it
-        int64_t lo = 0, hi = 0;
-        if (dp_overlap_hull(&lo, &hi) && wq.size() > 1) {
-            std::vector<pp_gemm_args> qa, qb;
-            std::vector<GemmHole> ha, hb;
-            for (size_t i = 0; i < wq.size(); ++i) {
-                const bool in = wq[i].C >= grads + lo && wq[i].C < grads + hi;
-                (in ? qa : qb).push_back(wq[i]);
-                (in ? ha : hb).push_back(wholes[i]);
-            }
-            if (!qa.empty() && !qb.empty()) {
-                PP_TRY(launch_wgrads(qa, stream, &ha, timed, aux, true));
-                PP_TRY(dp_bucket0_issue(grads, stream));
-                PP_TRY(launch_wgrads(qb, stream, &hb, false, nullptr, true));
-                wq.clear();
-                wholes.clear();
-                return 0;
-            }
-        }
-        PP_TRY(launch_wgrads(wq, stream, &wholes, timed, aux, true));
-        wq.clear();
-        wholes.clear();
-        return 0;
-    };
-    // Single-statement batch, one LSTM layer: every row is a trace's only time step, so the cell backward needs nothing
-    // but dh from the heads - it runs in the epilogue of the dH product (gemm_tile_direct), which also adds each tile's
-    // column sums of dG to its address's group sums; the loss is finalised by the jobs behind the weight-gradient tiles.
-    static const int fuse_cell_bwd = env_flag("PP_FUSE_CELL_BWD", 1);
-    const bool fused_bwd = compact && T == 1 && L == 1 && fuse_cell_bwd;
-    int dx_splits = 1;
-    std::vector<pp_gemm_args> dq;   // per-address data gradients into dH
-    for (int a = 0; a < net->n_addr; ++a) {
-        const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
-        if (n <= 0) continue;
-        const pp_addr& ad = net->addrs[a];
-        const float* A1 = w.A1 + (int64_t)g0 * w.hid4;
-        const float* DY = w.DY + (int64_t)g0 * w.out4;
-        float* dZ1 = w.dZ1 + (int64_t)g0 * w.hid4;
-        const bool fused = head_tail_supported(ad.kind, ad.hid, ad.n_out);   // dz1 already produced by the forward tail
-        queue_wgrad(wq, DY, w.out4, A1, w.hid4, nullptr, grads + ad.w2, n, ad.hid, ad.n_out);
-        if (!fused) {
-            PP_TRY(colsum_f32(DY, w.out4, nullptr, n, ad.n_out, grads + ad.b2, nullptr, st));
-            PP_TRY(linear_dgrad(DY, w.out4, P + ad.w2, dZ1, w.hid4, nullptr, A1, w.hid4, n, ad.hid, ad.n_out, false, st,
-                                det ? nullptr : grads + ad.b1));   // db1 = colsum(dZ1) fused into the epilogue
-            if (det) cs.push_back(ColsumJob{dZ1, w.hid4, nullptr, n, ad.hid, grads + ad.b1, nullptr});
-        }
-        // (panel kernel: one group that covers all rows in order - no gather, the product can take the streaming kernel)
-        queue_wgrad(wq, dZ1, w.hid4, heads_in, heads_ld, panel ? nullptr : bt->grp_rows + g0, grads + ad.w1, n, H, ad.hid);
-        {   // dH[rows of this address] = dZ1 W1: queued, every address group in one grouped launch
-            pp_gemm_args g{};
-            g.A = dZ1; g.lda = w.hid4;
-            g.B = P + ad.w1; g.ldb = H; g.b_kmajor = 1;
-            g.C = w.dH; g.ldc = H; g.c_idx = bt->grp_rows + g0;
-            g.M = n; g.N = H; g.K = ad.hid;
-            if (fused_bwd) g.colsum = w.gsum + (int64_t)a * 2 * 4 * H;   // group sums of dG (current-address slot)
-            dq.push_back(g);
-        }
-    }
-    if (panel) {
-        // (dG, the group sums and dX came out of the panel launch)
-    } else if (fused_bwd) {
-        GemmExt x{};
-        x.bw_G = w.Gl[0]; x.bw_C = w.Cl[0]; x.bw_H = H; x.lean = lean_cell ? 1 : 0;
-        PP_TRY(gemm_f32_grouped(dq.data(), (int)dq.size(), st, nullptr, &x));
-    } else {
-        PP_TRY(gemm_f32_grouped(dq.data(), (int)dq.size(), st));
-    }
-    // the gradient of the observe embedding is summed over the time steps from dX[:, :e_obs] (LSTM) / from dH (FF)
-    const float* dXs = ff ? w.dH : w.dX;
-    const int64_t ldxs = ff ? H : w.i4;
-    const int cz0 = net->e_obs, cz1 = net->e_obs + net->smp_dim + net->dtype_dim + net->addr_dim;   // previous-variable columns
-    float* dH_cur = w.dH;          // gradient into the hidden states of the layer being processed (top: from the heads)
-    float* dH_other = w.dH2;
-    for (int l = L - 1; l >= 0; --l) {
-        int dh_parts = 0;   // K splits of dG_{t+1} W_hh waiting in w.dHp for the cell backward of step t
-        for (int t = T - 1; t >= 0; --t) {
-            if (fused_bwd) break;   // dG is already in place
-            if (tail_teams && t >= tail_t0) {   // steps T-1 .. tail_t0 in one launch; it leaves dh / dc of step tail_t0 - 1
-                const LossFinalize fin{l == L - 1 ? fin_acc : nullptr, w.flag, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, status_out};
-                PP_TRY(lstm_tail_bwd(w.Gl[l], w.Cl[l], dH_cur, w.dC, P + lw_hh(l), bt->row_off_dev, tail_t0, T, H, tail_teams,
-                                     w.xch_f, w.xch_b, w.flag, det ? nullptr : grads + lb_ih(l), det ? nullptr : grads + lb_hh(l),
-                                     fin, st));
-                t = tail_t0;
-                continue;
-            }
-            const int n = bt->n_active[t], r0 = bt->row_off[t];
-            const int n_next = (t + 1 < T) ? bt->n_active[t + 1] : 0;
-            float* Gt = w.Gl[l] + (int64_t)r0 * 4 * H;
-            const float* c_prev = t > 0 ? w.Cl[l] + (int64_t)bt->row_off[t - 1] * H : nullptr;
-            // the backward pass's first cell launch folds the loss slots (the tail launch when there is one)
-            const bool fin = l == L - 1 && t == T - 1;
-            PP_TRY(lstm_cell_bwd(Gt, c_prev, w.Cl[l] + (int64_t)r0 * H, dH_cur + (int64_t)r0 * H, w.dC, n, n_next, H,
-                                 det ? nullptr : grads + lb_ih(l), det ? nullptr : grads + lb_hh(l), st,
-                                 fin ? fin_acc : nullptr, w.flag, B, loss_out, status_out, w.dHp, dh_parts,
-                                 (int64_t)B * H));   // bias gradients fused; + the stored partials of dG_{t+1} W_hh
-            dh_parts = 0;
-            if (t > 0) {  // dh_{t-1} += dG_t W_hh
-                // As K-split partial tiles that the NEXT cell-backward launch adds (rows [0, n) of step t - 1 are the same
-                // traces): no float atomics (6 us per 64 x 64 tile), no read-modify-write of dH
-                static const int dh_partials_env = env_flag("PP_DH_PARTIALS", 1);
-                const int tiles = cdiv(n, 64) * cdiv(H, 64), nslab = 4 * H / 32;
-                const int splits = std::max(1, std::min({DH_SPLITS, cdiv(256, tiles), nslab / 2}));
-                if (dh_partials_env && !det && splits > 1 && H % 4 == 0) {
-                    pp_gemm_args g{};
-                    g.A = Gt; g.lda = 4 * H;
-                    g.B = P + lw_hh(l); g.ldb = H; g.b_kmajor = 1;
-                    g.C = w.dHp; g.ldc = H;
-                    g.M = n; g.N = H; g.K = 4 * H;
-                    GemmExt x{};
-                    x.split_stride = (int64_t)B * H;
-                    x.force_splits = splits;
-                    PP_TRY(gemm_f32(&g, st, nullptr, &x));
-                    dh_parts = splits;
-                } else {
-                    PP_TRY(linear_dgrad(Gt, 4 * H, P + lw_hh(l), dH_cur + (int64_t)bt->row_off[t - 1] * H, H, nullptr, nullptr, 0,
-                                        n, H, 4 * H, true, st));
-                }
-            }
-        }
-        if (det)   // bias gradients = column sums of the complete dG of this layer, by the single-writer kernel
-            cs.push_back(ColsumJob{w.Gl[l], 4 * H, nullptr, R, 4 * H, grads + lb_ih(l), grads + lb_hh(l)});
-        // parameter gradients of this layer (leaves, grouped with every head's weight gradients). First-time-step rows give
-        // nothing to the forget-gate rows (dG[:, H:2H] = 0 where c_{t-1} = 0) and, in layer 0, nothing to the
-        // previous-variable columns of dW_ih (their inputs are zero there)
-        const float* in = l == 0 ? w.X : w.Hl[l - 1];
-        const int64_t in_ld = l == 0 ? w.i4 : H;
-        const int in_w = l == 0 ? I : H;
-        GemmHole wh{};
-        if (l == 0 && compact) {   // dW_ih[:, :c2] = dG^T [E | s_prev]; the table columns follow from the group sums (aux jobs)
-            wh.b[1] = GemmBlock{H, 2 * H, 0, nx, 0, B};
-            wh.b[0] = GemmBlock{0, 4 * H, cz0, nx, 0, B};
-            queue_wgrad(wq, w.Gl[0], 4 * H, w.X, w.i4, nullptr, grads + net->w_ih, R, nx, 4 * H, &wholes, wh);
-            wq.back().ldc = I;
-        } else {
-        wh.b[1] = GemmBlock{H, 2 * H, 0, in_w, 0, B};
-        if (l == 0) wh.b[0] = GemmBlock{0, 4 * H, cz0, cz1, 0, B};
-        queue_wgrad(wq, w.Gl[l], 4 * H, in, in_ld, nullptr, grads + lw_ih(l), R, in_w, 4 * H, &wholes, wh);
-        }
-        if (T > 1) {
-            const int r1 = bt->row_off[1];
-            queue_wgrad(wq, w.Gl[l] + (int64_t)r1 * 4 * H, 4 * H, w.Hl[l], H, bt->prev_row + r1, grads + lw_hh(l), R - r1, H,
-                        4 * H);
-        }
-        if (l > 0) {   // gradient into the hidden states of the layer below: dH_{l-1} = dG_l W_ih_l (the forget-gate part of
-            GemmHole dh{};                                         // the sum is zero for first-time-step rows)
-            dh.b[0] = GemmBlock{0, B, 0, H, H, 2 * H};
-            PP_TRY(linear_dgrad(w.Gl[l], 4 * H, P + lw_ih(l), dH_other, H, nullptr, nullptr, 0, R, H, 4 * H, false, st, nullptr,
-                                &dh));
-            std::swap(dH_cur, dH_other);
-        }
-    }
-    // LSTM parameter gradients are queued; layer 0's data gradient follows
-    if (!ff) {
-    // (wq is flushed at the very end, together with the observe-embedding weight gradients)
-    // dX = dG W_ih, then scatter into the embedding tables / sample embeddings / observe embedding. Nobody reads the
-    // previous-variable columns of first-time-step rows (no previous variable, no parameter behind them).
-    // The forget-gate part of the summation over the gates is zero for those rows.
-    if (compact) {
-        // dX[:, :c2] = dG W_ih[:, :c2] (observe-embedding and sample-embedding columns; the table columns need no per-row
-        // gradient: their parameter gradients follow from the column sums of dG per address group)
-        const GemmHole dx_unused{{{0, B, cz0, nx, 0, 4 * H}, {0, B, 0, nx, H, 2 * H}}};
-        pp_gemm_args g{};
-        g.A = w.G; g.lda = 4 * H;
-        g.B = P + net->w_ih; g.ldb = I; g.b_kmajor = 1;
-        g.C = w.dX; g.ldc = w.i4;
-        g.M = R; g.N = nx; g.K = 4 * H;
-        if (panel) {
-            dx_splits = 1;      // complete rows, written by the panel launch
-        } else if (dx_partials) {
-            // ~3 slabs per split (the K loop is short either way; more splits = more workgroups streaming dG)
-            const int nslab = 4 * H / 32;
-            dx_splits = std::max(1, std::min(DX_SPLITS, nslab / 4));
-            GemmExt x{};
-            x.split_stride = (int64_t)R * w.i4;
-            x.force_splits = dx_splits;
-            PP_TRY(gemm_f32(&g, st, &dx_unused, &x));
-        } else {
-        g.accumulate = 1;   // dX was cleared by the gather kernel
-        g.split_k = 1;
-        PP_TRY(gemm_f32(&g, st, &dx_unused));
-        }
-        if (!fused_bwd) {   // group sums of dG by current / previous address (the fused dH epilogue produced the former)
-            for (int a = 0; a < net->n_addr; ++a) {
-                const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
-                if (n > 0) cs.push_back(ColsumJob{w.G, 4 * H, bt->grp_rows + g0, n, 4 * H, w.gsum + (int64_t)a * 2 * 4 * H, nullptr});
-                const int q0 = bt->nxt_off[a], m = bt->nxt_off[a + 1] - q0;
-                if (m > 0) cs.push_back(ColsumJob{w.G, 4 * H, bt->nxt_rows + q0, m, 4 * H, w.gsum + ((int64_t)a * 2 + 1) * 4 * H, nullptr});
-            }
-        }
-    } else {
-    const GemmHole dx_unused{{{0, B, cz0, cz1, 0, 4 * H}, {0, B, 0, I, H, 2 * H}}};
-    PP_TRY(linear_dgrad(w.G, 4 * H, P + net->w_ih, w.dX, w.i4, nullptr, nullptr, 0, R, I, 4 * H, true, st, nullptr,
-                        &dx_unused));   // dX was cleared by the gather kernel
-    }
-    const int c1 = net->e_obs, c2 = c1 + net->smp_dim, c3 = c2 + net->dtype_dim, c4 = c3 + net->addr_dim,
-              c5 = c4 + net->dtype_dim;
-    for (int a = 0; a < net->n_addr && !compact; ++a) {
-        const pp_addr& ad = net->addrs[a];
-        const int g0 = bt->grp_off[a], n = bt->grp_off[a + 1] - g0;
-        if (n > 0) {  // rows where `a` is the current address
-            cs.push_back(ColsumJob{w.dX + c4, w.i4, bt->grp_rows + g0, n, net->dtype_dim, grads + ad.dtype_emb, nullptr});
-            cs.push_back(ColsumJob{w.dX + c5, w.i4, bt->grp_rows + g0, n, net->addr_dim, grads + ad.addr_emb, nullptr});
-        }
-        const int q0 = bt->nxt_off[a], m = bt->nxt_off[a + 1] - q0;
-        if (m > 0) {  // rows whose previous variable has address `a`
-            cs.push_back(ColsumJob{w.dX + c2, w.i4, bt->nxt_rows + q0, m, net->dtype_dim, grads + ad.dtype_emb, nullptr});
-            cs.push_back(ColsumJob{w.dX + c3, w.i4, bt->nxt_rows + q0, m, net->addr_dim, grads + ad.addr_emb, nullptr});
-        }
-    }
-    if (T > 1 && det)
-        PP_TRY(sample_embed_bwd_det(net, P, bt->value, bt->prev_row, bt->nxt_rows, bt->nxt_off, w.dX, w.i4, grads, st));
-    else if (T > 1)
-        PP_TRY(sample_embed_bwd(net, P, bt->value, bt->addr, bt->prev_row, bt->row_off[1], R, w.dX, w.i4, grads, st));
-    }   // !ff
-    // Column sums + weight-gradient leaves. Compact rows: the jobs that turn the group sums of dG into the table-column
-    // gradients (and, after the fused cell backward, the LSTM bias gradients and the loss) ride behind the tiles of the
-    // grouped weight-gradient launch; for a single-statement batch so do the column sums themselves (nothing in the
-    // launch depends on anything else in it), which removes the separate column-sum launch.
-    auto reduce_and_flush = [&]() -> int {
-        if (!compact && ff && !det) {
-            // FeedForward network: no column sum depends on another launch's group sums, so they all ride behind the
-            // weight-gradient tiles (and the loss is finalised there): one launch less per step
-            static const int ff_ride = env_flag("PP_AUX_COLSUM", 1);
-            int n_live = 0;
-            for (const auto& j : cs) n_live += (j.n_rows > 0 && j.n_cols > 0) ? 1 : 0;
-            if (ff_ride && n_live <= AUX_MAX_COLSUM && !wq.empty()) {
-                AuxJobs aux{};
-                for (const auto& j : cs)
-                    if (j.n_rows > 0 && j.n_cols > 0) aux.cs[aux.n_colsum++] = j;
-                aux.fin = LossFinalize{fin_acc, w.flag, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, status_out};
-                aux_layout(aux, false);
-                return flush_wgrads(st, true, &aux);
-            }
-        }
-        if (!compact) {
-            if (ff)   // (LSTM: the first cell launch of the backward pass finalises the loss)
-                PP_TRY(colsum_multi(cs.data(), (int)cs.size(), st, fin_acc, w.flag, B, loss_out, status_out));
-            else
-                PP_TRY(colsum_multi(cs.data(), (int)cs.size(), st));
-            return flush_wgrads(st, true);
-        }
-        AuxJobs aux{};
-        static const int cs_ride_env = env_flag("PP_AUX_COLSUM", 1);
-        int n_live = 0;
-        for (const auto& j : cs) n_live += (j.n_rows > 0 && j.n_cols > 0) ? 1 : 0;
-        if (fused_bwd && cs_ride_env && n_live <= AUX_MAX_COLSUM) {
-            for (const auto& j : cs)
-                if (j.n_rows > 0 && j.n_cols > 0) aux.cs[aux.n_colsum++] = j;
-        } else {
-            PP_TRY(colsum_multi(cs.data(), (int)cs.size(), st));
-        }
-        aux.gsum = w.gsum; aux.W = P + net->w_ih; aux.dW = grads + net->w_ih; aux.ldw = I;
-        aux.params = P; aux.grads = grads; aux.at = net->addr_table;
-        aux.N = 4 * H; aux.c2 = c2x; aux.c4 = c2x + ne_x; aux.nd = net->dtype_dim; aux.ne = ne_x; aux.n_addr = net->n_addr;
-        for (int q = 0; q < 32; ++q) aux.present[q] = abias.present[q];
-        aux.all_present = 0;
-        if (fused_bwd) {
-            aux.db_ih = grads + net->b_ih; aux.db_hh = grads + net->b_hh;
-            aux.fin = LossFinalize{fin_acc, w.flag, B > 0 ? 1.0f / (float)B : 0.0f, loss_out, status_out};
-        }
-        aux_layout(aux, true);
-        return flush_wgrads(st, true, &aux);
-    };
-    // observe embedding backward
-    if (obs_fused_supported(net)) {
-        // dE (sum over the trace's time steps of dX, masked by the last ReLU) and the data gradients of the whole stack
-        // in one fused launch; weight gradients join the grouped MFMA launch; bias gradients are column sums of the same
-        // buffers
-        const int64_t dhs = (int64_t)B * w.maxohid4;
-        if (!obs_tail)      // (single-statement batches on the panel kernel: done in its tail)
-            PP_TRY(obs_embed_dgrad_fused(net, P, B, w.obs_h, w.cat, w.f1, dXs, ldxs, bt->row_off_dev, T, w.E, w.dE, w.dF1, w.dCat,
-                                         w.dObsH, dhs, st, dx_splits, (int64_t)R * w.i4));
-        const int e = net->e_obs;
-        queue_wgrad(wq, w.dE, w.e4, w.f1, w.e4, nullptr, grads + net->fin_w1, B, e, e);
-        queue_wgrad(wq, w.dF1, w.e4, w.cat, w.e4, nullptr, grads + net->fin_w0, B, e, e);
-        cs.push_back(ColsumJob{w.dE, w.e4, nullptr, B, e, grads + net->fin_b1, nullptr});
-        cs.push_back(ColsumJob{w.dF1, w.e4, nullptr, B, e, grads + net->fin_b0, nullptr});
-        int ci = 0, co = 0;
-        for (int o = 0; o < net->n_obs; ++o) {
-            const int in = net->obs_in[o], hid = net->obs_hid[o], out = net->obs_out[o];
-            float* dHo = w.dObsH + (int64_t)o * dhs;
-            queue_wgrad(wq, w.dCat + co, w.e4, w.obs_h[o], w.ohid4[o], nullptr, grads + net->obs_w1[o], B, hid, out);
-            // dW0[:, k] = sum_b dh[b, :] obs[b, k]: a handful of input columns -> weighted column sums, not a GEMM
-            for (int k = 0; k < in; ++k)
-                cs.push_back(ColsumJob{dHo, w.ohid4[o], nullptr, B, hid, grads + net->obs_w0[o] + k, nullptr,
-                                       bt->obs + ci + k, bt->obs_width, in});
-            cs.push_back(ColsumJob{w.dCat + co, w.e4, nullptr, B, out, grads + net->obs_b1[o], nullptr});
-            cs.push_back(ColsumJob{dHo, w.ohid4[o], nullptr, B, hid, grads + net->obs_b0[o], nullptr});
-            ci += in;
-            co += out;
-        }
-        return reduce_and_flush();
-    }
-    PP_TRY(obs_grad(dXs, ldxs, bt->row_off_dev, T, B, net->e_obs, w.E, w.e4, w.dE, w.e4, st));   // dE, ReLU mask applied
-    PP_TRY(reduce_and_flush());
-    const int e = net->e_obs;
-    PP_TRY(linear_wgrad(w.dE, w.e4, w.f1, w.e4, nullptr, grads + net->fin_w1, grads + net->fin_b1, nullptr, B, e, e, st));
-    PP_TRY(linear_dgrad(w.dE, w.e4, P + net->fin_w1, w.dF1, w.e4, nullptr, w.f1, w.e4, B, e, e, false, st,
-                        det ? nullptr : grads + net->fin_b0));
-    if (det) PP_TRY(colsum_f32(w.dF1, w.e4, nullptr, B, e, grads + net->fin_b0, nullptr, st));
-    PP_TRY(linear_wgrad(w.dF1, w.e4, w.cat, w.e4, nullptr, grads + net->fin_w0, nullptr, nullptr, B, e, e, st));
-    PP_TRY(linear_dgrad(w.dF1, w.e4, P + net->fin_w0, w.dCat, w.e4, nullptr, w.cat, w.e4, B, e, e, false, st));
-    int ci = 0, co = 0;
-    for (int o = 0; o < net->n_obs; ++o) {
-        // backward through EmbeddingFeedForward(num_layers = depth): dz of layer l (ReLU mask already applied) gives
-        // dW_l = dz^T x_l, db_l = colsum dz, and dz of layer l - 1 = (dz W_l) * [x_l > 0]
-        const int depth = net->obs_depth[o] ? net->obs_depth[o] : 2;
-        const float* dz = w.dCat + co;
-        int64_t lddz = w.e4;
-        float* scratch[2] = {w.dObsH, w.dObsH2};
-        for (int l = depth - 1; l >= 0; --l) {
-            const bool cnn = net->obs_kind[o] == PP_OBS_CNN2D5C;      // layer 0 (_lin1) reads the convolution stack's features
-            const int out = l == depth - 1 ? net->obs_out[o] : net->obs_hid[o];
-            const int in = l == 0 ? (cnn ? net->obs_feat[o] : net->obs_in[o]) : net->obs_hid[o];
-            const float* x = l == 0 ? (cnn ? w.cnn_feat[o] : bt->obs + ci) : w.obs_hl[o][l - 1];
-            const int64_t ldx = l == 0 ? (cnn ? w.f4[o] : bt->obs_width) : w.ohid4[o];
-            const int64_t wl = net->obs_depth[o] ? net->obs_w[o][l] : (l == 0 ? net->obs_w0[o] : net->obs_w1[o]);
-            const int64_t bl = net->obs_depth[o] ? net->obs_b[o][l] : (l == 0 ? net->obs_b0[o] : net->obs_b1[o]);
-            PP_TRY(linear_wgrad(dz, lddz, x, ldx, nullptr, grads + wl, grads + bl, nullptr, B, in, out, st));
-            if (l > 0) {
-                float* dprev = scratch[l & 1];
-                PP_TRY(linear_dgrad(dz, lddz, P + wl, dprev, w.ohid4[o], nullptr, x, ldx, B, in, out, false, st));
-                dz = dprev;
-                lddz = w.ohid4[o];
-            } else if (cnn) {
-                // the image is data, its features are not: dFeatures = dz W_lin1 (no mask here: the pool backward applies
-                // conv5's), then back through the stack
-                PP_TRY(linear_dgrad(dz, lddz, P + wl, w.cnn_dfeat[o], w.f4[o], nullptr, nullptr, 0, B, in, out, false, st));
-                PP_TRY(cnn_backward(net, o, w.cnn_dfeat[o], w.f4[o], B, grads, w.cnn_ws[o], w.cnn_ws_bytes[o], st));
-            }
-        }
-        ci += net->obs_in[o];
-        co += net->obs_out[o];
-    }
-    return 0;
+    // (with a backward pass the loss slots are folded by the first LSTM-cell launch, or behind the weight-gradient tiles)
+    PP_TRY(heads_backward(s, q));
+    PP_TRY(lstm_backward(s, q));
+    if (!p.ff) PP_TRY(input_backward(s, q));
+    if (!p.fused_obs) return obs_backward_generic(s, q);
+    PP_TRY(obs_dgrad_fused(s));
+    queue_obs_grads_fused(s, q);
+    return reduce_and_flush(s, q);
 }
 
 }  // namespace pp
