@@ -644,6 +644,39 @@ int pp_mix_logweight(const pp_mixture* mix, const float* x, int32_t x_stride, fl
 int pp_mix_draw(const pp_mixture* mix, const int64_t* rows, int32_t m, int32_t n, uint64_t seed, uint64_t offset,
                 uint32_t stream_id, float* out /*dev [n]*/, void* stream);
 
+/* The likelihood of a VECTOR-valued observe of a lock-step run (state.observe, pyprob/state.py:118-155; trace.py:123-125 sums an
+ * observed variable's log_prob over its elements): the k-wide form of pp_dist_logweight, one row of k values per particle.
+ *     lp[r] = sum_{e<k} log p_kind( x[r,e] | params[0..3][r,e] ),   operand[r,e] = p[r * row_stride + e * elem_stride]
+ *     lw[r] += scale * lp[r],  lp_out[r] = lp[r]     for r = rows[j], j < m, or rows NULL: r < n (m, n, rows as pp_dist_logweight)
+ * Kinds: the scalar families 0, 1, 3, 4, 6-13 of the table above (Factor and Categorical are refused); params[q] is read for the
+ * parameters the kind has, the rest is ignored. Strides are element counts >= 0, as in pp_obs_draw: (row, elem) = (0, 0) a scalar,
+ * (0, 1) one row shared by all particles (the observed image), (1, 0) one value per particle, (k, 1) a full [n, k] block; a row
+ * stride above k is a padded view. Nothing is materialised to [n, k]. Rows that are not listed are not touched. lw or lp_out may
+ * be NULL (not both).
+ * Contracts:
+ *  - ONE FORMULA. An element's log-density is scalar_log_prob_at (csrc/dist_math.hpp), the definition pp_dist_logweight and
+ *    pp_mix_logweight evaluate, with its support guards: one element outside the support makes the row -inf, a NaN where that
+ *    definition gives NaN (a NaN mean, stddev, rate ...) makes the row NaN. k = 1 is bit-identical to pp_dist_logweight with that
+ *    single term, for lw (the product scale * lp is rounded, then added) and for lp_out.
+ *  - FIXED SUMMATION ORDER. A row's sum is a function of k and the row's values only - not of n, m, rows, the grid, the stride
+ *    form that delivered the values or the alignment of a pointer. A row has 256 slots, element e belongs to slot e & 255.
+ *    A slot starts at -0 (so an empty slot changes no bit) and adds its elements' log-densities in ascending e. Then
+ *    t[l] = (slot[4l] + slot[4l+1]) + (slot[4l+2] + slot[4l+3]) for l < 64, and the 64 values t are combined by a butterfly:
+ *    in stage d = 1, 2, 4, 8, 16, 32 every t[l] becomes t[l] + t[l ^ d]. An element passes through at most ceil(k / 256) + 8
+ *    additions. The lanes that work on a row are the smallest power of two >= ceil(k / 4), at most 64 (one wave per row;
+ *    several rows per wave for k <= 128) - a function of k alone; the 16-byte and the 4-byte load path add in this same
+ *    order. No float atomics: results are bit-identical from run to run.
+ *  - ADDRESSING. All offsets are 64-bit (r * row_stride and n * k may pass 2^31); any 4-byte aligned operand is accepted.
+ *    16-byte loads are used when k >= 4, p1..p3 are constant along a row (elem_stride 0) and params[0] and x are each constant
+ *    along a row or a run (elem_stride 1) with a 16-byte aligned base and a row stride that is a multiple of 4; anything else
+ *    is read with 4-byte loads. Both fill the same registers for one copy of the arithmetic.
+ * Returns nonzero without a launch (pp_last_error names pp_obs_logweight) for a kind outside the list, k < 1, n < 0, m < 0,
+ * m > n, m != n without rows, a NULL pointer or a negative stride of an operand the kind needs or of x, lw and lp_out both NULL.
+ * m == 0 returns 0 without a launch. */
+typedef struct pp_obs_operand { const float* p; int64_t row_stride; int32_t elem_stride; int32_t _pad; } pp_obs_operand;
+int pp_obs_logweight(int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t k, float scale, float* lw /*dev [n]*/,
+                     float* lp_out, const int64_t* rows, int32_t m, int32_t n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Individual kernels (used by the whole-path entry points; exported for unit parity tests and profiling)
  * ---------------------------------------------------------------------------------------------------- */

@@ -21,7 +21,11 @@ __device__ __forceinline__ float xlogyf(float a, float x) { return (a == 0.0f &&
 // ---- log-densities (kinds 6-13; the formulas of kinds 0-5 are is_draw.hpp's, shared with is_kernels.hip's term_log_prob) ------
 
 // 6 Exponential(rate): log(rate) - rate x, support [0, inf)
-__device__ __forceinline__ float lp_exponential(float rate, float x) { return x >= 0.0f ? logf(rate) - rate * x : -INFINITY; }
+// (the fused multiply-add is written out: it is what the compiler's contraction gives where one lane scores one value, and a
+// kernel that scores several values per lane - pp_obs_logweight, whose products the compiler packs in pairs - must not differ)
+__device__ __forceinline__ float lp_exponential(float rate, float x) {
+    return x >= 0.0f ? fmaf(-rate, x, logf(rate)) : -INFINITY;
+}
 
 // 7 Gamma(concentration a, rate b): xlogy(a, b) + xlogy(a - 1, x) - b x - lgamma(a), support [0, inf)
 __device__ __forceinline__ float lp_gamma(float a, float b, float x) {
@@ -92,24 +96,35 @@ __device__ __forceinline__ float lp_truncnormal(float mu, float sd, float low, f
     return -(z * z) / 2.0f - kHalfLog2Pi - logf(sd * Z);
 }
 
-// log p(x) of a scalar family (kinds 0, 1, 3, 4, 6-13) at particle r: parameter q is p[q][r * s[q]]. `kind` comes from a kernel
-// argument block, so every lane of a wave takes the same branch; shared by dist_logweight_kernel and mix_logweight_kernel.
-__device__ __forceinline__ float scalar_log_prob(int kind, const float* const* p, const int* s, int64_t r, float x) {
-    const float a = p[0][r * s[0]];
+// log p(x) of a scalar family (kinds 0, 1, 3, 4, 6-13) from the parameter VALUES a..d = p0..p3 (the kinds with fewer parameters
+// ignore the rest): the one per-element definition behind pp_dist_logweight, pp_mix_logweight and pp_obs_logweight. `kind` comes
+// from a kernel argument block or a template argument, so every lane of a wave takes the same branch.
+__device__ __forceinline__ float scalar_log_prob_at(int kind, float a, float b, float c, float d, float x) {
     switch (kind) {
-        case 0: return normal_lp(a, p[1][r * s[1]], x);
-        case 1: return uniform_lp(a, p[1][r * s[1]], x);
+        case 0: return normal_lp(a, b, x);
+        case 1: return uniform_lp(a, b, x);
         case 3: return (x >= 0.0f && x == floorf(x)) ? poisson_lp(a, x) : -INFINITY;      // (guarded here: is_draw.hpp)
         case 4: return (x == 0.0f || x == 1.0f) ? bernoulli_lp(a, x) : -INFINITY;
         case 6: return lp_exponential(a, x);
-        case 7: return lp_gamma(a, p[1][r * s[1]], x);
-        case 8: return lp_beta(a, p[1][r * s[1]], p[2][r * s[2]], p[3][r * s[3]], x);
-        case 9: return lp_lognormal(a, p[1][r * s[1]], x);
-        case 10: return lp_weibull(a, p[1][r * s[1]], x);
-        case 11: return lp_binomial(a, p[1][r * s[1]], x);
-        case 12: return lp_vonmises(a, p[1][r * s[1]], x);
-        default: return lp_truncnormal(a, p[1][r * s[1]], p[2][r * s[2]], p[3][r * s[3]], x);
+        case 7: return lp_gamma(a, b, x);
+        case 8: return lp_beta(a, b, c, d, x);
+        case 9: return lp_lognormal(a, b, x);
+        case 10: return lp_weibull(a, b, x);
+        case 11: return lp_binomial(a, b, x);
+        case 12: return lp_vonmises(a, b, x);
+        default: return lp_truncnormal(a, b, c, d, x);
     }
+}
+
+// The same at particle r: parameter q is p[q][r * s[q]] (only the parameters the kind has are read); shared by
+// dist_logweight_kernel and mix_logweight_kernel.
+__device__ __forceinline__ float scalar_log_prob(int kind, const float* const* p, const int* s, int64_t r, float x) {
+    const bool one = kind == 3 || kind == 4 || kind == 6, four = kind == 8 || kind == 13;
+    const float a = p[0][r * s[0]];
+    const float b = one ? 0.0f : p[1][r * s[1]];
+    const float c = four ? p[2][r * s[2]] : 0.0f;
+    const float d = four ? p[3][r * s[3]] : 0.0f;
+    return scalar_log_prob_at(kind, a, b, c, d, x);
 }
 
 // ---- samplers --------------------------------------------------------------------------------------------------------

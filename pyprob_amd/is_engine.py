@@ -16,8 +16,11 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .distributions import DIST_KINDS, DIST_PARAMS
-from .ops import ops
+from .distributions import DIST_KINDS, DIST_PARAMS, MIXTURE_COMPONENT_KINDS as SCALAR_KINDS
+from .ops import obs_draw_strides, ops
+
+# the attributes every scalar family's parameters are read from, in p0..p3 order (SCALAR_KINDS: kinds 0, 1, 3, 4, 6-13)
+SCALAR_PARAMS = dict(DIST_PARAMS, Normal=('mean', 'stddev'), Uniform=('low', 'high'), Poisson=('rate',), Bernoulli=('probs',))
 
 
 # ---- a log-weight term: what lw += scale * log p(x) needs to know about p. DistRunner.dist_term builds them; nothing else does.
@@ -76,6 +79,39 @@ class MixTerm(NamedTuple):
     probs: Any
     K: int
     fused = False
+
+
+class VecTerm(NamedTuple):
+    """A vector-valued likelihood (pp_obs_logweight): a scalar family's kind, its four parameter slots as (tensor, row stride,
+    element stride) operands (None: unused) over rows of k values, and k. Built by DistRunner.vec_term."""
+    kind: int
+    p0: Any
+    p1: Any
+    p2: Any
+    p3: Any
+    k: int
+    fused = False
+
+    @property
+    def operands(self):
+        return [self.p0, self.p1, self.p2, self.p3]
+
+    @property
+    def params(self):
+        return [None if o is None else o[0] for o in self.operands]
+
+    @property
+    def shared(self):
+        """Every parameter is one value or one row for all particles."""
+        return all(o is None or o[1] == 0 for o in self.operands)
+
+
+def _strip1(shape):
+    """A shape without its leading 1s."""
+    shape = tuple(int(d) for d in shape)
+    while shape and shape[0] == 1:
+        shape = shape[1:]
+    return shape
 
 
 class DistRunner:
@@ -140,18 +176,9 @@ class DistRunner:
         def s(v):
             return 0 if v.numel() == 1 else 1
         name = distribution.name
-        if name == 'Normal':
-            p0, p1 = t(distribution.mean), t(distribution.stddev)
-            return ScalarTerm(0, p0, s(p0), p1, s(p1))
-        if name == 'Uniform':
-            p0, p1 = t(distribution.low), t(distribution.high)
-            return ScalarTerm(1, p0, s(p0), p1, s(p1))
-        if name == 'Poisson':
-            p0 = t(distribution.rate)
-            return ScalarTerm(3, p0, s(p0), None, 0)
-        if name == 'Bernoulli':
-            p0 = t(distribution.probs)
-            return ScalarTerm(4, p0, s(p0), None, 0)
+        if name in ('Normal', 'Uniform', 'Poisson', 'Bernoulli'):
+            ps = [t(getattr(distribution, a)) for a in SCALAR_PARAMS[name]] + [None]
+            return ScalarTerm(SCALAR_KINDS[name], ps[0], s(ps[0]), ps[1], 0 if ps[1] is None else s(ps[1]))
         if name == 'Categorical':
             C_ = int(distribution.num_categories)
             p0 = t(distribution.probs)
@@ -194,6 +221,58 @@ class DistRunner:
             probs = torch.as_tensor(raw, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(self.dev).contiguous()
         return MixTerm('Mixture', kinds, ps, ss, probs, K)
 
+    def vec_term(self, distribution, value_shape, width, before_read=None):
+        """The VecTerm of a likelihood whose value has `value_shape` (k elements, shared by the `width` particles), or None: the
+        family is not a scalar one (Mixture, Categorical, Factor, an unknown name) or a parameter is none of
+            one element                                   -> (0, 0)  a scalar
+            the value's shape (leading 1s aside)          -> (0, 1)  one row for all particles
+            [width] + 1s, one dimension more than the value -> (1, 0)  one value per particle
+            [width, *value's shape]                       -> (k, 1)  one row per particle
+        - the readings under which torch's broadcast of parameter and value is what the kernel computes. A parameter that torch
+        has expanded (stride 0) is taken back to what it was expanded from; nothing is copied to [width, k] that was not. Only
+        a view that is not contiguous has to be copied, i.e. READ: `before_read` is called once before the first such copy (the
+        lock-step executor passes its flush: the view may be one of a draw that is still deferred)."""
+        kind = SCALAR_KINDS.get(getattr(distribution, 'name', None))
+        if kind is None:
+            return None
+        vs = _strip1(value_shape)
+        k = 1
+        for d in vs:
+            k *= d
+        n = int(width)
+        pending = [before_read]
+
+        def packed(t):
+            if not t.is_contiguous() and pending[0] is not None:
+                pending.pop()()
+                pending.append(None)
+            return t.contiguous()
+        ops_ = []
+        with torch._C.DisableTorchFunctionSubclass():
+            for attr in SCALAR_PARAMS[distribution.name]:
+                v = getattr(distribution, attr)
+                if not torch.is_tensor(v) or (v.device.type == 'cpu' and v.numel() == 1):
+                    ops_.append((self._const(float(v)), 0, 0))
+                    continue
+                t = v.as_subclass(torch.Tensor)
+                if t.dtype != torch.float32 or t.device != self.dev:
+                    t = t.to(self.dev, torch.float32)
+                shape, stride = tuple(t.shape), t.stride()
+                if all(s == 0 or d == 1 for s, d in zip(stride, shape)):                       # one value, expanded or not
+                    ops_.append((t[(0,) * t.dim()].reshape(1), 0, 0))
+                elif _strip1(shape) == vs or (t.dim() >= 1 and shape[0] == n and stride[0] == 0 and _strip1(shape[1:]) == vs):
+                    if _strip1(shape) != vs:
+                        t = t[0]                                                              # a row expanded over the particles
+                    ops_.append((packed(t).reshape(k), 0, 1))
+                elif t.dim() == len(vs) + 1 and shape[0] == n and all(s == 0 or d == 1 for s, d in zip(stride[1:], shape[1:])):
+                    ops_.append((packed(t[(slice(None),) + (0,) * (t.dim() - 1)]).reshape(n, 1), 1, 0))
+                elif t.dim() >= 2 and shape[0] == n and _strip1(shape[1:]) == vs:
+                    ops_.append((packed(t).reshape(n, k), k, 1))
+                else:
+                    return None
+        ops_ += [None] * (4 - len(ops_))
+        return VecTerm(kind, *ops_, k)
+
     def _flat(self, x):
         """x as a plain float32 contiguous flat tensor on the runner's device."""
         x = x.as_subclass(torch.Tensor) if type(x) is not torch.Tensor else x
@@ -205,6 +284,13 @@ class DistRunner:
         """The sizes the kernels rely on: x (if given) and every parameter hold 1 or n elements - Categorical: one probability
         row or n rows, a Mixture's weights: K or n K."""
         sized = [x]             # what holds 1 or n elements
+        if type(term) is VecTerm:       # x: the k observed values; an operand's strides are those of its shape
+            if x is not None and x.numel() != term.k:
+                raise RuntimeError('lock-step vector likelihood: a value of k = %d elements' % term.k)
+            for o in term.operands:
+                if o is not None and obs_draw_strides(o[0], n, term.k, 'parameter', 'obs_logweight') != (o[1], o[2]):
+                    raise RuntimeError('lock-step vector likelihood: an operand does not have the strides of its shape')
+            return
         if type(term) is ScalarTerm and term.kind == 5:
             if term.p0.numel() not in (term.s1, n * term.s1):
                 raise RuntimeError('lock-step Categorical: one row of C probabilities or n rows')
@@ -234,12 +320,14 @@ class DistRunner:
         """lw[r] += scale * log p(x[r]) for the particles r of a control-flow path: all of them, or - a path kept as a row list
         (LockStepState.by_rows) - the ascending int64 indices `rows`, or - a path kept as a mask - the bool [n] `mask`, next to
         which `rows` are the same particles as the state holds them. One launch per term type (pp_logweight_terms /
-        pp_logweight_accumulate_rows, pp_dist_logweight, pp_mix_logweight); a ScalarTerm under a mask is evaluated for every
+        pp_logweight_accumulate_rows, pp_dist_logweight, pp_mix_logweight, pp_obs_logweight: x = the k observed values); a ScalarTerm under a mask is evaluated for every
         particle (stale entries of the others may be anything) and added where the mask is set."""
         n = lw.numel()
         x = self._flat(x)
         self._check(term, x, n)
-        if type(term) is MixTerm:
+        if type(term) is VecTerm:
+            ops.obs_logweight(lw, int(term.kind), term.params, x, int(term.k), float(scale), rows, None, n)
+        elif type(term) is MixTerm:
             ops.mix_logweight(lw, term.kinds, term.params, term.strides, term.probs, x, float(scale), rows, None, n)
         elif type(term) is DistTerm:
             ops.dist_logweight(lw, [int(term.kind)], term.params, term.strides, [x], [float(scale)], rows, None, n)
@@ -256,6 +344,11 @@ class DistRunner:
     def log_prob(self, term, x, n=None):
         """log_prob(dist; x) per particle as a device tensor [n] (no accumulation)."""
         x = self._flat(x)
+        if type(term) is VecTerm:       # x: the k observed values, lp: their summed log-density per particle (n is needed)
+            self._check(term, x, n)
+            lp = torch.empty(n, dtype=torch.float32, device=self.dev)
+            ops.obs_logweight(None, int(term.kind), term.params, x, int(term.k), 1.0, None, lp, n)
+            return lp
         n = int(x.numel()) if n is None else n
         self._check(term, x, n)
         if type(term) is ScalarTerm:

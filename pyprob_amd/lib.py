@@ -91,6 +91,11 @@ class pp_mixture(C.Structure):
     _fields_ = [('count', i32), ('probs_stride', i32), ('probs', vp), ('comp', pp_dist * PP_MIX_MAX_COMPONENTS)]
 
 
+class pp_obs_operand(C.Structure):
+    """An operand of pp_obs_logweight: operand[r, e] = p[r * row_stride + e * elem_stride]."""
+    _fields_ = [('p', vp), ('row_stride', i64), ('elem_stride', i32), ('_pad', i32)]
+
+
 class pp_gemm_args(C.Structure):
     _fields_ = [('A', vp), ('lda', i64), ('a_idx', vp),
                 ('B', vp), ('ldb', i64), ('b_idx', vp),
@@ -174,6 +179,7 @@ PROTOTYPES = {
     'pp_dist_logweight': (C.c_int, [C.POINTER(pp_dist_term), i32, vp, vp, vp, i32, i32, vp]),
     'pp_dist_draw': (C.c_int, [C.POINTER(pp_dist), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_mix_logweight': (C.c_int, [C.POINTER(pp_mixture), vp, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
+    'pp_obs_logweight': (C.c_int, [i32, C.POINTER(pp_obs_operand), pp_obs_operand, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
     'pp_mix_draw': (C.c_int, [C.POINTER(pp_mixture), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_gemm_f32': (C.c_int, [C.POINTER(pp_gemm_args), vp]),
     'pp_gemm_f32_grouped': (C.c_int, [C.POINTER(pp_gemm_args), i32, vp]),

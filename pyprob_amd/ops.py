@@ -20,6 +20,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     dist_draw       draws of every distribution family (Philox)       pyprob/state.py:191-201, 218-221
     mix_logweight   Mixture.log_prob as a log-weight term               pyprob/distributions/mixture.py:38-45
     obs_draw        the synthetic observation block of n prior traces   pyprob/nn/dataset.py:50-62, state.py observe branch
+    obs_logweight   the summed log-density of a vector-valued observe    pyprob/state.py:118-155, trace.py:123-125
     mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -63,6 +64,8 @@ _lib.define('is_fused(Tensor(a!) workspace, int net, int addr_id, Tensor? prior,
             'bool overwrite, int seed, int offset, Tensor(d!)? stats_scratch) -> Tensor')
 _lib.define('prior_draw(int kind, Tensor p0, Tensor p1, int n, int seed, int offset, int stream_id) -> Tensor')
 _lib.define('obs_draw(int kind, Tensor p0, Tensor p1, int n, int k, int seed, int offset, int stream_id) -> Tensor')
+_lib.define('obs_logweight(Tensor(a!)? lw, int kind, Tensor?[] params, Tensor x, int k, float scale, Tensor? rows, '
+            'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('log_prob(int kind, Tensor p0, int p0_stride, Tensor? p1, int p1_stride, Tensor x, int n) -> Tensor')
 _lib.define('logweight_terms(Tensor(a!) lw, int[] kinds, Tensor?[] p0, int[] p0_strides, Tensor?[] p1, int[] p1_strides, '
             'Tensor[] x, float[] scales, bool overwrite) -> ()')
@@ -398,21 +401,29 @@ def _prior_draw_hip(kind, p0, p1, n, seed, offset, stream_id):
     return out
 
 
-def obs_draw_strides(t, n, k, name='p'):
-    """(row stride, element stride) with which pp_obs_draw reads a parameter of n rows of k values: a scalar (one element) ->
-    (0, 0); [k] or [1, k] - one row shared by all traces -> (0, 1); [n] or [n, 1] - one value per trace -> (1, 0); [n, k] ->
-    (k, 1). A 1-D tensor of k elements is the shared row also when n == k (callers pass per-trace values as [n, 1])."""
+def obs_draw_strides(t, n, k, name='p', what='obs_draw'):
+    """(row stride, element stride) with which pp_obs_draw / pp_obs_logweight read an operand of n rows of k values: a scalar (one
+    element) -> (0, 0); [k] or [1, k] - one row shared by all rows -> (0, 1); [n] or [n, 1] - one value per row -> (1, 0);
+    [n, k] -> (k, 1). A 1-D tensor of k elements is the shared row also when n == k (callers pass per-row values as [n, 1]).
+    For `obs_logweight` only (obs_draw's accepted shapes are what they were): a contiguous [n, *event] whose trailing dimensions
+    flatten to k (an image per row: [n, C, H, W]) -> (k, 1), and a 2-D [n, k] view with unit element stride and a row stride
+    above k (a padded block) -> (that row stride, 1). Every other tensor has to be contiguous."""
     shape = tuple(t.shape)
+    wide = what == 'obs_logweight'
+    if wide and shape == (n, k) and not t.is_contiguous() and t.stride(1) == 1 and t.stride(0) >= k:
+        return t.stride(0), 1
+    if wide and not t.is_contiguous():
+        raise RuntimeError('pyprob_hip::%s: %s must be contiguous (or a [n, k] view with padded rows)' % (what, name))
     if t.numel() == 1:
         return 0, 0
     if shape in ((k,), (1, k)):
         return 0, 1
     if shape in ((n,), (n, 1)):
         return 1, 0
-    if shape == (n, k):
+    if shape == (n, k) or (wide and len(shape) > 2 and shape[0] == n and t.numel() == n * k):
         return k, 1
-    raise RuntimeError('pyprob_hip::obs_draw: %s must be a scalar, [k], [n], [n, 1] or [n, k] (n = %d, k = %d), got %s'
-                       % (name, n, k, list(shape)))
+    raise RuntimeError('pyprob_hip::%s: %s must be a scalar, [k], [n], [n, 1] or [n, k] (n = %d, k = %d), got %s'
+                       % (what, name, n, k, list(shape)))
 
 
 def _obs_draw_hip(kind, p0, p1, n, k, seed, offset, stream_id):
@@ -428,6 +439,38 @@ def _obs_draw_hip(kind, p0, p1, n, k, seed, offset, stream_id):
                              int(stream_id) & 0xFFFFFFFF, out.data_ptr(), _stream(p0))
     L.check(rc, 'pp_obs_draw')
     return out
+
+
+def _obs_logweight_hip(lw, kind, params, x, k, scale, rows, lp_out, n):
+    lib = L.load()
+    n, k = int(n), int(k)
+    if len(params) != 4:
+        raise RuntimeError('pyprob_hip::obs_logweight: 4 parameter slots')
+    ref = lw if lw is not None else lp_out
+    if ref is None:
+        raise RuntimeError('pyprob_hip::obs_logweight: lw or lp_out is needed')
+    for t, name in ((lw, 'lw'), (lp_out, 'lp_out')):
+        if t is not None and (_f32(t, name).numel() != n):
+            raise RuntimeError('pyprob_hip::obs_logweight: %s must have n = %d elements' % (name, n))
+    _same_device(ref, lw, lp_out, rows, x, *params)
+    if n < 0 or k < 1:
+        raise RuntimeError('pyprob_hip::obs_logweight: n >= 0 rows of k >= 1 values, got n = %d, k = %d' % (n, k))
+
+    def operand(o, t, name):
+        if t.dtype != torch.float32:
+            raise RuntimeError('pyprob_hip: %s must be a float32 tensor' % name)
+        rs, es = obs_draw_strides(t, n, k, name, 'obs_logweight')
+        o.p, o.row_stride, o.elem_stride = t.data_ptr(), int(rs), int(es)
+    arr = (L.pp_obs_operand * 4)()
+    for q in range(4):
+        if params[q] is not None:
+            operand(arr[q], params[q], 'p%d' % q)
+    xo = L.pp_obs_operand()
+    operand(xo, x, 'x')
+    rp, m = _rows_arg(rows, n, 'obs_logweight')
+    with torch.cuda.device(ref.device):
+        rc = lib.pp_obs_logweight(int(kind), arr, xo, k, float(scale), L.ptr(lw), L.ptr(lp_out), rp, int(m), n, _stream(ref))
+    L.check(rc, 'pp_obs_logweight')
 
 
 def _log_prob_hip(kind, p0, p0_stride, p1, p1_stride, x, n):
@@ -603,6 +646,7 @@ _lib.impl('is_step_net', _is_step_net_hip, 'CUDA')
 _lib.impl('is_fused', _is_fused_hip, 'CUDA')
 _lib.impl('prior_draw', _prior_draw_hip, 'CUDA')
 _lib.impl('obs_draw', _obs_draw_hip, 'CUDA')
+_lib.impl('obs_logweight', _obs_logweight_hip, 'CUDA')
 _lib.impl('log_prob', _log_prob_hip, 'CUDA')
 _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')

@@ -963,6 +963,20 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
         if ls.observes <= ls.replay_observes:
             return
         from .distributions import Factor
+        term = _vector_likelihood_term(ls, distribution, value)
+        if term is not None and term.shared:
+            # one row for all particles: its sum is computed once (n = 1) and joins the weights as today's one-element factor
+            draw = getattr(ls, 'draw', None)
+            if draw is not None:      # (one particle: a shared parameter may BE the deferred draw's storage, which the kernel reads)
+                pend = draw['values'].untyped_storage().data_ptr()
+                if any(q is not None and q.untyped_storage().data_ptr() == pend for q in term.params):
+                    ls.flush()
+            x = ls.runner.log_prob(term, v, 1)
+            _lock_step_term(ls, ls.runner.dist_term(Factor(log_prob=x)), x)
+            return
+        if term is not None:
+            _lock_step_term(ls, term, v)
+            return
         lp = distribution.log_prob(v.reshape(torch.as_tensor(value).shape))
         with torch._C.DisableTorchFunctionSubclass():
             lp = lp.as_subclass(torch.Tensor).to(ls.runner.dev, torch.float32)
@@ -982,6 +996,17 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
     if term is None:
         raise RuntimeError('lock-step importance sampling has no device likelihood for {}'.format(distribution.name))
     _lock_step_term(ls, term, v, obs_name)
+
+
+def _vector_likelihood_term(ls, distribution, value):
+    """The VecTerm with which a vector-valued observe is scored in one launch (pp_obs_logweight), or None: the torch route.
+    PP_VEC_LIKELIHOOD, read here: `auto` (the default) - the kernel when the run is on a GPU device, torch on the CPU device;
+    `torch` - the torch route everywhere (A/B runs); `kernel` - the operator on every device."""
+    route = os.environ.get('PP_VEC_LIKELIHOOD', 'auto')
+    if route == 'torch' or (route != 'kernel' and ls.runner.dev.type != 'cuda'):
+        return None
+    # (vec_term calls the flush only if it has to copy - read - a view that is not contiguous: it may be one of a deferred draw)
+    return ls.runner.vec_term(distribution, tuple(torch.as_tensor(value).shape), ls.width, before_read=ls.flush)
 
 
 def _lock_step_term(ls, term, v, obs_name=None):
