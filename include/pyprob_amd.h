@@ -532,6 +532,45 @@ int pp_is_fused(const pp_net* net, int32_t addr_id, int32_t n, const float* prio
                 uint64_t seed, uint64_t offset, double* stats_out /*dev [6] or NULL*/, double* stats_scratch, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* Batched posteriors: M observations ("groups") with n_per particles each in ONE lock-step call. The reference serves one
+ * observation per posterior call (pyprob/model.py:106-117; InferenceNetwork._infer_init embeds THE observation,
+ * pyprob/nn/inference_network.py:141-148, and every trace's first _infer_step runs on it,
+ * pyprob/nn/inference_network_lstm.py:82-134, inference_network_feedforward.py:52-66; state.sample / state.observe score one
+ * trace at a time, pyprob/state.py:118-155, 203-219; Empirical reduces one posterior, pyprob/distributions/empirical.py:298-309,
+ * 451-466, 758-766): posteriors for M observations are M calls there, and M pp_is_first_statement + pp_is_fused pairs here.
+ *   pp_is_batch_workspace_bytes  scratch of the two calls below for n_groups observations (no zero-fill needed; independent of
+ *                       n_per).
+ *   pp_is_batch_first   _infer_init + _infer_step(prev_variable = None) + the proposal layer of `addr_id` for M DIFFERENT
+ *                       observations: obs dev [M, obs_width] (the observables' values in the network's order), y_out dev
+ *                       [M, ldy] (ldy a multiple of 4, >= the head's n_out) receives the head outputs - row g is what
+ *                       pp_is_first_statement leaves in its workspace for observation g, up to the rounding of another summation
+ *                       order. h_out / c_out: dev [M, H] or NULL - the LSTM state after the statement (for a caller that
+ *                       continues with a second statement; ignored by a FeedForward network). FEEDFORWARD observe embeddings, a
+ *                       FeedForward network or an LSTM of depth 1; PP_EINVAL otherwise. The launches are those of the training
+ *                       step's forward at T = 1: embedding GEMMs, input gather, gate GEMM, cell, head GEMMs.
+ *   pp_is_fused_groups  pp_is_fused for the M n_per particles: particle i = g n_per + j belongs to group g, draws from the
+ *                       proposal in row g of `y` (mixture heads; Philox counter offset + i, the key and stream of pp_is_fused and
+ *                       pp_is_step - an M-group call consumes exactly the counters of M one-group calls at offset + g n_per),
+ *                       lw[i] (+)= - log q(v) + sum_t scale_t term_t(i), value[i] = v; addr_id < 0: no draw, `value` is read (y
+ *                       and prior may be NULL). The terms are pp_lw_term's with the three stride fields holding an OPERAND CODE:
+ *                       0 one shared value, 1 one value per particle (index i), 2 one value per group (index g); Categorical
+ *                       (kind 5): p0_stride codes which row of p1_stride weights - the shared one, row i or row g. term_flags as
+ *                       in pp_is_fused. stats_out != NULL: dev double [M, 6], row g = the six numbers of pp_is_stats over group g
+ *                       (w = exp(lw - max lw) with exp in fp64), reduced by dependent launches on the same stream in a fixed
+ *                       order that depends on n_per alone - bit-identical from run to run and between an M-group call and the
+ *                       one-group call on the same particles. At most 8 terms, any n_per >= 1; 8 bytes per particle are
+ *                       written, the statistics read them once more. `net` is required (also without a draw). Of the
+ *                       workspace only the first PP_IS_GROUP_STATS_BYTES(n_groups) bytes are used, and only with stats_out. */
+#define PP_IS_GROUP_STATS_BYTES(m) ((size_t)((m) > 256 ? (m) : 256) * 48)
+size_t pp_is_batch_workspace_bytes(const pp_net* net, int32_t n_groups);
+int pp_is_batch_first(const pp_net* net, const float* params, const float* obs /*dev [M, obs_width]*/, int32_t addr_id, int32_t n_groups,
+                      float* y_out /*dev [M, ldy]*/, int64_t ldy, float* h_out, float* c_out /*dev [M, H] or NULL*/, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int pp_is_fused_groups(const pp_net* net, int32_t addr_id, int32_t n_groups, int32_t n_per, const float* y /*dev [M, ldy]*/, int64_t ldy,
+                       const float* prior /*dev [2]*/, const pp_lw_term* terms, const int32_t* term_flags, int32_t n_terms,
+                       float* value /*dev [M n_per]*/, float* lw /*dev [M n_per]*/, int32_t overwrite, uint64_t seed, uint64_t offset,
+                       double* stats_out /*dev double [M, 6] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

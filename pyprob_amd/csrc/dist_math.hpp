@@ -18,7 +18,7 @@ constexpr float kPi = 3.14159265358979323846f;
 // torch.xlogy(a, x): 0 where a == 0 (x not NaN), a * log(x) otherwise
 __device__ __forceinline__ float xlogyf(float a, float x) { return (a == 0.0f && x == x) ? 0.0f : a * logf(x); }
 
-// ---- log-densities (kinds 6-13; the formulas of kinds 0-5 are is_draw.hpp's, shared with is_kernels.hip's term_log_prob) ------
+// ---- log-densities (kinds 6-13; the formulas of kinds 0-5 are is_draw.hpp's, shared with term_log_prob) ------
 
 // 6 Exponential(rate): log(rate) - rate x, support [0, inf)
 // (the fused multiply-add is written out: it is what the compiler's contraction gives where one lane scores one value, and a

@@ -83,6 +83,27 @@ __device__ __forceinline__ float uniform_draw(float a, float b, uint32_t w0) {
     return v < b ? v : a;
 }
 
+// log_prob of the prior / likelihood families state.sample and state.observe score (state.py:211, 147-149), by the formulas
+// above (pp_logweight_*, pp_is_fused, pp_is_fused_groups):
+//   0 Normal(mean a, stddev b)   1 Uniform(low a, high b)   3 Poisson(rate a)   4 Bernoulli(probs a)
+//   5 Categorical(probs row p0[i * s0 .. + C), C = s1)
+__device__ __forceinline__ float term_log_prob(int kind, const float* __restrict__ p0, int s0, const float* __restrict__ p1,
+                                               int s1, float v, int64_t i) {
+    if (kind == 5) {         // (the index is the truncated value)
+        const float* p = p0 + i * s0;
+        const int C = s1, k = (int)v;
+        float sum = 0.0f;
+        for (int c = 0; c < C; ++c) sum += p[c];
+        if (k < 0 || k >= C) return -INFINITY;
+        return categorical_lp(p, sum, k);
+    }
+    const float a = p0[i * s0];
+    if (kind == 3) return poisson_lp(a, v);          // (no support test on the value here, nor for Bernoulli: is_draw.hpp)
+    if (kind == 4) return bernoulli_lp(a, v);
+    const float b = p1[i * s1];
+    return kind == 0 ? normal_lp(a, b, v) : uniform_lp(a, b, v);
+}
+
 // Standard normal deviate of the SHARED-proposal kernels (the first statement of a lock-step run: is_mixture_shared_kernel and
 // is_fused_kernel, one draw per particle, 10^6 particles per call): sqrt(-2 ln u1) cos(2 pi u2) on the hardware log2 / cos /
 // sqrt (v_log_f32, v_cos_f32 takes its argument in revolutions, v_sqrt_f32: ~1e-6 absolute on a deviate of unit scale, ~60

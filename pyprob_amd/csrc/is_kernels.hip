@@ -923,26 +923,7 @@ int is_step(const pp_net* net, const float* P, int addr_id, int prev_addr_id, in
     return 0;
 }
 
-// log_prob of the prior / likelihood families state.sample and state.observe score (state.py:211, 147-149), by the formulas
-// of is_draw.hpp:
-//   0 Normal(mean a, stddev b)   1 Uniform(low a, high b)   3 Poisson(rate a)   4 Bernoulli(probs a)
-//   5 Categorical(probs row p0[i * s0 .. + C), C = s1)
-__device__ __forceinline__ float term_log_prob(int kind, const float* __restrict__ p0, int s0, const float* __restrict__ p1,
-                                               int s1, float v, int64_t i) {
-    if (kind == 5) {         // (the index is the truncated value)
-        const float* p = p0 + i * s0;
-        const int C = s1, k = (int)v;
-        float sum = 0.0f;
-        for (int c = 0; c < C; ++c) sum += p[c];
-        if (k < 0 || k >= C) return -INFINITY;
-        return categorical_lp(p, sum, k);
-    }
-    const float a = p0[i * s0];
-    if (kind == 3) return poisson_lp(a, v);          // (no support test on the value here, nor for Bernoulli: is_draw.hpp)
-    if (kind == 4) return bernoulli_lp(a, v);
-    const float b = p1[i * s1];
-    return kind == 0 ? normal_lp(a, b, v) : uniform_lp(a, b, v);
-}
+// (term_log_prob, the log_prob of the prior / likelihood families state.sample and state.observe score: is_draw.hpp)
 
 // lw[i] += scale * log_prob(dist(p0_i, p1_i); x_i)
 __global__ __launch_bounds__(256) void logweight_kernel(int kind, const float* __restrict__ p0, int s0,

@@ -735,6 +735,89 @@ class ISRunner(DistRunner):
                 time.sleep(0)
         return values, lw, self._stats_dict(snp)
 
+    # ---- batched posteriors: M observations x n_per particles in one call (pp_is_batch_first, pp_is_fused_groups) --------------
+    def batch_supported(self):
+        """Does pp_is_batch_first take this network (FEEDFORWARD observe embeddings, FeedForward or a one-layer LSTM)?"""
+        net = self.eng.net
+        return (self.dev.type == 'cuda' and all(net.obs_kind[o] == L.PP_OBS_FEEDFORWARD for o in range(net.n_obs)) and
+                (self.eng.spec.lstm_dim == 0 or max(1, self.eng.spec.lstm_depth) == 1))
+
+    def init_batch(self, obs):
+        """_infer_init for M observations: obs [M, obs_width], one row per group, the observables' values in the network's
+        order. The rows go to the device once; the embedding is computed by first_batch."""
+        obs = torch.as_tensor(obs, dtype=torch.float32)
+        if obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != self.eng.spec.obs_width:
+            raise ValueError('observations of shape %s, the network expects [M >= 1, %d]' % (tuple(obs.shape), self.eng.spec.obs_width))
+        if torch.cuda.current_device() != (self.dev.index or 0):
+            torch.cuda.set_device(self.dev)
+        self._b_M = M = int(obs.shape[0])
+        self._b_obs = obs.to(self.dev).contiguous()
+        need = self.lib.pp_is_batch_workspace_bytes(C.byref(self.eng.net), M)
+        if getattr(self, '_b_ws', None) is None or need > self._b_ws.numel():
+            self._b_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        self._st = L.stream_ptr()
+        self.offset = 0
+        self.prev_value = self.last_value = None
+
+    def first_batch(self, addr_id, keep_state=False):
+        """_infer_step(prev_variable=None) + the proposal layer of `addr_id` for the M observations of init_batch: the head
+        outputs [M, ldy], one row per group (kept for fused_groups). keep_state: also (h, c) [M, H]."""
+        M, H = self._b_M, self.eng.spec.lstm_dim
+        ldy = (int(self.eng.net.addrs[int(addr_id)].n_out) + 3) & ~3
+        self._b_y = torch.empty(M, ldy, dtype=torch.float32, device=self.dev)
+        self._b_h = self._b_c = None
+        if keep_state and H:
+            self._b_h = torch.empty(M, H, dtype=torch.float32, device=self.dev)
+            self._b_c = torch.empty(M, H, dtype=torch.float32, device=self.dev)
+        L.check(self.lib.pp_is_batch_first(C.byref(self.eng.net), self.eng.params.data_ptr(), self._b_obs.data_ptr(), int(addr_id), M,
+                                           self._b_y.data_ptr(), ldy, L.ptr(self._b_h), L.ptr(self._b_c), self._b_ws.data_ptr(),
+                                           self._b_ws.numel(), self._st), 'pp_is_batch_first')
+        return self._b_y
+
+    def fused_groups(self, addr_id, n_per, prior, terms, value, lw, overwrite, seed=0, offset=0, stats=False, y=None):
+        """pp_is_fused_groups over value / lw [M n_per]: [draw from row i // n_per of the head outputs `y` (default: first_batch's),
+        - log q,] lw (+)= sum of `terms`, [the statistics of every group]. terms = [((kind, p0, c0, p1, c1), x, cx, scale, flags)]
+        with operand codes c0 / c1 / cx 0 shared, 1 per particle, 2 per group (Categorical: c1 = the number of categories) and
+        flags as in `fused`. Returns the statistics as a device tensor double [M, 6] when asked for (no synchronisation)."""
+        y = self._b_y if (y is None and addr_id is not None) else y
+        total = value.numel()
+        if total % int(n_per) or lw.numel() != total or not (value.is_contiguous() and lw.is_contiguous()):
+            raise RuntimeError('fused_groups: contiguous value and lw of M * n_per elements')
+        M = total // int(n_per)
+        count = len(terms)
+        arr = (L.pp_lw_term * max(count, 1))()
+        fl = (C.c_int32 * max(count, 1))()
+        sizes = {0: 1, 1: total, 2: M}
+        for q, ((kind, p0, c0, p1, c1), x, cx, scale, flags) in enumerate(terms):
+            rows = int(c1) if int(kind) == 5 else 1
+            if any(int(code) not in sizes for code in ((c0, cx) if int(kind) == 5 else (c0, c1, cx))):
+                raise RuntimeError('fused_groups: term %d: operand codes are 0 (shared), 1 (per particle) or 2 (per group)' % q)
+            for t, code, what in ((p0, c0, 'p0'), (p1, 0 if int(kind) == 5 else c1, 'p1'), (x, cx, 'x')):
+                if t is None:
+                    continue
+                if t.device != value.device or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise RuntimeError('fused_groups: term %d: %s must be a contiguous float32 tensor on %s' % (q, what, value.device))
+                if t.numel() < sizes[int(code)] * (rows if what == 'p0' else 1):
+                    raise RuntimeError('fused_groups: term %d: %s has %d elements, operand code %d' % (q, what, t.numel(), code))
+            arr[q].kind = int(kind)
+            arr[q].p0, arr[q].p1, arr[q].x = L.ptr(p0), L.ptr(p1), L.ptr(x)
+            arr[q].p0_stride, arr[q].p1_stride, arr[q].x_stride = int(c0), int(c1), int(cx)
+            arr[q].scale = float(scale)
+            fl[q] = int(flags)
+        need = max(M, 256) * 48          # PP_IS_GROUP_STATS_BYTES: the partial statistics records are all this call uses
+        if getattr(self, '_b_ws', None) is None or need > self._b_ws.numel():
+            self._b_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        out = torch.empty(M, 6, dtype=torch.float64, device=self.dev) if stats else None
+        if y is not None and (y.dim() != 2 or y.shape[0] < M or not y.is_contiguous()):
+            raise RuntimeError('fused_groups: head outputs [M, ldy]')
+        pr = None if prior is None else prior.reshape(-1)
+        st = self._st if self._st is not None else L.stream_ptr()
+        L.check(self.lib.pp_is_fused_groups(C.byref(self.eng.net), -1 if addr_id is None else int(addr_id), M, int(n_per), L.ptr(y),
+                                            0 if y is None else int(y.shape[1]), L.ptr(pr), arr, fl, count, value.data_ptr(),
+                                            lw.data_ptr(), 1 if overwrite else 0, int(seed), int(offset), L.ptr(out),
+                                            self._b_ws.data_ptr(), self._b_ws.numel(), st), 'pp_is_fused_groups')
+        return out
+
     PRIOR_KIND = {'Normal': 0, 'Uniform': 1}
 
     def whole_statement_ok(self, addr_id, prev_addr_id, m, dist_name, prior):

@@ -224,7 +224,7 @@ class Model:
             return None
 
     # attributes the Model base class itself keeps on the instance (never read by a program as constants)
-    _BASE_ATTRS = frozenset(('_inference_network', '_lockstep_plans', '_lock_step_ok', '_last_prior_resident', '_last_prior_obs_widths', '_plan_code_cache',
+    _BASE_ATTRS = frozenset(('_inference_network', '_lockstep_plans', '_lock_step_ok', '_batch_ok', '_last_prior_resident', '_last_prior_obs_widths', '_plan_code_cache',
                              '_plan_key_cache', '_plan_indirect_cache', '_plan_indirect_pairs'))
 
     @staticmethod
@@ -818,6 +818,146 @@ class Model:
                                 likelihood_importance, *args, **kwargs)
             post.rename('Posterior, IS, traces: {:,}, ESS: {:,.2f}'.format(post.length, post.effective_sample_size))
         return post
+
+    # ---- batched posteriors: M observations in one call ------------------------------------------------------------------
+    @staticmethod
+    def _normalise_observes(observes):
+        """(names, [M observe dicts], {name: float32 array [M, k]}) of `observes`: a list of M dicts with equal keys, or one dict
+        name -> tensor with a leading dimension M."""
+        if isinstance(observes, dict):
+            cols = {k: np.asarray(torch.as_tensor(v, dtype=torch.float32).cpu().numpy(), np.float32) for k, v in observes.items()}
+            if not cols or any(c.ndim < 1 for c in cols.values()):
+                raise ValueError('posterior_results_batch: every entry of `observes` needs a leading dimension M')
+            sizes = set(int(c.shape[0]) for c in cols.values())
+            if len(sizes) != 1:
+                raise ValueError('posterior_results_batch: the entries of `observes` have different leading dimensions %s' % sorted(sizes))
+            M = sizes.pop()
+            if M == 0:
+                raise ValueError('posterior_results_batch: no observation (M = 0)')
+            names = list(cols)
+            cols = {k: c.reshape(M, -1) for k, c in cols.items()}
+            dicts = [{k: torch.as_tensor(observes[k][g], dtype=torch.float32) for k in names} for g in range(M)]
+            return names, dicts, cols
+        dicts = list(observes)
+        if len(dicts) == 0:
+            raise ValueError('posterior_results_batch: no observation (M = 0)')
+        if any(not isinstance(d, dict) for d in dicts) or any(set(d) != set(dicts[0]) for d in dicts):
+            raise ValueError('posterior_results_batch: every observation must be a dict with the same keys')
+        names = list(dicts[0])
+        cols = {}
+        for k in names:
+            rows = [np.asarray(torch.as_tensor(d[k], dtype=torch.float32).cpu().numpy(), np.float32).reshape(-1) for d in dicts]
+            if len(set(r.size for r in rows)) != 1:
+                raise ValueError('posterior_results_batch: observable %r has different sizes across observations' % (k,))
+            cols[k] = np.stack(rows)
+        return names, dicts, cols
+
+    def posterior_results_batch(self, num_traces, observes, inference_engine=InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK,
+                                seed=0, offset=0, likelihood_importance=1., lock_step=None, *args, **kwargs):
+        """Posteriors for M observations: a list of M Empiricals, entry g = posterior_results(num_traces, observe=observes[g],
+        seed=seed, offset=offset + g * num_traces) in distribution - particle j of group g uses Philox counter
+        offset + g * num_traces + j, so the call consumes exactly the counters of those M calls. `observes`: a list of M observe
+        dicts with equal keys, or one dict name -> tensor with a leading dimension M.
+        A lock-step-safe program with ONE controlled sample statement on a mixture head (Normal / Uniform / Poisson prior), at most
+        8 scalar observes of the network's families, FEEDFORWARD observe embeddings and a FeedForward or one-layer LSTM network
+        runs all M * num_traces particles in ONE lock-step execution of forward() (the reference: M posterior calls,
+        pyprob/model.py:106-117); an observed value the program reads is then one value per group. Anything else is served by
+        that loop of posterior_results calls; which of the two is remembered per model."""
+        names, dicts, cols = self._normalise_observes(observes)
+        M, N = len(dicts), int(num_traces)
+
+        def loop():
+            return [self.posterior_results(N, inference_engine=inference_engine, observe=dicts[g], lock_step=lock_step, seed=seed,
+                                           offset=offset + g * N, likelihood_importance=likelihood_importance, *args, **kwargs)
+                    for g in range(M)]
+        net = self._inference_network
+        if inference_engine != InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK or net is None or \
+                lock_step in (False, 'per_trace') or N < 1:
+            return loop()
+        ok = getattr(self, '_batch_ok', None)
+        if ok is None and not (net._is.batch_supported() and (lock_step or self._lock_step_safe(dicts[0], *args, **kwargs))):
+            ok = self._batch_ok = False
+        if ok is False or any(c.shape[1] != 1 for c in cols.values()):      # (a vector or image observe: the loop)
+            return loop()
+        try:
+            runner = net._is
+            with torch.cuda.device(runner.dev):
+                return self._traces_lockstep_batch(N, names, cols, seed, offset, likelihood_importance, *args, **kwargs)
+        except state.BatchUnsupported:      # (nothing else: a device or runtime error of the fast path is the caller's to see)
+            self._batch_ok = False
+        return loop()
+
+    def _traces_lockstep_batch(self, num_traces, names, cols, seed, offset, likelihood_importance, *args, **kwargs):
+        """The fast path of posterior_results_batch: one execution of forward() for M * num_traces particles (state.BatchLockStepState),
+        sharded over groups where M * num_traces reaches the 2^32 / lstm_dim elements the state rows are addressed with. The M
+        Empiricals are slices of the call's device tensors; their statistics come back in ONE device-to-host copy."""
+        net = self._inference_network
+        runner = net._is
+        M, N = int(next(iter(cols.values())).shape[0]), int(num_traces)
+        missing = [n for n in net._obs_names if n not in cols]
+        if missing:
+            raise state.BatchUnsupported('observables %s of the network are not observed' % missing)
+        H = max(int(net._engine.spec.lstm_dim), 1)
+        per_call = max(1, (2 ** 32 // H - 1) // N)        # groups per execution
+        if N * H >= 2 ** 32:
+            raise ValueError('at most 2^32 / lstm_dim - 1 = %d particles per observation (got %d)' % (2 ** 32 // H - 1, N))
+        out = []
+        for g0 in range(0, M, per_call):
+            g1 = min(M, g0 + per_call)
+            obs = state.GroupObserves()
+            for k, c in cols.items():
+                obs[k] = torch.from_numpy(np.ascontiguousarray(c[g0:g1, 0])).to(runner.dev).as_subclass(state.GroupTensor)
+            obs.matrix = np.concatenate([cols[k][g0:g1] for k in net._obs_names], axis=1)
+            out += self._run_lockstep_batch(obs, g1 - g0, N, seed, offset + g0 * N, likelihood_importance, *args, **kwargs)
+        self._batch_ok = True
+        return out
+
+    def _run_lockstep_batch(self, obs, M, N, seed, offset, likelihood_importance, *args, **kwargs):
+        runner = self._inference_network._is
+        ls = state.BatchLockStepState(runner, M, N, seed, offset)
+        try:
+            state._init_traces(func=self.forward, trace_mode=TraceMode.POSTERIOR,
+                               inference_engine=InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK,
+                               inference_network=self._inference_network, observe=obs, likelihood_importance=likelihood_importance,
+                               lock_step=ls)
+            state._begin_trace()
+            result = self.forward(*args, **kwargs)
+            if not torch.is_tensor(result) or isinstance(result, state.GroupTensor) or result.numel() != M * N:
+                raise state.BatchUnsupported('forward() must return one value per particle')
+            if ls.statement != 1:
+                raise state.BatchUnsupported('no controlled sample statement')
+            values = result.as_subclass(torch.Tensor).reshape(-1)
+            if values.dtype != torch.float32 or values.device != runner.dev or not values.is_contiguous():
+                ls.flush()
+                values = values.to(runner.dev, torch.float32).contiguous()
+            ls.stats_values = values
+            ls.flush(final=True)
+            if ls.group_stats is None or ls.final_stats_of != (values.data_ptr(), values.numel()):
+                # (forward() returned something else than the draw that was still pending: the statistics are over ITS values)
+                ls.group_stats = runner.fused_groups(None, N, None, [], values, ls.lw, False, stats=True)
+        finally:
+            state._lock_step = None
+            state._current_trace = None
+            ls.memo = None
+        stats = ls.group_stats.cpu().numpy()          # the one device-to-host copy (and synchronisation) of the call
+        # (one split per tensor, not two slices per group: the per-group host work is what the call amortises)
+        v_parts, lw_parts = values.split(N), ls.lw.split(N)
+        log_parts = [[(a, rec[0].split(N), rec[1]) for a, rec in entry.items()] for entry in ls.log]
+        out = []
+        for g in range(M):
+            v_g, lw_g = v_parts[g], lw_parts[g]
+            st = runner._stats_dict(stats[g])
+            all_v, all_lw = v_g, lw_g
+            if int(st['count']) != N:
+                v_g, lw_g = _drop_non_finite(v_g, lw_g)
+                st = runner.stats(lw_g, v_g)
+            emp = Empirical.from_device(v_g, lw_g, st)
+            emp._all_values, emp._all_log_weights = all_v, all_lw
+            emp.num_paths = 1
+            emp.statement_log = [{a: (parts[g], addr_id) for a, parts, addr_id in entry} for entry in log_parts]
+            emp.rename('Posterior, IC, traces: {:,}, ESS: {:,.2f}'.format(emp.length, emp.effective_sample_size))
+            out.append(emp)
+        return out
 
     def posterior_results_distributed(self, num_traces, observe=None, seed=0, likelihood_importance=1., *args, **kwargs):
         """posterior_results(IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK) with the particles sharded over the ranks of the

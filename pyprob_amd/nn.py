@@ -252,6 +252,10 @@ class InferenceNetworkLSTM:
     def _infer_init(self, observe=None):
         """inference_network.py:141-148"""
         self._infer_observe = observe
+        if getattr(observe, 'matrix', None) is not None:      # state.GroupObserves: M observations, one embedding row each
+            self._is.init_batch(observe.matrix)
+            self._infer_prev_addr_id = None
+            return
         vals = []
         for name in self._obs_names:
             vals.extend(torch.as_tensor(observe[name], dtype=torch.float32).reshape(-1).tolist())
@@ -326,6 +330,8 @@ class InferenceNetworkLSTM:
         from .state import ParticleTensor
         if distribution.name == 'Mixture':      # no proposal layer exists for it (inference_network_lstm.py:68)
             raise RuntimeError('Distribution currently unsupported: {}'.format(distribution.name))
+        if getattr(ls, 'batched', False):       # M observations in one call: every group has its own proposal
+            return ls.batch_statement(self, address, distribution)
         spec = self._engine.spec
         runner = ls.runner
         j = ls.statement

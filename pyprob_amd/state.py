@@ -578,6 +578,156 @@ class PriorISState(LockStepState):
         return None
 
 
+class BatchUnsupported(Exception):
+    """Internal: the program did something the batched fast path (Model.posterior_results_batch) does not serve; the caller
+    falls back to one posterior_results call per observation."""
+
+
+class GroupTensor(ParticleTensor):
+    """An observed value of a batched lock-step call: [M], one value per group. It may be passed on (as the value of an observe
+    or a sample statement) and asked for its metadata; anything that computes with it is outside the fast path. (A subclass of
+    ParticleTensor so that torch asks THIS class first when an expression mixes the two: `mu - obs` raises BatchUnsupported, not a
+    shape error of [M N] against [M].)"""
+
+    def __bool__(self):
+        raise BatchUnsupported('an observed value is read by the program (bool)')
+
+    _METADATA = frozenset(('__get__', 'as_subclass', 'numel', 'size', 'dim', 'is_contiguous', 'data_ptr', 'stride', 'storage_offset',
+                           'element_size', 'nelement', '__len__', 'ndimension', 'is_floating_point', 'is_complex'))
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        if getattr(func, '__name__', '') in cls._METADATA:
+            with torch._C.DisableTorchFunctionSubclass():
+                return func(*args, **(kwargs or {}))
+        raise BatchUnsupported('an observed value is read by the program (%s)' % getattr(func, '__name__', func))
+
+
+class GroupObserves(dict):
+    """The observe dict of a batched call: name -> GroupTensor [M]; `matrix` [M, obs_width] holds the rows
+    InferenceNetwork._infer_init embeds (the observables' values in the network's order)."""
+    matrix = None
+
+
+class BatchLockStepState(LockStepState):
+    """M groups of n_per particles through ONE lock-step execution of forward() (Model.posterior_results_batch): particle
+    i = g n_per + j belongs to group g and sees observation g. Served: one controlled sample statement on a mixture head, drawn
+    from the group's own proposal (ISRunner.first_batch), and scalar ScalarTerm observes whose operands are shared, per particle
+    or per group (ISRunner.fused_groups). The first thing outside that raises BatchUnsupported."""
+    batched = True
+
+    def __init__(self, runner, n_groups, n_per, seed, offset):
+        self.n_groups, self.n_per = int(n_groups), int(n_per)
+        self.group_stats = None          # device double [M, 6] of the final flush
+        self.n_terms_total = 0
+        super().__init__(runner, self.n_groups * self.n_per, seed, offset)
+        self.by_rows = False
+        self.plan_ok = False
+
+    def branch(self, cond):
+        raise BatchUnsupported('a branch on a per-particle condition')
+
+    def prior_statement(self, address, distribution):
+        raise BatchUnsupported('a sample statement drawn from its prior')
+
+    def batch_statement(self, net, address, distribution):
+        """The controlled sample statement of the trace (InferenceNetwork._infer_step_lockstep hands over here): the network
+        part for the M observations now, the draw deferred to the fused pass."""
+        spec, runner = net._engine.spec, self.runner
+        if self.statement > 0 or self.draw is not None:
+            raise BatchUnsupported('a second controlled sample statement')
+        self.statement += 1
+        if address not in spec.address_id:
+            raise BatchUnsupported('an address without proposal layers')
+        a = spec.address_id[address]
+        info = spec.addresses[a]
+        prior = net._prior_tensor(distribution)
+        prior_term = runner.dist_term(distribution)
+        if not (info.dist_name in ('Normal', 'Uniform', 'Poisson') and distribution.name == info.dist_name and prior is not None and
+                prior.numel() == 2 and type(prior_term).__name__ == 'ScalarTerm'):
+            raise BatchUnsupported('a head pp_is_fused does not draw from, or per-particle prior parameters')
+        runner.first_batch(a)
+        values = torch.empty(self.n, dtype=torch.float32, device=runner.dev)
+        self.draw = dict(addr=a, prior=prior, values=values, seed=self.seed, prior_term=prior_term)   # (statement 0 of path 0)
+        self.log.append({address: (values, a)})
+        runner.prev_value = runner.last_value = values
+        self.prev_addr_id = a
+        return ParticleTensor.wrap(values)
+
+    def batch_likelihood(self, distribution, value):
+        """An observe (or an observed sample): a scalar ScalarTerm whose value is one number, one per group or one per particle."""
+        self.observes += 1
+        term = self.runner.dist_term(distribution)
+        if term is None or type(term).__name__ != 'ScalarTerm':
+            raise BatchUnsupported('a likelihood that is not a scalar ScalarTerm')
+        if isinstance(value, GroupTensor):
+            v = value.as_subclass(torch.Tensor)
+        elif not torch.is_tensor(value) or (value.device.type == 'cpu' and value.numel() == 1):
+            v = self.runner._const(float(value))
+        else:
+            v = torch.as_tensor(value, dtype=torch.float32).as_subclass(torch.Tensor).reshape(-1).to(self.runner.dev).contiguous()
+            if v.numel() not in (1, self.n):
+                raise BatchUnsupported('a vector-valued observe')
+        self.n_terms_total += 1
+        if self.n_terms_total > 8:
+            raise BatchUnsupported('more than 8 observes')
+        self.terms.append((term, v, float(_likelihood_importance), isinstance(value, GroupTensor)))
+        if len(self.terms) >= 7:
+            self.flush()
+
+    def defer_term(self, term, x, scale, source=None):
+        raise BatchUnsupported('a term outside the batched pass')
+
+    def _code(self, t, grouped, rows=1):
+        """Operand code of a term tensor: 0 shared, 1 per particle, 2 per group."""
+        if t is None or t.numel() == rows:
+            return 0
+        if grouped and t.numel() == self.n_groups * rows:
+            return 2
+        if t.numel() == self.n * rows:
+            return 1
+        raise BatchUnsupported('a term operand of %d elements' % t.numel())
+
+    def flush(self, final=False):
+        draw, terms = self.draw, self.terms
+        if draw is None and not terms and not final:
+            return None
+        self.flushes += 1
+        self.draw, self.terms = None, []
+        value = draw['values'] if draw is not None else None
+        vptr = None if value is None else value.data_ptr()
+
+        def is_value(t):
+            return vptr is not None and t is not None and t.numel() == self.n and t.data_ptr() == vptr
+        fterms = []
+        if draw is not None:      # + log p(v) of the program's own prior (state.py:211); - log q(v) is part of the draw
+            kind, p0, s0, p1, s1 = draw['prior_term']
+            fterms.append(((kind, p0, self._code(p0, False, s1 if kind == 5 else 1), p1, s1 if kind == 5 else self._code(p1, False)),
+                           None, 0, 1.0, 4))
+        for (kind, p0, s0, p1, s1), x, scale, grouped in terms:
+            fl = (1 if is_value(p0) else 0) | (2 if is_value(p1) else 0) | (4 if is_value(x) else 0)
+            # (a parameter is shared or per particle - the program cannot compute with an observed value; x may be per group)
+            fterms.append(((kind, p0, self._code(p0, False, s1 if kind == 5 else 1), p1, s1 if kind == 5 else self._code(p1, False)),
+                           x, self._code(x, grouped), scale, fl))
+        stats_x = value if value is not None else getattr(self, 'stats_values', None)
+        want_stats = final and stats_x is not None
+        if draw is None and not fterms and not want_stats:
+            return None
+        if stats_x is None:       # terms only, after an earlier flush drew: the values are read by flagged operands alone - never lw itself
+            stats_x = self.runner.last_value
+            if stats_x is None or stats_x.numel() != self.n or not stats_x.is_contiguous():
+                stats_x = torch.empty(self.n, dtype=torch.float32, device=self.dev)
+        out = self.runner.fused_groups(None if draw is None else draw['addr'], self.n_per, None if draw is None else draw['prior'],
+                                       fterms, stats_x, self._lw, not self._lw_valid,
+                                       seed=0 if draw is None else draw['seed'], offset=self.offset, stats=want_stats)
+        if draw is not None or fterms:
+            self._lw_valid = True
+        if want_stats:
+            self.group_stats = out
+            self.final_stats_of = (stats_x.data_ptr(), stats_x.numel())
+        return out
+
+
 def _inflate(distribution):
     """state._inflate, pyprob/state.py:87-93: with prior inflation the VALUE of a Normal is drawn with 3x the standard
     deviation and that of a Categorical uniformly; the variable keeps the original distribution (the prior parameters
@@ -949,6 +1099,8 @@ def _lock_step_likelihood(distribution, value, obs_name=None):
     """lw += likelihood_importance * log p(value | .) for the active particles of a lock-step IS run (state.py:147-149;
     also the 'Variable is observed' branch of state.sample, :175-180). A replayed prefix has already been scored."""
     ls = _lock_step
+    if getattr(ls, 'batched', False):       # M observations in one call: the value may be one per group (BatchLockStepState)
+        return ls.batch_likelihood(distribution, value)
     if not torch.is_tensor(value) or (value.device.type == 'cpu' and value.numel() == 1):
         v = ls.runner._const(float(value))       # cached device scalar (no host-to-device copy per statement)
     else:
@@ -1029,6 +1181,8 @@ def factor(log_prob=None, log_prob_func=None, name=None, address=None):
 
 def _lock_step_factor(distribution, value):
     ls = _lock_step
+    if getattr(ls, 'batched', False):
+        raise BatchUnsupported('a factor')
     ls.observes += 1
     if ls.observes <= ls.replay_observes:
         return
