@@ -538,8 +538,8 @@ int pp_is_fused(const pp_net* net, int32_t addr_id, int32_t n, const float* prio
  * pyprob/nn/inference_network_lstm.py:82-134, inference_network_feedforward.py:52-66; state.sample / state.observe score one
  * trace at a time, pyprob/state.py:118-155, 203-219; Empirical reduces one posterior, pyprob/distributions/empirical.py:298-309,
  * 451-466, 758-766): posteriors for M observations are M calls there, and M pp_is_first_statement + pp_is_fused pairs here.
- *   pp_is_batch_workspace_bytes  scratch of the two calls below for n_groups observations (no zero-fill needed; independent of
- *                       n_per).
+ *   pp_is_batch_workspace_bytes  scratch of the calls below (and of pp_is_batch_bias / pp_is_statement_groups, whose weight images
+ *                       lie at its end) for n_groups observations (no zero-fill needed; independent of n_per).
  *   pp_is_batch_first   _infer_init + _infer_step(prev_variable = None) + the proposal layer of `addr_id` for M DIFFERENT
  *                       observations: obs dev [M, obs_width] (the observables' values in the network's order), y_out dev
  *                       [M, ldy] (ldy a multiple of 4, >= the head's n_out) receives the head outputs - row g is what
@@ -560,8 +560,11 @@ int pp_is_fused(const pp_net* net, int32_t addr_id, int32_t n, const float* prio
  *                       order that depends on n_per alone - bit-identical from run to run and between an M-group call and the
  *                       one-group call on the same particles. At most 8 terms, any n_per >= 1; 8 bytes per particle are
  *                       written, the statistics read them once more. `net` is required (also without a draw). Of the
- *                       workspace only the first PP_IS_GROUP_STATS_BYTES(n_groups) bytes are used, and only with stats_out. */
+ *                       workspace only the first PP_IS_GROUP_STATS_BYTES(n_groups) bytes are used, and only with stats_out.
+ *                       overwrite | PP_GROUPS_PRIOR_PER_PARTICLE: `prior` is dev [M n_per, 2], one pair per particle (a later
+ *                       statement of a FeedForward network whose prior depends on an earlier draw). */
 #define PP_IS_GROUP_STATS_BYTES(m) ((size_t)((m) > 256 ? (m) : 256) * 48)
+#define PP_GROUPS_PRIOR_PER_PARTICLE 2
 size_t pp_is_batch_workspace_bytes(const pp_net* net, int32_t n_groups);
 int pp_is_batch_first(const pp_net* net, const float* params, const float* obs /*dev [M, obs_width]*/, int32_t addr_id, int32_t n_groups,
                       float* y_out /*dev [M, ldy]*/, int64_t ldy, float* h_out, float* c_out /*dev [M, H] or NULL*/, void* workspace,
@@ -570,6 +573,43 @@ int pp_is_fused_groups(const pp_net* net, int32_t addr_id, int32_t n_groups, int
                        const float* prior /*dev [2]*/, const pp_lw_term* terms, const int32_t* term_flags, int32_t n_terms,
                        float* value /*dev [M n_per]*/, float* lw /*dev [M n_per]*/, int32_t overwrite, uint64_t seed, uint64_t offset,
                        double* stats_out /*dev double [M, 6] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Later statements of a batched posterior call: the second, third, ... controlled sample statement of a straight-line program for
+ * all M n_per particles at once. The reference runs one _infer_step per trace and statement (InferenceNetworkLSTM._infer_step
+ * pyprob/nn/inference_network_lstm.py:82-134: the LSTM input row [E | s_prev | d_prev | a_prev | d_cur | a_cur] :116-121, one
+ * nn.LSTM step :123-125, the proposal layer :127-131; state.sample's IC branch pyprob/state.py:203-219; Mixture.sample / log_prob
+ * pyprob/distributions/mixture.py:38-63) inside one posterior call per observation (pyprob/model.py:106-117).
+ *   pp_is_batch_bias    the per-group part of the gate pre-activations of statement (addr_id, prev_addr_id >= 0): bias_out dev
+ *                       [M, 4H], row g = b_ih + b_hh + W_ih[:, shared columns] [E_g | 0 | d_prev | a_prev | d_cur | a_cur]
+ *                       (+ h_prev[g] W_hh^T with h_prev dev [M, H]: the second statement, whose previous state is one row per
+ *                       group). E_g are embedding rows the LAST pp_is_batch_first call left in `workspace` (kept, not recomputed):
+ *                       that call embedded ws_groups observations, this one serves rows [first_group, first_group + n_groups)
+ *                       of them - a caller that shards a call over groups embeds once and takes its slices, so that a shard's
+ *                       rows do not depend on the shard's size (the GEMMs of pp_is_batch_first pick their shape by the row
+ *                       count). One launch on a (gate column, group) grid running pp_is_step's own bias
+ *                       code: the products and their order are those of the single call and do not depend on M. One-layer LSTM,
+ *                       FEEDFORWARD observe embeddings, a mixture head at addr_id (the only consumer is the call below).
+ *   pp_is_statement_groups  the whole statement as ONE launch of the grouped fused statement kernel, whatever n_per: particle
+ *                       i = g n_per + j starts from bias row g (`bias` dev [M, 4H]); c0 != NULL (dev [M, H]): every particle of
+ *                       group g has the previous state (h_g, c_g) - h_g W_hh^T is part of bias row g, the cell reads c0[g] and
+ *                       (h, c) dev [M n_per, H] are only written; c0 == NULL: (h, c) hold every particle's own previous state and
+ *                       are updated in place. prev_value dev [M n_per] (the previous statement's draws), prior dev [2]
+ *                       (prior_stride 0) or [M n_per, 2] (prior_stride 1: a prior that depends on an earlier draw), prior_kind 0
+ *                       Normal / 1 Uniform; value[i] = the draw (Philox counter offset + i, key and stream of pp_is_step: an M-group
+ *                       call consumes exactly the counters of M one-group calls at offset + g n_per), lw[i] += log p(v) - log q(v)
+ *                       as pp_is_statement_rows does. y_out: NULL or dev [M n_per, ldy], a copy of the head outputs. PP_EINVAL
+ *                       without a launch when the network has no fused statement kernel for the address (H = 1024, depth > 1, heads
+ *                       wider than 32 outputs) or the head is not a Normal / Uniform mixture head. The workspace is
+ *                       pp_is_batch_workspace_bytes(n_groups): the fragment images of W_hh, W1, W2 are written there per call. */
+int pp_is_batch_bias(const pp_net* net, const float* params, int32_t addr_id, int32_t prev_addr_id, int32_t n_groups,
+                     int32_t ws_groups, int32_t first_group, const float* h_prev /*dev [M, H] or NULL*/,
+                     float* bias_out /*dev [M, 4H]*/, void* workspace, size_t workspace_bytes, void* stream);
+int pp_is_statement_groups(const pp_net* net, const float* params, int32_t addr_id, int32_t prev_addr_id, int32_t n_groups,
+                           int32_t n_per, const float* bias /*dev [M, 4H]*/, const float* c0 /*dev [M, H] or NULL*/,
+                           const float* prev_value /*dev [M n_per]*/, const float* prior, int32_t prior_stride, float* h, float* c,
+                           float* value /*dev [M n_per]*/, float* lw /*dev [M n_per]*/, int32_t prior_kind, uint64_t seed, uint64_t offset,
+                           float* y_out /*dev [M n_per, ldy] or NULL*/, int64_t ldy, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared

@@ -7,10 +7,15 @@
 //                       the training step's forward at T = 1: embedding GEMMs, input gather, gate GEMM, cell, head GEMMs), and
 //   pp_is_fused_groups  is pp_is_fused's pass with the proposal of particle i read from row i / n_per of the head outputs and
 //                       per-group operands, followed by the importance statistics of every group.
+//   pp_is_batch_bias    writes, for a LATER statement (prev_addr_id >= 0), the bias row of every group: what is_prep_kernel computes
+//                       for the one observation of a single call, on the M embedding rows pp_is_batch_first left in the workspace, and
+//   pp_is_statement_groups  runs that statement for all M n_per particles as ONE launch of the GROUPED fused statement kernel
+//                       (is_step_fused.hip, is_step_small.hip): particle i starts from bias row i / n_per.
 // Draw and log-density arithmetic is is_draw.hpp's (mixture_particle, term_log_prob) and head_math.hpp's: nothing is restated.
 #include "common.hpp"
 #include "gather.hpp"
 #include "is_draw.hpp"
+#include "is_step_fused.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -55,7 +60,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void is_fused_groups_kernel(const float* __restrict__ y, int64_t ldy, const float* __restrict__ prior,
                                                               int64_t total, int n_per, int K, const GroupTerms terms,
                                                               float* __restrict__ value, float* __restrict__ lw, int overwrite,
-                                                              uint64_t seed, uint64_t offset) {
+                                                              uint64_t seed, uint64_t offset, int prior_per_particle) {
     float pa = 0.0f, pb = 1.0f;
     if constexpr (KIND >= 0) {
         pa = prior[0];
@@ -69,6 +74,10 @@ __global__ __launch_bounds__(256) void is_fused_groups_kernel(const float* __res
             v = value[i];
         } else {
             float lq;
+            if (prior_per_particle) {      // a later statement whose prior depends on an earlier draw: [M n_per, 2]
+                pa = prior[2 * i];
+                pb = prior[2 * i + 1];
+            }
             mixture_particle<KIND>(y + g * ldy, pa, pb, K, false, 0.0f, seed, offset + (uint64_t)i, v, lq);
             acc -= lq;                 // - log q(v)   (state.py:212, 217)
             value[i] = v;
@@ -164,6 +173,7 @@ struct BatchWorkspace {
     double* partial;          // FIRST: pp_is_fused_groups needs nothing else
     float *oh0, *oh1, *cat, *f1, *E, *X, *G, *A1, *h, *c;
     int64_t e4, i4, hid4, out4, ohid4;
+    IsFusedBuffers fz;        // LAST: the fragment images of pp_is_statement_groups (empty: no fused statement kernel for this network)
     size_t bytes;
 };
 
@@ -201,6 +211,10 @@ void batch_carve(const pp_net* net, int M, void* p, BatchWorkspace& w) {
     w.A1 = takef(M * w.hid4);
     w.h = takef((int64_t)M * H);
     w.c = takef((int64_t)M * H);
+    is_fused_carve_sizes(net, w.fz);
+    w.fz.whh = takef(w.fz.n_whh);
+    w.fz.w1 = takef(w.fz.n_w1);
+    w.fz.w2 = takef(w.fz.n_w2);
     w.bytes = off + 256;
 }
 
@@ -327,10 +341,12 @@ int is_fused_groups(const pp_net* net, int addr_id, int M, int n_per, const floa
     }
     if (M == 0) return 0;
     const int64_t total = (int64_t)M * n_per;
+    const int prior_pp = (overwrite & PP_GROUPS_PRIOR_PER_PARTICLE) ? 1 : 0;
+    overwrite &= 1;
     const int blocks = (int)std::min<int64_t>(GROUP_BLOCKS, (total + 255) / 256);
 #define PP_GROUPS_LAUNCH(KIND)                                                                                              \
     hipLaunchKernelGGL(is_fused_groups_kernel<KIND>, dim3(blocks), dim3(256), 0, st, y, ldy, prior, total, n_per, K, t, value, lw, \
-                       overwrite, seed, offset)
+                       overwrite, seed, offset, prior_pp)
     if (kind < 0) PP_GROUPS_LAUNCH(-1);
     else if (kind == 0) PP_GROUPS_LAUNCH(0);
     else if (kind == 1) PP_GROUPS_LAUNCH(1);
@@ -353,6 +369,145 @@ int is_fused_groups(const pp_net* net, int addr_id, int M, int n_per, const floa
     }
     PP_LAUNCH_CHECK("pp_is_fused_groups(statistics)");
     return 0;
+}
+
+// ---- later statements of a batched call ---------------------------------------------------------------------------------------
+// The bias rows of statement (addr_id, prev_addr_id >= 0) for the groups: is_prep_kernel's bias code (is_step_fused.hip) on a grid
+// of (gate columns, groups) - the same products in the same order as the single call's row, so a group's row does not depend on
+// how many groups the call has. A workgroup serves four gate columns (one wave each) x BIAS_GROUPS groups: the weight rows are read
+// once for all of them.
+constexpr int BIAS_GROUPS = 4;
+
+struct BiasArgs {
+    const float* P;
+    const int64_t* at;
+    int64_t w_ih, w_hh, b_ih, b_hh;
+    int H, I, M;
+    GatherDims d;
+    int addr_id, prev_addr;
+    const float* E; int64_t lde;      // [M][lde] observe embeddings
+    const float* h_prev;              // [M][H] or nullptr
+    float* bias;                      // [M][4 H]
+};
+
+__global__ __launch_bounds__(256) void batch_bias_kernel(const BiasArgs a) {
+    __shared__ float sx[BIAS_GROUPS][1024 + 1024];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int H = a.H;
+    const int g0 = (int)blockIdx.y * BIAS_GROUPS, ng = min(BIAS_GROUPS, a.M - g0);
+    const int n = (int)blockIdx.x * 4 + wave;      // gate column (4 H is a multiple of 4)
+    const int c1 = a.d.e_obs, c2 = c1 + a.d.smp;
+    const float* wi = a.P + a.w_ih + (int64_t)n * a.I;
+    float acc[BIAS_GROUPS];
+#pragma unroll
+    for (int q = 0; q < BIAS_GROUPS; ++q) acc[q] = 0.0f;
+    if (a.h_prev)
+        for (int e = tid; e < ng * H; e += 256) sx[e / H][1024 + e % H] = a.h_prev[(int64_t)g0 * H + e];
+    for (int base = 0; base < a.I; base += 1024) {
+        const int cnt = min(1024, a.I - base);
+        if (base) __syncthreads();      // the previous chunk has been consumed
+        for (int kk = tid; kk < cnt; kk += 256) {
+            const int k = base + kk;
+            const bool obs = k < c1;
+            const float shared = (obs || k < c2) ? 0.0f : gather_embedding_elem(a.d, a.P, a.at, k, a.prev_addr, 0.0f, a.addr_id);
+            for (int q = 0; q < ng; ++q) sx[q][kk] = obs ? a.E[(int64_t)(g0 + q) * a.lde + k] : shared;
+        }
+        __syncthreads();
+        for (int kk = lane; kk < cnt; kk += 64) {
+            const float w = wi[base + kk];
+#pragma unroll
+            for (int q = 0; q < BIAS_GROUPS; ++q)
+                if (q < ng) acc[q] += w * sx[q][kk];
+        }
+    }
+    if (a.h_prev) {
+        const float* wh = a.P + a.w_hh + (int64_t)n * H;
+        for (int k = lane; k < H; k += 64) {
+            const float w = wh[k];
+#pragma unroll
+            for (int q = 0; q < BIAS_GROUPS; ++q)
+                if (q < ng) acc[q] += w * sx[q][1024 + k];
+        }
+    }
+    const float b = a.P[a.b_ih + n] + a.P[a.b_hh + n];
+#pragma unroll
+    for (int q = 0; q < BIAS_GROUPS; ++q) {
+        const float r = wave_sum(acc[q]);
+        if (q < ng && lane == 0) a.bias[(int64_t)(g0 + q) * 4 * H + n] = r + b;
+    }
+}
+
+int is_batch_bias(const pp_net* net, const float* P, int addr_id, int prev_addr_id, int M, int ws_groups, int first_group,
+                  const float* h_prev, float* bias_out, void* ws, size_t ws_bytes, hipStream_t st) {
+    PP_CHECK_ARG(net && P && bias_out && ws, "pp_is_batch_bias: null pointer");
+    PP_CHECK_ARG(batch_net_ok(net) && net->lstm_dim > 0 && net->lstm_dim <= 1024 && net->addr_table,
+                 "pp_is_batch_bias: FEEDFORWARD observe embeddings and an LSTM of depth 1 with at most 1024 hidden units");
+    PP_CHECK_ARG(addr_id >= 0 && addr_id < net->n_addr && prev_addr_id >= 0 && prev_addr_id < net->n_addr,
+                 "pp_is_batch_bias: a statement after the first one (address ids in range, prev_addr_id >= 0)");
+    PP_CHECK_ARG(M >= 0 && first_group >= 0 && (int64_t)first_group + M <= ws_groups,
+                 "pp_is_batch_bias: groups [first_group, first_group + n_groups) of the ws_groups rows pp_is_batch_first embedded");
+    {
+        const int kind = net->addrs[addr_id].kind;
+        PP_CHECK_ARG(kind == PP_HEAD_NORMAL_MIXTURE || kind == PP_HEAD_TRUNCNORMAL_MIXTURE,
+                     "pp_is_batch_bias: Normal / Uniform statements (mixture heads) only: the rows are pp_is_statement_groups' operand");
+    }
+    if (M == 0) return 0;
+    BatchWorkspace w;
+    batch_carve(net, ws_groups, ws, w);      // (as the pp_is_batch_first call carved it: that is where its embedding rows are)
+    if (w.bytes > ws_bytes) {
+        set_error("pp_is_batch_bias: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
+        return PP_ENOSPACE;
+    }
+    BiasArgs a{};
+    a.P = P; a.at = net->addr_table;
+    a.w_ih = net->w_ih; a.w_hh = net->w_hh; a.b_ih = net->b_ih; a.b_hh = net->b_hh;
+    a.H = net->lstm_dim; a.I = net->lstm_in; a.M = M;
+    a.d = GatherDims{net->e_obs, net->smp_dim, net->dtype_dim, net->addr_dim, net->lstm_in};
+    a.addr_id = addr_id; a.prev_addr = prev_addr_id;
+    a.E = w.E + (int64_t)first_group * w.e4; a.lde = w.e4;
+    a.h_prev = h_prev; a.bias = bias_out;
+    for (int g0 = 0; g0 < M; g0 += 65535 * BIAS_GROUPS) {
+        const int groups = std::min(M - g0, 65535 * BIAS_GROUPS);
+        BiasArgs q = a;
+        q.M = groups;
+        q.E = a.E + (int64_t)g0 * a.lde;
+        q.h_prev = h_prev ? h_prev + (int64_t)g0 * a.H : nullptr;
+        q.bias = bias_out + (int64_t)g0 * 4 * a.H;
+        hipLaunchKernelGGL(batch_bias_kernel, dim3(a.H, cdiv(groups, BIAS_GROUPS)), dim3(256), 0, st, q);
+    }
+    PP_LAUNCH_CHECK("pp_is_batch_bias");
+    return 0;
+}
+
+int is_batch_statement_groups(const pp_net* net, const float* P, int addr_id, int prev_addr_id, int M, int n_per, const float* bias,
+                              const float* c0, const float* prev_value, const float* prior, int prior_stride, float* h, float* c,
+                              float* value, float* lw, int prior_kind, uint64_t seed, uint64_t offset, float* y_out, int64_t ldy,
+                              void* ws, size_t ws_bytes, hipStream_t st) {
+    PP_CHECK_ARG(net && P && bias && prev_value && prior && h && c && value && lw && ws, "pp_is_statement_groups: null pointer");
+    PP_CHECK_ARG(M >= 0 && n_per >= 1, "pp_is_statement_groups: n_groups >= 0 and n_per >= 1");
+    PP_CHECK_ARG(addr_id >= 0 && addr_id < net->n_addr && prev_addr_id >= 0 && prev_addr_id < net->n_addr,
+                 "pp_is_statement_groups: a statement after the first one (address ids in range, prev_addr_id >= 0)");
+    PP_CHECK_ARG((prior_kind == 0 || prior_kind == 1) && (prior_stride == 0 || prior_stride == 1),
+                 "pp_is_statement_groups: Normal (0) or Uniform (1) prior, one shared pair (stride 0) or one pair per particle (1)");
+    const pp_addr& ad = net->addrs[addr_id];
+    PP_CHECK_ARG((ad.kind == PP_HEAD_NORMAL_MIXTURE || ad.kind == PP_HEAD_TRUNCNORMAL_MIXTURE) && ad.n_out % 3 == 0 && ad.n_out / 3 <= MAXK,
+                 "pp_is_statement_groups: Normal / Uniform statements (mixture heads) only");
+    PP_CHECK_ARG(is_statement_groups_supported(net, addr_id),
+                 "pp_is_statement_groups: no fused statement kernel for this network and address (one-layer LSTM of H = 32 .. 512, head of at "
+                 "most 32 outputs)");
+    PP_CHECK_ARG(!y_out || ldy >= ad.n_out, "pp_is_statement_groups: ldy is smaller than the head's %d outputs", ad.n_out);
+    PP_CHECK_ARG((int64_t)M * n_per * net->lstm_dim < (int64_t(1) << 32) && (int64_t)M * n_per <= 0x7fffffff,
+                 "pp_is_statement_groups: more than 2^32 state elements per call: shard the groups");
+    if (M == 0) return 0;
+    BatchWorkspace w;
+    batch_carve(net, M, ws, w);
+    if (w.bytes > ws_bytes) {
+        set_error("pp_is_statement_groups: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
+        return PP_ENOSPACE;
+    }
+    const IsStatementOut whole{value, lw, prior_kind};
+    return is_statement_groups(net, P, addr_id, prev_addr_id, M, n_per, bias, c0, prev_value, prior, prior_stride, h, c, whole, seed,
+                               offset, w.fz, y_out, ldy, st);
 }
 
 }  // namespace pp
@@ -378,6 +533,22 @@ int pp_is_fused_groups(const pp_net* net, int32_t addr_id, int32_t n_groups, int
                        size_t workspace_bytes, void* stream) {
     return pp::is_fused_groups(net, addr_id, n_groups, n_per, y, ldy, prior, terms, term_flags, n_terms, value, lw, overwrite, seed,
                                offset, stats_out, workspace, workspace_bytes, pp::as_stream(stream));
+}
+
+int pp_is_batch_bias(const pp_net* net, const float* params, int32_t addr_id, int32_t prev_addr_id, int32_t n_groups,
+                     int32_t ws_groups, int32_t first_group, const float* h_prev, float* bias_out, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+    return pp::is_batch_bias(net, params, addr_id, prev_addr_id, n_groups, ws_groups, first_group, h_prev, bias_out, workspace,
+                             workspace_bytes, pp::as_stream(stream));
+}
+
+int pp_is_statement_groups(const pp_net* net, const float* params, int32_t addr_id, int32_t prev_addr_id, int32_t n_groups,
+                           int32_t n_per, const float* bias, const float* c0, const float* prev_value, const float* prior,
+                           int32_t prior_stride, float* h, float* c, float* value, float* lw, int32_t prior_kind, uint64_t seed,
+                           uint64_t offset, float* y_out, int64_t ldy, void* workspace, size_t workspace_bytes, void* stream) {
+    return pp::is_batch_statement_groups(net, params, addr_id, prev_addr_id, n_groups, n_per, bias, c0, prev_value, prior, prior_stride,
+                                         h, c, value, lw, prior_kind, seed, offset, y_out, ldy, workspace, workspace_bytes,
+                                         pp::as_stream(stream));
 }
 
 }  // extern "C"

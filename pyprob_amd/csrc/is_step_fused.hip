@@ -213,6 +213,9 @@ struct FusedArgs {
     // wide LSTM launch (KM > 1): the new hidden rows go to hout [n][H K-extent] (compact); panels = workgroups per part
     float* hout;
     int panels;
+    // grouped statement (GROUPED, pp_is_statement_groups): particle i belongs to group i / n_per; bias is a block [groups][4 H] (row g:
+    // the bias row of group g's observation) and, with SHARED, c0 a block [groups][H] (the state pp_is_batch_first left for group g)
+    int n_per;
 };
 
 extern __shared__ __attribute__((aligned(1024))) float fused_lds[];
@@ -229,8 +232,11 @@ extern __shared__ __attribute__((aligned(1024))) float fused_lds[];
 // accumulators; workgroups [part * panels, (part + 1) * panels) take part `part`. c is updated in place (a part reads and writes
 // only its own units); the new h goes to a.hout ([n][HK], compact) because the other parts still read the old rows; the kernel
 // ends after the cell (the head layers and the draw run as the chain's launches, is_kernels.hip is_step).
-template <int UB, int KIND, bool SHARED, bool HEADONLY = false, int KM = 1>
+// GROUPED: the statement of a batched posterior call (is_batch.hip): M groups of n_per particles, one bias row (and, SHARED, one
+// previous state row) per group instead of one for everybody; no row list. A template parameter for the reason SHARED is one.
+template <int UB, int KIND, bool SHARED, bool HEADONLY = false, int KM = 1, bool GROUPED = false>
 __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
+    static_assert(!GROUPED || (!HEADONLY && KM == 1), "the grouped statement is the one-kernel statement");
     constexpr int H = 256 * UB;                    // hidden units of this workgroup
     constexpr int HK = H * KM;                     // hidden units of the LSTM: K extent of the recurrent product, state row pitch
     constexpr int NSH = H / 8;
@@ -243,6 +249,7 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
     float* sA1 = UB == 4 ? sH + 8192 : sH + NSH * 256;   // [ns2][64][4]: head layer 1 activations as A fragments
     float* sY = UB == 4 ? sH + NSH * 256 : sA1 + a.ns2 * 256;   // [32][33] head outputs
     int* sRow = reinterpret_cast<int*>(KM > 1 ? fused_lds : sY + FR * 33);   // [32] state row of every particle of the panel
+    int* sGrp = sRow + FR;                         // GROUPED: [32] group of every particle of the panel
     float* sPart = sH;                             // [8][32][32] K-split partials of head layer 2 (the tile is dead by then)
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -260,7 +267,8 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
     FUSED_STAMP(0);
     if (tid < FR) {
         const int gr = min(m0 + tid, a.n - 1);
-        sRow[tid] = a.rows ? (int)a.rows[gr] : gr;
+        sRow[tid] = (!GROUPED && a.rows) ? (int)a.rows[gr] : gr;
+        if constexpr (GROUPED) sGrp[tid] = gr / a.n_per;
     }
     if constexpr (HEADONLY) {
         __syncthreads();   // sRow
@@ -274,17 +282,38 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
         }
     } else {
     const int gr = min(m0 + c31, a.n - 1);              // this lane's particle (A operand row)
-    const int64_t ridx = a.rows ? a.rows[gr] : (int64_t)gr;
+    const int64_t ridx = (!GROUPED && a.rows) ? a.rows[gr] : (int64_t)gr;
     const float* arow = a.h + ridx * HK + 4 * hh;
     const float* bimg = a.whh_img + (size_t)part * ((size_t)(NSK + 1) * SLAB) + (size_t)wave * (NB * 256) + lane * 4;
 
     f32x16 acc[NB];
+    // GROUPED: first and last group of the panel (workgroup-uniform; equal for every panel when n_per is a multiple of 32, for all
+    // but one panel in n_per / 32 otherwise)
+    const int g_lo = GROUPED ? m0 / a.n_per : 0;
+    const int g_hi = GROUPED ? min(m0 + FR - 1, a.n - 1) / a.n_per : 0;
+    const bool one_group = g_lo == g_hi;
+    if constexpr (!GROUPED) {
 #pragma unroll
-    for (int blk = 0; blk < NB; ++blk) {
-        const int g = blk / UB, ub = blk % UB;
-        const float b = a.bias[g * HK + u0 + (wave * UB + ub) * 32 + c31];
+        for (int blk = 0; blk < NB; ++blk) {
+            const int g = blk / UB, ub = blk % UB;
+            const float b = a.bias[g * HK + u0 + (wave * UB + ub) * 32 + c31];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[blk][r] = b;
+            for (int r = 0; r < 16; ++r) acc[blk][r] = b;
+        }
+    } else {
+        // Row i of the panel takes bias row g(i) of the block. The accumulators are NOT initialised behind a branch on "one group
+        // or several": 64 UB registers defined in two arms meet at the join in different physical registers and stay live across
+        // the sample embedding - 106 registers at UB = 1 with the shared state against the ungrouped twin's 96, a wave of
+        // occupancy; adding the rows behind the K loop under such a branch: 150, and spills at UB = 2. They start from zero and
+        // the bias rows enter as a product behind the K loop (where the operand rings are dead): MFMA t has
+        // A = [g(i) == g_lo + 2 t + k] (exactly 1 or 0) and B = bias rows g_lo + 2 t + k, k = 0, 1. The products are exact; only
+        // the place of the bias in the order of the additions differs from the ungrouped kernel's. One MFMA and one load per
+        // block and lane when the panel lies in one group (the ungrouped kernel's loads); a panel over G groups takes G / 2 of
+        // them (n_per = 1: sixteen).
+#pragma unroll
+        for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[blk][r] = 0.0f;
     }
     auto load_blk = [&](int s, int blk) { return *reinterpret_cast<const f32x4*>(bimg + (size_t)s * SLAB + blk * 256); };
     auto load_a = [&](int s) { return *reinterpret_cast<const f32x4*>(arow + 8 * s); };
@@ -348,6 +377,25 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
         FUSED_SLAB(a0, b0, false, 0)
     }
 #undef FUSED_SLAB
+    if constexpr (GROUPED) {      // + the bias rows (see above), behind the K loop: its operand rings are dead here
+        int myg = 0;                                  // group of this lane's A row (particle m0 + c31), relative to g_lo
+        if (!one_group) {
+            __syncthreads();                          // sGrp: computed once per panel row above (the branch is workgroup-uniform)
+            myg = sGrp[c31] - g_lo;
+        }
+        const float* bcol = a.bias + u0 + wave * UB * 32 + c31;
+        for (int t = 0; 2 * t <= g_hi - g_lo; ++t) {
+            const int k = 2 * t + hh;
+            const bool valid = g_lo + k <= g_hi;      // (no load behind the panel's last group: the block ends there)
+            const float av = myg == k ? 1.0f : 0.0f;
+            const float* brow = bcol + (size_t)(g_lo + (valid ? k : 0)) * (4 * HK);
+#pragma unroll
+            for (int blk = 0; blk < NB; ++blk) {
+                const float bv = brow[(blk / UB) * HK + (blk % UB) * 32];
+                acc[blk] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, valid ? bv : 0.0f, acc[blk], 0, 0, 0);
+            }
+        }
+    }
     // Gate activations in place on the accumulators, before the barrier (a wave that is early does them while it would wait):
     // acc[i] <- sigmoid(i) tanh(g), acc[f] <- sigmoid(f), acc[o] <- sigmoid(o); the g accumulators are dead afterwards, which is
     // what keeps the cell phase below the register budget
@@ -378,13 +426,18 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
         for (int q = 0; q < 8; ++q) {
             const int r = 8 * half + q;
             const int row = (r & 3) + 8 * (r >> 2) + 4 * hh;
-            off[q] = (uint32_t)sRow[row] * (uint32_t)HK;
+            // (GROUPED && SHARED: identity rows, and off is only used by the guarded stores - plain arithmetic leaves the registers
+            // to the group offsets of a straddling panel)
+            off[q] = (GROUPED && SHARED) ? (uint32_t)(m0 + row) * (uint32_t)HK : (uint32_t)sRow[row] * (uint32_t)HK;
         }
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub) {
             const uint32_t u = (uint32_t)(u0 + (wave * UB + ub) * 32 + c31);
+            // (SHARED && GROUPED: the group's row of the [groups][H] block - one value for the whole panel when it lies in one
+            // group, as without groups; a straddling panel loads row by row inside the loop below: eight values held at once cost
+            // the UB = 1 kernel a wave of occupancy against its ungrouped twin)
 #pragma unroll
-            for (int q = 0; q < 8; ++q) cp[ub][q] = cprev[SHARED ? u : off[q] + u];
+            for (int q = 0; q < 8; ++q) cp[ub][q] = cprev[SHARED ? (uint32_t)g_lo * (uint32_t)HK + u : off[q] + u];
         }
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub) {
@@ -395,7 +448,11 @@ __global__ __launch_bounds__(512) void is_step_fused_kernel(const FusedArgs a) {
             for (int q = 0; q < 8; ++q) {
                 const int r = 8 * half + q;
                 const int row = (r & 3) + 8 * (r >> 2) + 4 * hh;
-                const float cn = acc[1 * UB + ub][r] * cp[ub][q] + acc[0 * UB + ub][r];
+                float cpq = cp[ub][q];
+                if constexpr (SHARED && GROUPED) {
+                    if (!one_group) cpq = cprev[(uint32_t)sGrp[row] * (uint32_t)HK + (uint32_t)u];
+                }
+                const float cn = acc[1 * UB + ub][r] * cpq + acc[0 * UB + ub][r];
                 const float hn = acc[3 * UB + ub][r] * fast_tanh(cn);
                 if constexpr (KM > 1) {
                     if (m0 + row < a.n) {
@@ -960,6 +1017,87 @@ int is_step_fused(const pp_net* net, const float* P, int addr_id, int prev_addr_
     if (rc) return rc;
     PP_LAUNCH_CHECK("pp_is_step(fused statement)");
     *sampled = kind != 3;   // false: the head outputs are in y_out, the caller's sampling kernel follows
+    return 0;
+}
+
+namespace {
+template <int UB, int KIND, bool SHARED>
+int launch_fused_grouped(const FusedArgs& a, size_t lds, hipStream_t st) {
+    static bool raised = false;
+    if (!raised) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&is_step_fused_kernel<UB, KIND, SHARED, false, 1, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) {
+            set_error("pp_is_statement_groups: cannot raise the LDS limit of the fused statement kernel: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+        raised = true;
+    }
+    hipLaunchKernelGGL((is_step_fused_kernel<UB, KIND, SHARED, false, 1, true>), dim3(cdiv(a.n, FR)), dim3(512), lds, st, a);
+    return 0;
+}
+}  // namespace
+
+bool is_statement_groups_supported(const pp_net* net, int addr_id) {
+    if (!net || std::max(1, (int)net->lstm_depth) != 1) return false;
+    // (small networks: the tuned widths. The run-time-index instantiation - H = 96, 160, 192, 224 - spills already without groups
+    // and more with them: those widths stay with the loop of single calls)
+    if (is_step_small_supported(net, addr_id)) return net->lstm_dim == 32 || net->lstm_dim == 64 || net->lstm_dim == 128;
+    return (net->lstm_dim == 256 || net->lstm_dim == 512) && is_step_fused_supported(net, addr_id);
+}
+
+// The grouped whole statement (pp_is_statement_groups): the fragment images of this address (the image blocks of the prepare
+// launch; the bias rows are the caller's block), then ONE launch of the GROUPED statement kernel, whatever n.
+int is_statement_groups(const pp_net* net, const float* P, int addr_id, int prev_addr_id, int n_groups, int n_per, const float* bias,
+                        const float* c0, const float* prev_value, const float* prior, int prior_stride, float* h, float* c,
+                        const IsStatementOut& whole, uint64_t seed, uint64_t offset, const IsFusedBuffers& f, float* y_out, int64_t ldy,
+                        hipStream_t st) {
+    const int n = n_groups * n_per;
+    if (is_small_network(net))
+        return is_step_small_groups(net, P, addr_id, prev_addr_id, n_groups, n_per, bias, c0, prev_value, prior, prior_stride, h, c, whole,
+                                    seed, offset, f, y_out, ldy, st);
+    const pp_addr& ad = net->addrs[addr_id];
+    const int H = net->lstm_dim, ub = H / 256, nsh = H / 8;
+    PrepArgs p{};
+    p.P = P; p.at = net->addr_table;
+    p.w_ih = net->w_ih; p.w_hh = net->w_hh; p.b_ih = net->b_ih; p.b_hh = net->b_hh; p.w1 = ad.w1; p.w2 = ad.w2;
+    p.H = H; p.I = net->lstm_in; p.ub = ub; p.nsh = nsh; p.hu = H; p.halves = 1;
+    p.d = GatherDims{net->e_obs, net->smp_dim, net->dtype_dim, net->addr_dim, net->lstm_in};
+    p.addr_id = addr_id; p.prev_addr = prev_addr_id;
+    p.hid = ad.hid; p.n_out = ad.n_out; p.nb16 = (ad.hid + 15) / 16; p.ns2 = (ad.hid + 7) / 8;
+    p.whh_img = f.whh; p.w1_img = f.w1; p.w2_img = f.w2;
+    p.q_whh = (int64_t)(nsh + 1) * FW * 4 * ub * 64;
+    p.q_w1 = (int64_t)(H / 16) * p.nb16 * 64;
+    p.q_w2 = (int64_t)p.ns2 * 64;
+    p.img_blocks = (int)std::min<int64_t>(1024, (p.q_whh + p.q_w1 + p.q_w2 + 255) / 256);
+    hipLaunchKernelGGL(is_prep_kernel, dim3(p.img_blocks), dim3(256), 0, st, p);      // (no bias blocks)
+    PP_LAUNCH_CHECK("pp_is_statement_groups(prepare)");
+
+    FusedArgs a{};
+    a.whh_img = f.whh; a.bias = bias;
+    a.h = h; a.c = c; a.c0 = c0; a.state_shared = c0 ? 1 : 0;
+    const pp_addr& pad = net->addrs[prev_addr_id];
+    a.prev_value = prev_value; a.smp_w = P + pad.smp_w; a.smp_b = P + pad.smp_b; a.smp_in = pad.smp_in; a.smp = net->smp_dim;
+    a.w1_img = f.w1; a.b1 = P + ad.b1; a.hid = ad.hid; a.nb16 = p.nb16;
+    a.w2_img = f.w2; a.b2 = P + ad.b2; a.n_out = ad.n_out; a.ns2 = p.ns2;
+    a.y_out = y_out; a.ldy = ldy;
+    a.prior = prior; a.prior_stride = prior_stride;
+    a.seed = seed; a.offset = offset; a.K = ad.n_out / 3; a.n = n; a.n_per = n_per;
+    a.prev_indexed = 1;
+    a.value_full = whole.value_full; a.lw_full = whole.lw_full; a.prior_kind = whole.prior_kind;
+    a.dbg = g_timeline;
+    const size_t lds = ((size_t)nsh * 256 + (size_t)p.ns2 * 256 + FR * 33 + 2 * FR) * sizeof(float);
+    const int kind = ad.kind == PP_HEAD_NORMAL_MIXTURE ? 0 : 1;
+    const double flops = (double)n * (2.0 * (net->lstm_in + (c0 ? 0 : H)) * 4.0 * H + 2.0 * ((double)H * ad.hid + (double)ad.hid * ad.n_out));
+    prof_begin(5, st);
+    int rc;
+#define PP_GROUPED_CASE(U, KD) rc = c0 ? launch_fused_grouped<U, KD, true>(a, lds, st) : launch_fused_grouped<U, KD, false>(a, lds, st)
+    if (ub == 1) { if (kind == 0) PP_GROUPED_CASE(1, 0); else PP_GROUPED_CASE(1, 1); }
+    else { if (kind == 0) PP_GROUPED_CASE(2, 0); else PP_GROUPED_CASE(2, 1); }
+#undef PP_GROUPED_CASE
+    prof_end(5, flops, st);
+    if (rc) return rc;
+    PP_LAUNCH_CHECK("pp_is_statement_groups(fused statement)");
     return 0;
 }
 

@@ -46,6 +46,21 @@ int is_step_small(const pp_net* net, const float* P, int addr_id, int prev_addr_
                   uint64_t offset, const IsFusedBuffers& f, float* y_out, int64_t ldy, bool net_only, bool* sampled, hipStream_t st,
                   const IsStatementOut* whole);
 
+// The statement of a BATCHED posterior call (is_batch.hip): n_groups * n_per particles, particle i in group i / n_per. bias
+// [n_groups][4 H]: row g = b_ih + b_hh + W_ih[:, shared columns] x_g (+ h_g W_hh^T with c0); c0 [n_groups][H] or nullptr: the previous
+// state is one row per GROUP (the second statement of a trace: no recurrent product, (h, c) are only written) or one row per particle.
+// Whole-statement mode, identity rows, always the one-kernel statement; mixture heads with a Normal / Uniform prior. f: the images
+// (bias unused). One-layer LSTMs of H = 32 .. 512 that have a fused statement kernel for the address.
+bool is_statement_groups_supported(const pp_net* net, int addr_id);
+int is_statement_groups(const pp_net* net, const float* P, int addr_id, int prev_addr_id, int n_groups, int n_per, const float* bias,
+                        const float* c0, const float* prev_value, const float* prior, int prior_stride, float* h, float* c,
+                        const IsStatementOut& whole, uint64_t seed, uint64_t offset, const IsFusedBuffers& f, float* y_out, int64_t ldy,
+                        hipStream_t st);
+int is_step_small_groups(const pp_net* net, const float* P, int addr_id, int prev_addr_id, int n_groups, int n_per, const float* bias,
+                         const float* c0, const float* prev_value, const float* prior, int prior_stride, float* h, float* c,
+                         const IsStatementOut& whole, uint64_t seed, uint64_t offset, const IsFusedBuffers& f, float* y_out, int64_t ldy,
+                         hipStream_t st);
+
 // H = 1024 (one layer): the LSTM step of a statement as ONE launch (two workgroups per 32 particles, half of the hidden units
 // each); the head layers and the draw stay with the caller's launches. c is updated in place, the new hidden rows go to hn [n][H]
 bool is_lstm_wide_supported(const pp_net* net);

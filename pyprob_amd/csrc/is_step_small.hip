@@ -169,6 +169,7 @@ struct SmallArgs {
     int K, n, L, ubk;
     int prev_indexed;
     float* value_full; float* lw_full; int prior_kind;
+    int n_per;                  // GROUPED (pp_is_statement_groups): particle i belongs to group i / n_per; bias [groups][4 H], c0 [groups][H]
     long long* dbg;             // debug: clock64 stamps [2 workgroups][2 waves][16] (pp_debug_timeline, tools/is_small_timeline.py)
 };
 
@@ -180,7 +181,9 @@ extern __shared__ __attribute__((aligned(16))) float small_lds[];
 // left alone takes ~180 (two waves per SIMD), and every phase of a workgroup outside the K loop (staging, cell, head layers, the
 // ~20 000-cycle draw of one wave) leaves the MFMA pipe to the OTHER workgroups of the CU.
 // UBK = 0: the unit-block count is a.ubk (H = 96, 160 .. 256: every index below is a run-time value; 32 particles per workgroup)
-template <int UBK, int KIND, bool SHARED>
+// GROUPED: the statement of a batched posterior call (is_batch.hip), one layer: M groups of n_per particles, one bias row (and, SHARED,
+// one previous cell row) per group; no row list. A template parameter like SHARED (is_step_fused.hip).
+template <int UBK, int KIND, bool SHARED, bool GROUPED = false>
 __global__ __launch_bounds__(UBK ? 2 * rows_per_block(UBK) * UBK : 512) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void is_step_small_kernel(const SmallArgs a) {
     const int ubk = UBK ? UBK : a.ubk;
@@ -193,7 +196,8 @@ void is_step_small_kernel(const SmallArgs a) {
     const int AP = a.ns2 * 8 + 4;                   // row pitch of the head activations
     float* sH = small_lds;                          // [64][HP] fresh hidden rows of the layer below (first: the sample embedding)
     int* sRow = reinterpret_cast<int*>(sH + SR * HP);   // [64]
-    float* sHold = reinterpret_cast<float*>(sRow + SR); // [L][64][HP] old hidden rows of every layer (not SHARED); dead after the
+    int* sGrp = sRow + SR;                              // GROUPED: [64] group of every particle of the panel
+    float* sHold = reinterpret_cast<float*>(sRow + (GROUPED ? 2 : 1) * SR); // [L][64][HP] old hidden rows of every layer (not SHARED); dead after the
     float* sA1 = sHold;                             // last layer's K loop: [64][AP] head activations and
     float* sY = sA1 + SR * AP;                      // [64][33] head outputs lie over them
 
@@ -214,8 +218,9 @@ void is_step_small_kernel(const SmallArgs a) {
     SMALL_STAMP();      // 0 start
     if (tid < SR) {
         const int gr = min(m0 + tid, a.n - 1);
-        const int64_t ri = a.rows ? a.rows[gr] : (int64_t)gr;
+        const int64_t ri = (!GROUPED && a.rows) ? a.rows[gr] : (int64_t)gr;
         sRow[tid] = (int)ri;
+        if constexpr (GROUPED) sGrp[tid] = gr / a.n_per;
         // slab 0 of the tile: relu(sample embedding) of the previous value, zero-padded to 8 (embedding_feedforward.py: one
         // Linear + ReLU; a Linear(1, smp_dim) of the value, or a row of the one-hot Linear(C, smp_dim))
         const float pv = a.prev_value[a.prev_indexed ? ri : (int64_t)gr];
@@ -244,7 +249,7 @@ void is_step_small_kernel(const SmallArgs a) {
                     const int l = e / per_layer, r = e - l * per_layer;
                     const int row = r / (H / 4), p = r - row * (H / 4);
                     const int gr = min(m0 + row, a.n - 1);
-                    const int64_t ri = a.rows ? a.rows[gr] : (int64_t)gr;
+                    const int64_t ri = (!GROUPED && a.rows) ? a.rows[gr] : (int64_t)gr;
                     v[q] = *reinterpret_cast<const f32x4*>(a.h + l * a.layer_stride + ri * H + 4 * p);
                 }
             }
@@ -266,18 +271,36 @@ void is_step_small_kernel(const SmallArgs a) {
     const float* gim = a.gimg + (size_t)ub * (4 * 256) + lane * 4;
     for (int l = 0; l < a.L; ++l) {
         f32x16 acc[4];
+        // GROUPED (one layer): the first and the last particle of this wave's row block in one group (wave-uniform): that group's
+        // row, one load per gate as without groups; a row block that straddles groups: one load per accumulator row (sGrp)
+        const int g_lo = GROUPED ? __builtin_amdgcn_readfirstlane(sGrp[rb * 32]) : 0;
+        const bool one_group = !GROUPED || g_lo == __builtin_amdgcn_readfirstlane(sGrp[rb * 32 + 31]);
+        if (one_group) {
+            const float* bias = a.bias + (size_t)g_lo * (4 * H);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const float b = a.bias[(l * 4 + g) * H + u];
+            for (int g = 0; g < 4; ++g) {
+                const float b = bias[(l * 4 + g) * H + u];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[g][r] = b;
+                for (int r = 0; r < 16; ++r) acc[g][r] = b;
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float* bias = a.bias + (size_t)sGrp[rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh] * (4 * H) + u;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) acc[g][r] = bias[g * H];
+                __builtin_amdgcn_sched_barrier(0);      // row by row (sixteen hoisted row addresses: registers)
+            }
         }
         // the previous cell state of this lane's 16 (row, unit) pairs: issued now, used after the K loop
         float cp[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            cp[r] = SHARED ? a.c0[l * H + u] : a.c[l * a.layer_stride + (int64_t)sRow[row] * H + u];
+            // (SHARED && GROUPED: the group's row of the [groups][H] block - one value when the row block lies in one group, as
+            // without groups; a straddling row block loads row by row in the cell below instead of holding sixteen values)
+            if constexpr (SHARED && GROUPED) cp[r] = a.c0[(int64_t)g_lo * H + u];
+            else cp[r] = SHARED ? a.c0[l * H + u] : a.c[l * a.layer_stride + (int64_t)sRow[row] * H + u];
         }
         const int n_in = l == 0 ? 1 : NSH;                  // items of the input product (A from the tile)
         const int T = n_in + (SHARED ? 0 : NSH);            // + the recurrent product (A from the staged old rows)
@@ -324,7 +347,11 @@ void is_step_small_kernel(const SmallArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            const float cn = acc[1][r] * cp[r] + acc[0][r];
+            float cpr = cp[r];
+            if constexpr (SHARED && GROUPED) {
+                if (!one_group) cpr = a.c0[(int64_t)sGrp[row] * H + u];
+            }
+            const float cn = acc[1][r] * cpr + acc[0][r];
             const float hn = acc[3][r] * fast_tanh(cn);
             if (m0 + row < a.n) {
                 const int64_t off = l * a.layer_stride + (int64_t)sRow[row] * H + u;
@@ -439,17 +466,17 @@ void is_step_small_kernel(const SmallArgs a) {
 #undef SMALL_STAMP
 }
 
-size_t small_lds_bytes(int H, int L, int ns2, bool shared) {
+size_t small_lds_bytes(int H, int L, int ns2, bool shared, bool grouped = false) {
     const int HP = H + 4, AP = ns2 * 8 + 4, SR = rows_per_block(H / 32);
     const size_t head = (size_t)SR * AP + SR * 33, old = shared ? 0 : (size_t)L * SR * HP;
-    return ((size_t)SR * HP + SR + std::max(head, old)) * sizeof(float);
+    return ((size_t)SR * HP + (grouped ? 2 : 1) * SR + std::max(head, old)) * sizeof(float);
 }
 
-template <int UBK, int KIND, bool SHARED>
+template <int UBK, int KIND, bool SHARED, bool GROUPED = false>
 int launch_small(const SmallArgs& a, size_t lds, hipStream_t st) {
     static bool raised = false;
     if (!raised && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&is_step_small_kernel<UBK, KIND, SHARED>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&is_step_small_kernel<UBK, KIND, SHARED, GROUPED>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) {
             set_error("pp_is_step: cannot raise the LDS limit of the small-network statement kernel: %s", hipGetErrorString(e));
@@ -458,8 +485,13 @@ int launch_small(const SmallArgs& a, size_t lds, hipStream_t st) {
         raised = true;
     }
     constexpr int SR = rows_per_block(UBK);
-    hipLaunchKernelGGL((is_step_small_kernel<UBK, KIND, SHARED>), dim3(cdiv(a.n, SR)), dim3(2 * SR * a.ubk), lds, st, a);
+    hipLaunchKernelGGL((is_step_small_kernel<UBK, KIND, SHARED, GROUPED>), dim3(cdiv(a.n, SR)), dim3(2 * SR * a.ubk), lds, st, a);
     return 0;
+}
+template <int UBK>
+int launch_small_grouped(const SmallArgs& a, int kind, bool shared, size_t lds, hipStream_t st) {
+    if (kind == 0) return shared ? launch_small<UBK, 0, true, true>(a, lds, st) : launch_small<UBK, 0, false, true>(a, lds, st);
+    return shared ? launch_small<UBK, 1, true, true>(a, lds, st) : launch_small<UBK, 1, false, true>(a, lds, st);
 }
 template <int UBK>
 int launch_small_kind(const SmallArgs& a, int kind, bool shared, size_t lds, hipStream_t st) {
@@ -577,6 +609,63 @@ int is_step_small(const pp_net* net, const float* P, int addr_id, int prev_addr_
     if (rc) return rc;
     PP_LAUNCH_CHECK("pp_is_step(fused statement, small network)");
     *sampled = kind != 3;
+    return 0;
+}
+
+// The grouped whole statement on a small one-layer LSTM (is_statement_groups, is_step_fused.hip): the images of this address (the
+// image blocks of the prepare launch; the bias rows are the caller's block), then ONE launch of the GROUPED kernel.
+int is_step_small_groups(const pp_net* net, const float* P, int addr_id, int prev_addr_id, int n_groups, int n_per, const float* bias,
+                         const float* c0, const float* prev_value, const float* prior, int prior_stride, float* h, float* c,
+                         const IsStatementOut& whole, uint64_t seed, uint64_t offset, const IsFusedBuffers& f, float* y_out, int64_t ldy,
+                         hipStream_t st) {
+    const pp_addr& ad = net->addrs[addr_id];
+    const int H = net->lstm_dim, nsh = H / 8, ubk = H / 32, n = n_groups * n_per;
+    const bool shared = c0 != nullptr;
+    SmallPrepArgs p{};
+    p.P = P; p.at = net->addr_table;
+    p.H = H; p.I = net->lstm_in; p.L = 1; p.ubk = ubk; p.nsh = nsh;
+    p.w_ih[0] = net->w_ih; p.w_hh[0] = net->w_hh; p.b_ih[0] = net->b_ih; p.b_hh[0] = net->b_hh;
+    p.d = GatherDims{net->e_obs, net->smp_dim, net->dtype_dim, net->addr_dim, net->lstm_in};
+    p.addr_id = addr_id; p.prev_addr = prev_addr_id;
+    p.w1 = ad.w1; p.w2 = ad.w2;
+    p.hid = ad.hid; p.n_out = ad.n_out; p.nb1 = (ad.hid + 31) / 32; p.ns2 = (ad.hid + 7) / 8;
+    p.gimg = f.whh; p.w1_img = f.w1; p.w2_img = f.w2;
+    p.q_g = (int64_t)(1 + nsh) * ubk * 4 * 64;
+    p.q_w1 = (int64_t)nsh * p.nb1 * 64;
+    p.q_w2 = (int64_t)p.ns2 * 64;
+    p.img_blocks = (int)std::min<int64_t>(512, (p.q_g + p.q_w1 + p.q_w2 + 255) / 256);
+    hipLaunchKernelGGL(is_small_prep_kernel, dim3(p.img_blocks), dim3(256), 0, st, p);      // (no bias blocks)
+    PP_LAUNCH_CHECK("pp_is_statement_groups(prepare, small network)");
+
+    SmallArgs a{};
+    a.ubk = ubk;
+    a.gimg = f.whh; a.bias = bias;
+    a.h = h; a.c = c; a.layer_stride = (int64_t)n * H; a.c0 = c0;
+    const pp_addr& pad = net->addrs[prev_addr_id];
+    a.prev_value = prev_value; a.smp_w = P + pad.smp_w; a.smp_b = P + pad.smp_b; a.smp_in = pad.smp_in; a.smp = net->smp_dim;
+    a.w1_img = f.w1; a.b1 = P + ad.b1; a.hid = ad.hid; a.nb1 = p.nb1;
+    a.w2_img = f.w2; a.b2 = P + ad.b2; a.n_out = ad.n_out; a.ns2 = p.ns2;
+    a.y_out = y_out; a.ldy = ldy;
+    a.prior = prior; a.prior_stride = prior_stride;
+    a.seed = seed; a.offset = offset; a.K = ad.n_out / 3; a.n = n; a.L = 1; a.n_per = n_per;
+    a.prev_indexed = 1;
+    a.value_full = whole.value_full; a.lw_full = whole.lw_full; a.prior_kind = whole.prior_kind;
+    a.dbg = g_timeline;
+    const int kind = ad.kind == PP_HEAD_NORMAL_MIXTURE ? 0 : 1;
+    const size_t lds = small_lds_bytes(H, 1, p.ns2, shared, true);
+    const double flops = 2.0 * (net->lstm_in + (shared ? 0 : H)) * 4.0 * H + 2.0 * ((double)H * ad.hid + (double)ad.hid * ad.n_out);
+    prof_begin(5, st);
+    int rc;
+    if (ubk == 1) rc = launch_small_grouped<1>(a, kind, shared, lds, st);
+    else if (ubk == 2) rc = launch_small_grouped<2>(a, kind, shared, lds, st);
+    else if (ubk == 4) rc = launch_small_grouped<4>(a, kind, shared, lds, st);
+    else {
+        set_error("pp_is_statement_groups: small networks of 32, 64 or 128 hidden units");
+        return PP_EINVAL;
+    }
+    prof_end(5, flops * n, st);
+    if (rc) return rc;
+    PP_LAUNCH_CHECK("pp_is_statement_groups(fused statement, small network)");
     return 0;
 }
 

@@ -742,16 +742,27 @@ class ISRunner(DistRunner):
         return (self.dev.type == 'cuda' and all(net.obs_kind[o] == L.PP_OBS_FEEDFORWARD for o in range(net.n_obs)) and
                 (self.eng.spec.lstm_dim == 0 or max(1, self.eng.spec.lstm_depth) == 1))
 
-    def init_batch(self, obs):
+    def init_batch(self, obs, rows=None, cache=None):
         """_infer_init for M observations: obs [M, obs_width], one row per group, the observables' values in the network's
-        order. The rows go to the device once; the embedding is computed by first_batch."""
+        order. The rows go to the device once; the embedding is computed by first_batch.
+        rows = (g0, g1), cache = a dict shared by the executions of ONE sharded call: this execution serves groups [g0, g1) of the
+        M observations. The network part of a first statement is evaluated once for all M rows (first_batch fills the cache) and
+        every shard takes its slice: pp_is_batch_first's GEMMs pick their shape by the row count, so a shard embedded on its own
+        would differ from the unsharded call in the last bits."""
         obs = torch.as_tensor(obs, dtype=torch.float32)
         if obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != self.eng.spec.obs_width:
             raise ValueError('observations of shape %s, the network expects [M >= 1, %d]' % (tuple(obs.shape), self.eng.spec.obs_width))
         if torch.cuda.current_device() != (self.dev.index or 0):
             torch.cuda.set_device(self.dev)
-        self._b_M = M = int(obs.shape[0])
-        self._b_obs = obs.to(self.dev).contiguous()
+        self._b_M_full = M = int(obs.shape[0])
+        self._b_rows = (0, M) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= self._b_rows[0] < self._b_rows[1] <= M:
+            raise ValueError('init_batch: rows %s of %d observations' % (self._b_rows, M))
+        self._b_M = self._b_rows[1] - self._b_rows[0]
+        self._b_cache = {} if cache is None else cache
+        if 'obs' not in self._b_cache:
+            self._b_cache['obs'] = obs.to(self.dev).contiguous()
+        self._b_obs = self._b_cache['obs']
         need = self.lib.pp_is_batch_workspace_bytes(C.byref(self.eng.net), M)
         if getattr(self, '_b_ws', None) is None or need > self._b_ws.numel():
             self._b_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
@@ -759,19 +770,28 @@ class ISRunner(DistRunner):
         self.offset = 0
         self.prev_value = self.last_value = None
 
-    def first_batch(self, addr_id, keep_state=False):
+    def first_batch(self, addr_id, keep_state=True):
         """_infer_step(prev_variable=None) + the proposal layer of `addr_id` for the M observations of init_batch: the head
-        outputs [M, ldy], one row per group (kept for fused_groups). keep_state: also (h, c) [M, H]."""
-        M, H = self._b_M, self.eng.spec.lstm_dim
-        ldy = (int(self.eng.net.addrs[int(addr_id)].n_out) + 3) & ~3
-        self._b_y = torch.empty(M, ldy, dtype=torch.float32, device=self.dev)
-        self._b_h = self._b_c = None
-        if keep_state and H:
-            self._b_h = torch.empty(M, H, dtype=torch.float32, device=self.dev)
-            self._b_c = torch.empty(M, H, dtype=torch.float32, device=self.dev)
-        L.check(self.lib.pp_is_batch_first(C.byref(self.eng.net), self.eng.params.data_ptr(), self._b_obs.data_ptr(), int(addr_id), M,
-                                           self._b_y.data_ptr(), ldy, L.ptr(self._b_h), L.ptr(self._b_c), self._b_ws.data_ptr(),
-                                           self._b_ws.numel(), self._st), 'pp_is_batch_first')
+        outputs [M, ldy], one row per group (kept for fused_groups). keep_state (LSTM networks): also (h, c) [M, H], the state a
+        second statement starts from (bias_batch, statement_groups)."""
+        M, H = self._b_M_full, self.eng.spec.lstm_dim
+        hit = self._b_cache.get(('first', int(addr_id), bool(keep_state)))
+        if hit is None:      # (all M rows, whichever groups this execution serves: see init_batch)
+            ldy = (int(self.eng.net.addrs[int(addr_id)].n_out) + 3) & ~3
+            y = torch.empty(M, ldy, dtype=torch.float32, device=self.dev)
+            h = c = None
+            if keep_state and H:
+                h = torch.empty(M, H, dtype=torch.float32, device=self.dev)
+                c = torch.empty(M, H, dtype=torch.float32, device=self.dev)
+            L.check(self.lib.pp_is_batch_first(C.byref(self.eng.net), self.eng.params.data_ptr(), self._b_obs.data_ptr(), int(addr_id), M,
+                                               y.data_ptr(), ldy, L.ptr(h), L.ptr(c), self._b_ws.data_ptr(), self._b_ws.numel(),
+                                               self._st), 'pp_is_batch_first')
+            hit = self._b_cache[('first', int(addr_id), bool(keep_state))] = (y, h, c)
+        g0, g1 = self._b_rows
+        y, h, c = hit
+        self._b_y = y[g0:g1]
+        self._b_h = None if h is None else h[g0:g1]
+        self._b_c = None if c is None else c[g0:g1]
         return self._b_y
 
     def fused_groups(self, addr_id, n_per, prior, terms, value, lw, overwrite, seed=0, offset=0, stats=False, y=None):
@@ -811,14 +831,74 @@ class ISRunner(DistRunner):
         if y is not None and (y.dim() != 2 or y.shape[0] < M or not y.is_contiguous()):
             raise RuntimeError('fused_groups: head outputs [M, ldy]')
         pr = None if prior is None else prior.reshape(-1)
+        if pr is not None and addr_id is not None and pr.numel() not in (2, 2 * total):
+            raise RuntimeError('fused_groups: prior [2] or [M n_per, 2]')
+        per_particle = 2 if (pr is not None and total > 1 and pr.numel() == 2 * total) else 0      # PP_GROUPS_PRIOR_PER_PARTICLE
         st = self._st if self._st is not None else L.stream_ptr()
         L.check(self.lib.pp_is_fused_groups(C.byref(self.eng.net), -1 if addr_id is None else int(addr_id), M, int(n_per), L.ptr(y),
                                             0 if y is None else int(y.shape[1]), L.ptr(pr), arr, fl, count, value.data_ptr(),
-                                            lw.data_ptr(), 1 if overwrite else 0, int(seed), int(offset), L.ptr(out),
+                                            lw.data_ptr(), (1 if overwrite else 0) | per_particle, int(seed), int(offset), L.ptr(out),
                                             self._b_ws.data_ptr(), self._b_ws.numel(), st), 'pp_is_fused_groups')
         return out
 
     PRIOR_KIND = {'Normal': 0, 'Uniform': 1}
+
+    # ---- later statements of a batched call (pp_is_batch_bias, pp_is_statement_groups) ----------------------------------------------
+    def statement_groups_ok(self, addr_id, n):
+        """Does pp_is_statement_groups take this network and address (a one-layer LSTM of 32, 64, 128, 256 or 512 hidden units
+        with a fused statement kernel for the address)?"""
+        spec = self.eng.spec
+        return (self.dev.type == 'cuda' and spec.lstm_dim in (32, 64, 128, 256, 512) and max(1, spec.lstm_depth) == 1 and
+                bool(self.lib.pp_is_step_fused_supported(C.byref(self.eng.net), int(addr_id), int(n))))
+
+    def bias_batch(self, addr_id, prev_addr_id, shared_state):
+        """The bias rows [M, 4H] of statement (addr_id, prev_addr_id) for the M observations of init_batch / first_batch;
+        shared_state: + h_g W_hh^T of the state first_batch left (the second statement of a trace)."""
+        M, H = self._b_M, self.eng.spec.lstm_dim
+        if shared_state and self._b_h is None:
+            raise RuntimeError('bias_batch: first_batch did not keep the state')
+        bias = torch.empty(M, 4 * H, dtype=torch.float32, device=self.dev)
+        L.check(self.lib.pp_is_batch_bias(C.byref(self.eng.net), self.eng.params.data_ptr(), int(addr_id), int(prev_addr_id), M,
+                                          self._b_M_full, self._b_rows[0], L.ptr(self._b_h if shared_state else None), bias.data_ptr(),
+                                          self._b_ws.data_ptr(), self._b_ws.numel(), self._st), 'pp_is_batch_bias')
+        return bias
+
+    def statement_groups(self, addr_id, prev_addr_id, n_per, bias, shared_state, prev_value, prior, values, lw, dist_name, seed=0,
+                         offset=0, y_out=None, c0=None):
+        """The whole statement for M * n_per particles in one launch (pp_is_statement_groups): particle i starts from bias row
+        i // n_per; shared_state: every particle of group g starts from first_batch's (h_g, c_g) (c0: another [M, H] block), else
+        from its own row of the (h, c) [M n_per, H] buffers, which are allocated here when the first later statement arrives.
+        prior [2] or [M n_per, 2]; values[i] = the draw, lw[i] += log p(v) - log q(v)."""
+        M, H = int(bias.shape[0]), self.eng.spec.lstm_dim
+        n = M * int(n_per)
+        if values.numel() != n or lw.numel() != n or prev_value.numel() != n or prior.numel() not in (2, 2 * n):
+            raise RuntimeError('statement_groups: values, lw and prev_value of M * n_per elements, prior [2] or [M n_per, 2]')
+        if shared_state and c0 is None:
+            c0 = self._b_c
+        gh = getattr(self, '_g_h', None)
+        if gh is None or gh.shape[0] != n or gh.shape[1] != H:
+            if not shared_state:
+                raise RuntimeError('statement_groups: no per-particle state yet (the second statement starts from the shared one)')
+            self._g_h = torch.empty(n, H, dtype=torch.float32, device=self.dev)
+            self._g_c = torch.empty(n, H, dtype=torch.float32, device=self.dev)
+        # (its own scratch for the weight images: the batch workspace holds the embedding rows of all the call's groups, carved
+        # for THEIR number, and a shard's call would lay its images over them)
+        need = self.lib.pp_is_batch_workspace_bytes(C.byref(self.eng.net), M)
+        if getattr(self, '_g_ws', None) is None or need > self._g_ws.numel():
+            self._g_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        st = self._st if self._st is not None else L.stream_ptr()
+        L.check(self.lib.pp_is_statement_groups(C.byref(self.eng.net), self.eng.params.data_ptr(), int(addr_id), int(prev_addr_id), M,
+                                                int(n_per), bias.data_ptr(), L.ptr(c0 if shared_state else None), prev_value.data_ptr(),
+                                                prior.data_ptr(), 0 if prior.numel() == 2 else 1, self._g_h.data_ptr(),
+                                                self._g_c.data_ptr(), values.data_ptr(), lw.data_ptr(), self.PRIOR_KIND[dist_name],
+                                                int(seed), int(offset), L.ptr(y_out), 0 if y_out is None else int(y_out.shape[1]),
+                                                self._g_ws.data_ptr(), self._g_ws.numel(), st), 'pp_is_statement_groups')
+        torch.autograd.graph.increment_version(values)
+        self.prev_value = self.last_value = values
+
+    def release_group_state(self):
+        """Drop the (h, c) [M n_per, H] buffers of statement_groups (the largest allocation of a batched call)."""
+        self._g_h = self._g_c = None
 
     def whole_statement_ok(self, addr_id, prev_addr_id, m, dist_name, prior):
         """Can `statement_rows` take this statement (fused statement kernel, shared Normal / Uniform prior pair)?"""

@@ -172,6 +172,9 @@ PROTOTYPES = {
     'pp_is_batch_first': (C.c_int, [C.POINTER(pp_net), vp, vp, i32, i32, vp, i64, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_fused_groups': (C.c_int, [C.POINTER(pp_net), i32, i32, i32, vp, i64, vp, C.POINTER(pp_lw_term), C.POINTER(C.c_int32), i32,
                                      vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp, C.c_size_t, vp]),
+    'pp_is_batch_bias': (C.c_int, [C.POINTER(pp_net), vp, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]),
+    'pp_is_statement_groups': (C.c_int, [C.POINTER(pp_net), vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32,
+                                         C.c_uint64, C.c_uint64, vp, i64, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

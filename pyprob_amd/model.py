@@ -224,7 +224,7 @@ class Model:
             return None
 
     # attributes the Model base class itself keeps on the instance (never read by a program as constants)
-    _BASE_ATTRS = frozenset(('_inference_network', '_lockstep_plans', '_lock_step_ok', '_batch_ok', '_last_prior_resident', '_last_prior_obs_widths', '_plan_code_cache',
+    _BASE_ATTRS = frozenset(('_inference_network', '_lockstep_plans', '_lock_step_ok', '_batch_ok', '_batch_keeps_state', '_last_prior_resident', '_last_prior_obs_widths', '_plan_code_cache',
                              '_plan_key_cache', '_plan_indirect_cache', '_plan_indirect_pairs'))
 
     @staticmethod
@@ -858,11 +858,14 @@ class Model:
         seed=seed, offset=offset + g * num_traces) in distribution - particle j of group g uses Philox counter
         offset + g * num_traces + j, so the call consumes exactly the counters of those M calls. `observes`: a list of M observe
         dicts with equal keys, or one dict name -> tensor with a leading dimension M.
-        A lock-step-safe program with ONE controlled sample statement on a mixture head (Normal / Uniform / Poisson prior), at most
-        8 scalar observes of the network's families, FEEDFORWARD observe embeddings and a FeedForward or one-layer LSTM network
-        runs all M * num_traces particles in ONE lock-step execution of forward() (the reference: M posterior calls,
-        pyprob/model.py:106-117); an observed value the program reads is then one value per group. Anything else is served by
-        that loop of posterior_results calls; which of the two is remembered per model."""
+        A lock-step-safe STRAIGHT-LINE program - a first controlled sample statement on a mixture head (Normal / Uniform / Poisson
+        prior), any number of later Normal / Uniform statements whose priors may depend on earlier draws (one-layer LSTM networks
+        of 32, 64, 128, 256 or 512 hidden units, or a FeedForward network) -, at most 8 scalar observes of
+        the network's families and FEEDFORWARD observe embeddings runs all M * num_traces particles in ONE lock-step execution
+        of forward() (the reference: M posterior calls, pyprob/model.py:106-117); an observed value the program reads is then one
+        value per group. The per-particle LSTM state of later statements is held to PP_BATCH_STATE_BYTES (default 4 GiB) per
+        execution by sharding over groups. Anything else (branches, other heads at later statements, H = 1024, deeper LSTMs) is
+        served by that loop of posterior_results calls; which of the two is remembered per model."""
         names, dicts, cols = self._normalise_observes(observes)
         M, N = len(dicts), int(num_traces)
 
@@ -901,20 +904,50 @@ class Model:
         per_call = max(1, (2 ** 32 // H - 1) // N)        # groups per execution
         if N * H >= 2 ** 32:
             raise ValueError('at most 2^32 / lstm_dim - 1 = %d particles per observation (got %d)' % (2 ** 32 // H - 1, N))
-        out = []
-        for g0 in range(0, M, per_call):
-            g1 = min(M, g0 + per_call)
-            obs = state.GroupObserves()
-            for k, c in cols.items():
-                obs[k] = torch.from_numpy(np.ascontiguousarray(c[g0:g1, 0])).to(runner.dev).as_subclass(state.GroupTensor)
-            obs.matrix = np.concatenate([cols[k][g0:g1] for k in net._obs_names], axis=1)
-            out += self._run_lockstep_batch(obs, g1 - g0, N, seed, offset + g0 * N, likelihood_importance, *args, **kwargs)
+        # A program with a second statement on an LSTM network keeps (h, c) [groups * N, H] per execution: at most
+        # PP_BATCH_STATE_BYTES of them (default 4 GiB; one group where a single group is larger). Whether the program has a second
+        # statement shows when it runs: the state raises BatchStateBudget there, the call starts again with the smaller shard and
+        # the model remembers.
+        import ctypes as C
+        budget = int(_environ.get('PP_BATCH_STATE_BYTES', 4 * 2 ** 30))
+        state_groups = max(1, budget // (8 * N * H))
+
+        # The shards of one call share the network part of every first statement (embedding, first LSTM step, head: evaluated once
+        # for all M rows, GroupObserves.cache) where its workspace fits the same budget; else every shard embeds its own rows and
+        # may differ from the unsharded call in the last bits of the proposals.
+        full = np.concatenate([cols[k] for k in net._obs_names], axis=1)
+        share = int(runner.lib.pp_is_batch_workspace_bytes(C.byref(net._engine.net), M)) <= budget
+
+        def run(groups, state_budget):
+            out = []
+            cache = {}
+            for g0 in range(0, M, groups):
+                g1 = min(M, g0 + groups)
+                obs = state.GroupObserves()
+                for k, c in cols.items():
+                    obs[k] = torch.from_numpy(np.ascontiguousarray(c[g0:g1, 0])).to(runner.dev).as_subclass(state.GroupTensor)
+                if share and groups < M:
+                    obs.matrix, obs.rows, obs.cache = full, (g0, g1), cache
+                else:
+                    obs.matrix = full[g0:g1]
+                out += self._run_lockstep_batch(obs, g1 - g0, N, seed, offset + g0 * N, likelihood_importance, *args,
+                                                state_budget=state_budget, **kwargs)
+            return out
+        try:
+            if getattr(self, '_batch_keeps_state', False):
+                out = run(min(per_call, state_groups), None)
+            else:
+                out = run(per_call, budget)
+        except state.BatchStateBudget:
+            self._batch_keeps_state = True
+            out = run(min(per_call, state_groups), None)
         self._batch_ok = True
         return out
 
-    def _run_lockstep_batch(self, obs, M, N, seed, offset, likelihood_importance, *args, **kwargs):
+    def _run_lockstep_batch(self, obs, M, N, seed, offset, likelihood_importance, *args, state_budget=None, **kwargs):
         runner = self._inference_network._is
         ls = state.BatchLockStepState(runner, M, N, seed, offset)
+        ls.state_budget = state_budget
         try:
             state._init_traces(func=self.forward, trace_mode=TraceMode.POSTERIOR,
                                inference_engine=InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK,
@@ -924,7 +957,7 @@ class Model:
             result = self.forward(*args, **kwargs)
             if not torch.is_tensor(result) or isinstance(result, state.GroupTensor) or result.numel() != M * N:
                 raise state.BatchUnsupported('forward() must return one value per particle')
-            if ls.statement != 1:
+            if ls.statement < 1:
                 raise state.BatchUnsupported('no controlled sample statement')
             values = result.as_subclass(torch.Tensor).reshape(-1)
             if values.dtype != torch.float32 or values.device != runner.dev or not values.is_contiguous():
@@ -939,6 +972,7 @@ class Model:
             state._lock_step = None
             state._current_trace = None
             ls.memo = None
+            runner.release_group_state()
         stats = ls.group_stats.cpu().numpy()          # the one device-to-host copy (and synchronisation) of the call
         # (one split per tensor, not two slices per group: the per-group host work is what the call amortises)
         v_parts, lw_parts = values.split(N), ls.lw.split(N)

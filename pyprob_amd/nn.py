@@ -253,7 +253,7 @@ class InferenceNetworkLSTM:
         """inference_network.py:141-148"""
         self._infer_observe = observe
         if getattr(observe, 'matrix', None) is not None:      # state.GroupObserves: M observations, one embedding row each
-            self._is.init_batch(observe.matrix)
+            self._is.init_batch(observe.matrix, rows=getattr(observe, 'rows', None), cache=getattr(observe, 'cache', None))
             self._infer_prev_addr_id = None
             return
         vals = []

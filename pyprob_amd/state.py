@@ -583,6 +583,11 @@ class BatchUnsupported(Exception):
     falls back to one posterior_results call per observation."""
 
 
+class BatchStateBudget(Exception):
+    """Internal: the per-particle LSTM state of a later statement of a batched call would exceed PP_BATCH_STATE_BYTES; the caller
+    runs the call again over fewer groups per execution."""
+
+
 class GroupTensor(ParticleTensor):
     """An observed value of a batched lock-step call: [M], one value per group. It may be passed on (as the value of an observe
     or a sample statement) and asked for its metadata; anything that computes with it is outside the fast path. (A subclass of
@@ -605,20 +610,27 @@ class GroupTensor(ParticleTensor):
 
 class GroupObserves(dict):
     """The observe dict of a batched call: name -> GroupTensor [M]; `matrix` [M, obs_width] holds the rows
-    InferenceNetwork._infer_init embeds (the observables' values in the network's order)."""
+    InferenceNetwork._infer_init embeds (the observables' values in the network's order). One execution of a SHARDED call:
+    `matrix` holds the rows of all the call's groups, `rows` = (g0, g1) the ones this execution serves, `cache` the dict the
+    executions share (ISRunner.init_batch)."""
     matrix = None
+    rows = None
+    cache = None
 
 
 class BatchLockStepState(LockStepState):
     """M groups of n_per particles through ONE lock-step execution of forward() (Model.posterior_results_batch): particle
-    i = g n_per + j belongs to group g and sees observation g. Served: one controlled sample statement on a mixture head, drawn
-    from the group's own proposal (ISRunner.first_batch), and scalar ScalarTerm observes whose operands are shared, per particle
-    or per group (ISRunner.fused_groups). The first thing outside that raises BatchUnsupported."""
+    i = g n_per + j belongs to group g and sees observation g. Served: a straight-line program of controlled sample statements on
+    mixture heads - the first drawn from the group's own proposal (ISRunner.first_batch), later ones (Normal / Uniform, the prior
+    shared or depending on earlier draws) by the grouped statement kernel (ISRunner.bias_batch, statement_groups) - and scalar
+    ScalarTerm observes whose operands are shared, per particle or per group (ISRunner.fused_groups). The first thing outside that
+    raises BatchUnsupported."""
     batched = True
 
     def __init__(self, runner, n_groups, n_per, seed, offset):
         self.n_groups, self.n_per = int(n_groups), int(n_per)
         self.group_stats = None          # device double [M, 6] of the final flush
+        self.state_budget = None         # bytes the (h, c) rows of later statements may take (Model._traces_lockstep_batch)
         self.n_terms_total = 0
         super().__init__(runner, self.n_groups * self.n_per, seed, offset)
         self.by_rows = False
@@ -631,11 +643,12 @@ class BatchLockStepState(LockStepState):
         raise BatchUnsupported('a sample statement drawn from its prior')
 
     def batch_statement(self, net, address, distribution):
-        """The controlled sample statement of the trace (InferenceNetwork._infer_step_lockstep hands over here): the network
-        part for the M observations now, the draw deferred to the fused pass."""
+        """A controlled sample statement of the trace (InferenceNetwork._infer_step_lockstep hands over here). The first one: the
+        network part for the M observations now, the draw deferred to the fused pass. Later ones (a straight-line program):
+        `later_statement`."""
         spec, runner = net._engine.spec, self.runner
-        if self.statement > 0 or self.draw is not None:
-            raise BatchUnsupported('a second controlled sample statement')
+        if self.statement > 0:
+            return self.later_statement(net, address, distribution)
         self.statement += 1
         if address not in spec.address_id:
             raise BatchUnsupported('an address without proposal layers')
@@ -649,6 +662,47 @@ class BatchLockStepState(LockStepState):
         runner.first_batch(a)
         values = torch.empty(self.n, dtype=torch.float32, device=runner.dev)
         self.draw = dict(addr=a, prior=prior, values=values, seed=self.seed, prior_term=prior_term)   # (statement 0 of path 0)
+        self.log.append({address: (values, a)})
+        runner.prev_value = runner.last_value = values
+        self.prev_addr_id = a
+        return ParticleTensor.wrap(values)
+
+    def later_statement(self, net, address, distribution):
+        """Statement t >= 2 of a straight-line program: the previous statement's deferred draw and terms run first (its values are
+        this statement's previous values), then the bias rows of the M observations and the whole statement for all particles in
+        one launch (ISRunner.bias_batch, statement_groups; FeedForward network: the head on the M embedding rows and the grouped
+        draw pass); logged and seeded as LockStepState's statements are (seed + 7919 * statement index, path 0)."""
+        spec, runner = net._engine.spec, self.runner
+        j = self.statement
+        self.flush()
+        if address not in spec.address_id:
+            raise BatchUnsupported('an address without proposal layers')
+        a = spec.address_id[address]
+        info = spec.addresses[a]
+        prior = net._prior_tensor(distribution)
+        if not (info.dist_name in ('Normal', 'Uniform') and distribution.name == info.dist_name and prior is not None and
+                prior.numel() in (2, 2 * self.n)):
+            raise BatchUnsupported('a later statement that is not a Normal / Uniform statement on a mixture head')
+        seed = self.seed + 7919 * j
+        values = torch.empty(self.n, dtype=torch.float32, device=runner.dev)
+        if spec.feedforward:
+            prior_term = runner.dist_term(distribution)
+            if type(prior_term).__name__ != 'ScalarTerm':
+                raise BatchUnsupported('a prior without a device term')
+            self.statement += 1
+            runner.first_batch(a)
+            self.draw = dict(addr=a, prior=prior, values=values, seed=seed, prior_term=prior_term)
+        else:
+            if not runner.statement_groups_ok(a, self.n) or self.prev_addr_id is None:
+                raise BatchUnsupported('a network without a grouped statement kernel for this address')
+            H = int(spec.lstm_dim)
+            if j == 1 and self.n_groups > 1 and self.state_budget is not None and 8 * self.n * H > self.state_budget:
+                raise BatchStateBudget()
+            self.statement += 1
+            shared = j == 1        # every particle of a group still has the state of the group's first statement
+            bias = runner.bias_batch(a, self.prev_addr_id, shared)
+            runner.statement_groups(a, self.prev_addr_id, self.n_per, bias, shared, runner.prev_value, prior, values, self.lw,
+                                    info.dist_name, seed=seed, offset=self.offset)
         self.log.append({address: (values, a)})
         runner.prev_value = runner.last_value = values
         self.prev_addr_id = a
