@@ -838,6 +838,12 @@ int pp_head_logprob(int32_t kind, const float* y, int64_t ldy, const int32_t* ro
  * tile kernels take the flush). */
 int pp_debug_wgrad_plan(const pp_gemm_args* products, const int32_t* zero_blocks, int32_t count, int64_t* out, int32_t cap,
                         int32_t* n_blocks);
+/* The same plan, launched alone: wide_out[i] (host [cap], may be NULL) = 1 when problem i of the plan streams its operands with
+ * 16-byte loads (both operand pointers 16-byte aligned after the cut, lda and ldb multiples of 4, every vector inside its row;
+ * PP_WGRAD_WIDE=0: none), 0 for the dword loop. launch != 0: runs the weight-gradient launch on `stream` without reduction jobs
+ * (products = dev pointers then). Returns the number of problems; 0: refused, nothing launched. */
+int pp_debug_wgrad_run(const pp_gemm_args* products, const int32_t* zero_blocks, int32_t count, int32_t launch, void* stream,
+                       int32_t* wide_out, int32_t cap);
 int pp_prof_arm(int32_t which, int32_t max_samples);          /* allocate event pairs; 0 disarms */
 int pp_prof_stride(int32_t stride);                           /* time every stride-th launch of the class (default 1):
                                                                  an event pair costs the stream ~3 us, a stride keeps the

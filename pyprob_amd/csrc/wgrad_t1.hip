@@ -15,6 +15,12 @@
 // Single-statement batches (behind the panel kernel): 23.2 -> 15.2 us. Ragged batches (K up to 2 600 rows, 33 problems):
 // one launch instead of two, step 0.555 -> 0.519 ms; what bounds it there: DESIGN.md 8.2 (the float atomics).
 //
+// Two K loops share the kernel, chosen per problem by the host (WgradT1Prob::wide, wgrad_t1_build): the WIDE loop - one float4
+// per lane and operand on v_mfma_f32_16x16x4_f32, tile edges in units of 16, a ring of five quad-rows, the waves meeting in
+// two rounds of b128 LDS operations whose layout hands every atomic instruction 64 consecutive floats of a row - for
+// operands that are 16-byte aligned with pitches that are multiples of 4 (every problem of the training steps), and the
+// dword loop described above for everything else (PP_WGRAD_WIDE=0: for every problem - the A/B arm).
+//
 // The reduction jobs of the backward pass (aux_jobs.hpp: column sums, table-column gradients, bias gradients, the loss) ride
 // behind the tiles as before (in a launch of one round: the derived jobs first, wgrad_t1()).
 #include "wgrad_t1.hpp"
@@ -109,8 +115,205 @@ __device__ __forceinline__ void wgrad_kloop(f32x16 (&acc)[2][2], const float* __
         if (j < nrem) mma(f[j]);
 }
 
+// ---- the wide loop: 16-byte operand loads on v_mfma_f32_16x16x4_f32 ----------------------------------------------------
+// A k-major row is also the operand layout of the 16x16x4 MFMA (lane (q = l / 16, c = l % 16) supplies k = q, column c), and
+// nothing says that column c of the MFMA has to be column c of the tile: lane (q, c) loads ONE float4 of row k0 + q at the
+// tile's columns 4 c .. 4 c + 3 of A and of B, and MFMA (i, j) multiplies component i of the A vector by component j of the B
+// vector - the output block {rows 4 x + i} x {columns 4 y + j} of the tile. Two 1 KB loads feed 16 MFMAs over four rows (the
+// dword loop: four 256 B loads per four MFMAs over two rows), and lane (q, c) ends up with the 16 x 4 block at rows
+// 16 q + 4 r + i (r = accumulator register), columns 4 c + j: for a fixed (i, r) its four j-accumulators are one float4 of a
+// tile row, which is what the epilogue below moves through LDS.
+// Tile edges come in units of 16: a tile is MB x NB blocks of 16 (MB, NB in {1, 2, 4}: vectors of 4, 2, 1 floats at column
+// MB c, rows MB (4 q + r) + i) - M = 271 is four 64-row tiles and one of 16, where the 32-wide quadrants multiplied 320.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int WG_RINGW = 5;   // quad-rows in the ring, 4 .. 6 fit under 128 VGPRs: five in flight (10 KB per wave, 80 KB per
+                              // workgroup) while one multiplies
+constexpr int WG_RINGW_GATHER = 4;      // (the row gather keeps two index registers and the lane selects: five spill; and 4 divides an index block)
+
+template <int MB, int NB>
+struct Quad {      // four rows (k + lane / 16) of the tile's A and B columns: the operands of MB x NB MFMAs
+    float a[MB], b[NB];
+};
+
+template <int W>
+__device__ __forceinline__ void load_vec(float (&d)[W], const float* __restrict__ p) {
+    if constexpr (W == 4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+    } else if constexpr (W == 2) {
+        const f32x2 v = *reinterpret_cast<const f32x2*>(p);
+        d[0] = v[0]; d[1] = v[1];
+    } else {
+        d[0] = *p;
+    }
+}
+
+// K loop of one wave: the whole tile over rows [kb, ke), conventions as in wgrad_kloop (unconditional loads, rows past the
+// range enter as a * 0, the row gather's indices in blocks of 64 rows = 16 quad-rows).
+template <bool GATHER, int MB, int NB>
+__device__ __forceinline__ void wgrad_kloop_wide(f32x4 (&acc)[4][4], const float* __restrict__ A, const float* __restrict__ B,
+                                                 const int32_t* __restrict__ bidx, const int lda, const int ldb, const int M,
+                                                 const int N, const int m0, const int n0, const int kb, const int ke,
+                                                 const int lane) {
+    const int c = lane & 15, q = lane >> 4;
+    // single columns are clamped as in the dword loop; a float2 / float4 lies inside the row pitch (the host's rule) and
+    // what it reads beyond M / N lands in accumulator rows / columns the epilogue never stores
+    const float* pa = A + (MB == 1 ? min(m0 + c, M - 1) : m0 + MB * c);
+    const float* pb = B + (NB == 1 ? min(n0 + c, N - 1) : n0 + NB * c);
+    // Row gather: the block scheme of the dword loop (a lane keeps the indices of 64 rows = 16 quad-rows, a quad-row takes its
+    // four with v_readlane), but WITHOUT a branch round the index load - the compiler drains the queue where such a branch
+    // joins: the ring is four deep here, so every fourth load (a fixed place of the unrolled loop) is the possible first
+    // quad-row of a block; there the next block's indices are loaded again, unconditionally (64 lanes x 4 bytes per 8 KB of
+    // operands), after the register of the current block took the previous copy if a block begins.
+    int cur = 0, nxt = 0;
+    if (GATHER) {
+        cur = bidx[min(kb + lane, ke - 1)];
+        nxt = bidx[min(kb + 64 + lane, ke - 1)];
+        asm volatile("" : "+v"(nxt));      // (lands with cur, which the first B load waits for anyway: sunk into the loop's
+                                           // preheader, behind the ring's first loads, it costs the loop a wait on them)
+    }
+    const int q_odd = -(q & 1), q_hi = -(q >> 1);
+    auto load = [&](int pidx, Quad<MB, NB>& p, bool site) {      // quad-row pidx of this wave: rows kb + 4 pidx + q
+        const int k = kb + 4 * pidx + q;
+        const int kc = min(k, ke - 1);
+        load_vec<MB>(p.a, pa + (int64_t)kc * lda);
+        int kb2 = kc;
+        if (GATHER) {
+            if (site) {      // (pidx % 4 == 0, known at compile time)
+                cur = (pidx & 15) == 0 ? nxt : cur;
+                nxt = bidx[min(kb + 64 * ((pidx >> 4) + 1) + lane, ke - 1)];
+            }
+            const int v = cur;
+            const int sel = 4 * (pidx & 15);
+            const int r0 = __builtin_amdgcn_readlane(v, sel), r1 = __builtin_amdgcn_readlane(v, sel + 1);
+            const int r2 = __builtin_amdgcn_readlane(v, sel + 2), r3 = __builtin_amdgcn_readlane(v, sel + 3);
+            // (bit selects: a ?: chain over q becomes a switch with a branch per load)
+            const int t0 = r0 ^ ((r0 ^ r1) & q_odd), t1 = r2 ^ ((r2 ^ r3) & q_odd);
+            kb2 = t0 ^ ((t0 ^ t1) & q_hi);
+        }
+        load_vec<NB>(p.b, pb + (int64_t)kb2 * ldb);
+    };
+    // (the * 0 of the rows past the range is applied here, not at the load: behind the load it is an s_waitcnt on the
+    // youngest load of the ring)
+    auto mma = [&](int pidx, const Quad<MB, NB>& p) {
+        const float keep = kb + 4 * pidx + q < ke ? 1.0f : 0.0f;
+#pragma unroll
+        for (int i = 0; i < MB; ++i) {
+            const float a = p.a[i] * keep;
+#pragma unroll
+            for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, p.b[j], acc[i][j], 0, 0, 0);
+        }
+    };
+    constexpr int RING = GATHER ? WG_RINGW_GATHER : WG_RINGW;
+    static_assert(WG_RINGW_GATHER == 4, "the index blocks' reload sits at every fourth quad-row");
+    Quad<MB, NB> f[RING];
+    const int nfr = (ke - kb + 3) >> 2;      // quad-rows of this wave
+#pragma unroll
+    for (int i = 0; i < RING - 1; ++i) load(i, f[i], false);
+    int i0 = 0;
+    for (; i0 + RING <= nfr; i0 += RING) {
+#pragma unroll
+        for (int j = 0; j < RING; ++j) {
+            load(i0 + j + RING - 1, f[(j + RING - 1) % RING], ((j + RING - 1) & 3) == 0);
+            __builtin_amdgcn_sched_barrier(0);      // (left alone the scheduler gathers an iteration's loads behind its MFMAs and
+            mma(i0 + j, f[j]);                      // drains the queue - s_waitcnt vmcnt(0) - once per trip round the ring)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    const int nrem = nfr - i0;      // < RING: already in the ring
+#pragma unroll
+    for (int j = 0; j < RING - 1; ++j)
+        if (j < nrem) mma(i0 + j, f[j]);
+}
+
+template <int MB, int NB>
+__device__ __forceinline__ void wgrad_kloop_wide_any(f32x4 (&acc)[4][4], const float* A, const float* B, const int32_t* bidx,
+                                                     const int lda, const int ldb, const int M, const int N, const int m0,
+                                                     const int n0, const int kb, const int ke, const int lane) {
+    if (bidx) wgrad_kloop_wide<true, MB, NB>(acc, A, B, bidx, lda, ldb, M, N, m0, n0, kb, ke, lane);
+    else wgrad_kloop_wide<false, MB, NB>(acc, A, B, bidx, lda, ldb, M, N, m0, n0, kb, ke, lane);
+}
+
+// One tile of a wide problem over the rows [k0, k1) of its split: the K loop, then the eight waves' partial tiles meet in LDS
+// in TWO rounds of 64 KB (round h: the accumulators i = 2 h, 2 h + 1 = 32 of the tile's rows) and three barriers (the 32 x 32
+// quadrants of the dword loop: seven, on 64 + 64 dword operations per thread). An accumulator (i, j) of lane (q, c) is a
+// float4 over r: four rows of ONE column, 4 c + j. It goes as it is (ds_write_b128) to slot (i & 1, q) of the wave's 8 KB, to
+// the float4 of its column - so that the thread that sums a slot over the eight waves reads the float4 of column `lane`
+// (ds_read_b128) and a wave's atomic instruction covers 64 consecutive floats of one row of dW. The float4s of a slot are
+// swizzled inside groups of four, (c, j) -> 4 c + (j ^ (c >> 1 & 3)): a store instruction (one j) would otherwise put its
+// eight-lane groups on two of the eight 16-byte bank columns, four ways; reads stay inside their aligned groups of four.
+__device__ __forceinline__ void wgrad_tile_wide(const WgradT1Args& g, const WgradT1Prob& p, const int m0, const int n0, const int k0,
+                                                const int k1, float* lds) {
+    const float* const A = p.A;
+    const float* const B = p.B;
+    float* const C = p.C;
+    const int32_t* const bidx = p.bidx;
+    const int lda = p.lda, ldb = p.ldb, ldc = p.ldc, M = p.M, N = p.N;
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, q = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int per = ((k1 - k0 + 31) >> 5) * 4;      // rows per wave: whole quad-rows
+    const int kb = k0 + wave * per, ke = min(k1, kb + per);
+    const int mb = M - m0 > 32 ? 4 : M - m0 > 16 ? 2 : 1, nb = N - n0 > 32 ? 4 : N - n0 > 16 ? 2 : 1;      // (wave-uniform)
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (kb < ke) {
+#define PP_WIDE_CASE(MB, NB) \
+    case MB * 8 + NB: wgrad_kloop_wide_any<MB, NB>(acc, A, B, bidx, lda, ldb, M, N, m0, n0, kb, ke, lane); break;
+        switch (mb * 8 + nb) {
+            PP_WIDE_CASE(4, 4) PP_WIDE_CASE(4, 2) PP_WIDE_CASE(4, 1)
+            PP_WIDE_CASE(2, 4) PP_WIDE_CASE(2, 2) PP_WIDE_CASE(2, 1)
+            PP_WIDE_CASE(1, 4) PP_WIDE_CASE(1, 2) PP_WIDE_CASE(1, 1)
+        }
+#undef PP_WIDE_CASE
+    }
+    if (g.trace && threadIdx.x == 0) g.trace[8 * blockIdx.x + 4] = wall_clock64();
+    // the thread's slot of a round: rows mb (4 sq + r) + 2 h + si, r = 0 .. 3, of column (nb = 4: lane) nb (lane >> 2) + (lane & 3)
+    const int si = wave >> 2, sq = wave & 3;
+    const int oc = lane >> 2, oj = lane & 3;
+    f32x4 out[2];
+    auto add_out = [&](int h, const f32x4& v) {
+        const int i = 2 * h + si, gn = n0 + nb * oc + oj;
+        if (i >= mb || oj >= nb || gn >= N) return;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int gm = m0 + mb * (4 * sq + r) + i;
+            if (gm < M) atomicAdd(C + (int64_t)gm * ldc + gn, v[r]);
+        }
+    };
+    const int wr = wave * 2048 + q * 256 + 16 * c, swz = (c >> 1) & 3;      // + si 1024 + 4 (j ^ swz)
+    const int rd = wave * 256 + 4 * ((lane & ~3) | (oj ^ ((lane >> 3) & 3)));      // + source wave 2048
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (2 * h >= mb) break;      // (block-uniform: a tile of 16 or 32 rows has no accumulators i >= 2)
+        if (h) __syncthreads();
+#pragma unroll
+        for (int il = 0; il < 2; ++il)
+            if (2 * h + il < mb) {      // (the slots of rows the tile does not have are neither written nor read)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(lds + wr + il * 1024 + 4 * (j ^ swz)) = acc[2 * h + il][j];
+            }
+        __syncthreads();
+        f32x4 v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (2 * h + si < mb) {
+#pragma unroll
+            for (int w = 0; w < 8; ++w) v += *reinterpret_cast<const f32x4*>(lds + w * 2048 + rd);
+        }
+        out[h] = v;
+        if (!g.aux_first) add_out(h, v);      // one round of workgroups: the atomics of a round overlap the next round's LDS traffic
+    }
+    if (g.aux_first) {      // (several rounds of workgroups: the atomics after the last LDS round, as in the dword path)
+        add_out(0, out[0]);
+        if (mb > 2) add_out(1, out[1]);
+    }
+}
+
 __global__ __launch_bounds__(512, 4) void wgrad_t1_kernel(const WgradT1Args g, const AuxJobs aux) {
-    __shared__ float lds[8192];      // [8 waves][16][64] partial quadrants; the reduction jobs use 2 048 floats
+    __shared__ __attribute__((aligned(16))) float lds[16384];      // wide tiles: [8 waves][8 slots][64 lanes] float4; dword tiles: [8 waves][16][64] partial quadrants (the first half); the reduction jobs use 2 048 floats
     const long long t_start = g.trace ? wall_clock64() : 0;
     // The reduction jobs ride in front of the tiles when the tiles need more than one round of the chip's workgroup slots
     // (ragged batches: they would otherwise start when the last tile has been dispatched and BE the tail of the launch,
@@ -160,6 +363,14 @@ __global__ __launch_bounds__(512, 4) void wgrad_t1_kernel(const WgradT1Args g, c
         const int t = local - s * tiles;
         tm = t / nt;
         tn = t - tm * nt;
+    }
+    if (g.p[pi].wide) {      // (per problem, from the host: alignment and pitches; PP_WGRAD_WIDE=0: none)
+        wgrad_tile_wide(g, g.p[pi], tm * 64, tn * 64, s * ks, min(K, s * ks + ks), lds);
+        if (g.trace && threadIdx.x == 0) {
+            long long* tr = g.trace + 8 * blockIdx.x;
+            tr[0] = t_start; tr[1] = wall_clock64(); tr[2] = pi; tr[3] = s;
+        }
+        return;
     }
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -243,8 +454,21 @@ bool wgrad_t1_build(const pp_gemm_args* q, const GemmHole* holes, int n, WgradT1
     static const bool env_wgs_set = false;
     static const int env_wgs = 240;
     if (!env || deterministic_mode() || n <= 0) return false;
+    // PP_WGRAD_WIDE=0: every problem takes the dword loop and its epilogue (read per call, for the A/B and the parity tests)
+    const char* const env_wide = getenv("PP_WGRAD_WIDE");
+    const bool wide_on = !(env_wide && atoi(env_wide) == 0);
     out = WgradT1Args{};
     int np = 0;
+    // The 16-byte loop (wgrad_kloop_wide) takes a problem whose operand pointers are 16-byte aligned after the cut, whose
+    // pitches are multiples of 4 floats, and whose last tile's float2 / float4 (16 vectors from the tile's first column; a
+    // 16-wide edge loads single clamped floats) end inside the row pitch: M = 271 with lda = 272 does (256 + 16 x 1), an odd
+    // pitch or a cut at an odd column does not.
+    auto vec_ok = [](const float* ptr, int64_t ld, int lo, int ext) {
+        if (((uintptr_t)ptr & 15) || (ld & 3)) return false;
+        const int t0 = (ext - 1) / 64 * 64, rem = ext - t0;
+        const int w = rem > 32 ? 4 : rem > 16 ? 2 : 1;
+        return w == 1 || (int64_t)lo + t0 + 16 * w <= ld;
+    };
     // a cut [m_lo, m_hi) x [n_lo, n_hi) of problem a whose first k_lo rows contribute nothing
     auto add = [&](const pp_gemm_args& a, int m_lo, int m_hi, int n_lo, int n_hi, int k_lo) -> bool {
         if (m_hi <= m_lo || n_hi <= n_lo || k_lo >= a.K) return true;
@@ -257,6 +481,7 @@ bool wgrad_t1_build(const pp_gemm_args* q, const GemmHole* holes, int n, WgradT1
         p.lda = (int)a.lda; p.ldb = (int)a.ldb; p.ldc = (int)a.ldc;
         p.M = m_hi - m_lo; p.N = n_hi - n_lo; p.nt = cdiv(p.N, 64);
         p.K = a.K - k_lo;
+        p.wide = (wide_on && vec_ok(p.A, a.lda, m_lo, p.M) && vec_ok(p.B, a.ldb, n_lo, p.N)) ? 1 : 0;
         return true;
     };
     for (int i = 0; i < n; ++i) {
@@ -385,3 +610,20 @@ extern "C" int pp_debug_wgrad_plan(const pp_gemm_args* q, const int32_t* zero_bl
     return a.n_prob;
 }
 
+// Builds the same plan, reports per problem (in the plan's order) whether it takes the 16-byte loop (wide_out[i] = 1) or the
+// dword loop, and with launch != 0 runs the launch on `stream` without reduction jobs: the kernel alone, for tests and
+// timelines. Returns the number of problems; 0: refused (the tile kernels take these products), nothing is launched.
+extern "C" int pp_debug_wgrad_run(const pp_gemm_args* q, const int32_t* zero_blocks, int32_t count, int32_t launch, void* stream,
+                                  int32_t* wide_out, int32_t cap) {
+    std::vector<pp::GemmHole> holes((size_t)std::max(count, 0));
+    for (int i = 0; i < count && zero_blocks; ++i)
+        for (int b = 0; b < 2; ++b) {
+            const int32_t* z = zero_blocks + ((int64_t)i * 2 + b) * 6;
+            holes[i].b[b] = pp::GemmBlock{z[0], z[1], z[2], z[3], z[4], z[5]};
+        }
+    pp::WgradT1Args a;
+    if (!pp::wgrad_t1_build(q, zero_blocks ? holes.data() : nullptr, count, a)) return 0;
+    for (int i = 0; i < a.n_prob && i < cap && wide_out; ++i) wide_out[i] = a.p[i].wide;
+    if (launch && pp::wgrad_t1(a, nullptr, (hipStream_t)stream) != 0) return 0;
+    return a.n_prob;
+}

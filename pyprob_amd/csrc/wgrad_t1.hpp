@@ -19,6 +19,8 @@ struct WgradT1Prob {
     int K, S, ks;        // rows, row splits, rows per split (multiple of 4)
     int first;           // first workgroup of the problem in the launch
     int mtg;             // > 0: XCD-aware tile order (groups of 8 row tiles, see wgrad_t1_kernel); 0: column tiles fastest
+    int wide;            // 1: 16-byte operand loads on v_mfma_f32_16x16x4_f32 and the b128 epilogue (both operands 16-byte aligned,
+                         // pitches multiples of 4, every vector inside its row: wgrad_t1_build); 0: the dword loop
 };
 
 struct WgradT1Args {
