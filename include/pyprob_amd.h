@@ -545,9 +545,16 @@ int pp_is_fused(const pp_net* net, int32_t addr_id, int32_t n, const float* prio
  *                       [M, ldy] (ldy a multiple of 4, >= the head's n_out) receives the head outputs - row g is what
  *                       pp_is_first_statement leaves in its workspace for observation g, up to the rounding of another summation
  *                       order. h_out / c_out: dev [M, H] or NULL - the LSTM state after the statement (for a caller that
- *                       continues with a second statement; ignored by a FeedForward network). FEEDFORWARD observe embeddings, a
- *                       FeedForward network or an LSTM of depth 1; PP_EINVAL otherwise. The launches are those of the training
- *                       step's forward at T = 1: embedding GEMMs, input gather, gate GEMM, cell, head GEMMs.
+ *                       continues with a second statement; ignored by a FeedForward network). FEEDFORWARD and CNN2D5C observe
+ *                       embeddings, a FeedForward network or an LSTM of depth 1; PP_EINVAL otherwise. The launches are those of
+ *                       the training step's forward at T = 1: embedding GEMMs, input gather, gate GEMM, cell, head GEMMs. A
+ *                       CNN2D5C observable (embedding_cnn_2d_5c.py): its M images - columns [ci, ci + C H W) of the obs rows, ci
+ *                       the widths of the observables before it - go through the convolution stack in ONE pass at B = M
+ *                       (pp_cnn2d5c_forward's launches, no backward images) into an [M, round4(F)] feature block of the
+ *                       workspace that _lin1 / _lin2 read, as pp_is_init does for one image. An image's features have the same
+ *                       bits whatever batch it sits in; the linear layers after them pick their shape by M. The workspace grows
+ *                       by the feature block and pp_cnn2d5c_workspace_bytes(o, M) per CNN2D5C observable, laid between the
+ *                       network rows and the fragment images; a network without one keeps its size byte for byte.
  *   pp_is_fused_groups  pp_is_fused for the M n_per particles: particle i = g n_per + j belongs to group g, draws from the
  *                       proposal in row g of `y` (mixture heads; Philox counter offset + i, the key and stream of pp_is_fused and
  *                       pp_is_step - an M-group call consumes exactly the counters of M one-group calls at offset + g n_per),
@@ -588,7 +595,8 @@ int pp_is_fused_groups(const pp_net* net, int32_t addr_id, int32_t n_groups, int
  *                       rows do not depend on the shard's size (the GEMMs of pp_is_batch_first pick their shape by the row
  *                       count). One launch on a (gate column, group) grid running pp_is_step's own bias
  *                       code: the products and their order are those of the single call and do not depend on M. One-layer LSTM,
- *                       FEEDFORWARD observe embeddings, a mixture head at addr_id (the only consumer is the call below).
+ *                       FEEDFORWARD or CNN2D5C observe embeddings (the rows are read, no image is embedded again), a mixture head
+ *                       at addr_id (the only consumer is the call below).
  *   pp_is_statement_groups  the whole statement as ONE launch of the grouped fused statement kernel, whatever n_per: particle
  *                       i = g n_per + j starts from bias row g (`bias` dev [M, 4H]); c0 != NULL (dev [M, H]): every particle of
  *                       group g has the previous state (h_g, c_g) - h_g W_hh^T is part of bias row g, the cell reads c0[g] and
@@ -755,6 +763,30 @@ int pp_mix_draw(const pp_mixture* mix, const int64_t* rows, int32_t m, int32_t n
 typedef struct pp_obs_operand { const float* p; int64_t row_stride; int32_t elem_stride; int32_t _pad; } pp_obs_operand;
 int pp_obs_logweight(int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t k, float scale, float* lw /*dev [n]*/,
                      float* lp_out, const int64_t* rows, int32_t m, int32_t n, void* stream);
+
+/* pp_obs_logweight for the n_groups * n_per rows of a batched posterior call (pp_is_fused_groups' layout): row i = g * n_per + j
+ * belongs to group g = i / n_per. per_group marks the operands that hold ONE ROW PER GROUP: bit q < 4 - params[q], bit 4 - x
+ * (PP_OBS_PER_GROUP_X). A marked operand is read as p[g * row_stride + e * elem_stride], every other one as
+ * p[i * row_stride + e * elem_stride], with all the stride forms of pp_obs_logweight. The normal use: x = the [n_groups, k]
+ * observed images (bit 4), params[0] = the [n_groups * n_per, k] means of the particles. Nothing is materialised to
+ * [n_groups * n_per, k]: the per-particle operands are read once, a group's row is re-read by its n_per rows from the caches.
+ *     lw[i] += scale * lp[i],  lp_out[i] = lp[i]     for every i < n_groups * n_per (there is no row list)
+ * Contracts:
+ *  - ONE FORMULA, ONE SUMMATION ORDER: row i has the bits pp_obs_logweight gives a row with the same element values - the same
+ *    compiled arithmetic (scalar_log_prob_at, the 256 slots, the butterfly, the two roundings of lw += scale * lp), the lanes
+ *    per row a function of k alone.
+ *  - THE GROUP SIZE CANNOT CHANGE A BIT: the group index selects row addresses and never enters the arithmetic; rows of
+ *    different groups share a wave whenever k <= 128, n_per need not divide anything, any n_per >= 1 is accepted.
+ *  - ADDRESSING: 64-bit offsets (n_groups * n_per and g * row_stride may pass 2^31). The 16-byte path has pp_obs_logweight's
+ *    condition, applied to a per-group operand's own base and row stride (a [n_groups, k] block with k % 4 != 0 is read with
+ *    4-byte loads); both paths give the same bits. No float atomics; one dependent launch on `stream`.
+ * Returns nonzero without a launch (pp_last_error names pp_obs_logweight_groups) for a kind outside the list, k < 1,
+ * n_groups < 0, n_per < 1, a per_group outside 0..31, a NULL pointer or a negative stride of an operand the kind needs or of x,
+ * lw and lp_out both NULL. n_groups == 0 returns 0 without a launch. */
+#define PP_OBS_PER_GROUP_X 16
+int pp_obs_logweight_groups(int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t per_group, int32_t k,
+                            float scale, float* lw /*dev [n_groups * n_per]*/, float* lp_out, int32_t n_groups, int32_t n_per,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * Individual kernels (used by the whole-path entry points; exported for unit parity tests and profiling)

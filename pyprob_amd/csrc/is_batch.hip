@@ -4,7 +4,8 @@
 // pyprob/nn/inference_network.py:141-148; every trace's first _infer_step runs on that one embedding,
 // pyprob/nn/inference_network_lstm.py:82-134), so posteriors for M observations are M calls. Here
 //   pp_is_batch_first   evaluates embedding + first LSTM step + proposal layer for M observation rows at once (the launches of
-//                       the training step's forward at T = 1: embedding GEMMs, input gather, gate GEMM, cell, head GEMMs), and
+//                       the training step's forward at T = 1: [the convolution stack of a CNN2D5C observable at B = M,] embedding
+//                       GEMMs, input gather, gate GEMM, cell, head GEMMs), and
 //   pp_is_fused_groups  is pp_is_fused's pass with the proposal of particle i read from row i / n_per of the head outputs and
 //                       per-group operands, followed by the importance statistics of every group.
 //   pp_is_batch_bias    writes, for a LATER statement (prev_addr_id >= 0), the bias row of every group: what is_prep_kernel computes
@@ -12,6 +13,7 @@
 //   pp_is_statement_groups  runs that statement for all M n_per particles as ONE launch of the GROUPED fused statement kernel
 //                       (is_step_fused.hip, is_step_small.hip): particle i starts from bias row i / n_per.
 // Draw and log-density arithmetic is is_draw.hpp's (mixture_particle, term_log_prob) and head_math.hpp's: nothing is restated.
+#include "cnn2d.hpp"
 #include "common.hpp"
 #include "gather.hpp"
 #include "is_draw.hpp"
@@ -173,6 +175,9 @@ struct BatchWorkspace {
     double* partial;          // FIRST: pp_is_fused_groups needs nothing else
     float *oh0, *oh1, *cat, *f1, *E, *X, *G, *A1, *h, *c;
     int64_t e4, i4, hid4, out4, ohid4;
+    float* cnn_feat[PP_MAX_OBS];      // a CNN2D5C observable's [M, round4(F)] features and the scratch of its convolution stack at B = M
+    void* cnn_ws[PP_MAX_OBS];
+    size_t cnn_ws_bytes[PP_MAX_OBS];
     IsFusedBuffers fz;        // LAST: the fragment images of pp_is_statement_groups (empty: no fused statement kernel for this network)
     size_t bytes;
 };
@@ -211,6 +216,15 @@ void batch_carve(const pp_net* net, int M, void* p, BatchWorkspace& w) {
     w.A1 = takef(M * w.hid4);
     w.h = takef((int64_t)M * H);
     w.c = takef((int64_t)M * H);
+    // (after every block a network without an image observable has: such a network keeps its size and offsets byte for byte)
+    for (int o = 0; o < PP_MAX_OBS; ++o) {
+        w.cnn_feat[o] = nullptr; w.cnn_ws[o] = nullptr; w.cnn_ws_bytes[o] = 0;
+        if (o < net->n_obs && net->obs_kind[o] == PP_OBS_CNN2D5C) {
+            w.cnn_feat[o] = takef(M * r4(net->obs_feat[o]));
+            w.cnn_ws_bytes[o] = cnn_workspace_bytes(net, o, M);
+            w.cnn_ws[o] = take((int64_t)w.cnn_ws_bytes[o]);
+        }
+    }
     is_fused_carve_sizes(net, w.fz);
     w.fz.whh = takef(w.fz.n_whh);
     w.fz.w1 = takef(w.fz.n_w1);
@@ -232,8 +246,10 @@ int lin(const float* x, int64_t ldx, const float* W, const float* b, const float
 
 bool batch_net_ok(const pp_net* net) {
     if (!net || net->n_obs < 1 || net->n_obs > PP_MAX_OBS) return false;
-    for (int o = 0; o < net->n_obs; ++o)
-        if (net->obs_kind[o] != PP_OBS_FEEDFORWARD) return false;
+    for (int o = 0; o < net->n_obs; ++o) {
+        CnnGeom g;
+        if (net->obs_kind[o] != PP_OBS_FEEDFORWARD && !(net->obs_kind[o] == PP_OBS_CNN2D5C && cnn_geom(net, o, g))) return false;
+    }
     return net->lstm_dim == 0 || std::max(1, (int)net->lstm_depth) == 1;
 }
 
@@ -242,7 +258,7 @@ bool batch_net_ok(const pp_net* net) {
 int is_batch_first(const pp_net* net, const float* P, const float* obs, int addr_id, int M, float* y_out, int64_t ldy, float* h_out,
                    float* c_out, void* ws, size_t ws_bytes, hipStream_t st) {
     PP_CHECK_ARG(net && P && obs && y_out && ws, "pp_is_batch_first: null pointer");
-    PP_CHECK_ARG(batch_net_ok(net), "pp_is_batch_first: FEEDFORWARD observe embeddings and a FeedForward network or an LSTM of depth 1");
+    PP_CHECK_ARG(batch_net_ok(net), "pp_is_batch_first: FEEDFORWARD or CNN2D5C observe embeddings and a FeedForward network or an LSTM of depth 1");
     PP_CHECK_ARG(addr_id >= 0 && addr_id < net->n_addr, "pp_is_batch_first: address id out of range");
     PP_CHECK_ARG(M >= 0, "pp_is_batch_first: negative group count");
     const pp_addr& ad = net->addrs[addr_id];
@@ -255,7 +271,9 @@ int is_batch_first(const pp_net* net, const float* P, const float* obs, int addr
         return PP_ENOSPACE;
     }
     // _infer_init for M rows: EmbeddingFeedForward per observable (the hidden rows ping-pong between two buffers), concatenation,
-    // the two final layers (inference_network.py:132-148)
+    // the two final layers (inference_network.py:132-148). A CNN2D5C observable: its M images (columns [ci, ci + C H W) of the rows)
+    // through the convolution stack at B = M, _lin1 / _lin2 read the [M, round4(F)] features - pp_is_init's route for one image
+    // (an image's features do not depend on the batch it sits in, cnn2d.hip).
     int ci = 0, co = 0, width = 0;
     for (int o = 0; o < net->n_obs; ++o) width += net->obs_in[o];
     for (int o = 0; o < net->n_obs; ++o) {
@@ -263,6 +281,11 @@ int is_batch_first(const pp_net* net, const float* P, const float* obs, int addr
         const float* x = obs + ci;
         int64_t ldx = width;
         int in = net->obs_in[o];
+        if (net->obs_kind[o] == PP_OBS_CNN2D5C) {
+            const int64_t f4 = r4(net->obs_feat[o]);
+            PP_TRY(cnn_forward(net, o, P, x, ldx, M, w.cnn_feat[o], f4, w.cnn_ws[o], w.cnn_ws_bytes[o], false, st));
+            x = w.cnn_feat[o]; ldx = f4; in = net->obs_feat[o];
+        }
         for (int l = 0; l < depth; ++l) {
             const bool last = l == depth - 1;
             const int out = last ? net->obs_out[o] : net->obs_hid[o];
@@ -441,7 +464,7 @@ int is_batch_bias(const pp_net* net, const float* P, int addr_id, int prev_addr_
                   const float* h_prev, float* bias_out, void* ws, size_t ws_bytes, hipStream_t st) {
     PP_CHECK_ARG(net && P && bias_out && ws, "pp_is_batch_bias: null pointer");
     PP_CHECK_ARG(batch_net_ok(net) && net->lstm_dim > 0 && net->lstm_dim <= 1024 && net->addr_table,
-                 "pp_is_batch_bias: FEEDFORWARD observe embeddings and an LSTM of depth 1 with at most 1024 hidden units");
+                 "pp_is_batch_bias: FEEDFORWARD or CNN2D5C observe embeddings and an LSTM of depth 1 with at most 1024 hidden units");
     PP_CHECK_ARG(addr_id >= 0 && addr_id < net->n_addr && prev_addr_id >= 0 && prev_addr_id < net->n_addr,
                  "pp_is_batch_bias: a statement after the first one (address ids in range, prev_addr_id >= 0)");
     PP_CHECK_ARG(M >= 0 && first_group >= 0 && (int64_t)first_group + M <= ws_groups,

@@ -2,6 +2,8 @@
 // trace.py:123-125, which sums an observed variable's log_prob over its elements): one row of k values per particle - an image,
 // a k-vector - scored in one launch. pp_dist_logweight (dist_kernels.hip) is the scalar form; this kernel is its k-wide form
 // and for k = 1 gives the same bits. The per-element formula is dist_math.hpp's scalar_log_prob_at, nothing else.
+// pp_obs_logweight_groups is the same kernel for the M n_per rows of a batched posterior call (is_batch.hip), where an operand may
+// hold one row per GROUP (the observed image of each group): a template flag that resolves row pointers, one copy of everything else.
 #include "common.hpp"
 #include "dist_math.hpp"
 
@@ -19,6 +21,7 @@ struct ObsOperand {
 struct ObsArgs {
     ObsOperand q[4];
     ObsOperand x;
+    int per_group;      // pp_obs_logweight_groups: bit q < 4 - q[q], bit 4 - x is addressed with the row's GROUP index
 };
 
 // SUMMATION ORDER (include/pyprob_amd.h states it as part of the ABI). A row has 256 slots; element e belongs to slot e & 255.
@@ -56,15 +59,18 @@ __device__ __forceinline__ constexpr int obs_n_params() {
 // then read again by elements); otherwise 4-byte loads through the stride pairs (an element index past the row's end reads the
 // row's last element again). Both ways fill the SAME registers and fall into the SAME instructions that evaluate and add the
 // log-densities: there is one compiled copy of the arithmetic per family, so how the values were delivered cannot change a bit.
-template <int KIND, int U>
-__device__ __forceinline__ void obs_row(const ObsArgs& A, bool fast, int64_t r, int l, int G, int nfull, int ng, int k, float& s0,
-                                        float& s1, float& s2, float& s3) {
+// GROUPS (pp_obs_logweight_groups): an operand marked in A.per_group starts its row at group index gr instead of r. The group
+// index picks row POINTERS and nothing else: from the loads on, the code is the code of GROUPS = false.
+template <int KIND, int U, bool GROUPS>
+__device__ __forceinline__ void obs_row(const ObsArgs& A, bool fast, int64_t r, int64_t gr, int l, int G, int nfull, int ng, int k,
+                                        float& s0, float& s1, float& s2, float& s3) {
     constexpr int NP = obs_n_params<KIND>();
-    const float* ar = A.q[0].p + r * A.q[0].rs;
-    const float* xr = A.x.p + r * A.x.rs;
-    const float* br = NP >= 2 ? A.q[1].p + r * A.q[1].rs : ar;
-    const float* cr = NP >= 4 ? A.q[2].p + r * A.q[2].rs : ar;
-    const float* dr = NP >= 4 ? A.q[3].p + r * A.q[3].rs : ar;
+    const auto row = [&](int q) -> int64_t { return GROUPS && ((A.per_group >> q) & 1) ? gr : r; };
+    const float* ar = A.q[0].p + row(0) * A.q[0].rs;
+    const float* xr = A.x.p + row(4) * A.x.rs;
+    const float* br = NP >= 2 ? A.q[1].p + row(1) * A.q[1].rs : ar;
+    const float* cr = NP >= 4 ? A.q[2].p + row(2) * A.q[2].rs : ar;
+    const float* dr = NP >= 4 ? A.q[3].p + row(3) * A.q[3].rs : ar;
     const int64_t ea = A.q[0].es, eb = NP >= 2 ? A.q[1].es : 0, ec = NP >= 4 ? A.q[2].es : 0, ed = NP >= 4 ? A.q[3].es : 0,
                   ex = A.x.es;
     for (int i0 = l; i0 < ng; i0 += U * G) {
@@ -130,10 +136,12 @@ __device__ __forceinline__ void obs_row(const ObsArgs& A, bool fast, int64_t r, 
     }
 }
 
-template <int KIND>
+// GROUPS: m = n_groups * n_per rows without a row list, row j of group j / n_per (a workgroup, and for k <= 128 a wave, may
+// straddle groups: the lanes of a row are still the G lanes they are in the plain kernel).
+template <int KIND, bool GROUPS>
 __global__ __launch_bounds__(256) void obs_logweight_kernel(ObsArgs A, int fast, int k, int G, float scale, float* __restrict__ lw,
                                                             float* __restrict__ lp_out, const int64_t* __restrict__ rows,
-                                                            int m) {
+                                                            int64_t m, int n_per) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l = lane & (G - 1);          // the lane holds slots 4l .. 4l + 3
     const int rpw = 64 / G;                // rows per wave
@@ -142,13 +150,14 @@ __global__ __launch_bounds__(256) void obs_logweight_kernel(ObsArgs A, int fast,
     for (int64_t base = ((int64_t)blockIdx.x * 4 + wave) * rpw; base < m; base += step) {      // (wave-uniform)
         const int64_t j = base + lane / G;
         const bool live = j < m;
-        const int64_t r = live ? (rows ? rows[j] : j) : 0;
+        const int64_t r = live ? (!GROUPS && rows ? rows[j] : j) : 0;
+        const int64_t gr = GROUPS ? r / n_per : 0;
         float s0 = -0.0f, s1 = -0.0f, s2 = -0.0f, s3 = -0.0f;      // the lane's four slots
         if (live) {
             if (ng > G)      // (a function of k alone, like G)
-                obs_row<KIND, 4>(A, fast != 0, r, l, G, nfull, ng, k, s0, s1, s2, s3);
+                obs_row<KIND, 4, GROUPS>(A, fast != 0, r, gr, l, G, nfull, ng, k, s0, s1, s2, s3);
             else
-                obs_row<KIND, 1>(A, fast != 0, r, l, G, nfull, ng, k, s0, s1, s2, s3);
+                obs_row<KIND, 1, GROUPS>(A, fast != 0, r, gr, l, G, nfull, ng, k, s0, s1, s2, s3);
         }
         float acc = (s0 + s1) + (s2 + s3);
         for (int d = 1; d < G; d <<= 1) acc += __shfl_xor(acc, d);      // (G is wave-uniform: every lane takes every stage)
@@ -165,58 +174,84 @@ static inline bool obs_aligned_run(const ObsOperand& o) {
     return o.es == 1 && (reinterpret_cast<uintptr_t>(o.p) & 15u) == 0 && (o.rs & 3) == 0;
 }
 
-}  // namespace pp
-
-extern "C" {
-
-int pp_obs_logweight(int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t k, float scale, float* lw,
-                     float* lp_out, const int64_t* rows, int32_t m, int32_t n, void* stream) {
+// The checks and the launch behind both entry points. groups: m = n_groups * n_per rows, no row list, per_group marks.
+static int obs_logweight_launch(const char* who, int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t k,
+                                float scale, float* lw, float* lp_out, const int64_t* rows, int64_t m, bool groups, int n_per,
+                                int per_group, void* stream) {
     if (kind < 0 || kind > PP_DIST_MAX_KIND || kind == 2 || kind == 5) {
-        pp::set_error("pp_obs_logweight: kind %d is not a scalar family (0, 1, 3, 4, 6-13)", (int)kind);
-        return PP_EINVAL;
-    }
-    if (k < 1 || n < 0 || m < 0 || (!rows && m != n) || m > n) {
-        pp::set_error("pp_obs_logweight: k >= 1 values per row, 0 <= m <= n rows, m = n without a row list (k %d, m %d, n %d)", (int)k,
-                      (int)m, (int)n);
+        set_error("%s: kind %d is not a scalar family (0, 1, 3, 4, 6-13)", who, (int)kind);
         return PP_EINVAL;
     }
     if (!lw && !lp_out) {
-        pp::set_error("pp_obs_logweight: lw or lp_out is needed");
+        set_error("%s: lw or lp_out is needed", who);
         return PP_EINVAL;
     }
-    const int np = pp::obs_kind_params(kind);
-    pp::ObsArgs A{};
+    const int np = obs_kind_params(kind);
+    ObsArgs A{};
     for (int q = 0; q < np; ++q) {
         if (!params || !params[q].p || params[q].row_stride < 0 || params[q].elem_stride < 0) {
-            pp::set_error("pp_obs_logweight: kind %d needs parameter %d (a pointer and strides >= 0)", (int)kind, q);
+            set_error("%s: kind %d needs parameter %d (a pointer and strides >= 0)", who, (int)kind, q);
             return PP_EINVAL;
         }
-        A.q[q] = pp::ObsOperand{params[q].p, params[q].row_stride, params[q].elem_stride};
+        A.q[q] = ObsOperand{params[q].p, params[q].row_stride, params[q].elem_stride};
     }
     if (!x.p || x.row_stride < 0 || x.elem_stride < 0) {
-        pp::set_error("pp_obs_logweight: no value block (a pointer and strides >= 0)");
+        set_error("%s: no value block (a pointer and strides >= 0)", who);
         return PP_EINVAL;
     }
-    A.x = pp::ObsOperand{x.p, x.row_stride, x.elem_stride};
+    A.x = ObsOperand{x.p, x.row_stride, x.elem_stride};
+    A.per_group = groups ? per_group : 0;
     if (m == 0) return 0;
     bool fast = k >= 4;
     for (int q = 1; q < np; ++q) fast = fast && A.q[q].es == 0;
-    fast = fast && (A.q[0].es == 0 || pp::obs_aligned_run(A.q[0])) && (A.x.es == 0 || pp::obs_aligned_run(A.x)) &&
+    fast = fast && (A.q[0].es == 0 || obs_aligned_run(A.q[0])) && (A.x.es == 0 || obs_aligned_run(A.x)) &&
            (A.q[0].es == 1 || A.x.es == 1);
-    const int G = pp::obs_group(k);
+    const int G = obs_group(k);
     const int64_t rpb = 4 * (64 / G);      // rows per workgroup
     const dim3 grid((unsigned)std::min<int64_t>(65536, (m + rpb - 1) / rpb)), block(256);
-    hipStream_t st = pp::as_stream(stream);
-#define PP_OBS_LW(K) \
-    case K: hipLaunchKernelGGL((pp::obs_logweight_kernel<K>), grid, block, 0, st, A, fast ? 1 : 0, k, G, scale, lw, lp_out, rows, m); break
+    hipStream_t st = as_stream(stream);
+#define PP_OBS_LW(K)                                                                                                                  \
+    case K:                                                                                                                           \
+        if (groups)                                                                                                                   \
+            hipLaunchKernelGGL((obs_logweight_kernel<K, true>), grid, block, 0, st, A, fast ? 1 : 0, k, G, scale, lw, lp_out, rows, m, \
+                               n_per);                                                                                                \
+        else                                                                                                                          \
+            hipLaunchKernelGGL((obs_logweight_kernel<K, false>), grid, block, 0, st, A, fast ? 1 : 0, k, G, scale, lw, lp_out, rows, m, \
+                               n_per);                                                                                                \
+        break
     switch (kind) {
         PP_OBS_LW(0); PP_OBS_LW(1); PP_OBS_LW(3); PP_OBS_LW(4); PP_OBS_LW(6); PP_OBS_LW(7); PP_OBS_LW(8); PP_OBS_LW(9);
         PP_OBS_LW(10); PP_OBS_LW(11); PP_OBS_LW(12); PP_OBS_LW(13);
         default: break;
     }
 #undef PP_OBS_LW
-    PP_LAUNCH_CHECK("pp_obs_logweight");
+    PP_LAUNCH_CHECK(who);
     return 0;
+}
+
+}  // namespace pp
+
+extern "C" {
+
+int pp_obs_logweight(int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t k, float scale, float* lw,
+                     float* lp_out, const int64_t* rows, int32_t m, int32_t n, void* stream) {
+    if (k < 1 || n < 0 || m < 0 || (!rows && m != n) || m > n) {
+        pp::set_error("pp_obs_logweight: k >= 1 values per row, 0 <= m <= n rows, m = n without a row list (k %d, m %d, n %d)", (int)k,
+                      (int)m, (int)n);
+        return PP_EINVAL;
+    }
+    return pp::obs_logweight_launch("pp_obs_logweight", kind, params, x, k, scale, lw, lp_out, rows, m, false, 1, 0, stream);
+}
+
+int pp_obs_logweight_groups(int32_t kind, const pp_obs_operand params[4], pp_obs_operand x, int32_t per_group, int32_t k, float scale,
+                            float* lw, float* lp_out, int32_t n_groups, int32_t n_per, void* stream) {
+    if (k < 1 || n_groups < 0 || n_per < 1 || per_group < 0 || per_group > 31) {
+        pp::set_error("pp_obs_logweight_groups: k >= 1 values per row, n_groups >= 0 groups of n_per >= 1 rows, per_group a mask of "
+                      "bits 0-4 (k %d, n_groups %d, n_per %d, per_group %d)", (int)k, (int)n_groups, (int)n_per, (int)per_group);
+        return PP_EINVAL;
+    }
+    return pp::obs_logweight_launch("pp_obs_logweight_groups", kind, params, x, k, scale, lw, lp_out, nullptr,
+                                    (int64_t)n_groups * n_per, true, n_per, per_group, stream);
 }
 
 }  // extern "C"

@@ -737,9 +737,10 @@ class ISRunner(DistRunner):
 
     # ---- batched posteriors: M observations x n_per particles in one call (pp_is_batch_first, pp_is_fused_groups) --------------
     def batch_supported(self):
-        """Does pp_is_batch_first take this network (FEEDFORWARD observe embeddings, FeedForward or a one-layer LSTM)?"""
+        """Does pp_is_batch_first take this network (FEEDFORWARD and CNN2D5C observe embeddings, FeedForward or a one-layer LSTM)?"""
         net = self.eng.net
-        return (self.dev.type == 'cuda' and all(net.obs_kind[o] == L.PP_OBS_FEEDFORWARD for o in range(net.n_obs)) and
+        return (self.dev.type == 'cuda' and
+                all(net.obs_kind[o] in (L.PP_OBS_FEEDFORWARD, L.PP_OBS_CNN2D5C) for o in range(net.n_obs)) and
                 (self.eng.spec.lstm_dim == 0 or max(1, self.eng.spec.lstm_depth) == 1))
 
     def init_batch(self, obs, rows=None, cache=None):
@@ -840,6 +841,20 @@ class ISRunner(DistRunner):
                                             lw.data_ptr(), (1 if overwrite else 0) | per_particle, int(seed), int(offset), L.ptr(out),
                                             self._b_ws.data_ptr(), self._b_ws.numel(), st), 'pp_is_fused_groups')
         return out
+
+    def obs_logweight_groups(self, lw, term, x, x_per_group, n_groups, n_per, scale=1.0):
+        """lw[i] += scale * sum_e log p(x[., e] | parameters[i, e]) for the M n_per particles of a batched call in one launch
+        (pp_obs_logweight_groups): `term` a VecTerm built for width M n_per (parameters shared or per particle), x the observed
+        values - [M, k] one row per group (x_per_group), else [k] shared by all or [M n_per, k] per particle."""
+        k = int(term.k)
+        if x_per_group:
+            x = x.reshape(int(n_groups), k)
+        elif x.numel() == k:
+            x = x.reshape(k)
+        else:
+            x = x.reshape(int(n_groups) * int(n_per), k)
+        ops.obs_logweight_groups(lw, int(term.kind), term.params, x, L.PP_OBS_PER_GROUP_X if x_per_group else 0, k, float(scale),
+                                 None, int(n_groups), int(n_per))
 
     PRIOR_KIND = {'Normal': 0, 'Uniform': 1}
 

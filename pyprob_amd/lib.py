@@ -85,6 +85,7 @@ class pp_dist_term(C.Structure):
 
 
 PP_MIX_MAX_COMPONENTS = 16
+PP_OBS_PER_GROUP_X = 16      # pp_obs_logweight_groups: bit 4 of per_group marks x, bit q < 4 params[q]
 
 
 class pp_mixture(C.Structure):
@@ -187,6 +188,7 @@ PROTOTYPES = {
     'pp_dist_draw': (C.c_int, [C.POINTER(pp_dist), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_mix_logweight': (C.c_int, [C.POINTER(pp_mixture), vp, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
     'pp_obs_logweight': (C.c_int, [i32, C.POINTER(pp_obs_operand), pp_obs_operand, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
+    'pp_obs_logweight_groups': (C.c_int, [i32, C.POINTER(pp_obs_operand), pp_obs_operand, i32, i32, C.c_float, vp, vp, i32, i32, vp]),
     'pp_mix_draw': (C.c_int, [C.POINTER(pp_mixture), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_gemm_f32': (C.c_int, [C.POINTER(pp_gemm_args), vp]),
     'pp_gemm_f32_grouped': (C.c_int, [C.POINTER(pp_gemm_args), i32, vp]),

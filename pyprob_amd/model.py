@@ -861,10 +861,13 @@ class Model:
         A lock-step-safe STRAIGHT-LINE program - a first controlled sample statement on a mixture head (Normal / Uniform / Poisson
         prior), any number of later Normal / Uniform statements whose priors may depend on earlier draws (one-layer LSTM networks
         of 32, 64, 128, 256 or 512 hidden units, or a FeedForward network) -, at most 8 scalar observes of
-        the network's families and FEEDFORWARD observe embeddings runs all M * num_traces particles in ONE lock-step execution
+        the network's families, any number of vector or image observes of the scalar families (Normal, Uniform, Poisson, ...: one
+        launch each over all M * num_traces rows, pp_obs_logweight_groups) and FEEDFORWARD or CNN2D5C observe embeddings (the M
+        images pass the convolution stack once, at batch M) runs all M * num_traces particles in ONE lock-step execution
         of forward() (the reference: M posterior calls, pyprob/model.py:106-117); an observed value the program reads is then one
-        value per group. The per-particle LSTM state of later statements is held to PP_BATCH_STATE_BYTES (default 4 GiB) per
-        execution by sharding over groups. Anything else (branches, other heads at later statements, H = 1024, deeper LSTMs) is
+        value (vector, image) per group. The per-particle LSTM state of later statements is held to PP_BATCH_STATE_BYTES (default 4 GiB) per
+        execution by sharding over groups. Anything else (branches, other heads at the first or at later statements, a Mixture or
+        Categorical likelihood over a vector, H = 1024, deeper LSTMs) is
         served by that loop of posterior_results calls; which of the two is remembered per model."""
         names, dicts, cols = self._normalise_observes(observes)
         M, N = len(dicts), int(num_traces)
@@ -880,20 +883,23 @@ class Model:
         ok = getattr(self, '_batch_ok', None)
         if ok is None and not (net._is.batch_supported() and (lock_step or self._lock_step_safe(dicts[0], *args, **kwargs))):
             ok = self._batch_ok = False
-        if ok is False or any(c.shape[1] != 1 for c in cols.values()):      # (a vector or image observe: the loop)
+        if ok is False:
             return loop()
         try:
             runner = net._is
+            events = {k: tuple(torch.as_tensor(dicts[0][k]).shape) for k in names}
             with torch.cuda.device(runner.dev):
-                return self._traces_lockstep_batch(N, names, cols, seed, offset, likelihood_importance, *args, **kwargs)
+                return self._traces_lockstep_batch(N, names, cols, seed, offset, likelihood_importance, *args, event_shapes=events,
+                                                   **kwargs)
         except state.BatchUnsupported:      # (nothing else: a device or runtime error of the fast path is the caller's to see)
             self._batch_ok = False
         return loop()
 
-    def _traces_lockstep_batch(self, num_traces, names, cols, seed, offset, likelihood_importance, *args, **kwargs):
+    def _traces_lockstep_batch(self, num_traces, names, cols, seed, offset, likelihood_importance, *args, event_shapes=None, **kwargs):
         """The fast path of posterior_results_batch: one execution of forward() for M * num_traces particles (state.BatchLockStepState),
         sharded over groups where M * num_traces reaches the 2^32 / lstm_dim elements the state rows are addressed with. The M
-        Empiricals are slices of the call's device tensors; their statistics come back in ONE device-to-host copy."""
+        Empiricals are slices of the call's device tensors; their statistics come back in ONE device-to-host copy.
+        The program sees observable `name` as a GroupTensor [M, *event_shapes[name]] (a scalar: [M]; an image: [M, C, H, W])."""
         net = self._inference_network
         runner = net._is
         M, N = int(next(iter(cols.values())).shape[0]), int(num_traces)
@@ -925,7 +931,11 @@ class Model:
                 g1 = min(M, g0 + groups)
                 obs = state.GroupObserves()
                 for k, c in cols.items():
-                    obs[k] = torch.from_numpy(np.ascontiguousarray(c[g0:g1, 0])).to(runner.dev).as_subclass(state.GroupTensor)
+                    event = tuple((event_shapes or {}).get(k, ()))
+                    if int(np.prod(event, dtype=np.int64)) != c.shape[1]:      # (no shape given: a scalar or a flat vector)
+                        event = () if c.shape[1] == 1 else (int(c.shape[1]),)
+                    obs[k] = torch.from_numpy(np.ascontiguousarray(c[g0:g1]).reshape((g1 - g0,) + event)).to(runner.dev) \
+                        .as_subclass(state.GroupTensor)
                 if share and groups < M:
                     obs.matrix, obs.rows, obs.cache = full, (g0, g1), cache
                 else:

@@ -21,6 +21,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     mix_logweight   Mixture.log_prob as a log-weight term               pyprob/distributions/mixture.py:38-45
     obs_draw        the synthetic observation block of n prior traces   pyprob/nn/dataset.py:50-62, state.py observe branch
     obs_logweight   the summed log-density of a vector-valued observe    pyprob/state.py:118-155, trace.py:123-125
+    obs_logweight_groups  the same for the M N rows of a batched call, operands per particle or per group
     mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -66,6 +67,8 @@ _lib.define('prior_draw(int kind, Tensor p0, Tensor p1, int n, int seed, int off
 _lib.define('obs_draw(int kind, Tensor p0, Tensor p1, int n, int k, int seed, int offset, int stream_id) -> Tensor')
 _lib.define('obs_logweight(Tensor(a!)? lw, int kind, Tensor?[] params, Tensor x, int k, float scale, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
+_lib.define('obs_logweight_groups(Tensor(a!)? lw, int kind, Tensor?[] params, Tensor x, int per_group, int k, float scale, '
+            'Tensor(b!)? lp_out, int n_groups, int n_per) -> ()')
 _lib.define('log_prob(int kind, Tensor p0, int p0_stride, Tensor? p1, int p1_stride, Tensor x, int n) -> Tensor')
 _lib.define('logweight_terms(Tensor(a!) lw, int[] kinds, Tensor?[] p0, int[] p0_strides, Tensor?[] p1, int[] p1_strides, '
             'Tensor[] x, float[] scales, bool overwrite) -> ()')
@@ -473,6 +476,54 @@ def _obs_logweight_hip(lw, kind, params, x, k, scale, rows, lp_out, n):
     L.check(rc, 'pp_obs_logweight')
 
 
+def obs_group_operands(params, x, per_group, n_groups, n_per, k):
+    """The five operands (params[0..3], x) of pp_obs_logweight_groups as (tensor, row stride, element stride) or None: an operand
+    whose bit is set in per_group (bit q < 4: params[q], bit 4: x) holds one row per GROUP and is classified by obs_draw_strides with
+    n = n_groups rows ([M, k], [M, *event], a padded [M, k] view, [M, 1], or a shape shared by all rows); every other one with
+    n = n_groups * n_per rows."""
+    out = []
+    for q, t in enumerate(list(params) + [x]):
+        if t is None:
+            out.append(None)
+            continue
+        name = 'x' if q == 4 else 'p%d' % q
+        if t.dtype != torch.float32:
+            raise RuntimeError('pyprob_hip: %s must be a float32 tensor' % name)
+        rows = n_groups if (per_group >> q) & 1 else n_groups * n_per
+        rs, es = obs_draw_strides(t, rows, k, name, 'obs_logweight')
+        out.append((t, int(rs), int(es)))
+    return out
+
+
+def _obs_logweight_groups_hip(lw, kind, params, x, per_group, k, scale, lp_out, n_groups, n_per):
+    lib = L.load()
+    n_groups, n_per, k, per_group = int(n_groups), int(n_per), int(k), int(per_group)
+    if len(params) != 4:
+        raise RuntimeError('pyprob_hip::obs_logweight_groups: 4 parameter slots')
+    ref = lw if lw is not None else lp_out
+    if ref is None:
+        raise RuntimeError('pyprob_hip::obs_logweight_groups: lw or lp_out is needed')
+    if n_groups < 0 or n_per < 1 or k < 1 or not 0 <= per_group <= 31:
+        raise RuntimeError('pyprob_hip::obs_logweight_groups: n_groups >= 0 groups of n_per >= 1 rows of k >= 1 values and a mask '
+                           'of bits 0-4, got n_groups = %d, n_per = %d, k = %d, per_group = %d' % (n_groups, n_per, k, per_group))
+    n = n_groups * n_per
+    for t, name in ((lw, 'lw'), (lp_out, 'lp_out')):
+        if t is not None and (_f32(t, name).numel() != n):
+            raise RuntimeError('pyprob_hip::obs_logweight_groups: %s must have n_groups n_per = %d elements' % (name, n))
+    _same_device(ref, lw, lp_out, x, *params)
+    operands = obs_group_operands(params, x, per_group, n_groups, n_per, k)
+    arr = (L.pp_obs_operand * 4)()
+    xo = L.pp_obs_operand()
+    for q, o in enumerate(operands):
+        if o is not None:
+            dst = xo if q == 4 else arr[q]
+            dst.p, dst.row_stride, dst.elem_stride = o[0].data_ptr(), o[1], o[2]
+    with torch.cuda.device(ref.device):
+        rc = lib.pp_obs_logweight_groups(int(kind), arr, xo, per_group, k, float(scale), L.ptr(lw), L.ptr(lp_out), n_groups, n_per,
+                                         _stream(ref))
+    L.check(rc, 'pp_obs_logweight_groups')
+
+
 def _log_prob_hip(kind, p0, p0_stride, p1, p1_stride, x, n):
     lib = L.load()
     _same_device(x, p0, p1)
@@ -647,6 +698,7 @@ _lib.impl('is_fused', _is_fused_hip, 'CUDA')
 _lib.impl('prior_draw', _prior_draw_hip, 'CUDA')
 _lib.impl('obs_draw', _obs_draw_hip, 'CUDA')
 _lib.impl('obs_logweight', _obs_logweight_hip, 'CUDA')
+_lib.impl('obs_logweight_groups', _obs_logweight_groups_hip, 'CUDA')
 _lib.impl('log_prob', _log_prob_hip, 'CUDA')
 _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')

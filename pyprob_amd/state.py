@@ -589,7 +589,7 @@ class BatchStateBudget(Exception):
 
 
 class GroupTensor(ParticleTensor):
-    """An observed value of a batched lock-step call: [M], one value per group. It may be passed on (as the value of an observe
+    """An observed value of a batched lock-step call: [M, *event shape], one value (vector, image) per group. It may be passed on (as the value of an observe
     or a sample statement) and asked for its metadata; anything that computes with it is outside the fast path. (A subclass of
     ParticleTensor so that torch asks THIS class first when an expression mixes the two: `mu - obs` raises BatchUnsupported, not a
     shape error of [M N] against [M].)"""
@@ -609,7 +609,7 @@ class GroupTensor(ParticleTensor):
 
 
 class GroupObserves(dict):
-    """The observe dict of a batched call: name -> GroupTensor [M]; `matrix` [M, obs_width] holds the rows
+    """The observe dict of a batched call: name -> GroupTensor [M, *event shape]; `matrix` [M, obs_width] holds the rows
     InferenceNetwork._infer_init embeds (the observables' values in the network's order). One execution of a SHARDED call:
     `matrix` holds the rows of all the call's groups, `rows` = (g0, g1) the ones this execution serves, `cache` the dict the
     executions share (ISRunner.init_batch)."""
@@ -622,9 +622,9 @@ class BatchLockStepState(LockStepState):
     """M groups of n_per particles through ONE lock-step execution of forward() (Model.posterior_results_batch): particle
     i = g n_per + j belongs to group g and sees observation g. Served: a straight-line program of controlled sample statements on
     mixture heads - the first drawn from the group's own proposal (ISRunner.first_batch), later ones (Normal / Uniform, the prior
-    shared or depending on earlier draws) by the grouped statement kernel (ISRunner.bias_batch, statement_groups) - and scalar
-    ScalarTerm observes whose operands are shared, per particle or per group (ISRunner.fused_groups). The first thing outside that
-    raises BatchUnsupported."""
+    shared or depending on earlier draws) by the grouped statement kernel (ISRunner.bias_batch, statement_groups) -, scalar
+    ScalarTerm observes whose operands are shared, per particle or per group (ISRunner.fused_groups), and vector or image observes
+    of the scalar families, one launch each (ISRunner.obs_logweight_groups). The first thing outside that raises BatchUnsupported."""
     batched = True
 
     def __init__(self, runner, n_groups, n_per, seed, offset):
@@ -709,8 +709,20 @@ class BatchLockStepState(LockStepState):
         return ParticleTensor.wrap(values)
 
     def batch_likelihood(self, distribution, value):
-        """An observe (or an observed sample): a scalar ScalarTerm whose value is one number, one per group or one per particle."""
+        """An observe (or an observed sample): a scalar ScalarTerm whose value is one number, one per group or one per particle; or
+        a value of k > 1 elements per group, shared by all particles or per particle (`vector_likelihood`)."""
         self.observes += 1
+        if isinstance(value, GroupTensor):
+            with torch._C.DisableTorchFunctionSubclass():
+                shape = tuple(value.shape)
+            if shape[0] != self.n_groups:
+                raise BatchUnsupported('an observed value without one row per group')
+            if value.numel() > self.n_groups:
+                return self.vector_likelihood(distribution, value.as_subclass(torch.Tensor), shape[1:], True)
+        elif torch.is_tensor(value) and value.numel() not in (1, self.n):
+            shape = tuple(value.shape)
+            per_particle = len(shape) >= 2 and shape[0] == self.n
+            return self.vector_likelihood(distribution, value.as_subclass(torch.Tensor), shape[1:] if per_particle else shape, False)
         term = self.runner.dist_term(distribution)
         if term is None or type(term).__name__ != 'ScalarTerm':
             raise BatchUnsupported('a likelihood that is not a scalar ScalarTerm')
@@ -728,6 +740,21 @@ class BatchLockStepState(LockStepState):
         self.terms.append((term, v, float(_likelihood_importance), isinstance(value, GroupTensor)))
         if len(self.terms) >= 7:
             self.flush()
+
+    def vector_likelihood(self, distribution, v, event, per_group):
+        """lw += likelihood_importance * the log-density of an observe of `event` shape summed over its k elements, for all M n_per
+        particles in ONE launch (pp_obs_logweight_groups): v is [M, *event] (one row per group: the observed image), [*event]
+        (one row for all) or [M n_per, *event]; the parameters are shared (one element, the event's shape) or per particle
+        ([M n_per] + 1s, [M n_per, *event]) - never per group: the program cannot compute with an observed value. The term is no
+        part of the fused pass: the deferred draw and terms run first (the mean is usually computed from that draw), and the
+        launch adds into lw (zeroed by now if nothing had been accumulated, so the next fused pass adds to it)."""
+        term = self.runner.vec_term(distribution, event, self.n, before_read=self.flush)
+        if term is None:
+            raise BatchUnsupported('a vector-valued observe outside the scalar families, or a parameter shape the kernel does not read')
+        self.flush()
+        if v.dtype != torch.float32 or v.device != self.runner.dev or not v.is_contiguous():
+            v = v.to(self.runner.dev, torch.float32).contiguous()
+        self.runner.obs_logweight_groups(self.lw, term, v, per_group, self.n_groups, self.n_per, float(_likelihood_importance))
 
     def defer_term(self, term, x, scale, source=None):
         raise BatchUnsupported('a term outside the batched pass')
