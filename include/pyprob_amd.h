@@ -619,6 +619,50 @@ int pp_is_statement_groups(const pp_net* net, const float* params, int32_t addr_
                            float* y_out /*dev [M n_per, ldy] or NULL*/, int64_t ldy, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Resampling the particles of a lock-step posterior call on the device. The reference normalises the weights of an Empirical on
+ * the host (finalize, pyprob/distributions/empirical.py:298-309), draws one index per call from a Categorical over them (sample,
+ * pyprob/distributions/empirical.py:392-408) and resamples by one such call per drawn value (resample,
+ * pyprob/distributions/empirical.py:617-637). Both entry points take the [M n_per] layout of a batched call; a single posterior is
+ * M = 1.
+ *   pp_is_cdf_groups    cdf_out[g n_per + i] = sum over particles 0..i of group g of w = exp((double)lw - max_g) in fp64 (finalize's
+ *                       weights, :298-309, before the division by their sum); w = 0 where lw is not finite (-inf, +inf, NaN: the
+ *                       particles pp_is_stats does not count). max_g = stats[6 g] when `stats` (dev double [M, 6], what pp_is_stats
+ *                       or pp_is_fused_groups reduced) is given, else a first launch finds the maximum of the finite log-weights;
+ *                       both give the same bits. Dependent launches on the caller's stream: a workgroup of 256 threads scans one
+ *                       tile of PP_IS_CDF_TILE particles of one group, eight consecutive particles per thread; one workgroup per
+ *                       group turns the tile totals into exclusive offsets in index order; the offsets are added in place (groups
+ *                       of one tile: the first launch only). Inside a tile the running sum is carried forward from lane to lane
+ *                       (wave shuffles of doubles) and through the four waves in LDS, every offset being the rounded value the
+ *                       particle before it received: the cdf never decreases and is flat exactly across a particle of weight 0.
+ *                       The order of the additions depends on n_per alone: group g of an M-group call equals the one-group call on
+ *                       the same particles bit for bit, and so do two identical calls. No workgroup waits for another inside a
+ *                       kernel, no atomics. Any n_per >= 1 and n_groups >= 0 (0: returns 0 without a launch; more than 65535 groups
+ *                       are split over launches); nothing is written outside cdf_out[0 .. M n_per) and the workspace
+ *                       (pp_is_cdf_workspace_bytes; PP_ENOSPACE when shorter).
+ *   pp_is_resample_groups  n_out multinomial draws per group in ONE launch (one thread per draw, at most 2048 workgroups): draw j of
+ *                       group g takes the Philox4x32-10 block with key `seed`, counter offset + g n_out + j and stream id 0x52, forms
+ *                       the 53-bit uniform u = (((uint64)(word0 >> 5) << 26) + (word1 >> 6) + 0.5) 2^-53 and, with base = (lo > 0 ?
+ *                       cdf[g, lo - 1] : 0) and total = cdf[g, hi - 1] - base, the target fl(base + fl(u total)) (two separately
+ *                       rounded operations). index = lo + the number of i in [lo, hi) with cdf[g, i] <= target, by binary search, at
+ *                       most hi - 1: numpy.searchsorted(cdf_g, target, side='right'). A particle of weight 0 inside the range is not
+ *                       selected (but for a target that rounds up to the range's last cdf value, probability 2^-52 per draw, which
+ *                       takes particle hi - 1 whatever its weight). index_out[g n_out + j] = that index within the group,
+ *                       value_out[g n_out + j] = values[g n_per + index]; either may be NULL, not both; value_out needs `values`.
+ *                       A group whose total is not positive and finite gets index -1 and value NaN, and none of its elements is
+ *                       read beyond the two that form the total. lo / hi (0 <= lo < hi <= n_per: min_index / max_index of
+ *                       Empirical.sample and resample) are shared by the groups. An M-group call consumes the counters of the M
+ *                       one-group calls at offset + g n_out.
+ * Both return PP_EINVAL without a launch for a NULL required pointer, n_per < 1, n_groups < 0, n_out < 0, lo / hi outside
+ * 0 <= lo < hi <= n_per, or M n_per / M n_out above 2^31 - 1. */
+#define PP_IS_CDF_TILE 2048
+size_t pp_is_cdf_workspace_bytes(int32_t n_groups, int32_t n_per);
+int pp_is_cdf_groups(const float* lw /*dev [M n_per]*/, int32_t n_groups, int32_t n_per,
+                     const double* stats /*dev double [M, 6] or NULL*/, double* cdf_out /*dev double [M n_per]*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int pp_is_resample_groups(const double* cdf /*dev [M n_per]*/, const float* values /*dev [M n_per] or NULL*/, int32_t n_groups,
+                          int32_t n_per, int32_t lo, int32_t hi, int32_t n_out, uint64_t seed, uint64_t offset,
+                          int64_t* index_out /*dev [M n_out] or NULL*/, float* value_out /*dev [M n_out] or NULL*/, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

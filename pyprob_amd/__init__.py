@@ -17,6 +17,10 @@ def __getattr__(name):
         from .spec import ObserveEmbedding
         globals()[name] = ObserveEmbedding
         return ObserveEmbedding
+    if name == 'resample_batch':
+        from .distributions import resample_batch
+        globals()[name] = resample_batch
+        return resample_batch
     if name == 'Model':
         from .model import Model
         globals()[name] = Model

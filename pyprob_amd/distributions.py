@@ -7,6 +7,7 @@ proposal distributions themselves (Mixture / TruncatedNormal) live in the HIP ke
 """
 import copy
 import math
+import os
 import warnings
 
 import numpy as np
@@ -733,6 +734,8 @@ class Empirical:
         self._values.append(value)
         self._log_weights.append(0.0 if log_weight is None else float(log_weight))
         self._finalized = False
+        for k in ('_dev_cdf', '_batch', '_batch_cdf'):
+            self.__dict__.pop(k, None)
 
     def add_sequence(self, values, log_weights=None, weights=None):
         for i, v in enumerate(values):
@@ -839,9 +842,56 @@ class Empirical:
         total = self._cum[hi - 1] - base
         return np.minimum(np.searchsorted(self._cum, base + u * total, side='right'), hi - 1)
 
+    # ---- device route of sample / resample (csrc/is_resample.hip) --------------------------------------------------
+    def _device_backed(self):
+        """Values and log-weights are ONE contiguous float32 device tensor each (the result of a lock-step posterior call):
+        sample / resample then run on the device. PP_EMPIRICAL_DEVICE=0 keeps the host route for such objects too."""
+        v, lw = self.__dict__.get('_values'), self.__dict__.get('_log_weights')
+        return (self._finalized and torch.is_tensor(v) and torch.is_tensor(lw) and v.is_cuda and lw.is_cuda and
+                v.dtype == torch.float32 and lw.dtype == torch.float32 and v.dim() == 1 and lw.dim() == 1 and
+                v.numel() == lw.numel() and v.numel() > 0 and v.is_contiguous() and lw.is_contiguous() and
+                os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0')
+
+    def _device_cdf(self):
+        """The running sum of exp(lw - max lw) in float64 on the device (pp_is_cdf_groups): computed once per object, 8 bytes per
+        particle, dropped with the object. A group of a batched call hands the kernel the maximum its call already reduced."""
+        cdf = self.__dict__.get('_dev_cdf')
+        if cdf is None:
+            from .ops import ops
+            batch = self.__dict__.get('_batch')
+            stats = batch[2][batch[3]] if (batch is not None and batch[2] is not None) else None
+            cdf = self.__dict__['_dev_cdf'] = ops.is_cdf_groups(self._log_weights, self.length, stats)
+        return cdf
+
+    def _index_range(self, min_index, max_index):
+        lo = 0 if min_index is None else int(min_index)
+        hi = self.length if max_index is None else int(max_index)
+        if hi <= lo:
+            raise ValueError('empty index range')
+        if lo < 0 or hi > self.length:
+            raise ValueError('index range [%d, %d) outside the %d values' % (lo, hi, self.length))
+        return lo, hi
+
+    def _device_draw(self, n, min_index, max_index, seed, offset):
+        """n values drawn on the device according to the weights of [min_index, max_index): one launch, a device tensor."""
+        from .ops import ops
+        lo, hi = self._index_range(min_index, max_index)
+        # (the key from torch's global generator, as PriorLockStep takes it: pyprob.seed / torch.manual_seed reproduce a run)
+        key = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        return ops.is_resample_groups(self._device_cdf(), self._values, self.length, lo, hi, int(n), key, int(offset), False)[1]
+
+    def _resampled(self, values, zeros, stats, num_samples, ess_before):
+        out = Empirical.from_device(values, zeros, stats, name=self.name)
+        out._metadata = dict(self._metadata)
+        out.add_metadata(op='resample', length=self.length, num_samples=int(num_samples), ess_before=ess_before)
+        return out
+
     def sample(self, min_index=None, max_index=None):
-        """One value drawn according to the weights (empirical.py:392-408; min_index inclusive, max_index exclusive)."""
+        """One value drawn according to the weights (empirical.py:392-408; min_index inclusive, max_index exclusive). A
+        device-backed Empirical draws on the device (see resample)."""
         self._check_finalized()
+        if self._device_backed():
+            return self._device_draw(1, min_index, max_index, None, 0)[0].cpu()
         return self._value(int(self._draw_indices(1, min_index, max_index)[0]))
 
     # ---- transformations (each returns a new Empirical) ------------------------------------------------------
@@ -865,9 +915,29 @@ class Empirical:
         warnings.warn('Empirical.filter will be deprecated in future releases. Use Empirical.condition instead.')
         return self.condition(*args, **kwargs)
 
-    def resample(self, num_samples, map_func=None, min_index=None, max_index=None):
-        """num_samples unweighted draws (empirical.py:617-637)."""
+    def resample(self, num_samples, map_func=None, min_index=None, max_index=None, seed=None, offset=0):
+        """num_samples unweighted draws (empirical.py:617-637).
+
+        A device-backed Empirical (the result of a lock-step posterior call) is resampled on the device: its cumulative weights
+        are computed once (pp_is_cdf_groups) and the draws are one launch (pp_is_resample_groups); the result is device-backed
+        again, with the statistics of the drawn values reduced on the device, and no list of the particles is built. With
+        map_func only the num_samples drawn values travel to the host and the result is host-backed. Draw j uses the Philox
+        block of key `seed` and counter `offset + j`; seed=None takes the key from torch's global generator, so pyprob.seed /
+        torch.manual_seed reproduce a run. These draws are a DIFFERENT STREAM of the same distribution as the host route's, which
+        draws from torch's generator directly, ignores seed / offset, and serves every other Empirical (and all of them under
+        PP_EMPIRICAL_DEVICE=0)."""
         self._check_finalized()
+        if self._device_backed():
+            if int(num_samples) < 1:
+                raise ValueError('num_samples must be positive')
+            ess = self.effective_sample_size
+            drawn = self._device_draw(num_samples, min_index, max_index, seed, offset)
+            if map_func is not None:
+                out = [map_func(v) for v in drawn.cpu().unbind(0)]
+                return self._like(out, np.zeros(len(out)), op='resample', length=self.length, num_samples=int(num_samples),
+                                  ess_before=ess)
+            zeros = torch.zeros_like(drawn)
+            return self._resampled(drawn, zeros, _device_stats(zeros, drawn), num_samples, ess)
         ess = self.effective_sample_size
         idx = self._draw_indices(int(num_samples), min_index, max_index)
         vals = self.get_values()
@@ -990,3 +1060,52 @@ class Empirical:
             return 'Empirical(items:{}, weighted:{}, mean:{}, stddev:{})'.format(self.length, self.weighted, self.mean, self.stddev)
         except Exception:   # noqa: BLE001 - values that are not scalars
             return 'Empirical(items:{})'.format(self.length)
+
+
+_STATS_SCRATCH = {}
+
+
+def _device_stats(lw, x):
+    """pp_is_stats over (lw, x) as the dict Empirical.from_device takes (one small device-to-host copy)."""
+    from . import lib as L
+    from .is_engine import DistRunner
+    from .ops import ops
+    scratch = _STATS_SCRATCH.get(lw.device)
+    if scratch is None:
+        scratch = _STATS_SCRATCH[lw.device] = torch.zeros(L.PP_IS_STATS_SCRATCH, dtype=torch.float64, device=lw.device)
+    return DistRunner._stats_dict(ops.is_stats(lw, x, scratch))
+
+
+def resample_batch(posteriors, num_samples, seed=None, offset=0):
+    """[p.resample(num_samples, seed=seed, offset=offset + g * num_samples) for g, p in enumerate(posteriors)] - and, where the
+    posteriors are the M groups of ONE Model.posterior_results_batch execution in order, the same values bit for bit from one
+    pp_is_cdf_groups and one pp_is_resample_groups launch over all groups, with the statistics of the M resampled groups from the
+    grouped statistics pass in one device-to-host copy. seed=None: one key from torch's global generator for the whole list."""
+    posteriors = list(posteriors)
+    n = int(num_samples)
+    if not posteriors:
+        return []
+    key = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+    first = posteriors[0].__dict__.get('_batch')
+    M = len(posteriors)
+    fast = first is not None and n >= 1 and first[0].numel() == M * first[4] and M * n <= 0x7fffffff
+    for g, p in enumerate(posteriors):
+        b = p.__dict__.get('_batch')
+        fast = fast and b is not None and b[0] is first[0] and b[1] is first[1] and b[2] is first[2] and b[3] == g and \
+            p._device_backed() and p.__dict__.get('_batch_runner') is not None
+    if not fast:
+        return [p.resample(n, seed=key, offset=int(offset) + g * n) for g, p in enumerate(posteriors)]
+    from .ops import ops
+    values, lw, group_stats, _, N = first
+    cdf = posteriors[0].__dict__.get('_batch_cdf')
+    if cdf is None:       # (once per batched call, kept by its first group; every group's own cdf is its slice - the same bits)
+        cdf = posteriors[0].__dict__['_batch_cdf'] = ops.is_cdf_groups(lw, N, group_stats)
+        for p, part in zip(posteriors, cdf.split(N)):
+            p.__dict__.setdefault('_dev_cdf', part)
+    drawn = ops.is_resample_groups(cdf, values, N, 0, N, n, key, int(offset), False)[1]
+    runner = posteriors[0]._batch_runner
+    zeros = torch.zeros_like(drawn)
+    stats = runner.fused_groups(None, n, None, [], drawn, zeros, False, stats=True).cpu().numpy()
+    d_parts, z_parts = drawn.split(n), zeros.split(n)
+    return [p._resampled(d_parts[g], z_parts[g], runner._stats_dict(stats[g]), n, p.effective_sample_size)
+            for g, p in enumerate(posteriors)]

@@ -28,6 +28,7 @@ def larc_scratch_floats(n_params, n_tensors):
 
 
 PP_IS_STATS_SCRATCH = 6144   # doubles (include/pyprob_amd.h)
+PP_IS_CDF_TILE = 2048        # particles per workgroup of pp_is_cdf_groups (include/pyprob_amd.h)
 
 i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p
 
@@ -176,6 +177,9 @@ PROTOTYPES = {
     'pp_is_batch_bias': (C.c_int, [C.POINTER(pp_net), vp, i32, i32, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_statement_groups': (C.c_int, [C.POINTER(pp_net), vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32,
                                          C.c_uint64, C.c_uint64, vp, i64, vp, C.c_size_t, vp]),
+    'pp_is_cdf_workspace_bytes': (C.c_size_t, [i32, i32]),
+    'pp_is_cdf_groups': (C.c_int, [vp, i32, i32, vp, vp, vp, C.c_size_t, vp]),
+    'pp_is_resample_groups': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

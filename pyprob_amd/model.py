@@ -985,7 +985,8 @@ class Model:
             runner.release_group_state()
         stats = ls.group_stats.cpu().numpy()          # the one device-to-host copy (and synchronisation) of the call
         # (one split per tensor, not two slices per group: the per-group host work is what the call amortises)
-        v_parts, lw_parts = values.split(N), ls.lw.split(N)
+        lw_all = ls.lw
+        v_parts, lw_parts = values.split(N), lw_all.split(N)
         log_parts = [[(a, rec[0].split(N), rec[1]) for a, rec in entry.items()] for entry in ls.log]
         out = []
         for g in range(M):
@@ -997,6 +998,8 @@ class Model:
                 st = runner.stats(lw_g, v_g)
             emp = Empirical.from_device(v_g, lw_g, st)
             emp._all_values, emp._all_log_weights = all_v, all_lw
+            if v_g is all_v:      # (no particle dropped) the call's whole tensors: resample_batch serves all groups in one launch
+                emp._batch, emp._batch_runner = (values, lw_all, ls.group_stats, g, N), runner
             emp.num_paths = 1
             emp.statement_log = [{a: (parts[g], addr_id) for a, parts, addr_id in entry} for entry in log_parts]
             emp.rename('Posterior, IC, traces: {:,}, ESS: {:,.2f}'.format(emp.length, emp.effective_sample_size))

@@ -23,6 +23,8 @@ kernels for these operators from tests/, to execute the host logic above them wi
     obs_logweight   the summed log-density of a vector-valued observe    pyprob/state.py:118-155, trace.py:123-125
     obs_logweight_groups  the same for the M N rows of a batched call, operands per particle or per group
     mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
+    is_cdf_groups       Empirical.finalize's weights as a running sum per group  pyprob/distributions/empirical.py:298-309
+    is_resample_groups  Empirical.sample / resample: multinomial draws (Philox)   pyprob/distributions/empirical.py:392-408, 617-637
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -73,6 +75,9 @@ _lib.define('log_prob(int kind, Tensor p0, int p0_stride, Tensor? p1, int p1_str
 _lib.define('logweight_terms(Tensor(a!) lw, int[] kinds, Tensor?[] p0, int[] p0_strides, Tensor?[] p1, int[] p1_strides, '
             'Tensor[] x, float[] scales, bool overwrite) -> ()')
 _lib.define('is_stats(Tensor lw, Tensor? x, Tensor(a!) scratch) -> Tensor')
+_lib.define('is_cdf_groups(Tensor lw, int n_per, Tensor? stats) -> Tensor')
+_lib.define('is_resample_groups(Tensor cdf, Tensor? values, int n_per, int lo, int hi, int n_out, int seed, int offset, '
+            'bool want_index) -> (Tensor, Tensor)')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
@@ -685,6 +690,51 @@ def _is_stats_hip(lw, x, scratch):
     return out
 
 
+def _groups_of(t, n_per, what):
+    n_per = int(n_per)
+    if t.dim() != 1 or not t.is_contiguous() or n_per < 1 or t.numel() % n_per:
+        raise RuntimeError('pyprob_hip::%s: a contiguous 1-D tensor of M * n_per elements (n_per >= 1)' % what)
+    return t.numel() // n_per
+
+
+def _is_cdf_groups_hip(lw, n_per, stats):
+    """cdf [M n_per] (float64) of the M groups of n_per log-weights; stats: the [M, 6] (or, M = 1, the 6+) doubles pp_is_stats /
+    pp_is_fused_groups reduced over the same log-weights - their maxima are taken instead of being searched."""
+    lib = L.load()
+    _same_device(lw, stats)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_cdf_groups')
+    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
+        raise RuntimeError('pyprob_hip::is_cdf_groups: stats must be a contiguous float64 tensor of [M, 6]')
+    out = torch.empty(M * int(n_per), dtype=torch.float64, device=lw.device)
+    need = lib.pp_is_cdf_workspace_bytes(M, int(n_per))
+    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_cdf_groups(lw.data_ptr(), M, int(n_per), L.ptr(stats), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_cdf_groups')
+    return out
+
+
+def _is_resample_groups_hip(cdf, values, n_per, lo, hi, n_out, seed, offset, want_index):
+    """(index int64 [M n_out] or empty, value float32 [M n_out] or empty): n_out draws from every group's cdf in [lo, hi)."""
+    lib = L.load()
+    _same_device(cdf, values)
+    if cdf.dtype != torch.float64:
+        raise RuntimeError('pyprob_hip::is_resample_groups: cdf must be float64 (is_cdf_groups)')
+    M = _groups_of(cdf, n_per, 'is_resample_groups')
+    if values is not None and _f32(values, 'values').numel() != cdf.numel():
+        raise RuntimeError('pyprob_hip::is_resample_groups: values must have the cdf\'s M * n_per elements')
+    n_out = int(n_out)
+    index = torch.empty(M * max(n_out, 0) if want_index else 0, dtype=torch.int64, device=cdf.device)
+    value = torch.empty(M * max(n_out, 0) if values is not None else 0, dtype=torch.float32, device=cdf.device)
+    with torch.cuda.device(cdf.device):
+        rc = lib.pp_is_resample_groups(cdf.data_ptr(), L.ptr(values), M, int(n_per), int(lo), int(hi), n_out,
+                                       int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                       index.data_ptr() if want_index else None, value.data_ptr() if values is not None else None,
+                                       _stream(cdf))
+    L.check(rc, 'pp_is_resample_groups')
+    return index, value
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -702,6 +752,8 @@ _lib.impl('obs_logweight_groups', _obs_logweight_groups_hip, 'CUDA')
 _lib.impl('log_prob', _log_prob_hip, 'CUDA')
 _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')
+_lib.impl('is_cdf_groups', _is_cdf_groups_hip, 'CUDA')
+_lib.impl('is_resample_groups', _is_resample_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
