@@ -663,6 +663,46 @@ int pp_is_resample_groups(const double* cdf /*dev [M n_per]*/, const float* valu
                           int32_t n_per, int32_t lo, int32_t hi, int32_t n_out, uint64_t seed, uint64_t offset,
                           int64_t* index_out /*dev [M n_out] or NULL*/, float* value_out /*dev [M n_out] or NULL*/, void* stream);
 
+/* Joint weighted moments of up to PP_IS_MOMENTS_MAX_COLS latent columns of a lock-step posterior call on the device. The reference
+ * normalises the weights on the host (finalize, pyprob/distributions/empirical.py:298-309) and answers mean / variance as
+ * expectations over the values of ONE mapped Empirical at a time (expectation :451-466, mean / variance :668-690); here the
+ * moments of all requested latents of one weighted particle set, and of all M groups of a batched call, come from one call.
+ *   pp_is_moments_groups  row g of `out` (PP_IS_MOMENTS_WIDTH(J) doubles) holds, in this order,
+ *                           max lw, W = sum w, sum w^2, count of finite lw
+ *                           c_j                                       (J values)
+ *                           S_j  = sum w (x_j - c_j)                  (J values)
+ *                           Q_jk = sum w (x_j - c_j)(x_k - c_k)       for j <= k, row-major upper triangle
+ *                       over the n_per particles of group g, with x_j = cols[j] (a HOST array of J device pointers, each to
+ *                       [M n_per] floats). w = exp((double)lw - max_g) in fp64. max_g = stats[6 g] when `stats` (dev double [M, 6],
+ *                       what pp_is_stats or pp_is_fused_groups reduced) is given, else a first launch finds the maximum of the
+ *                       finite log-weights (-inf where there is none); both give the same bits. A particle whose lw is not finite
+ *                       (-inf, +inf, NaN: the particles pp_is_stats does not count) is SKIPPED entirely: its column values enter
+ *                       no product, so 0 * NaN never reaches a sum (a lock-step run leaves arbitrary values in the rows of
+ *                       particles that did not execute a statement). A non-finite value under a finite weight propagates, as in
+ *                       pp_is_stats. The pivot c_j is x_j[g, 0] if that is finite, else 0; the caller forms
+ *                       mean_j = c_j + S_j / W and cov_jk = Q_jk / W - (S_j / W)(S_k / W), the biased, weight-normalised form of
+ *                       Empirical.variance. Sums about a pivot keep a narrow posterior far from zero accurate; raw second moments
+ *                       cancel there. A group without a finite log-weight gives count 0 and sums 0.
+ *                       Dependent launches on the caller's stream: a workgroup of 256 threads takes one tile of 2048 particles of
+ *                       one group and one pair of 4-column blocks (eight particles per thread, 23 fp64 accumulators; the lanes
+ *                       of a wave exchange doubles by DPP, the four waves meet in LDS) and STORES its partial sums in the workspace; one workgroup per
+ *                       group adds them in tile order. No atomics, no workgroup waits for another. The order of the additions
+ *                       depends on n_per and n_cols alone: group g of an M-group call equals the one-group call on the same
+ *                       particles bit for bit, and so do two identical calls. Any n_per >= 1 and n_groups >= 0 (0: returns 0
+ *                       without a launch; more than 65535 groups are split over launches); nothing is written outside
+ *                       out[0 .. M PP_IS_MOMENTS_WIDTH(J)) and the workspace (pp_is_moments_workspace_bytes; PP_ENOSPACE when
+ *                       shorter).
+ * Returns PP_EINVAL without a launch for a NULL required pointer (lw, cols, any cols[j], out, workspace), n_cols outside
+ * 1 .. PP_IS_MOMENTS_MAX_COLS, n_per < 1, n_groups < 0 or M n_per above 2^31 - 1. pp_is_moments_workspace_bytes returns 0 for
+ * arguments outside that envelope. */
+#define PP_IS_MOMENTS_MAX_COLS 16
+#define PP_IS_MOMENTS_WIDTH(J) (4 + 2 * (J) + (J) * ((J) + 1) / 2)
+size_t pp_is_moments_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_cols);
+int pp_is_moments_groups(const float* lw /*dev [M n_per]*/, const float* const* cols /*host array of J dev pointers, each [M n_per]*/,
+                         int32_t n_cols, int32_t n_groups, int32_t n_per, const double* stats /*dev double [M, 6] or NULL*/,
+                         double* out /*dev double [M, PP_IS_MOMENTS_WIDTH(J)]*/, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

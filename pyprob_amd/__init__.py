@@ -21,6 +21,10 @@ def __getattr__(name):
         from .distributions import resample_batch
         globals()[name] = resample_batch
         return resample_batch
+    if name == 'joint_batch':
+        from .distributions import joint_batch
+        globals()[name] = joint_batch
+        return joint_batch
     if name == 'Model':
         from .model import Model
         globals()[name] = Model

@@ -667,6 +667,12 @@ class Factor(Distribution):
         return 'Factor()'
 
 
+_NO_STATEMENT_LOG = ('this Empirical has no statement log: only the result of a lock-step posterior call '
+                     '(posterior_results(..., lock_step=True), posterior_results_batch) keeps its latents per address')
+_STALE_STATEMENT_LOG = ('this Empirical grew (add) after its lock-step posterior call: the statement log describes the particles of '
+                        'that call only, so addresses / marginal / joint / resample_joint are not served')
+
+
 class Empirical:
     """Weighted samples: the result type of Model.prior / posterior (pyprob/distributions/empirical.py). Memory-backed;
     values are floats / tensors / arbitrary objects (or ONE device tensor for lock-step runs), weights are log-weights.
@@ -717,6 +723,8 @@ class Empirical:
             self.finalize()          # host-side weights of a device-backed Empirical, on first use
             if name in self.__dict__:
                 return self.__dict__[name]
+        if name in ('addresses', 'statement_rows'):      # (the properties below raised AttributeError: say why)
+            raise AttributeError(_STALE_STATEMENT_LOG if self.__dict__.get('_log_stale') else _NO_STATEMENT_LOG)
         raise AttributeError(name)
 
     def _host_weights_ready(self):
@@ -734,8 +742,14 @@ class Empirical:
         self._values.append(value)
         self._log_weights.append(0.0 if log_weight is None else float(log_weight))
         self._finalized = False
-        for k in ('_dev_cdf', '_batch', '_batch_cdf'):
+        for k in ('_dev_cdf', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
             self.__dict__.pop(k, None)
+        # the statement log describes the particles of the lock-step call, not this grown set: marginal / joint must not answer
+        # for the old one (statement_log itself stays readable, as before; _latent_table refuses through _log_stale)
+        for k in ('_latents', '_statement_rows', '_statement_rows_raw'):
+            self.__dict__.pop(k, None)
+        if 'statement_log' in self.__dict__:
+            self.__dict__['_log_stale'] = True
 
     def add_sequence(self, values, log_weights=None, weights=None):
         for i, v in enumerate(values):
@@ -893,6 +907,173 @@ class Empirical:
         if self._device_backed():
             return self._device_draw(1, min_index, max_index, None, 0)[0].cpu()
         return self._value(int(self._draw_indices(1, min_index, max_index)[0]))
+
+    # ---- the other latents of a lock-step call (csrc/is_moments.hip) ------------------------------------------------
+    def _latent_table(self):
+        """{address: (values [n] of ALL particles of the call, rows that executed it or None)} in the order the statement log
+        first meets each address - the statement log of a lock-step posterior call. Every other Empirical has none.
+
+        The log is keyed by statement index first, and a branch that changes the number of statements before a common one puts
+        the same address at different indices for different paths (`if a > 0: b = sample(...)` before `c = sample(...)`: 'c' is
+        statement 2 of one path and statement 1 of the other). Such an address is ONE latent: its entries are merged into one
+        column - each entry's rows copied in - under the union of their row lists, None where that is every particle."""
+        log = self.__dict__.get('statement_log')
+        if log is None:
+            raise AttributeError(_NO_STATEMENT_LOG)
+        if self.__dict__.get('_log_stale'):
+            raise AttributeError(_STALE_STATEMENT_LOG)
+        if os.environ.get('PP_EMPIRICAL_DEVICE', '1') == '0':
+            raise ValueError('PP_EMPIRICAL_DEVICE=0 keeps every Empirical on the host route: the statement log is not served '
+                             '(addresses / marginal / joint / resample_joint need the device route)')
+        table = self.__dict__.get('_latents')
+        if table is None:
+            rows = self.statement_rows
+            found = {}
+            for j, entry in enumerate(log):
+                for address, rec in entry.items():
+                    if torch.is_tensor(rec[0]) and rec[0].dim() == 1:
+                        found.setdefault(address, []).append((rec[0], rows[j].get(address) if j < len(rows) else None))
+            table = {}
+            for address, parts in found.items():
+                whole = [p for p in parts if p[1] is None]
+                if whole or len(parts) == 1:       # one entry, or an entry every particle wrote: the log's own tensor
+                    table[address] = whole[0] if whole else parts[0]
+                    continue
+                column = parts[0][0].clone()
+                for values, r in parts[1:]:
+                    column.index_copy_(0, r, values.index_select(0, r))
+                union = torch.unique(torch.cat([r for _, r in parts]))      # (sorted)
+                table[address] = (column, None if union.numel() == column.numel() else union)
+            self.__dict__['_latents'] = table
+        return table
+
+    @property
+    def statement_rows(self):
+        """Per statement index {address: the ascending int64 indices of the particles that executed it, or None = all of them}."""
+        merged = self.__dict__.get('_statement_rows')
+        if merged is None:
+            raw = self.__dict__.get('_statement_rows_raw')
+            if raw is None:
+                raise AttributeError(_STALE_STATEMENT_LOG if self.__dict__.get('_log_stale') else _NO_STATEMENT_LOG)
+            merged = [{a: (None if r is None else (r[0] if len(r) == 1 else torch.sort(torch.cat(r))[0])) for a, r in e.items()}
+                      for e in raw]
+            self.__dict__['_statement_rows'] = merged
+        return merged
+
+    @property
+    def addresses(self):
+        """The addresses of the statement log in statement order."""
+        return list(self._latent_table())
+
+    def _latent(self, address):
+        table = self._latent_table()
+        if address not in table:
+            address = self.__dict__.get('statement_names', {}).get(address, address)
+        if address not in table:       # the address= of a sample statement: the one full address it begins ('a' -> 'a__Normal__1')
+            begun = [a for a in table if a.startswith(str(address) + '__')]
+            address = begun[0] if len(begun) == 1 else address
+        if address not in table:
+            raise KeyError('unknown address {!r}: this posterior knows {} (names: {})'.format(
+                address, list(table), list(self.__dict__.get('statement_names', {}))))
+        return (address,) + table[address]
+
+    def _all_lw(self):
+        lw = self.__dict__.get('_all_log_weights')
+        return lw if lw is not None else self._log_weights
+
+    def marginal(self, address):
+        """The posterior of ONE latent of a lock-step call as an Empirical of its own (pyprob: posterior.map(lambda t:
+        t.named_variables[name].value)): the address's values of the statement log under the call's log-weights, its
+        device_stats reduced on the device (pp_is_stats; the call's own for the latent forward() returned), so that mean /
+        variance / resample / sample / median answer on the device as they do for the result column. `address` is an address of
+        `addresses`, the name= of its sample statement, or the address= the statement was given where that begins one address
+        only. Particles with a non-finite log-weight are dropped as the call dropped them. An address only some particles executed
+        (a branch) gives the Empirical over THOSE particles, weights renormalised among them (pyprob: condition + map).
+
+        The call's own statistics are reused only where the posterior's value column IS the log's tensor (the same memory): the
+        inference-network route returning a latent as it drew it. Where the call copied the return value (the prior route) or
+        forward() returned anything computed, the marginal takes pp_is_stats like every other address, and its mean may sit ~1e-9
+        relative from `post.mean` (fp64 against fp32 exponent of the weights) - the same distribution either way."""
+        address, values, rows = self._latent(address)
+        lw = self._all_lw()
+        own, own_stats = self.__dict__.get('_all_values'), self.__dict__.get('device_stats')
+        if rows is None and own_stats is not None and torch.is_tensor(own) and own.data_ptr() == values.data_ptr() and \
+                own.numel() == values.numel():
+            # the latent forward() returned: this posterior's own column, under the statistics its call reduced - one source of
+            # truth for the same numbers (the call's fused pass takes its weights from an fp32 exponent, pp_is_stats from an fp64
+            # one: mean and variance of the same column differ by ~1e-9 relative between the two)
+            values, lw, stats = self._values, self._log_weights, own_stats
+        else:
+            if rows is not None:
+                values, lw = values.index_select(0, rows), lw.index_select(0, rows)
+            stats = _device_stats(lw, values)
+            if int(stats['count']) != lw.numel():
+                ok = torch.isfinite(lw)
+                values, lw = values[ok].contiguous(), lw[ok].contiguous()
+                if lw.numel() == 0:
+                    raise ValueError('no particle with a finite log-weight executed address {!r}'.format(address))
+                stats = _device_stats(lw, values)
+        out = Empirical.from_device(values, lw, stats, name=self.name)
+        out._metadata = dict(self._metadata)
+        out.add_metadata(op='marginal', address=address, length=self.length, length_after=out.length)
+        return out
+
+    def _joint_columns(self, addresses):
+        table = self._latent_table()
+        if addresses is None:
+            chosen = [a for a, (_, rows) in table.items() if rows is None]
+        else:
+            chosen = []
+            for a in addresses:
+                a, _, rows = self._latent(a)
+                if rows is not None:
+                    raise ValueError('address {!r} was executed by {} of the particles only (a branch): joint() takes addresses '
+                                     'that every particle executed - see marginal()'.format(a, int(rows.numel())))
+                chosen.append(a)
+        if not chosen:
+            raise ValueError('no address that every particle executed')
+        return chosen, [table[a][0] for a in chosen]
+
+    def joint(self, addresses=None):
+        """Means, covariances and correlations of several latents of a lock-step call over its weighted particles, as a
+        JointMoments (addresses, mean [J], cov [J, J], corr [J, J], stddev [J] in float64 numpy, ess, count): one
+        pp_is_moments_groups launch over the statement log's columns and one device-to-host copy. The covariance is the biased,
+        weight-normalised form of Empirical.variance. addresses: addresses or statement names, default every address that ALL
+        particles executed; an address of a branch raises ValueError. More than 16 addresses are served in blocks of 8 columns,
+        one call per pair of blocks: the entries that cross two blocks come from separate calls (each over the same weights,
+        each bit-reproducible). No particle with a finite log-weight: NaN arrays, count 0."""
+        chosen, cols = self._joint_columns(addresses)
+        lw = self._all_lw()
+        batch = self.__dict__.get('_batch')
+        stats = batch[2][batch[3]] if (batch is not None and batch[2] is not None) else None
+        return _joint_rows(chosen, _moment_rows(lw, cols, lw.numel(), stats))[0]
+
+    def resample_joint(self, num_samples, addresses=None, seed=None, offset=0):
+        """num_samples JOINT draws of several latents: ONE index per sample from the weights (pp_is_resample_groups, the Philox
+        contract of resample: draw k = key `seed`, counter offset + k), then row index[k] of every requested column. Returns
+        {address: device tensor [num_samples]} plus 'index' (int64, into ALL particles of the call: the rows of the statement
+        log's columns). With the same seed and offset the indices - and so the result column - are those resample() draws,
+        PROVIDED the call dropped no particle. Where it dropped particles with a non-finite log-weight, the posterior's own
+        particles are renumbered and resample() indexes those; here the cumulative weights run over all particles with weight 0
+        for the dropped ones, so no draw lands on them, row k of every column is still one particle's, and the draws follow the
+        same distribution - but they are another stream than resample()'s."""
+        from .ops import ops
+        if int(num_samples) < 1:
+            raise ValueError('num_samples must be positive')
+        chosen, cols = self._joint_columns(addresses)
+        lw = self._all_lw()
+        if lw is self._log_weights:
+            cdf = self._device_cdf()
+        else:       # (the call dropped particles: the cdf over ALL of them, weight 0 where the log-weight is not finite)
+            cdf = self.__dict__.get('_all_cdf')
+            if cdf is None:
+                cdf = self.__dict__['_all_cdf'] = ops.is_cdf_groups(lw, lw.numel(), None)
+        key = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
+        n = lw.numel()
+        index = ops.is_resample_groups(cdf, None, n, 0, n, int(num_samples), key, int(offset), True)[0]
+        out = {a: c.index_select(0, index) for a, c in zip(chosen, cols)}
+        out['index'] = index
+        return out
 
     # ---- transformations (each returns a new Empirical) ------------------------------------------------------
     def map(self, func, min_index=None, max_index=None):
@@ -1074,6 +1255,114 @@ def _device_stats(lw, x):
     if scratch is None:
         scratch = _STATS_SCRATCH[lw.device] = torch.zeros(L.PP_IS_STATS_SCRATCH, dtype=torch.float64, device=lw.device)
     return DistRunner._stats_dict(ops.is_stats(lw, x, scratch))
+
+
+class JointMoments:
+    """First and second moments of J latents over one weighted particle set (Empirical.joint): addresses, mean [J], cov [J, J],
+    corr [J, J], stddev [J] (float64 numpy), ess = (sum w)^2 / sum w^2 and count = the particles with a finite log-weight."""
+
+    def __init__(self, addresses, mean, cov, corr, stddev, ess, count):
+        self.addresses = list(addresses)
+        self.mean, self.cov, self.corr, self.stddev = mean, cov, corr, stddev
+        self.ess, self.count = float(ess), int(count)
+
+    def __repr__(self):
+        return 'JointMoments(addresses:{}, count:{}, ess:{:.2f}, mean:{})'.format(self.addresses, self.count, self.ess,
+                                                                                  self.mean.tolist())
+
+
+def _joint_rows(addresses, rows):
+    """The M output rows of pp_is_moments_groups (max lw, W, sum w^2, count | c_j | S_j | Q_jk for j <= k) as M JointMoments, all
+    groups in one pass of array arithmetic (the same operations per element whatever M is: a group's numbers do not depend on the
+    groups next to it): mean_j = c_j + S_j / W, cov_jk = Q_jk / W - (S_j / W)(S_k / W) with the diagonal clamped at 0 like
+    Empirical.variance, stddev = sqrt(diagonal), corr = cov / sqrt(var_j var_k). A group without a weight: NaN arrays, ess 0."""
+    J = len(addresses)
+    rows = np.asarray(rows, np.float64).reshape(-1, 4 + 2 * J + J * (J + 1) // 2)
+    W, W2, count = rows[:, 1], rows[:, 2], rows[:, 3]
+    ok = (count > 0) & (W > 0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        Wd = np.where(ok, W, np.nan)[:, None]
+        s = rows[:, 4 + J:4 + 2 * J] / Wd
+        mean = rows[:, 4:4 + J] + s
+        iu, ku = np.triu_indices(J)
+        cov = np.empty((rows.shape[0], J, J))
+        cov[:, iu, ku] = rows[:, 4 + 2 * J:] / Wd
+        cov[:, ku, iu] = cov[:, iu, ku]
+        cov -= s[:, :, None] * s[:, None, :]
+        d = np.arange(J)
+        var = cov[:, d, d]
+        var = np.where(var < 0, 0.0, var)       # (NaN stays NaN)
+        cov[:, d, d] = var
+        stddev = np.sqrt(var)
+        corr = cov / np.sqrt(var[:, :, None] * var[:, None, :])
+        ess = np.where(ok, W * W / np.where(ok, W2, 1.0), 0.0)
+    return [JointMoments(addresses, mean[g], cov[g], corr[g], stddev[g], ess[g], count[g]) for g in range(rows.shape[0])]
+
+
+def joint_from_moments(addresses, row):
+    """One output row of pp_is_moments_groups as a JointMoments (see _joint_rows)."""
+    return _joint_rows(addresses, np.asarray(row, np.float64)[None])[0]
+
+
+def _moment_rows(lw, cols, n_per, stats):
+    """numpy [M, PP_IS_MOMENTS_WIDTH(J)] of pp_is_moments_groups over the J columns: one launch and one copy up to 16 columns;
+    beyond that blocks of 8 columns, one call per pair of blocks, the rows assembled on the host."""
+    from . import lib as L
+    from .ops import ops
+    J = len(cols)
+    if J <= L.PP_IS_MOMENTS_MAX_COLS:
+        return ops.is_moments_groups(lw, list(cols), int(n_per), stats).cpu().numpy()
+    half = L.PP_IS_MOMENTS_MAX_COLS // 2
+    blocks = [list(range(b, min(J, b + half))) for b in range(0, J, half)]
+    pairs = [(a, b) for a in range(len(blocks)) for b in range(a + 1, len(blocks))]
+    parts = torch.cat([ops.is_moments_groups(lw, [cols[j] for j in blocks[a] + blocks[b]], int(n_per), stats)
+                       for a, b in pairs], 1).cpu().numpy()
+    M = parts.shape[0]
+    out = np.zeros((M, L.PP_IS_MOMENTS_WIDTH(J)))
+    where = {}
+    e = 4 + 2 * J
+    for j in range(J):
+        for k in range(j, J):
+            where[(j, k)] = e
+            e += 1
+    at = 0
+    for a, b in pairs:
+        idx = blocks[a] + blocks[b]
+        n = len(idx)
+        part = parts[:, at:at + L.PP_IS_MOMENTS_WIDTH(n)]
+        at += L.PP_IS_MOMENTS_WIDTH(n)
+        out[:, :4] = part[:, :4]
+        q = 4 + 2 * n
+        for u in range(n):
+            out[:, 4 + idx[u]], out[:, 4 + J + idx[u]] = part[:, 4 + u], part[:, 4 + n + u]
+            for v in range(u, n):
+                out[:, where[(idx[u], idx[v])]] = part[:, q]
+                q += 1
+    return out
+
+
+def joint_batch(posteriors, addresses=None):
+    """[p.joint(addresses) for p in posteriors] - and, where the posteriors are the M groups of ONE
+    Model.posterior_results_batch execution in order, the same numbers bit for bit from ONE pp_is_moments_groups launch over all
+    groups (the maxima from the call's own [M, 6] statistics) and one device-to-host copy."""
+    posteriors = list(posteriors)
+    if not posteriors:
+        return []
+    first = posteriors[0].__dict__.get('_batch')
+    log = posteriors[0].__dict__.get('_batch_log')
+    M = len(posteriors)
+    fast = first is not None and log is not None and first[2] is not None and first[0].numel() == M * first[4] and \
+        os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0'
+    for g, p in enumerate(posteriors):
+        b = p.__dict__.get('_batch')
+        fast = fast and b is not None and b[0] is first[0] and b[1] is first[1] and b[2] is first[2] and b[3] == g and \
+            p.__dict__.get('_batch_log') is log
+    if not fast:
+        return [p.joint(addresses) for p in posteriors]
+    chosen, _ = posteriors[0]._joint_columns(addresses)
+    whole = {a: rec[0] for entry in log for a, rec in entry.items()}
+    _, lw, group_stats, _, N = first
+    return _joint_rows(chosen, _moment_rows(lw, [whole[a] for a in chosen], N, group_stats))
 
 
 def resample_batch(posteriors, num_samples, seed=None, offset=0):

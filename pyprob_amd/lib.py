@@ -29,6 +29,15 @@ def larc_scratch_floats(n_params, n_tensors):
 
 PP_IS_STATS_SCRATCH = 6144   # doubles (include/pyprob_amd.h)
 PP_IS_CDF_TILE = 2048        # particles per workgroup of pp_is_cdf_groups (include/pyprob_amd.h)
+PP_IS_MOMENTS_MAX_COLS = 16  # columns of one pp_is_moments_groups call (include/pyprob_amd.h)
+
+
+def PP_IS_MOMENTS_WIDTH(n_cols):
+    """Doubles per group of pp_is_moments_groups' output (include/pyprob_amd.h): 4 weight numbers, J pivots, J sums and the
+    upper triangle of J (J + 1) / 2 products."""
+    n_cols = int(n_cols)
+    return 4 + 2 * n_cols + n_cols * (n_cols + 1) // 2
+
 
 i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p
 
@@ -180,6 +189,8 @@ PROTOTYPES = {
     'pp_is_cdf_workspace_bytes': (C.c_size_t, [i32, i32]),
     'pp_is_cdf_groups': (C.c_int, [vp, i32, i32, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_resample_groups': (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    'pp_is_moments_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
+    'pp_is_moments_groups': (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

@@ -213,6 +213,8 @@ class Model:
         emp._all_values, emp._all_log_weights = all_values, all_lw
         emp.num_paths = n_paths
         emp.statement_log = ls.log       # per statement index: {address: (values [n], address id)} - what each path drew
+        # which particles executed each entry (merged on first use: Empirical.statement_rows) and the names of the statements
+        emp._statement_rows_raw, emp.statement_names = ls.log_rows, dict(ls.names)
         return emp
 
     # ---- launch plan of a static lock-step program ---------------------------------------------------------------------
@@ -589,7 +591,7 @@ class Model:
                                                    for _, a, _, b, _, _, _ in terms):
             obs_index = {name: i for i, name in enumerate(net._obs_names)}       # position in the observation vector
         new = dict(addr=int(draw['addr']), address=address, prior=draw['prior'], prior_term=draw['prior_term'], terms=terms, sig=sig,
-                   observe=self._observe_values(observe), verified=False, obs_index=obs_index)
+                   observe=self._observe_values(observe), verified=False, obs_index=obs_index, names=dict(ls.names))
         old = plans.get(key)
         if old is not None and old['sig'] == sig and old['addr'] == new['addr'] and old['observe'] != new['observe']:
             new['verified'] = True       # same constants under different observations: they do not depend on the observed values
@@ -617,6 +619,7 @@ class Model:
             emp._all_values, emp._all_log_weights = all_values, all_lw
             emp.num_paths = 1
             emp.statement_log = [{plan['address']: (all_values, plan['addr'])}]
+            emp._statement_rows_raw, emp.statement_names = [{plan['address']: None}], dict(plan.get('names', {}))
             emp.replayed_plan = True
             return emp
         net._infer_init(observe)                        # InferenceNetwork._infer_init (inference_network.py:141-148)
@@ -640,6 +643,7 @@ class Model:
         emp._all_values, emp._all_log_weights = all_values, all_lw
         emp.num_paths = 1
         emp.statement_log = [{plan['address']: (all_values, plan['addr'])}]
+        emp._statement_rows_raw, emp.statement_names = [{plan['address']: None}], dict(plan.get('names', {}))
         emp.replayed_plan = True
         return emp
 
@@ -988,6 +992,7 @@ class Model:
         lw_all = ls.lw
         v_parts, lw_parts = values.split(N), lw_all.split(N)
         log_parts = [[(a, rec[0].split(N), rec[1]) for a, rec in entry.items()] for entry in ls.log]
+        names = dict(ls.names)
         out = []
         for g in range(M):
             v_g, lw_g = v_parts[g], lw_parts[g]
@@ -1000,8 +1005,10 @@ class Model:
             emp._all_values, emp._all_log_weights = all_v, all_lw
             if v_g is all_v:      # (no particle dropped) the call's whole tensors: resample_batch serves all groups in one launch
                 emp._batch, emp._batch_runner = (values, lw_all, ls.group_stats, g, N), runner
+                emp._batch_log = ls.log       # (the call's whole columns: joint_batch serves all groups in one launch)
             emp.num_paths = 1
             emp.statement_log = [{a: (parts[g], addr_id) for a, parts, addr_id in entry} for entry in log_parts]
+            emp._statement_rows_raw, emp.statement_names = ls.log_rows, names
             emp.rename('Posterior, IC, traces: {:,}, ESS: {:,.2f}'.format(emp.length, emp.effective_sample_size))
             out.append(emp)
         return out

@@ -25,6 +25,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
     is_cdf_groups       Empirical.finalize's weights as a running sum per group  pyprob/distributions/empirical.py:298-309
     is_resample_groups  Empirical.sample / resample: multinomial draws (Philox)   pyprob/distributions/empirical.py:392-408, 617-637
+    is_moments_groups   weighted first and second moments of several latents per group   pyprob/distributions/empirical.py:298-309, 451-466, 668-690
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -78,6 +79,7 @@ _lib.define('is_stats(Tensor lw, Tensor? x, Tensor(a!) scratch) -> Tensor')
 _lib.define('is_cdf_groups(Tensor lw, int n_per, Tensor? stats) -> Tensor')
 _lib.define('is_resample_groups(Tensor cdf, Tensor? values, int n_per, int lo, int hi, int n_out, int seed, int offset, '
             'bool want_index) -> (Tensor, Tensor)')
+_lib.define('is_moments_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? stats) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
@@ -735,6 +737,32 @@ def _is_resample_groups_hip(cdf, values, n_per, lo, hi, n_out, seed, offset, wan
     return index, value
 
 
+def _is_moments_groups_hip(lw, cols, n_per, stats):
+    """[M, PP_IS_MOMENTS_WIDTH(J)] (float64): the weight sums, pivots, first and second moments about the pivots of the J columns
+    over each of the M groups of n_per particles (pp_is_moments_groups). stats: as for is_cdf_groups."""
+    lib = L.load()
+    cols = list(cols)
+    _same_device(lw, stats, *cols)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_moments_groups')
+    J = len(cols)
+    if not 1 <= J <= L.PP_IS_MOMENTS_MAX_COLS:
+        raise RuntimeError('pyprob_hip::is_moments_groups: 1 .. %d columns per call' % L.PP_IS_MOMENTS_MAX_COLS)
+    for c in cols:
+        if _f32(c, 'cols').dim() != 1 or c.numel() != lw.numel():
+            raise RuntimeError('pyprob_hip::is_moments_groups: every column must be a 1-D tensor of the log-weights\' M * n_per elements')
+    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
+        raise RuntimeError('pyprob_hip::is_moments_groups: stats must be a contiguous float64 tensor of [M, 6]')
+    out = torch.empty((M, L.PP_IS_MOMENTS_WIDTH(J)), dtype=torch.float64, device=lw.device)
+    need = lib.pp_is_moments_workspace_bytes(M, int(n_per), J)
+    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    ptrs = (C.c_void_p * J)(*[c.data_ptr() for c in cols])
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_moments_groups(lw.data_ptr(), C.cast(ptrs, C.c_void_p), J, M, int(n_per), L.ptr(stats), out.data_ptr(),
+                                      ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_moments_groups')
+    return out
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -754,6 +782,7 @@ _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')
 _lib.impl('is_cdf_groups', _is_cdf_groups_hip, 'CUDA')
 _lib.impl('is_resample_groups', _is_resample_groups_hip, 'CUDA')
+_lib.impl('is_moments_groups', _is_moments_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')

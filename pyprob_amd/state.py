@@ -288,6 +288,8 @@ class PathExecutor:
         self.n = n
         self.dev = device
         self.log = []                 # per statement index: {address: recorded values ...}
+        self.log_rows = []            # per statement index: {address: None (every particle) | the row lists that executed it}
+        self.names = {}               # sample(..., name=...) -> the address of its first use
         self.pending = []
         self.path_id = 0
         self.start_path(None, [], 0, 0)
@@ -315,6 +317,23 @@ class PathExecutor:
         self.observes = 0
         self.prev_addr_id = None
         self.prev_unknown = False
+
+    def note_statement(self, j, address, name):
+        """Statement j of this execution wrote its values into log[j][address] for the particles of this path: remember which
+        (Empirical.statement_rows) and the statement's name. A replayed statement was noted by the execution that drew it."""
+        if name is not None:
+            self.names.setdefault(name, address)
+        if j < self.replay_statements:
+            return
+        while len(self.log_rows) <= j:
+            self.log_rows.append({})
+        rec = self.log_rows[j]
+        if self.rows is None:
+            rec[address] = None
+        elif address not in rec:
+            rec[address] = [self.rows]
+        elif rec[address] is not None:
+            rec[address].append(self.rows)
 
     def global_rows(self, mask=None):
         """Global particle indices of the (masked) elements of this execution's tensors; None = every particle."""
@@ -1379,6 +1398,7 @@ def sample(distribution, name=None, address=None, control=True):
         variable = Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
                             log_prob=None, control=control, name=name)
         _current_trace.add(variable)
+        ls.note_statement(ls.statement - 1, addr, name)
         hist = getattr(ls, 'history', None)
         if hist is not None:
             hist.append((variable, ls.log[ls.statement - 1][addr][0], None, value))
@@ -1392,6 +1412,7 @@ def sample(distribution, name=None, address=None, control=True):
         variable = Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
                             log_prob=None, control=True, name=name)
         _current_trace.add(variable)
+        ls.note_statement(ls.statement - 1, addr, name)
         hist = getattr(ls, 'history', None)
         if hist is not None:
             rec = ls.log[ls.statement - 1].get(addr) if ls.statement - 1 < len(ls.log) else None
