@@ -703,6 +703,62 @@ int pp_is_moments_groups(const float* lw /*dev [M n_per]*/, const float* const* 
                          double* out /*dev double [M, PP_IS_MOMENTS_WIDTH(J)]*/, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* Weighted histograms of one latent (1-D) or a pair of latents (2-D) of a lock-step posterior call on the device, and the extent
+ * of a latent. The reference normalises the weights on the host (finalize, pyprob/distributions/empirical.py:298-309) and draws
+ * its histogram from all values and weights on the host (plot_histogram, pyprob/distributions/empirical.py:889-914); here the M
+ * groups of a batched call are binned by one call and only the rows of bins travel.
+ *   pp_is_hist_groups   row g of `out` is [2][slots] 64-bit integers: out[g][0][s] the fixed-point mass of slot s, out[g][1][s] the
+ *                       number of particles in it, over the n_per particles of group g.
+ *                       WEIGHTS. w = exp((double)lw - max_g) in fp64; max_g = stats[6 g] when `stats` (dev double [M, 6], what
+ *                       pp_is_stats or pp_is_fused_groups reduced) is given, else a first launch finds the maximum of the finite
+ *                       log-weights; both give the same bits. A particle whose lw is not finite (-inf, +inf, NaN) is SKIPPED
+ *                       entirely: it is in no slot and no count, and its x / y (rows a diverged path never wrote) are not
+ *                       interpreted. No finite log-weight in the group: the row is all zero.
+ *                       FIXED POINT. A particle adds q = llrint(min(w, 1) 2^S) to its slot and 1 to the slot's count, with
+ *                       S = pp_is_hist_shift(n_per) = 62 - ceil(log2(n_per)): a group's total is at most n_per 2^S <= 2^62 and
+ *                       cannot overflow (w <= 1 whenever max_g is the maximum; the clamp keeps the guarantee under a wrong `stats`).
+ *                       Integer sums do not depend on the order of the additions: two identical calls give the same bits, group
+ *                       g of an M-group call equals the one-group call on its slice, and so would any other tiling. The caller
+ *                       forms the posterior mass of a slot as slot / total, total = the exact integer sum of all slots of the row.
+ *                       Derived bound: |slot - sum_i w_i 2^S| <= 0.5 count + 2^-48 sum_i w_i 2^S (half a unit of rounding per
+ *                       particle, 16 fp64 ulp for the device exp); S = 42 at n_per = 10^6.
+ *                       BINS. edges_x holds bins_x + 1 strictly increasing finite doubles - the caller guarantees it; this layer
+ *                       cannot check device memory without a launch and does not. edges_x_stride = 0: one array shared by the
+ *                       groups, else group g reads edges_x + g edges_x_stride (stride >= bins_x + 1). In fp64, bin b holds
+ *                       e_b <= x < e_{b+1} and the last bin also x == e_bins: numpy.searchsorted(edges, x, 'right') - 1 with
+ *                       numpy.histogram's right-edge rule, by binary search over the edges staged in LDS (uniform or not).
+ *                       1-D (y, edges_y NULL; bins_y = 1): slots = bins_x + 3 = [bins ..., below (x < e_0, -inf), above
+ *                       (x > e_last, +inf), x is NaN]. 2-D: slots = bins_x bins_y + 2 = [bin ix bins_y + iy ..., outside (no
+ *                       coordinate NaN, either out of its range), either coordinate NaN].
+ *                       Dependent launches on the caller's stream: a workgroup of 256 threads bins one tile of one group (2048
+ *                       particles up to 256 bins, 8192 above) into an LDS histogram (64-bit mass and 32-bit count by integer LDS
+ *                       adds; with the edges about 41 KB at 2048 bins) and STORES its partial row in the workspace; a second launch
+ *                       adds the partial rows of every group, one thread per slot (a group of one tile stores its row in `out`
+ *                       directly). No global atomics, no workgroup waits for another.
+ *   pp_is_extent_groups out[g] = { min x, max x, particles counted, particles whose x is NaN }: the exact fp32 minimum and maximum,
+ *                       widened to double, over the particles of group g with a finite lw and a non-NaN x (+-inf count), the
+ *                       number of those, and the number of particles with a finite lw whose x is NaN. Nothing counted:
+ *                       +inf, -inf, 0, k. Minima, maxima and integer counts do not depend on the order: the identities above hold.
+ * Both take any n_per >= 1 and n_groups >= 0 (0: return 0 without a launch; more than 65535 groups are split over launches) and
+ * write nothing outside `out` and the workspace (pp_is_hist_workspace_bytes / pp_is_extent_workspace_bytes; PP_ENOSPACE when
+ * shorter). Both return PP_EINVAL without a launch for a NULL required pointer (lw, x, edges_x, out, workspace), n_per < 1,
+ * n_groups < 0, M n_per above 2^31 - 1, bins_x < 1, bins_y < 1, bins_x bins_y > PP_IS_HIST_MAX_BINS, y without edges_y or edges_y
+ * without y (1-D: bins_y must be 1), or a stride that is neither 0 nor at least bins + 1. The workspace functions return 0 outside
+ * that envelope. pp_is_hist_shift returns -1 for n_per < 1. */
+#define PP_IS_HIST_MAX_BINS 2048          /* bins_x * bins_y (bins_y = 1 for 1-D) */
+int32_t pp_is_hist_shift(int32_t n_per);  /* S = 62 - ceil(log2(n_per)), 62 for n_per = 1; -1 for n_per < 1 */
+size_t pp_is_hist_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t bins_x, int32_t bins_y);
+int pp_is_hist_groups(const float* lw /*dev [M n_per]*/, const float* x /*dev [M n_per]*/, const float* y /*dev [M n_per] or NULL = 1-D*/,
+                      int32_t n_groups, int32_t n_per,
+                      const double* edges_x /*dev*/, int32_t bins_x, int64_t edges_x_stride /*0 = shared by the groups, else >= bins_x + 1*/,
+                      const double* edges_y /*dev or NULL*/, int32_t bins_y, int64_t edges_y_stride,
+                      const double* stats /*dev double [M, 6] or NULL*/, int64_t* out /*dev [M, 2, slots]*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t pp_is_extent_workspace_bytes(int32_t n_groups, int32_t n_per);
+int pp_is_extent_groups(const float* lw, const float* x, int32_t n_groups, int32_t n_per,
+                        double* out /*dev [M, 4]: min x, max x, particles counted, particles whose x is NaN*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

@@ -25,6 +25,11 @@ def __getattr__(name):
         from .distributions import joint_batch
         globals()[name] = joint_batch
         return joint_batch
+    if name in ('histogram_batch', 'Histogram', 'Histogram2D'):
+        from . import distributions
+        value = getattr(distributions, name)
+        globals()[name] = value
+        return value
     if name == 'Model':
         from .model import Model
         globals()[name] = Model

@@ -742,7 +742,7 @@ class Empirical:
         self._values.append(value)
         self._log_weights.append(0.0 if log_weight is None else float(log_weight))
         self._finalized = False
-        for k in ('_dev_cdf', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
+        for k in ('_dev_cdf', '_dev_extent', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
             self.__dict__.pop(k, None)
         # the statement log describes the particles of the lock-step call, not this grown set: marginal / joint must not answer
         # for the old one (statement_log itself stays readable, as before; _latent_table refuses through _log_stale)
@@ -1075,6 +1075,59 @@ class Empirical:
         out['index'] = index
         return out
 
+    # ---- histograms (csrc/is_hist.hip) ---------------------------------------------------------------------------------
+    def _group_stats_row(self):
+        """The [6] statistics row of this group of a batched call on the device (its maximum spares the kernels a launch)."""
+        batch = self.__dict__.get('_batch')
+        return batch[2][batch[3]] if (batch is not None and batch[2] is not None) else None
+
+    def histogram(self, bins=50, range=None, edges=None):
+        """The weighted histogram of the values as a Histogram (edges, mass, density, count, below, above, nan, particles; cdf,
+        quantile, credible_interval, mode). bins: the number of equal bins over `range` = (lo, hi); range=None takes the finite
+        extent of the values (of the particles with a finite log-weight; lo == hi is widened by 0.5 on either side as numpy does;
+        an infinite value needs an explicit range) and the edges are numpy.linspace(lo, hi, bins + 1). edges: the bin edges
+        themselves, strictly increasing and finite (log bins, for instance), instead of bins / range; at most 2048 bins. Bin b
+        holds e_b <= x < e_{b+1}, the last bin also x == e_last (numpy.histogram's rule).
+
+        A device-backed Empirical (the result of a lock-step posterior call, post.marginal(address), a device resample) is binned
+        on the device: pp_is_extent_groups where the range is needed (four doubles come back), then pp_is_hist_groups - weights
+        in fp64, summed in 64-bit fixed point, so the same call gives the same bits every time - and one copy of the row of
+        bins. Every other Empirical, and all of them under PP_EMPIRICAL_DEVICE=0, computes the same Histogram in float64 numpy
+        by the same bin rule (no fixed point: masses agree to rounding, counts exactly)."""
+        self._check_finalized()
+        if self.length == 0:
+            raise ValueError('histogram of an empty Empirical')
+        if self._device_backed():
+            return _device_histograms(self._log_weights, self._values, self.length, bins, range, edges, self._group_stats_row())[0]
+        lw = np.asarray(self._lw, np.float64)
+        x = self.values_numpy()
+        if x.shape != lw.shape:
+            raise ValueError('histogram needs scalar values')
+        e = _hist_edges_for(bins, range, edges, lambda: _host_extent(lw, x)[None])
+        return _histogram_rows(e, _host_hist_row(lw, x, e[0])[None], exact=False)[0]
+
+    def histogram2d(self, x, y, bins=(32, 32), range=None):
+        """The weighted 2-D histogram of two latents of a lock-step call as a Histogram2D (x_edges, y_edges, mass [bx, by],
+        density, count, outside, nan, particles): pp_is_hist_groups over the two columns of the statement log under the call's
+        log-weights, one copy of the row. x / y: addresses or statement names as joint() takes them (an address only some particles
+        executed raises joint()'s ValueError). bins: one number or (bins_x, bins_y), bins_x bins_y <= 2048; range: ((xlo, xhi),
+        (ylo, yhi)), default the finite extent of each column (pp_is_extent_groups)."""
+        chosen, cols = self._joint_columns([x, y])
+        lw = self._all_lw()
+        bx, by = (bins, bins) if np.ndim(bins) == 0 else bins
+        _check_bins(bx)
+        _check_bins(by)
+        if int(bx) * int(by) > _HIST_MAX_BINS:
+            raise ValueError('at most %d bins (bins_x * bins_y)' % _HIST_MAX_BINS)
+        rx, ry = (None, None) if range is None else range
+        from .ops import ops
+        n = lw.numel()
+        ex = _hist_edges_for(bx, rx, None, lambda: ops.is_extent_groups(lw, cols[0], n).cpu().numpy())[0]
+        ey = _hist_edges_for(by, ry, None, lambda: ops.is_extent_groups(lw, cols[1], n).cpu().numpy())[0]
+        row = ops.is_hist_groups(lw, cols[0], cols[1], n, torch.from_numpy(ex).to(lw.device), torch.from_numpy(ey).to(lw.device),
+                                 self._group_stats_row()).cpu().numpy()[0]
+        return _histogram2d_row(chosen, ex, ey, row)
+
     # ---- transformations (each returns a new Empirical) ------------------------------------------------------
     def map(self, func, min_index=None, max_index=None):
         self._check_finalized()
@@ -1220,12 +1273,28 @@ class Empirical:
             return float(np.median(self.values_numpy()))       # :723-724
         return self.resample(1000).median           # empirical.py:727
 
+    def _device_extent(self):
+        """(min, max, counted, NaN values) of a device-backed Empirical from pp_is_extent_groups (computed once per object: four
+        doubles travel, not the particles), or None where the kernel did not look at every particle (it skips those without a
+        finite log-weight, numpy.min over the values does not)."""
+        ext = self.__dict__.get('_dev_extent')
+        if ext is None:
+            from .ops import ops
+            ext = self.__dict__['_dev_extent'] = ops.is_extent_groups(self._log_weights, self._values, self.length).cpu().numpy()[0]
+        return ext if int(ext[2]) + int(ext[3]) == self.length else None
+
     @property
     def min(self):
+        ext = self._device_extent() if self._device_backed() else None
+        if ext is not None:
+            return float('nan') if ext[3] else float(ext[0])
         return float(np.min(self.values_numpy()))
 
     @property
     def max(self):
+        ext = self._device_extent() if self._device_backed() else None
+        if ext is not None:
+            return float('nan') if ext[3] else float(ext[1])
         return float(np.max(self.values_numpy()))
 
     def arg_max(self, map_func):
@@ -1339,6 +1408,230 @@ def _moment_rows(lw, cols, n_per, stats):
                 out[:, where[(idx[u], idx[v])]] = part[:, q]
                 q += 1
     return out
+
+
+_HIST_MAX_BINS = 2048      # PP_IS_HIST_MAX_BINS (include/pyprob_amd.h)
+
+
+class Histogram:
+    """A weighted 1-D histogram of one weighted particle set (Empirical.histogram), float64 numpy: edges [bins + 1], mass [bins]
+    (the posterior weight of every bin: mass.sum() + below + above + nan == 1), density = mass / bin width, count [bins] (int64:
+    the particles per bin), below / above (the weight left and right of the edges; -inf and +inf values sit there), nan (the
+    weight of the particles whose value is NaN) and particles (those with a finite log-weight, binned or not). A group without
+    weight: NaN arrays and particles == 0."""
+
+    def __init__(self, edges, mass, count, below, above, nan, particles):
+        self.edges, self.mass, self.count = edges, mass, count
+        self.below, self.above, self.nan, self.particles = float(below), float(above), float(nan), int(particles)
+        self.density = mass / np.diff(edges)
+
+    def cdf(self):
+        """The cumulative posterior mass AT every edge [bins + 1]: cdf()[0] == below, cdf()[-1] == 1 - above - nan."""
+        return self.below + np.concatenate([[0.0], np.cumsum(self.mass)])
+
+    def quantile(self, q):
+        """The value below which a fraction q of the posterior mass lies, for a scalar or an array q in [0, 1]: the cumulative
+        mass interpolated linearly INSIDE the bin it crosses q in (the leftmost such point where bins are empty). Its resolution
+        is the bin width: the histogram does not know where in a bin its particles sit. Mass below or above the edges is not
+        resolved at all: a quantile that falls there is edges[0] / edges[-1], with a RuntimeWarning (so is one beyond 1 - nan)."""
+        qs = np.asarray(q, np.float64)
+        if np.any((qs < 0) | (qs > 1)):
+            raise ValueError('quantiles lie in [0, 1]')
+        if self.particles == 0:
+            return float('nan') if qs.ndim == 0 else np.full(qs.shape, np.nan)
+        c = self.cdf()
+        k = np.searchsorted(c, qs, side='left')      # the first edge whose cumulative mass reaches q
+        outside = (qs < c[0]) | (qs > c[-1] + 1e-12)      # (1e-12: the cumulative sum of all the mass is 1 to rounding only)
+        if np.any(outside):
+            warnings.warn('quantile outside the histogram\'s edges (mass below {:.3g}, above {:.3g}, NaN {:.3g}): the edge is '
+                          'returned'.format(self.below, self.above, self.nan), RuntimeWarning, stacklevel=2)
+        kk = np.clip(k, 1, len(c) - 1)
+        step = c[kk] - c[kk - 1]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            frac = np.where(step > 0, (qs - c[kk - 1]) / np.where(step > 0, step, 1.0), 0.0)
+        out = self.edges[kk - 1] + np.clip(frac, 0.0, 1.0) * (self.edges[kk] - self.edges[kk - 1])
+        out = np.where(k == 0, self.edges[0], np.where(k > len(c) - 1, self.edges[-1], out))
+        return float(out) if qs.ndim == 0 else out
+
+    def credible_interval(self, level=0.9):
+        """The equal-tailed interval (quantile((1 - level) / 2), quantile((1 + level) / 2))."""
+        if not 0 < level < 1:
+            raise ValueError('level lies in (0, 1)')
+        return self.quantile((1.0 - level) / 2.0), self.quantile((1.0 + level) / 2.0)
+
+    @property
+    def mode(self):
+        """The centre of the bin of highest density (the first of equals)."""
+        if self.particles == 0 or not np.isfinite(self.density).any():
+            return float('nan')
+        b = int(np.nanargmax(self.density))
+        return float(0.5 * (self.edges[b] + self.edges[b + 1]))
+
+    def __repr__(self):
+        return 'Histogram(bins:{}, range:[{}, {}], particles:{}, below:{:.3g}, above:{:.3g}, nan:{:.3g})'.format(
+            len(self.mass), self.edges[0], self.edges[-1], self.particles, self.below, self.above, self.nan)
+
+
+class Histogram2D:
+    """A weighted 2-D histogram of two latents of one weighted particle set (Empirical.histogram2d), float64 numpy: addresses,
+    x_edges [bx + 1], y_edges [by + 1], mass [bx, by] (mass.sum() + outside + nan == 1), density = mass / bin area, count [bx, by]
+    (int64), outside (the weight with either coordinate out of its range), nan (either coordinate NaN) and particles."""
+
+    def __init__(self, addresses, x_edges, y_edges, mass, count, outside, nan, particles):
+        self.addresses = list(addresses)
+        self.x_edges, self.y_edges, self.mass, self.count = x_edges, y_edges, mass, count
+        self.outside, self.nan, self.particles = float(outside), float(nan), int(particles)
+        self.density = mass / (np.diff(x_edges)[:, None] * np.diff(y_edges)[None, :])
+
+    def __repr__(self):
+        return 'Histogram2D(addresses:{}, bins:{}x{}, particles:{}, outside:{:.3g}, nan:{:.3g})'.format(
+            self.addresses, self.mass.shape[0], self.mass.shape[1], self.particles, self.outside, self.nan)
+
+
+def _check_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= _HIST_MAX_BINS:
+        raise ValueError('bins must be an integer in 1 .. %d, not %r' % (_HIST_MAX_BINS, bins))
+
+
+def _check_edges(e):
+    """edges [.., bins + 1] in float64: finite and strictly increasing along the last axis, at most 2048 bins."""
+    if e.shape[-1] < 2 or e.shape[-1] - 1 > _HIST_MAX_BINS:
+        raise ValueError('edges must hold 2 .. %d values (at most %d bins)' % (_HIST_MAX_BINS + 1, _HIST_MAX_BINS))
+    if not np.isfinite(e).all() or not (np.diff(e, axis=-1) > 0).all():
+        raise ValueError('edges must be finite and strictly increasing (a range too narrow for its number of bins in float64 is not)')
+    return e
+
+
+def _auto_range(ext):
+    """(lo [M], hi [M]) from rows of (min, max, counted, NaN values): the finite extent; nothing counted: (0, 1) as numpy takes for
+    no data; lo == hi: widened by 0.5 on either side as numpy does."""
+    ext = np.asarray(ext, np.float64).reshape(-1, 4)
+    none = ext[:, 2] == 0
+    lo, hi = np.where(none, 0.0, ext[:, 0]), np.where(none, 1.0, ext[:, 1])
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError('the extent of the values is not finite (an infinite value under a finite weight): pass range=(lo, hi)')
+    same = lo == hi
+    return np.where(same, lo - 0.5, lo), np.where(same, hi + 0.5, hi)
+
+
+def _linspace_rows(lo, hi, bins):
+    """numpy.linspace(lo[g], hi[g], bins + 1) for every g as [M, bins + 1]: one vectorised call where that is the same arithmetic
+    (numpy switches formula for ALL rows when any step is zero)."""
+    if np.all((hi - lo) / bins != 0):
+        return np.ascontiguousarray(np.linspace(lo, hi, bins + 1, axis=-1))
+    return np.stack([np.linspace(a, b, bins + 1) for a, b in zip(lo, hi)])
+
+
+def _hist_edges_for(bins, range, edges, extent):
+    """The edges [M, bins + 1] (M = 1 unless `extent` returns more rows) of histogram(bins, range, edges); extent() is called only
+    where the range has to be found."""
+    if edges is not None:
+        e = np.array(edges, np.float64)
+        if e.ndim != 1:
+            raise ValueError('edges must be one-dimensional')
+        return _check_edges(e)[None]
+    _check_bins(bins)
+    if range is None:
+        lo, hi = _auto_range(extent())
+    else:
+        lo, hi = (float(v) for v in range)
+        if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
+            raise ValueError('range must be finite with lo <= hi, not %r' % (range,))
+        if lo == hi:
+            lo, hi = lo - 0.5, hi + 0.5
+        lo, hi = np.asarray([lo]), np.asarray([hi])
+    return _check_edges(_linspace_rows(lo, hi, int(bins)))
+
+
+def _histogram_rows(edges, rows, exact=True):
+    """M Histograms from edges [1 or M, bins + 1] and rows [M, 2, bins + 3] (masses | counts over bins, below, above, NaN): the
+    rows of pp_is_hist_groups (exact: fixed point - a slot's mass is slot / total, total = the exact integer sum of the row) or
+    float64 sums of the host route. The same elementwise arithmetic whatever M is."""
+    rows = np.asarray(rows)
+    M, bins = rows.shape[0], rows.shape[2] - 3
+    fixed = rows[:, 0, :]
+    total = fixed.sum(1)        # (int64 for the device rows: at most 2^62, exact)
+    ok = total > 0
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mass = np.where(ok[:, None], fixed.astype(np.float64) / np.where(ok, total, 1).astype(np.float64)[:, None], np.nan)
+    count = rows[:, 1, :].astype(np.int64)
+    particles = np.where(ok, count.sum(1), 0)
+    return [Histogram(edges[g if edges.shape[0] > 1 else 0], mass[g, :bins], count[g, :bins], mass[g, bins], mass[g, bins + 1],
+                      mass[g, bins + 2], particles[g]) for g in np.arange(M)]
+
+
+def _histogram2d_row(addresses, ex, ey, row):
+    bx, by = len(ex) - 1, len(ey) - 1
+    fixed, count = row[0], row[1].astype(np.int64)
+    total = int(fixed.sum())
+    mass = fixed.astype(np.float64) / float(total) if total > 0 else np.full(fixed.shape, np.nan)
+    return Histogram2D(addresses, ex, ey, mass[:bx * by].reshape(bx, by), count[:bx * by].reshape(bx, by), mass[bx * by],
+                       mass[bx * by + 1], int(count.sum()) if total > 0 else 0)
+
+
+def _host_extent(lw, x):
+    """pp_is_extent_groups' row in numpy: min, max over the values with a finite log-weight that are not NaN, the two counts."""
+    fin = np.isfinite(lw)
+    nan = np.isnan(x)
+    v = x[fin & ~nan]
+    return np.array([v.min() if v.size else np.inf, v.max() if v.size else -np.inf, v.size, int((fin & nan).sum())])
+
+
+def _host_hist_row(lw, x, e):
+    """The row [2, bins + 3] of the host route: float64 weight sums and counts per slot by pp_is_hist_groups' bin rule."""
+    bins = len(e) - 1
+    fin = np.isfinite(lw)
+    l, v = lw[fin], x[fin]
+    w = np.exp(l - l.max()) if l.size else np.zeros(0)
+    with np.errstate(invalid='ignore'):
+        b = np.searchsorted(e, v, side='right') - 1
+        slot = np.where(np.isnan(v), bins + 2, np.where(v < e[0], bins, np.where(v > e[-1], bins + 1, np.minimum(b, bins - 1))))
+    return np.stack([np.bincount(slot, weights=w, minlength=bins + 3), np.bincount(slot, minlength=bins + 3).astype(np.float64)])
+
+
+def _device_histograms(lw, x, n_per, bins, range, edges, stats):
+    """The Histograms of the M groups of n_per particles of (lw, x) on the device: pp_is_extent_groups and a copy of [M, 4] where
+    the range has to be found, pp_is_hist_groups (edges shared by the groups, or one row per group from its own extent) and a copy
+    of the rows."""
+    from .ops import ops
+    e = _hist_edges_for(bins, range, edges, lambda: ops.is_extent_groups(lw, x, int(n_per)).cpu().numpy())
+    dev = torch.from_numpy(e if e.shape[0] > 1 else e[0]).to(lw.device)
+    return _histogram_rows(e, ops.is_hist_groups(lw, x, None, int(n_per), dev, None, stats).cpu().numpy())
+
+
+def histogram_batch(posteriors, bins=50, range=None, address=None):
+    """[p.histogram(bins, range) for p in posteriors], or with address= [p.marginal(address).histogram(bins, range) ...] - and,
+    where the posteriors are the M groups of ONE Model.posterior_results_batch execution in order (recognised as joint_batch
+    recognises them), the same Histograms bit for bit from one pp_is_extent_groups launch (range=None: every group gets edges over
+    its own extent), ONE pp_is_hist_groups launch sequence over all groups (the maxima from the call's own [M, 6] statistics) and
+    one device-to-host copy of the rows. address=None: the value forward() returned; else an address (or statement name) of the
+    call's statement log that every particle executed. Anything else is served by the loop."""
+    posteriors = list(posteriors)
+    if not posteriors:
+        return []
+    first = posteriors[0].__dict__.get('_batch')
+    log = posteriors[0].__dict__.get('_batch_log')
+    M = len(posteriors)
+    fast = first is not None and log is not None and first[2] is not None and first[0].numel() == M * first[4] and \
+        os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0'
+    for g, p in enumerate(posteriors):
+        b = p.__dict__.get('_batch')
+        fast = fast and b is not None and b[0] is first[0] and b[1] is first[1] and b[2] is first[2] and b[3] == g and \
+            p.__dict__.get('_batch_log') is log and p._device_backed()
+    column = None
+    if fast:
+        values, lw, group_stats, _, N = first
+        if address is None:
+            column = values
+        else:
+            a, _, rows = posteriors[0]._latent(address)
+            whole = {k: rec[0] for entry in log for k, rec in entry.items()}
+            column = whole.get(a) if rows is None else None       # (a branch's address: each group's marginal has its own particles)
+            if column is not None and (column.dtype != torch.float32 or column.numel() != lw.numel() or not column.is_contiguous()):
+                column = None
+    if column is None:
+        return [(p if address is None else p.marginal(address)).histogram(bins, range) for p in posteriors]
+    return _device_histograms(lw, column, N, bins, range, None, group_stats)
 
 
 def joint_batch(posteriors, addresses=None):

@@ -26,6 +26,8 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_cdf_groups       Empirical.finalize's weights as a running sum per group  pyprob/distributions/empirical.py:298-309
     is_resample_groups  Empirical.sample / resample: multinomial draws (Philox)   pyprob/distributions/empirical.py:392-408, 617-637
     is_moments_groups   weighted first and second moments of several latents per group   pyprob/distributions/empirical.py:298-309, 451-466, 668-690
+    is_hist_groups      weighted 1-D / 2-D histogram of a latent (pair) per group, fixed point   pyprob/distributions/empirical.py:298-309, 889-914
+    is_extent_groups    minimum, maximum and NaN count of a latent per group             pyprob/distributions/empirical.py:770-794
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -80,6 +82,8 @@ _lib.define('is_cdf_groups(Tensor lw, int n_per, Tensor? stats) -> Tensor')
 _lib.define('is_resample_groups(Tensor cdf, Tensor? values, int n_per, int lo, int hi, int n_out, int seed, int offset, '
             'bool want_index) -> (Tensor, Tensor)')
 _lib.define('is_moments_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? stats) -> Tensor')
+_lib.define('is_hist_groups(Tensor lw, Tensor x, Tensor? y, int n_per, Tensor edges_x, Tensor? edges_y, Tensor? stats) -> Tensor')
+_lib.define('is_extent_groups(Tensor lw, Tensor x, int n_per) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
@@ -763,6 +767,60 @@ def _is_moments_groups_hip(lw, cols, n_per, stats):
     return out
 
 
+def _hist_edges(e, M, what):
+    """(bins, stride) of an edge tensor: [bins + 1] shared by the groups (stride 0) or [M, bins + 1], one row per group."""
+    if e.dtype != torch.float64 or not e.is_contiguous() or e.dim() not in (1, 2) or e.shape[-1] < 2 or (e.dim() == 2 and e.shape[0] != M):
+        raise RuntimeError('pyprob_hip::is_hist_groups: %s must be a contiguous float64 tensor of [bins + 1] or [M, bins + 1]' % what)
+    return int(e.shape[-1]) - 1, (0 if e.dim() == 1 else int(e.shape[-1]))
+
+
+def _is_hist_groups_hip(lw, x, y, n_per, edges_x, edges_y, stats):
+    """[M, 2, slots] (int64): the fixed-point masses and the particle counts of the slots of each of the M groups of n_per particles
+    (pp_is_hist_groups); slots = bins + 3 (1-D) or bins_x bins_y + 2 (2-D: y and edges_y given). Edges of dim 1 are shared by the
+    groups, [M, bins + 1] is one row per group. stats: as for is_cdf_groups."""
+    lib = L.load()
+    _same_device(lw, x, y, edges_x, edges_y, stats)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_hist_groups')
+    if _f32(x, 'x').dim() != 1 or x.numel() != lw.numel() or not x.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_hist_groups: x must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    if (y is None) != (edges_y is None):
+        raise RuntimeError('pyprob_hip::is_hist_groups: y and edges_y are given together (2-D) or not at all (1-D)')
+    if y is not None and (_f32(y, 'y').dim() != 1 or y.numel() != lw.numel() or not y.is_contiguous()):
+        raise RuntimeError('pyprob_hip::is_hist_groups: y must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    bx, sx = _hist_edges(edges_x, M, 'edges_x')
+    by, sy = _hist_edges(edges_y, M, 'edges_y') if edges_y is not None else (1, 0)
+    if bx * by > L.PP_IS_HIST_MAX_BINS:
+        raise RuntimeError('pyprob_hip::is_hist_groups: at most %d bins per call' % L.PP_IS_HIST_MAX_BINS)
+    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
+        raise RuntimeError('pyprob_hip::is_hist_groups: stats must be a contiguous float64 tensor of [M, 6]')
+    slots = bx + 3 if y is None else bx * by + 2
+    out = torch.empty((M, 2, slots), dtype=torch.int64, device=lw.device)
+    need = lib.pp_is_hist_workspace_bytes(M, int(n_per), bx, by)
+    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_hist_groups(lw.data_ptr(), x.data_ptr(), L.ptr(y), M, int(n_per), edges_x.data_ptr(), bx, sx, L.ptr(edges_y),
+                                   by, sy, L.ptr(stats), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_hist_groups')
+    return out
+
+
+def _is_extent_groups_hip(lw, x, n_per):
+    """[M, 4] (float64): min x, max x, particles counted, particles whose x is NaN, per group of n_per particles
+    (pp_is_extent_groups)."""
+    lib = L.load()
+    _same_device(lw, x)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_extent_groups')
+    if _f32(x, 'x').dim() != 1 or x.numel() != lw.numel() or not x.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_extent_groups: x must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    out = torch.empty((M, 4), dtype=torch.float64, device=lw.device)
+    need = lib.pp_is_extent_workspace_bytes(M, int(n_per))
+    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_extent_groups(lw.data_ptr(), x.data_ptr(), M, int(n_per), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_extent_groups')
+    return out
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -783,6 +841,8 @@ _lib.impl('is_stats', _is_stats_hip, 'CUDA')
 _lib.impl('is_cdf_groups', _is_cdf_groups_hip, 'CUDA')
 _lib.impl('is_resample_groups', _is_resample_groups_hip, 'CUDA')
 _lib.impl('is_moments_groups', _is_moments_groups_hip, 'CUDA')
+_lib.impl('is_hist_groups', _is_hist_groups_hip, 'CUDA')
+_lib.impl('is_extent_groups', _is_extent_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
