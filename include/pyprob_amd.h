@@ -277,6 +277,47 @@ int pp_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                  int32_t flags, const int32_t* skip, void* stream);
 
 /*
+ * The same step for the training paths: workgroups are launched for the LIVE chunks only. The library keeps, per bound
+ * gradient buffer, a host-side mark per tensor - "its gradient or its moments may be non-zero" (touched). pp_ic_loss marks
+ * the tensors its backward pass writes; every other entry of this header that can write into a bound gradient or moment
+ * buffer (pp_dp_reduce_grads outside its skip ranges, pp_adam_step itself - its caller filled the gradients -, pp_sgd_step,
+ * pp_larc_scale, pp_axpy, pp_gemm_f32, ...) and a live step with weight decay mark all tensors; a caller that writes the buffers itself (checkpoint load, its own collectives, torch operators) calls
+ * pp_adam_live_mark_touched. Marks are never cleared. While a tensor is untouched its gradient and moments are exactly
+ * zero, so without weight decay Adam only advances its step count: the launch covers the chunk runs of the touched tensors
+ * (all tensors when weight_decay != 0) and one thread per remaining tensor. Same results as pp_adam_step, bit for bit; the
+ * two may alternate on one state. Falls back to pp_adam_step's launch when `grads` is not bound, when the runs exceed the
+ * kernel-argument table (4) and with PP_ADAM_LIVE=0 (read per call).
+ *   pp_adam_live_bind     tensor_first host [n_tensors + 1]: first chunk of each tensor, ascending, [n_tensors] = n_params / 1024.
+ *                         clean != 0: the three buffers were just zero-filled (no tensor touched); 0: all tensors touched.
+ *                         Re-binding replaces the record; pp_adam_live_unbind forgets it (before the buffers are freed).
+ *   pp_adam_live_mark_touched   buffer: any pointer into a bound gradient / moment buffer; marks all its tensors.
+ *   pp_adam_live_info     out host int64 [4] = {bound, marks version, tables built so far, untouched tensors};
+ *                         touched_out host uint8 [n_tensors] or NULL.
+ *   pp_adam_live_plan     the run builder alone (host only): live host uint8 [n_tensors]; out host int32 [21] =
+ *                         {runs, workgroups of the runs, gaps, 4 x {first workgroup, first chunk},
+ *                         5 x {first tensor, end tensor} of the gaps}. Returns 0, or 1 when the runs exceed the table
+ *                         (full grid), < 0 on a bad argument.
+ */
+int pp_adam_step_live(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n_params,
+                      const int32_t* chunk_tensor, const float* active, int32_t* tensor_step, int32_t* scratch,
+                      int32_t n_tensors, float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                      int32_t flags, const int32_t* skip, void* stream);
+int pp_adam_live_bind(const float* grads /*dev*/, const float* exp_avg /*dev*/, const float* exp_avg_sq /*dev*/, int64_t n_params,
+                      const int32_t* tensor_first /*host*/, int32_t n_tensors, int32_t clean);
+int pp_adam_live_unbind(const float* grads);
+int pp_adam_live_mark_touched(const void* buffer);
+/* the tensors that hold floats [offset, offset + count) of the bound gradient buffer `grads` (the caller wrote those
+ * gradients, or the moments at the same offsets) */
+int pp_adam_live_mark_range(const float* grads, int64_t offset, int64_t count);
+int pp_adam_live_info(const float* grads, int64_t* out /*host [4]*/, uint8_t* touched_out /*host or NULL*/);
+int pp_adam_live_plan(const int32_t* tensor_first /*host*/, int32_t n_tensors, const uint8_t* live /*host*/,
+                      int32_t* out /*host [21]*/);
+/* the table pp_adam_step_live would launch with for these (bound) buffers now - built, or taken from the record's cache (host
+ * only; `out` as above). Returns 1 when it would launch the full grid. */
+int pp_adam_live_table(const float* grads, const float* exp_avg, const float* exp_avg_sq, int64_t n_params, int32_t n_tensors,
+                       float weight_decay, int32_t* out /*host [21]*/);
+
+/*
  * optimizer.step() for torch.optim.SGD(lr, momentum, nesterov, weight_decay) - Optimizer.SGD of
  * InferenceNetwork._create_optimizer (pyprob/nn/inference_network.py:349-350, nesterov=True there) - over the same flat
  * buffers as pp_adam_step (chunk_tensor / active / grad_scale / flags / skip mean the same):
@@ -1062,7 +1103,9 @@ int pp_dp_overlap_stats(int32_t arm, float* us_out);
 
 int pp_debug_timeline(long long* buf /*dev [16] or NULL*/);
 /* debug: per-workgroup {start, end, problem, split, operands ready, loads issued, first slab landed, K loop done} stamps (10 ns ticks) of the grouped async GEMM launches
- * (mode 1: weight-gradient groups, 2: data-gradient products); buf = dev int64 [8 * cap] or NULL (tools/wg_trace.py) */
+ * (mode 1: weight-gradient groups, 2: data-gradient products); buf = dev int64 [8 * cap] or NULL (tools/wg_trace.py).
+ * mode 3: the Adam launches - {start, tensor known, gradient arrived, p / m / v arrived, corrections ready, stores issued, end,
+ * tensor id} per workgroup (tools/adam_wg_trace.py) */
 int pp_debug_wgtrace(long long* buf, int32_t cap, int32_t mode);
 int pp_debug_clock_probe(int32_t iters, long long* out /*dev [2]*/, float* sink /*dev [1]*/, void* stream);
 

@@ -42,6 +42,7 @@ class HipLoss(torch.autograd.Function):
         flags = L.PP_LOSS_BACKWARD | (0 if network._hip_grads_clean else L.PP_LOSS_ZERO_GRADS)
         batch_dev, batch_host = packed.op_tensors(eng.device)
         eng._ensure_workspace(packed.n_traces, packed.n_rows)
+        eng.mark_touched()      # (autograd and the caller own the gradients on this route: nothing is known about them afterwards)
         loss, status, _ = ops.ic_loss(eng.params, eng.grads, eng.workspace, batch_dev, batch_host, eng.net_handle, flags)
         network._hip_grads_clean = False
         network._hip_status = status

@@ -576,6 +576,7 @@ int pp_cnn2d5c_backward(const pp_net* net, int32_t o, const float* params, const
     pp::CnnGeom g;
     PP_CHECK_ARG(pp::cnn_geom(net, o, g), "pp_cnn2d5c_backward: observable %d is not a CNN2D5C embedding", o);
     PP_CHECK_ARG(flags == 0, "pp_cnn2d5c_backward: flags must be 0");
+    pp::grads_touch_all(grads);
     (void)params;      // (kept in the signature: the forward call's weight images are what backward reads)
     return pp::cnn_backward(net, o, d_features, g.F, n_images, grads, workspace, workspace_bytes, pp::as_stream(stream));
 }

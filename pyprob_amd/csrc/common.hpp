@@ -19,6 +19,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void set_error(const char* fmt, ...);
 
+// Marks of the bound gradient buffers (adam_live.hpp, kernels.hip): every host entry that may leave a non-zero gradient or
+// moment says so, else the live-chunk Adam launch would leave the tensor out. No-ops for pointers outside a bound buffer.
+void grads_touch(const float* ptr);                                  // the tensor that holds this gradient word
+void grads_touch_range(const float* grads, int64_t off, int64_t cnt);   // every tensor in [off, off + cnt) floats
+void grads_touch_all(const void* ptr);                               // all tensors, if ptr lies in a bound gradient / moment buffer
+
 #define PP_CHECK_ARG(cond, ...)          \
     do {                                 \
         if (!(cond)) {                   \

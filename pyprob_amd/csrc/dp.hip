@@ -156,6 +156,16 @@ int dp_reduce_grads(float* grads_full, int64_t n_params, int n_tensors, const fl
                     hipStream_t st) {
     PP_CHECK_ARG(g_rccl.comm && grads_full && status && n_params > 0 && n_tensors >= 0 && n_skip >= 0 && n_skip <= 6 && (!g_ov.pending || n_skip <= 4),
                  "pp_dp_reduce_grads: bad argument");
+    // what the exchange sums in may be another rank's non-zero gradient: every tensor outside the caller's ranges (those are
+    // zero on every rank by agreement) is touched from now on (adam_live.hpp)
+    {
+        int64_t pos = 0;
+        for (int i = 0; i < n_skip; ++i) {
+            grads_touch_range(grads_full, pos, skip_off[i] - pos);
+            pos = skip_off[i] + skip_cnt[i];
+        }
+        grads_touch_range(grads_full, pos, n_params - pos);
+    }
     float* tail = grads_full + n_params;
     hipLaunchKernelGGL(dp_tail_pre_kernel, dim3(1), dim3(256), 0, st, tail, presence, n_tensors, status);
     PP_LAUNCH_CHECK("pp_dp_reduce_grads (tail)");
@@ -293,6 +303,7 @@ int pp_dp_overlap_stats(int32_t arm, float* us_out) {
 }
 
 int pp_dp_allreduce(float* base, const int64_t* off, const int64_t* cnt, int32_t n, void* stream) {
+    for (int i = 0; base && off && cnt && i < n; ++i) pp::grads_touch_range(base, off[i], cnt[i]);
     return pp::dp_allreduce_pieces(base, off, cnt, n, pp::as_stream(stream));
 }
 

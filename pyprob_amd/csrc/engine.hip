@@ -7,6 +7,7 @@
 #include "panel16.hpp"
 #include "wgrad_t1.hpp"
 #include "cnn2d.hpp"
+#include "adam_live.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -65,6 +66,15 @@ int sample_embed_bwd_det(const pp_net* net, const float* params, const float* va
 int adam_step(float* params, float* grads, float* m, float* v, int64_t n_params, const int32_t* chunk_tensor,
               const float* active, int32_t* tensor_step, int32_t* arrived, int n_tensors, float lr, float beta1, float beta2,
               float eps, float wd, float gscale, int flags, const int32_t* skip, hipStream_t st);
+int adam_step_live(float* params, float* grads, float* m, float* v, int64_t n_params, const int32_t* chunk_tensor,
+                   const float* active, int32_t* tensor_step, int32_t* arrived, int n_tensors, float lr, float beta1, float beta2,
+                   float eps, float wd, float gscale, int flags, const int32_t* skip, hipStream_t st);
+int adam_live_bind(const float* grads, const float* m, const float* v, int64_t n_params, const int32_t* first, int n_tensors,
+                   bool clean);
+void adam_live_unbind(const float* grads);
+bool adam_live_table(const float* grads, const float* m, const float* v, int64_t n_params, int n_tensors, bool wd_on,
+                     AdamLiveTable& tab);
+int adam_live_info(const float* grads, int64_t* out, uint8_t* touched_out);
 
 extern long long* g_timeline;   // kernels.hip
 
@@ -890,6 +900,8 @@ static int heads_backward(const Step& s, GradQueue& q) {
         float* dZ1 = w.dZ1 + (int64_t)g0 * w.hid4;
         queue_head_wgrads(s, q, a);
         if (!head_tail_supported(ad.kind, ad.hid, ad.n_out)) {   // (else dz1 was produced by the forward tail)
+            grads_touch(grads + ad.b2);
+            grads_touch(grads + ad.b1);
             PP_TRY(colsum_f32(DY, w.out4, nullptr, n, ad.n_out, grads + ad.b2, nullptr, st));
             PP_TRY(linear_dgrad(DY, w.out4, P + ad.w2, dZ1, w.hid4, nullptr, A1, w.hid4, n, ad.hid, ad.n_out, false, st,
                                 p.det ? nullptr : grads + ad.b1));   // db1 = colsum(dZ1) fused into the epilogue
@@ -946,6 +958,8 @@ static int lstm_backward_steps(const Step& s, int l, float* dH_cur) {
     const float* Whh = s.P + ly.w_hh;
     float* db_ih = p.det ? nullptr : s.grads + ly.b_ih;
     float* db_hh = p.det ? nullptr : s.grads + ly.b_hh;
+    if (db_ih) grads_touch(db_ih);
+    if (db_hh) grads_touch(db_hh);
     // the top layer's first cell launch folds the loss slots (the tail launch when there is one)
     LossFinalize fin = p.fin;
     if (l != p.L - 1) fin.acc = nullptr;
@@ -1063,6 +1077,7 @@ static int input_backward(const Step& s, GradQueue& q) {
             }
         }
     }
+    if (T > 1) grads_touch_all(grads);   // (the sample-embedding scatter writes the layers of every previous address)
     if (T > 1 && p.det)
         PP_TRY(sample_embed_bwd_det(net, P, bt->value, bt->prev_row, bt->nxt_rows, bt->nxt_off, w.dX, w.i4, grads, st));
     else if (T > 1)
@@ -1120,6 +1135,23 @@ static int reduce_and_flush(const Step& s, GradQueue& q) {
     const pp_net* net = s.net; const StepPlan& p = s.p;
     const bool ride = step_env().aux_colsum;
     AuxJobs aux{};
+    // the tensors these leaves write may be non-zero from now on (adam_live.hpp; group sums into the workspace mark nothing)
+    for (const auto& g : q.wq) grads_touch(g.C);
+    for (const auto& j : q.cs) {
+        grads_touch(j.out);
+        if (j.out2) grads_touch(j.out2);
+    }
+    if (p.compact) {   // the jobs derived from the group sums: the table columns of dW_ih, every address's tables, the biases
+        grads_touch(s.grads + net->w_ih);
+        for (int a = 0; a < net->n_addr; ++a) {
+            grads_touch(s.grads + net->addrs[a].addr_emb);
+            grads_touch(s.grads + net->addrs[a].dtype_emb);
+        }
+        if (p.fused_bwd) {
+            grads_touch(s.grads + net->b_ih);
+            grads_touch(s.grads + net->b_hh);
+        }
+    }
     if (!p.compact) {
         // FeedForward network: no column sum depends on another launch's group sums, so they all ride behind the
         // weight-gradient tiles (and the loss is finalised there): one launch less per step
@@ -1192,6 +1224,7 @@ static int obs_backward_generic(const Step& s, GradQueue& q) {
     const int B = p.B, e = net->e_obs;
     int64_t ldxs;
     const float* dXs = obs_grad_rows(s, &ldxs);
+    grads_touch_all(grads);   // (layer by layer below, the convolution stack included: no leaf list to mark from)
     PP_TRY(obs_grad(dXs, ldxs, bt->row_off_dev, p.T, B, e, w.E, w.e4, w.dE, w.e4, st));   // dE, ReLU mask applied
     PP_TRY(reduce_and_flush(s, q));
     PP_TRY(linear_wgrad(w.dE, w.e4, w.f1, w.e4, nullptr, grads + net->fin_w1, grads + net->fin_b1, nullptr, B, e, e, st));
@@ -1329,6 +1362,9 @@ int pp_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
                  const int32_t* skip, void* stream) {
     // kernel class 3 of the in-stream timing: the optimizer pass over the flat buffers (HBM bound): reads of params, grads
     // and both moments, writes of params, both moments and the cleared gradients - 8 x 4 bytes per (padded) parameter
+    // (the caller filled `grads` by means this library does not see, and the call moves the moments of whatever is non-zero:
+    // for the live-chunk launch of the training paths every tensor of a bound buffer is touched from here on)
+    pp::grads_touch_all(grads);
     pp::prof_begin(3, pp::as_stream(stream));
     const int rc = pp::adam_step(params, grads, exp_avg, exp_avg_sq, n_params, chunk_tensor, active, tensor_step, arrived,
                                  n_tensors, lr, beta1, beta2, eps, weight_decay, grad_scale, flags, skip, pp::as_stream(stream));
@@ -1336,8 +1372,71 @@ int pp_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq,
     return rc;
 }
 
+int pp_adam_step_live(float* params, float* grads, float* exp_avg, float* exp_avg_sq, int64_t n_params,
+                      const int32_t* chunk_tensor, const float* active, int32_t* tensor_step, int32_t* arrived, int32_t n_tensors,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, int32_t flags,
+                      const int32_t* skip, void* stream) {
+    pp::prof_begin(3, pp::as_stream(stream));
+    const int rc = pp::adam_step_live(params, grads, exp_avg, exp_avg_sq, n_params, chunk_tensor, active, tensor_step, arrived,
+                                      n_tensors, lr, beta1, beta2, eps, weight_decay, grad_scale, flags, skip,
+                                      pp::as_stream(stream));
+    pp::prof_end(3, ((flags & PP_ADAM_ZERO_GRADS) ? 32.0 : 28.0) * (double)n_params, pp::as_stream(stream));
+    return rc;
+}
+
+int pp_adam_live_bind(const float* grads, const float* exp_avg, const float* exp_avg_sq, int64_t n_params,
+                      const int32_t* tensor_first, int32_t n_tensors, int32_t clean) {
+    return pp::adam_live_bind(grads, exp_avg, exp_avg_sq, n_params, tensor_first, n_tensors, clean != 0);
+}
+
+int pp_adam_live_unbind(const float* grads) {
+    pp::adam_live_unbind(grads);
+    return 0;
+}
+
+int pp_adam_live_mark_touched(const void* buffer) {
+    pp::grads_touch_all(buffer);
+    return 0;
+}
+
+int pp_adam_live_mark_range(const float* grads, int64_t offset, int64_t count) {
+    pp::grads_touch_range(grads, offset, count);
+    return 0;
+}
+
+int pp_adam_live_info(const float* grads, int64_t* out, uint8_t* touched_out) {
+    if (!out) return PP_EINVAL;
+    return pp::adam_live_info(grads, out, touched_out);
+}
+
+static void adam_table_words(const pp::AdamLiveTable& tab, int32_t* out) {
+    int k = 0;
+    out[k++] = tab.n_runs; out[k++] = tab.live_blocks; out[k++] = tab.n_gaps;
+    for (int r = 0; r < pp::ADAM_LIVE_MAX_RUNS; ++r) { out[k++] = tab.run_blk[r]; out[k++] = tab.run_chunk[r]; }
+    for (int g = 0; g <= pp::ADAM_LIVE_MAX_RUNS; ++g) { out[k++] = tab.gap_t0[g]; out[k++] = tab.gap_t1[g]; }
+}
+
+int pp_adam_live_plan(const int32_t* tensor_first, int32_t n_tensors, const uint8_t* live, int32_t* out) {
+    if (!(tensor_first && live && out) || n_tensors <= 0) return PP_EINVAL;
+    pp::AdamLiveTable tab;
+    if (!pp::adam_live_plan(tensor_first, n_tensors, live, tab)) return 1;
+    adam_table_words(tab, out);
+    return 0;
+}
+
+int pp_adam_live_table(const float* grads, const float* exp_avg, const float* exp_avg_sq, int64_t n_params, int32_t n_tensors,
+                       float weight_decay, int32_t* out) {
+    if (!out) return PP_EINVAL;
+    pp::AdamLiveTable tab;
+    if (!pp::adam_live_table(grads, exp_avg, exp_avg_sq, n_params, n_tensors, weight_decay != 0.0f, tab)) return 1;
+    adam_table_words(tab, out);
+    return 0;
+}
+
 int pp_colsum_f32(const float* X, int64_t ldx, const int32_t* row_idx, int32_t n_rows, int32_t n_cols, float* out,
                   float* out2, void* stream) {
+    pp::grads_touch_all(out);
+    pp::grads_touch_all(out2);
     return pp::colsum_f32(X, ldx, row_idx, n_rows, n_cols, out, out2, pp::as_stream(stream));
 }
 

@@ -1887,7 +1887,12 @@ extern "C" int pp_debug_wgtrace(long long* buf, int32_t cap, int32_t mode) {
     return 0;
 }
 
-extern "C" int pp_gemm_f32(const pp_gemm_args* args, void* stream) { return pp::gemm_f32(args, pp::as_stream(stream), nullptr, nullptr); }
+// (a product written into a bound gradient or moment buffer from outside the backward pass: adam_live.hpp)
+extern "C" int pp_gemm_f32(const pp_gemm_args* args, void* stream) {
+    if (args) pp::grads_touch_all(args->C);
+    return pp::gemm_f32(args, pp::as_stream(stream), nullptr, nullptr);
+}
 extern "C" int pp_gemm_f32_grouped(const pp_gemm_args* args, int32_t count, void* stream) {
+    for (int i = 0; args && i < count; ++i) pp::grads_touch_all(args[i].C);
     return pp::gemm_f32_grouped(args, count, pp::as_stream(stream), nullptr, nullptr, nullptr);
 }

@@ -1669,6 +1669,7 @@ int pp_partition_rows_polled(const uint8_t* cond, const int64_t* rows, int32_t m
 int pp_axpy(float scale, const float* term, float* lw, int32_t n, void* stream) {
     if (!(term && lw)) return PP_EINVAL;
     if (n <= 0) return 0;
+    pp::grads_touch_all(lw);   // (adam_live.hpp: the destination may be a bound gradient or moment buffer)
     hipLaunchKernelGGL(pp::axpy_kernel, dim3(pp::cdiv(n, 256)), dim3(256), 0, pp::as_stream(stream), scale, term, lw, n);
     PP_LAUNCH_CHECK("pp_axpy");
     return 0;

@@ -5,12 +5,14 @@
 #include "gather.hpp"
 #include "head_math.hpp"
 #include "aux_jobs.hpp"
+#include "adam_live.hpp"
 
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 namespace pp {
@@ -1142,15 +1144,84 @@ constexpr int ADAM_TOP = 1024, ADAM_FIRST = 1025, ADAM_CHUNKS = 1026;   // after
 // 1/8 of their Adam traffic this way. The host sets the flag when it writes moments itself (checkpoint load).
 constexpr int ADAM_SEEN = 1027;
 
+// debug (pp_debug_wgtrace, mode 3; tools/adam_wg_trace.py): per workgroup eight wall-clock words (10 ns ticks) -
+// 0 start, 1 tensor known, 2 gradient arrived, 3 p / m / v arrived, 4 corrections ready, 5 stores issued, 6 end, 7 tensor id.
+// An "arrived" stamp waits for the loads issued so far; `lane0` names the stamping thread.
+#define ADAM_STAMP(k, lane0) do { if (tr && threadIdx.x == (lane0)) { __builtin_amdgcn_sched_barrier(0); tr[k] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#define ADAM_STAMP_ARRIVED(k, lane0) do { if (tr) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); ADAM_STAMP(k, lane0); } } while (0)
+
+// bias corrections of step `step` (thread 0, double precision like torch.optim.Adam's Python floats)
+__device__ __forceinline__ void adam_corrections(int step, float lr, float beta1, float beta2, float* corr) {
+    // beta^step by repeated squaring (integer exponent): ~40 double multiplies instead of two generic pow() calls,
+    // which cost ~6 us on the single active lane every workgroup waits for
+    double p1 = 1.0, p2 = 1.0, q1 = (double)beta1, q2 = (double)beta2;
+    for (int e = step; e > 0; e >>= 1) {
+        if (e & 1) { p1 *= q1; p2 *= q2; }
+        q1 *= q1;
+        q2 *= q2;
+    }
+    const double bc1 = 1.0 - p1, bc2 = 1.0 - p2;
+    corr[0] = (float)((double)lr / bc1);
+    corr[1] = (float)(1.0 / sqrt(bc2));
+}
+
+// the update of one thread's four parameters and its stores (wt: write-through, common.hpp store16_wt)
+__device__ __forceinline__ void adam_update_store(float* __restrict__ P, float* __restrict__ Gr, float* __restrict__ M,
+                                                  float* __restrict__ V, int64_t o, uint32_t buf_bytes, uint32_t wo, f32x4 g0,
+                                                  f32x4 p, f32x4 m, f32x4 v, float step_size, float inv_sqrt_bc2, float beta1,
+                                                  float beta2, float eps, float wd, float gscale, int zero_grads, int wt) {
+    const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float g = g0[e] * gscale;
+        if (wd != 0.0f) g += wd * p[e];
+        m[e] = beta1 * m[e] + (1.0f - beta1) * g;
+        v[e] = beta2 * v[e] + (1.0f - beta2) * g * g;
+        const float denom = sqrtf(v[e]) * inv_sqrt_bc2 + eps;
+        p[e] -= step_size * (m[e] / denom);
+    }
+    if (wt) {
+        store16_wt(P, buf_bytes, wo, p);
+        store16_wt(M, buf_bytes, wo, m);
+        store16_wt(V, buf_bytes, wo, v);
+        if (zero_grads) store16_wt(Gr, buf_bytes, wo, zero4);
+    } else {
+        *reinterpret_cast<f32x4*>(P + o) = p;
+        *reinterpret_cast<f32x4*>(M + o) = m;
+        *reinterpret_cast<f32x4*>(V + o) = v;
+        if (zero_grads) *reinterpret_cast<f32x4*>(Gr + o) = zero4;
+    }
+}
+
+// the chunk run [first, first + chunks) of tensor t in the ascending chunk -> tensor map; `b` is any chunk of the tensor
+__device__ __forceinline__ void adam_find_run(const int32_t* __restrict__ chunk_tensor, int n_chunks, int t, int b, int& first,
+                                              int& chunks) {
+    int lo = 0, hi = b;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (chunk_tensor[mid] < t) lo = mid + 1; else hi = mid;
+    }
+    int lo2 = b, hi2 = n_chunks;
+    while (lo2 < hi2) {
+        const int mid = (lo2 + hi2) >> 1;
+        if (chunk_tensor[mid] <= t) lo2 = mid + 1; else hi2 = mid;
+    }
+    first = lo;
+    chunks = lo2 - lo;
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float* __restrict__ Gr, float* __restrict__ M,
                                                    float* __restrict__ V, const int32_t* __restrict__ chunk_tensor,
                                                    int n_chunks, const float* __restrict__ active,
                                                    int32_t* __restrict__ tensor_step, int32_t* __restrict__ scratch, float lr,
                                                    float beta1, float beta2, float eps, float wd, float gscale,
-                                                   int zero_grads, const int32_t* __restrict__ skip, int wt) {
+                                                   int zero_grads, const int32_t* __restrict__ skip, int wt,
+                                                   long long* __restrict__ trace) {
     // wt (PP_STORE_WT): the chunk's results are stored write-through (common.hpp store16_wt) - the next launch reads them
     // from all eight XCDs, nothing of this kernel reads them again
     __shared__ float s_corr[2];
+    long long* const tr = trace ? trace + 8 * (int64_t)blockIdx.x : nullptr;
+    ADAM_STAMP(0, 0);
     const uint32_t buf_bytes = (uint32_t)n_chunks * 4096u, wo = ((uint32_t)blockIdx.x * 1024u + threadIdx.x * 4u) * 4u;
     const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
     const int b = blockIdx.x;
@@ -1158,6 +1229,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
     // optimizer step); checked on the device so that the host does not have to synchronise every iteration
     const bool skipped = skip && skip[0] != 0;
     const int t = chunk_tensor[b];
+    if (tr) {
+        asm volatile("" ::"s"(t));
+        ADAM_STAMP(1, 0);
+    }
     if (t < 0 || !(active[t] > 0.0f)) return;   // workgroup-uniform; every chunk of a tensor takes the same branch
     if (skipped) {   // no update, no step count; the (non-finite) gradients are still cleared for the next step
         if (zero_grads) {
@@ -1185,6 +1260,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
     } else if (!seen && threadIdx.x == 0) {
         __atomic_store_n(sc + ADAM_SEEN, 1, __ATOMIC_RELAXED);
     }
+    ADAM_STAMP_ARRIVED(2, 0);
     f32x4 p = f32x4{0.f, 0.f, 0.f, 0.f}, m = p, v = p;
     if (!idle) {
         p = *reinterpret_cast<f32x4*>(P + o);
@@ -1195,37 +1271,15 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
     if (threadIdx.x == 0) {
         first = __atomic_load_n(sc + ADAM_FIRST, __ATOMIC_RELAXED) - 1;
         chunks = __atomic_load_n(sc + ADAM_CHUNKS, __ATOMIC_RELAXED);
-        if (first < 0) {
-            // chunks of one tensor are contiguous and the ids ascend: two binary searches (~20 dependent loads), done by
-            // every workgroup of the FIRST call only; the last one to arrive caches the run
-            int lo = 0, hi = b;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (chunk_tensor[mid] < t) lo = mid + 1; else hi = mid;
-            }
-            int lo2 = b, hi2 = n_chunks;
-            while (lo2 < hi2) {
-                const int mid = (lo2 + hi2) >> 1;
-                if (chunk_tensor[mid] <= t) lo2 = mid + 1; else hi2 = mid;
-            }
-            first = lo;
-            chunks = lo2 - lo;
-        }
+        // chunks of one tensor are contiguous and the ids ascend: two binary searches (~20 dependent loads), done by
+        // every workgroup of the FIRST call only; the last one to arrive caches the run
+        if (first < 0) adam_find_run(chunk_tensor, n_chunks, t, b, first, chunks);
         step_old = __atomic_load_n(tensor_step + t, __ATOMIC_RELAXED);
-        const int step = step_old + 1;
-        // beta^step by repeated squaring (integer exponent): ~40 double multiplies instead of two generic pow() calls,
-        // which cost ~6 us on the single active lane every workgroup waits for
-        double p1 = 1.0, p2 = 1.0, q1 = (double)beta1, q2 = (double)beta2;
-        for (int e = step; e > 0; e >>= 1) {
-            if (e & 1) { p1 *= q1; p2 *= q2; }
-            q1 *= q1;
-            q2 *= q2;
-        }
-        const double bc1 = 1.0 - p1, bc2 = 1.0 - p2;
-        s_corr[0] = (float)((double)lr / bc1);
-        s_corr[1] = (float)(1.0 / sqrt(bc2));
+        adam_corrections(step_old + 1, lr, beta1, beta2, s_corr);
     }
+    ADAM_STAMP_ARRIVED(3, 64);   // (the second wave: thread 0's wave walks the chain above first)
     __syncthreads();
+    ADAM_STAMP(4, 0);
     const float step_size = s_corr[0], inv_sqrt_bc2 = s_corr[1];
     // Arrival is signalled NOW (every workgroup has read the old step count by the time it gets here) and the returned
     // ticket is only looked at after the update below, so the atomic's round trip overlaps the chunk's arithmetic and
@@ -1235,28 +1289,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
     const int quota = (chunks - k + 31) >> 5;               // chunks of the tensor that share it
     int ticket = -1;
     if (threadIdx.x == 0) ticket = atomicAdd(sc + 32 * k, 1);
-    if (!idle) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float g = g0[e] * gscale;
-            if (wd != 0.0f) g += wd * p[e];
-            m[e] = beta1 * m[e] + (1.0f - beta1) * g;
-            v[e] = beta2 * v[e] + (1.0f - beta2) * g * g;
-            const float denom = sqrtf(v[e]) * inv_sqrt_bc2 + eps;
-            p[e] -= step_size * (m[e] / denom);
-        }
-        if (wt) {
-            store16_wt(P, buf_bytes, wo, p);
-            store16_wt(M, buf_bytes, wo, m);
-            store16_wt(V, buf_bytes, wo, v);
-            if (zero_grads) store16_wt(Gr, buf_bytes, wo, zero4);
-        } else {
-            *reinterpret_cast<f32x4*>(P + o) = p;
-            *reinterpret_cast<f32x4*>(M + o) = m;
-            *reinterpret_cast<f32x4*>(V + o) = v;
-            if (zero_grads) *reinterpret_cast<f32x4*>(Gr + o) = zero4;
-        }
-    }
+    if (!idle)
+        adam_update_store(P, Gr, M, V, o, buf_bytes, wo, g0, p, m, v, step_size, inv_sqrt_bc2, beta1, beta2, eps, wd, gscale,
+                          zero_grads, wt);
+    ADAM_STAMP(5, 0);
     if (threadIdx.x == 0 && ticket == quota - 1) {
         __atomic_store_n(sc + 32 * k, 0, __ATOMIC_RELAXED);
         if (atomicAdd(sc + ADAM_TOP, 1) == min(chunks, 32) - 1) {   // last chunk of the tensor
@@ -1266,6 +1302,140 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ P, float*
             __atomic_store_n(tensor_step + t, step_old + 1, __ATOMIC_RELAXED);
         }
     }
+    if (tr && threadIdx.x == 0) {
+        tr[7] = t;
+        ADAM_STAMP(6, 0);
+    }
+}
+
+// The live-chunk launch of the training paths (adam_live.hpp): workgroup -> chunk is scalar arithmetic on the run table in the
+// kernel arguments, and everything that depends on the chunk index alone - the gradient, the parameters, both moments, the
+// chunk's tensor, the skip flag - is loaded at entry, in one memory trip instead of the four dependent ones of adam_kernel
+// (tensor, presence flag, gradient + ADAM_SEEN, then p / m / v); the presence flag, the step count and the cached run follow
+// together once the tensor is known. There is no ADAM_SEEN shortcut here: a live chunk whose gradient and moments are zero computes p - step_size * (0 / (0 + eps)) = p and m = v = 0, the
+// bits the shortcut leaves. The last workgroup of a tensor SETS the flag, so adam_kernel may run on the same state later.
+// The launch's last workgroup steps the tensors outside the runs, one thread each: no workgroup reads or writes their
+// counters, so they need no arrival counting.
+__global__ __launch_bounds__(256) void live_adam_kernel(float* __restrict__ P, float* __restrict__ Gr, float* __restrict__ M,
+                                                        float* __restrict__ V, const int32_t* __restrict__ chunk_tensor,
+                                                        int n_chunks, const float* __restrict__ active,
+                                                        int32_t* __restrict__ tensor_step, int32_t* __restrict__ scratch,
+                                                        float lr, float beta1, float beta2, float eps, float wd, float gscale,
+                                                        int zero_grads, const int32_t* __restrict__ skip, int wt,
+                                                        const AdamLiveTable tab, long long* __restrict__ trace) {
+    __shared__ float s_corr[2];
+    long long* const tr = trace ? trace + 8 * (int64_t)blockIdx.x : nullptr;
+    ADAM_STAMP(0, 0);
+    const int bid = blockIdx.x;
+    // workgroup -> chunk: selects, not branches, so that the table's words are loaded together (a branch per run made each
+    // run's words a scalar load of its own, one after the other: 0.5 us before the chunk was known)
+    int b = tab.run_chunk[0] + bid;
+#pragma unroll
+    for (int r = 1; r < ADAM_LIVE_MAX_RUNS; ++r) {
+        const bool in = (r < tab.n_runs) & (bid >= tab.run_blk[r]);
+        b = in ? tab.run_chunk[r] + (bid - tab.run_blk[r]) : b;
+    }
+    if (bid >= tab.live_blocks) {   // the tensors between the runs: their step counts (and run caches, as adam_kernel leaves them)
+        if (skip && skip[0] != 0) return;
+        for (int g = 0; g < tab.n_gaps; ++g) {
+            int t0 = tab.gap_t0[0], t1 = tab.gap_t1[0];
+#pragma unroll
+            for (int i = 1; i <= ADAM_LIVE_MAX_RUNS; ++i)
+                if (g == i) {
+                    t0 = tab.gap_t0[i];
+                    t1 = tab.gap_t1[i];
+                }
+            for (int t = t0 + (int)threadIdx.x; t < t1; t += 256) {
+                if (!(active[t] > 0.0f)) continue;
+                int32_t* const sc = scratch + (int64_t)t * PP_ADAM_SCRATCH;
+                int first = sc[ADAM_FIRST] - 1, chunks = sc[ADAM_CHUNKS];
+                if (first < 0) {   // (first call: any chunk of the tensor starts the search - find one)
+                    int lo = 0, hi = n_chunks;
+                    while (lo < hi) {
+                        const int mid = (lo + hi) >> 1;
+                        if (chunk_tensor[mid] < t) lo = mid + 1; else hi = mid;
+                    }
+                    if (lo >= n_chunks || chunk_tensor[lo] != t) continue;   // no chunk: adam_kernel never steps it either
+                    adam_find_run(chunk_tensor, n_chunks, t, lo, first, chunks);
+                }
+                sc[ADAM_FIRST] = first + 1;
+                sc[ADAM_CHUNKS] = chunks;
+                tensor_step[t] = tensor_step[t] + 1;
+            }
+        }
+        return;
+    }
+    const uint32_t buf_bytes = (uint32_t)n_chunks * 4096u, wo = ((uint32_t)b * 1024u + threadIdx.x * 4u) * 4u;
+    const int64_t o = (int64_t)b * 1024 + threadIdx.x * 4;
+    int first = -1, chunks = 0;
+    const int t = chunk_tensor[b];
+    const f32x4 g0 = *reinterpret_cast<const f32x4*>(Gr + o);
+    const f32x4 p = *reinterpret_cast<const f32x4*>(P + o);
+    const f32x4 m = *reinterpret_cast<const f32x4*>(M + o);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(V + o);
+    // (read through a pointer that is always valid: no branch around the load, so it travels with the tensor lookup)
+    const int32_t skip_word = (skip ? skip : chunk_tensor)[0];
+    const bool skipped = skip && skip_word != 0;
+    if (tr) {
+        asm volatile("" ::"s"(t));
+        ADAM_STAMP(1, 0);
+    }
+    if (t < 0) return;
+    int32_t* const sc = scratch + (int64_t)t * PP_ADAM_SCRATCH;
+    const float act = active[t];
+    int step_old = 0;
+    if (threadIdx.x == 0) {
+        step_old = __atomic_load_n(tensor_step + t, __ATOMIC_RELAXED);
+        first = __atomic_load_n(sc + ADAM_FIRST, __ATOMIC_RELAXED) - 1;
+        chunks = __atomic_load_n(sc + ADAM_CHUNKS, __ATOMIC_RELAXED);
+    }
+    if (!(act > 0.0f)) return;   // workgroup-uniform; the early loads are dropped
+    if (skipped) {   // no update, no step count; the (non-finite) gradients are still cleared for the next step
+        if (zero_grads) {
+            const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (wt) store16_wt(Gr, buf_bytes, wo, zero4);
+            else *reinterpret_cast<f32x4*>(Gr + o) = zero4;
+        }
+        return;
+    }
+    if (threadIdx.x == 0) {
+        if (first < 0) adam_find_run(chunk_tensor, n_chunks, t, b, first, chunks);   // (first call only, as in adam_kernel)
+        adam_corrections(step_old + 1, lr, beta1, beta2, s_corr);
+    }
+    ADAM_STAMP_ARRIVED(2, 64);   // (gradient and p / m / v travel together here: one stamp for both)
+    ADAM_STAMP(3, 64);
+    __syncthreads();
+    ADAM_STAMP(4, 0);
+    const float step_size = s_corr[0], inv_sqrt_bc2 = s_corr[1];
+    // arrival tickets as in adam_kernel: signalled now, looked at after the update
+    const int k = (b - first) & 31;
+    const int quota = (chunks - k + 31) >> 5;
+    int ticket = -1;
+    if (threadIdx.x == 0) ticket = atomicAdd(sc + 32 * k, 1);
+    adam_update_store(P, Gr, M, V, o, buf_bytes, wo, g0, p, m, v, step_size, inv_sqrt_bc2, beta1, beta2, eps, wd, gscale,
+                      zero_grads, wt);
+    ADAM_STAMP(5, 0);
+    if (threadIdx.x == 0 && ticket == quota - 1) {
+        __atomic_store_n(sc + 32 * k, 0, __ATOMIC_RELAXED);
+        if (atomicAdd(sc + ADAM_TOP, 1) == min(chunks, 32) - 1) {   // last chunk of the tensor
+            __atomic_store_n(sc + ADAM_TOP, 0, __ATOMIC_RELAXED);
+            __atomic_store_n(sc + ADAM_FIRST, first + 1, __ATOMIC_RELAXED);
+            __atomic_store_n(sc + ADAM_CHUNKS, chunks, __ATOMIC_RELAXED);
+            __atomic_store_n(sc + ADAM_SEEN, 1, __ATOMIC_RELAXED);
+            __atomic_store_n(tensor_step + t, step_old + 1, __ATOMIC_RELAXED);
+        }
+    }
+    if (tr && threadIdx.x == 0) {
+        tr[7] = t;
+        ADAM_STAMP(6, 0);
+    }
+}
+
+extern long long* g_wgtrace;   // gemm_f32.hip (pp_debug_wgtrace; mode 3: the Adam launch)
+extern int g_wgtrace_cap, g_wgtrace_mode;
+
+static long long* adam_trace(int blocks) {
+    return g_wgtrace && g_wgtrace_mode == 3 && blocks <= g_wgtrace_cap ? g_wgtrace : nullptr;
 }
 
 int adam_step(float* params, float* grads, float* m, float* v, int64_t n_params, const int32_t* chunk_tensor,
@@ -1278,8 +1448,131 @@ int adam_step(float* params, float* grads, float* m, float* v, int64_t n_params,
     // (the write-through stores address the buffers with 32-bit byte offsets)
     const int wt = store_wt_mode() && n_params < ((int64_t)1 << 30) ? 1 : 0;
     hipLaunchKernelGGL(adam_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, params, grads, m, v, chunk_tensor, n_chunks,
-                       active, tensor_step, scratch, lr, beta1, beta2, eps, wd, gscale, (flags & PP_ADAM_ZERO_GRADS) ? 1 : 0, skip, wt);
+                       active, tensor_step, scratch, lr, beta1, beta2, eps, wd, gscale, (flags & PP_ADAM_ZERO_GRADS) ? 1 : 0, skip, wt,
+                       adam_trace(n_chunks));
     PP_LAUNCH_CHECK("pp_adam_step");
+    return 0;
+}
+
+// ---- the gradient buffers' marks (adam_live.hpp) -------------------------------------------------------------------------
+static std::mutex g_track_mutex;
+static std::vector<GradTrack> g_tracks;
+
+// PP_ADAM_LIVE (read per call): 0 = every path launches the full grid (adam_kernel); default 1 = the live chunks
+static int adam_live_mode() {
+    const char* e = getenv("PP_ADAM_LIVE");
+    return e ? (atoi(e) != 0) : 1;
+}
+
+static GradTrack* track_of(const void* ptr) {   // the record whose gradient buffer holds ptr (g_track_mutex held)
+    const float* f = static_cast<const float*>(ptr);
+    for (auto& tr : g_tracks)
+        if (f >= tr.grads && f < tr.grads + tr.n_params) return &tr;
+    return nullptr;
+}
+
+// Binds (or re-binds) a gradient buffer: first[t] = first chunk of tensor t, first[n_tensors] = n_params / 1024. `clean`: the
+// caller has just zero-filled the gradient and both moment buffers, so no tensor is touched; otherwise all of them are.
+int adam_live_bind(const float* grads, const float* m, const float* v, int64_t n_params, const int32_t* first, int n_tensors,
+                   bool clean) {
+    PP_CHECK_ARG(grads && m && v && first && n_tensors > 0 && n_params > 0 && n_params % 1024 == 0, "pp_adam_live_bind: bad argument");
+    PP_CHECK_ARG(first[0] == 0 && first[n_tensors] == n_params / 1024, "pp_adam_live_bind: the boundaries do not span the buffer");
+    for (int t = 0; t < n_tensors; ++t) PP_CHECK_ARG(first[t] <= first[t + 1], "pp_adam_live_bind: the boundaries must ascend");
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    // (a record whose buffers overlap the new ones describes memory that was freed since)
+    for (size_t i = 0; i < g_tracks.size();) {
+        const GradTrack& o = g_tracks[i];
+        if (grads < o.grads + o.n_params && o.grads < grads + n_params) g_tracks.erase(g_tracks.begin() + i); else ++i;
+    }
+    GradTrack tr;
+    tr.grads = grads; tr.m = m; tr.v = v; tr.n_params = n_params; tr.n_tensors = n_tensors;
+    tr.first.assign(first, first + n_tensors + 1);
+    tr.touched.assign(n_tensors, clean ? 0 : 1);
+    g_tracks.push_back(std::move(tr));
+    return 0;
+}
+
+void adam_live_unbind(const float* grads) {
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    for (size_t i = 0; i < g_tracks.size();)
+        if (g_tracks[i].grads == grads) g_tracks.erase(g_tracks.begin() + i); else ++i;
+}
+
+// out[0] = bound, [1] = version, [2] = tables built, [3] = untouched tensors; touched_out [n_tensors] (or NULL)
+int adam_live_info(const float* grads, int64_t* out, uint8_t* touched_out) {
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    GradTrack* tr = track_of(grads);
+    out[0] = tr ? 1 : 0; out[1] = out[2] = out[3] = 0;
+    if (!tr) return 0;
+    out[1] = (int64_t)tr->version; out[2] = (int64_t)tr->builds;
+    for (int t = 0; t < tr->n_tensors; ++t) {
+        out[3] += tr->touched[t] ? 0 : 1;
+        if (touched_out) touched_out[t] = tr->touched[t];
+    }
+    return 0;
+}
+
+void grads_touch(const float* ptr) {
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    if (GradTrack* tr = track_of(ptr)) tr->touch_offset(ptr - tr->grads);
+}
+
+void grads_touch_all(const void* ptr) {
+    if (!ptr) return;
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    const float* f = static_cast<const float*>(ptr);
+    for (auto& tr : g_tracks)
+        if ((f >= tr.grads && f < tr.grads + tr.n_params) || (f >= tr.m && f < tr.m + tr.n_params) ||
+            (f >= tr.v && f < tr.v + tr.n_params))
+            tr.touch_all();
+}
+
+void grads_touch_range(const float* grads, int64_t off, int64_t cnt) {
+    if (cnt <= 0) return;
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    GradTrack* tr = track_of(grads);
+    if (!tr) return;
+    off += grads - tr->grads;
+    for (int64_t c = std::max<int64_t>(off, 0) >> 10; c <= (std::min(off + cnt, tr->n_params) - 1) >> 10; ++c)
+        tr->touch_tensor(tr->tensor_of_chunk(c));
+}
+
+// The run table of this call (cached per state of the marks); false: not bound as passed, or more runs than the table holds
+bool adam_live_table(const float* grads, const float* m, const float* v, int64_t n_params, int n_tensors, bool wd_on,
+                     AdamLiveTable& tab) {
+    if (!grads) return false;
+    std::lock_guard<std::mutex> lock(g_track_mutex);
+    GradTrack* tr = track_of(grads);
+    if (!(tr && tr->grads == grads && tr->n_params == n_params && tr->n_tensors == n_tensors)) return false;
+    if (tr->m != m || tr->v != v) tr->touch_all();   // other moment buffers than the bound ones: nothing is known of them
+    if (wd_on) tr->touch_all();                      // weight decay moves every tensor's moments: none is zero afterwards
+    const AdamLiveTable* t = nullptr;
+    if (!tr->table(wd_on, &t)) return false;
+    tab = *t;
+    return true;
+}
+
+// Adam of the training paths: the live chunks of a bound gradient buffer (pp_adam_live_bind), else adam_step as it stands
+int adam_step_live(float* params, float* grads, float* m, float* v, int64_t n_params, const int32_t* chunk_tensor,
+                   const float* active, int32_t* tensor_step, int32_t* scratch, int n_tensors, float lr, float beta1, float beta2,
+                   float eps, float wd, float gscale, int flags, const int32_t* skip, hipStream_t st) {
+    const int mode = adam_live_mode();
+    AdamLiveTable tab{};
+    // (the write-through stores address the buffers with 32-bit byte offsets: larger buffers keep adam_step's choice)
+    const bool live = mode != 0 && n_params < ((int64_t)1 << 30) &&
+                      adam_live_table(grads, m, v, n_params, n_tensors, wd != 0.0f, tab);
+    if (!live)
+        return adam_step(params, grads, m, v, n_params, chunk_tensor, active, tensor_step, scratch, n_tensors, lr, beta1, beta2, eps,
+                         wd, gscale, flags, skip, st);
+    PP_CHECK_ARG(params && m && v && chunk_tensor && active && tensor_step && scratch, "pp_adam_step_live: null pointer");
+    const int n_chunks = (int)(n_params / 1024);
+    const int wt = store_wt_mode();
+    const int blocks = tab.live_blocks + (tab.n_gaps > 0 ? 1 : 0);
+    if (blocks == 0) return 0;
+    const int zg = (flags & PP_ADAM_ZERO_GRADS) ? 1 : 0;
+    hipLaunchKernelGGL(live_adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, params, grads, m, v, chunk_tensor, n_chunks,
+                       active, tensor_step, scratch, lr, beta1, beta2, eps, wd, gscale, zg, skip, wt, tab, adam_trace(blocks));
+    PP_LAUNCH_CHECK("pp_adam_step_live");
     return 0;
 }
 

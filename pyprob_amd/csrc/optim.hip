@@ -186,6 +186,8 @@ int pp_sgd_step(float* params, float* grads, float* momentum_buf, int64_t n_para
                 const float* active, int32_t n_tensors, float lr, float momentum, int32_t nesterov, float weight_decay,
                 float grad_scale, int32_t flags, const int32_t* skip, void* stream) {
     // kernel class 3 of the in-stream timing (the optimizer pass): params, grads, buffer read; params, buffer (, grads) written
+    pp::grads_touch_all(grads);   // (the momentum buffer is Adam's exp_avg: adam_live.hpp)
+    pp::grads_touch_all(momentum_buf);
     pp::prof_begin(3, pp::as_stream(stream));
     const int rc = pp::sgd_step(params, grads, momentum_buf, n_params, chunk_tensor, active, n_tensors, lr, momentum, nesterov,
                                 weight_decay, grad_scale, flags, skip, pp::as_stream(stream));
@@ -197,6 +199,7 @@ int pp_sgd_step(float* params, float* grads, float* momentum_buf, int64_t n_para
 int pp_larc_scale(const float* params, float* grads, int64_t n_params, const int32_t* chunk_tensor, const float* active,
                   int32_t n_tensors, float lr, float weight_decay, float grad_scale, float trust_coefficient, float eps,
                   float epsilon, int32_t clip, float* scratch, const int32_t* skip, void* stream) {
+    pp::grads_touch_all(grads);   // (weight decay is folded into the gradients: a zero gradient does not stay zero)
     return pp::larc_scale(params, grads, n_params, chunk_tensor, active, n_tensors, lr, weight_decay, grad_scale,
                           trust_coefficient, eps, epsilon, clip, scratch, skip, pp::as_stream(stream));
 }

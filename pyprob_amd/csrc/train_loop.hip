@@ -21,6 +21,9 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
 int adam_step(float* params, float* grads, float* m, float* v, int64_t n_params, const int32_t* chunk_tensor,
               const float* active, int32_t* tensor_step, int32_t* arrived, int n_tensors, float lr, float beta1, float beta2,
               float eps, float wd, float gscale, int flags, const int32_t* skip, hipStream_t st);
+int adam_step_live(float* params, float* grads, float* m, float* v, int64_t n_params, const int32_t* chunk_tensor,
+                   const float* active, int32_t* tensor_step, int32_t* arrived, int n_tensors, float lr, float beta1, float beta2,
+                   float eps, float wd, float gscale, int flags, const int32_t* skip, hipStream_t st);   // live chunks only (adam_live.hpp)
 int dp_world();
 int dp_reduce_grads(float* grads_full, int64_t n_params, int n_tensors, const float* presence, const int32_t* status,
                     const int64_t* skip_off, const int64_t* skip_cnt, int n_skip, float* loss_out, int32_t* status_out,
@@ -149,10 +152,10 @@ int pp_train_steps(const pp_net* net, const pp_train_buffers* tb, const pp_tenso
             }
             // Adam checks the step's non-finite flag itself (`skip`) and clears the gradients it consumed (the next
             // step's zero_grad, :486); data parallel: the merged presence map, the summed gradients / world
-            rc = pp::adam_step(tb->params, tb->grads, tb->exp_avg, tb->exp_avg_sq, net->n_params, tb->chunk_tensor,
-                               dp ? dp_tail : dev + pk[k].words, tb->tensor_step, tb->adam_scratch, n_tensors, lr[i], beta1, beta2,
-                               eps, weight_decay, dp ? 1.0f / (float)tb->dp_world : 1.0f, PP_ADAM_ZERO_GRADS,
-                               tb->status_ring + i, st);
+            rc = pp::adam_step_live(tb->params, tb->grads, tb->exp_avg, tb->exp_avg_sq, net->n_params, tb->chunk_tensor,
+                                    dp ? dp_tail : dev + pk[k].words, tb->tensor_step, tb->adam_scratch, n_tensors, lr[i], beta1,
+                                    beta2, eps, weight_decay, dp ? 1.0f / (float)tb->dp_world : 1.0f, PP_ADAM_ZERO_GRADS,
+                                    tb->status_ring + i, st);
         }
     }
     // Returns with the last groups still queued: the caller plans its next run meanwhile. The staging halves stay
@@ -198,9 +201,9 @@ int pp_train_resident(const pp_net* net, const pp_train_buffers* tb, const pp_ba
                                      tb->dp_skip_cnt, tb->dp_n_skip, tb->loss_ring + i, tb->status_ring + i, st);
             if (rc != 0) return rc;
         }
-        rc = pp::adam_step(tb->params, tb->grads, tb->exp_avg, tb->exp_avg_sq, net->n_params, tb->chunk_tensor,
-                           dp ? dp_tail : active[i], tb->tensor_step, tb->adam_scratch, n_tensors, lr[i], beta1, beta2, eps,
-                           weight_decay, dp ? 1.0f / (float)tb->dp_world : 1.0f, PP_ADAM_ZERO_GRADS, tb->status_ring + i, st);
+        rc = pp::adam_step_live(tb->params, tb->grads, tb->exp_avg, tb->exp_avg_sq, net->n_params, tb->chunk_tensor,
+                                dp ? dp_tail : active[i], tb->tensor_step, tb->adam_scratch, n_tensors, lr[i], beta1, beta2, eps,
+                                weight_decay, dp ? 1.0f / (float)tb->dp_world : 1.0f, PP_ADAM_ZERO_GRADS, tb->status_ring + i, st);
         if (rc != 0) return rc;
     }
     return 0;

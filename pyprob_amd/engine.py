@@ -72,7 +72,9 @@ class ICEngine:
         self.tensor_step = torch.zeros(spec.n_tensors, dtype=torch.int32, device=self.device)
         self.arrived = torch.zeros(L.PP_ADAM_SCRATCH * spec.n_tensors, dtype=torch.int32, device=self.device)   # pp_adam_step scratch
         self._grads_clean = False      # the last Adam step cleared the gradient buffer (zero_grad of the next step)
-        self.chunk_tensor = torch.from_numpy(spec.chunk_tensor_map()).to(self.device)
+        chunk_map = spec.chunk_tensor_map()
+        self.chunk_tensor = torch.from_numpy(chunk_map).to(self.device)
+        self._bind_live(chunk_map)
         self.addr_table = torch.from_numpy(spec.address_table()).to(self.device)
         self.net = spec.c_struct(self.addr_table.data_ptr())
         from . import ops
@@ -81,6 +83,42 @@ class ICEngine:
         self._active_cache = {}
         self._active_key = None
         self.ws_shape = (0, 0)
+
+    def _bind_live(self, chunk_map):
+        """Tell the library where the tensors of the (fresh, zero-filled) gradient and moment buffers begin: the training paths'
+        Adam launch covers the chunks of the tensors that were written since (pp_adam_step_live, include/pyprob_amd.h)."""
+        old = getattr(self, '_live_bound', None)
+        if old is not None:
+            self.lib.pp_adam_live_unbind(old)
+        self._live_bound = None
+        cm = np.asarray(chunk_map, np.int64)
+        nt = self.spec.n_tensors
+        if nt <= 0 or cm.size == 0 or cm[0] < 0 or np.any(np.diff(cm) < 0) or cm[-1] >= nt or cm.size * 1024 != self.spec.n_params:
+            return      # (not the ascending, padded layout: the full grid stays)
+        first = np.ascontiguousarray(np.searchsorted(cm, np.arange(nt + 1)), np.int32)
+        L.check(self.lib.pp_adam_live_bind(self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                                           self.spec.n_params, first.ctypes.data, nt, 1), 'pp_adam_live_bind')
+        self._live_bound = self.grads.data_ptr()
+
+    def __del__(self):
+        bound, lib = getattr(self, '_live_bound', None), getattr(self, 'lib', None)
+        if bound is not None and lib is not None:
+            try:
+                lib.pp_adam_live_unbind(bound)
+            except Exception:
+                pass
+
+    def mark_touched(self):
+        """The caller wrote the gradient or the moment buffers itself (torch operators, its own collective, a checkpoint):
+        every tensor counts as touched from now on, the training paths' Adam launch leaves none out."""
+        self.lib.pp_adam_live_mark_touched(self.grads.data_ptr())
+
+    def live_info(self):
+        """(bound, marks version, tables built, untouched tensors), touched[n_tensors] of pp_adam_live_info."""
+        out = np.zeros(4, np.int64)
+        touched = np.zeros(max(self.spec.n_tensors, 1), np.uint8)
+        self.lib.pp_adam_live_info(self.grads.data_ptr(), out.ctypes.data, touched.ctypes.data)
+        return tuple(int(x) for x in out), touched[:self.spec.n_tensors].astype(bool)
 
     def add_addresses(self, items):
         """items: iterable of (address, dist_name, num_categories). Returns True if layers were created."""
@@ -181,11 +219,13 @@ class ICEngine:
         binding's optimizers, data parallel)."""
         return self._presence if self._active_key is not None else self.active
 
-    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, zero_grads=False, skip=None, grad_scale=None):
+    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, zero_grads=False, skip=None, grad_scale=None,
+                  live=False):
         """optimizer.step() for optim.Adam (inference_network.py:348,496); grads are divided by world_size first
         when data-parallel (inference_network.py:324-325). zero_grads=True also performs the NEXT step's
         optimizer.zero_grad() (:486) in the same pass: the consumed gradient chunks are cleared, gradients of tensors
-        without a gradient this step are zero already."""
+        without a gradient this step are zero already. live=True (the training step): the launch covers the chunks of the
+        tensors that were written so far (pp_adam_step_live); a caller that filled `grads` itself keeps the default."""
         gs = 1.0 / self.world_size if grad_scale is None else grad_scale
         if getattr(self, '_use_ops', False):
             from .ops import ops
@@ -193,11 +233,12 @@ class ICEngine:
                           self.tensor_step, self.arrived, lr, beta1, beta2, eps, weight_decay, gs,
                           L.PP_ADAM_ZERO_GRADS if zero_grads else 0, skip)
         else:
-            rc = self.lib.pp_adam_step(self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
-                                       self.exp_avg_sq.data_ptr(), self.spec.n_params, self.chunk_tensor.data_ptr(),
-                                       self.presence().data_ptr(), self.tensor_step.data_ptr(), self.arrived.data_ptr(),
-                                       self.spec.n_tensors, lr, beta1, beta2, eps, weight_decay, gs,
-                                       L.PP_ADAM_ZERO_GRADS if zero_grads else 0, L.ptr(skip), L.stream_ptr())
+            step = self.lib.pp_adam_step_live if live else self.lib.pp_adam_step
+            rc = step(self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(),
+                      self.exp_avg_sq.data_ptr(), self.spec.n_params, self.chunk_tensor.data_ptr(),
+                      self.presence().data_ptr(), self.tensor_step.data_ptr(), self.arrived.data_ptr(),
+                      self.spec.n_tensors, lr, beta1, beta2, eps, weight_decay, gs,
+                      L.PP_ADAM_ZERO_GRADS if zero_grads else 0, L.ptr(skip), L.stream_ptr())
             L.check(rc, 'pp_adam_step')
         self._grads_clean = bool(zero_grads)
 
@@ -246,7 +287,7 @@ class ICEngine:
                                         self._larc_scratch.data_ptr(), L.ptr(skip), L.stream_ptr())
             L.check(rc, 'pp_larc_scale')
 
-    def optimizer_step(self, lr, weight_decay=0.0, zero_grads=False, skip=None):
+    def optimizer_step(self, lr, weight_decay=0.0, zero_grads=False, skip=None, live=False):
         """optimizer.step() of the optimizer chosen with set_optimizer (inference_network.py:496)."""
         opt = self.optimizer
         scale = None
@@ -256,9 +297,9 @@ class ICEngine:
         if opt['kind'] == 'sgd':
             self.sgd_step(lr, opt['momentum'], True, weight_decay, zero_grads, skip, grad_scale=scale)
         elif scale is None:
-            self.adam_step(lr, weight_decay=weight_decay, zero_grads=zero_grads, skip=skip)
+            self.adam_step(lr, weight_decay=weight_decay, zero_grads=zero_grads, skip=skip, live=live)
         else:
-            self.adam_step(lr, weight_decay=0.0, zero_grads=zero_grads, skip=skip, grad_scale=1.0)
+            self.adam_step(lr, weight_decay=0.0, zero_grads=zero_grads, skip=skip, grad_scale=1.0, live=live)
 
     def _adam_only(self, what):
         if self.optimizer['kind'] != 'adam' or self.optimizer['larc']:
@@ -270,9 +311,9 @@ class ICEngine:
         loss = self.loss(batch, backward=True)
         if self.world_size > 1 or self.force_allreduce:
             self.allreduce_grads()
-            self.optimizer_step(lr, weight_decay=weight_decay, zero_grads=_ADAM_CLEARS, skip=self.reduced_status())
+            self.optimizer_step(lr, weight_decay=weight_decay, zero_grads=_ADAM_CLEARS, skip=self.reduced_status(), live=True)
         else:
-            self.optimizer_step(lr, weight_decay=weight_decay, zero_grads=_ADAM_CLEARS, skip=self.status_buf)
+            self.optimizer_step(lr, weight_decay=weight_decay, zero_grads=_ADAM_CLEARS, skip=self.status_buf, live=True)
         return loss
 
     def train_run(self, dataset, id_lists, lrs, weight_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
@@ -470,6 +511,7 @@ class ICEngine:
                     'pp_dp_reduce_grads')
             return
         from .parallel import allreduce_flat_
+        self.mark_touched()          # (torch's collective writes the gradients: another rank's may be non-zero where ours are not)
         self.status_tail.copy_(self.status_buf[:1])          # int32 flag -> float, into the reduced tail
         if self.dp_overlap:
             # the bucketed order of enable_dp_overlap on torch.distributed: the early ranges go out first as asynchronous
@@ -583,3 +625,4 @@ class ICEngine:
         """The caller filled exp_avg / exp_avg_sq itself (checkpoint load): pp_adam_step must not assume zero moments for
         tensors that have not seen a gradient in THIS process (PP_ADAM_SEEN, include/pyprob_amd.h)."""
         self.arrived.view(-1, L.PP_ADAM_SCRATCH)[:, L.PP_ADAM_SEEN] = 1
+        self.mark_touched()

@@ -161,6 +161,15 @@ PROTOTYPES = {
     'pp_ic_loss': (C.c_int, [C.POINTER(pp_net), C.POINTER(pp_batch), vp, vp, vp, C.c_size_t, vp, vp, vp, i32, vp]),
     'pp_adam_step': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_float, C.c_float, i32, vp, vp]),
+    'pp_adam_step_live': (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, i32, vp, vp]),
+    'pp_adam_live_bind': (C.c_int, [vp, vp, vp, i64, vp, i32, i32]),
+    'pp_adam_live_unbind': (C.c_int, [vp]),
+    'pp_adam_live_mark_touched': (C.c_int, [vp]),
+    'pp_adam_live_mark_range': (C.c_int, [vp, i64, i64]),
+    'pp_adam_live_info': (C.c_int, [vp, vp, vp]),
+    'pp_adam_live_plan': (C.c_int, [vp, i32, vp, vp]),
+    'pp_adam_live_table': (C.c_int, [vp, vp, vp, i64, i32, C.c_float, vp]),
     'pp_sgd_step': (C.c_int, [vp, vp, vp, i64, vp, vp, i32, C.c_float, C.c_float, i32, C.c_float, C.c_float, i32, vp, vp]),
     'pp_larc_scale': (C.c_int, [vp, vp, i64, vp, vp, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                 i32, vp, vp, vp]),
