@@ -1105,7 +1105,10 @@ int pp_debug_timeline(long long* buf /*dev [16] or NULL*/);
 /* debug: per-workgroup {start, end, problem, split, operands ready, loads issued, first slab landed, K loop done} stamps (10 ns ticks) of the grouped async GEMM launches
  * (mode 1: weight-gradient groups, 2: data-gradient products); buf = dev int64 [8 * cap] or NULL (tools/wg_trace.py).
  * mode 3: the Adam launches - {start, tensor known, gradient arrived, p / m / v arrived, corrections ready, stores issued, end,
- * tensor id} per workgroup (tools/adam_wg_trace.py) */
+ * tensor id} per workgroup (tools/adam_wg_trace.py)
+ * mode 4: the step's first launch (obs_embed_fwd_kernel) - embedding workgroups {start, entry loads issued, weights arrived, LDS
+ * image complete, observation arrived and layer 0 done, last dense layer done, stores issued, end}, bias / image workgroups
+ * {start, operands arrived, end, -, -, -, -, job kind: 1 bias, 2 image} (tools/first_launch_wg_trace.py) */
 int pp_debug_wgtrace(long long* buf, int32_t cap, int32_t mode);
 int pp_debug_clock_probe(int32_t iters, long long* out /*dev [2]*/, float* sink /*dev [1]*/, void* stream);
 

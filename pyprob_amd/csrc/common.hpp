@@ -159,6 +159,11 @@ __device__ __forceinline__ void warm_kernargs(int bytes) {
     }
 }
 
+// Stamps of the per-workgroup timelines (pp_debug_wgtrace; `tr` = the workgroup's eight words or nullptr): word k <- wall
+// clock (10 ns ticks), taken by thread 0. An "arrived" stamp waits for the loads issued so far.
+#define PP_WG_STAMP(tr, k) do { if ((tr) && threadIdx.x == 0) { __builtin_amdgcn_sched_barrier(0); (tr)[k] = wall_clock64(); __builtin_amdgcn_sched_barrier(0); } } while (0)
+#define PP_WG_STAMP_ARRIVED(tr, k) do { if (tr) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); PP_WG_STAMP(tr, k); } } while (0)
+
 // Cooperative global -> LDS copy by a 256-thread workgroup with 8 independent loads in flight per thread (a plain
 // `for (i = tid; i < n; i += 256) lds[i] = g[i]` is compiled load -> wait -> store and pays a full memory round trip
 // per element: ~1 us each at low occupancy).

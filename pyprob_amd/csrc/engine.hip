@@ -179,6 +179,7 @@ struct Workspace {
 // deterministic_mode() is: at the first workspace-size query or step, whichever comes first (carve needs PP_ADDR_BIAS)
 struct StepEnv {
     int addr_bias, dx_partials, fuse_cell_bwd, fuse_cell, gemm_holes, cell_lean, fuse_cell_rec, dh_partials, aux_colsum;
+    int first_early;   // PP_FIRST_EARLY: the first launch's embedding workgroups in their early order (obs_embed.hip); 0 = the order before
 };
 static int env_flag(const char* name, int dflt) {
     const char* e = getenv(name);
@@ -187,7 +188,8 @@ static int env_flag(const char* name, int dflt) {
 static const StepEnv& step_env() {
     static const StepEnv env{env_flag("PP_ADDR_BIAS", 1),     env_flag("PP_DX_PARTIALS", 1),   env_flag("PP_FUSE_CELL_BWD", 1),
                              env_flag("PP_FUSE_CELL", 1),     env_flag("PP_GEMM_HOLES", 1),    env_flag("PP_CELL_LEAN", 1),
-                             env_flag("PP_FUSE_CELL_REC", 1), env_flag("PP_DH_PARTIALS", 1),   env_flag("PP_AUX_COLSUM", 1)};
+                             env_flag("PP_FUSE_CELL_REC", 1), env_flag("PP_DH_PARTIALS", 1),   env_flag("PP_AUX_COLSUM", 1),
+                             env_flag("PP_FIRST_EARLY", 1)};
     return env;
 }
 
@@ -413,7 +415,7 @@ static ObsLin obs_lin(const pp_net* net, int o, int l) {
 // the observe embedding on its own: small embeddings (`fused`) in one launch (obs_embed.hip), else layer by layer
 static int observe_embedding_fwd(const pp_net* net, const float* P, const float* obs, int64_t ldobs, int B, const Workspace& w,
                                  hipStream_t st, bool bwd, bool fused) {
-    if (fused) return obs_embed_fwd_fused(net, P, obs, B, w.obs_h, w.cat, w.f1, w.E, st);
+    if (fused) return obs_embed_fwd_fused(net, P, obs, B, w.obs_h, w.cat, w.f1, w.E, st, nullptr, nullptr, nullptr, step_env().first_early);
     int ci = 0, co = 0;
     for (int o = 0; o < net->n_obs; ++o) {
         const int depth = obs_layers(net, o);
@@ -643,7 +645,7 @@ static int first_launch(const Step& s) {
             RowBuild rb{};
             rb.zero_small = p.in_place ? w.loss_acc : nullptr;
             rb.n_small = n_clear;
-            PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb));
+            PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb, nullptr, nullptr, step_env().first_early));
         } else {
             PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, p.bwd, false));
         }
@@ -659,7 +661,7 @@ static int first_launch(const Step& s) {
         PanelTranspose ptr{};
         if (p.panel) ptr = panel_transpose_job(s);
         PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb, p.compact ? &abias : nullptr,
-                                   p.panel ? &ptr : nullptr));
+                                   p.panel ? &ptr : nullptr, step_env().first_early));
     } else {
         PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, p.bwd, p.fused_obs));
         // (also clears the loss slots and, for a backward pass, dX: see the kernel)

@@ -98,7 +98,8 @@ static inline int addr_bias_blocks(const AddrBias& ab) { return ab.n_addr * ((ab
 // table columns [c2, I) (2 ne contiguous floats per row) come in with coalesced 16-byte loads, all issued before the first
 // LDS store (one memory round trip); thread (row, part) then takes an eighth of the two dot products from LDS and the
 // eight partial sums meet through DPP. Needs ldw, c2 and ne to be multiples of 4, 2 and 2 (engine.hip checks).
-__device__ __forceinline__ void addr_bias_block(const AddrBias& ab, int bb, float* lds) {
+// (tr: debug stamps of the first launch's timeline, pp_debug_wgtrace mode 4)
+__device__ __forceinline__ void addr_bias_block(const AddrBias& ab, int bb, float* lds, long long* tr = nullptr) {
     const int tid = threadIdx.x;
     if (bb == 0 && tid == 0 && ab.step_epoch) ab.step_epoch[0] += 1;
     const int nchunk = (ab.N + ADDR_BIAS_ROWS - 1) / ADDR_BIAS_ROWS;
@@ -122,6 +123,7 @@ __device__ __forceinline__ void addr_bias_block(const AddrBias& ab, int bb, floa
     }
     float e0 = 0.0f;
     if (tid < ne) e0 = tid < nd ? dt[tid] : ad[tid - nd];
+    PP_WG_STAMP_ARRIVED(tr, 1);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int i = tid + 256 * u;
@@ -165,6 +167,6 @@ int lstm_input_gather(const pp_net* net, const float* params, const float* E, in
 struct PanelTranspose;   // panel.hpp
 int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int n_traces, float* const* obs_h,
                         float* cat, float* f1, float* E, hipStream_t st, const RowBuild* rows = nullptr,
-                        const AddrBias* bias = nullptr, const PanelTranspose* transpose = nullptr);
+                        const AddrBias* bias = nullptr, const PanelTranspose* transpose = nullptr, int early = 0);
 
 }  // namespace pp

@@ -17,104 +17,180 @@
 
 namespace pp {
 
+// PP_FIRST_EARLY (engine.hip, StepEnv): what the embedding workgroups of the kernel below do out of the order they had before.
+// Nothing here changes a value that is stored: the same products in the same order (tests/test_gpu_first_launch.py: bitwise).
+constexpr int FE_OBS = 1;    // lane l < width loads obs[b][l] at ENTRY, in front of the weight loads (one coalesced load per
+                             // trace, the next trace's one iteration ahead); layer 0 takes its inputs from that register with
+                             // v_readlane - the observation was a cold line fetched BEHIND the staging and its barrier
+constexpr int FE_LATE = 2;   // a trace's results (obs_h, cat, f1, E) are stored behind its LAST dense layer: the wait the
+                             // compiler puts in front of a layer's k loop counts every store issued before it, so a store
+                             // between two layers put its acknowledgement into the chain
+constexpr int FE_WIDE = 4;   // the weight matrices come in through 16-byte loads (obs_embed.hpp obs_stage_all_wide); only where
+                             // every matrix qualifies (obs_stage_wide_ok)
+constexpr int FE_KEPT = FE_OBS | FE_LATE | FE_WIDE;
+
+extern long long* g_wgtrace;   // gemm_f32.hip (pp_debug_wgtrace; mode 4: this launch)
+extern int g_wgtrace_cap, g_wgtrace_mode;
+
+// saves the per-observable layers' results of trace b: hidden units (lane = hoff[o] + unit) and concatenated outputs
+template <int NOBS>
+__device__ __forceinline__ void obs_front_save(const ObsFusedArgs& a, int b, int lane, float h, float c, float* __restrict__ cat) {
+#pragma unroll
+    for (int o = 0; o < NOBS; ++o) {
+        if (o >= a.n_obs) break;
+        const int jh = lane - a.hoff[o];
+        if (jh >= 0 && jh < a.hid[o]) a.obs_h[o][(int64_t)b * a.ohid_ld[o] + jh] = h;
+    }
+    if (lane < a.e_obs) cat[(int64_t)b * a.e_ld + lane] = c;
+}
+
+// The per-observable layers of trace b: layer 0 (hidden unit per lane -> h) and the per-observable output layer; returns the
+// concatenated outputs (lane < e_obs). SAVE: both are stored where they arise (obs_h, cat), else the caller does it with
+// obs_front_save. OBS_REG: the observation sits in lanes [0, width) of `ob` (else it is read from memory, the same address in
+// every active lane).
+template <int NOBS, bool OBS_REG, bool SAVE>
+__device__ __forceinline__ float obs_front_layers(const ObsFusedArgs& a, const float* lds, const float* __restrict__ obs, float ob,
+                                                  int b, int lane, float* __restrict__ cat, float& h_out, long long* tr) {
+    float h = 0.0f, c = 0.0f;
+    int ci = 0, co = 0;
+#pragma unroll
+    for (int o = 0; o < NOBS; ++o) {
+        if (o >= a.n_obs) break;
+        const int jh = lane - a.hoff[o];
+        const bool acth = jh >= 0 && jh < a.hid[o];
+        if (OBS_REG) {   // every lane walks the k loop (v_readlane outside divergent code), inactive lanes on row 0
+            const int row = acth ? jh : 0;
+            const float* w = lds + a.l0[o].lds_w + row * (a.in[o] + 1);
+            float s = lds[a.l0[o].lds_b + row];
+            for (int i = 0; i < a.in[o]; ++i) s += w[i] * bcast(ob, ci + i);
+            if (acth) {
+                h = relu_keep_nan(s);
+                if (SAVE) a.obs_h[o][(int64_t)b * a.ohid_ld[o] + jh] = h;
+            }
+        } else if (acth) {   // layer 0 reads the raw observation directly (no cross-lane traffic)
+            const float* w = lds + a.l0[o].lds_w + jh * (a.in[o] + 1);
+            float s = lds[a.l0[o].lds_b + jh];
+            for (int i = 0; i < a.in[o]; ++i) s += w[i] * obs[(int64_t)b * a.width + ci + i];
+            h = relu_keep_nan(s);
+            if (SAVE) a.obs_h[o][(int64_t)b * a.ohid_ld[o] + jh] = h;
+        }
+        ci += a.in[o];
+    }
+    PP_WG_STAMP(tr, 4);
+#pragma unroll
+    for (int o = 0; o < NOBS; ++o) {
+        if (o >= a.n_obs) break;
+        const int jc = lane - co;
+        const bool actc = jc >= 0 && jc < a.out[o];
+        const float v = obs_dense(lds, a.l1[o], jc, actc, h, a.hoff[o]);
+        if (actc) c = v;
+        co += a.out[o];
+    }
+    if (SAVE && lane < a.e_obs) cat[(int64_t)b * a.e_ld + lane] = c;
+    h_out = h;
+    return c;
+}
+
+// LSTM input rows of trace b, one per time step it is alive in (step-major rows: row_off[t] + b): the embedding y2 sits in
+// lane c < e_obs, the address / previous-sample columns come from the tables (a separate gather launch did this before:
+// one launch and one read of E less). Also clears dX.
+__device__ __forceinline__ void obs_build_rows(const RowBuild& rb, int b, int lane, bool acte, float y2) {
+    {   // t = 0 needs no index loads: row_off[0] = 0, every trace is alive, no previous statement (pr = -1) - the
+        // columns [e_obs, c4) are zero; only full-width rows look the current address up
+        const int c4 = rb.d.e_obs + rb.d.smp + rb.d.dtype + rb.d.addr;
+        const int ad = rb.xcols > c4 ? rb.addr[b] : 0;
+        float* xr = rb.X + (int64_t)b * rb.ldx;
+        if (acte) xr[lane] = y2;
+        for (int c = rb.d.e_obs + lane; c < rb.xcols; c += 64) xr[c] = gather_embedding_elem(rb.d, rb.params, rb.at, c, -1, 0.0f, ad);
+        if (rb.zero_like) {
+            float* zr = rb.zero_like + (int64_t)b * rb.ldx;
+            for (int c = lane; c < rb.xcols; c += 64) zr[c] = 0.0f;
+        }
+    }
+    for (int t = 1; t < rb.t_max; ++t) {
+        const int r0 = rb.row_off[t];
+        if (b >= rb.row_off[t + 1] - r0) break;   // wave-uniform
+        const int r = r0 + b;
+        const int pr = rb.prev_row[r];
+        const int ap = pr < 0 ? -1 : rb.addr[pr];
+        const float v = pr < 0 ? 0.0f : rb.value[pr];
+        const int ad = rb.addr[r];
+        float* xr = rb.X + (int64_t)r * rb.ldx;
+        if (acte) xr[lane] = y2;
+        for (int c = rb.d.e_obs + lane; c < rb.xcols; c += 64) xr[c] = gather_embedding_elem(rb.d, rb.params, rb.at, c, ap, v, ad);
+        if (rb.zero_like) {
+            float* zr = rb.zero_like + (int64_t)r * rb.ldx;
+            for (int c = lane; c < rb.xcols; c += 64) zr[c] = 0.0f;
+        }
+    }
+}
+
 // NOBS: compile-time bound of the observable loops (1, 2, 4, 8 >= n_obs). With the loops unrolled every index into the
 // argument structs is static and the LOCAL copies below live in scalar registers; through the kernel-argument memory and
 // run-time indices the compiler re-loaded the layer descriptions at every use (136 scalar loads, each with a wait, on
 // the critical path of a kernel that runs one trace per wave).
-template <int NOBS>
+// EARLY: the FE_* bits above (0: the order before). trace: debug (pp_debug_wgtrace, mode 4; tools/first_launch_wg_trace.py),
+// eight wall-clock words (10 ns ticks) per workgroup - embedding workgroups: 0 start, 1 entry loads issued, 2 weights arrived,
+// 3 LDS image complete (behind the barrier), 4 observation arrived and layer 0 of the first trace done, 5 its last dense layer
+// done, 6 stores issued, 7 end; bias / image workgroups: 0 start, 1 operands arrived, 2 end, 7 job kind (1 bias, 2 image).
+template <int NOBS, int EARLY>
 __global__ __launch_bounds__(256) void obs_embed_fwd_kernel(const ObsFusedArgs ain, const float* __restrict__ P,
                                                             const float* __restrict__ obs, int n_traces,
                                                             int traces_per_wave, float* __restrict__ cat,
                                                             float* __restrict__ f1, float* __restrict__ E,
                                                             const RowBuild rbin, const AddrBias ab,
-                                                            const PanelTranspose tr) {
+                                                            const PanelTranspose tr_job, long long* __restrict__ trace) {
     __shared__ float lds[10240];
+    long long* const tr = trace ? trace + 8 * (int64_t)blockIdx.x : nullptr;
+    PP_WG_STAMP(tr, 0);
     const ObsFusedArgs a = ain;
     const RowBuild rb = rbin;
-    if (tr.n_blocks && (int)blockIdx.x >= tr.first_block) {   // extra workgroups: k-major weight copies for the panel kernel
-        panel_transpose_block(tr, (int)blockIdx.x - tr.first_block, lds);
+    if (tr_job.n_blocks && (int)blockIdx.x >= tr_job.first_block) {   // extra workgroups: k-major weight copies for the panel kernel
+        panel_transpose_block(tr_job, (int)blockIdx.x - tr_job.first_block, lds, tr);
+        if (tr && threadIdx.x == 0) { tr[2] = wall_clock64(); tr[7] = 2; }
         return;
     }
     if (ab.AB && (int)blockIdx.x >= ab.first_block) {   // extra workgroups: per-address bias vectors of the LSTM input
-        addr_bias_block(ab, (int)blockIdx.x - ab.first_block, lds);
+        addr_bias_block(ab, (int)blockIdx.x - ab.first_block, lds, tr);
+        if (tr && threadIdx.x == 0) { tr[2] = wall_clock64(); tr[7] = 1; }
         return;
     }
     warm_kernargs((int)(sizeof(ObsFusedArgs) + sizeof(RowBuild) + sizeof(AddrBias) + sizeof(PanelTranspose)) + 64);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = (blockIdx.x * 4 + wave) * traces_per_wave;
+    constexpr bool OBS_REG = (EARLY & FE_OBS) != 0;
+    float ob = 0.0f;   // the trace's observation, lane l < width (depends on nothing but the workgroup's place: loaded first)
+    if (OBS_REG && b0 < n_traces && lane < a.width) ob = obs[(int64_t)b0 * a.width + lane];
     // training step: this is the first kernel - clear the loss slots that later kernels add into
     if (rb.zero_small && blockIdx.x == 0)
         for (int q = tid; q < rb.n_small; q += 256) rb.zero_small[q] = 0.0f;
-    obs_stage_all<NOBS>(a, P, lds, tid);
+    if (EARLY & FE_WIDE) obs_stage_all_wide<NOBS>(a, P, lds, tid, tr);
+    else obs_stage_all<NOBS>(a, P, lds, tid, tr);
     __syncthreads();
-    const int b0 = (blockIdx.x * 4 + wave) * traces_per_wave;
+    PP_WG_STAMP(tr, 3);
+    constexpr bool LATE = (EARLY & FE_LATE) != 0;
     for (int t = 0; t < traces_per_wave; ++t) {
         const int b = b0 + t;
         if (b >= n_traces) break;   // wave-uniform
-        float h = 0.0f, c = 0.0f;
-        int ci = 0, co = 0;
-#pragma unroll
-        for (int o = 0; o < NOBS; ++o) {
-            if (o >= a.n_obs) break;
-            const int jh = lane - a.hoff[o];
-            const bool acth = jh >= 0 && jh < a.hid[o];
-            if (acth) {   // layer 0 reads the raw observation directly (no cross-lane traffic)
-                const float* w = lds + a.l0[o].lds_w + jh * (a.in[o] + 1);
-                float s = lds[a.l0[o].lds_b + jh];
-                for (int i = 0; i < a.in[o]; ++i) s += w[i] * obs[(int64_t)b * a.width + ci + i];
-                h = relu_keep_nan(s);
-                a.obs_h[o][(int64_t)b * a.ohid_ld[o] + jh] = h;
-            }
-            ci += a.in[o];
-        }
-#pragma unroll
-        for (int o = 0; o < NOBS; ++o) {
-            if (o >= a.n_obs) break;
-            const int jc = lane - co;
-            const bool actc = jc >= 0 && jc < a.out[o];
-            const float v = obs_dense(lds, a.l1[o], jc, actc, h, a.hoff[o]);
-            if (actc) c = v;
-            co += a.out[o];
-        }
+        float ob_next = 0.0f;
+        if (OBS_REG && t + 1 < traces_per_wave && b + 1 < n_traces && lane < a.width) ob_next = obs[(int64_t)(b + 1) * a.width + lane];
+        float h;
+        const float c = obs_front_layers<NOBS, OBS_REG, !LATE>(a, lds, obs, ob, b, lane, cat, h, t == 0 ? tr : nullptr);
         const bool acte = lane < a.e_obs;
-        if (acte) cat[(int64_t)b * a.e_ld + lane] = c;
         const float y1 = obs_dense(lds, a.f0, lane, acte, c, 0);
-        if (acte) f1[(int64_t)b * a.e_ld + lane] = y1;
+        if (!LATE && acte) f1[(int64_t)b * a.e_ld + lane] = y1;
         const float y2 = obs_dense(lds, a.f1, lane, acte, y1, 0);
-        if (acte) E[(int64_t)b * a.e_ld + lane] = y2;
-        if (rb.X) {
-            // LSTM input rows of this trace, one per time step it is alive in (step-major rows: row_off[t] + b): the
-            // embedding just computed sits in lane c < e_obs, the address / previous-sample columns come from the tables
-            // (a separate gather launch did this before: one launch and one read of E less). Also clears dX.
-            {   // t = 0 needs no index loads: row_off[0] = 0, every trace is alive, no previous statement (pr = -1) - the
-                // columns [e_obs, c4) are zero; only full-width rows look the current address up
-                const int c4 = rb.d.e_obs + rb.d.smp + rb.d.dtype + rb.d.addr;
-                const int ad = rb.xcols > c4 ? rb.addr[b] : 0;
-                float* xr = rb.X + (int64_t)b * rb.ldx;
-                if (acte) xr[lane] = y2;
-                for (int c = rb.d.e_obs + lane; c < rb.xcols; c += 64) xr[c] = gather_embedding_elem(rb.d, rb.params, rb.at, c, -1, 0.0f, ad);
-                if (rb.zero_like) {
-                    float* zr = rb.zero_like + (int64_t)b * rb.ldx;
-                    for (int c = lane; c < rb.xcols; c += 64) zr[c] = 0.0f;
-                }
-            }
-            for (int t = 1; t < rb.t_max; ++t) {
-                const int r0 = rb.row_off[t];
-                if (b >= rb.row_off[t + 1] - r0) break;   // wave-uniform
-                const int r = r0 + b;
-                const int pr = rb.prev_row[r];
-                const int ap = pr < 0 ? -1 : rb.addr[pr];
-                const float v = pr < 0 ? 0.0f : rb.value[pr];
-                const int ad = rb.addr[r];
-                float* xr = rb.X + (int64_t)r * rb.ldx;
-                if (acte) xr[lane] = y2;
-                for (int c = rb.d.e_obs + lane; c < rb.xcols; c += 64) xr[c] = gather_embedding_elem(rb.d, rb.params, rb.at, c, ap, v, ad);
-                if (rb.zero_like) {
-                    float* zr = rb.zero_like + (int64_t)r * rb.ldx;
-                    for (int c = lane; c < rb.xcols; c += 64) zr[c] = 0.0f;
-                }
-            }
+        if (t == 0) PP_WG_STAMP(tr, 5);
+        if (LATE) {
+            obs_front_save<NOBS>(a, b, lane, h, c, cat);
+            if (acte) f1[(int64_t)b * a.e_ld + lane] = y1;
         }
+        if (acte) E[(int64_t)b * a.e_ld + lane] = y2;
+        if (rb.X) obs_build_rows(rb, b, lane, acte, y2);
+        ob = ob_next;
     }
+    PP_WG_STAMP(tr, 6);
+    PP_WG_STAMP_ARRIVED(tr, 7);
 }
 
 // Backward of the observe embedding, DATA gradients only: per trace (one wave)
@@ -266,7 +342,7 @@ static int pick_traces_per_wave(int n, int target_blocks) {
 // obs_h: host array of n_obs device pointers; E/cat/f1 leading dim = round4(e_obs)
 int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int n_traces, float* const* obs_h,
                         float* cat, float* f1, float* E, hipStream_t st, const RowBuild* rows, const AddrBias* bias,
-                        const PanelTranspose* transpose) {
+                        const PanelTranspose* transpose, int early) {
     ObsFusedArgs a;
     if (!obs_fused_supported(net) || !obs_fused_args(net, obs_h, a)) return PP_EINVAL;
     const int tpw = pick_traces_per_wave(n_traces, 256);   // forward: staging is cheap, spread the traces
@@ -286,12 +362,17 @@ int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int
         tr.first_block = blocks;
         blocks += tr.n_blocks;
     }
-#define PP_OBS_FWD(N) hipLaunchKernelGGL(obs_embed_fwd_kernel<N>, dim3(blocks), dim3(256), 0, st, a, P, obs, n_traces, tpw, cat, f1, E, rb, ab, tr)
+    long long* const trace = g_wgtrace && g_wgtrace_mode == 4 && blocks <= g_wgtrace_cap ? g_wgtrace : nullptr;
+    // early: PP_FIRST_EARLY (0 = the order before)
+    const int mask = early == 0 ? 0 : obs_stage_wide_ok(a, P) ? FE_KEPT : FE_KEPT & ~FE_WIDE;
+#define PP_OBS_FWD2(N, M) hipLaunchKernelGGL((obs_embed_fwd_kernel<N, M>), dim3(blocks), dim3(256), 0, st, a, P, obs, n_traces, tpw, cat, f1, E, rb, ab, tr, trace)
+#define PP_OBS_FWD(N) do { if (!mask) PP_OBS_FWD2(N, 0); else if (mask & FE_WIDE) PP_OBS_FWD2(N, FE_KEPT); else PP_OBS_FWD2(N, FE_KEPT & ~FE_WIDE); } while (0)
     if (a.n_obs <= 1) PP_OBS_FWD(1);
     else if (a.n_obs <= 2) PP_OBS_FWD(2);
     else if (a.n_obs <= 4) PP_OBS_FWD(4);
     else PP_OBS_FWD(8);
 #undef PP_OBS_FWD
+#undef PP_OBS_FWD2
     PP_LAUNCH_CHECK("obs_embed_fwd_fused");
     return 0;
 }

@@ -78,8 +78,10 @@ __device__ __forceinline__ float obs_dense_t(const float* lds, const ObsLayer& L
 // ---- all layers' weights -> LDS -------------------------------------------------------------------------------
 // The parameters were just rewritten by Adam on other XCDs, so every load is a long trip (~1-2 us). ALL loads of ALL
 // layers are therefore issued first (one round trip), and only then the LDS stores.
+// (tr: debug stamps of the first launch's timeline - 1 loads issued, 2 weights arrived)
 template <int NOBS>
-__device__ __forceinline__ void obs_stage_all(const ObsFusedArgs& a, const float* __restrict__ P, float* lds, int tid) {
+__device__ __forceinline__ void obs_stage_all(const ObsFusedArgs& a, const float* __restrict__ P, float* lds, int tid,
+                                              long long* tr = nullptr) {
     ObsStage<16> sf0, sf1;                 // 64 x 64
     ObsStage<8> s1[NOBS];                  // out x hid <= 64 x 32
     ObsStage<1> s0[NOBS];                  // hid x in  <= 32 x 8
@@ -97,6 +99,8 @@ __device__ __forceinline__ void obs_stage_all(const ObsFusedArgs& a, const float
             b0[o] = tid < a.l0[o].rows ? P[a.l0[o].b_off + tid] : 0.0f;
         }
     }
+    PP_WG_STAMP(tr, 1);
+    PP_WG_STAMP_ARRIVED(tr, 2);
     const int dummy = a.lds_total;   // one spare word behind the image
     sf0.store(lds, a.f0.lds_w, a.f0.rows, a.f0.cols, dummy, tid);
     sf1.store(lds, a.f1.lds_w, a.f1.rows, a.f1.cols, dummy, tid);
@@ -107,6 +111,80 @@ __device__ __forceinline__ void obs_stage_all(const ObsFusedArgs& a, const float
         if (o < a.n_obs) {
             s1[o].store(lds, a.l1[o].lds_w, a.l1[o].rows, a.l1[o].cols, dummy, tid);
             s0[o].store(lds, a.l0[o].lds_w, a.l0[o].rows, a.l0[o].cols, dummy, tid);
+            if (tid < a.l1[o].rows) lds[a.l1[o].lds_b + tid] = b1[o];
+            if (tid < a.l0[o].rows) lds[a.l0[o].lds_b + tid] = b0[o];
+        }
+    }
+}
+
+// ---- the same image through 16-byte loads (the first launch's early order, obs_embed_fwd_kernel) -------------------------------
+// A weight matrix whose rows are a multiple of four floats long comes in as float4 pieces: a quarter of the load instructions,
+// and ONE offset computation per four LDS words (a piece never crosses a row). The words and their LDS offsets are those of
+// ObsStage. Needs cols % 4 == 0 and a 16-byte aligned matrix (obs_stage_wide_ok: the host decides per network).
+template <int U, int NT = 256>
+struct ObsStage4 {
+    f32x4 v[U];
+    __device__ __forceinline__ void load(const float* __restrict__ g, int n4, int tid) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = reinterpret_cast<const f32x4*>(g)[min(tid + NT * u, n4 - 1)];
+    }
+    // row = floor(i / (cols / 4)) through an exact float reciprocal (i < 2^11, cols / 4 <= 16)
+    __device__ __forceinline__ void store(float* lds, int lds_w, int rows, int cols, int tid) const {
+        const int c4 = cols >> 2, n4 = rows * c4;
+        const float inv = 1.0f / (float)c4;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = tid + NT * u;
+            const int r = (int)(((float)i + 0.5f) * inv);
+            float* d = lds + lds_w + r * (cols + 1) + 4 * (i - r * c4);
+            if (i < n4) {
+                d[0] = v[u][0]; d[1] = v[u][1]; d[2] = v[u][2]; d[3] = v[u][3];
+            }
+        }
+    }
+};
+
+static inline bool obs_stage_wide_ok(const ObsFusedArgs& a, const float* P) {
+    bool ok = ((uintptr_t)P & 15) == 0;
+    auto mat = [&](const ObsLayer& L) { ok = ok && L.cols % 4 == 0 && L.w_off % 4 == 0; };
+    mat(a.f0); mat(a.f1);
+    for (int o = 0; o < a.n_obs; ++o) mat(a.l1[o]);
+    return ok;
+}
+
+// obs_stage_all with the final matrices and the per-observable output layers on 16-byte loads (layer 0, rows of 1 - 8 floats,
+// and the biases stay dwords): 18 instead of 50 loads per thread for two observables
+template <int NOBS>
+__device__ __forceinline__ void obs_stage_all_wide(const ObsFusedArgs& a, const float* __restrict__ P, float* lds, int tid,
+                                                   long long* tr = nullptr) {
+    ObsStage4<4> sf0, sf1;                 // 64 x 64
+    ObsStage4<2> s1[NOBS];                 // out x hid <= 64 x 32
+    ObsStage<1> s0[NOBS];                  // hid x in  <= 32 x 8
+    float bf0, bf1, b1[NOBS], b0[NOBS];
+    sf0.load(P + a.f0.w_off, a.f0.rows * a.f0.cols >> 2, tid);
+    sf1.load(P + a.f1.w_off, a.f1.rows * a.f1.cols >> 2, tid);
+    bf0 = tid < a.f0.rows ? P[a.f0.b_off + tid] : 0.0f;
+    bf1 = tid < a.f1.rows ? P[a.f1.b_off + tid] : 0.0f;
+#pragma unroll
+    for (int o = 0; o < NOBS; ++o) {
+        if (o < a.n_obs) {
+            s1[o].load(P + a.l1[o].w_off, a.l1[o].rows * a.l1[o].cols >> 2, tid);
+            s0[o].load(P + a.l0[o].w_off, a.l0[o].rows * a.l0[o].cols, tid);
+            b1[o] = tid < a.l1[o].rows ? P[a.l1[o].b_off + tid] : 0.0f;
+            b0[o] = tid < a.l0[o].rows ? P[a.l0[o].b_off + tid] : 0.0f;
+        }
+    }
+    PP_WG_STAMP(tr, 1);
+    PP_WG_STAMP_ARRIVED(tr, 2);
+    sf0.store(lds, a.f0.lds_w, a.f0.rows, a.f0.cols, tid);
+    sf1.store(lds, a.f1.lds_w, a.f1.rows, a.f1.cols, tid);
+    if (tid < a.f0.rows) lds[a.f0.lds_b + tid] = bf0;
+    if (tid < a.f1.rows) lds[a.f1.lds_b + tid] = bf1;
+#pragma unroll
+    for (int o = 0; o < NOBS; ++o) {
+        if (o < a.n_obs) {
+            s1[o].store(lds, a.l1[o].lds_w, a.l1[o].rows, a.l1[o].cols, tid);
+            s0[o].store(lds, a.l0[o].lds_w, a.l0[o].rows, a.l0[o].cols, a.lds_total, tid);
             if (tid < a.l1[o].rows) lds[a.l1[o].lds_b + tid] = b1[o];
             if (tid < a.l0[o].rows) lds[a.l0[o].lds_b + tid] = b0[o];
         }

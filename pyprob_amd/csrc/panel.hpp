@@ -56,9 +56,10 @@ struct PanelTranspose {
 };
 static inline int panel_transpose_blocks(int H, int hid) { return 3 * H / 64 + ((hid + 63) / 64) * (H / 64); }
 
-__device__ __forceinline__ void panel_transpose_block(const PanelTranspose& tr, int b, float* lds /* >= 64 * 65 floats */) {
+__device__ __forceinline__ void panel_transpose_block(const PanelTranspose& tr, int b, float* lds /* >= 64 * 65 floats */,
+                                                      long long* stamps = nullptr) {
     if (tr.mode16) {
-        panel16_image_block(tr.Wih, tr.ldw, tr.W1, tr.H, tr.hid, tr.e, tr.p16, b, tr.wt);
+        panel16_image_block(tr.Wih, tr.ldw, tr.W1, tr.H, tr.hid, tr.e, tr.p16, b, tr.wt, stamps);
         return;
     }
     const int tid = threadIdx.x;       // 256 threads
@@ -83,6 +84,7 @@ __device__ __forceinline__ void panel_transpose_block(const PanelTranspose& tr, 
         const int r = r0 + ty + 4 * u, c = c0 + tx;
         v[u] = (r < rmax && c < cmax) ? src[(int64_t)r * ld_src + c] : 0.0f;
     }
+    PP_WG_STAMP_ARRIVED(stamps, 1);
 #pragma unroll
     for (int u = 0; u < 16; ++u) lds[(ty + 4 * u) * 65 + tx] = v[u];
     __syncthreads();

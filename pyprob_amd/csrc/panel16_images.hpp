@@ -45,7 +45,8 @@ struct Panel16Prep {      // rides in PanelTranspose (mode 16): the source matri
 
 // one thread per (fragment, lane): a float4 of four K steps
 __device__ __forceinline__ void panel16_image_block(const float* __restrict__ Wih, int64_t ldw, const float* __restrict__ W1,
-                                                    int H, int hid, int e, const Panel16Prep& p, int b, int wt) {
+                                                    int H, int hid, int e, const Panel16Prep& p, int b, int wt,
+                                                    long long* tr = nullptr) {
     int im = 0;
 #pragma unroll
     for (int i = 1; i < 6; ++i)
@@ -95,6 +96,7 @@ __device__ __forceinline__ void panel16_image_block(const float* __restrict__ Wi
             v[s] = Wih[(int64_t)row * ldw + 16 * tile + c];
         }
     }
+    PP_WG_STAMP_ARRIVED(tr, 1);
     // (the panel kernel of the next launch reads the images from every XCD: write-through, common.hpp store16_wt)
     if (wt) store16_wt(p.im.img[im], (uint32_t)(p.im.frags[im] * 1024), (uint32_t)q * 16u, v);
     else reinterpret_cast<f32x4*>(p.im.img[im])[q] = v;
