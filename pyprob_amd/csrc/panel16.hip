@@ -30,7 +30,8 @@
 //   phase 5  dh = dz1 W1 for the wave's 16 units (68 MFMAs) -> cell backward in registers -> dG to memory, column sums
 //   phase 6  partial dX = dG[:, own] W_ih[own, :e]: K = the wave's own 3 x 16 gate rows (A operand from a wave-private LDS
 //            tile, no workgroup barrier), the eight waves' tiles meet in LDS, the four workgroups' in memory; every workgroup
-//            finishes 4 of the panel's rows and walks them backward through the observe embedding (panel.hip's tail).
+//            finishes 4 of the panel's rows and walks them backward through the observe embedding (panel.hip's tail); the tail's
+//            weight image goes to LDS between the publish and the poll of that exchange.
 // The four workgroups of a panel are blocks b, b + 8, b + 16, b + 24 of a 32-block window: the same XCD under round-robin
 // placement (speed only). Not bit-reproducible (float atomics of the loss and column sums): PP_DETERMINISTIC=1 keeps the tile
 // path. Parity: tests/test_gpu_panel.py (every buffer and gradient against the tile path and the oracle, both panel kernels).
@@ -171,7 +172,10 @@ struct FragPtrs {
 // store16_wt) read back from the tile that sits in LDS anyway, right behind the barrier that completes it, instead of one plain
 // dword store per lane and element from the registers: the next launch reads them on every XCD, nothing in this kernel does. The
 // same values to the same addresses; rows at or beyond B stay unwritten either way.
-template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false>
+// EARLY (the default; PP_PANEL_PUBLISH=late keeps the kernel as it was): in exchange 2 the workgroup publishes its partial dX
+// BEFORE it writes the tail's weight image into LDS - the image used to delay every partner's arrival - and with the tail in
+// leaves dX itself unwritten. The same granules to the same slots, the same sums.
+template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false, bool EARLY = false>
 __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, const PanelObs oin) {
     using T = P16<HH_>;
     constexpr int HH = T::HH, UT = T::UT, UTW = T::UTW, NT = T::NT, TPW = T::TPW, ZK = T::ZK, ZT = T::ZT, PH = T::PH, PZ = T::PZ;
@@ -713,15 +717,21 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
     float* const sT0 = smem + T::L_H;                // A operands of the tail's layers: [16][PX], rows 0..3 = this workgroup's rows
     float* const sT1 = smem + T::L_Z;                // (over the partial dX tiles, behind a barrier)
     float* const sT2 = smem + T::L_Z + PR * PX;
-    if (OBS) {
-        const ObsFusedArgs& oa = oin.a;
-        const int dummy = oa.lds_total;
-        of1.store(oimg, oa.f1.lds_w, oa.f1.rows, oa.f1.cols, dummy, tid);
-        of0.store(oimg, oa.f0.lds_w, oa.f0.rows, oa.f0.cols, dummy, tid);
+    // the tail's three weight matrices -> LDS. The image depends on nothing in the exchange and nothing in the exchange touches its
+    // region: L_OIMG lies above the partial dX tiles (sXP), and sE and the tail's operand rows (sT0) lie below them.
+    static_assert(T::L_OIMG >= T::L_XP + NWV * PR * PX && T::L_H + PR * PX <= T::L_XP && T::L_E + PR * PE <= T::L_H, "LDS regions of exchange 2");
+    auto obs_image = [&]() {
+        if (OBS) {
+            const ObsFusedArgs& oa = oin.a;
+            const int dummy = oa.lds_total;
+            of1.store(oimg, oa.f1.lds_w, oa.f1.rows, oa.f1.cols, dummy, tid);
+            of0.store(oimg, oa.f0.lds_w, oa.f0.rows, oa.f0.cols, dummy, tid);
 #pragma unroll
-        for (int o = 0; o < ONB; ++o)
-            if (o < oa.n_obs) ol1[o].store(oimg, oa.l1[o].lds_w, oa.l1[o].rows, oa.l1[o].cols, dummy, tid);
-    }
+            for (int o = 0; o < ONB; ++o)
+                if (o < oa.n_obs) ol1[o].store(oimg, oa.l1[o].lds_w, oa.l1[o].rows, oa.l1[o].cols, dummy, tid);
+        }
+    };
+    if constexpr (!EARLY) obs_image();      // (the order this kernel had: the image first, every partner waits for it)
     {   // dX: the eight waves' partial tiles, then the three partner workgroups' sums for this workgroup's four rows
         unsigned long long* const xd_own = a.xd + (int64_t)(panel * SS + q) * (PR * EE);
         const int col = tid & 63;
@@ -739,6 +749,7 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
             if ((r >> 2) == q) { mine = sum; myrow = r; }
         }
         if constexpr (FLAGS) flag_set(flags_of(q) + 16 + wave);
+        if constexpr (EARLY) obs_image();      // behind the publish, in front of the poll: the granules fly meanwhile
         if (myrow >= 0) {      // (wave-uniform: the four waves whose row r = wave (+ 8) lies in this workgroup's quarter)
             const unsigned tag = gtag(epoch);
             float xs[3];
@@ -772,7 +783,11 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
             const float v2 = q == 2 ? mine : (q > 2 ? xs[2] : xs[1]);
             const float v3 = q == 3 ? mine : xs[2];
             const float dx = ((v0 + v1) + v2) + v3;
-            if (m0 + myrow < a.B) a.dX[(int64_t)(m0 + myrow) * a.ldx + col] = dx;
+            // (EARLY with the tail in: the tail below is dX's only consumer on this path - engine.hip ic_loss skips obs_dgrad_fused,
+            // the one reader of the buffer, when the panel launch carries the tail - so the 256 KB of stores are left out)
+            if constexpr (!(OBS && EARLY)) {
+                if (m0 + myrow < a.B) a.dX[(int64_t)(m0 + myrow) * a.ldx + col] = dx;
+            }
             if (OBS) {      // dz2 = dX * [E > 0] (inference_network.py:132-139 backward, the last ReLU of the final stack)
                 const float dz2 = sE[myrow * PE + col] > 0.0f ? dx : 0.0f;
                 sT0[(myrow & 3) * PX + col] = dz2;
@@ -846,12 +861,12 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
 #undef P16_ISSUE
 }
 
-template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false>
+template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false, bool EARLY = false>
 static int panel16_launch(const Panel16Args& a, const PanelObs& po, hipStream_t st) {
     constexpr size_t lds = (size_t)P16<HH_>::L_END * sizeof(float);
     static thread_local bool configured = false;   // > 64 KB of dynamic LDS needs the opt-in once per kernel
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel16_kernel<HH_, KIND, OBS, FLAGS, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)panel16_kernel<HH_, KIND, OBS, FLAGS, WT, EARLY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             set_error("panel16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
             return (int)e;
@@ -859,7 +874,7 @@ static int panel16_launch(const Panel16Args& a, const PanelObs& po, hipStream_t 
         configured = true;
     }
     const int panels = cdiv(a.a.B, PR);
-    hipLaunchKernelGGL((panel16_kernel<HH_, KIND, OBS, FLAGS, WT>), dim3(8 * SS * cdiv(panels, 8)), dim3(512), lds, st, a, po);
+    hipLaunchKernelGGL((panel16_kernel<HH_, KIND, OBS, FLAGS, WT, EARLY>), dim3(8 * SS * cdiv(panels, 8)), dim3(512), lds, st, a, po);
     return 0;
 }
 
@@ -868,8 +883,9 @@ static int panel16_slots() {      // workgroups of this kernel the device holds 
     int dev = 0, cus = 0, per_cu = 0;
     constexpr size_t lds = (size_t)P16<HH_>::L_END * sizeof(float);
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipFuncSetAttribute((const void*)panel16_kernel<HH_, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)panel16_kernel<HH_, 0, true>, 512, lds) != hipSuccess) return 0;
+    const void* const k = (const void*)panel16_kernel<HH_, 0, true, false, true, true>;      // (the default instantiation)
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 512, lds) != hipSuccess) return 0;
     return cus * per_cu;
 }
 
@@ -920,6 +936,11 @@ int panel16(int kind, const Panel16Args& a, hipStream_t st, const PanelObs* obs)
     // wave instead of {value, tag} granules - the kernel with the observe-embedding tail, H = 512 only (the benchmarked instantiations)
     const char* hv = getenv("PP_PANEL_HANDOFF");
     const bool flags = hv && hv[0] == 'f' && obs && p.H == 512;
+    // PP_PANEL_PUBLISH=late (read per call too): exchange 2 as it was - the weight image first, then the publish; dX stored.
+    // The A/B arm, instantiated for what the tests and the benchmark run (the observe-embedding tail with write-through result
+    // stores, both widths, every head kind); any other call publishes early whatever the switch says
+    const char* pv = getenv("PP_PANEL_PUBLISH");
+    const bool late = pv && pv[0] == 'l';
     // PP_STORE_WT (read per call as well): 16-byte write-through result stores; they need 16-byte aligned rows and address
     // their buffers with 32-bit byte offsets - anything else keeps the plain stores
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -928,8 +949,9 @@ int panel16(int kind, const Panel16Args& a, hipStream_t st, const PanelObs* obs)
 #define PP_P16_GO(HH_, KIND, WT_)                                                                            \
     do {                                                                                                     \
         if (obs && flags && HH_ == 512) PP_TRY((panel16_launch<512, KIND, true, true, WT_>(a, *obs, st)));  \
-        else if (obs) PP_TRY((panel16_launch<HH_, KIND, true, false, WT_>(a, *obs, st)));                    \
-        else PP_TRY((panel16_launch<HH_, KIND, false, false, WT_>(a, none, st)));                            \
+        else if (obs && late && WT_) PP_TRY((panel16_launch<HH_, KIND, true, false, true>(a, *obs, st)));    \
+        else if (obs) PP_TRY((panel16_launch<HH_, KIND, true, false, WT_, true>(a, *obs, st)));              \
+        else PP_TRY((panel16_launch<HH_, KIND, false, false, WT_, true>(a, none, st)));                      \
     } while (0)
 #define PP_P16_KIND(HH_, WT_)                                                  \
     do {                                                                       \
