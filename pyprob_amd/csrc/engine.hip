@@ -478,6 +478,9 @@ struct StepPlan {
     bool panel16_go;               // the 16-row kernel (panel16.hip) instead of the 8-row one (panel.hip)
     bool obs_tail;                 // training: the observe-embedding backward of the rows rides in the panel kernel's tail
     ObsFusedArgs obs_args;         // ... with these layer descriptions
+    // ... and the FORWARD embedding in its staging phase (panel16.hip EMBED, PP_PANEL_EMBED): the first launch has no embedding
+    // workgroups then. Set by ic_loss once the launch's arguments stand (panel16_embed_ok); every other path leaves it false
+    bool panel_embed;
     // ragged batches: the time steps t >= tail_t0 (few rows each) of every LSTM layer run in one launch per direction
     int tail_t0, tail_teams;
     // FeedForward, single-statement batch: row r IS trace r, the heads read E in place and the embedding kernel clears the
@@ -579,6 +582,13 @@ static AddrBias addr_bias(const Step& s) {
     ab.params = s.P; ab.at = net->addr_table; ab.ldw = p.I;
     ab.N = 4 * p.H; ab.c2 = p.c2; ab.c3 = p.c3; ab.c4 = p.c4; ab.c5 = p.c5; ab.I = p.I; ab.n_addr = net->n_addr;
     for (int q = 0; q < 32; ++q) ab.present[q] = p.present[q];
+    // PP_ADDR_BIAS_DIRECT (default 1, read per call: the A/B arm): one present address - its embedding vectors' offsets from the
+    // host's record, the table round trip leaves the bias workgroups' load chain (gather.hpp)
+    const char* dv = getenv("PP_ADDR_BIAS_DIRECT");
+    if (p.n_present == 1 && !(dv && atoi(dv) == 0)) {
+        ab.direct_on = 1; ab.direct_addr = p.only_addr;
+        ab.direct_dt = net->addrs[p.only_addr].dtype_emb; ab.direct_ad = net->addrs[p.only_addr].addr_emb;
+    }
     return ab;
 }
 // ... and the jobs behind its weight-gradient tiles turn the group sums of dG into the table-column gradients
@@ -638,6 +648,10 @@ static int first_launch(const Step& s) {
         gather_bytes += (double)p.n_present * (4.0 * 4 * H * (2.0 * p.ne) + 4.0 * 4.0 * 4 * H);
     }
     for (int o = 0; o < net->n_obs; ++o) gather_bytes += 4.0 * B * net->obs_hid[o];
+    if (p.panel_embed) {      // no embedding workgroups: the launch is its jobs (the panel launch reads the observations and writes the rows)
+        gather_bytes = 0.0;
+        if (p.compact) gather_bytes += (double)p.n_present * (4.0 * 4 * H * (2.0 * p.ne) + 4.0 * 4.0 * 4 * H);
+    }
     prof_begin(2, st);
     if (p.ff) {
         // every time step's proposal layer reads the observe embedding of its trace (:72,85): Hs rows = E[trace]
@@ -660,8 +674,9 @@ static int first_launch(const Step& s) {
         rb.zero_small = w.loss_acc; rb.n_small = n_clear;
         PanelTranspose ptr{};
         if (p.panel) ptr = panel_transpose_job(s);
+        // (panel_embed: the panel launch computes the embedding of its rows and writes E, cat, f1, the hidden rows and X)
         PP_TRY(obs_embed_fwd_fused(net, P, bt->obs, B, w.obs_h, w.cat, w.f1, w.E, st, &rb, p.compact ? &abias : nullptr,
-                                   p.panel ? &ptr : nullptr, step_env().first_early));
+                                   p.panel ? &ptr : nullptr, step_env().first_early, p.panel_embed));
     } else {
         PP_TRY(observe_embedding_fwd(net, P, bt->obs, bt->obs_width, B, w, st, p.bwd, p.fused_obs));
         // (also clears the loss slots and, for a backward pass, dX: see the kernel)
@@ -674,12 +689,13 @@ static int first_launch(const Step& s) {
 
 // Second launch of the panel step: everything between the LSTM input rows and dX (and, training, the observe-embedding
 // backward in its tail)
-static int panel_launch(const Step& s) {
+// (the launch's arguments; also what ic_loss asks panel16_embed_ok about, in front of the first launch)
+static void panel_args(const Step& s, PanelArgs& pa, PanelObs& po) {
     const pp_net* net = s.net; const pp_batch* bt = s.bt; const Workspace& w = s.w; const StepPlan& p = s.p;
-    const float* P = s.P; hipStream_t st = s.st;
+    const float* P = s.P;
     const int B = p.B, R = p.R, H = p.H;
     const pp_addr& ad = net->addrs[p.only_addr];
-    PanelArgs pa{};
+    pa = PanelArgs{};
     pa.B = R; pa.H = H; pa.hid = ad.hid; pa.n_out = ad.n_out; pa.K = ad.n_out / 3; pa.e = net->e_obs;
     pa.ldx = (int)w.i4; pa.lda1 = (int)w.hid4; pa.lddy = (int)w.out4; pa.ldw = p.I;
     pa.X = w.X; pa.Wih = P + net->w_ih; pa.AB = w.AB + (int64_t)p.only_addr * 2 * 4 * H;
@@ -692,13 +708,25 @@ static int panel_launch(const Step& s) {
     pa.lp_out = (s.flags & PP_LOSS_KEEP_LP) ? s.lp_out : nullptr;
     pa.loss_acc = w.loss_acc; pa.flag = w.flag; pa.grad_scale = -1.0f / (float)B;
     pa.dbg = g_timeline;
-    PanelObs po{};
+    po = PanelObs{};
     if (p.obs_tail) {
         po.a = p.obs_args;
         po.P = P; po.cat = w.cat; po.f1 = w.f1;
         po.dE = w.dE; po.dF1 = w.dF1; po.dCat = w.dCat; po.dHo0 = w.dObsH;
         po.dh_stride = (int64_t)B * w.maxohid4;
+        po.embed = p.panel_embed ? 1 : 0; po.xcols = w.xc;
+        po.obs = bt->obs; po.E = w.E; po.Xw = w.X; po.cat_w = w.cat; po.f1_w = w.f1;
     }
+}
+
+static int panel_launch(const Step& s) {
+    const pp_net* net = s.net; const Workspace& w = s.w; const StepPlan& p = s.p;
+    hipStream_t st = s.st;
+    const int R = p.R, H = p.H;
+    const pp_addr& ad = net->addrs[p.only_addr];
+    PanelArgs pa;
+    PanelObs po;
+    panel_args(s, pa, po);
     prof_begin(0, st);
     if (p.panel16_go) {
         Panel16Args p16{};
@@ -1289,8 +1317,14 @@ int ic_loss(const pp_net* net, const pp_batch* bt, const float* P, float* grads,
         return PP_ENOSPACE;
     }
     if (bwd && (flags & PP_LOSS_ZERO_GRADS)) (void)hipMemsetAsync(grads, 0, (size_t)net->n_params * sizeof(float), st);
-    const StepPlan p = plan_step(net, bt, flags, lp_out, loss_out, status_out, w);
+    StepPlan p = plan_step(net, bt, flags, lp_out, loss_out, status_out, w);
     const Step s{net, bt, P, grads, w, p, st, lp_out, flags};
+    if (p.panel16_go && p.obs_tail && p.T == 1 && p.compact) {      // (both launches read the answer from the plan)
+        PanelArgs pa;
+        PanelObs po;
+        panel_args(s, pa, po);
+        p.panel_embed = bt->obs_width == p.obs_args.width && panel16_embed_ok(pa, po);
+    }
     GradQueue q;
     PP_TRY(first_launch(s));
     if (p.panel) {

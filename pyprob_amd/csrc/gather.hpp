@@ -84,6 +84,10 @@ struct AddrBias {
     int all_present;
     int* step_epoch;        // counts the calls of this workspace (the job rides in a call's FIRST launch): the tag of the
                             // cross-workgroup hand-offs of the launches that follow (handoff.hpp); nullptr: not counted
+    // one present address (direct_on != 0): its two embedding vectors' offsets (the host's copy of the table record, pp_addr) ride
+    // in the arguments, so their loads go out WITH the W_ih loads instead of one table round trip behind them
+    int direct_on, direct_addr;
+    int64_t direct_dt, direct_ad;
 };
 
 __device__ __forceinline__ bool addr_present(const uint32_t (&mask)[32], int all, int a) {
@@ -109,8 +113,9 @@ __device__ __forceinline__ void addr_bias_block(const AddrBias& ab, int bb, floa
     const int ncol = 2 * ne, q4 = ncol >> 2, ss = ncol + 1;
     float* S = lds;                          // [32][2 ne + 1]
     float* ev = lds + ADDR_BIAS_ROWS * ss;   // [ne]
-    const float* dt = ab.params + ab.at[a * PP_ADDR_TABLE_COLS + PP_AT_DTYPE_EMB];
-    const float* ad = ab.params + ab.at[a * PP_ADDR_TABLE_COLS + PP_AT_ADDR_EMB];
+    const bool direct = ab.direct_on && a == ab.direct_addr;   // (workgroup-uniform)
+    float e0 = 0.0f;
+    if (direct && tid < ne) e0 = tid < nd ? ab.params[ab.direct_dt + tid] : ab.params[ab.direct_ad + tid - nd];
     constexpr int U = 8;   // 16-byte pieces per thread: 32 rows x 2 ne / 4 <= 2048
     f32x4 v[U];
     const int total = ADDR_BIAS_ROWS * q4;
@@ -121,8 +126,11 @@ __device__ __forceinline__ void addr_bias_block(const AddrBias& ab, int bb, floa
         const int n = min(n0 + r, ab.N - 1);
         v[u] = *reinterpret_cast<const f32x4*>(ab.W + (int64_t)n * ab.ldw + ab.c2 + 4 * c);
     }
-    float e0 = 0.0f;
-    if (tid < ne) e0 = tid < nd ? dt[tid] : ad[tid - nd];
+    if (!direct) {
+        const float* dt = ab.params + ab.at[a * PP_ADDR_TABLE_COLS + PP_AT_DTYPE_EMB];
+        const float* ad = ab.params + ab.at[a * PP_ADDR_TABLE_COLS + PP_AT_ADDR_EMB];
+        if (tid < ne) e0 = tid < nd ? dt[tid] : ad[tid - nd];
+    }
     PP_WG_STAMP_ARRIVED(tr, 1);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -167,6 +175,7 @@ int lstm_input_gather(const pp_net* net, const float* params, const float* E, in
 struct PanelTranspose;   // panel.hpp
 int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int n_traces, float* const* obs_h,
                         float* cat, float* f1, float* E, hipStream_t st, const RowBuild* rows = nullptr,
-                        const AddrBias* bias = nullptr, const PanelTranspose* transpose = nullptr, int early = 0);
+                        const AddrBias* bias = nullptr, const PanelTranspose* transpose = nullptr, int early = 0,
+                        bool jobs_only = false);
 
 }  // namespace pp

@@ -133,7 +133,9 @@ __device__ __forceinline__ void obs_build_rows(const RowBuild& rb, int b, int la
 // eight wall-clock words (10 ns ticks) per workgroup - embedding workgroups: 0 start, 1 entry loads issued, 2 weights arrived,
 // 3 LDS image complete (behind the barrier), 4 observation arrived and layer 0 of the first trace done, 5 its last dense layer
 // done, 6 stores issued, 7 end; bias / image workgroups: 0 start, 1 operands arrived, 2 end, 7 job kind (1 bias, 2 image).
-template <int NOBS, int EARLY>
+// JOBS: a launch without embedding workgroups (the 16-row panel kernel computes the embedding of its rows itself, panel16.hip
+// EMBED): bias and image jobs only, one instantiation; its block 0 - a job workgroup - clears the loss slots.
+template <int NOBS, int EARLY, bool JOBS = false>
 __global__ __launch_bounds__(256) void obs_embed_fwd_kernel(const ObsFusedArgs ain, const float* __restrict__ P,
                                                             const float* __restrict__ obs, int n_traces,
                                                             int traces_per_wave, float* __restrict__ cat,
@@ -145,6 +147,10 @@ __global__ __launch_bounds__(256) void obs_embed_fwd_kernel(const ObsFusedArgs a
     PP_WG_STAMP(tr, 0);
     const ObsFusedArgs a = ain;
     const RowBuild rb = rbin;
+    if constexpr (JOBS) {
+        if (rb.zero_small && blockIdx.x == 0)
+            for (int q = threadIdx.x; q < rb.n_small; q += 256) rb.zero_small[q] = 0.0f;
+    }
     if (tr_job.n_blocks && (int)blockIdx.x >= tr_job.first_block) {   // extra workgroups: k-major weight copies for the panel kernel
         panel_transpose_block(tr_job, (int)blockIdx.x - tr_job.first_block, lds, tr);
         if (tr && threadIdx.x == 0) { tr[2] = wall_clock64(); tr[7] = 2; }
@@ -155,6 +161,7 @@ __global__ __launch_bounds__(256) void obs_embed_fwd_kernel(const ObsFusedArgs a
         if (tr && threadIdx.x == 0) { tr[2] = wall_clock64(); tr[7] = 1; }
         return;
     }
+    if constexpr (JOBS) return;
     warm_kernargs((int)(sizeof(ObsFusedArgs) + sizeof(RowBuild) + sizeof(AddrBias) + sizeof(PanelTranspose)) + 64);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b0 = (blockIdx.x * 4 + wave) * traces_per_wave;
@@ -340,11 +347,17 @@ static int pick_traces_per_wave(int n, int target_blocks) {
 }
 
 // obs_h: host array of n_obs device pointers; E/cat/f1 leading dim = round4(e_obs)
+// jobs_only: no embedding workgroups (the 16-row panel kernel computes the embedding of its rows in its staging phase and writes
+// E, cat, f1, obs_h and the X rows itself): the launch is the bias and image jobs, and its block 0 clears the loss slots
 int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int n_traces, float* const* obs_h,
                         float* cat, float* f1, float* E, hipStream_t st, const RowBuild* rows, const AddrBias* bias,
-                        const PanelTranspose* transpose, int early) {
+                        const PanelTranspose* transpose, int early, bool jobs_only) {
     ObsFusedArgs a;
     if (!obs_fused_supported(net) || !obs_fused_args(net, obs_h, a)) return PP_EINVAL;
+    if (jobs_only) {
+        PP_CHECK_ARG((bias && bias->AB) || (transpose && transpose->n_blocks > 0), "obs_embed_fwd_fused: a launch of jobs only needs a job");
+        n_traces = 0;
+    }
     const int tpw = pick_traces_per_wave(n_traces, 256);   // forward: staging is cheap, spread the traces
     RowBuild rb{};
     if (rows) rb = *rows;
@@ -367,7 +380,8 @@ int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int
     const int mask = early == 0 ? 0 : obs_stage_wide_ok(a, P) ? FE_KEPT : FE_KEPT & ~FE_WIDE;
 #define PP_OBS_FWD2(N, M) hipLaunchKernelGGL((obs_embed_fwd_kernel<N, M>), dim3(blocks), dim3(256), 0, st, a, P, obs, n_traces, tpw, cat, f1, E, rb, ab, tr, trace)
 #define PP_OBS_FWD(N) do { if (!mask) PP_OBS_FWD2(N, 0); else if (mask & FE_WIDE) PP_OBS_FWD2(N, FE_KEPT); else PP_OBS_FWD2(N, FE_KEPT & ~FE_WIDE); } while (0)
-    if (a.n_obs <= 1) PP_OBS_FWD(1);
+    if (jobs_only) hipLaunchKernelGGL((obs_embed_fwd_kernel<1, 0, true>), dim3(blocks), dim3(256), 0, st, a, P, obs, 0, tpw, cat, f1, E, rb, ab, tr, trace);
+    else if (a.n_obs <= 1) PP_OBS_FWD(1);
     else if (a.n_obs <= 2) PP_OBS_FWD(2);
     else if (a.n_obs <= 4) PP_OBS_FWD(4);
     else PP_OBS_FWD(8);

@@ -35,6 +35,12 @@ struct PanelObs {
     const float* cat; const float* f1;   // saved activations [B][e_ld]
     float* dE; float* dF1; float* dCat; float* dHo0;
     int64_t dh_stride;
+    // 16-row kernel, embed != 0 (panel16.hip EMBED): the kernel computes the FORWARD embedding of its rows in its staging phase
+    // - the step's first launch then has no embedding workgroups - and writes what that launch wrote: E (also into columns
+    // [0, e) of the X rows; columns [e, xcols) are zeros at t = 0), cat, f1 and the observables' hidden rows (a.obs_h)
+    int embed, xcols;
+    const float* obs;                    // [B][a.width] observations
+    float* E; float* Xw; float* cat_w; float* f1_w;
 };
 constexpr int PANEL_OBS_LDS = 10240 + 8 + 4 * 64;      // the LDS image (+ its dummy word) and four dX rows, floats
 

@@ -175,7 +175,11 @@ struct FragPtrs {
 // EARLY (the default; PP_PANEL_PUBLISH=late keeps the kernel as it was): in exchange 2 the workgroup publishes its partial dX
 // BEFORE it writes the tail's weight image into LDS - the image used to delay every partner's arrival - and with the tail in
 // leaves dX itself unwritten. The same granules to the same slots, the same sums.
-template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false, bool EARLY = false>
+// EMBED (the default at H = 512 where the launch carries the tail and hands off through granules; PP_PANEL_EMBED=0 keeps the first launch's
+// embedding workgroups, 1 asks for it at H = 1024 too): the forward embedding of the panel's rows is computed HERE, in the staging phase, while the head of the ring is
+// in flight - the first launch loses its embedding workgroups (its longest chain) and E, cat, f1 and the hidden rows are no
+// longer written by one launch and read back by the next.
+template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false, bool EARLY = false, bool EMBED = false>
 __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, const PanelObs oin) {
     using T = P16<HH_>;
     constexpr int HH = T::HH, UT = T::UT, UTW = T::UTW, NT = T::NT, TPW = T::TPW, ZK = T::ZK, ZT = T::ZT, PH = T::PH, PZ = T::PZ;
@@ -252,10 +256,68 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
     fp.p4 = reinterpret_cast<const f32x4*>(ain.img[3]) + wave * 64 + lane;
     fp.p5 = reinterpret_cast<const f32x4*>(ain.img[4]) + ut0 * 64 + lane;
     fp.p6 = reinterpret_cast<const f32x4*>(ain.img[5]) + (ut0 * 3 * KE) * 64 + lane;
+    // masks of the tail's three layers for this lane's outputs: waves 0..3 = column tile `wave` of the two 64-wide layers, lanes
+    // 0..15 (row group 0 of the C layout) = the workgroup's four rows; waves o < n_obs: the hidden units of observable o
+    float m_f1[4] = {0, 0, 0, 0}, m_cat[4] = {0, 0, 0, 0}, m_h[4] = {0, 0, 0, 0};
+    // ---------------- EMBED: operands of the forward embedding of the panel's 16 rows, in front of the ring ----------------
+    // (as cold as the head of the ring; vmcnt counts in order, so what the forward waits for must not queue behind 24 fragments)
+    // layer 0: thread = (row tid & 15, hidden unit (tid >> 4) & 15 of observable tid >> 8); waves 0..3: column tile `wave` of
+    // the three MFMA layers - B[k][n] = W[n][k]: lane (c, g) of (unit u, tile t) holds W[16 t + c][16 u + 4 g .. + 3]
+    constexpr int ONB = 2;
+    float e_x[OBS_INMAX], e_w[OBS_INMAX], e_b0 = 0.0f, e_b1 = 0.0f, e_b2 = 0.0f, e_b3 = 0.0f;
+    f32x4 e_l1 = {0, 0, 0, 0}, e_f0[KE], e_f1[KE];
+    int e_in = 0, e_o = 0;               // layer 0: inputs of this thread's unit (0: a pad thread); tile: its observable
+    int e_hidw = 0, e_thid = 0;          // hidden units of observable `wave` (waves 0, 1) and of the tile's observable
+    bool e_act = false;
+    if constexpr (EMBED) {
+        // (every field by VALUE through a static index, selected afterwards: `x ? oa.f[1] : oa.f[0]` on the argument struct is a
+        // selected ADDRESS and one more dependent scalar load - eleven serial trips to the kernel arguments in front of the loads)
+        const ObsFusedArgs& oa = oin.a;
+        const float* const Pp = oin.P;
+        const int n_obs = oa.n_obs, width = oa.width, hid0 = oa.hid[0], hid1 = oa.hid[1], in0 = oa.in[0], in1 = oa.in[1], out0 = oa.out[0];
+        const int64_t l0w0 = oa.l0[0].w_off, l0w1 = oa.l0[1].w_off, l0b0 = oa.l0[0].b_off, l0b1 = oa.l0[1].b_off;
+        const int64_t l1w0 = oa.l1[0].w_off, l1w1 = oa.l1[1].w_off, l1b0 = oa.l1[0].b_off, l1b1 = oa.l1[1].b_off;
+        const int64_t f0w = oa.f0.w_off, f0b = oa.f0.b_off, f1w = oa.f1.w_off, f1b = oa.f1.b_off;
+        const int eo = (wave >> 2) < n_obs ? (wave >> 2) : 0, ej = (tid >> 4) & 15;
+        const int ohid = eo ? hid1 : hid0, oin_ = eo ? in1 : in0;
+        const bool eact = (wave >> 2) < n_obs && ej < ohid;
+        const int ejc = eact ? ej : 0;
+        const float* const xr = oin.obs + (int64_t)min(m0 + (tid & 15), a.B - 1) * width + (eo ? in0 : 0);
+        const float* const w0 = Pp + (eo ? l0w1 : l0w0) + ejc * oin_;
+#pragma unroll
+        for (int i = 0; i < OBS_INMAX; ++i) {
+            const int ii = max(min(i, oin_ - 1), 0);
+            e_x[i] = xr[ii];
+            e_w[i] = w0[ii];
+        }
+        e_b0 = Pp[(eo ? l0b1 : l0b0) + ejc];
+        e_in = eact ? oin_ : 0;
+        e_act = eact;
+        e_hidw = wave == 0 ? hid0 : (wave == 1 ? hid1 : 0);
+        if (wave < 4) {
+            e_o = (n_obs > 1 && 16 * wave >= out0) ? 1 : 0;
+            const int thid = e_o ? hid1 : hid0;
+            const int n1 = 16 * wave - (e_o ? out0 : 0) + c;      // row of the observable's output layer
+            const float* const w1 = Pp + (e_o ? l1w1 : l1w0) + n1 * thid;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) e_l1[s] = w1[min(4 * g + s, thid - 1)];      // (lanes beyond hid: zeroed where they are used)
+            e_thid = thid;
+            e_b1 = Pp[(e_o ? l1b1 : l1b0) + n1];
+#pragma unroll
+            for (int u = 0; u < KE; ++u) {
+                e_f0[u] = *reinterpret_cast<const f32x4*>(Pp + f0w + (16 * wave + c) * EE + 16 * u + 4 * g);
+                e_f1[u] = *reinterpret_cast<const f32x4*>(Pp + f1w + (16 * wave + c) * EE + 16 * u + 4 * g);
+            }
+            e_b2 = Pp[f0b + 16 * wave + c];
+            e_b3 = Pp[f1b + 16 * wave + c];
+        }
+    }
     // ---------------- staging: E rows (their loads go out first), then the head of the fragment stream ----------------
     f32x4 ev = {0, 0, 0, 0};
-    if (tid < PR * (EE / 4))
-        ev = *reinterpret_cast<const f32x4*>(a.X + (int64_t)min(m0 + (tid >> 4), a.B - 1) * a.ldx + 4 * (tid & 15));
+    if constexpr (!EMBED) {
+        if (tid < PR * (EE / 4))
+            ev = *reinterpret_cast<const f32x4*>(a.X + (int64_t)min(m0 + (tid >> 4), a.B - 1) * a.ldx + 4 * (tid & 15));
+    }
     f32x4 ring[RING];
 #define P16_ISSUE(G)                                                           \
     do {                                                                       \
@@ -280,10 +342,100 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
     const float m_v = a.value[mrow], m_pa = a.prior[2 * mrow], m_pb = a.prior[2 * mrow + 1];
     const int mcol = min(c, K - 1);
     const float m_b2mu = a.b2[mcol], m_b2sd = a.b2[K + mcol], m_b2z = a.b2[2 * K + mcol];
-    if (tid < PR * (EE / 4)) *reinterpret_cast<f32x4*>(sE + (tid >> 4) * PE + 4 * (tid & 15)) = ev;
+    // forward tiles [16][PX] of the embedding (hidden units | cat | f1) over sZ: dead until phase 2 fills it
+    float* const sF0 = smem + T::L_Z;
+    float* const sF1 = sF0 + PR * PX;
+    float* const sF2 = sF1 + PR * PX;
+    static_assert(3 * PR * PX <= PR * T::PZ, "the forward tiles of the embedding must fit sZ");
+    if constexpr (EMBED) {
+        // The embedding of the panel's 16 rows (InferenceNetwork._embed_observe), redundantly in the panel's four workgroups: the
+        // same instructions on the same inputs, so E is bit-identical on all four sides (the cross-workgroup sums rely on it).
+        // Layer 0 on VALU; l1[o], f0, f1 on MFMA: the A operand from the previous layer's LDS tile, bias and ReLU on the
+        // accumulators. The tail's masks are this workgroup's rows of the tiles, taken here (lanes of row group 0).
+        const ObsFusedArgs& oa = oin.a;
+        // (the scheduler otherwise moves layer 0 - and the wait for its operands - in FRONT of the ring issue: the head of the
+        // ring then starts its first touch one memory round trip late, +8 k cycles of staging in the phase stamps)
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            float s = e_b0;
+#pragma unroll
+            for (int i = 0; i < OBS_INMAX; ++i) s += i < e_in ? e_w[i] * e_x[i] : 0.0f;
+            sF0[(tid & 15) * PX + (tid >> 4)] = e_act ? relu_keep_nan(s) : 0.0f;
+        }
+        __syncthreads();
+        if (wave < 4) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(sF0 + c * PX + 16 * e_o + 4 * g);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) e_l1[s] = 4 * g + s < e_thid ? e_l1[s] : 0.0f;      // hid padded to 16 with zero lanes
+            const f32x4 acc = mma4(av, e_l1, f32x4{0, 0, 0, 0});
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sF1[(4 * g + i) * PX + 16 * wave + c] = relu_keep_nan(acc[i] + e_b1);
+            if (g == 0 && wave < oa.n_obs && c < e_hidw) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) m_h[i] = sF0[(4 * q + i) * PX + 16 * wave + c];
+            }
+        }
+        __syncthreads();
+        auto fwd64 = [&](const float* Tin, const f32x4 (&bf)[KE], float bias_c, float* Tout, int pitch, float (&mask)[4]) {
+            f32x4 c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0};
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(Tin + c * PX + 4 * g);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(Tin + c * PX + 16 + 4 * g);
+            const f32x4 a2 = *reinterpret_cast<const f32x4*>(Tin + c * PX + 32 + 4 * g);
+            const f32x4 a3 = *reinterpret_cast<const f32x4*>(Tin + c * PX + 48 + 4 * g);
+            PP_MMA(0, a0, bf[0], c0); PP_MMA(0, a1, bf[1], c1);
+            PP_MMA(1, a0, bf[0], c0); PP_MMA(1, a1, bf[1], c1);
+            PP_MMA(2, a0, bf[0], c0); PP_MMA(2, a1, bf[1], c1);
+            PP_MMA(3, a0, bf[0], c0); PP_MMA(3, a1, bf[1], c1);
+            PP_MMA(0, a2, bf[2], c0); PP_MMA(0, a3, bf[3], c1);
+            PP_MMA(1, a2, bf[2], c0); PP_MMA(1, a3, bf[3], c1);
+            PP_MMA(2, a2, bf[2], c0); PP_MMA(2, a3, bf[3], c1);
+            PP_MMA(3, a2, bf[2], c0); PP_MMA(3, a3, bf[3], c1);
+            if (g == 0) {      // (this layer's INPUT is the mask of the tail's layer below it)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) mask[i] = Tin[(4 * q + i) * PX + 16 * wave + c];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Tout[(4 * g + i) * pitch + 16 * wave + c] = relu_keep_nan((c0[i] + c1[i]) + bias_c);
+        };
+        if (wave < 4) fwd64(sF1, e_f0, e_b2, sF2, PX, m_cat);
+        __syncthreads();
+        if (wave < 4) fwd64(sF2, e_f1, e_b3, sE, PE, m_f1);
+    } else {
+        if (tid < PR * (EE / 4)) *reinterpret_cast<f32x4*>(sE + (tid >> 4) * PE + 4 * (tid & 15)) = ev;
+    }
     for (int i = tid; i < PR * PDY; i += 512) sDY[i] = 0.0f;
     __syncthreads();
     P16_STAMP(1);
+    if constexpr (EMBED) {
+        // What the first launch's embedding workgroups wrote, for this workgroup's four rows (live rows only): wave 0 E (also
+        // columns [0, e) of the X row), 1 cat, 2 f1 as 16-byte stores (write-through with WT); wave 3 the observables' hidden rows;
+        // wave 4 the columns [e, xcols) of the X rows, zeros at t = 0 (no previous statement). The tiles stay until phase 2.
+        const ObsFusedArgs& oa = oin.a;
+        const int rr = lane >> 4, r = 4 * q + rr;
+        const bool rlive = m0 + r < a.B;
+        if (wave < 3) {
+            const float* const tile = wave == 0 ? sE : (wave == 1 ? sF1 : sF2);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(tile + r * (wave == 0 ? PE : PX) + 4 * c);
+            const uint32_t ebytes = (uint32_t)a.B * (uint32_t)oa.e_ld * 4u;
+            float* const dst = wave == 0 ? oin.E : (wave == 1 ? oin.cat_w : oin.f1_w);
+            if (rlive) {
+                if constexpr (WT) {
+                    store16_wt(dst, ebytes, ((uint32_t)(m0 + r) * (uint32_t)oa.e_ld + 4 * c) * 4u, v);
+                    if (wave == 0) store16_wt(oin.Xw, (uint32_t)a.B * (uint32_t)a.ldx * 4u, ((uint32_t)(m0 + r) * (uint32_t)a.ldx + 4 * c) * 4u, v);
+                } else {      // (PP_STORE_WT=0: the same 16 bytes as plain stores)
+                    *reinterpret_cast<f32x4*>(dst + (int64_t)(m0 + r) * oa.e_ld + 4 * c) = v;
+                    if (wave == 0) *reinterpret_cast<f32x4*>(oin.Xw + (int64_t)(m0 + r) * a.ldx + 4 * c) = v;
+                }
+            }
+        } else if (wave == 3) {
+#pragma unroll
+            for (int o = 0; o < ONB; ++o)
+                if (o < oa.n_obs && rlive && c < oa.hid[o]) oa.obs_h[o][(int64_t)(m0 + r) * oa.ohid_ld[o] + c] = sF0[r * PX + 16 * o + c];
+        } else if (wave == 4) {
+            if (rlive)
+                for (int col = EE + c; col < oin.xcols; col += 16) oin.Xw[(int64_t)(m0 + r) * a.ldx + col] = 0.0f;
+        }
+    }
 
     // ---------------- phase 1: G = E W_ih[:, :e]^T + bias, LSTM cell (c0 = 0) ----------------
     float gi[UTW][4], gg[UTW][4], go[UTW][4], tc[UTW][4];        // gate activations and tanh(c) of (row 4 g + i, unit)
@@ -593,12 +745,9 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
     if constexpr (WT) rows_out(a.dZ1, a.lda1, sDZ, PZ, ZK, ZK);      // (phase 5 only reads the tile)
 
     // observe-embedding backward (tail): its weights and the masks of this lane's outputs are fetched behind phase 6
-    constexpr int ONB = 2;
+    // (EMBED: the masks - declared at the staging - are the forward's own values, nothing is read back)
     ObsStage<8, 512> of1, of0;
     ObsStage<4, 512> ol1[ONB];
-    // masks of the tail's three layers for this lane's outputs: waves 0..3 = column tile `wave` of the two 64-wide layers, lanes
-    // 0..15 (row group 0 of the C layout) = the workgroup's four rows; waves o < n_obs: the hidden units of observable o
-    float m_f1[4] = {0, 0, 0, 0}, m_cat[4] = {0, 0, 0, 0}, m_h[4] = {0, 0, 0, 0};
     f32x4 xacc[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};      // partial dX tiles of this wave
     // ---------------- phases 5 and 6, one unit tile of the wave at a time ----------------
     // phase 5: dh = dz1 W1 for the tile's 16 units, cell backward in registers; phase 6: partial dX[:, :e] += dG[:, tile's gate rows]
@@ -676,7 +825,7 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
 #pragma unroll
                 for (int o = 0; o < ONB; ++o)
                     if (o < oa.n_obs) ol1[o].load(oin.P + oa.l1[o].w_off, oa.l1[o].rows * oa.l1[o].cols, tid);
-                if (wave < 4 && g == 0) {
+                if (!EMBED && wave < 4 && g == 0) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int tb = min(m0 + 4 * q + i, a.B - 1);
@@ -861,12 +1010,12 @@ __global__ __launch_bounds__(512) void panel16_kernel(const Panel16Args ain, con
 #undef P16_ISSUE
 }
 
-template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false, bool EARLY = false>
+template <int HH_, int KIND, bool OBS, bool FLAGS = false, bool WT = false, bool EARLY = false, bool EMBED = false>
 static int panel16_launch(const Panel16Args& a, const PanelObs& po, hipStream_t st) {
     constexpr size_t lds = (size_t)P16<HH_>::L_END * sizeof(float);
     static thread_local bool configured = false;   // > 64 KB of dynamic LDS needs the opt-in once per kernel
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute((const void*)panel16_kernel<HH_, KIND, OBS, FLAGS, WT, EARLY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)panel16_kernel<HH_, KIND, OBS, FLAGS, WT, EARLY, EMBED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             set_error("panel16: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
             return (int)e;
@@ -874,7 +1023,7 @@ static int panel16_launch(const Panel16Args& a, const PanelObs& po, hipStream_t 
         configured = true;
     }
     const int panels = cdiv(a.a.B, PR);
-    hipLaunchKernelGGL((panel16_kernel<HH_, KIND, OBS, FLAGS, WT, EARLY>), dim3(8 * SS * cdiv(panels, 8)), dim3(512), lds, st, a, po);
+    hipLaunchKernelGGL((panel16_kernel<HH_, KIND, OBS, FLAGS, WT, EARLY, EMBED>), dim3(8 * SS * cdiv(panels, 8)), dim3(512), lds, st, a, po);
     return 0;
 }
 
@@ -924,6 +1073,50 @@ bool panel16_obs_ok(const ObsFusedArgs& oa) {
     return tot == EE;
 }
 
+// what the switches of a call select (each read per call: the A/B tests flip them inside one process)
+struct P16Mode { bool flags, late, wt; };
+static P16Mode panel16_mode(const PanelArgs& p, bool obs) {
+    // PP_PANEL_HANDOFF=flag: 4-byte payloads behind one flag per producer wave instead of {value, tag} granules - the kernel
+    // with the observe-embedding tail, H = 512 only (the benchmarked instantiations)
+    const char* hv = getenv("PP_PANEL_HANDOFF");
+    const bool flags = hv && hv[0] == 'f' && obs && p.H == 512;
+    // PP_PANEL_PUBLISH=late: exchange 2 as it was - the weight image first, then the publish; dX stored.
+    // The A/B arm, instantiated for what the tests and the benchmark run (the observe-embedding tail with write-through result
+    // stores, both widths, every head kind); any other call publishes early whatever the switch says
+    const char* pv = getenv("PP_PANEL_PUBLISH");
+    const bool late = pv && pv[0] == 'l';
+    // PP_STORE_WT: 16-byte write-through result stores; they need 16-byte aligned rows and address
+    // their buffers with 32-bit byte offsets - anything else keeps the plain stores
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const bool wt = store_wt_mode() && p.lda1 % 4 == 0 && p.lddy % 4 == 0 && al16(p.Hs) && al16(p.G) && al16(p.A1) && al16(p.dZ1) &&
+                    al16(p.DY) && (int64_t)p.B * 16 * p.H < ((int64_t)1 << 32) && (int64_t)p.B * 4 * std::max(p.lda1, p.lddy) < ((int64_t)1 << 32);
+    return P16Mode{flags, late, wt};
+}
+
+// PP_PANEL_EMBED (read per call; 0 = the first launch's embedding workgroups as before; 1 = here; unset = here at H = 512): does this call's panel
+// launch compute the forward embedding itself (EMBED)? The launch with the tail and the granule hand-off does, under either
+// setting of PP_PANEL_PUBLISH and PP_STORE_WT (their A/B tests hold per-row values bitwise equal across those switches, so
+// the embedding must not change with them), and only where the two 64 x 64 matrices come in as aligned float4 pieces of their
+// parameter rows and the outputs leave as 16-byte stores; every other call keeps the first launch's workgroups.
+// `po.embed` is not read here: the caller sets it from this answer, for the first launch and for panel16() alike.
+bool panel16_embed_ok(const PanelArgs& p, const PanelObs& po) {
+    // (unset: H = 512 only - at H = 1024 the first launch is as long as its 1 600 image workgroups with or without the embedding
+    // ones, and the panel kernel's longer staging is a net loss; PP_PANEL_EMBED=1 asks for it at both widths)
+    const char* ev = getenv("PP_PANEL_EMBED");
+    if (ev ? atoi(ev) == 0 : p.H != 512) return false;
+    if (!panel16_obs_ok(po.a)) return false;
+    const P16Mode m = panel16_mode(p, true);
+    if (m.flags || p.ldx % 4 != 0) return false;
+    auto al16 = [](const void* q) { return q && (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const ObsFusedArgs& oa = po.a;
+    if (!al16(po.P) || oa.f0.w_off % 4 != 0 || oa.f1.w_off % 4 != 0 || oa.e_ld % 4 != 0) return false;
+    if (!po.obs || !al16(po.E) || !al16(po.Xw) || !al16(po.cat_w) || !al16(po.f1_w)) return false;
+    if (po.xcols < EE || po.xcols > p.ldx || (int64_t)p.B * 4 * std::max<int64_t>(p.ldx, oa.e_ld) >= ((int64_t)1 << 32)) return false;
+    for (int o = 0; o < oa.n_obs; ++o)
+        if (oa.in[o] < 1 || oa.in[o] > OBS_INMAX || !oa.obs_h[o]) return false;
+    return true;
+}
+
 int panel16(int kind, const Panel16Args& a, hipStream_t st, const PanelObs* obs) {
     const PanelArgs& p = a.a;
     PP_CHECK_ARG(panel16_supported(kind, p.H, p.hid, p.n_out, p.e, p.B), "panel16: unsupported shape");
@@ -932,24 +1125,16 @@ int panel16(int kind, const Panel16Args& a, hipStream_t st, const PanelObs* obs)
                  "panel16: bad leading dimensions or missing buffers");
     if (obs) PP_CHECK_ARG(panel16_obs_ok(obs->a), "panel16: the observe-embedding tail does not fit");
     static const PanelObs none{};
-    // PP_PANEL_HANDOFF=flag (read per call: the A/B tests flip it inside one process): 4-byte payloads behind one flag per producer
-    // wave instead of {value, tag} granules - the kernel with the observe-embedding tail, H = 512 only (the benchmarked instantiations)
-    const char* hv = getenv("PP_PANEL_HANDOFF");
-    const bool flags = hv && hv[0] == 'f' && obs && p.H == 512;
-    // PP_PANEL_PUBLISH=late (read per call too): exchange 2 as it was - the weight image first, then the publish; dX stored.
-    // The A/B arm, instantiated for what the tests and the benchmark run (the observe-embedding tail with write-through result
-    // stores, both widths, every head kind); any other call publishes early whatever the switch says
-    const char* pv = getenv("PP_PANEL_PUBLISH");
-    const bool late = pv && pv[0] == 'l';
-    // PP_STORE_WT (read per call as well): 16-byte write-through result stores; they need 16-byte aligned rows and address
-    // their buffers with 32-bit byte offsets - anything else keeps the plain stores
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool wt = store_wt_mode() && p.lda1 % 4 == 0 && p.lddy % 4 == 0 && al16(p.Hs) && al16(p.G) && al16(p.A1) && al16(p.dZ1) &&
-                    al16(p.DY) && (int64_t)p.B * 16 * p.H < ((int64_t)1 << 32) && (int64_t)p.B * 4 * std::max(p.lda1, p.lddy) < ((int64_t)1 << 32);
+    const P16Mode md = panel16_mode(p, obs != nullptr);
+    const bool flags = md.flags, late = md.late, wt = md.wt;
+    const bool embed = obs && obs->embed;
+    if (embed) PP_CHECK_ARG(panel16_embed_ok(p, *obs), "panel16: the forward embedding was asked of a launch that cannot carry it");
 #define PP_P16_GO(HH_, KIND, WT_)                                                                            \
     do {                                                                                                     \
         if (obs && flags && HH_ == 512) PP_TRY((panel16_launch<512, KIND, true, true, WT_>(a, *obs, st)));  \
+        else if (obs && late && WT_ && embed) PP_TRY((panel16_launch<HH_, KIND, true, false, true, false, true>(a, *obs, st))); \
         else if (obs && late && WT_) PP_TRY((panel16_launch<HH_, KIND, true, false, true>(a, *obs, st)));    \
+        else if (obs && embed) PP_TRY((panel16_launch<HH_, KIND, true, false, WT_, true, true>(a, *obs, st))); \
         else if (obs) PP_TRY((panel16_launch<HH_, KIND, true, false, WT_, true>(a, *obs, st)));              \
         else PP_TRY((panel16_launch<HH_, KIND, false, false, WT_, true>(a, none, st)));                      \
     } while (0)

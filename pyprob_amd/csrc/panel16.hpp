@@ -15,6 +15,8 @@ struct Panel16Args {
 // single-statement batch, one address, one LSTM layer, mixture head of <= 30 outputs, H = 512 | 1024, e = 64: the 16-row kernel
 bool panel16_supported(int kind, int H, int hid, int n_out, int e, int B);
 bool panel16_obs_ok(const ObsFusedArgs& oa);      // the embedding shapes its (MFMA) tail takes
+// PP_PANEL_EMBED (read per call): may this call's launch compute the forward embedding of its rows itself (PanelObs::embed)?
+bool panel16_embed_ok(const PanelArgs& p, const PanelObs& po);
 int panel16(int kind, const Panel16Args& a, hipStream_t st, const PanelObs* obs = nullptr);
 // granules (8 bytes) of the two hand-off buffers for B rows
 int64_t panel16_xz_granules(int B, int H);

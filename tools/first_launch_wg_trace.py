@@ -2,6 +2,8 @@
 (GPU box; the sibling of tools/adam_wg_trace.py: the same engine, batches and warm-up):
    python tools/first_launch_wg_trace.py                     # the order the step runs (PP_FIRST_EARLY as set; default 1)
    PP_FIRST_EARLY=0 python tools/first_launch_wg_trace.py    # the parent's order
+   PP_PANEL_EMBED=0 python tools/first_launch_wg_trace.py    # with the embedding workgroups (unset, the panel kernel embeds its
+                                                             # rows and this launch has none: bias and image workgroups only)
 Stamps (pp_debug_wgtrace mode 4, 10 ns ticks). Embedding workgroups: start, entry loads issued, weights arrived, LDS image
 complete (behind the barrier), observation arrived and layer 0 done, last dense layer done, stores issued, end. Bias and
 image workgroups: start, operands arrived, end, job kind. An "arrived" stamp waits for the loads issued so far, so the traced
