@@ -19,6 +19,7 @@ reference is copied: we call its public API and record inputs/outputs:
 
 Case gumd: the gum program with observe embeddings of depth 3 (obs0) and 1 (obs1).
 Case gumm2: the gumm program with lstm_depth=2 (stacked nn.LSTM layers, lstm_dim=32).
+Case gumm4d: the gumm program with lstm_depth=4 and observe embeddings of depth 4 (obs0) and 2 (obs1).
 Cases ff / ffc: the same records for InferenceNetworkFeedForward (pyprob/nn/inference_network_feedforward.py) on the
 gumm / cat programs (no LSTM records). Cases: gum (GaussianUnknownMean, tests/test_inference.py:97-109), gumm (…Marsaglia, :252-275), both with
 lstm_dim=64 so the fixtures stay small, and cat (a Categorical->Normal toy model exercising
@@ -353,6 +354,12 @@ if __name__ == '__main__':
     if only == 'gumm2':
         # nn.LSTM(I, H, 2) (learn_inference_network(lstm_depth=2), inference_network_lstm.py:31): stacked layers
         run_case('gumm2', GaussianWithUnknownMeanMarsaglia(), 32, 1280, 64, 48, 24, obs, lstm_depth=2)
+        sys.exit(0)
+    if only == 'gumm4d':
+        # nn.LSTM(I, H, 4) next to observe embeddings of depth 4 and 2: the largest depths the engine accepts
+        # (PP_MAX_LSTM_DEPTH, PP_MAX_OBS_DEPTH); trace, batch and particle counts of gumm2
+        run_case('gumm4d', GaussianWithUnknownMeanMarsaglia(), 32, 1280, 64, 48, 24, obs, lstm_depth=4,
+                 obs_emb={'obs0': {'dim': 32, 'depth': 4}, 'obs1': {'dim': 16, 'depth': 2}})
         sys.exit(0)
     if only == 'ff':
         # InferenceNetworkFeedForward (pyprob/nn/inference_network_feedforward.py): heads read the observe embedding

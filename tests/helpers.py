@@ -166,29 +166,203 @@ def synthetic_gumm_arrays(n, seed=0, max_iter=6):
 KINK_MARGIN = 2e-6
 
 
-def away_from_relu_kinks(eng, arrays, addresses, dist_names, n):
+def _near_kink(x, W, b):
+    """[n] bool: a unit of relu(x W^T + b) whose float64 pre-activation lies within KINK_MARGIN of zero, relative to the sum of
+    |terms|."""
+    z = x @ W.T + b
+    return (np.abs(z) < KINK_MARGIN * (np.abs(x) @ np.abs(W).T + np.abs(b))).any(1)
+
+
+def away_from_relu_kinks(eng, arrays, addresses, dist_names, n, embedding=False):
     """The first n traces of `arrays` whose proposal layer-0 pre-activations all lie further than KINK_MARGIN (relative to
     the sum of |terms|) from the ReLU kink in float64. Nearer, the fp32 summation order decides the ReLU mask, and a flipped
     unit moves every gradient upstream of it by the unit's whole contribution: measured on MI355X with trained-looking
     weights, one unit at a margin of 9e-9 in 277 000 put the head's dW0 3e-3 off on every path (tiles, both panels,
-    PP_DETERMINISTIC=1) - a property of the data, not of a kernel."""
+    PP_DETERMINISTIC=1) - a property of the data, not of a kernel. embedding=True: the same for every ReLU layer of the
+    observe embedding (the observables' layers and the two final ones). A FeedForward network's heads read the observe
+    embedding at every time step."""
     from oracle import ic_oracle as O
     params = {k: v.numpy() for k, v in eng.state_dict().items()}
     net = O.Net(params, [o[0] for o in eng.spec.obs], K=eng.spec.K)
-    out = O.loss_and_grads(net, arrays, addresses, dist_names, want_grads=False)
     off = np.concatenate([[0], np.cumsum(arrays['trace_len'])])
     bad = np.zeros(len(arrays['trace_len']), bool)
-    for sb, hs in zip(out['sub_batches'], out['lstm_out']):
+    if eng.spec.feedforward:
+        subs, _ = O.split_sub_batches(arrays['trace_len'], arrays['addr_idx'])
+        E = O.embed_observe(net, np.asarray(arrays['obs'], np.float64))[0]
+        heads_in = [np.broadcast_to(E[np.asarray(sb)], (int(arrays['trace_len'][sb[0]]), len(sb), E.shape[1])) for sb in subs]
+    else:
+        out = O.loss_and_grads(net, arrays, addresses, dist_names, want_grads=False)
+        subs, heads_in = out['sub_batches'], out['lstm_out']
+    for sb, hs in zip(subs, heads_in):
         sb = np.asarray(sb)
         for t in range(hs.shape[0]):
             Ws, bs = net.ff('_layers_proposal.%s._ff' % addresses[arrays['addr_idx'][off[sb[0]] + t]])
-            z = hs[t] @ Ws[0].T + bs[0]
-            bad[sb[(np.abs(z) < KINK_MARGIN * (np.abs(hs[t]) @ np.abs(Ws[0]).T + np.abs(bs[0]))).any(1)]] = True
+            bad[sb[_near_kink(hs[t], Ws[0], bs[0])]] = True
+    if embedding:
+        _, (caches, acts_final) = O.embed_observe(net, np.asarray(arrays['obs'], np.float64))
+        for prefix, acts in [('_layers_observe_embedding.' + o[0], c) for o, c in zip(eng.spec.obs, caches)] + \
+                            [('_layers_observe_embedding_final', acts_final)]:
+            for x, W, b in zip(acts, *net.ff(prefix)):
+                bad |= _near_kink(x, W, b)
     keep = np.nonzero(~bad)[0][:n]
     assert len(keep) == n, (len(keep), n)
     rows = np.concatenate([np.arange(off[b], off[b + 1]) for b in keep])
     return dict(trace_len=arrays['trace_len'][keep], addr_idx=arrays['addr_idx'][rows], values=arrays['values'][rows],
                 prior=arrays['prior'][rows], obs=arrays['obs'][keep])
+
+
+# ---- the training step against the float64 oracle (tests/test_gpu_path.py, tests/test_gpu_depth.py) -------------------------------
+# gradient bars against the float64 oracle: <= 10x the largest error measured on MI355X (profiles/r04_grad_errors.jsonl:
+# 8.6e-7 relative on the single-statement shapes; 5.0e-9 ABSOLUTE on the ragged ones, whose gradients are ~1e-6)
+GRAD_BAR = 1e-5
+GRAD_ABS_RAGGED = 5e-8
+# absolute floors of the trained-looking cases with TruncatedNormal heads, whose head gradients are sums over ~1 000 rows that
+# cancel. Largest absolute error of a tensor beyond 1e-5 of its max |gradient|, measured on MI355X on the tile path
+# (PP_PANEL=0) / with PP_DETERMINISTIC=1 / on the default path - the same on every path, so fp32 summation order:
+#   single statements (GRAD_ABS_UNIFORM_TRAINED): K = 3 2.3e-8 / 2.1e-8 / 2.2e-8 (dW2 of the head, max 5e-5);
+#     K = 15 5.8e-9 / 5.9e-9 / 5.5e-9; K = 16 5.4e-9 / 6.1e-9 / 5.4e-9
+#   ragged GUMM (GRAD_ABS_RAGGED_TRAINED): H = 512 K = 1 5.2e-8 / 5.1e-8 / 5.2e-8 (dW2 of a head, max 5e-5);
+#     H = 512 K = 16 8.1e-9 / 9.4e-9 / 8.1e-9; H = 256 depth 2 K = 16 4.6e-9 / 4.7e-9 / 4.6e-9
+# (the ragged FeedForward cases keep GRAD_ABS_RAGGED: K = 1 3.8e-8, K = 16 1.3e-8 on all three paths)
+GRAD_ABS_UNIFORM_TRAINED = 5e-8
+GRAD_ABS_RAGGED_TRAINED = 1.5e-7
+DEFAULT_OBS = {'obs0': {'dim': 32}, 'obs1': {'dim': 32}}
+
+
+def unpack_lp(pb, lp_rows):
+    """per-row log_prob (packed row order) -> trace-major order of the batch arrays"""
+    out = np.empty(pb.n_rows, np.float64)
+    out[pb.src_row] = lp_rows
+    return out
+
+
+def check_golden_step(case, meta, params, batch, loss):
+    """One golden case through the C ABI against the reference's records: loss, per-row log_prob, every parameter gradient,
+    the presence map and the status word."""
+    import torch
+    eng = engine_from_golden(meta, params)
+    pb = packed_from_golden(meta, batch, eng.spec).to(eng.device)
+    l, lp = eng.loss(pb, backward=True, keep_lp=True)
+    torch.cuda.synchronize()
+    assert int(eng.status_buf[0].item()) == 0
+    ref_loss = float(loss['loss'])
+    assert abs(float(l.item()) - ref_loss) <= 1e-5 * abs(ref_loss), (float(l.item()), ref_loss)
+    # per-row log_prob against the reference's Mixture/Categorical.log_prob outputs
+    lp_tm = unpack_lp(pb, lp.cpu().numpy())
+    off = np.concatenate([[0], np.cumsum(batch['trace_len'])])
+    for k, (si, t) in enumerate(meta['lp_index']):
+        rows = off[np.array(meta['sub_batches'][si])] + t
+        ref = loss['lp_%d_%d' % (si, t)]
+        if ref.size == len(rows) ** 2 and len(rows) > 1:   # Bernoulli proposal: the reference's [n, n] broadcast matrix
+            ref = ref.reshape(len(rows), len(rows)).sum(1)
+        np.testing.assert_allclose(lp_tm[rows], ref, rtol=1e-4, atol=1e-4 * max(1.0, np.abs(ref).max()))
+    # every parameter gradient against loss.backward() of the reference
+    # (the reference's gradients are fp32 themselves: the bar is 1e-5 of a tensor's largest element + the 5e-8 absolute fp32
+    # summation floor of helpers.grad_check - measured against these goldens on MI355X: profiles/r06_grad_errors.jsonl)
+    g = eng.grad_dict()
+    for i, n in enumerate(meta['param_names']):
+        ref = loss['g%d' % i]
+        if not meta['has_grad'][i]:
+            assert np.all(g[n] == 0), n
+            continue
+        grad_check('golden_%s/%s' % (case, n), g[n], ref, 1e-5, 5e-8)
+    # presence map = which tensors had grad != None in the reference
+    act = eng.presence().cpu().numpy()
+    names = list(eng.spec.tensors.keys())
+    ref_has = dict(zip(meta['param_names'], meta['has_grad']))
+    assert [bool(a) for a in act] == [bool(ref_has[n]) for n in names]
+
+
+def oracle_run(spec, params, arrays, addresses, dist_names, want_grads=True):
+    from oracle import ic_oracle as O
+    net = O.Net(params, [o[0] for o in spec.obs], K=spec.K)
+    fn = O.loss_and_grads_feedforward if spec.feedforward else O.loss_and_grads
+    return fn(net, arrays, addresses, dist_names, want_grads=want_grads)
+
+
+def fresh_engine(lstm_dim, addresses, dist, seed=0, K=10, lstm_depth=1, network='lstm', extra=(), obs=None, device='cuda:0'):
+    """extra: (address, dist, num_categories) added after `addresses`. obs: the observe embeddings (DEFAULT_OBS).
+    device='cpu': the engine's buffers on the host (tests/oracle_ops.py CpuBufferEngine) - the initialisation is numpy's, the
+    weights are the same on either device."""
+    spec = NetSpec(obs or DEFAULT_OBS, lstm_dim=lstm_dim, proposal_mixture_components=K, network=network, lstm_depth=lstm_depth)
+    for a in addresses:
+        spec.add_address(a, dist)
+    for a, d, ncat in extra:
+        spec.add_address(a, d, ncat)
+    if device == 'cpu':
+        import oracle_ops
+        return oracle_ops.CpuBufferEngine(spec, seed=seed)
+    from pyprob_amd.engine import ICEngine
+    return ICEngine(spec, device=device, seed=seed)
+
+
+def trained_looking(eng, seed):
+    """LSTM and proposal weights x3 plus noisy biases (as test_gpu_is_step_fused._engine): the mixtures are far from uniform,
+    so a wrong component index moves log_prob and not only the gradients."""
+    rng = np.random.default_rng(seed)
+    sd = {k: (v.numpy() * (3.0 if ('lstm' in k or 'proposal' in k) else 1.0)).astype(np.float32) for k, v in eng.state_dict().items()}
+    for k in sd:
+        if k.endswith('bias') or 'bias_' in k:
+            sd[k] = (sd[k] + 0.1 * rng.standard_normal(sd[k].shape)).astype(np.float32)
+    eng.load_state_dict(sd)
+    return eng
+
+
+def packed(arrays, spec):
+    from pyprob_amd.packed import PackedBatch
+    return PackedBatch.from_ragged(arrays['trace_len'], arrays['addr_idx'], arrays['values'], arrays['prior'],
+                                   arrays['obs'], len(spec.addresses))
+
+
+def single_statement_arrays(B, dist, seed):
+    """One statement per trace, values spread wider than the prior: Normal N(1, 2 sqrt5) under the prior N(1, sqrt5); Uniform
+    U(-4, 6) with every 97th value outside the support (log_prob -inf -> rescued row); Poisson counts 0..40 (the head's
+    TruncatedNormal mixture on the fixed [0, 40], pyprob_amd.packed.POISSON_LOW_HIGH)."""
+    from pyprob_amd.packed import POISSON_LOW_HIGH
+    arr = synthetic_gum_arrays(B, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    if dist == 'Normal':
+        arr['values'] = (1.0 + 2.0 * np.sqrt(5.0) * rng.standard_normal(B)).astype(np.float32)
+    elif dist == 'Uniform':
+        arr['prior'] = np.tile(np.array([[-4.0, 6.0]], np.float32), (B, 1))
+        arr['values'] = rng.uniform(-4.0, 6.0, B).astype(np.float32)
+        arr['values'][::97] = 7.5
+    else:
+        arr['prior'] = np.tile(np.array([POISSON_LOW_HIGH], np.float32), (B, 1))
+        arr['values'] = rng.integers(0, 41, B).astype(np.float32)
+    return arr
+
+
+def oracle_lp_rows(out, arrays):
+    """The oracle's log_prob lists (one per sub-batch and time step) -> one value per row of the trace-major arrays."""
+    off = np.concatenate([[0], np.cumsum(arrays['trace_len'])])
+    ref = np.full(int(off[-1]), np.nan)
+    k = 0
+    for sb in out['sub_batches']:
+        sb = np.asarray(sb)
+        for t in range(int(arrays['trace_len'][sb[0]])):
+            ref[off[sb] + t] = out['lp'][k]
+            k += 1
+    assert k == len(out['lp']) and not np.isnan(ref).any()
+    return ref
+
+
+def check_lp(lp_tm, ref, label):
+    fin = np.isfinite(ref)
+    assert np.array_equal(np.isfinite(lp_tm), fin), label
+    np.testing.assert_allclose(lp_tm[fin], ref[fin], rtol=1e-4, atol=1e-4, err_msg=label)
+
+
+def check_grads(label, eng, out, abs_floor=0.0, grads=None):
+    """Every gradient tensor against the oracle's (GRAD_BAR of its largest element + abs_floor); a tensor the batch does not
+    touch - identically zero in the oracle - is identically zero on the device. grads: the device gradients by name (default:
+    the engine's current ones)."""
+    g = eng.grad_dict() if grads is None else grads
+    for n in eng.spec.tensors:
+        if np.abs(out['grads'][n]).max() >= 1e-7:
+            grad_check('%s/%s' % (label, n), g[n], out['grads'][n], GRAD_BAR, abs_floor)
+        elif not np.any(out['grads'][n]):
+            assert not np.any(g[n]), (label, n)        # a tensor the batch does not touch
 
 
 # ---- the importance-sampling test network (tests/test_gpu_is_step_fused.py, tests/test_gpu_is_fused_kernel.py) -----------------

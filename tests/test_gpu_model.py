@@ -412,3 +412,30 @@ def test_two_layer_lstm_trains_and_infers():
         '_layers_lstm.weight_hh_l1', net._engine.exp_avg_sq).abs().max()) > 0       # the second layer's recurrence trains
     post = model.posterior_results(600, IC, observe={'obs0': 4, 'obs1': 5}, lock_step=False, seed=1)
     assert post.length > 500 and np.isfinite(post.mean) and post.effective_sample_size > 3
+
+
+def test_three_layer_lstm_with_a_depth_three_embedding_trains_and_infers():
+    """learn_inference_network(lstm_depth=3) with one observable of embedding depth 3 on GUM, the trace counts of the test
+    above: the parameter names and shapes of nn.LSTM(I, H, 3) and of EmbeddingFeedForward(num_layers=3), every layer trains
+    (the step takes the generic embedding path), and the posterior mean for obs (8, 9) is within the GUM bound of this file."""
+    torch.manual_seed(17)
+    model = GaussianWithUnknownMean()
+    emb = {'obs0': {'dim': 32, 'depth': 3}, 'obs1': {'dim': 32}}
+    model.learn_inference_network(inference_network=LSTM, num_traces=30000, observe_embeddings=emb, batch_size=128, lstm_dim=32,
+                                  lstm_depth=3, seed=5)
+    net = model._inference_network
+    sd = net.state_dict()
+    I = net._engine.spec.lstm_in
+    ref = torch.nn.LSTM(I, 32, 3)
+    lstm_names = sorted(k for k in sd if k.startswith('_layers_lstm.'))
+    assert lstm_names == sorted('_layers_lstm.' + n for n, _ in ref.named_parameters())
+    for n, p in ref.named_parameters():
+        assert tuple(sd['_layers_lstm.' + n].shape) == tuple(p.shape), n
+    assert [tuple(sd['_layers_observe_embedding.obs0._layers.%d.weight' % l].shape) for l in range(3)] == [(16, 1), (16, 16), (32, 16)]
+    assert '_layers_observe_embedding.obs0._layers.3.weight' not in sd and '_layers_observe_embedding.obs1._layers.2.weight' not in sd
+    assert net._loss_previous < net._loss_init
+    for n in ['_layers_lstm.weight_ih_l%d' % l for l in range(3)] + ['_layers_observe_embedding.obs0._layers.%d.weight' % l for l in range(3)]:
+        assert float(net._engine.tensor(n, net._engine.exp_avg_sq).abs().max()) > 0, n      # every layer trains
+    post = model.posterior_results(50000, IC, observe=OBS, lock_step=True, seed=3)
+    assert abs(post.mean - 7.25) < 0.75
+    assert post.effective_sample_size > 3

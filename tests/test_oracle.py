@@ -92,8 +92,11 @@ def test_gradients_match_reference(golden):
     out = _run(golden)
     worst = 0.0
     # (gumm2: a 32-wide, barely trained network whose gradients are ~1e-6 in magnitude - the fp32 reference's own
-    # round-off is a few 1e-4 of that; the float64 oracle is compared at 1e-3 there)
-    tol = 1e-3 if case == 'gumm2' else 5e-4
+    # round-off is a few 1e-4 of that; the float64 oracle is compared at 1e-3 there. gumm4d, recorded the same way: its worst
+    # tensor, the last layer of a TruncatedNormal head with gradients of 1e-5, is 9.0e-4 from the record, and the oracle run in
+    # float32 is 9.7e-4 from the oracle in float64 on the same tensor - the fp32 round-off of the record. Its LSTM and
+    # embedding tensors are held to 5e-4 by tests/test_oracle_depth.py)
+    tol = 1e-3 if case in ('gumm2', 'gumm4d') else 5e-4
     for i, n in enumerate(meta['param_names']):
         ref = loss['g%d' % i]
         got = out['grads'][n]
