@@ -167,11 +167,15 @@ def ff_backward(dy, acts, Ws, relu_last):
 
 
 def embed_observe(net, obs):
-    """InferenceNetwork._embed_observe, pyprob/nn/inference_network.py:132-139. obs: [B, n_obs] scalars."""
-    parts, caches = [], []
-    for j, name in enumerate(net.obs_names):
+    """InferenceNetwork._embed_observe, pyprob/nn/inference_network.py:132-139. obs: [B, sum of the observables' input widths] -
+    observable j reads the w_j columns behind those of observables 0..j-1, w_j the input width of its first layer (scalar
+    observables: column j)."""
+    parts, caches, c = [], [], 0
+    for name in net.obs_names:
         Ws, bs = net.ff('_layers_observe_embedding.' + name)
-        y, acts = ff_forward(obs[:, j:j + 1].astype(net.dtype), Ws, bs, True)
+        w = Ws[0].shape[1]
+        y, acts = ff_forward(obs[:, c:c + w].astype(net.dtype), Ws, bs, True)
+        c += w
         parts.append(y)
         caches.append(acts)
     cat = np.concatenate(parts, axis=1)

@@ -302,22 +302,9 @@ __global__ __launch_bounds__(256) void obs_embed_dgrad_kernel(const ObsFusedArgs
 // ---- host side -----------------------------------------------------------------------------------------
 static inline int64_t round4(int64_t x) { return (x + 3) & ~int64_t(3); }
 
-bool obs_fused_supported(const pp_net* net) {
-    if (net->e_obs > OBS_EMAX) return false;
-    for (int o = 0; o < net->n_obs; ++o)
-        if (net->obs_kind[o] != PP_OBS_FEEDFORWARD) return false;   // a CNN2D5C observable: convolution stack + generic path
-    for (int o = 0; o < net->n_obs; ++o)
-        if (net->obs_depth[o] != 0 && net->obs_depth[o] != 2) return false;   // other depths: generic GEMM path (engine.hip)
-    int hsum = 0;
-    for (int o = 0; o < net->n_obs; ++o) {
-        if (net->obs_in[o] > OBS_INMAX || net->obs_hid[o] > OBS_HIDMAX || net->obs_hid[o] < 1) return false;
-        hsum += net->obs_hid[o];
-    }
-    return hsum <= 64;
-}
-
-bool obs_fused_args(const pp_net* net, float* const* obs_h, ObsFusedArgs& a) {
-    for (int o = 0; o < PP_MAX_OBS; ++o) a.obs_h[o] = o < net->n_obs ? obs_h[o] : nullptr;
+// The layer descriptions and the offsets of the LDS image (everything of ObsFusedArgs but the activation buffers); false if the
+// image does not fit the kernels' 10 240 floats. The one place that knows the image's size.
+static bool obs_fused_layout(const pp_net* net, ObsFusedArgs& a) {
     a.n_obs = net->n_obs;
     a.e_obs = net->e_obs;
     a.e_ld = round4(net->e_obs);
@@ -342,6 +329,34 @@ bool obs_fused_args(const pp_net* net, float* const* obs_h, ObsFusedArgs& a) {
     return lds + 1 <= 10240;   // + the dummy word of the branch-free staging
 }
 
+// the shapes the kernels take: lanes, registers and the staging's loads per thread
+static bool obs_fused_shapes_ok(const pp_net* net) {
+    if (net->n_obs < 1 || net->n_obs > PP_MAX_OBS || net->e_obs > OBS_EMAX) return false;
+    for (int o = 0; o < net->n_obs; ++o)
+        if (net->obs_kind[o] != PP_OBS_FEEDFORWARD) return false;   // a CNN2D5C observable: convolution stack + generic path
+    for (int o = 0; o < net->n_obs; ++o)
+        if (net->obs_depth[o] != 0 && net->obs_depth[o] != 2) return false;   // other depths: generic GEMM path (engine.hip)
+    int hsum = 0;
+    for (int o = 0; o < net->n_obs; ++o) {
+        if (net->obs_in[o] > OBS_INMAX || net->obs_hid[o] > OBS_HIDMAX || net->obs_hid[o] < 1) return false;
+        hsum += net->obs_hid[o];
+    }
+    return hsum <= 64;
+}
+
+// The one predicate of the fused route (plan_step, is_init, is_first_statement_supported, panel_obs_tail_ok): the shapes the
+// kernels take AND a weight image that fits - one scalar observable of dim 64 (hid = 32) needs 10 721 words and takes the
+// generic path
+bool obs_fused_supported(const pp_net* net) {
+    ObsFusedArgs a;
+    return obs_fused_shapes_ok(net) && obs_fused_layout(net, a);
+}
+
+bool obs_fused_args(const pp_net* net, float* const* obs_h, ObsFusedArgs& a) {
+    for (int o = 0; o < PP_MAX_OBS; ++o) a.obs_h[o] = o < net->n_obs ? obs_h[o] : nullptr;
+    return obs_fused_layout(net, a);
+}
+
 static int pick_traces_per_wave(int n, int target_blocks) {
     return std::max((n + 4 * target_blocks - 1) / (4 * target_blocks), 1);
 }
@@ -353,7 +368,8 @@ int obs_embed_fwd_fused(const pp_net* net, const float* P, const float* obs, int
                         float* cat, float* f1, float* E, hipStream_t st, const RowBuild* rows, const AddrBias* bias,
                         const PanelTranspose* transpose, int early, bool jobs_only) {
     ObsFusedArgs a;
-    if (!obs_fused_supported(net) || !obs_fused_args(net, obs_h, a)) return PP_EINVAL;
+    PP_CHECK_ARG(obs_fused_shapes_ok(net) && obs_fused_args(net, obs_h, a),
+                 "obs_embed_fwd_fused: an embedding outside the fused kernels' shapes (obs_fused_supported)");
     if (jobs_only) {
         PP_CHECK_ARG((bias && bias->AB) || (transpose && transpose->n_blocks > 0), "obs_embed_fwd_fused: a launch of jobs only needs a job");
         n_traces = 0;
@@ -397,7 +413,8 @@ int obs_embed_dgrad_fused(const pp_net* net, const float* P, int n_traces, float
                           const float* E, float* dE, float* dF1, float* dCat, float* dHo0, int64_t dh_stride,
                           hipStream_t st, int n_split, int64_t split_stride) {
     ObsFusedArgs a;
-    if (!obs_fused_supported(net) || !obs_fused_args(net, obs_h, a)) return PP_EINVAL;
+    PP_CHECK_ARG(obs_fused_shapes_ok(net) && obs_fused_args(net, obs_h, a),
+                 "obs_embed_dgrad_fused: an embedding outside the fused kernels' shapes (obs_fused_supported)");
     const int tpw = pick_traces_per_wave(n_traces, 256);
     const int nsp = n_split > 1 && t_max == 1 ? n_split : 1;
 #define PP_OBS_BWD(N) hipLaunchKernelGGL(obs_embed_dgrad_kernel<N>, dim3(cdiv(n_traces, 4 * tpw)), dim3(256), 0, st, a, P, n_traces, tpw, cat, f1, dX, ldx, row_off_dev, t_max, E, dE, dF1, dCat, dHo0, dh_stride, nsp, split_stride)

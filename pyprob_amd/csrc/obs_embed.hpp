@@ -248,6 +248,7 @@ __device__ __forceinline__ float obs_forward_row(const ObsFusedArgs& a, const fl
 
 // fills the layer descriptions (LDS image offsets included); false if the image does not fit 10 240 floats
 bool obs_fused_args(const pp_net* net, float* const* obs_h, ObsFusedArgs& a);
+// the one predicate of the fused route: the kernels' shapes AND an image that fits (obs_fused_args succeeds where this holds)
 bool obs_fused_supported(const pp_net* net);
 
 }  // namespace pp

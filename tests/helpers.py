@@ -365,6 +365,22 @@ def check_grads(label, eng, out, abs_floor=0.0, grads=None):
             assert not np.any(g[n]), (label, n)        # a tensor the batch does not touch
 
 
+def first_launch_workgroups(eng, pb):
+    """Workgroups of the fused first launch (obs_embed.hip) that one step started: pp_debug_wgtrace mode 4 stamps them."""
+    import torch
+    from pyprob_amd import lib as L
+    lib, cap = L.load(), 4096
+    trace = torch.zeros(8 * cap, dtype=torch.int64, device=eng.device)
+    torch.cuda.synchronize()
+    lib.pp_debug_wgtrace(trace.data_ptr(), cap, 4)
+    try:
+        eng.loss(pb, backward=True)
+        torch.cuda.synchronize()
+    finally:
+        lib.pp_debug_wgtrace(None, 0, 0)
+    return int((trace.cpu().numpy().reshape(cap, 8)[:, 0] > 0).sum())
+
+
 # ---- the importance-sampling test network (tests/test_gpu_is_step_fused.py, tests/test_gpu_is_fused_kernel.py) -----------------
 IS_EMB = {'obs0': {'dim': 32}, 'obs1': {'dim': 32}}
 IS_ADDRS = [('a_normal', 'Normal', None), ('a_uniform', 'Uniform', None), ('a_cat', 'Categorical', 7), ('a_poisson', 'Poisson', None),

@@ -13,7 +13,7 @@ import pytest
 
 import depth_cases as D
 from conftest import REPO, load_golden
-from helpers import check_golden_step, rel_err
+from helpers import check_golden_step, first_launch_workgroups, rel_err
 from oracle import ic_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -85,30 +85,15 @@ def test_generic_observe_embedding_against_oracle(name, kind):
     D.step_against_oracle('depth_embed_%s_%s' % (name, kind), eng, arrays, addresses, dists, D.abs_floor(kind))
 
 
-def _first_launch_workgroups(eng, pb):
-    """Workgroups of the fused first launch (obs_embed.hip) that one step started: pp_debug_wgtrace mode 4 stamps them."""
-    from pyprob_amd import lib as L
-    lib, cap = L.load(), 4096
-    trace = torch.zeros(8 * cap, dtype=torch.int64, device=eng.device)
-    torch.cuda.synchronize()
-    lib.pp_debug_wgtrace(trace.data_ptr(), cap, 4)
-    try:
-        eng.loss(pb, backward=True)
-        torch.cuda.synchronize()
-    finally:
-        lib.pp_debug_wgtrace(None, 0, 0)
-    return int((trace.cpu().numpy().reshape(cap, 8)[:, 0] > 0).sum())
-
-
 def test_generic_embedding_takes_the_step_off_the_panel_path():
     """(512, depth 1, B = 40) single statements would run on the 16-row panel kernel behind the fused first launch; with
     embeddings of depth 4 and 2 the step must take the generic path instead. Observed, not assumed: the fused first launch
     stamps its workgroups in the trace (mode 4) - none with the deep embedding, some with the default one on the same batch."""
     eng, arrays, addresses, dists = D.build(*D.EMB_H512)
     pb, _, _ = D.step_against_oracle('depth_embed_d4_d2_h512_b40', eng, arrays, addresses, dists, D.abs_floor('single'))
-    assert _first_launch_workgroups(eng, pb) == 0
+    assert first_launch_workgroups(eng, pb) == 0
     control = D.engine('single', 512, 1)
-    assert _first_launch_workgroups(control, D.packed(arrays, control.spec).to(control.device)) > 0
+    assert first_launch_workgroups(control, D.packed(arrays, control.spec).to(control.device)) > 0
 
 
 def test_generic_embedding_feedforward_network_against_oracle():
