@@ -280,11 +280,14 @@ def oracle_run(spec, params, arrays, addresses, dist_names, want_grads=True):
     return fn(net, arrays, addresses, dist_names, want_grads=want_grads)
 
 
-def fresh_engine(lstm_dim, addresses, dist, seed=0, K=10, lstm_depth=1, network='lstm', extra=(), obs=None, device='cuda:0'):
+def fresh_engine(lstm_dim, addresses, dist, seed=0, K=10, lstm_depth=1, network='lstm', extra=(), obs=None, device='cuda:0',
+                 smp_dim=4, addr_dim=64, dtype_dim=8):
     """extra: (address, dist, num_categories) added after `addresses`. obs: the observe embeddings (DEFAULT_OBS).
+    smp_dim / addr_dim / dtype_dim: the sample, address and distribution-type embedding widths (the reference's defaults).
     device='cpu': the engine's buffers on the host (tests/oracle_ops.py CpuBufferEngine) - the initialisation is numpy's, the
     weights are the same on either device."""
-    spec = NetSpec(obs or DEFAULT_OBS, lstm_dim=lstm_dim, proposal_mixture_components=K, network=network, lstm_depth=lstm_depth)
+    spec = NetSpec(obs or DEFAULT_OBS, lstm_dim=lstm_dim, proposal_mixture_components=K, network=network, lstm_depth=lstm_depth,
+                   sample_embedding_dim=smp_dim, address_embedding_dim=addr_dim, distribution_type_embedding_dim=dtype_dim)
     for a in addresses:
         spec.add_address(a, dist)
     for a, d, ncat in extra:
@@ -387,12 +390,14 @@ IS_ADDRS = [('a_normal', 'Normal', None), ('a_uniform', 'Uniform', None), ('a_ca
             ('a_bern', 'Bernoulli', None)]
 
 
-def is_engine(H, seed=0, depth=1, emb=None, K=10, addrs=IS_ADDRS, device='cuda:0'):
+def is_engine(H, seed=0, depth=1, emb=None, K=10, addrs=IS_ADDRS, device='cuda:0', smp_dim=4, addr_dim=64, dtype_dim=8):
     """(engine, ISRunner, state dict) of a network with one address per proposal head and trained-looking weights.
+    smp_dim / addr_dim / dtype_dim: the sample, address and distribution-type embedding widths (the reference's defaults).
     device='cpu': the engine's buffers on the host (tests/oracle_ops.py CpuBufferEngine; the operators are then the oracle-backed
     stand-ins) - the initialisation is numpy's, the weights are the same on either device."""
     from pyprob_amd.is_engine import ISRunner
-    spec = NetSpec(emb or IS_EMB, lstm_dim=H, lstm_depth=depth, proposal_mixture_components=K)
+    spec = NetSpec(emb or IS_EMB, lstm_dim=H, lstm_depth=depth, proposal_mixture_components=K, sample_embedding_dim=smp_dim,
+                   address_embedding_dim=addr_dim, distribution_type_embedding_dim=dtype_dim)
     if device == 'cpu':
         import oracle_ops
         eng = oracle_ops.CpuBufferEngine(spec, seed=seed)

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import dim_cases as DC
 from helpers import IS_ADDRS as ADDRS, IS_EMB as EMB, is_engine as _engine
 from oracle import ic_oracle as O
 from pyprob_amd import lib as L
@@ -44,7 +45,8 @@ def _oracle_statement(sd, H, observe, prev, cur, prev_val, h0, c0, values, prior
     x[:, :col] = E[0]
     cat = {a: c for a, d, c in addrs}[a_prev] if d_prev == 'Categorical' else None
     s, _ = O.sample_embedding(net, a_prev, d_prev, prev_val, cat)
-    S, Ed, Ea = s.shape[1], 8, 64
+    S = s.shape[1]
+    Ed, Ea = (net.P[k + a].shape[0] for k, a in (('_layers_distribution_type_embedding.', d_prev), ('_layers_address_embedding.', a_prev)))
     x[:, col:col + S] = s
     x[:, col + S:col + S + Ed] = net.P['_layers_distribution_type_embedding.' + d_prev]
     x[:, col + S + Ed:col + S + Ed + Ea] = net.P['_layers_address_embedding.' + a_prev]
@@ -93,6 +95,15 @@ def _prev_values(dist, n, rng, ncat=7):
 
 def _ids(eng, name):
     return eng.spec.address_id[name]
+
+
+def statement_inputs(H, depth, n, prev, cur, ncat=7):
+    """(h0, c0, previous values, prior) of a statement case (also drawn by tests/test_oracle_dim_cases.py, with the oracle alone)."""
+    rng = np.random.default_rng(5)
+    h0 = (0.5 * rng.standard_normal((depth, n, H))).astype(np.float32).clip(-0.99, 0.99)
+    c0 = rng.standard_normal((depth, n, H)).astype(np.float32)
+    pv = _prev_values(prev[1], n, rng, ncat)
+    return h0, c0, pv, _prior_for(cur[1], n, rng)
 
 
 STATEMENT_CASES = [
@@ -157,18 +168,24 @@ STATEMENT_CASES_KC = [
                          [pytest.param(*c, 10, 7, id='%d-%d-prev%d-cur%d-%d' % (c[0], c[1], i, i, c[4])) for i, c in enumerate(STATEMENT_CASES)]
                          + STATEMENT_CASES_KC)
 def test_fused_statement_against_the_oracle(H, n, prev, cur, depth, K, ncat):
+    _statement_against_the_oracle(H, n, prev, cur, depth, K, ncat)
+
+
+def _statement_against_the_oracle(H, n, prev, cur, depth, K, ncat, dims=None):
+    """dims: the name of an off-grid network of tests/dim_cases.py (embedding widths, observe embedding) instead of the default
+    one; whether the fused statement takes it is then dim_cases.routes' to say."""
     from pyprob_amd.ops import ops
     addrs = _addrs(ncat)
-    eng, run, sd = _engine(H, depth=depth, K=K, addrs=addrs)
+    kw = DC.is_kw(dims) if dims else dict(depth=depth)
+    eng, run, sd = _engine(H, K=K, addrs=addrs, **kw)
+    emb = kw.get('emb')
     # (the fixture forces the fused statement at any n; by default H = 1024 takes it from 2 049 particles on)
     n_out = eng.spec.head_dims(eng.spec.addresses[_ids(eng, cur[0])])[0]
     fused = ((H in (512, 1024) and depth == 1) or (H % 32 == 0 and H <= 256)) and n_out <= 32
+    if dims:
+        fused = DC.routes(DC.ALL[dims])['is_fused'] and n_out <= 32
     assert eng.lib.pp_is_step_fused_supported(C.byref(eng.net), _ids(eng, cur[0]), n) == (1 if fused else 0)
-    rng = np.random.default_rng(5)
-    h0 = (0.5 * rng.standard_normal((depth, n, H))).astype(np.float32).clip(-0.99, 0.99)
-    c0 = rng.standard_normal((depth, n, H)).astype(np.float32)
-    pv = _prev_values(prev[1], n, rng, ncat)
-    prior = _prior_for(cur[1], n, rng)
+    h0, c0, pv, prior = statement_inputs(H, depth, n, prev, cur, ncat)
     dev = eng.device
     h = torch.from_numpy(h0.copy()).to(dev).contiguous()
     c = torch.from_numpy(c0.copy()).to(dev).contiguous()
@@ -189,7 +206,7 @@ def test_fused_statement_against_the_oracle(H, n, prev, cur, depth, K, ncat):
     if cur[1] == 'Categorical':
         assert np.all((v >= 0) & (v < ncat) & (v == np.floor(v)))
     href, cref, lq_ref, _ = _oracle_statement(sd, H, [8.0, 9.0], prev, cur, pv, o_h0, o_c0, v.astype(np.float64), prior.astype(np.float64),
-                                              depth=depth, K=K, addrs=addrs)
+                                              depth=depth, emb=emb, K=K, addrs=addrs)
     # the LSTM cell on v_exp_f32 / v_rcp_f32 sigmoid / tanh: absolute error of (h, c) asserted here
     eh = np.abs(h.cpu().numpy().reshape(np.shape(href)) - href).max()
     ec = np.abs(c.cpu().numpy().reshape(np.shape(cref)) - cref).max()
@@ -206,6 +223,82 @@ def test_fused_statement_against_the_oracle(H, n, prev, cur, depth, K, ncat):
     v2, lq2 = ops.is_step(eng.params, run.ws, eng.net_handle, _ids(eng, cur[0]), _ids(eng, prev[0]), n, run.e_obs,
                           torch.from_numpy(pv).to(dev), pt, h2, c2, n, value, 99, 0)
     assert torch.equal(v2, value) and torch.equal(lq2, logq) and torch.equal(h2, h) and torch.equal(c2, c)
+
+
+@pytest.mark.parametrize('name,n,prev,cur', DC.IS_STATEMENTS, ids=['%s-%d-%d' % (c[0], c[1], i) for i, c in enumerate(DC.IS_STATEMENTS)])
+def test_fused_statement_at_off_grid_dimensions_against_the_oracle(name, n, prev, cur):
+    """The statement above on the networks of tests/dim_cases.py: hidden sizes 50 / 100 / 33 (the chain), sample embeddings of 1 / 5
+    / 8 columns in the kernels' zero-padded k-slab of 8 (small kernel, big kernel, the wide launch at H = 1024) and of 9 (must
+    report unsupported and take the chain), address / distribution-type widths of 128 and 7, and the network with every dimension
+    odd. Same inputs, same tolerances, same bit-equal re-score; pp_is_step_fused_supported against dim_cases.routes."""
+    c = DC.ALL[name]
+    _statement_against_the_oracle(c[0], n, prev, cur, c[1], 10, 7, dims=name)
+
+
+def _oracle_first_statement(sd, observe, cur, values, prior, depth, emb, addrs):
+    """A trace's first `_infer_step` in float64: no previous statement (zero sample / address / type columns), zero state; one
+    row, shared by the n particles. Returns (h, c) [depth, H] and log q [n]."""
+    net = O.Net(sd, list(emb or EMB), K=10)
+    E, _ = O.embed_observe(net, np.asarray(observe, np.float64).reshape(1, -1))
+    x = np.zeros((1, net.lstm_layer(0)[0].shape[1]))
+    x[:, :E.shape[1]] = E[0]
+    Ed, Ea = (net.P[k + a].shape[0] for k, a in (('_layers_distribution_type_embedding.', cur[1]), ('_layers_address_embedding.', cur[0])))
+    x[:, -(Ed + Ea):-Ea] = net.P['_layers_distribution_type_embedding.' + cur[1]]
+    x[:, -Ea:] = net.P['_layers_address_embedding.' + cur[0]]
+    hs, cs, inp = [], [], x
+    for l in range(depth):
+        _, _, (hl, cl) = O.lstm_forward(inp[None], *net.lstm_layer(l), None, None)
+        hs.append(hl[0]); cs.append(cl[0]); inp = hl
+    n = len(values)
+    lq, _, _ = O.head_forward(net, cur[0], cur[1], np.tile(inp, (n, 1)), prior, values)
+    return np.stack(hs), np.stack(cs), lq
+
+
+@pytest.mark.parametrize('name', DC.IS_FIRST)
+def test_first_statement_at_off_grid_dimensions_against_the_oracle(name):
+    """A trace's first statement (prev_addr_id = -1: one shared row, state_rows = 1) on networks pp_is_first_statement takes
+    (addr10, smp8: W_ih rows of 104 / 216 floats) and does not take (addr128: lstm_in 340 > 256; H = 50 and 33: not % 4).
+    pp_is_first_statement_supported against dim_cases.routes; both ways - is_step, and ISRunner.step_net (the fused first
+    statement where supported) followed by the draw of pp_is_fused - the shared state row and log q at the drawn values match the
+    oracle at the statement test's tolerances."""
+    c = DC.ALL[name]
+    H, depth, n = c[0], c[1], DC.IS_FIRST_N
+    kw = DC.is_kw(name)
+    eng, run, sd = _engine(H, **kw)
+    cur = ('a_uniform', 'Uniform')
+    a = _ids(eng, cur[0])
+    supported = eng.lib.pp_is_first_statement_supported(C.byref(eng.net), a)
+    assert supported == (1 if DC.routes(c)['is_first'] else 0), (name, supported)
+    prior = np.array([DC.IS_FIRST_PRIOR], np.float32)
+    pt = torch.from_numpy(prior).to(eng.device)
+    pn = np.tile(prior.astype(np.float64), (n, 1))
+
+    def check(h, c_, v, lq, what):
+        assert np.all((v >= prior[0, 0]) & (v < prior[0, 1])), what
+        href, cref, lq_ref = _oracle_first_statement(sd, [8.0, 9.0], cur, v.astype(np.float64), pn, depth, kw['emb'], ADDRS)
+        eh, ec = np.abs(h[:, 0] - href).max(), np.abs(c_[:, 0] - cref).max()
+        assert eh < 4e-6 and ec < 2e-5, (what, eh, ec)
+        ok = np.isfinite(lq_ref)
+        assert ok.mean() > 0.99
+        err = np.abs(lq[ok] - lq_ref[ok]) / np.maximum(1.0, np.abs(lq_ref[ok]))
+        assert err.max() < 1e-4, (what, err.max())
+    run.begin(n)
+    value, logq = run.step(a, None, pt, seed=77)
+    torch.cuda.synchronize()
+    check(run.h.cpu().numpy(), run.c.cpu().numpy(), value.cpu().numpy(), logq.cpu().numpy(), 'is_step')
+    # the route of the lock-step executor: network part (embedding + LSTM row + proposal layer), then draw and - log q
+    run.init([8.0, 9.0])
+    run.begin(n)
+    run.h.zero_(); run.c.zero_()
+    run.step_net(a, None)
+    assert run._init_pending == 0
+    v2 = torch.full((n,), float('nan'), device=eng.device)
+    lw = torch.full((n,), float('nan'), device=eng.device)
+    nothing = ((2, None, 0, None, 0), torch.zeros(1, device=eng.device), 0.0, 0)      # (an identity term of scale 0: lw = - log q)
+    run.fused(a, pt, [nothing], v2, lw, True, seed=77)
+    torch.cuda.synchronize()
+    assert torch.equal(v2, value)      # the same Philox stream as pp_is_step
+    check(run.h.cpu().numpy(), run.c.cpu().numpy(), v2.cpu().numpy(), -lw.cpu().numpy(), 'step_net + fused')
 
 
 @pytest.mark.parametrize('H,depth', [(512, 1), (1024, 1), (32, 2), (64, 1), (128, 2), (192, 2)])
@@ -287,9 +380,20 @@ def test_row_index_list_updates_the_state_in_place(H, depth, m):
 def test_second_statement_with_the_shared_first_state(H, depth):
     """state_rows = 1: row 0 (of every layer) holds the state every particle left the first statement with; its recurrent
     product joins the bias row, the cell reads the one shared previous cell state, all n rows are written."""
+    _second_statement_with_the_shared_first_state(H, depth)
+
+
+@pytest.mark.parametrize('name', DC.IS_SECOND)
+def test_second_statement_with_the_shared_first_state_at_off_grid_dimensions(name):
+    """The same at H = 64 with a sample embedding of 8 columns (the small kernel's slab exactly full) and at H = 100 (the chain)."""
+    _second_statement_with_the_shared_first_state(DC.ALL[name][0], DC.ALL[name][1], dims=name)
+
+
+def _second_statement_with_the_shared_first_state(H, depth, dims=None):
     from pyprob_amd.ops import ops
     n = 3001
-    eng, run, sd = _engine(H, seed=6, depth=depth)
+    kw = DC.is_kw(dims) if dims else dict(depth=depth)
+    eng, run, sd = _engine(H, seed=6, **kw)
     rng = np.random.default_rng(3)
     h_row = (0.5 * rng.standard_normal((depth, 1, H))).astype(np.float32)
     c_row = rng.standard_normal((depth, 1, H)).astype(np.float32)
@@ -307,7 +411,8 @@ def test_second_statement_with_the_shared_first_state(H, depth):
     if depth == 1:
         o_h0, o_c0 = o_h0[0], o_c0[0]
     href, cref, lq_ref, _ = _oracle_statement(sd, H, [8.0, 9.0], ('a_uniform', 'Uniform'), ('a_uniform', 'Uniform'), pv,
-                                              o_h0, o_c0, v.cpu().numpy().astype(np.float64), prior.astype(np.float64), depth=depth)
+                                              o_h0, o_c0, v.cpu().numpy().astype(np.float64), prior.astype(np.float64), depth=depth,
+                                              emb=kw.get('emb'))
     tol = (1.0 if H <= 512 else 2.0) * depth
     assert np.abs(h.cpu().numpy().reshape(np.shape(href)) - href).max() < 4e-6 * tol
     assert np.abs(c.cpu().numpy().reshape(np.shape(cref)) - cref).max() < 2e-5 * tol
