@@ -800,6 +800,68 @@ int pp_is_extent_groups(const float* lw, const float* x, int32_t n_groups, int32
                         double* out /*dev [M, 4]: min x, max x, particles counted, particles whose x is NaN*/,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Order statistics of one latent of a lock-step posterior call on the device: the particles of every group in order of value,
+ * exact weighted quantiles over them, and the distinct values with their masses. The reference estimates a weighted median from
+ * 1000 resampled values on the host (median, pyprob/distributions/empirical.py:714-728) and combines duplicates by one host pass
+ * over all values per distinct value (combine_duplicates, pyprob/distributions/empirical.py:809-834); here the M groups of a
+ * batched call are sorted by one call and only the answers travel.
+ *   pp_is_sort_groups   KEY. Particle i of group g gets the 32-bit key 0xFFFFFFFF if lw is not finite (-inf, +inf, NaN) or x is
+ *                       NaN; else, with b the bits of x and -0.0 first made +0.0, ~b for a negative x and b | 0x80000000
+ *                       otherwise - unsigned order of the keys is numeric order of the values, and +-inf under a finite weight
+ *                       are ordinary keys at the two ends.
+ *                       OUTPUTS. The STABLE ascending sort of the n_per particles of the group by that key (ties keep particle
+ *                       order, so the permutation is unique): index_out[g n_per + k] = the index within the group of the k-th
+ *                       particle, value_out[..] = x[index] (the original bits), lw_out[..] = lw[index]; counted_out[g] =
+ *                       { c_g = particles with a key below 0xFFFFFFFF, particles with a finite lw whose x is NaN }. The first
+ *                       c_g sorted particles are the counted ones; the others follow in particle order.
+ *                       `stats` (dev double [M, 6] or NULL) is accepted for symmetry with the calls below: the keys do not
+ *                       depend on the weights' maximum, so the outputs carry the same bits with and without it.
+ *                       Dependent launches on the caller's stream, a least-significant-digit radix sort with 8-bit digits: a
+ *                       group of at most PP_IS_SORT_TILE particles is sorted by one workgroup of 256 threads in LDS (33 KB) in
+ *                       one launch; a longer group takes three launches per pass - per-tile digit counts, one workgroup per group
+ *                       that turns the (tile, digit) counts into offsets, and a scatter with in-tile stable ranks (wave ballots)
+ *                       between two buffers of the workspace (16 bytes per particle). No global atomics, no workgroup waits for
+ *                       another. Every output is a function of the keys alone: two identical calls give the same bits and
+ *                       group g of an M-group call equals the one-group call on its slice.
+ *   cumulative weights  pp_is_cdf_groups over lw_out (same `stats`) gives the cumulative weights in sorted order; the particles
+ *                       that are not counted lie at or beyond c_g and are never read below.
+ *   pp_is_quantile_groups  out[g n_q + j] = the inverted-cdf quantile q[j] (dev double [n_q] in [0, 1], shared by the groups) of
+ *                       group g, one thread per result, by binary search: T = cdf[g, c_g - 1], t = fl(q T); t > 0: k = the
+ *                       number of i < c_g with cdf[g, i] < t (numpy.searchsorted(cdf[:c_g], t, 'left')); else k = the number
+ *                       of i < c_g with cdf[g, i] <= 0 (the first particle of positive cumulative weight); k is at most
+ *                       c_g - 1; the result is (double)value_sorted[g, k]. c_g == 0 or a T that is not positive and finite: NaN.
+ *                       With uniform weights and q = 0.5 this is the lower of the two middle values.
+ *   pp_is_unique_groups  A run is a maximal stretch of the first c_g sorted particles with equal keys. For run r of group g:
+ *                       value_out[g n_per + r] = the value of its first particle, count_out[..] = its particles, mass_out[..] =
+ *                       sum llrint(min(w, 1) 2^S), w = exp((double)lw - max_g), S = pp_is_hist_shift(n_per) - the fixed point
+ *                       of pp_is_hist_groups with its order-independence and its derived bound |mass - sum w 2^S| <= 0.5 count
+ *                       + 2^-48 sum w 2^S; max_g = stats[6 g] or, without `stats`, the maximum of the finite lw_sorted of the
+ *                       whole group (both give the same bits). runs_out[g] = the number of runs; entries at or beyond it are
+ *                       not written. Dependent launches: the runs that begin in every tile of PP_IS_SORT_TILE particles are
+ *                       counted, one workgroup per group numbers them, a tile adds up its runs in LDS (integer adds) and a last
+ *                       launch adds to a run that crosses tiles the parts the following tiles hold of it (one thread per run:
+ *                       no global atomics).
+ * All three take the [M n_per] layout, any n_per >= 1 and n_groups >= 0 (0: return 0 without a launch; more than 65535 groups are
+ * split over launches), and write nothing outside their outputs and the workspace (pp_is_sort_workspace_bytes /
+ * pp_is_unique_workspace_bytes; PP_ENOSPACE when shorter). They return PP_EINVAL without a launch for a NULL required pointer
+ * (everything but `stats`), n_per < 1, n_groups < 0, n_q < 0, or M n_per / M n_q above 2^31 - 1. The workspace functions return 0
+ * outside that envelope. */
+#define PP_IS_SORT_TILE 2048
+size_t pp_is_sort_workspace_bytes(int32_t n_groups, int32_t n_per);
+int pp_is_sort_groups(const float* lw /*dev [M n_per]*/, const float* x /*dev [M n_per]*/, int32_t n_groups, int32_t n_per,
+                      const double* stats /*dev double [M, 6] or NULL*/, float* value_out /*dev [M n_per]*/,
+                      float* lw_out /*dev [M n_per]*/, int32_t* index_out /*dev [M n_per]*/, int32_t* counted_out /*dev [M, 2]*/,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int pp_is_quantile_groups(const float* value_sorted /*dev [M n_per]*/, const double* cdf_sorted /*dev [M n_per]*/,
+                          const int32_t* counted /*dev [M, 2]*/, int32_t n_groups, int32_t n_per, const double* q /*dev [n_q]*/,
+                          int32_t n_q, double* out /*dev [M, n_q]*/, void* stream);
+size_t pp_is_unique_workspace_bytes(int32_t n_groups, int32_t n_per);
+int pp_is_unique_groups(const float* value_sorted /*dev [M n_per]*/, const float* lw_sorted /*dev [M n_per]*/,
+                        const int32_t* counted /*dev [M, 2]*/, int32_t n_groups, int32_t n_per,
+                        const double* stats /*dev double [M, 6] or NULL*/, float* value_out /*dev [M n_per]*/,
+                        int64_t* mass_out /*dev [M n_per]*/, int32_t* count_out /*dev [M n_per]*/, int32_t* runs_out /*dev [M]*/,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

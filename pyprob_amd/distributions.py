@@ -742,7 +742,7 @@ class Empirical:
         self._values.append(value)
         self._log_weights.append(0.0 if log_weight is None else float(log_weight))
         self._finalized = False
-        for k in ('_dev_cdf', '_dev_extent', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
+        for k in ('_dev_cdf', '_dev_extent', '_dev_sorted', '_fixed_mass', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
             self.__dict__.pop(k, None)
         # the statement log describes the particles of the lock-step call, not this grown set: marginal / joint must not answer
         # for the old one (statement_log itself stays readable, as before; _latent_table refuses through _log_stale)
@@ -756,6 +756,20 @@ class Empirical:
             self.add(v, None if log_weights is None else log_weights[i], None if weights is None else weights[i])
 
     def finalize(self):
+        fixed = self.__dict__.get('_fixed_mass')
+        if fixed is not None:
+            # the result of combine_duplicates on the device: the host-side weights come from the integer masses themselves, in
+            # float64 (the float32 log-weights on the device carry them to 2^-24 only)
+            mass, shift, top = fixed
+            m = mass.cpu().numpy().astype(np.float64)
+            with np.errstate(divide='ignore'):
+                self._lw = np.log(m) - shift * math.log(2.0) + top
+            self.length = len(m)
+            self._w = m / m.sum()
+            self._uniform = bool(self.length) and bool(np.all(m == m[0]))
+            self._cum = None
+            self._finalized = True
+            return self
         lw = np.asarray(self._log_weights.cpu() if torch.is_tensor(self._log_weights) else self._log_weights, np.float64)
         self._lw = lw
         self.length = len(lw)
@@ -1127,6 +1141,125 @@ class Empirical:
         row = ops.is_hist_groups(lw, cols[0], cols[1], n, torch.from_numpy(ex).to(lw.device), torch.from_numpy(ey).to(lw.device),
                                  self._group_stats_row()).cpu().numpy()[0]
         return _histogram2d_row(chosen, ex, ey, row)
+
+    # ---- order statistics (csrc/is_sort.hip) ---------------------------------------------------------------------------
+    def _device_sorted(self):
+        """(values, log-weights, index int32, counted int32 [1, 2], cumulative weights float64) of the particles in stable ascending
+        order of value on the device (pp_is_sort_groups, then pp_is_cdf_groups over the sorted log-weights): computed once per
+        object and kept like the cdf of resample - 20 bytes per particle, dropped with the object."""
+        s = self.__dict__.get('_dev_sorted')
+        if s is None:
+            from .ops import ops
+            stats = self._group_stats_row()
+            value, lw, index, counted = ops.is_sort_groups(self._log_weights, self._values, self.length, stats)
+            s = self.__dict__['_dev_sorted'] = (value, lw, index, counted, ops.is_cdf_groups(lw, self.length, stats))
+        return s
+
+    def _host_scalars(self):
+        """(log-weights, values) in float64 numpy for the host route of the order statistics; values that are not scalars: None."""
+        try:
+            x = self.values_numpy()
+        except (TypeError, ValueError, RuntimeError):
+            return np.asarray(self._lw, np.float64), None
+        lw = np.asarray(self._lw, np.float64)
+        return lw, (x if x.shape == lw.shape else None)
+
+    def quantile(self, q):
+        """The exact weighted quantile of the values by the inverted cdf, for a scalar q (a float) or a sequence (float64 numpy
+        [Q]), each in [0, 1]: with the counted particles (finite log-weight, value not NaN) in ascending order of value (ties in
+        particle order, -0.0 == +0.0), W_k the cumulative sum of exp(lw - max lw) in that order and T its last value, the value of
+        the first particle with W_k >= fl(q T) - for fl(q T) == 0 the first particle of positive cumulative weight. With uniform
+        weights quantile(0.5) is the lower of the two middle values (what median returns for uniform tensor values). Nothing
+        counted, or a total that is not positive and finite: NaN.
+
+        A device-backed Empirical (the result of a lock-step posterior call, post.marginal(address), a device resample) is sorted
+        once on the device (pp_is_sort_groups and the cumulative weights of the sorted particles, kept with the object); every
+        call is then one launch of a binary search per q (pp_is_quantile_groups) and Q doubles travel back. Every other
+        Empirical, and all of them under PP_EMPIRICAL_DEVICE=0, computes the same definition in float64 numpy (over float64
+        values: the sums agree to rounding, the value returned is one of the particles' either way)."""
+        self._check_finalized()
+        qs = np.asarray(q, np.float64)
+        scalar = qs.ndim == 0
+        qs = np.ascontiguousarray(qs.reshape(-1)) if qs.ndim <= 1 else qs
+        if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 1)):
+            raise ValueError('quantiles lie in [0, 1] (a scalar or a sequence)')
+        if self.length == 0:
+            raise ValueError('quantile of an empty Empirical')
+        if self._device_backed():
+            from .ops import ops
+            value, _, _, counted, cdf = self._device_sorted()
+            out = ops.is_quantile_groups(value, cdf, counted, self.length, torch.from_numpy(qs).to(value.device)).cpu().numpy()[0]
+        else:
+            lw, x = self._host_scalars()
+            if x is None:
+                raise ValueError('quantile needs scalar values')
+            out = _host_quantiles(lw, x, qs)
+        return float(out[0]) if scalar else out
+
+    def credible_interval(self, level=0.9):
+        """The equal-tailed interval (quantile((1 - level) / 2), quantile((1 + level) / 2)), both from one quantile call."""
+        if not 0 < level <= 1:
+            raise ValueError('level lies in (0, 1]')
+        lo, hi = self.quantile([(1.0 - level) / 2.0, (1.0 + level) / 2.0])
+        return float(lo), float(hi)
+
+    def argsort(self):
+        """The indices of the counted particles (finite log-weight, value not NaN) in stable ascending order of value: a device
+        int64 tensor for a device-backed Empirical - to gather the other latents of the statement log in value order - and an
+        int64 numpy array for every other."""
+        self._check_finalized()
+        if self.length and self._device_backed():
+            _, _, index, counted, _ = self._device_sorted()
+            return index[:int(counted[0, 0])].long()
+        lw, x = self._host_scalars()
+        if x is None:
+            raise ValueError('argsort needs scalar values')
+        return _host_order(lw, x)
+
+    def combine_duplicates(self):
+        """A new Empirical of the DISTINCT values, each under the summed weight of its particles (combine_duplicates,
+        empirical.py:809-834), metadata op='combine_duplicates'. The values ASCEND (the reference keeps the order of first
+        occurrence); particles without a finite log-weight or with a NaN value are left out; -0.0 and +0.0 are one value.
+
+        A device-backed Empirical gives a device-backed result: the runs of equal values of the sorted particles are reduced on
+        the device (pp_is_unique_groups: the histogram's 64-bit fixed point, so the same call gives the same bits) and
+        log_weight = log(mass) - S ln 2 + max lw with S = pp_is_hist_shift(length); a value whose whole mass rounds to 0 (below
+        2^-S of the heaviest particle) keeps log_weight -inf. Host-backed Empiricals with scalar values do the same in float64
+        numpy; values that are not scalars raise the reference's RuntimeError for values that are not hashable."""
+        self._check_finalized()
+        if self.length and self._device_backed():
+            from . import lib as L
+            from .ops import ops
+            value, lw, _, counted, _ = self._device_sorted()
+            uv, mass, _, runs = ops.is_unique_groups(value, lw, counted, self.length, self._group_stats_row())
+            r = int(runs[0])
+            st = self.__dict__.get('device_stats')
+            top = float(st['max_lw']) if st is not None else float(torch.where(torch.isfinite(lw), lw, lw.new_tensor(-math.inf)).max())
+            shift = L.load().pp_is_hist_shift(self.length)
+            values = uv[0, :r].contiguous()
+            new_lw = (torch.log(mass[0, :r].double()) - shift * math.log(2.0) + top).float().contiguous()
+            if r == 0:
+                out = Empirical(name=self.name)
+            else:
+                out = Empirical.from_device(values, new_lw, _device_stats(new_lw, values), name=self.name)
+                out.__dict__['_fixed_mass'] = (mass[0, :r].contiguous(), shift, top)
+            out._metadata = dict(self._metadata)
+            out.add_metadata(op='combine_duplicates', length=self.length, length_after=r)
+            return out
+        vals = self.get_values() if self.length else []
+        if not all(isinstance(v, (int, float, np.integer, np.floating)) or (torch.is_tensor(v) and v.numel() == 1) or
+                   (isinstance(v, np.ndarray) and v.size == 1) for v in vals):
+            raise RuntimeError('The values in this Empirical as not hashable. Combining of duplicates not currently supported.')
+        lw = np.asarray(self._lw, np.float64)
+        x = np.asarray([float(v) for v in vals], np.float64)
+        order = _host_order(lw, x)
+        xs, ls = x[order], lw[order]
+        heads = np.nonzero(np.concatenate([[True], xs[1:] != xs[:-1]]))[0] if len(order) else np.zeros(0, np.int64)
+        top = ls.max() if len(order) else 0.0
+        with np.errstate(divide='ignore'):
+            new_lw = np.log(np.add.reduceat(np.exp(ls - top), heads)) + top if len(order) else np.zeros(0)
+        return self._like([float(v) for v in xs[heads]], new_lw, op='combine_duplicates', length=self.length,
+                          length_after=len(heads))
 
     # ---- transformations (each returns a new Empirical) ------------------------------------------------------
     def map(self, func, min_index=None, max_index=None):
@@ -1632,6 +1765,77 @@ def histogram_batch(posteriors, bins=50, range=None, address=None):
     if column is None:
         return [(p if address is None else p.marginal(address)).histogram(bins, range) for p in posteriors]
     return _device_histograms(lw, column, N, bins, range, None, group_stats)
+
+
+def _host_order(lw, x):
+    """The indices of the particles with a finite log-weight and a value that is not NaN, in stable ascending order of value
+    (numpy compares -0.0 == +0.0: ties keep particle order) - pp_is_sort_groups' order in float64."""
+    keep = np.nonzero(np.isfinite(lw) & ~np.isnan(x))[0]
+    return keep[np.argsort(x[keep], kind='stable')].astype(np.int64)
+
+
+def _host_quantiles(lw, x, qs):
+    """pp_is_quantile_groups' definition in float64 numpy for one particle set."""
+    order = _host_order(lw, x)
+    if len(order) == 0:
+        return np.full(len(qs), np.nan)
+    l = lw[order]
+    cdf = np.cumsum(np.exp(l - np.max(lw[np.isfinite(lw)])))
+    total = cdf[-1]
+    if not (total > 0 and np.isfinite(total)):
+        return np.full(len(qs), np.nan)
+    t = qs * total
+    k = np.where(t > 0, np.searchsorted(cdf, t, side='left'), np.count_nonzero(cdf <= 0))
+    return x[order][np.minimum(k, len(order) - 1)].astype(np.float64)
+
+
+def _batch_column(posteriors, address):
+    """(lw, column, N, group statistics) where the posteriors are the M groups of ONE Model.posterior_results_batch execution in
+    order (recognised as histogram_batch recognises them) and `address` names the value forward() returned (None) or a column of
+    the call's statement log that every particle executed; else None."""
+    first = posteriors[0].__dict__.get('_batch')
+    log = posteriors[0].__dict__.get('_batch_log')
+    M = len(posteriors)
+    fast = first is not None and log is not None and first[2] is not None and first[0].numel() == M * first[4] and \
+        os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0'
+    for g, p in enumerate(posteriors):
+        b = p.__dict__.get('_batch')
+        fast = fast and b is not None and b[0] is first[0] and b[1] is first[1] and b[2] is first[2] and b[3] == g and \
+            p.__dict__.get('_batch_log') is log and p._device_backed()
+    if not fast:
+        return None
+    values, lw, group_stats, _, N = first
+    column = values
+    if address is not None:
+        a, _, rows = posteriors[0]._latent(address)
+        whole = {k: rec[0] for entry in log for k, rec in entry.items()}
+        column = whole.get(a) if rows is None else None       # (a branch's address: each group's marginal has its own particles)
+        if column is not None and (column.dtype != torch.float32 or column.numel() != lw.numel() or not column.is_contiguous()):
+            column = None
+    return None if column is None else (lw, column, N, group_stats)
+
+
+def quantile_batch(posteriors, q, address=None):
+    """numpy.stack([p.quantile(q) for p in posteriors]) as float64 [M, Q] (a scalar q: Q = 1), or with address=
+    [p.marginal(address).quantile(q) ...] - and, where the posteriors are the M groups of ONE Model.posterior_results_batch
+    execution in order, the same numbers bit for bit from ONE pp_is_sort_groups launch sequence over all groups, one
+    pp_is_cdf_groups call over the sorted log-weights, one pp_is_quantile_groups launch and one device-to-host copy. address=None:
+    the value forward() returned; else an address (or statement name) of the call's statement log that every particle executed.
+    Anything else is served by the loop."""
+    posteriors = list(posteriors)
+    qs = np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1)) if np.ndim(q) <= 1 else np.asarray(q, np.float64)
+    if qs.ndim != 1 or not np.all((qs >= 0) & (qs <= 1)):
+        raise ValueError('quantiles lie in [0, 1] (a scalar or a sequence)')
+    if not posteriors:
+        return np.zeros((0, len(qs)))
+    found = _batch_column(posteriors, address)
+    if found is None:
+        return np.stack([(p if address is None else p.marginal(address)).quantile(qs) for p in posteriors])
+    from .ops import ops
+    lw, column, N, group_stats = found
+    value, lw_sorted, _, counted = ops.is_sort_groups(lw, column, N, group_stats)
+    cdf = ops.is_cdf_groups(lw_sorted, N, group_stats)
+    return ops.is_quantile_groups(value, cdf, counted, N, torch.from_numpy(qs).to(lw.device)).cpu().numpy()
 
 
 def joint_batch(posteriors, addresses=None):

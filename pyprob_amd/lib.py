@@ -31,6 +31,7 @@ PP_IS_STATS_SCRATCH = 6144   # doubles (include/pyprob_amd.h)
 PP_IS_CDF_TILE = 2048        # particles per workgroup of pp_is_cdf_groups (include/pyprob_amd.h)
 PP_IS_MOMENTS_MAX_COLS = 16  # columns of one pp_is_moments_groups call (include/pyprob_amd.h)
 PP_IS_HIST_MAX_BINS = 2048   # bins_x * bins_y of one pp_is_hist_groups call (include/pyprob_amd.h)
+PP_IS_SORT_TILE = 2048       # particles one workgroup of pp_is_sort_groups sorts in LDS (include/pyprob_amd.h)
 
 
 def PP_IS_MOMENTS_WIDTH(n_cols):
@@ -206,6 +207,11 @@ PROTOTYPES = {
     'pp_is_hist_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, i64, vp, i32, i64, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_extent_workspace_bytes': (C.c_size_t, [i32, i32]),
     'pp_is_extent_groups': (C.c_int, [vp, vp, i32, i32, vp, vp, C.c_size_t, vp]),
+    'pp_is_sort_workspace_bytes': (C.c_size_t, [i32, i32]),
+    'pp_is_sort_groups': (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    'pp_is_quantile_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp]),
+    'pp_is_unique_workspace_bytes': (C.c_size_t, [i32, i32]),
+    'pp_is_unique_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

@@ -28,6 +28,9 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_moments_groups   weighted first and second moments of several latents per group   pyprob/distributions/empirical.py:298-309, 451-466, 668-690
     is_hist_groups      weighted 1-D / 2-D histogram of a latent (pair) per group, fixed point   pyprob/distributions/empirical.py:298-309, 889-914
     is_extent_groups    minimum, maximum and NaN count of a latent per group             pyprob/distributions/empirical.py:770-794
+    is_sort_groups      the particles of every group in order of value (stable radix sort)   pyprob/distributions/empirical.py:714-728, 809-834
+    is_quantile_groups  exact weighted quantiles over the sorted particles (inverted cdf)     pyprob/distributions/empirical.py:714-728
+    is_unique_groups    distinct values with fixed-point masses and counts (combine_duplicates)   pyprob/distributions/empirical.py:809-834
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -84,6 +87,10 @@ _lib.define('is_resample_groups(Tensor cdf, Tensor? values, int n_per, int lo, i
 _lib.define('is_moments_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? stats) -> Tensor')
 _lib.define('is_hist_groups(Tensor lw, Tensor x, Tensor? y, int n_per, Tensor edges_x, Tensor? edges_y, Tensor? stats) -> Tensor')
 _lib.define('is_extent_groups(Tensor lw, Tensor x, int n_per) -> Tensor')
+_lib.define('is_sort_groups(Tensor lw, Tensor x, int n_per, Tensor? stats) -> (Tensor, Tensor, Tensor, Tensor)')
+_lib.define('is_quantile_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor q) -> Tensor')
+_lib.define('is_unique_groups(Tensor value_sorted, Tensor lw_sorted, Tensor counted, int n_per, Tensor? stats) -> '
+            '(Tensor, Tensor, Tensor, Tensor)')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
@@ -821,6 +828,85 @@ def _is_extent_groups_hip(lw, x, n_per):
     return out
 
 
+def _group_stats_ok(stats, M, what):
+    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
+        raise RuntimeError('pyprob_hip::%s: stats must be a contiguous float64 tensor of [M, 6]' % what)
+
+
+def _counted_ok(counted, M, what):
+    if counted.dtype != torch.int32 or not counted.is_contiguous() or counted.numel() != 2 * M:
+        raise RuntimeError('pyprob_hip::%s: counted must be the contiguous int32 [M, 2] tensor of is_sort_groups' % what)
+
+
+def _is_sort_groups_hip(lw, x, n_per, stats):
+    """(value float32 [M n_per], lw float32 [M n_per], index int32 [M n_per], counted int32 [M, 2]): the particles of each of the M
+    groups in stable ascending order of the key of x (pp_is_sort_groups); counted[g] = {particles with a real key, particles with a
+    finite log-weight whose x is NaN}. stats: as for is_cdf_groups (the outputs do not depend on it)."""
+    lib = L.load()
+    _same_device(lw, x, stats)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_sort_groups')
+    if _f32(x, 'x').dim() != 1 or x.numel() != lw.numel() or not x.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_sort_groups: x must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    _group_stats_ok(stats, M, 'is_sort_groups')
+    value, lw_out = torch.empty_like(x), torch.empty_like(lw)
+    index = torch.empty(lw.numel(), dtype=torch.int32, device=lw.device)
+    counted = torch.empty((M, 2), dtype=torch.int32, device=lw.device)
+    need = lib.pp_is_sort_workspace_bytes(M, int(n_per))
+    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_sort_groups(lw.data_ptr(), x.data_ptr(), M, int(n_per), L.ptr(stats), value.data_ptr(), lw_out.data_ptr(),
+                                   index.data_ptr(), counted.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_sort_groups')
+    return value, lw_out, index, counted
+
+
+def _is_quantile_groups_hip(value_sorted, cdf_sorted, counted, n_per, q):
+    """[M, Q] (float64): the inverted-cdf quantiles q (float64 [Q] in [0, 1], shared by the groups) of each of the M groups of n_per
+    sorted particles (pp_is_quantile_groups); cdf_sorted = is_cdf_groups over the sorted log-weights."""
+    lib = L.load()
+    _same_device(value_sorted, cdf_sorted, counted, q)
+    M = _groups_of(_f32(value_sorted, 'value_sorted'), n_per, 'is_quantile_groups')
+    if cdf_sorted.dtype != torch.float64 or cdf_sorted.dim() != 1 or cdf_sorted.numel() != value_sorted.numel() or \
+            not cdf_sorted.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_quantile_groups: cdf_sorted must be a contiguous float64 tensor of the values\' '
+                           'M * n_per elements (is_cdf_groups)')
+    _counted_ok(counted, M, 'is_quantile_groups')
+    if q.dtype != torch.float64 or q.dim() != 1 or not q.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_quantile_groups: q must be a contiguous 1-D float64 tensor')
+    Q = int(q.numel())
+    out = torch.empty((M, Q), dtype=torch.float64, device=value_sorted.device)
+    with torch.cuda.device(value_sorted.device):
+        rc = lib.pp_is_quantile_groups(value_sorted.data_ptr(), cdf_sorted.data_ptr(), counted.data_ptr(), M, int(n_per),
+                                       q.data_ptr(), Q, out.data_ptr(), _stream(value_sorted))
+    L.check(rc, 'pp_is_quantile_groups')
+    return out
+
+
+def _is_unique_groups_hip(value_sorted, lw_sorted, counted, n_per, stats):
+    """(value float32 [M, n_per], mass int64 [M, n_per], count int32 [M, n_per], runs int32 [M]): the runs of equal keys among the
+    counted sorted particles of each group (pp_is_unique_groups); entries at or beyond runs[g] are not written."""
+    lib = L.load()
+    _same_device(value_sorted, lw_sorted, counted, stats)
+    M = _groups_of(_f32(value_sorted, 'value_sorted'), n_per, 'is_unique_groups')
+    if _f32(lw_sorted, 'lw_sorted').dim() != 1 or lw_sorted.numel() != value_sorted.numel() or not lw_sorted.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_unique_groups: lw_sorted must be a contiguous 1-D tensor of the values\' M * n_per elements')
+    _counted_ok(counted, M, 'is_unique_groups')
+    _group_stats_ok(stats, M, 'is_unique_groups')
+    dev = value_sorted.device
+    value = torch.empty((M, int(n_per)), dtype=torch.float32, device=dev)
+    mass = torch.empty((M, int(n_per)), dtype=torch.int64, device=dev)
+    count = torch.empty((M, int(n_per)), dtype=torch.int32, device=dev)
+    runs = torch.empty(M, dtype=torch.int32, device=dev)
+    need = lib.pp_is_unique_workspace_bytes(M, int(n_per))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_unique_groups(value_sorted.data_ptr(), lw_sorted.data_ptr(), counted.data_ptr(), M, int(n_per), L.ptr(stats),
+                                     value.data_ptr(), mass.data_ptr(), count.data_ptr(), runs.data_ptr(), ws.data_ptr(), need,
+                                     _stream(value_sorted))
+    L.check(rc, 'pp_is_unique_groups')
+    return value, mass, count, runs
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -843,6 +929,9 @@ _lib.impl('is_resample_groups', _is_resample_groups_hip, 'CUDA')
 _lib.impl('is_moments_groups', _is_moments_groups_hip, 'CUDA')
 _lib.impl('is_hist_groups', _is_hist_groups_hip, 'CUDA')
 _lib.impl('is_extent_groups', _is_extent_groups_hip, 'CUDA')
+_lib.impl('is_sort_groups', _is_sort_groups_hip, 'CUDA')
+_lib.impl('is_quantile_groups', _is_quantile_groups_hip, 'CUDA')
+_lib.impl('is_unique_groups', _is_unique_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
