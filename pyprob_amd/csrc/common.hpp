@@ -144,6 +144,27 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// The same pattern for a double, as two 32-bit halves (__shfl_xor of a double is two ds_bpermute per step, 12 per sum): a fixed
+// order, (0 + 16) + (32 + 48) over the four row totals; every lane ends with the total.
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov(double v) {
+    const uint64_t u = __double_as_longlong(v);
+    const uint32_t lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xF, 0xF, false);
+    const uint32_t hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, false);
+    return __longlong_as_double(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane_bcast(double v, int lane) {
+    const uint64_t u = __double_as_longlong(v);
+    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)u, lane), hi = __builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+    return __longlong_as_double(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_dpp(double v) {
+    v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
+    v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
+    v += dpp_mov<0x124>(v);   // row_ror:4
+    v += dpp_mov<0x128>(v);   // row_ror:8
+    return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
+}
 
 // Touch every 64-byte line of the kernel-argument segment with ONE vector load per workgroup wave: the host wrote the
 // arguments just before the launch, so each line's first scalar load is an HBM-latency miss (~1-2 us); a kernel with a

@@ -3,8 +3,8 @@
 // The reference normalises the weights of an Empirical on the host (pyprob/distributions/empirical.py:298-309) and draws its
 // histogram from all values and weights on the host (plot_histogram, :889-914). Here
 //   pp_is_hist_groups    writes, per group g of n_per particles, the row [2][slots] of 64-bit integers: the fixed-point mass
-//       sum_i llrint(w_i 2^S) and the particle count of every slot, w = exp((double)lw - max_g) in fp64, S = 62 - ceil(log2 n_per)
-//       (a group's total is at most n_per 2^S <= 2^62). Slots, 1-D: [bins ..., below, above, x is NaN]; 2-D: [ix bins_y + iy ...,
+//       sum_i llrint(w_i 2^S) and the particle count of every slot (is_groups.hpp: which particles count, the clamped weight w
+//       and the shift S). Slots, 1-D: [bins ..., below, above, x is NaN]; 2-D: [ix bins_y + iy ...,
 //       outside, either coordinate NaN]. Bin b holds e_b <= x < e_{b+1}, the last bin also x == e_last (numpy.histogram's rule),
 //       found by binary search over the edges staged in LDS: non-uniform edges cost the same as uniform ones, and the bin is a
 //       function of the very array the host shows the user.
@@ -19,13 +19,9 @@
 //
 // ORDER. Integer sums, minima and maxima do not depend on the order they are taken in: a call repeated gives the same bits, group g
 // of an M-group call carries the bits of the one-group call on its slice, and the tile size is free to change. (fp64 accumulators
-// would need a fixed order for that, and float atomics have none.) A particle whose log-weight is not finite is SKIPPED: its x / y
-// (uninitialised rows of a diverged path) are loaded, but whatever they hold selects no slot and enters no count.
-#include "common.hpp"
-
-#include <math.h>
-
-#include <algorithm>
+// would need a fixed order for that, and float atomics have none.) The x / y of a skipped particle are loaded, but whatever they
+// hold selects no slot and enters no count.
+#include "is_groups.hpp"
 
 namespace pp {
 namespace {
@@ -39,9 +35,7 @@ constexpr int PER_THREAD = 8;
 constexpr int SMALL_BINS = 256, SMALL_THREADS = 256, LARGE_THREADS = 1024;
 constexpr int EXTENT_TILE = 256 * PER_THREAD;
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
 inline int tile_for(int bins) { return (bins <= SMALL_BINS ? SMALL_THREADS : LARGE_THREADS) * PER_THREAD; }
-inline int tiles_of(int n_per, int tile) { return cdiv(n_per, tile); }
 inline int slots_of(int bx, int by, bool two_d) { return two_d ? bx * by + 2 : bx + 3; }
 
 // Workspace: one partial row (2 slots int64) per (group, tile) where a group has more than one tile, one float (the tile's maximum)
@@ -52,14 +46,13 @@ struct HistWorkspace {
     size_t bytes;
 };
 void hist_carve(int M, int n_per, int bins, void* p, HistWorkspace& w) {      // (bins + 3 slots cover the 1-D and the 2-D row)
-    char* base = static_cast<char*>(p);
+    Carver c(p);
     const int slots = bins + 3;
     const int T = tiles_of(std::max(n_per, 1), tile_for(bins));
     const int64_t tiles = (int64_t)std::max(M, 0) * T;
-    const int64_t rows = align256(T > 1 ? tiles * 2 * slots * 8 : 0);
-    w.partial = reinterpret_cast<int64_t*>(base);
-    w.tmax = reinterpret_cast<float*>(base ? base + rows : nullptr);
-    w.bytes = (size_t)(256 + rows + align256(tiles * 4));
+    w.partial = c.take<int64_t>(T > 1 ? tiles * 2 * slots * 8 : 0);
+    w.tmax = c.take<float>(tiles * 4);
+    w.bytes = c.bytes();
 }
 
 struct ExtentPartial {
@@ -69,34 +62,6 @@ struct ExtentPartial {
 size_t extent_bytes(int M, int n_per) {
     const int T = tiles_of(std::max(n_per, 1), EXTENT_TILE);
     return (size_t)(256 + align256(T > 1 ? (int64_t)std::max(M, 0) * T * (int64_t)sizeof(ExtentPartial) : 0));
-}
-
-template <int THREADS>
-__device__ __forceinline__ float block_max(float m, float* shmax) {
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) shmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    float r = shmax[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) r = fmaxf(r, shmax[w]);
-    return r;
-}
-
-// The maximum of the finite log-weights of tile blockIdx.x of group g0 + blockIdx.y (groups of more than one tile, no statistics
-// given). A maximum does not depend on the order it is taken in.
-__global__ __launch_bounds__(256) void hist_tile_max_kernel(const float* __restrict__ lw, int n_per, int tile, int T, int g0,
-                                                            float* __restrict__ tmax) {
-    __shared__ float shmax[4];
-    const int64_t g = (int64_t)g0 + blockIdx.y;
-    const float* l = lw + g * n_per;
-    const int64_t lo = (int64_t)blockIdx.x * tile, hi = min((int64_t)n_per, lo + tile);
-    float m = -INFINITY;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
-        const float a = l[j];
-        if (isfinite(a)) m = fmaxf(m, a);
-    }
-    m = block_max<256>(m, shmax);
-    if (threadIdx.x == 0) tmax[g * T + blockIdx.x] = m;
 }
 
 // The bins of the eight values v[k] in the n = nb + 1 strictly increasing edges e (LDS): pos = the number of edges <= v, found by
@@ -151,30 +116,16 @@ __global__ __launch_bounds__(THREADS) void hist_tile_kernel(const float* __restr
     const int64_t base = g * n_per;
     const float* l = lw + base;
     const int64_t first = (int64_t)blockIdx.x * (THREADS * PER_THREAD) + tid;
-    // the group's maximum: what pp_is_stats / pp_is_fused_groups reduced, or the maximum of the finite log-weights found here
-    double M;
-    if (stats) {
-        M = stats[6 * g];
-    } else {
-        float m = -INFINITY;
-        if (T == 1) {
-            for (int64_t j = tid; j < n_per; j += THREADS) {
-                const float a = l[j];
-                if (isfinite(a)) m = fmaxf(m, a);
-            }
-        } else {
-            for (int t = tid; t < T; t += THREADS) m = fmaxf(m, tmax[g * T + t]);
-        }
-        M = (double)block_max<THREADS>(m, shmax);
-    }
-    const bool any = M > -INFINITY && M < INFINITY;      // (no finite log-weight: every particle is skipped)
-    __syncthreads();
     float a[PER_THREAD], xv[PER_THREAD], yv[PER_THREAD];
+#pragma unroll
+    for (int k = 0; k < PER_THREAD; ++k) a[k] = first + THREADS * k < n_per ? l[first + THREADS * k] : -INFINITY;
+    const double M = group_max<THREADS>(stats, tmax, g, T, a, shmax);      // (one tile: the workgroup's own particles are the group)
+    const bool any = group_any(M);
+    __syncthreads();
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) {
         const int64_t i = first + THREADS * k;
         const bool in = i < n_per;
-        a[k] = in ? l[i] : -INFINITY;
         xv[k] = in ? x[base + i] : 0.0f;
         yv[k] = (in && two_d) ? y[base + i] : 0.0f;
     }
@@ -184,9 +135,8 @@ __global__ __launch_bounds__(THREADS) void hist_tile_kernel(const float* __restr
     if (two_d) bins_of(edge_y, by, yv, iy);
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) {
-        if (!(any && isfinite(a[k]))) continue;      // (a skipped particle is in no slot and no count)
-        const double w = fmin(exp((double)a[k] - M), 1.0);
-        const unsigned long long q = (unsigned long long)llrint(w * scale);
+        if (!particle_counted(a[k], any)) continue;      // (a skipped particle is in no slot and no count)
+        const unsigned long long q = fixed_mass(particle_weight_clamped(a[k], M, any), scale);
         int slot;
         if (!two_d) {
             slot = xv[k] != xv[k] ? bx + 2 : ix[k] < 0 ? bx : ix[k] == bx ? bx + 1 : ix[k];
@@ -212,25 +162,7 @@ __global__ __launch_bounds__(256) void hist_combine_kernel(const int64_t* __rest
     const int64_t g = (int64_t)g0 + blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= width) return;
-    const int64_t* p = partial + g * T * width + e;
-    int64_t acc = 0;
-    int t = 0;
-    for (; t + 32 <= T; t += 32) {      // (32 loads in flight)
-        int64_t u[32];
-#pragma unroll
-        for (int q = 0; q < 32; ++q) u[q] = p[(int64_t)(t + q) * width];
-#pragma unroll
-        for (int q = 0; q < 32; ++q) acc += u[q];
-    }
-    for (; t + 4 <= T; t += 4) {
-        int64_t u[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) u[q] = p[(int64_t)(t + q) * width];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc += u[q];
-    }
-    for (; t < T; ++t) acc += p[(int64_t)t * width];
-    out[g * width + e] = acc;
+    out[g * width + e] = add_rows(int64_t(0), partial + g * T * width + e, (int64_t)width, 0, T);
 }
 
 // min / max of x and the two counts over tile blockIdx.x of group g0 + blockIdx.y; a group of one tile writes its output row.
@@ -330,16 +262,8 @@ __global__ __launch_bounds__(256) void extent_combine_kernel(const ExtentPartial
     }
 }
 
-int hist_shift(int n_per) {
-    if (n_per < 1) return -1;
-    int c = 0;
-    while ((int64_t(1) << c) < n_per) ++c;
-    return 62 - c;
-}
-
 bool hist_shape_ok(int M, int n_per, int bx, int by) {
-    return M >= 0 && n_per >= 1 && (int64_t)M * n_per <= 0x7fffffff && bx >= 1 && by >= 1 &&
-           (int64_t)bx * by <= PP_IS_HIST_MAX_BINS;
+    return groups_shape_ok(M, n_per) && bx >= 1 && by >= 1 && (int64_t)bx * by <= PP_IS_HIST_MAX_BINS;
 }
 
 }  // namespace
@@ -347,8 +271,7 @@ bool hist_shape_ok(int M, int n_per, int bx, int by) {
 int is_hist_groups(const float* lw, const float* x, const float* y, int M, int n_per, const double* ex, int bx, int64_t sx,
                    const double* ey, int by, int64_t sy, const double* stats, int64_t* out, void* ws, size_t ws_bytes, hipStream_t st) {
     PP_CHECK_ARG(lw && x && ex && out && ws, "pp_is_hist_groups: null pointer (lw, x, edges_x, out and the workspace are required)");
-    PP_CHECK_ARG(n_per >= 1 && M >= 0, "pp_is_hist_groups: n_per >= 1 and n_groups >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff, "pp_is_hist_groups: more than 2^31 - 1 particles per call: shard the groups");
+    PP_CHECK_GROUPS("pp_is_hist_groups", M, n_per);
     PP_CHECK_ARG(bx >= 1 && by >= 1 && (int64_t)bx * by <= PP_IS_HIST_MAX_BINS,
                  "pp_is_hist_groups: bins_x >= 1, bins_y >= 1 and bins_x * bins_y <= %d", PP_IS_HIST_MAX_BINS);
     PP_CHECK_ARG((y != nullptr) == (ey != nullptr), "pp_is_hist_groups: y and edges_y are given together (2-D) or not at all (1-D)");
@@ -359,18 +282,14 @@ int is_hist_groups(const float* lw, const float* x, const float* y, int M, int n
     const int slots = slots_of(bx, by, two_d);
     HistWorkspace w;
     hist_carve(M, n_per, bx * by, ws, w);      // (one size for 1-D and 2-D: pp_is_hist_workspace_bytes does not know which)
-    if (w.bytes > ws_bytes) {
-        set_error("pp_is_hist_groups: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
-        return PP_ENOSPACE;
-    }
+    PP_CHECK_WORKSPACE("pp_is_hist_groups", ws_bytes, w.bytes);
     if (M == 0) return 0;
     const int tile = tile_for(bx * by), T = tiles_of(n_per, tile), width = 2 * slots;
     const int ne = bx + 1 + (two_d ? by + 1 : 0);
     const size_t lds = (size_t)slots * 12 + (size_t)ne * 8;
-    const double scale = ldexp(1.0, hist_shift(n_per));
-    for (int g0 = 0; g0 < M; g0 += 65535) {
-        const int groups = std::min(65535, M - g0);
-        if (T > 1 && !stats) hipLaunchKernelGGL(hist_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, tile, T, g0, w.tmax);
+    const double scale = hist_scale(n_per);
+    for_each_group_chunk(M, [&](int g0, int groups) {
+        if (T > 1 && !stats) hipLaunchKernelGGL(group_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, tile, T, g0, w.tmax);
         int64_t* dst = T > 1 ? w.partial : out;
         if (tile == SMALL_THREADS * PER_THREAD)
             hipLaunchKernelGGL(hist_tile_kernel<SMALL_THREADS>, dim3(T, groups), dim3(SMALL_THREADS), lds, st, lw, x, y, n_per, T, g0, ex, bx,
@@ -381,29 +300,23 @@ int is_hist_groups(const float* lw, const float* x, const float* y, int M, int n
         if (T > 1)
             hipLaunchKernelGGL(hist_combine_kernel, dim3(cdiv(width, 256), groups), dim3(256), 0, st, (const int64_t*)w.partial, width,
                                T, g0, out);
-    }
+    });
     PP_LAUNCH_CHECK("pp_is_hist_groups");
     return 0;
 }
 
 int is_extent_groups(const float* lw, const float* x, int M, int n_per, double* out, void* ws, size_t ws_bytes, hipStream_t st) {
     PP_CHECK_ARG(lw && x && out && ws, "pp_is_extent_groups: null pointer (lw, x, out and the workspace are required)");
-    PP_CHECK_ARG(n_per >= 1 && M >= 0, "pp_is_extent_groups: n_per >= 1 and n_groups >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff, "pp_is_extent_groups: more than 2^31 - 1 particles per call: shard the groups");
-    const size_t need = extent_bytes(M, n_per);
-    if (need > ws_bytes) {
-        set_error("pp_is_extent_groups: workspace too small (%zu < %zu bytes)", ws_bytes, need);
-        return PP_ENOSPACE;
-    }
+    PP_CHECK_GROUPS("pp_is_extent_groups", M, n_per);
+    PP_CHECK_WORKSPACE("pp_is_extent_groups", ws_bytes, extent_bytes(M, n_per));
     if (M == 0) return 0;
     const int T = tiles_of(n_per, EXTENT_TILE);
     ExtentPartial* partial = static_cast<ExtentPartial*>(ws);
-    for (int g0 = 0; g0 < M; g0 += 65535) {
-        const int groups = std::min(65535, M - g0);
+    for_each_group_chunk(M, [&](int g0, int groups) {
         hipLaunchKernelGGL(extent_tile_kernel, dim3(T, groups), dim3(256), 0, st, lw, x, n_per, T, g0, partial, out);
         if (T > 1)
             hipLaunchKernelGGL(extent_combine_kernel, dim3(groups), dim3(256), 0, st, (const ExtentPartial*)partial, T, g0, out);
-    }
+    });
     PP_LAUNCH_CHECK("pp_is_extent_groups");
     return 0;
 }
@@ -429,7 +342,7 @@ int pp_is_hist_groups(const float* lw, const float* x, const float* y, int32_t n
 }
 
 size_t pp_is_extent_workspace_bytes(int32_t n_groups, int32_t n_per) {
-    if (n_groups < 0 || n_per < 1 || (int64_t)n_groups * n_per > 0x7fffffff) return 0;
+    if (!pp::groups_shape_ok(n_groups, n_per)) return 0;
     return pp::extent_bytes(n_groups, n_per);
 }
 

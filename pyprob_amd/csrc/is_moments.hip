@@ -5,7 +5,7 @@
 // expectations (:668-690); the posterior of another latent of the same particles is posterior.map(...) followed by those. Here
 //   pp_is_moments_groups  writes, per group g of n_per particles, the row
 //       max lw, W = sum w, sum w^2, count of finite lw | c_j | S_j = sum w (x_j - c_j) | Q_jk = sum w (x_j - c_j)(x_k - c_k), j <= k
-//   with w = exp((double)lw - max_g) in fp64 and the pivot c_j = x_j[g, 0] (0 where that is not finite). The host forms
+//   with the particle's weight w (is_groups.hpp: which particles count and what they weigh) and the pivot c_j = x_j[g, 0] (0 where that is not finite). The host forms
 //   mean_j = c_j + S_j / W and cov_jk = Q_jk / W - (S_j / W)(S_k / W): sums about a pivot keep a narrow posterior far from zero
 //   accurate where raw second moments cancel.
 //
@@ -17,15 +17,11 @@
 // no workgroup waits for another: the launches are dependent launches on the caller's stream.
 //
 // ORDER OF THE SUMS. A lane adds its eight particles (tile offset + 256 k + thread) in the order of k, the 64 lanes of a wave
-// meet by lane exchanges of doubles in a fixed pattern (wave_sum_dpp), the four waves in LDS as ((0 + 1) + 2) + 3, the tiles in
+// meet by lane exchanges of doubles in a fixed pattern (wave_sum_dpp, common.hpp), the four waves in LDS as ((0 + 1) + 2) + 3, the tiles in
 // index order. The order is a function of n_per and n_cols alone: group g of an M-group call carries the bits of the one-group
-// call on the same particles, and a call repeated gives the same bits. A particle whose log-weight is not finite is SKIPPED - its
-// column values (uninitialised rows of a diverged path) are read but enter no product.
-#include "common.hpp"
-
-#include <math.h>
-
-#include <algorithm>
+// call on the same particles, and a call repeated gives the same bits. The column values of a skipped particle are read but enter
+// no product.
+#include "is_groups.hpp"
 
 namespace pp {
 namespace {
@@ -42,8 +38,6 @@ struct MomentCols {
     const float* p[PP_IS_MOMENTS_MAX_COLS];
 };
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-inline int tiles_of(int n_per) { return cdiv(n_per, TILE); }
 __host__ __device__ inline int blocks_of(int J) { return (J + BLK - 1) / BLK; }
 inline int pairs_of(int J) { return blocks_of(J) * (blocks_of(J) + 1) / 2; }
 // block pairs (bi <= bj) in row-major order of the upper triangle
@@ -56,61 +50,14 @@ struct MomentsWorkspace {
     size_t bytes;
 };
 void moments_carve(int M, int n_per, int J, void* p, MomentsWorkspace& w) {
-    char* base = static_cast<char*>(p);
-    const int64_t slots = (int64_t)std::max(M, 0) * tiles_of(std::max(n_per, 1));
-    const int64_t rows = align256(slots * pairs_of(J) * SLOTS * 8);
-    w.partial = reinterpret_cast<double*>(base);
-    w.tmax = reinterpret_cast<float*>(base ? base + rows : nullptr);
-    w.bytes = (size_t)(256 + rows + align256(slots * 4));
+    Carver c(p);
+    const int64_t slots = (int64_t)std::max(M, 0) * tiles_of(std::max(n_per, 1), TILE);
+    w.partial = c.take<double>(slots * pairs_of(J) * SLOTS * 8);
+    w.tmax = c.take<float>(slots * 4);
+    w.bytes = c.bytes();
 }
 
-// The 64 lanes of a wave added on the VALU (DPP), not through the LDS crossbar (__shfl_xor of a double is two ds_bpermute per
-// step, 12 per sum, and a workgroup reduces 23 sums): quad_perm for lanes xor 1 and xor 2, row_ror 4 and 8 for the 16-lane row,
-// then the four row totals by v_readlane as (0 + 16) + (32 + 48). A fixed order; every lane ends with the total.
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double v) {
-    const uint64_t u = __double_as_longlong(v);
-    const uint32_t lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, 0xF, 0xF, false);
-    const uint32_t hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double lane_bcast(double v, int lane) {
-    const uint64_t u = __double_as_longlong(v);
-    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)u, lane), hi = __builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-    return __longlong_as_double(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum_dpp(double v) {
-    v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-    v += dpp_mov<0x124>(v);   // row_ror:4
-    v += dpp_mov<0x128>(v);   // row_ror:8
-    return (lane_bcast(v, 0) + lane_bcast(v, 16)) + (lane_bcast(v, 32) + lane_bcast(v, 48));
-}
-
-__device__ __forceinline__ float block_max(float m, float* shmax) {
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) shmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    return fmaxf(fmaxf(shmax[0], shmax[1]), fmaxf(shmax[2], shmax[3]));
-}
-
-// Step 0 (groups of more than one tile, no statistics given): the maximum of the finite log-weights of tile blockIdx.x of group
-// g0 + blockIdx.y. A maximum does not depend on the order it is taken in: the tile kernel combines the tile maxima of its group.
-__global__ __launch_bounds__(256) void moments_tile_max_kernel(const float* __restrict__ lw, int n_per, int T, int g0,
-                                                               float* __restrict__ tmax) {
-    __shared__ float shmax[4];
-    const int64_t g = (int64_t)g0 + blockIdx.y;
-    const float* l = lw + g * n_per;
-    const int64_t lo = (int64_t)blockIdx.x * TILE, hi = min((int64_t)n_per, lo + TILE);
-    float m = -INFINITY;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
-        const float a = l[j];
-        if (isfinite(a)) m = fmaxf(m, a);
-    }
-    m = block_max(m, shmax);
-    if (threadIdx.x == 0) tmax[g * T + blockIdx.x] = m;
-}
-
+// Step 0 (groups of more than one tile, no statistics given): group_tile_max_kernel.
 // Step 1: workgroup (tile blockIdx.x, block pair blockIdx.y, group g0 + blockIdx.z) stores its partial row.
 __global__ __launch_bounds__(256) void moments_tile_kernel(const float* __restrict__ lw, MomentCols cols, int J, int n_per, int T,
                                                            int g0, const double* __restrict__ stats,
@@ -133,22 +80,8 @@ __global__ __launch_bounds__(256) void moments_tile_kernel(const float* __restri
     float a[PER_THREAD];
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) a[k] = first + 256 * k < n_per ? l[first + 256 * k] : -INFINITY;
-    // the group's maximum: what pp_is_stats / pp_is_fused_groups reduced, or the maximum of the finite log-weights found here
-    double M;
-    if (stats) {
-        M = stats[6 * g];
-    } else {
-        float m = -INFINITY;
-        if (T == 1) {
-#pragma unroll
-            for (int k = 0; k < PER_THREAD; ++k)
-                if (isfinite(a[k])) m = fmaxf(m, a[k]);
-        } else {
-            for (int t = tid; t < T; t += 256) m = fmaxf(m, tmax[g * T + t]);
-        }
-        M = (double)block_max(m, shmax);
-    }
-    const bool any = M > -INFINITY && M < INFINITY;      // (no finite log-weight: every particle is skipped)
+    const double M = group_max<256>(stats, tmax, g, T, a, shmax);
+    const bool any = group_any(M);
     // the columns of the two blocks and their pivots: the group's first value where that is finite, else 0
     const float* pa[BLK];
     const float* pb[BLK];
@@ -179,8 +112,8 @@ __global__ __launch_bounds__(256) void moments_tile_kernel(const float* __restri
             xa[q] = (in && pa[q]) ? pa[q][i] : 0.0f;
             xb[q] = (in && pb[q] && !diag) ? pb[q][i] : 0.0f;
         }
-        if (any && isfinite(a[k])) {      // (a skipped particle's values enter no product: 0 * NaN never reaches a sum)
-            const double w = exp((double)a[k] - M);
+        if (particle_counted(a[k], any)) {      // (a skipped particle's values enter no product: 0 * NaN never reaches a sum)
+            const double w = particle_weight(a[k], M, any);
             if (diag) {      // (W, W2, count and S are read from diagonal pairs only: an off-diagonal pair sums its Q alone)
                 W += w;
                 W2 += w * w;
@@ -263,26 +196,7 @@ __global__ __launch_bounds__(256) void moments_combine_kernel(const double* __re
             slot = BLK * (j % BLK) + k % BLK;
         }
         const double* p = rows + (int64_t)pair * SLOTS + slot;
-        double acc = p[0];
-        if (summed) {
-            int t = 1;
-            for (; t + 32 <= T; t += 32) {      // (32 loads in flight, added in tile order)
-                double u[32];
-#pragma unroll
-                for (int q = 0; q < 32; ++q) u[q] = p[(t + q) * stride];
-#pragma unroll
-                for (int q = 0; q < 32; ++q) acc += u[q];
-            }
-            for (; t + 4 <= T; t += 4) {
-                double u[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) u[q] = p[(t + q) * stride];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc += u[q];
-            }
-            for (; t < T; ++t) acc += p[t * stride];
-        }
-        out[g * width + e] = acc;
+        out[g * width + e] = summed ? add_rows(p[0], p, stride, 1, T) : p[0];      // (in tile order)
     }
 }
 
@@ -292,8 +206,7 @@ int is_moments_groups(const float* lw, const float* const* cols, int J, int M, i
                       size_t ws_bytes, hipStream_t st) {
     PP_CHECK_ARG(lw && cols && out && ws, "pp_is_moments_groups: null pointer (lw, cols, out and the workspace are required)");
     PP_CHECK_ARG(J >= 1 && J <= PP_IS_MOMENTS_MAX_COLS, "pp_is_moments_groups: n_cols in 1 .. %d", PP_IS_MOMENTS_MAX_COLS);
-    PP_CHECK_ARG(n_per >= 1 && M >= 0, "pp_is_moments_groups: n_per >= 1 and n_groups >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff, "pp_is_moments_groups: more than 2^31 - 1 particles per call: shard the groups");
+    PP_CHECK_GROUPS("pp_is_moments_groups", M, n_per);
     MomentCols c;
     for (int j = 0; j < PP_IS_MOMENTS_MAX_COLS; ++j) {
         c.p[j] = j < J ? cols[j] : nullptr;
@@ -301,20 +214,16 @@ int is_moments_groups(const float* lw, const float* const* cols, int J, int M, i
     }
     MomentsWorkspace w;
     moments_carve(M, n_per, J, ws, w);
-    if (w.bytes > ws_bytes) {
-        set_error("pp_is_moments_groups: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
-        return PP_ENOSPACE;
-    }
+    PP_CHECK_WORKSPACE("pp_is_moments_groups", ws_bytes, w.bytes);
     if (M == 0) return 0;
-    const int T = tiles_of(n_per), P = pairs_of(J);
-    for (int g0 = 0; g0 < M; g0 += 65535) {
-        const int groups = std::min(65535, M - g0);
+    const int T = tiles_of(n_per, TILE), P = pairs_of(J);
+    for_each_group_chunk(M, [&](int g0, int groups) {
         if (T > 1 && !stats)
-            hipLaunchKernelGGL(moments_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, T, g0, w.tmax);
+            hipLaunchKernelGGL(group_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, TILE, T, g0, w.tmax);
         hipLaunchKernelGGL(moments_tile_kernel, dim3(T, P, groups), dim3(256), 0, st, lw, c, J, n_per, T, g0, stats,
                            (const float*)w.tmax, w.partial);
         hipLaunchKernelGGL(moments_combine_kernel, dim3(groups), dim3(256), 0, st, (const double*)w.partial, J, T, P, g0, out);
-    }
+    });
     PP_LAUNCH_CHECK("pp_is_moments_groups");
     return 0;
 }

@@ -4,7 +4,8 @@
 // The reference keeps the normalised weights of an Empirical on the host (finalize, pyprob/distributions/empirical.py:298-309),
 // draws ONE index per call from a Categorical over them (sample, :392-408) and resamples by calling sample() num_samples times
 // (resample, :617-637). Here
-//   pp_is_cdf_groups       writes cdf[g, i] = sum_{j <= i} exp(lw[g, j] - max_g) in fp64 (0 for a non-finite log-weight), and
+//   pp_is_cdf_groups       writes cdf[g, i] = the sum of the weights of particles 0 .. i of group g in fp64 (is_groups.hpp: what
+//                          a particle weighs and which particles weigh nothing), and
 //   pp_is_resample_groups  draws n_out indices per group by inverting that cdf at Philox uniforms of 53 bits, one thread per draw.
 //
 // ORDER OF THE SUMS. cdf[g, i] is built as  tile offset + (wave offset + (lane offset + running sum of the thread's own eight)),
@@ -15,12 +16,8 @@
 // agree on it and a particle of weight 0 is not selected. The order is a function of n_per alone: group g of an M-group call
 // carries the bits of the one-group call on the same particles, and a call repeated gives the same bits. No workgroup waits for
 // another inside a kernel and nothing is accumulated with atomics: the three steps are dependent launches on the caller's stream.
-#include "common.hpp"
 #include "is_draw.hpp"
-
-#include <math.h>
-
-#include <algorithm>
+#include "is_groups.hpp"
 
 namespace pp {
 namespace {
@@ -30,8 +27,6 @@ constexpr int PER_THREAD = 8;
 static_assert(TILE == 256 * PER_THREAD, "a tile is 256 threads of eight particles");
 constexpr int RESAMPLE_BLOCKS = 2048;     // workgroups of the draw kernel at most (8 per CU)
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-inline int tiles_of(int n_per) { return cdiv(n_per, TILE); }
 
 // Workspace of pp_is_cdf_groups: one double (tile total, then tile offset) and one float (tile maximum) per tile of every group
 // with more than one tile; a one-tile group needs neither.
@@ -41,38 +36,15 @@ struct CdfWorkspace {
     size_t bytes;
 };
 void cdf_carve(int M, int n_per, void* p, CdfWorkspace& w) {
-    char* base = static_cast<char*>(p);
-    const int T = tiles_of(std::max(n_per, 1));
+    Carver c(p);
+    const int T = tiles_of(std::max(n_per, 1), TILE);
     const int64_t slots = T > 1 ? (int64_t)std::max(M, 0) * T : 0;
-    w.total = reinterpret_cast<double*>(base);
-    w.tmax = reinterpret_cast<float*>(base ? base + align256(slots * 8) : nullptr);
-    w.bytes = (size_t)(256 + align256(slots * 8) + align256(slots * 4));
+    w.total = c.take<double>(slots * 8);
+    w.tmax = c.take<float>(slots * 4);
+    w.bytes = c.bytes();
 }
 
-__device__ __forceinline__ float block_max(float m, float* shmax) {
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) shmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    return fmaxf(fmaxf(shmax[0], shmax[1]), fmaxf(shmax[2], shmax[3]));
-}
-
-// Step 0 (groups of more than one tile, no statistics given): the maximum of the finite log-weights of tile (blockIdx.x) of group
-// g0 + blockIdx.y. A maximum does not depend on the order it is taken in: the scan kernel combines the tile maxima of its group.
-__global__ __launch_bounds__(256) void cdf_tile_max_kernel(const float* __restrict__ lw, int n_per, int T, int g0,
-                                                           float* __restrict__ tmax) {
-    __shared__ float shmax[4];
-    const int64_t g = (int64_t)g0 + blockIdx.y;
-    const float* l = lw + g * n_per;
-    const int64_t lo = (int64_t)blockIdx.x * TILE, hi = min((int64_t)n_per, lo + TILE);
-    float m = -INFINITY;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {
-        const float a = l[j];
-        if (isfinite(a)) m = fmaxf(m, a);
-    }
-    m = block_max(m, shmax);
-    if (threadIdx.x == 0) tmax[g * T + blockIdx.x] = m;
-}
-
+// Step 0 (groups of more than one tile, no statistics given): group_tile_max_kernel.
 // Step 1: workgroup (tile t, group g0 + blockIdx.y) writes the tile-local inclusive sums of its particles to cdf and (T > 1) the
 // tile's total to total[g T + t]. Thread `tid` owns particles [t TILE + 8 tid, + 8).
 __global__ __launch_bounds__(256) void cdf_scan_kernel(const float* __restrict__ lw, int n_per, int T, int g0,
@@ -88,29 +60,14 @@ __global__ __launch_bounds__(256) void cdf_scan_kernel(const float* __restrict__
     float a[PER_THREAD];
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) a[k] = first + k < n_per ? l[first + k] : -INFINITY;
-    // the group's maximum: what pp_is_stats / pp_is_fused_groups reduced, or the maximum of the finite log-weights found here
-    double M;
-    if (stats) {
-        M = stats[6 * g];
-    } else {
-        float m = -INFINITY;
-        if (T == 1) {
-#pragma unroll
-            for (int k = 0; k < PER_THREAD; ++k)
-                if (isfinite(a[k])) m = fmaxf(m, a[k]);
-        } else {
-            for (int t = tid; t < T; t += 256) m = fmaxf(m, tmax[g * T + t]);
-        }
-        M = (double)block_max(m, shmax);
-    }
-    const bool any = M > -INFINITY && M < INFINITY;      // (no finite log-weight: every weight is 0)
+    const double M = group_max<256>(stats, tmax, g, T, a, shmax);
+    const bool any = group_any(M);
     // the thread's own running sums
     double s[PER_THREAD];
     double run = 0.0;
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) {
-        const double w = (any && isfinite(a[k])) ? exp((double)a[k] - M) : 0.0;
-        run += w;
+        run += particle_weight(a[k], M, any);
         s[k] = run;
     }
     // lane offsets, carried forward through the wave: offset(l + 1) = offset(l) + total(l). Every lane follows the whole chain
@@ -213,26 +170,21 @@ __global__ __launch_bounds__(256) void resample_kernel(const double* __restrict_
 
 int is_cdf_groups(const float* lw, int M, int n_per, const double* stats, double* cdf, void* ws, size_t ws_bytes, hipStream_t st) {
     PP_CHECK_ARG(lw && cdf && ws, "pp_is_cdf_groups: null pointer (lw, cdf_out and the workspace are required)");
-    PP_CHECK_ARG(n_per >= 1 && M >= 0, "pp_is_cdf_groups: n_per >= 1 and n_groups >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff, "pp_is_cdf_groups: more than 2^31 - 1 particles per call: shard the groups");
+    PP_CHECK_GROUPS("pp_is_cdf_groups", M, n_per);
     CdfWorkspace w;
     cdf_carve(M, n_per, ws, w);
-    if (w.bytes > ws_bytes) {
-        set_error("pp_is_cdf_groups: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
-        return PP_ENOSPACE;
-    }
+    PP_CHECK_WORKSPACE("pp_is_cdf_groups", ws_bytes, w.bytes);
     if (M == 0) return 0;
-    const int T = tiles_of(n_per);
-    for (int g0 = 0; g0 < M; g0 += 65535) {
-        const int groups = std::min(65535, M - g0);
+    const int T = tiles_of(n_per, TILE);
+    for_each_group_chunk(M, [&](int g0, int groups) {
         if (T > 1 && !stats)
-            hipLaunchKernelGGL(cdf_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, T, g0, w.tmax);
+            hipLaunchKernelGGL(group_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, TILE, T, g0, w.tmax);
         hipLaunchKernelGGL(cdf_scan_kernel, dim3(T, groups), dim3(256), 0, st, lw, n_per, T, g0, stats, (const float*)w.tmax, cdf, w.total);
         if (T > 1) {
             hipLaunchKernelGGL(cdf_offsets_kernel, dim3(groups), dim3(256), 0, st, w.total, T, g0);
             hipLaunchKernelGGL(cdf_add_kernel, dim3(T - 1, groups), dim3(256), 0, st, cdf, n_per, T, g0, (const double*)w.total);
         }
-    }
+    });
     PP_LAUNCH_CHECK("pp_is_cdf_groups");
     return 0;
 }
@@ -242,7 +194,7 @@ int is_resample_groups(const double* cdf, const float* values, int M, int n_per,
     PP_CHECK_ARG(cdf, "pp_is_resample_groups: null pointer (the cdf is required)");
     PP_CHECK_ARG(n_per >= 1 && M >= 0 && n_out >= 0, "pp_is_resample_groups: n_per >= 1, n_groups >= 0 and n_out >= 0");
     PP_CHECK_ARG(0 <= lo && lo < hi && hi <= n_per, "pp_is_resample_groups: an index range 0 <= lo < hi <= n_per");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff && (int64_t)M * n_out <= 0x7fffffff,
+    PP_CHECK_ARG(groups_count_ok(M, n_per) && groups_count_ok(M, n_out),
                  "pp_is_resample_groups: more than 2^31 - 1 particles or draws per call: shard the groups");
     PP_CHECK_ARG(index_out || value_out, "pp_is_resample_groups: index_out or value_out (or both)");
     PP_CHECK_ARG(!value_out || values, "pp_is_resample_groups: value_out needs the values");

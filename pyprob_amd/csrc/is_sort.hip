@@ -6,7 +6,8 @@
 //   pp_is_sort_groups      writes, per group of n_per particles, the stable ascending order of the particles by a 32-bit key of
 //       x (value_out, lw_out, index_out) and the two counts of counted_out;
 //   pp_is_quantile_groups  searches the cumulative weights of the sorted particles (pp_is_cdf_groups over lw_out) for q T;
-//   pp_is_unique_groups    reduces every run of equal keys to (value, fixed-point mass, particle count).
+//   pp_is_unique_groups    reduces every run of equal keys to (value, fixed-point mass, particle count); the mass is the
+//       histogram's (is_groups.hpp: which particles count, the clamped weight and the shift).
 //
 // SHAPE OF THE SORT. A least-significant-digit radix sort with 8-bit digits, four passes. A workgroup of 256 threads takes a tile of
 // up to 2048 particles; wave w owns the consecutive positions [w seg, (w + 1) seg) of it and walks them 64 at a time, so "position
@@ -19,11 +20,7 @@
 // exclusive offsets, and the scatter into the other of two buffers in the workspace. No global atomics, no workgroup waits for
 // another inside a kernel. Every output is a function of the keys alone: two identical calls give the same bits and group g of an
 // M-group call carries the bits of the one-group call on its slice.
-#include "common.hpp"
-
-#include <math.h>
-
-#include <algorithm>
+#include "is_groups.hpp"
 
 namespace pp {
 namespace {
@@ -33,9 +30,6 @@ static_assert(TILE == PP_IS_SORT_TILE, "a tile is 256 threads of eight particles
 constexpr int DIGITS = 256;
 constexpr uint32_t EXCLUDED = 0xFFFFFFFFu;
 
-inline int64_t align256(int64_t b) { return (b + 255) & ~int64_t(255); }
-inline int tiles_of(int n_per) { return cdiv(n_per, TILE); }
-inline bool shape_ok(int M, int n_per) { return M >= 0 && n_per >= 1 && (int64_t)M * n_per <= 0x7fffffff; }
 
 // The key of a particle: EXCLUDED where the log-weight is not finite or x is NaN, else the order-preserving map of the bits of x
 // (-0.0 first made +0.0). No value maps to EXCLUDED: that would take the bits of a NaN.
@@ -326,25 +320,19 @@ struct SortWorkspace {
     size_t bytes;
 };
 void sort_carve(int M, int n_per, void* p, SortWorkspace& w) {
-    char* at = static_cast<char*>(p);
-    const int T = tiles_of(std::max(n_per, 1));
+    Carver c(p);
+    const int T = tiles_of(std::max(n_per, 1), TILE);
     const int64_t m = std::max(M, 0);
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        char* r = at ? at + off : nullptr;
-        off += align256(bytes);
-        return r;
-    };
     const bool big = T > 1;
     const int64_t words = big ? m * n_per * 4 : 0;
-    w.keys_a = reinterpret_cast<uint32_t*>(take(words));
-    w.keys_b = reinterpret_cast<uint32_t*>(take(words));
-    w.idx_a = reinterpret_cast<int*>(take(words));
-    w.idx_b = reinterpret_cast<int*>(take(words));
-    w.hist = reinterpret_cast<int*>(take(big ? m * T * DIGITS * 4 : 0));
-    w.dbase = reinterpret_cast<int*>(take(big ? m * DIGITS * 4 : 0));
-    w.tilecnt = reinterpret_cast<int*>(take(big ? m * T * 8 : 0));
-    w.bytes = (size_t)(256 + off);
+    w.keys_a = c.take<uint32_t>(words);
+    w.keys_b = c.take<uint32_t>(words);
+    w.idx_a = c.take<int>(words);
+    w.idx_b = c.take<int>(words);
+    w.hist = c.take<int>(big ? m * T * DIGITS * 4 : 0);
+    w.dbase = c.take<int>(big ? m * DIGITS * 4 : 0);
+    w.tilecnt = c.take<int>(big ? m * T * 8 : 0);
+    w.bytes = c.bytes();
 }
 
 // ---- quantile ------------------------------------------------------------------------------------------------------------------
@@ -383,13 +371,6 @@ __device__ __forceinline__ uint32_t value_key(float x) {
     return b;      // (equal keys <=> equal bits after -0.0 -> +0.0: the map of sort_key is one to one)
 }
 
-__device__ __forceinline__ float block_max(float m, float* shmax) {
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) shmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    return fmaxf(fmaxf(shmax[0], shmax[1]), fmaxf(shmax[2], shmax[3]));
-}
-
 // Thread `tid` of tile blockIdx.x owns the eight consecutive particles from first = tile TILE + 8 tid. head[k]: the particle is
 // among the first c counted ones and begins a run (its key differs from the one before it, or it is particle 0).
 __device__ __forceinline__ int load_heads(const float* __restrict__ v, int64_t first, int c, float (&val)[PER_THREAD],
@@ -425,13 +406,10 @@ __global__ __launch_bounds__(THREADS) void unique_count_kernel(const float* __re
     block_exclusive(mine, shw, total);
     if (tid == 0) heads[g * T + blockIdx.x] = total;
     if (tmax) {
-        float m = -INFINITY;
+        float a[PER_THREAD];
 #pragma unroll
-        for (int k = 0; k < PER_THREAD; ++k) {
-            const float a = first + k < n_per ? lw[g * n_per + first + k] : -INFINITY;
-            if (isfinite(a)) m = fmaxf(m, a);
-        }
-        m = block_max(m, shmax);
+        for (int k = 0; k < PER_THREAD; ++k) a[k] = first + k < n_per ? lw[g * n_per + first + k] : -INFINITY;
+        const float m = block_max<THREADS>(finite_max(a), shmax);
         if (tid == 0) tmax[g * T + blockIdx.x] = m;
     }
 }
@@ -456,10 +434,9 @@ __global__ __launch_bounds__(THREADS) void unique_offsets_kernel(const int* __re
     }
     if (tid == 0) runs_out[g] = carry;
     if (tmax) {
-        float m = -INFINITY;
-        for (int t = tid; t < T; t += THREADS) m = fmaxf(m, tmax[g * T + t]);
+        float m = tiles_max<THREADS>(tmax, g, T);
         __syncthreads();
-        m = block_max(m, shmax);
+        m = block_max<THREADS>(m, shmax);
         if (tid == 0) gmax[g] = (double)m;
     }
 }
@@ -491,7 +468,7 @@ __global__ __launch_bounds__(THREADS) void unique_reduce_kernel(const float* __r
     int total;
     int local = block_exclusive(mine, shw, total);      // (the syncs inside also publish the zeroed rows)
     const double M = stats ? stats[6 * g] : gmax[g];
-    const bool any = M > -INFINITY && M < INFINITY;
+    const bool any = group_any(M);
     const int run0 = first_run[g * T + blockIdx.x];
     unsigned long long acc = 0;
     unsigned int n = 0;
@@ -509,9 +486,7 @@ __global__ __launch_bounds__(THREADS) void unique_reduce_kernel(const float* __r
             ++local;
             value_out[b + run0 + local - 1] = val[k];
         }
-        const float a = lw[b + i];
-        const double w = (any && isfinite(a)) ? fmin(exp((double)a - M), 1.0) : 0.0;
-        acc += (unsigned long long)llrint(w * scale);
+        acc += fixed_mass(particle_weight_clamped(lw[b + i], M, any), scale);
         ++n;
     }
     if (n) {
@@ -563,21 +538,15 @@ struct UniqueWorkspace {
     size_t bytes;
 };
 void unique_carve(int M, int n_per, void* p, UniqueWorkspace& w) {
-    char* at = static_cast<char*>(p);
-    const int64_t tiles = (int64_t)std::max(M, 0) * tiles_of(std::max(n_per, 1));
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) {
-        char* r = at ? at + off : nullptr;
-        off += align256(bytes);
-        return r;
-    };
-    w.heads = reinterpret_cast<int*>(take(tiles * 4));
-    w.first_run = reinterpret_cast<int*>(take(tiles * 4));
-    w.lead_count = reinterpret_cast<int*>(take(tiles * 4));
-    w.tmax = reinterpret_cast<float*>(take(tiles * 4));
-    w.gmax = reinterpret_cast<double*>(take((int64_t)std::max(M, 0) * 8));
-    w.lead_mass = reinterpret_cast<int64_t*>(take(tiles * 8));
-    w.bytes = (size_t)(256 + off);
+    Carver c(p);
+    const int64_t tiles = (int64_t)std::max(M, 0) * tiles_of(std::max(n_per, 1), TILE);
+    w.heads = c.take<int>(tiles * 4);
+    w.first_run = c.take<int>(tiles * 4);
+    w.lead_count = c.take<int>(tiles * 4);
+    w.tmax = c.take<float>(tiles * 4);
+    w.gmax = c.take<double>((int64_t)std::max(M, 0) * 8);
+    w.lead_mass = c.take<int64_t>(tiles * 8);
+    w.bytes = c.bytes();
 }
 
 }  // namespace
@@ -587,22 +556,17 @@ int is_sort_groups(const float* lw, const float* x, int M, int n_per, const doub
     (void)stats;      // (the keys do not depend on the weights' maximum: with and without it the same bits)
     PP_CHECK_ARG(lw && x && value_out && lw_out && index_out && counted_out && ws,
                  "pp_is_sort_groups: null pointer (lw, x, the four outputs and the workspace are required)");
-    PP_CHECK_ARG(n_per >= 1 && M >= 0, "pp_is_sort_groups: n_per >= 1 and n_groups >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff, "pp_is_sort_groups: more than 2^31 - 1 particles per call: shard the groups");
+    PP_CHECK_GROUPS("pp_is_sort_groups", M, n_per);
     SortWorkspace w;
     sort_carve(M, n_per, ws, w);
-    if (w.bytes > ws_bytes) {
-        set_error("pp_is_sort_groups: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
-        return PP_ENOSPACE;
-    }
+    PP_CHECK_WORKSPACE("pp_is_sort_groups", ws_bytes, w.bytes);
     if (M == 0) return 0;
-    const int T = tiles_of(n_per);
-    for (int g0 = 0; g0 < M; g0 += 65535) {
-        const int groups = std::min(65535, M - g0);
+    const int T = tiles_of(n_per, TILE);
+    for_each_group_chunk(M, [&](int g0, int groups) {
         if (T == 1) {
             hipLaunchKernelGGL(sort_small_kernel, dim3(groups), dim3(THREADS), 0, st, lw, x, n_per, g0, value_out, lw_out, index_out,
                                counted_out);
-            continue;
+            return;
         }
         const dim3 tiles(T, groups);
         // pass 0: (lw, x) -> a; pass 1: a -> b; pass 2: b -> a; pass 3: a -> the outputs
@@ -631,7 +595,7 @@ int is_sort_groups(const float* lw, const float* x, int M, int n_per, const doub
                                    8 * pass, (const int*)w.hist, (const int*)w.dbase, (uint32_t*)nullptr, (int*)nullptr, value_out,
                                    lw_out, index_out);
         }
-    }
+    });
     PP_LAUNCH_CHECK("pp_is_sort_groups");
     return 0;
 }
@@ -641,7 +605,7 @@ int is_quantile_groups(const float* value, const double* cdf, const int* counted
     PP_CHECK_ARG(value && cdf && counted && q && out,
                  "pp_is_quantile_groups: null pointer (the sorted values, their cdf, the counts, q and out are required)");
     PP_CHECK_ARG(n_per >= 1 && M >= 0 && n_q >= 0, "pp_is_quantile_groups: n_per >= 1, n_groups >= 0 and n_q >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff && (int64_t)M * n_q <= 0x7fffffff,
+    PP_CHECK_ARG(groups_count_ok(M, n_per) && groups_count_ok(M, n_q),
                  "pp_is_quantile_groups: more than 2^31 - 1 particles or results per call: shard the groups");
     const int64_t outputs = (int64_t)M * n_q;
     if (outputs == 0) return 0;
@@ -656,20 +620,15 @@ int is_unique_groups(const float* value, const float* lw, const int* counted, in
     PP_CHECK_ARG(value && lw && counted && value_out && mass_out && count_out && runs_out && ws,
                  "pp_is_unique_groups: null pointer (the sorted values and log-weights, the counts, the four outputs and the "
                  "workspace are required)");
-    PP_CHECK_ARG(n_per >= 1 && M >= 0, "pp_is_unique_groups: n_per >= 1 and n_groups >= 0");
-    PP_CHECK_ARG((int64_t)M * n_per <= 0x7fffffff, "pp_is_unique_groups: more than 2^31 - 1 particles per call: shard the groups");
+    PP_CHECK_GROUPS("pp_is_unique_groups", M, n_per);
     UniqueWorkspace w;
     unique_carve(M, n_per, ws, w);
-    if (w.bytes > ws_bytes) {
-        set_error("pp_is_unique_groups: workspace too small (%zu < %zu bytes)", ws_bytes, w.bytes);
-        return PP_ENOSPACE;
-    }
+    PP_CHECK_WORKSPACE("pp_is_unique_groups", ws_bytes, w.bytes);
     if (M == 0) return 0;
-    const int T = tiles_of(n_per);
-    const double scale = ldexp(1.0, pp_is_hist_shift(n_per));
+    const int T = tiles_of(n_per, TILE);
+    const double scale = hist_scale(n_per);
     float* tmax = stats ? nullptr : w.tmax;
-    for (int g0 = 0; g0 < M; g0 += 65535) {
-        const int groups = std::min(65535, M - g0);
+    for_each_group_chunk(M, [&](int g0, int groups) {
         const dim3 tiles(T, groups);
         hipLaunchKernelGGL(unique_count_kernel, tiles, dim3(THREADS), 0, st, value, lw, counted, n_per, T, g0, w.heads, tmax);
         hipLaunchKernelGGL(unique_offsets_kernel, dim3(groups), dim3(THREADS), 0, st, (const int*)w.heads, w.first_run, T, g0,
@@ -681,7 +640,7 @@ int is_unique_groups(const float* value, const float* lw, const int* counted, in
             hipLaunchKernelGGL(unique_stitch_kernel, dim3(cdiv(T, THREADS), groups), dim3(THREADS), 0, st, (const int*)w.heads,
                                (const int*)w.first_run, (const int64_t*)w.lead_mass, (const int*)w.lead_count, n_per, T, g0, mass_out,
                                count_out);
-    }
+    });
     PP_LAUNCH_CHECK("pp_is_unique_groups");
     return 0;
 }
@@ -691,7 +650,7 @@ int is_unique_groups(const float* value, const float* lw, const int* counted, in
 extern "C" {
 
 size_t pp_is_sort_workspace_bytes(int32_t n_groups, int32_t n_per) {
-    if (!pp::shape_ok(n_groups, n_per)) return 0;
+    if (!pp::groups_shape_ok(n_groups, n_per)) return 0;
     pp::SortWorkspace w;
     pp::sort_carve(n_groups, n_per, nullptr, w);
     return w.bytes;
@@ -710,7 +669,7 @@ int pp_is_quantile_groups(const float* value_sorted, const double* cdf_sorted, c
 }
 
 size_t pp_is_unique_workspace_bytes(int32_t n_groups, int32_t n_per) {
-    if (!pp::shape_ok(n_groups, n_per)) return 0;
+    if (!pp::groups_shape_ok(n_groups, n_per)) return 0;
     pp::UniqueWorkspace w;
     pp::unique_carve(n_groups, n_per, nullptr, w);
     return w.bytes;

@@ -886,9 +886,7 @@ class Empirical:
         cdf = self.__dict__.get('_dev_cdf')
         if cdf is None:
             from .ops import ops
-            batch = self.__dict__.get('_batch')
-            stats = batch[2][batch[3]] if (batch is not None and batch[2] is not None) else None
-            cdf = self.__dict__['_dev_cdf'] = ops.is_cdf_groups(self._log_weights, self.length, stats)
+            cdf = self.__dict__['_dev_cdf'] = ops.is_cdf_groups(self._log_weights, self.length, self._group_stats_row())
         return cdf
 
     def _index_range(self, min_index, max_index):
@@ -1058,9 +1056,7 @@ class Empirical:
         each bit-reproducible). No particle with a finite log-weight: NaN arrays, count 0."""
         chosen, cols = self._joint_columns(addresses)
         lw = self._all_lw()
-        batch = self.__dict__.get('_batch')
-        stats = batch[2][batch[3]] if (batch is not None and batch[2] is not None) else None
-        return _joint_rows(chosen, _moment_rows(lw, cols, lw.numel(), stats))[0]
+        return _joint_rows(chosen, _moment_rows(lw, cols, lw.numel(), self._group_stats_row()))[0]
 
     def resample_joint(self, num_samples, addresses=None, seed=None, offset=0):
         """num_samples JOINT draws of several latents: ONE index per sample from the weights (pp_is_resample_groups, the Philox

@@ -710,17 +710,31 @@ def _groups_of(t, n_per, what):
     return t.numel() // n_per
 
 
+def _particles_like(t, lw, name, what, of="the log-weights'"):
+    if _f32(t, name).dim() != 1 or t.numel() != lw.numel():
+        raise RuntimeError('pyprob_hip::%s: %s must be a contiguous 1-D tensor of %s M * n_per elements' % (what, name, of))
+
+
+def _group_stats_ok(stats, M, what):
+    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
+        raise RuntimeError('pyprob_hip::%s: stats must be a contiguous float64 tensor of [M, 6]' % what)
+
+
+def _workspace(sizer, device, *shape):
+    """(uint8 tensor, its size): the workspace a pp_*_workspace_bytes function asks for at this shape."""
+    need = sizer(*shape)
+    return torch.empty(need, dtype=torch.uint8, device=device), need
+
+
 def _is_cdf_groups_hip(lw, n_per, stats):
     """cdf [M n_per] (float64) of the M groups of n_per log-weights; stats: the [M, 6] (or, M = 1, the 6+) doubles pp_is_stats /
     pp_is_fused_groups reduced over the same log-weights - their maxima are taken instead of being searched."""
     lib = L.load()
     _same_device(lw, stats)
     M = _groups_of(_f32(lw, 'lw'), n_per, 'is_cdf_groups')
-    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
-        raise RuntimeError('pyprob_hip::is_cdf_groups: stats must be a contiguous float64 tensor of [M, 6]')
+    _group_stats_ok(stats, M, 'is_cdf_groups')
     out = torch.empty(M * int(n_per), dtype=torch.float64, device=lw.device)
-    need = lib.pp_is_cdf_workspace_bytes(M, int(n_per))
-    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    ws, need = _workspace(lib.pp_is_cdf_workspace_bytes, lw.device, M, int(n_per))
     with torch.cuda.device(lw.device):
         rc = lib.pp_is_cdf_groups(lw.data_ptr(), M, int(n_per), L.ptr(stats), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
     L.check(rc, 'pp_is_cdf_groups')
@@ -759,13 +773,10 @@ def _is_moments_groups_hip(lw, cols, n_per, stats):
     if not 1 <= J <= L.PP_IS_MOMENTS_MAX_COLS:
         raise RuntimeError('pyprob_hip::is_moments_groups: 1 .. %d columns per call' % L.PP_IS_MOMENTS_MAX_COLS)
     for c in cols:
-        if _f32(c, 'cols').dim() != 1 or c.numel() != lw.numel():
-            raise RuntimeError('pyprob_hip::is_moments_groups: every column must be a 1-D tensor of the log-weights\' M * n_per elements')
-    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
-        raise RuntimeError('pyprob_hip::is_moments_groups: stats must be a contiguous float64 tensor of [M, 6]')
+        _particles_like(c, lw, 'every column', 'is_moments_groups')
+    _group_stats_ok(stats, M, 'is_moments_groups')
     out = torch.empty((M, L.PP_IS_MOMENTS_WIDTH(J)), dtype=torch.float64, device=lw.device)
-    need = lib.pp_is_moments_workspace_bytes(M, int(n_per), J)
-    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    ws, need = _workspace(lib.pp_is_moments_workspace_bytes, lw.device, M, int(n_per), J)
     ptrs = (C.c_void_p * J)(*[c.data_ptr() for c in cols])
     with torch.cuda.device(lw.device):
         rc = lib.pp_is_moments_groups(lw.data_ptr(), C.cast(ptrs, C.c_void_p), J, M, int(n_per), L.ptr(stats), out.data_ptr(),
@@ -788,22 +799,19 @@ def _is_hist_groups_hip(lw, x, y, n_per, edges_x, edges_y, stats):
     lib = L.load()
     _same_device(lw, x, y, edges_x, edges_y, stats)
     M = _groups_of(_f32(lw, 'lw'), n_per, 'is_hist_groups')
-    if _f32(x, 'x').dim() != 1 or x.numel() != lw.numel() or not x.is_contiguous():
-        raise RuntimeError('pyprob_hip::is_hist_groups: x must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    _particles_like(x, lw, 'x', 'is_hist_groups')
     if (y is None) != (edges_y is None):
         raise RuntimeError('pyprob_hip::is_hist_groups: y and edges_y are given together (2-D) or not at all (1-D)')
-    if y is not None and (_f32(y, 'y').dim() != 1 or y.numel() != lw.numel() or not y.is_contiguous()):
-        raise RuntimeError('pyprob_hip::is_hist_groups: y must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    if y is not None:
+        _particles_like(y, lw, 'y', 'is_hist_groups')
     bx, sx = _hist_edges(edges_x, M, 'edges_x')
     by, sy = _hist_edges(edges_y, M, 'edges_y') if edges_y is not None else (1, 0)
     if bx * by > L.PP_IS_HIST_MAX_BINS:
         raise RuntimeError('pyprob_hip::is_hist_groups: at most %d bins per call' % L.PP_IS_HIST_MAX_BINS)
-    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
-        raise RuntimeError('pyprob_hip::is_hist_groups: stats must be a contiguous float64 tensor of [M, 6]')
+    _group_stats_ok(stats, M, 'is_hist_groups')
     slots = bx + 3 if y is None else bx * by + 2
     out = torch.empty((M, 2, slots), dtype=torch.int64, device=lw.device)
-    need = lib.pp_is_hist_workspace_bytes(M, int(n_per), bx, by)
-    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    ws, need = _workspace(lib.pp_is_hist_workspace_bytes, lw.device, M, int(n_per), bx, by)
     with torch.cuda.device(lw.device):
         rc = lib.pp_is_hist_groups(lw.data_ptr(), x.data_ptr(), L.ptr(y), M, int(n_per), edges_x.data_ptr(), bx, sx, L.ptr(edges_y),
                                    by, sy, L.ptr(stats), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
@@ -817,20 +825,13 @@ def _is_extent_groups_hip(lw, x, n_per):
     lib = L.load()
     _same_device(lw, x)
     M = _groups_of(_f32(lw, 'lw'), n_per, 'is_extent_groups')
-    if _f32(x, 'x').dim() != 1 or x.numel() != lw.numel() or not x.is_contiguous():
-        raise RuntimeError('pyprob_hip::is_extent_groups: x must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    _particles_like(x, lw, 'x', 'is_extent_groups')
     out = torch.empty((M, 4), dtype=torch.float64, device=lw.device)
-    need = lib.pp_is_extent_workspace_bytes(M, int(n_per))
-    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    ws, need = _workspace(lib.pp_is_extent_workspace_bytes, lw.device, M, int(n_per))
     with torch.cuda.device(lw.device):
         rc = lib.pp_is_extent_groups(lw.data_ptr(), x.data_ptr(), M, int(n_per), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
     L.check(rc, 'pp_is_extent_groups')
     return out
-
-
-def _group_stats_ok(stats, M, what):
-    if stats is not None and (stats.dtype != torch.float64 or not stats.is_contiguous() or stats.numel() < 6 * M):
-        raise RuntimeError('pyprob_hip::%s: stats must be a contiguous float64 tensor of [M, 6]' % what)
 
 
 def _counted_ok(counted, M, what):
@@ -845,14 +846,12 @@ def _is_sort_groups_hip(lw, x, n_per, stats):
     lib = L.load()
     _same_device(lw, x, stats)
     M = _groups_of(_f32(lw, 'lw'), n_per, 'is_sort_groups')
-    if _f32(x, 'x').dim() != 1 or x.numel() != lw.numel() or not x.is_contiguous():
-        raise RuntimeError('pyprob_hip::is_sort_groups: x must be a contiguous 1-D tensor of the log-weights\' M * n_per elements')
+    _particles_like(x, lw, 'x', 'is_sort_groups')
     _group_stats_ok(stats, M, 'is_sort_groups')
     value, lw_out = torch.empty_like(x), torch.empty_like(lw)
     index = torch.empty(lw.numel(), dtype=torch.int32, device=lw.device)
     counted = torch.empty((M, 2), dtype=torch.int32, device=lw.device)
-    need = lib.pp_is_sort_workspace_bytes(M, int(n_per))
-    ws = torch.empty(need, dtype=torch.uint8, device=lw.device)
+    ws, need = _workspace(lib.pp_is_sort_workspace_bytes, lw.device, M, int(n_per))
     with torch.cuda.device(lw.device):
         rc = lib.pp_is_sort_groups(lw.data_ptr(), x.data_ptr(), M, int(n_per), L.ptr(stats), value.data_ptr(), lw_out.data_ptr(),
                                    index.data_ptr(), counted.data_ptr(), ws.data_ptr(), need, _stream(lw))
@@ -888,8 +887,7 @@ def _is_unique_groups_hip(value_sorted, lw_sorted, counted, n_per, stats):
     lib = L.load()
     _same_device(value_sorted, lw_sorted, counted, stats)
     M = _groups_of(_f32(value_sorted, 'value_sorted'), n_per, 'is_unique_groups')
-    if _f32(lw_sorted, 'lw_sorted').dim() != 1 or lw_sorted.numel() != value_sorted.numel() or not lw_sorted.is_contiguous():
-        raise RuntimeError('pyprob_hip::is_unique_groups: lw_sorted must be a contiguous 1-D tensor of the values\' M * n_per elements')
+    _particles_like(lw_sorted, value_sorted, 'lw_sorted', 'is_unique_groups', of="the values'")
     _counted_ok(counted, M, 'is_unique_groups')
     _group_stats_ok(stats, M, 'is_unique_groups')
     dev = value_sorted.device
@@ -897,8 +895,7 @@ def _is_unique_groups_hip(value_sorted, lw_sorted, counted, n_per, stats):
     mass = torch.empty((M, int(n_per)), dtype=torch.int64, device=dev)
     count = torch.empty((M, int(n_per)), dtype=torch.int32, device=dev)
     runs = torch.empty(M, dtype=torch.int32, device=dev)
-    need = lib.pp_is_unique_workspace_bytes(M, int(n_per))
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws, need = _workspace(lib.pp_is_unique_workspace_bytes, dev, M, int(n_per))
     with torch.cuda.device(dev):
         rc = lib.pp_is_unique_groups(value_sorted.data_ptr(), lw_sorted.data_ptr(), counted.data_ptr(), M, int(n_per), L.ptr(stats),
                                      value.data_ptr(), mass.data_ptr(), count.data_ptr(), runs.data_ptr(), ws.data_ptr(), need,

@@ -17,24 +17,24 @@ def moments_ref(lw, cols):
     cols = np.asarray(cols, np.float32)
     J, M, N = cols.shape
     rows, scale = np.zeros((M, width(J))), np.zeros((M, width(J)))
-    for g in range(M):
-        fin = np.isfinite(lw[g])
-        l = lw[g][fin].astype(np.float64)
-        m = l.max() if l.size else -np.inf
-        w = np.exp(l - m) if l.size else np.zeros(0)
-        first = cols[:, g, 0].astype(np.float64)
-        c = np.where(np.isfinite(first), first, 0.0)
-        d = cols[:, g, :][:, fin].astype(np.float64) - c[:, None]
-        rows[g, :4] = m, w.sum(), (w * w).sum(), fin.sum()
-        rows[g, 4:4 + J] = c
-        rows[g, 4 + J:4 + 2 * J] = (w * d).sum(1)
-        scale[g, 4 + J:4 + 2 * J] = (w * np.abs(d)).sum(1)
-        e = 4 + 2 * J
-        for j in range(J):
-            for k in range(j, J):
-                rows[g, e] = (w * d[j] * d[k]).sum()
-                scale[g, e] = (w * np.abs(d[j]) * np.abs(d[k])).sum()
-                e += 1
+    fin = np.isfinite(lw)                                                     # [M, N]
+    m = np.where(fin, lw, -np.inf).astype(np.float64).max(axis=1)             # (-inf: no finite log-weight in the group)
+    with np.errstate(invalid='ignore', over='ignore'):
+        w = np.where(fin, np.exp(np.where(fin, lw, 0.0).astype(np.float64) - np.where(np.isfinite(m), m, 0.0)[:, None]), 0.0)
+    first = cols[:, :, 0].astype(np.float64)                                  # [J, M]
+    c = np.where(np.isfinite(first), first, 0.0)
+    d = np.where(fin, cols, 0.0).astype(np.float64) - c[:, :, None]           # (a skipped particle's values are replaced, not used:
+    d = np.where(fin, d, 0.0)                                                 # every term of it is an exact zero)
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = m, w.sum(1), (w * w).sum(1), fin.sum(1)
+    rows[:, 4:4 + J] = c.T
+    rows[:, 4 + J:4 + 2 * J] = (w * d).sum(2).T
+    scale[:, 4 + J:4 + 2 * J] = (w * np.abs(d)).sum(2).T
+    e = 4 + 2 * J
+    for j in range(J):
+        for k in range(j, J):
+            rows[:, e] = (w * d[j] * d[k]).sum(1)
+            scale[:, e] = (w * np.abs(d[j]) * np.abs(d[k])).sum(1)
+            e += 1
     return rows, scale
 
 

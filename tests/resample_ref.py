@@ -44,11 +44,17 @@ def resample_ref(cdf, values, lo, hi, n_out, seed, offset):
     cdf = np.asarray(cdf, np.float64)
     M, N = cdf.shape
     index = np.full((M, n_out), -1, np.int64)
-    for g in range(M):
-        u = uniform53(seed, (int(offset) + g * n_out + np.arange(n_out, dtype=np.uint64)) & np.uint64(0xFFFFFFFFFFFFFFFF))
-        target, total = targets_ref(cdf[g], lo, hi, u)
-        if total > 0 and np.isfinite(total):
-            index[g] = np.minimum(lo + np.searchsorted(cdf[g, lo:hi], target, side='right'), hi - 1)
+    first = np.uint64(int(offset) & 0xFFFFFFFFFFFFFFFF) + np.arange(M, dtype=np.uint64)[:, None] * np.uint64(n_out)      # (wraps mod 2^64)
+    u = uniform53(seed, first + np.arange(n_out, dtype=np.uint64))
+    target, total = targets_ref(cdf.T, lo, hi, u.T)      # (the group is the LAST axis of both: [n_out, M] targets, [M] totals)
+    target = target.T
+    live = (total > 0) & np.isfinite(total)
+    if M * n_out * (hi - lo) <= 2 ** 26:      # searchsorted(side='right') = the number of entries <= target, for all groups at once
+        found = lo + (cdf[:, None, lo:hi] <= target[:, :, None]).sum(2)
+        index[live] = np.minimum(found, hi - 1)[live]
+    else:
+        for g in np.nonzero(live)[0]:
+            index[g] = np.minimum(lo + np.searchsorted(cdf[g, lo:hi], target[g], side='right'), hi - 1)
     value = None
     if values is not None:
         v = np.asarray(values, np.float32).reshape(M, N)

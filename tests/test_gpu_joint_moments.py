@@ -30,7 +30,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 IC = InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK
 
-SHAPES = [(1, 1, 1), (1, 63, 2), (3, 257, 5), (7, 300, 3), (2, 2049, 16), (1, 4097, 4)]
+SHAPES = [(1, 1, 1), (1, 63, 2), (3, 257, 5), (7, 300, 3), (2, 2049, 16), (1, 4097, 4), (66000, 2, 1)]      # (66000: two launch chunks)
 PAD = 2            # poisoned rows in front of and behind the live rows of the output
 DEV = 'cuda:0'
 BAR = 1e-10        # the project's bar for its fp64 statistics: 1e-10 of the scale of the sum
@@ -78,12 +78,25 @@ def _call(lw, x, stats=None):
     return out.cpu().numpy()
 
 
+def _groups_to_check(M):
+    """The groups that get calls of their own: all of them, or (one launch each) the first ones and both sides of the launch chunk."""
+    return range(M) if M <= 7 else sorted({g for g in (0, 1, 2, 65534, 65535, 65536, M - 2, M - 1) if g < M})
+
+
 def _stats(lw, x0):
-    """pp_is_stats per group: device double [M, 6]."""
+    """pp_is_stats per group: device double [M, 6]. Beyond 7 groups only the rows of _groups_to_check come from pp_is_stats; the
+    others hold the maximum of the group's finite log-weights (exact in any arithmetic, and asserted here to be what pp_is_stats
+    gives) and NaN in the five entries pp_is_moments_groups does not read."""
     from pyprob_amd import ops as P
     scratch = torch.zeros(L.PP_IS_STATS_SCRATCH, dtype=torch.float64, device=DEV)
-    rows = [P.ops.is_stats(torch.from_numpy(lw[g]).to(DEV), torch.from_numpy(x0[g]).to(DEV), scratch)[:6] for g in range(lw.shape[0])]
-    return torch.stack(rows).contiguous()
+    host = np.full((lw.shape[0], 6), np.nan)
+    host[:, 0] = np.where(np.isfinite(lw), lw, -np.inf).max(axis=1)
+    st = torch.from_numpy(host).to(DEV)
+    for g in _groups_to_check(lw.shape[0]):
+        st[g] = P.ops.is_stats(torch.from_numpy(lw[g]).to(DEV), torch.from_numpy(x0[g]).to(DEV), scratch)[:6]
+    some = np.isfinite(host[:, 0])      # (a group without a finite log-weight has no maximum to compare)
+    assert np.array_equal(_bits(st[:, 0].cpu().numpy()[some]), _bits(host[some, 0]))
+    return st.contiguous()
 
 
 def _case(M, N, J):
@@ -123,7 +136,7 @@ def test_rows_against_the_float64_restatement(M, N, J):
         assert (got[1, 4:4 + J] == 0).all()         # (its first particle carries NaN: pivot 0)
     # the rows as moments: means and covariances of every group with a weight against a two-pass computation
     from pyprob_amd.distributions import joint_from_moments
-    for g in range(M - 1 if M >= 2 else M):
+    for g in [g for g in _groups_to_check(M) if g < M - 1 or M == 1]:
         j = joint_from_moments(list(range(J)), got[g])
         mean, cov = MR.mean_cov_ref(lw[g], x[:, g])
         sd = np.sqrt(np.diag(cov))
@@ -156,7 +169,7 @@ def test_bit_identity_of_calls_groups_and_maxima(M, N, J):
     with_stats = _call(lw, x, st)
     assert np.isnan(with_stats[:PAD]).all() and np.isnan(with_stats[PAD + M:]).all()
     assert np.array_equal(_bits(with_stats[PAD:PAD + M]), _bits(got))                # the maximum pp_is_stats reduced: the same bits
-    for g in range(M):
+    for g in _groups_to_check(M):
         one = _call(lw[g:g + 1], x[:, g:g + 1])[PAD]
         assert np.array_equal(_bits(one), _bits(got[g])), (g, np.nonzero(_bits(one) != _bits(got[g]))[0][:5].tolist())
         one = _call(lw[g:g + 1], x[:, g:g + 1], st[g:g + 1].contiguous())[PAD]

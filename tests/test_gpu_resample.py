@@ -26,7 +26,10 @@ IC = InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK
 
 T = L.PP_IS_CDF_TILE
 SHAPES = [(1, 1), (3, 1), (257, 1), (5, 63), (5, 64), (5, 65), (5, 255), (5, 256), (5, 257), (5, T - 1), (5, T), (5, T + 1),
-          (3, 2 * T + 1), (2, 70001)]
+          (3, 2 * T + 1), (2, 70001), (66000, 2)]      # (66000 groups: two launch chunks of at most 65535)
+# The draws of a shape: the float64 restatement runs Philox in numpy, a few seconds per 10^7 draws, so 66000 groups take 1 and 7
+# draws each and not 1000 (the draw kernel strides over the outputs of a call: it has no launch chunk to cross).
+DRAWS = [(M, N, n_out) for M, N in SHAPES for n_out in (1, 7, 1000) if M * n_out <= 2 ** 20]
 PAD = 3            # poisoned rows in front of and behind the live block
 DEV = 'cuda:0'
 _CASES = {}
@@ -37,7 +40,11 @@ def _bits(a):
 
 
 def _groups_to_check(M):
-    return range(M) if M <= 7 else [0, 1, 127, 255, 256]
+    return range(M) if M <= 7 else [0, 1, 127, 255, 256] + [g for g in (65534, 65535, 65536, M - 2) if g < M]
+
+
+def _stats_rows(M):
+    return range(M) if M <= 1000 else _groups_to_check(M)
 
 
 def _inputs(M, N):
@@ -68,11 +75,20 @@ def _cdf_call(lw, stats=None):
 
 
 def _stats(lw, x):
-    """pp_is_stats per group: device double [M, 6]."""
+    """pp_is_stats per group: device double [M, 6]. One launch per group: beyond 1000 groups only the rows of _stats_rows come from
+    pp_is_stats; the others hold the maximum of the group's finite log-weights (exact in any arithmetic, and asserted below to be
+    what pp_is_stats gives) and NaN in the five entries pp_is_cdf_groups does not read."""
     from pyprob_amd import ops as P
+    M = lw.shape[0]
     scratch = torch.zeros(L.PP_IS_STATS_SCRATCH, dtype=torch.float64, device=DEV)
-    rows = [P.ops.is_stats(torch.from_numpy(lw[g]).to(DEV), torch.from_numpy(x[g]).to(DEV), scratch)[:6] for g in range(lw.shape[0])]
-    return torch.stack(rows).contiguous()
+    host = np.full((M, 6), np.nan)
+    host[:, 0] = np.where(np.isfinite(lw), lw, -np.inf).max(axis=1)
+    st = torch.from_numpy(host).to(DEV)
+    for g in _stats_rows(M):
+        st[g] = P.ops.is_stats(torch.from_numpy(lw[g]).to(DEV), torch.from_numpy(x[g]).to(DEV), scratch)[:6]
+    some = np.isfinite(host[:, 0])      # (a group without a finite log-weight has no maximum to compare)
+    assert np.array_equal(_bits(st[:, 0].cpu().numpy()[some]), _bits(host[some, 0]))
+    return st.contiguous()
 
 
 def _case(M, N):
@@ -113,8 +129,9 @@ def test_cdf_of_every_group(M, N):
     with_stats, _ = _cdf_call(lw, st)
     assert np.array_equal(_bits(with_stats[PAD:PAD + M]), _bits(c))
     assert np.isnan(with_stats[:PAD]).all() and np.isnan(with_stats[PAD + M:]).all()
-    sum_w = st.cpu().numpy()[:, 1]
-    assert (np.abs(c[:, -1] - sum_w) <= bound[:, 0]).all()
+    rows = list(_stats_rows(M))
+    sum_w = st.cpu().numpy()[rows, 1]
+    assert (np.abs(c[rows, -1] - sum_w) <= bound[rows, 0]).all()
     # two identical calls
     again, _ = _cdf_call(lw)
     assert np.array_equal(_bits(again[PAD:PAD + M]), _bits(c))
@@ -137,8 +154,7 @@ def _draw_call(cdf_dev_rows, values, M, N, lo, hi, n_out, seed, offset):
     return ti.cpu().numpy(), tv.cpu().numpy()
 
 
-@pytest.mark.parametrize('n_out', [1, 7, 1000])
-@pytest.mark.parametrize('M,N', SHAPES)
+@pytest.mark.parametrize('M,N,n_out', DRAWS)
 def test_indices_are_searchsorted_on_the_device_cdf(M, N, n_out):
     lw, x, whole, dev = _case(M, N)
     c = whole[PAD:PAD + M]
