@@ -862,6 +862,45 @@ int pp_is_unique_groups(const float* value_sorted /*dev [M n_per]*/, const float
                         int64_t* mass_out /*dev [M n_per]*/, int32_t* count_out /*dev [M n_per]*/, int32_t* runs_out /*dev [M]*/,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Weighted Gaussian-mixture EM over one latent of a lock-step posterior call on the device. The reference's density_estimate
+ * (pyprob/distributions/empirical.py:795-807) resamples 1000 values on the host, drops the weights and fits scikit-learn's
+ * GaussianMixture(covariance_type='diag') to them; here the EM of that class runs in one dimension over ALL particles of each of
+ * the M groups under their own weights, in fp64 (only x and lw are float32), from the caller's initial parameters.
+ *   pp_is_gmm_groups    w_i = exp((double)lw_i - max_g) for the particles with a finite lw (max_g = stats[6 g] or, without `stats`,
+ *                       the largest finite lw of the group: the same bits either way); every other particle is skipped - its value
+ *                       is read but enters nothing. W = sum w_i. With pi_k, mu_k, v_k (k < K) the current weights, means and
+ *                       variances of the group - at first params_init[g] = pi | mu | v - iteration t = 1 .. max_iter is
+ *                         E-step  l_ik = log pi_k - 1/2 log(2 pi v_k) - (x_i - mu_k)^2 / (2 v_k),  L_i = logsumexp_k l_ik,
+ *                                 r_ik = w_i exp(l_ik - L_i),  lb_t = sum_i w_i L_i / W
+ *                         M-step  N_k = sum_i r_ik + 10 DBL_EPSILON,  d_k = sum_i r_ik (x_i - mu_k) / N_k,  mu'_k = mu_k + d_k,
+ *                                 v'_k = max(sum_i r_ik (x_i - mu_k)^2 / N_k - d_k^2, 0) + reg_covar,  pi'_k = N_k / sum_k N_k
+ *                         stop    |lb_t - lb_{t-1}| < tol (lb_0 = -inf): the group is converged, n_iter = t and the parameters are
+ *                                 those AFTER this M-step, as in scikit-learn; tol = 0 runs exactly max_iter iterations.
+ *                       The M-step's sums are taken about the current mean as pivot, so a narrow posterior far from zero keeps its
+ *                       variance. Row g of `out` (PP_IS_GMM_WIDTH(K) doubles): pi [K] | mu [K] | v [K] | the last lower bound,
+ *                       n_iter, converged (0 / 1), W, the count of finite lw, max_g. A group without a finite lw: NaN parameters
+ *                       and lower bound, n_iter 0, converged 1, W 0, count 0, max_g -inf. A NaN value under a finite lw makes the
+ *                       lower bound NaN: the group never converges and leaves NaN parameters after max_iter iterations.
+ *                       Two dependent launches per iteration on the caller's stream (a workgroup per tile of 2048 particles stores a
+ *                       partial row of 3 K + 3 sums, a workgroup per group adds them in tile order and updates its row of `out`);
+ *                       no atomics, no workgroup waits for another. A converged group is frozen: its workgroups return at entry.
+ *                       Every check_every iterations (< 1: 8) the host reads one word that says whether all groups converged and
+ *                       stops enqueuing: this call SYNCHRONISES the stream there. The sums' order is a function of n_per and K
+ *                       alone: the result of a group does not depend on check_every, on M or on the other groups of the call, and
+ *                       a call repeated gives the same bits.
+ * Any n_per >= 1 and n_groups >= 0 (0: return 0 without a launch); nothing is written outside `out` and the workspace
+ * (pp_is_gmm_workspace_bytes; PP_ENOSPACE when shorter). PP_EINVAL without a launch for a NULL required pointer (lw, x, params_init,
+ * out, workspace), n_components outside 1 .. PP_IS_GMM_MAX_K, n_per < 1, n_groups < 0, M n_per above 2^31 - 1, max_iter < 1, tol < 0
+ * or reg_covar < 0 (NaN included). pp_is_gmm_workspace_bytes returns 0 outside that envelope. */
+#define PP_IS_GMM_MAX_K 16
+#define PP_IS_GMM_WIDTH(K) (3 * (K) + 6)
+size_t pp_is_gmm_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_components);
+int pp_is_gmm_groups(const float* lw /*dev [M n_per]*/, const float* x /*dev [M n_per]*/, int32_t n_components, int32_t n_groups,
+                     int32_t n_per, const double* stats /*dev double [M, 6] or NULL*/,
+                     const double* params_init /*dev double [M, 3 K]*/, int32_t max_iter, double tol, double reg_covar,
+                     int32_t check_every, double* out /*dev double [M, PP_IS_GMM_WIDTH(K)]*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

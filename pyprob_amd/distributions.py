@@ -1257,6 +1257,64 @@ class Empirical:
         return self._like([float(v) for v in xs[heads]], new_lw, op='combine_duplicates', length=self.length,
                           length_after=len(heads))
 
+    # ---- density estimate (csrc/is_gmm.hip) ----------------------------------------------------------------------------
+    def _skipping_variance(self):
+        """The weighted variance over the particles with a finite log-weight only (`variance` on the host multiplies the value of a
+        particle without weight by 0: NaN where that value is NaN): the device statistics of a device-backed Empirical - the
+        object's own, else reduced here -, float64 numpy for every other."""
+        if self._device_backed():
+            st = self._device_moments() or _device_stats(self._log_weights, self._values)
+            return float(max(st['var'], 0.0))
+        lw, x = self._host_scalars()
+        keep = np.isfinite(lw)
+        if x is None or not keep.any():
+            return float('nan')
+        w = np.exp(lw[keep] - lw[keep].max())
+        mean = np.sum(w * x[keep]) / w.sum()
+        return float(np.sum(w * (x[keep] - mean) ** 2) / w.sum())
+
+    def density_estimate(self, num_mixture_components=1, num_samples=None, tol=1e-3, max_iter=100, reg_covar=1e-6,
+                         weights_init=None, means_init=None, stddevs_init=None):
+        """A Mixture of num_mixture_components (K <= 16) Normals fitted to the weighted values by expectation-maximisation
+        (density_estimate, empirical.py:795-807: scikit-learn's GaussianMixture(covariance_type='diag') in one dimension). The
+        reference resamples 1000 values and drops the weights; here num_samples=None fits ALL particles under their own weights,
+        in float64, by the definition of pp_is_gmm_groups (include/pyprob_amd.h): at most max_iter iterations, converged when the
+        weighted mean log-likelihood changes by less than tol; reg_covar is added to every variance. An integer num_samples first
+        resamples, as the reference does, on the route resample() takes for this object, and fits the draws.
+
+        The start needs no random numbers: weights 1 / K, means the exact weighted quantiles (k + 1/2) / K (quantile(): the sort is
+        kept with the object), variances variance / K^2 + reg_covar. weights_init / means_init / stddevs_init (K numbers each)
+        replace each of these; weights_init is taken as given (positive numbers that sum to one).
+
+        The returned Mixture carries `.fit` (MixtureFit): weights, means, stddevs in float64 numpy - the Normals themselves hold
+        float32 -, lower_bound, n_iter, converged, count and metadata (op='density_estimate'). A fit that did not converge warns.
+        A device-backed Empirical (the result of a lock-step posterior call, post.marginal(address), a device resample, a device
+        combine_duplicates) is fitted on the device and 3 K + 6 doubles travel back; every other Empirical, and all of them
+        under PP_EMPIRICAL_DEVICE=0, runs the same definition in float64 numpy."""
+        self._check_finalized()
+        K = _gmm_arguments(num_mixture_components, tol, max_iter, reg_covar)
+        if self.length == 0:
+            raise ValueError('density_estimate of an empty Empirical')
+        if num_samples is not None:
+            return self.resample(int(num_samples)).density_estimate(K, None, tol, max_iter, reg_covar, weights_init, means_init,
+                                                                    stddevs_init)
+        levels = (np.arange(K) + 0.5) / K
+        device = self._device_backed()
+        if not device:
+            lw, x = self._host_scalars()
+            if x is None:
+                raise ValueError('density_estimate needs scalar values')
+        init = _gmm_init_rows(K, reg_covar, weights_init, means_init, stddevs_init,
+                              lambda: np.asarray(self.quantile(levels), np.float64)[None], lambda: [self._skipping_variance()])
+        if device:
+            from .ops import ops
+            rows = ops.is_gmm_groups(self._log_weights, self._values, K, self.length, self._group_stats_row(),
+                                     torch.from_numpy(init).to(self._log_weights.device), int(max_iter), float(tol),
+                                     float(reg_covar)).cpu().numpy()
+        else:
+            rows = _host_gmm(lw, x, init[0], int(max_iter), float(tol), float(reg_covar))[None]
+        return _mixtures_from_rows(rows, K, dict(self._metadata), self.length, tol, max_iter, reg_covar)[0]
+
     # ---- transformations (each returns a new Empirical) ------------------------------------------------------
     def map(self, func, min_index=None, max_index=None):
         self._check_finalized()
@@ -1832,6 +1890,145 @@ def quantile_batch(posteriors, q, address=None):
     value, lw_sorted, _, counted = ops.is_sort_groups(lw, column, N, group_stats)
     cdf = ops.is_cdf_groups(lw_sorted, N, group_stats)
     return ops.is_quantile_groups(value, cdf, counted, N, torch.from_numpy(qs).to(lw.device)).cpu().numpy()
+
+
+_GMM_MAX_K = 16      # PP_IS_GMM_MAX_K (include/pyprob_amd.h)
+
+
+class MixtureFit:
+    """What Empirical.density_estimate fitted, in float64 numpy: weights [K], means [K], stddevs [K]; lower_bound (the weighted mean
+    log-likelihood of the last E-step), n_iter, converged, count (the particles with a finite log-weight) and metadata."""
+
+    def __init__(self, weights, means, stddevs, lower_bound, n_iter, converged, count, metadata):
+        self.weights, self.means, self.stddevs = weights, means, stddevs
+        self.lower_bound, self.n_iter, self.converged, self.count = float(lower_bound), int(n_iter), bool(converged), int(count)
+        self.metadata = metadata
+
+    def __repr__(self):
+        return 'MixtureFit(components:{}, n_iter:{}, converged:{}, lower_bound:{})'.format(len(self.weights), self.n_iter,
+                                                                                           self.converged, self.lower_bound)
+
+
+def _gmm_arguments(num_mixture_components, tol, max_iter, reg_covar):
+    K = num_mixture_components
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= _GMM_MAX_K:
+        raise ValueError('num_mixture_components must be an integer in 1 .. %d, not %r' % (_GMM_MAX_K, K))
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or int(max_iter) < 1:
+        raise ValueError('max_iter must be a positive integer, not %r' % (max_iter,))
+    if not float(tol) >= 0 or not float(reg_covar) >= 0:
+        raise ValueError('tol and reg_covar must not be negative')
+    return int(K)
+
+
+def _gmm_init_rows(K, reg_covar, weights_init, means_init, stddevs_init, quantiles, variances):
+    """The initial parameters [M, 3 K] (weights | means | variances, float64) of density_estimate: the overrides where given (one
+    row of K numbers, shared by the groups), else 1 / K, quantiles() = [M, K] and variances() = [M] / K^2 + reg_covar - each
+    called only where its default is needed."""
+    def override(a, name):
+        a = np.asarray(a, np.float64).reshape(-1)
+        if a.shape != (K,) or not np.isfinite(a).all():
+            raise ValueError('%s must hold %d finite numbers' % (name, K))
+        return a[None]
+    mu = override(means_init, 'means_init') if means_init is not None else np.asarray(quantiles(), np.float64).reshape(-1, K)
+    if stddevs_init is not None:
+        v = override(stddevs_init, 'stddevs_init') ** 2
+    else:
+        v = np.asarray(variances(), np.float64).reshape(-1, 1) / float(K * K) + float(reg_covar) + np.zeros((1, K))
+    pi = override(weights_init, 'weights_init') if weights_init is not None else np.full((1, K), 1.0 / K)
+    if not (pi > 0).all():
+        raise ValueError('weights_init must be positive')
+    M = max(mu.shape[0], v.shape[0])
+    if not (v[np.isfinite(v)] > 0).all():
+        raise ValueError('the initial variances must be positive (constant values need reg_covar > 0 or stddevs_init)')
+    return np.ascontiguousarray(np.concatenate([np.broadcast_to(a, (M, K)) for a in (pi, mu, v)], 1))
+
+
+def _host_gmm(lw, x, init, max_iter, tol, reg_covar):
+    """pp_is_gmm_groups' definition (include/pyprob_amd.h) in float64 numpy for one particle set: its output row [3 K + 6]."""
+    K = len(init) // 3
+    pi, mu, v = (np.array(init[j * K:(j + 1) * K], np.float64) for j in range(3))
+    fin = np.isfinite(lw)
+    if not fin.any():
+        return np.concatenate([np.full(3 * K + 1, np.nan), [0.0, 1.0, 0.0, 0.0, -np.inf]])
+    top = lw[fin].max()
+    w, xs = np.exp(lw[fin] - top), np.asarray(x, np.float64)[fin]
+    W = w.sum()
+    before, lb, n_iter, converged = -np.inf, np.nan, 0, False
+    with np.errstate(all='ignore'):
+        for t in range(1, max_iter + 1):
+            d = xs[:, None] - mu[None, :]
+            l = np.log(pi) - 0.5 * np.log(2.0 * np.pi * v) - d * d / (2.0 * v)
+            m = l.max(1)
+            L = m + np.log(np.exp(l - m[:, None]).sum(1))
+            r = w[:, None] * np.exp(l - L[:, None])
+            lb = float((w * L).sum() / W)
+            N = r.sum(0) + 10.0 * np.finfo(np.float64).eps
+            dk = (r * d).sum(0) / N
+            mu = mu + dk
+            v = np.maximum((r * d * d).sum(0) / N - dk * dk, 0.0) + reg_covar
+            pi = N / N.sum()
+            n_iter = t
+            if abs(lb - before) < tol:
+                converged = True
+                break
+            before = lb
+    return np.concatenate([pi, mu, v, [lb, float(n_iter), float(converged), W, float(fin.sum()), top]])
+
+
+def _mixtures_from_rows(rows, K, metadata, length, tol, max_iter, reg_covar):
+    """The output rows [M, 3 K + 6] of pp_is_gmm_groups as M Mixtures of Normals, each with its MixtureFit as `.fit`. metadata: one
+    dict, or one per row. The float32 parameters of all M K Normals are converted in one pass (a batched call builds hundreds)."""
+    rows = np.asarray(rows, np.float64).reshape(-1, 3 * K + 6)
+    M = rows.shape[0]
+    pi, mu, sd = rows[:, :K].copy(), rows[:, K:2 * K].copy(), np.sqrt(rows[:, 2 * K:3 * K])
+    if not (rows[:, 3 * K + 4] > 0).all():
+        raise ValueError('density_estimate: no particle with a finite log-weight')
+    if not (np.isfinite(pi).all() and np.isfinite(mu).all() and np.isfinite(sd).all()):
+        raise ValueError('density_estimate: the fit is not finite (a value that is not finite under a finite log-weight?)')
+    for row in rows[rows[:, 3 * K + 2] == 0]:
+        warnings.warn('density_estimate did not converge in {} iterations (last lower bound {}): raise max_iter or tol, or '
+                      'check the initial parameters'.format(int(row[3 * K + 1]), row[3 * K]), RuntimeWarning, stacklevel=3)
+    loc = torch.from_numpy(mu.astype(np.float32)).reshape(-1).unbind(0)
+    scale = torch.from_numpy(sd.astype(np.float32)).reshape(-1).unbind(0)
+    probs = torch.from_numpy(pi.astype(np.float32)).unbind(0)
+    out = []
+    for g in range(M):
+        meta = dict(metadata if isinstance(metadata, dict) else metadata[g])
+        meta.update(op='density_estimate', length=int(length), num_mixture_components=K, tol=float(tol), max_iter=int(max_iter),
+                    reg_covar=float(reg_covar))
+        mix = Mixture([Normal(loc[g * K + k], scale[g * K + k]) for k in range(K)], probs[g])
+        mix.fit = MixtureFit(pi[g], mu[g], sd[g], rows[g, 3 * K], rows[g, 3 * K + 1], rows[g, 3 * K + 2], rows[g, 3 * K + 4], meta)
+        out.append(mix)
+    return out
+
+
+def density_estimate_batch(posteriors, num_mixture_components=1, address=None, num_samples=None, tol=1e-3, max_iter=100,
+                           reg_covar=1e-6, weights_init=None, means_init=None, stddevs_init=None):
+    """[p.density_estimate(num_mixture_components, ...) for p in posteriors], or with address=
+    [p.marginal(address).density_estimate(...) ...] - and, where the posteriors are the M groups of ONE
+    Model.posterior_results_batch execution in order (recognised as quantile_batch recognises them) and num_samples is None, the
+    same Mixtures bit for bit from ONE quantile_batch call for the initial means, one pp_is_gmm_groups call over all groups (the
+    maxima from the call's own [M, 6] statistics; groups that converge early are frozen while the others go on) and one
+    device-to-host copy of the rows. The initial variances are each group's own `variance` (address=None: the statistics of the
+    call; an address: the statistics of its marginal, one small reduction per group). Anything else is served by the loop."""
+    posteriors = list(posteriors)
+    K = _gmm_arguments(num_mixture_components, tol, max_iter, reg_covar)
+    if not posteriors:
+        return []
+    found = _batch_column(posteriors, address) if num_samples is None else None
+    if found is None:
+        return [(p if address is None else p.marginal(address)).density_estimate(K, num_samples, tol, max_iter, reg_covar,
+                                                                                  weights_init, means_init, stddevs_init)
+                for p in posteriors]
+    from .ops import ops
+    lw, column, N, group_stats = found
+    levels = (np.arange(K) + 0.5) / K
+    init = _gmm_init_rows(K, reg_covar, weights_init, means_init, stddevs_init, lambda: quantile_batch(posteriors, levels, address),
+                          lambda: [(p if address is None else p.marginal(address))._skipping_variance() for p in posteriors])
+    init = np.array(np.broadcast_to(init, (len(posteriors), 3 * K)))
+    rows = ops.is_gmm_groups(lw, column, K, N, group_stats, torch.from_numpy(init).to(lw.device), int(max_iter), float(tol),
+                             float(reg_covar)).cpu().numpy()
+    return _mixtures_from_rows(rows, K, [p._metadata for p in posteriors], N, tol, max_iter, reg_covar)
 
 
 def joint_batch(posteriors, addresses=None):

@@ -32,6 +32,7 @@ PP_IS_CDF_TILE = 2048        # particles per workgroup of pp_is_cdf_groups (incl
 PP_IS_MOMENTS_MAX_COLS = 16  # columns of one pp_is_moments_groups call (include/pyprob_amd.h)
 PP_IS_HIST_MAX_BINS = 2048   # bins_x * bins_y of one pp_is_hist_groups call (include/pyprob_amd.h)
 PP_IS_SORT_TILE = 2048       # particles one workgroup of pp_is_sort_groups sorts in LDS (include/pyprob_amd.h)
+PP_IS_GMM_MAX_K = 16         # mixture components of one pp_is_gmm_groups call (include/pyprob_amd.h)
 
 
 def PP_IS_MOMENTS_WIDTH(n_cols):
@@ -39,6 +40,12 @@ def PP_IS_MOMENTS_WIDTH(n_cols):
     upper triangle of J (J + 1) / 2 products."""
     n_cols = int(n_cols)
     return 4 + 2 * n_cols + n_cols * (n_cols + 1) // 2
+
+
+def PP_IS_GMM_WIDTH(n_components):
+    """Doubles per group of pp_is_gmm_groups' output (include/pyprob_amd.h): K weights, K means, K variances, the last lower bound,
+    n_iter, converged, W, the count of finite log-weights and the group's maximum."""
+    return 3 * int(n_components) + 6
 
 
 i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p
@@ -212,6 +219,8 @@ PROTOTYPES = {
     'pp_is_quantile_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp]),
     'pp_is_unique_workspace_bytes': (C.c_size_t, [i32, i32]),
     'pp_is_unique_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    'pp_is_gmm_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
+    'pp_is_gmm_groups': (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

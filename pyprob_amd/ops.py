@@ -31,6 +31,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_sort_groups      the particles of every group in order of value (stable radix sort)   pyprob/distributions/empirical.py:714-728, 809-834
     is_quantile_groups  exact weighted quantiles over the sorted particles (inverted cdf)     pyprob/distributions/empirical.py:714-728
     is_unique_groups    distinct values with fixed-point masses and counts (combine_duplicates)   pyprob/distributions/empirical.py:809-834
+    is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -91,6 +92,8 @@ _lib.define('is_sort_groups(Tensor lw, Tensor x, int n_per, Tensor? stats) -> (T
 _lib.define('is_quantile_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor q) -> Tensor')
 _lib.define('is_unique_groups(Tensor value_sorted, Tensor lw_sorted, Tensor counted, int n_per, Tensor? stats) -> '
             '(Tensor, Tensor, Tensor, Tensor)')
+_lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Tensor? stats, Tensor params_init, int max_iter, '
+            'float tol, float reg_covar) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
@@ -904,6 +907,41 @@ def _is_unique_groups_hip(value_sorted, lw_sorted, counted, n_per, stats):
     return value, mass, count, runs
 
 
+def gmm_check_every():
+    """After how many EM iterations pp_is_gmm_groups asks whether every group converged: PP_GMM_CHECK, default 8. The result of
+    a fit does not depend on it (a converged group is frozen on the device either way); it trades launches of frozen groups
+    against host synchronisations."""
+    import os
+    try:
+        n = int(os.environ.get('PP_GMM_CHECK', '8'))
+    except ValueError:
+        n = 8
+    return n if n >= 1 else 8
+
+
+def _is_gmm_groups_hip(lw, x, n_components, n_per, stats, params_init, max_iter, tol, reg_covar):
+    """[M, PP_IS_GMM_WIDTH(K)] (float64): weights, means, variances | last lower bound, n_iter, converged, W, count, max lw of the
+    weighted K-component Gaussian-mixture EM over x in each of the M groups of n_per particles (pp_is_gmm_groups), started from
+    params_init (float64 [M, 3 K]: weights | means | variances). stats: as for is_cdf_groups."""
+    lib = L.load()
+    _same_device(lw, x, stats, params_init)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_gmm_groups')
+    _particles_like(x, lw, 'x', 'is_gmm_groups')
+    K = int(n_components)
+    if not 1 <= K <= L.PP_IS_GMM_MAX_K:
+        raise RuntimeError('pyprob_hip::is_gmm_groups: 1 .. %d mixture components' % L.PP_IS_GMM_MAX_K)
+    _group_stats_ok(stats, M, 'is_gmm_groups')
+    if params_init.dtype != torch.float64 or not params_init.is_contiguous() or params_init.numel() != M * 3 * K:
+        raise RuntimeError('pyprob_hip::is_gmm_groups: params_init must be a contiguous float64 tensor of [M, 3 K]')
+    out = torch.empty((M, L.PP_IS_GMM_WIDTH(K)), dtype=torch.float64, device=lw.device)
+    ws, need = _workspace(lib.pp_is_gmm_workspace_bytes, lw.device, M, int(n_per), K)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_gmm_groups(lw.data_ptr(), x.data_ptr(), K, M, int(n_per), L.ptr(stats), params_init.data_ptr(), int(max_iter),
+                                  float(tol), float(reg_covar), gmm_check_every(), out.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_gmm_groups')
+    return out
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -929,6 +967,7 @@ _lib.impl('is_extent_groups', _is_extent_groups_hip, 'CUDA')
 _lib.impl('is_sort_groups', _is_sort_groups_hip, 'CUDA')
 _lib.impl('is_quantile_groups', _is_quantile_groups_hip, 'CUDA')
 _lib.impl('is_unique_groups', _is_unique_groups_hip, 'CUDA')
+_lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
