@@ -31,8 +31,11 @@ __device__ __forceinline__ float std_pdf(float x) { return kInvSqrt2Pi * expf(-0
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 
-// log of a mixture weight clamped to [eps, 1 - eps] (util.clamp_probs)
-__device__ __forceinline__ float log_clamped(float p) { return logf(fminf(fmaxf(p, kFp32Eps), 1.0f - kFp32Eps)); }
+// log of a mixture weight clamped to [eps, 1 - eps] (util.clamp_probs). A NaN weight stays NaN, as torch's clamp keeps it:
+// fmaxf / fminf alone would turn it into eps and a NaN logit into a finite log_prob.
+__device__ __forceinline__ float log_clamped(float p) {
+    return p == p ? logf(fminf(fmaxf(p, kFp32Eps), 1.0f - kFp32Eps)) : p;
+}
 
 // One component from the head outputs (ymu, ysd) of its mean and scale; sm, ss = sigmoid(ymu), sigmoid(ysd) are what the
 // backward of KIND 1 / 2 needs (0 for KIND 0).

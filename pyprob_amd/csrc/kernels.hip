@@ -580,14 +580,17 @@ template <int KIND>
 __device__ __forceinline__ float mixture_logprob(const MixtureParams& m, int K, float v, float low, float high,
                                                  float a[MAXK]) {
     float amax = -INFINITY;
+    bool nan = false;
 #pragma unroll
     for (int k = 0; k < MAXK; ++k)
         if (k < K) {
             float t, alpha, beta, Z;
             a[k] = log_clamped(m.p[k]) + component_logpdf<KIND>(v, m.mu[k], m.sd[k], low, high, t, alpha, beta, Z);
+            nan = nan || a[k] != a[k];
             amax = fmaxf(amax, a[k]);
         }
-    if (!(amax > -INFINITY)) return amax;  // -inf (or NaN)
+    if (nan) return NAN;                   // fmaxf drops a NaN: with every component NaN the row would pass for rescued
+    if (!(amax > -INFINITY)) return amax;  // -inf
     float s = 0.0f;
 #pragma unroll
     for (int k = 0; k < MAXK; ++k)
