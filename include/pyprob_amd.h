@@ -704,6 +704,26 @@ int pp_is_resample_groups(const double* cdf /*dev [M n_per]*/, const float* valu
                           int32_t n_per, int32_t lo, int32_t hi, int32_t n_out, uint64_t seed, uint64_t offset,
                           int64_t* index_out /*dev [M n_out] or NULL*/, float* value_out /*dev [M n_out] or NULL*/, void* stream);
 
+/* Low-variance resampling. The reference's resample is sample() repeated (pyprob/distributions/empirical.py:617-637): multinomial
+ * only. pp_is_resample_scheme_groups takes pp_is_resample_groups' arguments with a `scheme` in front of `seed`, in the same single
+ * launch (one thread per draw):
+ *   PP_RESAMPLE_MULTINOMIAL  pp_is_resample_groups itself: the same kernel, the same bits.
+ *   PP_RESAMPLE_STRATIFIED   draw j of group g sits at position p = min(fl(fl((double)j + u) / (double)n_out), 1 - 2^-53) of the
+ *                            group's mass, u the 53-bit uniform above of the block at counter offset + g n_out + j, stream id 0x52;
+ *                            target = fl(base + fl(p total)); the index, the value and the rule for a group whose total is not
+ *                            positive and finite (index -1, value NaN) are those of pp_is_resample_groups.
+ *   PP_RESAMPLE_SYSTEMATIC   the same with ONE u per group: the block at counter offset + g, stream id 0x53.
+ * With both new schemes p does not decrease in j, so the indices of a group never decrease in j. Every output is a function of the
+ * inputs alone; group g of an M-group call equals the one-group call on its slice at offset + g n_out (stratified, multinomial) or
+ * offset + g (systematic). PP_EINVAL without a launch for any other scheme and for what pp_is_resample_groups rejects. */
+#define PP_RESAMPLE_MULTINOMIAL 0
+#define PP_RESAMPLE_STRATIFIED 1
+#define PP_RESAMPLE_SYSTEMATIC 2
+int pp_is_resample_scheme_groups(const double* cdf /*dev [M n_per]*/, const float* values /*dev [M n_per] or NULL*/,
+                                 int32_t n_groups, int32_t n_per, int32_t lo, int32_t hi, int32_t n_out, int32_t scheme,
+                                 uint64_t seed, uint64_t offset, int64_t* index_out /*dev [M n_out] or NULL*/,
+                                 float* value_out /*dev [M n_out] or NULL*/, void* stream);
+
 /* Joint weighted moments of up to PP_IS_MOMENTS_MAX_COLS latent columns of a lock-step posterior call on the device. The reference
  * normalises the weights on the host (finalize, pyprob/distributions/empirical.py:298-309) and answers mean / variance as
  * expectations over the values of ONE mapped Empirical at a time (expectation :451-466, mean / variance :668-690); here the
@@ -861,6 +881,43 @@ int pp_is_unique_groups(const float* value_sorted /*dev [M n_per]*/, const float
                         const double* stats /*dev double [M, 6] or NULL*/, float* value_out /*dev [M n_per]*/,
                         int64_t* mass_out /*dev [M n_per]*/, int32_t* count_out /*dev [M n_per]*/, int32_t* runs_out /*dev [M]*/,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* The highest-posterior-density interval and the cdf at a point of one latent of a lock-step posterior call on the device. The
+ * reference has neither an HPD interval nor a cdf: its Empirical answers moments, mode, min / max and a median of 1000 resampled
+ * values (pyprob/distributions/empirical.py:668-728). Both calls take pp_is_sort_groups' value_out and counted_out and
+ * pp_is_cdf_groups over its lw_out - what pp_is_quantile_groups takes. For group g let c = counted[g, 0], v and cdf its sorted values
+ * and cumulative weights, T = cdf[c - 1].
+ *   pp_is_hpd_groups    For level L = level[l] (dev double [n_l], shared by the groups): c == 0, a T that is not positive and
+ *                       finite, or an L that is NaN or outside (0, 1]: out[g, l] = (NaN, NaN), index_out[g, l] = (-1, -1). Else
+ *                       m = fl(L T); a start i < c is VALID when cdf[i] > prev_i (prev_i = i > 0 ? cdf[i - 1] : 0: the particle has
+ *                       positive weight) and t_i = fl(prev_i + m) <= T; its end is j_i = max(i, #{k < c : cdf[k] < t_i}), that is
+ *                       numpy.searchsorted(cdf[:c], t_i, 'left') clamped from below; its width (double)v[j_i] - (double)v[i], a NaN
+ *                       width (inf - inf) counting as +inf. The result is the valid start of smallest width, ties to the smallest
+ *                       i: out[g, l] = ((double)v[i], (double)v[j_i]), index_out[g, l] = (i, j_i), positions in sorted order
+ *                       (index_out may be NULL). The first particle of positive weight is always valid, fl(L T) <= T.
+ *                       One thread per start, eight independent binary searches per thread in flight; a workgroup of 256 threads
+ *                       reduces the PP_IS_HPD_TILE starts of its tile to one (width, i, j) by wave shuffles and LDS. A group of one
+ *                       tile is finished by that launch; a longer one stores a record of 16 bytes per (level, tile) in the
+ *                       workspace and a second launch reduces them in tile order, one workgroup per (group, level).
+ *   pp_is_ecdf_groups   For point x[g, q] (dev double [M, n_x]: PER GROUP): k = #{i < c : (double)v[i] <= x} (strict != 0: < x) by
+ *                       binary search, one thread per result; rank_out[g, q] = k (may be NULL), out[g, q] = k == 0 ? 0.0 :
+ *                       fl(cdf[k - 1] / T). A NaN x, c == 0 or a T that is not positive and finite: out NaN, rank -1.
+ * Both take the [M n_per] layout, any n_per >= 1 and n_groups >= 0 (0: return 0 without a launch; more than 65535 groups are split
+ * over launches), write nothing outside their outputs and the workspace (pp_is_hpd_workspace_bytes; PP_ENOSPACE when shorter) and
+ * are dependent launches on the caller's stream: no global atomics, no workgroup waits for another. Every output is a function of
+ * the inputs alone: two calls give the same bits, and group g of an M-group call equals the one-group call on its slice. PP_EINVAL
+ * without a launch for a NULL required pointer (everything but index_out / rank_out), n_per < 1, n_groups < 0, n_l < 0, n_x < 0, or
+ * M n_per, 2 M n_l or M n_x above 2^31 - 1. pp_is_hpd_workspace_bytes returns 0 outside that envelope. */
+#define PP_IS_HPD_TILE 2048
+size_t pp_is_hpd_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_l);
+int pp_is_hpd_groups(const float* value_sorted /*dev [M n_per]*/, const double* cdf_sorted /*dev [M n_per]*/,
+                     const int32_t* counted /*dev [M, 2]*/, int32_t n_groups, int32_t n_per, const double* level /*dev [n_l]*/,
+                     int32_t n_l, double* out /*dev [M, n_l, 2]*/, int32_t* index_out /*dev [M, n_l, 2] or NULL*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int pp_is_ecdf_groups(const float* value_sorted /*dev [M n_per]*/, const double* cdf_sorted /*dev [M n_per]*/,
+                      const int32_t* counted /*dev [M, 2]*/, int32_t n_groups, int32_t n_per, const double* x /*dev [M, n_x]*/,
+                      int32_t n_x, int32_t strict, double* out /*dev [M, n_x]*/, int32_t* rank_out /*dev [M, n_x] or NULL*/,
+                      void* stream);
 
 /* Weighted Gaussian-mixture EM over one latent of a lock-step posterior call on the device. The reference's density_estimate
  * (pyprob/distributions/empirical.py:795-807) resamples 1000 values on the host, drops the weights and fits scikit-learn's

@@ -25,7 +25,8 @@ def __getattr__(name):
         from .distributions import joint_batch
         globals()[name] = joint_batch
         return joint_batch
-    if name in ('histogram_batch', 'Histogram', 'Histogram2D', 'quantile_batch', 'density_estimate_batch', 'MixtureFit'):
+    if name in ('histogram_batch', 'Histogram', 'Histogram2D', 'quantile_batch', 'density_estimate_batch', 'MixtureFit',
+                'hpd_batch', 'cdf_batch'):
         from . import distributions
         value = getattr(distributions, name)
         globals()[name] = value

@@ -6,7 +6,8 @@
 // (resample, :617-637). Here
 //   pp_is_cdf_groups       writes cdf[g, i] = the sum of the weights of particles 0 .. i of group g in fp64 (is_groups.hpp: what
 //                          a particle weighs and which particles weigh nothing), and
-//   pp_is_resample_groups  draws n_out indices per group by inverting that cdf at Philox uniforms of 53 bits, one thread per draw.
+//   pp_is_resample_groups  draws n_out indices per group by inverting that cdf at Philox uniforms of 53 bits, one thread per draw;
+//   pp_is_resample_scheme_groups  the same launch shape for stratified and systematic positions (resample_scheme_kernel).
 //
 // ORDER OF THE SUMS. cdf[g, i] is built as  tile offset + (wave offset + (lane offset + running sum of the thread's own eight)),
 // and every offset is carried FORWARD: the offset of lane l + 1 is (offset of lane l) + (total of lane l), rounded once - the
@@ -166,6 +167,46 @@ __global__ __launch_bounds__(256) void resample_kernel(const double* __restrict_
     }
 }
 
+// The low-variance schemes, one thread per draw as above. Draw j of group g sits at position p = min((j + u) / n_out, 1 - 2^-53) of
+// the group's mass (two roundings before the minimum) and takes target = base + p * total (two more) through the search of
+// resample_kernel. STRATIFIED: u is the 53-bit uniform of the block at counter offset + g n_out + j, stream 0x52 - one per draw.
+// SYSTEMATIC: ONE u per group, from the block at counter offset + g, stream 0x53 (every thread of the group regenerates it).
+// p never decreases in j, so neither do the targets and the indices of a group.
+__global__ __launch_bounds__(256) void resample_scheme_kernel(const double* __restrict__ cdf, const float* __restrict__ values,
+                                                              int n_per, int lo, int hi, int n_out, int64_t outputs, int scheme,
+                                                              uint64_t seed, uint64_t offset, int64_t* __restrict__ index_out,
+                                                              float* __restrict__ value_out) {
+    for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < outputs; o += (int64_t)gridDim.x * 256) {
+        const int64_t g = o / n_out;
+        const int64_t j = o - g * n_out;
+        const double* c = cdf + g * n_per;
+        const double base = lo > 0 ? c[lo - 1] : 0.0;
+        const double total = c[hi - 1] - base;
+        int64_t idx = -1;
+        float v = NAN;
+        if (total > 0.0 && total < INFINITY) {
+            const bool systematic = scheme == PP_RESAMPLE_SYSTEMATIC;
+            Philox rng(seed, offset + (uint64_t)(systematic ? g : o), systematic ? 0x53 : 0x52);
+            uint32_t r[4];
+            rng.next(r);
+            const uint64_t bits = ((uint64_t)(r[0] >> 5) << 26) + (uint64_t)(r[1] >> 6);
+            const double u = __dmul_rn(__dadd_rn((double)bits, 0.5), 0x1.0p-53);
+            const double p = fmin(__ddiv_rn(__dadd_rn((double)j, u), (double)n_out), 1.0 - 0x1.0p-53);
+            const double target = __dadd_rn(base, __dmul_rn(p, total));
+            int a = lo, b = hi;      // the first i in [lo, hi] with cdf[i] > target (hi: none)
+            while (a < b) {
+                const int mid = a + ((b - a) >> 1);
+                if (c[mid] <= target) a = mid + 1;
+                else b = mid;
+            }
+            idx = min(a, hi - 1);
+            if (value_out) v = values[g * n_per + idx];
+        }
+        if (index_out) index_out[o] = idx;
+        if (value_out) value_out[o] = v;
+    }
+}
+
 }  // namespace
 
 int is_cdf_groups(const float* lw, int M, int n_per, const double* stats, double* cdf, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -207,6 +248,28 @@ int is_resample_groups(const double* cdf, const float* values, int M, int n_per,
     return 0;
 }
 
+int is_resample_scheme_groups(const double* cdf, const float* values, int M, int n_per, int lo, int hi, int n_out, int scheme,
+                              uint64_t seed, uint64_t offset, int64_t* index_out, float* value_out, hipStream_t st) {
+    PP_CHECK_ARG(scheme == PP_RESAMPLE_MULTINOMIAL || scheme == PP_RESAMPLE_STRATIFIED || scheme == PP_RESAMPLE_SYSTEMATIC,
+                 "pp_is_resample_scheme_groups: scheme is PP_RESAMPLE_MULTINOMIAL, _STRATIFIED or _SYSTEMATIC");
+    if (scheme == PP_RESAMPLE_MULTINOMIAL)
+        return is_resample_groups(cdf, values, M, n_per, lo, hi, n_out, seed, offset, index_out, value_out, st);
+    PP_CHECK_ARG(cdf, "pp_is_resample_scheme_groups: null pointer (the cdf is required)");
+    PP_CHECK_ARG(n_per >= 1 && M >= 0 && n_out >= 0, "pp_is_resample_scheme_groups: n_per >= 1, n_groups >= 0 and n_out >= 0");
+    PP_CHECK_ARG(0 <= lo && lo < hi && hi <= n_per, "pp_is_resample_scheme_groups: an index range 0 <= lo < hi <= n_per");
+    PP_CHECK_ARG(groups_count_ok(M, n_per) && groups_count_ok(M, n_out),
+                 "pp_is_resample_scheme_groups: more than 2^31 - 1 particles or draws per call: shard the groups");
+    PP_CHECK_ARG(index_out || value_out, "pp_is_resample_scheme_groups: index_out or value_out (or both)");
+    PP_CHECK_ARG(!value_out || values, "pp_is_resample_scheme_groups: value_out needs the values");
+    const int64_t outputs = (int64_t)M * n_out;
+    if (outputs == 0) return 0;
+    const int blocks = (int)std::min<int64_t>(RESAMPLE_BLOCKS, (outputs + 255) / 256);
+    hipLaunchKernelGGL(resample_scheme_kernel, dim3(blocks), dim3(256), 0, st, cdf, values, n_per, lo, hi, n_out, outputs, scheme, seed,
+                       offset, index_out, value_out);
+    PP_LAUNCH_CHECK("pp_is_resample_scheme_groups");
+    return 0;
+}
+
 }  // namespace pp
 
 extern "C" {
@@ -227,6 +290,13 @@ int pp_is_resample_groups(const double* cdf, const float* values, int32_t n_grou
                           int32_t n_out, uint64_t seed, uint64_t offset, int64_t* index_out, float* value_out, void* stream) {
     return pp::is_resample_groups(cdf, values, n_groups, n_per, lo, hi, n_out, seed, offset, index_out, value_out,
                                   pp::as_stream(stream));
+}
+
+int pp_is_resample_scheme_groups(const double* cdf, const float* values, int32_t n_groups, int32_t n_per, int32_t lo, int32_t hi,
+                                 int32_t n_out, int32_t scheme, uint64_t seed, uint64_t offset, int64_t* index_out, float* value_out,
+                                 void* stream) {
+    return pp::is_resample_scheme_groups(cdf, values, n_groups, n_per, lo, hi, n_out, scheme, seed, offset, index_out, value_out,
+                                         pp::as_stream(stream));
 }
 
 }  // extern "C"

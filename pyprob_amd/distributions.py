@@ -854,14 +854,19 @@ class Empirical:
             return self._value(int(index))
         raise RuntimeError('Cannot use the given value ({}) as index'.format(index))
 
-    def _draw_indices(self, n, lo=None, hi=None):
+    def _draw_indices(self, n, lo=None, hi=None, scheme='multinomial'):
         """n indices distributed like the (renormalised) weights of [lo, hi); randomness from torch's global generator
-        (so pyprob.seed / torch.manual_seed make it reproducible)."""
+        (so pyprob.seed / torch.manual_seed make it reproducible). scheme 'stratified' / 'systematic': the positions
+        min((j + u_j) / n, 1 - 2^-53) of pp_is_resample_scheme_groups, u_j one uniform per draw / one for all."""
         lo = 0 if lo is None else lo
         hi = self.length if hi is None else hi
         if hi <= lo:
             raise ValueError('empty index range')
-        u = torch.rand(n, dtype=torch.float64).numpy()
+        if _scheme_id(scheme) == 0:
+            u = torch.rand(n, dtype=torch.float64).numpy()
+        else:
+            u = torch.rand(n if scheme == 'stratified' else 1, dtype=torch.float64).numpy()
+            u = np.minimum((np.arange(n, dtype=np.float64) + u) / float(n), 1.0 - 2.0 ** -53)
         if self._uniform:
             return lo + np.minimum((u * (hi - lo)).astype(np.int64), hi - lo - 1)
         if self._cum is None:
@@ -898,18 +903,18 @@ class Empirical:
             raise ValueError('index range [%d, %d) outside the %d values' % (lo, hi, self.length))
         return lo, hi
 
-    def _device_draw(self, n, min_index, max_index, seed, offset):
+    def _device_draw(self, n, min_index, max_index, seed, offset, scheme='multinomial'):
         """n values drawn on the device according to the weights of [min_index, max_index): one launch, a device tensor."""
         from .ops import ops
         lo, hi = self._index_range(min_index, max_index)
         # (the key from torch's global generator, as PriorLockStep takes it: pyprob.seed / torch.manual_seed reproduce a run)
         key = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
-        return ops.is_resample_groups(self._device_cdf(), self._values, self.length, lo, hi, int(n), key, int(offset), False)[1]
+        return _resample_op(self._device_cdf(), self._values, self.length, lo, hi, int(n), scheme, key, int(offset), False)[1]
 
-    def _resampled(self, values, zeros, stats, num_samples, ess_before):
+    def _resampled(self, values, zeros, stats, num_samples, ess_before, scheme='multinomial'):
         out = Empirical.from_device(values, zeros, stats, name=self.name)
         out._metadata = dict(self._metadata)
-        out.add_metadata(op='resample', length=self.length, num_samples=int(num_samples), ess_before=ess_before)
+        out.add_metadata(op='resample', length=self.length, num_samples=int(num_samples), ess_before=ess_before, **_scheme_meta(scheme))
         return out
 
     def sample(self, min_index=None, max_index=None):
@@ -1058,7 +1063,7 @@ class Empirical:
         lw = self._all_lw()
         return _joint_rows(chosen, _moment_rows(lw, cols, lw.numel(), self._group_stats_row()))[0]
 
-    def resample_joint(self, num_samples, addresses=None, seed=None, offset=0):
+    def resample_joint(self, num_samples, addresses=None, seed=None, offset=0, scheme='multinomial'):
         """num_samples JOINT draws of several latents: ONE index per sample from the weights (pp_is_resample_groups, the Philox
         contract of resample: draw k = key `seed`, counter offset + k), then row index[k] of every requested column. Returns
         {address: device tensor [num_samples]} plus 'index' (int64, into ALL particles of the call: the rows of the statement
@@ -1066,8 +1071,9 @@ class Empirical:
         PROVIDED the call dropped no particle. Where it dropped particles with a non-finite log-weight, the posterior's own
         particles are renumbered and resample() indexes those; here the cumulative weights run over all particles with weight 0
         for the dropped ones, so no draw lands on them, row k of every column is still one particle's, and the draws follow the
-        same distribution - but they are another stream than resample()'s."""
+        same distribution - but they are another stream than resample()'s. scheme: as for resample."""
         from .ops import ops
+        _scheme_id(scheme)
         if int(num_samples) < 1:
             raise ValueError('num_samples must be positive')
         chosen, cols = self._joint_columns(addresses)
@@ -1080,7 +1086,7 @@ class Empirical:
                 cdf = self.__dict__['_all_cdf'] = ops.is_cdf_groups(lw, lw.numel(), None)
         key = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
         n = lw.numel()
-        index = ops.is_resample_groups(cdf, None, n, 0, n, int(num_samples), key, int(offset), True)[0]
+        index = _resample_op(cdf, None, n, 0, n, int(num_samples), scheme, key, int(offset), True)[0]
         out = {a: c.index_select(0, index) for a, c in zip(chosen, cols)}
         out['index'] = index
         return out
@@ -1198,6 +1204,60 @@ class Empirical:
             raise ValueError('level lies in (0, 1]')
         lo, hi = self.quantile([(1.0 - level) / 2.0, (1.0 + level) / 2.0])
         return float(lo), float(hi)
+
+    def hpd_interval(self, level=0.9):
+        """The highest-posterior-density interval: the SHORTEST interval [lo, hi] between two particles that holds the mass
+        `level` - (lo, hi) floats for a scalar level in (0, 1], float64 numpy [L, 2] for a sequence. With the counted particles in
+        ascending order of value, W_k their cumulative weights (quantile's) and T the last: among the particles i of positive
+        weight with fl(W_{i-1} + fl(level T)) <= T, the one whose window up to the first particle j with W_j >= that target is
+        narrowest, ties to the smallest i. On a skewed or one-sided posterior it differs from the equal-tailed credible_interval:
+        an Exponential's 90 % interval starts at its minimum. A posterior of several modes gets ONE interval (regions of more
+        than one interval are not built). Nothing counted, or a total that is not positive and finite: NaN.
+
+        A device-backed Empirical is sorted once (as for quantile); every call is then one operator call (pp_is_hpd_groups: a
+        thread per start, a binary search each) and one copy of 2 L doubles. Every other Empirical, and all of them under
+        PP_EMPIRICAL_DEVICE=0, computes the same definition in float64 numpy."""
+        self._check_finalized()
+        levels, scalar = _hpd_levels(level)
+        if self.length == 0:
+            raise ValueError('hpd_interval of an empty Empirical')
+        if self._device_backed():
+            from .ops import ops
+            value, _, _, counted, cdf = self._device_sorted()
+            out = ops.is_hpd_groups(value, cdf, counted, self.length, torch.from_numpy(levels).to(value.device))[0].cpu().numpy()[0]
+        else:
+            lw, x = self._host_scalars()
+            if x is None:
+                raise ValueError('hpd_interval needs scalar values')
+            out = _host_hpd(lw, x, levels)
+        return (float(out[0, 0]), float(out[0, 1])) if scalar else out
+
+    def cdf(self, x, strict=False):
+        """The posterior cdf P(X <= x) (strict: P(X < x)) at a scalar x (a float) or a sequence (float64 numpy of its shape [Q]): the
+        cumulative weight of the counted particles (finite log-weight, value not NaN) whose value is <= x, over their total - the
+        forward map of quantile(): cdf(quantile(q)) >= q up to two roundings. A NaN x, nothing counted or a total that is not
+        positive and finite: NaN. Device-backed Empiricals answer from the sorted particles (as quantile) by one operator call
+        (pp_is_ecdf_groups, a binary search per point) and one copy; every other Empirical, and all of them under
+        PP_EMPIRICAL_DEVICE=0, in float64 numpy."""
+        self._check_finalized()
+        xs = np.asarray(x, np.float64)
+        scalar = xs.ndim == 0
+        if xs.ndim > 1:
+            raise ValueError('cdf takes a scalar or a sequence of points')
+        xs = np.ascontiguousarray(xs.reshape(-1))
+        if self.length == 0:
+            raise ValueError('cdf of an empty Empirical')
+        if self._device_backed():
+            from .ops import ops
+            value, _, _, counted, cdf = self._device_sorted()
+            out = ops.is_ecdf_groups(value, cdf, counted, self.length, torch.from_numpy(xs[None]).to(value.device),
+                                     bool(strict))[0].cpu().numpy()[0]
+        else:
+            lw, v = self._host_scalars()
+            if v is None:
+                raise ValueError('cdf needs scalar values')
+            out = _host_ecdf(lw, v, xs, strict)
+        return float(out[0]) if scalar else out
 
     def argsort(self):
         """The indices of the counted particles (finite log-weight, value not NaN) in stable ascending order of value: a device
@@ -1336,7 +1396,7 @@ class Empirical:
         warnings.warn('Empirical.filter will be deprecated in future releases. Use Empirical.condition instead.')
         return self.condition(*args, **kwargs)
 
-    def resample(self, num_samples, map_func=None, min_index=None, max_index=None, seed=None, offset=0):
+    def resample(self, num_samples, map_func=None, min_index=None, max_index=None, seed=None, offset=0, scheme='multinomial'):
         """num_samples unweighted draws (empirical.py:617-637).
 
         A device-backed Empirical (the result of a lock-step posterior call) is resampled on the device: its cumulative weights
@@ -1346,25 +1406,32 @@ class Empirical:
         block of key `seed` and counter `offset + j`; seed=None takes the key from torch's global generator, so pyprob.seed /
         torch.manual_seed reproduce a run. These draws are a DIFFERENT STREAM of the same distribution as the host route's, which
         draws from torch's generator directly, ignores seed / offset, and serves every other Empirical (and all of them under
-        PP_EMPIRICAL_DEVICE=0)."""
+        PP_EMPIRICAL_DEVICE=0).
+
+        scheme: 'multinomial' (independent draws, the reference's), 'stratified' (draw j at position (j + u_j) / num_samples of
+        the mass, one uniform per draw) or 'systematic' ((j + u) / num_samples, ONE uniform for all draws: counter `offset`,
+        stream 0x53) - pp_is_resample_scheme_groups, the same single launch. The two low-variance schemes return the particles in
+        index order and every particle floor(n w) or ceil(n w) times (systematic; stratified within 2); the metadata names a
+        scheme other than the default."""
         self._check_finalized()
+        _scheme_id(scheme)
         if self._device_backed():
             if int(num_samples) < 1:
                 raise ValueError('num_samples must be positive')
             ess = self.effective_sample_size
-            drawn = self._device_draw(num_samples, min_index, max_index, seed, offset)
+            drawn = self._device_draw(num_samples, min_index, max_index, seed, offset, scheme)
             if map_func is not None:
                 out = [map_func(v) for v in drawn.cpu().unbind(0)]
                 return self._like(out, np.zeros(len(out)), op='resample', length=self.length, num_samples=int(num_samples),
-                                  ess_before=ess)
+                                  ess_before=ess, **_scheme_meta(scheme))
             zeros = torch.zeros_like(drawn)
-            return self._resampled(drawn, zeros, _device_stats(zeros, drawn), num_samples, ess)
+            return self._resampled(drawn, zeros, _device_stats(zeros, drawn), num_samples, ess, scheme)
         ess = self.effective_sample_size
-        idx = self._draw_indices(int(num_samples), min_index, max_index)
+        idx = self._draw_indices(int(num_samples), min_index, max_index, scheme)
         vals = self.get_values()
         out = [vals[i] if map_func is None else map_func(vals[i]) for i in idx]
         return self._like(out, np.zeros(len(out)), op='resample', length=self.length, num_samples=int(num_samples),
-                          ess_before=ess)
+                          ess_before=ess, **_scheme_meta(scheme))
 
     def thin(self, num_samples, map_func=None, min_index=None, max_index=None):
         self._check_finalized()
@@ -1843,6 +1910,93 @@ def _host_quantiles(lw, x, qs):
     return x[order][np.minimum(k, len(order) - 1)].astype(np.float64)
 
 
+def _host_sorted_cdf(lw, x):
+    """(values in sorted order, their cumulative weights) of the counted particles in float64 numpy; (None, None) where nothing
+    is counted or the total is not positive and finite."""
+    order = _host_order(lw, x)
+    if len(order) == 0:
+        return None, None
+    cdf = np.cumsum(np.exp(lw[order] - np.max(lw[np.isfinite(lw)])))
+    if not (cdf[-1] > 0 and np.isfinite(cdf[-1])):
+        return None, None
+    return x[order].astype(np.float64), cdf
+
+
+def _hpd_search(v, cdf, levels):
+    """pp_is_hpd_groups' definition on sorted values v and their cumulative weights cdf (float64 [c]): ([L, 2] values, [L, 2]
+    positions)."""
+    out, pos = np.full((len(levels), 2), np.nan), np.full((len(levels), 2), -1, np.int64)
+    c = len(cdf)
+    if c == 0 or not (cdf[-1] > 0 and np.isfinite(cdf[-1])):
+        return out, pos
+    T = cdf[-1]
+    prev = np.concatenate([[0.0], cdf[:-1]])
+    for l, L in enumerate(levels):
+        if not (L > 0 and L <= 1):
+            continue
+        t = prev + L * T
+        starts = np.nonzero((cdf > prev) & (t <= T))[0]
+        ends = np.maximum(starts, np.searchsorted(cdf, t[starts], side='left'))
+        with np.errstate(invalid='ignore'):
+            width = v[ends].astype(np.float64) - v[starts].astype(np.float64)
+        width = np.where(np.isnan(width), np.inf, width)
+        k = int(np.argmin(width))                 # (the first minimum: ties go to the smallest start)
+        pos[l] = starts[k], ends[k]
+        out[l] = v[starts[k]], v[ends[k]]
+    return out, pos
+
+
+def _host_hpd(lw, x, levels):
+    """pp_is_hpd_groups' definition in float64 numpy for one particle set: [L, 2]."""
+    v, cdf = _host_sorted_cdf(lw, x)
+    if v is None:
+        return np.full((len(levels), 2), np.nan)
+    return _hpd_search(v, cdf, levels)[0]
+
+
+def _host_ecdf(lw, x, xs, strict):
+    """pp_is_ecdf_groups' definition in float64 numpy for one particle set."""
+    v, cdf = _host_sorted_cdf(lw, x)
+    if v is None:
+        return np.full(len(xs), np.nan)
+    k = np.searchsorted(v, np.where(np.isnan(xs), 0.0, xs), side='left' if strict else 'right')
+    out = np.where(k == 0, 0.0, cdf[np.maximum(k, 1) - 1] / cdf[-1])
+    return np.where(np.isnan(xs), np.nan, out)
+
+
+def _hpd_levels(level):
+    """(float64 [L] levels, whether a scalar was given); levels outside (0, 1] raise."""
+    levels = np.asarray(level, np.float64)
+    scalar = levels.ndim == 0
+    if levels.ndim > 1:
+        raise ValueError('level lies in (0, 1] (a scalar or a sequence)')
+    levels = np.ascontiguousarray(levels.reshape(-1))
+    if not np.all((levels > 0) & (levels <= 1)):
+        raise ValueError('level lies in (0, 1] (a scalar or a sequence)')
+    return levels, scalar
+
+
+_SCHEMES = {'multinomial': 0, 'stratified': 1, 'systematic': 2}      # PP_RESAMPLE_* (include/pyprob_amd.h)
+
+
+def _scheme_id(scheme):
+    if scheme not in _SCHEMES:
+        raise ValueError('scheme is one of {}'.format(', '.join(repr(k) for k in _SCHEMES)))
+    return _SCHEMES[scheme]
+
+
+def _scheme_meta(scheme):
+    return {} if scheme == 'multinomial' else {'scheme': scheme}
+
+
+def _resample_op(cdf, values, n_per, lo, hi, n_out, scheme, key, offset, want_index):
+    """The draw operator of a scheme: the default keeps the operator (and the bits) it always took."""
+    from .ops import ops
+    if _scheme_id(scheme) == 0:
+        return ops.is_resample_groups(cdf, values, n_per, lo, hi, n_out, key, offset, want_index)
+    return ops.is_resample_scheme_groups(cdf, values, n_per, lo, hi, n_out, _SCHEMES[scheme], key, offset, want_index)
+
+
 def _batch_column(posteriors, address):
     """(lw, column, N, group statistics) where the posteriors are the M groups of ONE Model.posterior_results_batch execution in
     order (recognised as histogram_batch recognises them) and `address` names the value forward() returned (None) or a column of
@@ -1890,6 +2044,53 @@ def quantile_batch(posteriors, q, address=None):
     value, lw_sorted, _, counted = ops.is_sort_groups(lw, column, N, group_stats)
     cdf = ops.is_cdf_groups(lw_sorted, N, group_stats)
     return ops.is_quantile_groups(value, cdf, counted, N, torch.from_numpy(qs).to(lw.device)).cpu().numpy()
+
+
+def hpd_batch(posteriors, level=0.9, address=None):
+    """numpy.stack([p.hpd_interval(level) for p in posteriors]) as float64 [M, 2] (a scalar level) or [M, L, 2], or with address=
+    [p.marginal(address).hpd_interval(level) ...] - and, where the posteriors are the M groups of ONE
+    Model.posterior_results_batch execution in order (recognised as quantile_batch recognises them), the same numbers bit for bit
+    from one pp_is_sort_groups call, one pp_is_cdf_groups call over the sorted log-weights, ONE pp_is_hpd_groups call and one
+    device-to-host copy. Anything else is served by the loop."""
+    posteriors = list(posteriors)
+    levels, scalar = _hpd_levels(level)
+    if not posteriors:
+        return np.zeros((0, 2) if scalar else (0, len(levels), 2))
+    found = _batch_column(posteriors, address)
+    if found is None:
+        out = np.stack([np.asarray((p if address is None else p.marginal(address)).hpd_interval(levels)) for p in posteriors])
+    else:
+        from .ops import ops
+        lw, column, N, group_stats = found
+        value, lw_sorted, _, counted = ops.is_sort_groups(lw, column, N, group_stats)
+        cdf = ops.is_cdf_groups(lw_sorted, N, group_stats)
+        out = ops.is_hpd_groups(value, cdf, counted, N, torch.from_numpy(levels).to(lw.device))[0].cpu().numpy()
+    return out[:, 0] if scalar else out
+
+
+def cdf_batch(posteriors, x, address=None, strict=False):
+    """[p.cdf(x[g], strict) for g, p in enumerate(posteriors)] as float64 numpy of x's shape - x is [M] (one point per posterior: the
+    ground truth of a calibration check) or [M, Q] - or with address= [p.marginal(address).cdf(x[g], strict) ...]; and, where the
+    posteriors are the M groups of ONE Model.posterior_results_batch execution in order, the same numbers bit for bit from one
+    sort, one cdf over the sorted log-weights, ONE pp_is_ecdf_groups call (every group with its own points) and one copy."""
+    posteriors = list(posteriors)
+    xs = np.asarray(x, np.float64)
+    if xs.ndim not in (1, 2) or xs.shape[0] != len(posteriors):
+        raise ValueError('x is [M] or [M, Q]: one row of points per posterior')
+    if not posteriors:
+        return np.zeros(xs.shape)
+    pts = np.ascontiguousarray(xs.reshape(len(posteriors), -1))
+    found = _batch_column(posteriors, address)
+    if found is None:
+        out = np.stack([np.asarray((p if address is None else p.marginal(address)).cdf(pts[g], strict))
+                        for g, p in enumerate(posteriors)])
+    else:
+        from .ops import ops
+        lw, column, N, group_stats = found
+        value, lw_sorted, _, counted = ops.is_sort_groups(lw, column, N, group_stats)
+        cdf = ops.is_cdf_groups(lw_sorted, N, group_stats)
+        out = ops.is_ecdf_groups(value, cdf, counted, N, torch.from_numpy(pts).to(lw.device), bool(strict))[0].cpu().numpy()
+    return out.reshape(xs.shape)
 
 
 _GMM_MAX_K = 16      # PP_IS_GMM_MAX_K (include/pyprob_amd.h)
@@ -2055,13 +2256,15 @@ def joint_batch(posteriors, addresses=None):
     return _joint_rows(chosen, _moment_rows(lw, [whole[a] for a in chosen], N, group_stats))
 
 
-def resample_batch(posteriors, num_samples, seed=None, offset=0):
-    """[p.resample(num_samples, seed=seed, offset=offset + g * num_samples) for g, p in enumerate(posteriors)] - and, where the
+def resample_batch(posteriors, num_samples, seed=None, offset=0, scheme='multinomial'):
+    """[p.resample(num_samples, seed=seed, offset=offset + g * num_samples) for g, p in enumerate(posteriors)] (scheme='systematic',
+    which takes ONE uniform per group: offset + g; scheme as for Empirical.resample) - and, where the
     posteriors are the M groups of ONE Model.posterior_results_batch execution in order, the same values bit for bit from one
     pp_is_cdf_groups and one pp_is_resample_groups launch over all groups, with the statistics of the M resampled groups from the
     grouped statistics pass in one device-to-host copy. seed=None: one key from torch's global generator for the whole list."""
     posteriors = list(posteriors)
     n = int(num_samples)
+    _scheme_id(scheme)
     if not posteriors:
         return []
     key = int(torch.randint(0, 2 ** 62, (1,)).item()) if seed is None else int(seed)
@@ -2073,7 +2276,10 @@ def resample_batch(posteriors, num_samples, seed=None, offset=0):
         fast = fast and b is not None and b[0] is first[0] and b[1] is first[1] and b[2] is first[2] and b[3] == g and \
             p._device_backed() and p.__dict__.get('_batch_runner') is not None
     if not fast:
-        return [p.resample(n, seed=key, offset=int(offset) + g * n) for g, p in enumerate(posteriors)]
+        if scheme == 'multinomial':
+            return [p.resample(n, seed=key, offset=int(offset) + g * n) for g, p in enumerate(posteriors)]
+        step = 1 if scheme == 'systematic' else n
+        return [p.resample(n, seed=key, offset=int(offset) + g * step, scheme=scheme) for g, p in enumerate(posteriors)]
     from .ops import ops
     values, lw, group_stats, _, N = first
     cdf = posteriors[0].__dict__.get('_batch_cdf')
@@ -2081,10 +2287,10 @@ def resample_batch(posteriors, num_samples, seed=None, offset=0):
         cdf = posteriors[0].__dict__['_batch_cdf'] = ops.is_cdf_groups(lw, N, group_stats)
         for p, part in zip(posteriors, cdf.split(N)):
             p.__dict__.setdefault('_dev_cdf', part)
-    drawn = ops.is_resample_groups(cdf, values, N, 0, N, n, key, int(offset), False)[1]
+    drawn = _resample_op(cdf, values, N, 0, N, n, scheme, key, int(offset), False)[1]
     runner = posteriors[0]._batch_runner
     zeros = torch.zeros_like(drawn)
     stats = runner.fused_groups(None, n, None, [], drawn, zeros, False, stats=True).cpu().numpy()
     d_parts, z_parts = drawn.split(n), zeros.split(n)
-    return [p._resampled(d_parts[g], z_parts[g], runner._stats_dict(stats[g]), n, p.effective_sample_size)
+    return [p._resampled(d_parts[g], z_parts[g], runner._stats_dict(stats[g]), n, p.effective_sample_size, scheme)
             for g, p in enumerate(posteriors)]

@@ -25,12 +25,15 @@ kernels for these operators from tests/, to execute the host logic above them wi
     mix_draw        Mixture.sample (component selection + draw, Philox) pyprob/distributions/mixture.py:47-63
     is_cdf_groups       Empirical.finalize's weights as a running sum per group  pyprob/distributions/empirical.py:298-309
     is_resample_groups  Empirical.sample / resample: multinomial draws (Philox)   pyprob/distributions/empirical.py:392-408, 617-637
+    is_resample_scheme_groups  the same with stratified / systematic positions (one launch)   pyprob/distributions/empirical.py:617-637
     is_moments_groups   weighted first and second moments of several latents per group   pyprob/distributions/empirical.py:298-309, 451-466, 668-690
     is_hist_groups      weighted 1-D / 2-D histogram of a latent (pair) per group, fixed point   pyprob/distributions/empirical.py:298-309, 889-914
     is_extent_groups    minimum, maximum and NaN count of a latent per group             pyprob/distributions/empirical.py:770-794
     is_sort_groups      the particles of every group in order of value (stable radix sort)   pyprob/distributions/empirical.py:714-728, 809-834
     is_quantile_groups  exact weighted quantiles over the sorted particles (inverted cdf)     pyprob/distributions/empirical.py:714-728
     is_unique_groups    distinct values with fixed-point masses and counts (combine_duplicates)   pyprob/distributions/empirical.py:809-834
+    is_hpd_groups       highest-posterior-density interval over the sorted particles (the reference has none)   pyprob/distributions/empirical.py:668-728
+    is_ecdf_groups      the posterior cdf at points given per group (the reference has none)      pyprob/distributions/empirical.py:668-728
     is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -85,6 +88,8 @@ _lib.define('is_stats(Tensor lw, Tensor? x, Tensor(a!) scratch) -> Tensor')
 _lib.define('is_cdf_groups(Tensor lw, int n_per, Tensor? stats) -> Tensor')
 _lib.define('is_resample_groups(Tensor cdf, Tensor? values, int n_per, int lo, int hi, int n_out, int seed, int offset, '
             'bool want_index) -> (Tensor, Tensor)')
+_lib.define('is_resample_scheme_groups(Tensor cdf, Tensor? values, int n_per, int lo, int hi, int n_out, int scheme, int seed, '
+            'int offset, bool want_index) -> (Tensor, Tensor)')
 _lib.define('is_moments_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? stats) -> Tensor')
 _lib.define('is_hist_groups(Tensor lw, Tensor x, Tensor? y, int n_per, Tensor edges_x, Tensor? edges_y, Tensor? stats) -> Tensor')
 _lib.define('is_extent_groups(Tensor lw, Tensor x, int n_per) -> Tensor')
@@ -92,6 +97,9 @@ _lib.define('is_sort_groups(Tensor lw, Tensor x, int n_per, Tensor? stats) -> (T
 _lib.define('is_quantile_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor q) -> Tensor')
 _lib.define('is_unique_groups(Tensor value_sorted, Tensor lw_sorted, Tensor counted, int n_per, Tensor? stats) -> '
             '(Tensor, Tensor, Tensor, Tensor)')
+_lib.define('is_hpd_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor level) -> (Tensor, Tensor)')
+_lib.define('is_ecdf_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor x, bool strict) -> '
+            '(Tensor, Tensor)')
 _lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Tensor? stats, Tensor params_init, int max_iter, '
             'float tol, float reg_covar) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -765,6 +773,27 @@ def _is_resample_groups_hip(cdf, values, n_per, lo, hi, n_out, seed, offset, wan
     return index, value
 
 
+def _is_resample_scheme_groups_hip(cdf, values, n_per, lo, hi, n_out, scheme, seed, offset, want_index):
+    """is_resample_groups with a scheme (lib.PP_RESAMPLE_MULTINOMIAL / _STRATIFIED / _SYSTEMATIC): pp_is_resample_scheme_groups."""
+    lib = L.load()
+    _same_device(cdf, values)
+    if cdf.dtype != torch.float64:
+        raise RuntimeError('pyprob_hip::is_resample_scheme_groups: cdf must be float64 (is_cdf_groups)')
+    M = _groups_of(cdf, n_per, 'is_resample_scheme_groups')
+    if values is not None and _f32(values, 'values').numel() != cdf.numel():
+        raise RuntimeError('pyprob_hip::is_resample_scheme_groups: values must have the cdf\'s M * n_per elements')
+    n_out = int(n_out)
+    index = torch.empty(M * max(n_out, 0) if want_index else 0, dtype=torch.int64, device=cdf.device)
+    value = torch.empty(M * max(n_out, 0) if values is not None else 0, dtype=torch.float32, device=cdf.device)
+    with torch.cuda.device(cdf.device):
+        rc = lib.pp_is_resample_scheme_groups(cdf.data_ptr(), L.ptr(values), M, int(n_per), int(lo), int(hi), n_out, int(scheme),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                              index.data_ptr() if want_index else None,
+                                              value.data_ptr() if values is not None else None, _stream(cdf))
+    L.check(rc, 'pp_is_resample_scheme_groups')
+    return index, value
+
+
 def _is_moments_groups_hip(lw, cols, n_per, stats):
     """[M, PP_IS_MOMENTS_WIDTH(J)] (float64): the weight sums, pivots, first and second moments about the pivots of the J columns
     over each of the M groups of n_per particles (pp_is_moments_groups). stats: as for is_cdf_groups."""
@@ -884,6 +913,57 @@ def _is_quantile_groups_hip(value_sorted, cdf_sorted, counted, n_per, q):
     return out
 
 
+def _sorted_ok(value_sorted, cdf_sorted, counted, n_per, what):
+    M = _groups_of(_f32(value_sorted, 'value_sorted'), n_per, what)
+    if cdf_sorted.dtype != torch.float64 or cdf_sorted.dim() != 1 or cdf_sorted.numel() != value_sorted.numel() or \
+            not cdf_sorted.is_contiguous():
+        raise RuntimeError('pyprob_hip::%s: cdf_sorted must be a contiguous float64 tensor of the values\' M * n_per elements '
+                           '(is_cdf_groups)' % what)
+    _counted_ok(counted, M, what)
+    return M
+
+
+def _is_hpd_groups_hip(value_sorted, cdf_sorted, counted, n_per, level):
+    """(interval float64 [M, L, 2], index int32 [M, L, 2]): the highest-posterior-density interval of every level (float64 [L],
+    shared by the groups) of each of the M groups of n_per sorted particles and its two positions in sorted order
+    (pp_is_hpd_groups); cdf_sorted = is_cdf_groups over the sorted log-weights."""
+    lib = L.load()
+    _same_device(value_sorted, cdf_sorted, counted, level)
+    M = _sorted_ok(value_sorted, cdf_sorted, counted, n_per, 'is_hpd_groups')
+    if level.dtype != torch.float64 or level.dim() != 1 or not level.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_hpd_groups: level must be a contiguous 1-D float64 tensor')
+    nl = int(level.numel())
+    dev = value_sorted.device
+    out = torch.empty((M, nl, 2), dtype=torch.float64, device=dev)
+    index = torch.empty((M, nl, 2), dtype=torch.int32, device=dev)
+    ws, need = _workspace(lib.pp_is_hpd_workspace_bytes, dev, M, int(n_per), nl)
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_hpd_groups(value_sorted.data_ptr(), cdf_sorted.data_ptr(), counted.data_ptr(), M, int(n_per), level.data_ptr(),
+                                  nl, out.data_ptr(), index.data_ptr(), ws.data_ptr(), need, _stream(value_sorted))
+    L.check(rc, 'pp_is_hpd_groups')
+    return out, index
+
+
+def _is_ecdf_groups_hip(value_sorted, cdf_sorted, counted, n_per, x, strict):
+    """(cdf float64 [M, Q], rank int32 [M, Q]): P(X <= x) (strict: <) at the Q points x[g] (float64 [M, Q]: per group) of each of
+    the M groups of n_per sorted particles, and the number of counted particles at or below (below) the point
+    (pp_is_ecdf_groups)."""
+    lib = L.load()
+    _same_device(value_sorted, cdf_sorted, counted, x)
+    M = _sorted_ok(value_sorted, cdf_sorted, counted, n_per, 'is_ecdf_groups')
+    if x.dtype != torch.float64 or x.dim() != 2 or x.shape[0] != M or not x.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_ecdf_groups: x must be a contiguous float64 tensor of [M, Q]')
+    Q = int(x.shape[1])
+    dev = value_sorted.device
+    out = torch.empty((M, Q), dtype=torch.float64, device=dev)
+    rank = torch.empty((M, Q), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_ecdf_groups(value_sorted.data_ptr(), cdf_sorted.data_ptr(), counted.data_ptr(), M, int(n_per), x.data_ptr(), Q,
+                                   1 if strict else 0, out.data_ptr(), rank.data_ptr(), _stream(value_sorted))
+    L.check(rc, 'pp_is_ecdf_groups')
+    return out, rank
+
+
 def _is_unique_groups_hip(value_sorted, lw_sorted, counted, n_per, stats):
     """(value float32 [M, n_per], mass int64 [M, n_per], count int32 [M, n_per], runs int32 [M]): the runs of equal keys among the
     counted sorted particles of each group (pp_is_unique_groups); entries at or beyond runs[g] are not written."""
@@ -961,12 +1041,15 @@ _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')
 _lib.impl('is_cdf_groups', _is_cdf_groups_hip, 'CUDA')
 _lib.impl('is_resample_groups', _is_resample_groups_hip, 'CUDA')
+_lib.impl('is_resample_scheme_groups', _is_resample_scheme_groups_hip, 'CUDA')
 _lib.impl('is_moments_groups', _is_moments_groups_hip, 'CUDA')
 _lib.impl('is_hist_groups', _is_hist_groups_hip, 'CUDA')
 _lib.impl('is_extent_groups', _is_extent_groups_hip, 'CUDA')
 _lib.impl('is_sort_groups', _is_sort_groups_hip, 'CUDA')
 _lib.impl('is_quantile_groups', _is_quantile_groups_hip, 'CUDA')
 _lib.impl('is_unique_groups', _is_unique_groups_hip, 'CUDA')
+_lib.impl('is_hpd_groups', _is_hpd_groups_hip, 'CUDA')
+_lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
