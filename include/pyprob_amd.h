@@ -919,6 +919,48 @@ int pp_is_ecdf_groups(const float* value_sorted /*dev [M n_per]*/, const double*
                       int32_t n_x, int32_t strict, double* out /*dev [M, n_x]*/, int32_t* rank_out /*dev [M, n_x] or NULL*/,
                       void* stream);
 
+/* Pareto-smoothed importance weights and the k-hat diagnostic of a lock-step posterior call on the device (PSIS: Vehtari, Simpson,
+ * Gelman, Yao, Gabry, JMLR 2024). The reference has no counterpart: the only reliability figure of its Empirical is
+ * effective_sample_size (pyprob/distributions/empirical.py:758-766), which looks healthy exactly when the proposal misses a heavy tail.
+ * INPUTS per group g of the [M n_per] layout: the outputs of pp_is_sort_groups called with x = lw - a sort keyed on the log-weight
+ * itself, so particles with a non-finite lw have key 0xFFFFFFFF and lie last: lw_sorted, index_sorted and counted. Let
+ * c = counted[g, 0], s[0..c-1] the sorted finite log-weights as doubles, M_g = s[c-1] (`stats`, dev double [M, 6] or NULL, is
+ * accepted for symmetry: stats[6 g] has the same bits, M_g is the maximum either way).
+ *   tail length     n_t = tail if tail > 0, else (int)ceil(fmin(c / 5.0, 3.0 * sqrt((double)c))).
+ *   cutoff          b = c - n_t - 1. NO FIT (A) if c == 0 or b < 0.
+ *   first tail position  f = #{i < c : s[i] <= s[b]} (ties with the cutoff are not in the tail); n = c - f; u = exp(s[b] - M_g).
+ *   exceedances     y_r = exp(s[f + r] - M_g) - u for r < n (ascending). NO FIT (B) if n <= 4 or not (y_0 > 0).
+ *   no fit          k-hat = +inf, sigma = NaN, and every log-weight of the group leaves with the bits it came with.
+ *   grid            m = 30 + floor(sqrt(n)), q = y[(int)(n / 4.0 + 0.5) - 1]; for j = 1..m:
+ *                   theta_j = 1 / y_{n-1} + (1 - sqrt(m / (j - 0.5))) / (3 q), kappa_j = (1/n) sum_r log1p(-theta_j y_r),
+ *                   L_j = n (log(-theta_j / kappa_j) - kappa_j - 1).
+ *   weights         omega_j = 1 / sum_l exp(L_l - L_j) (a sum that overflows: omega_j = 0); theta-hat = sum_j omega_j theta_j;
+ *                   kappa = (1/n) sum_r log1p(-theta-hat y_r); sigma = -kappa / theta-hat; k-hat = (n kappa + 5) / (n + 10) (the
+ *                   paper's weak prior: ten pseudo-observations at 0.5).
+ *   smoothing       only where k-hat is finite. For tail rank r (sorted order, ties in particle order: the sort is stable):
+ *                   p_r = (r + 0.5) / n, w_r = u + sigma expm1(-k-hat log1p(-p_r)) / k-hat (k-hat == 0: u - sigma log1p(-p_r)),
+ *                   lw_out[g, index_sorted[f + r]] = (float)(fmin(log(w_r), 0.0) + M_g). Every other particle of the group gets
+ *                   its input bits: non-tail particles, non-finite ones, NaN payloads. A k-hat that comes out NaN is reported as
+ *                   such and the weights stay unchanged.
+ *   out             row g, PP_IS_PSIS_WIDTH doubles: k-hat, sigma, n, m, f, s[b] (the cutoff log-weight), c, M_g. Without a
+ *                   fit m = 0; under (A) n = f = 0 and s[b] = NaN; M_g = NaN where c == 0.
+ * lw_out (float [M n_per], particle order) may be NULL: a diagnostic-only call that skips the smoothing launch and writes the
+ * same `out` bits. Four dependent launches on the caller's stream: one thread per tail rank stores y (one fp64 exp) in the
+ * workspace; one WAVE per (group, grid point) adds log1p(-theta_j y_r) - lane l over r = l, l + 64, ... in index order with a
+ * compensated sum, the lane sums by a fixed butterfly; one workgroup per group turns L into omega and theta-hat and passes once
+ * over y; one thread per sorted position scatters the smoothed or copied log-weight. No global atomics, no workgroup waits for
+ * another, nothing is written outside the outputs and the workspace (pp_is_psis_workspace_bytes; PP_ENOSPACE when shorter). Every
+ * sum's order is a function of n and m alone: two calls give the same bits, group g of an M-group call equals the one-group call
+ * on its slice. Any n_per >= 1 and n_groups >= 0 (0: return 0 without a launch; more than 65535 groups are split over launches).
+ * PP_EINVAL without a launch for a NULL required pointer (everything but `stats` and lw_out), n_per < 1, n_groups < 0, tail < 0 or
+ * M n_per above 2^31 - 1. pp_is_psis_workspace_bytes returns 0 outside that envelope. */
+#define PP_IS_PSIS_WIDTH 8
+size_t pp_is_psis_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t tail);
+int pp_is_psis_groups(const float* lw_sorted /*dev [M n_per]*/, const int32_t* index_sorted /*dev [M n_per]*/,
+                      const int32_t* counted /*dev [M, 2]*/, int32_t n_groups, int32_t n_per,
+                      const double* stats /*dev double [M, 6] or NULL*/, int32_t tail, float* lw_out /*dev [M n_per] or NULL*/,
+                      double* out /*dev [M, PP_IS_PSIS_WIDTH]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Weighted Gaussian-mixture EM over one latent of a lock-step posterior call on the device. The reference's density_estimate
  * (pyprob/distributions/empirical.py:795-807) resamples 1000 values on the host, drops the weights and fits scikit-learn's
  * GaussianMixture(covariance_type='diag') to them; here the EM of that class runs in one dimension over ALL particles of each of

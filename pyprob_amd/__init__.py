@@ -26,7 +26,7 @@ def __getattr__(name):
         globals()[name] = joint_batch
         return joint_batch
     if name in ('histogram_batch', 'Histogram', 'Histogram2D', 'quantile_batch', 'density_estimate_batch', 'MixtureFit',
-                'hpd_batch', 'cdf_batch'):
+                'hpd_batch', 'cdf_batch', 'pareto_k_batch', 'psis_batch', 'PsisFit'):
         from . import distributions
         value = getattr(distributions, name)
         globals()[name] = value

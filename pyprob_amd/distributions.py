@@ -742,7 +742,7 @@ class Empirical:
         self._values.append(value)
         self._log_weights.append(0.0 if log_weight is None else float(log_weight))
         self._finalized = False
-        for k in ('_dev_cdf', '_dev_extent', '_dev_sorted', '_fixed_mass', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
+        for k in ('_dev_cdf', '_dev_extent', '_dev_sorted', '_dev_lw_sorted', '_fixed_mass', '_batch', '_batch_cdf', '_batch_log', '_all_cdf'):
             self.__dict__.pop(k, None)
         # the statement log describes the particles of the lock-step call, not this grown set: marginal / joint must not answer
         # for the old one (statement_log itself stays readable, as before; _latent_table refuses through _log_stale)
@@ -1259,6 +1259,94 @@ class Empirical:
             out = _host_ecdf(lw, v, xs, strict)
         return float(out[0]) if scalar else out
 
+    # ---- Pareto-smoothed importance sampling (csrc/is_psis.hip) -----------------------------------------------------------
+    def _device_lw_sorted(self):
+        """(log-weights, index int32, counted int32 [1, 2]) of the call's particles in stable ascending order of their LOG-WEIGHT on
+        the device (pp_is_sort_groups keyed on the log-weights themselves; the non-finite ones last): computed once per object and
+        kept like _device_sorted - 8 bytes per particle, dropped with the object."""
+        s = self.__dict__.get('_dev_lw_sorted')
+        if s is None:
+            from .ops import ops
+            lw = self._all_lw()
+            _, lw_sorted, index, counted = ops.is_sort_groups(lw, lw, lw.numel(), self._group_stats_row())
+            s = self.__dict__['_dev_lw_sorted'] = (lw_sorted, index, counted)
+        return s
+
+    def pareto_k(self, tail=None):
+        """The shape k-hat of the generalised Pareto distribution fitted to the largest importance weights (PSIS: Vehtari, Simpson,
+        Gelman, Yao, Gabry, JMLR 2024), a float: below 0.7 the importance-sampling estimates can be trusted, above it their
+        variance is practically or literally infinite - what effective_sample_size does not show when the proposal misses a heavy
+        tail. tail: the number of largest weights fitted, default ceil(min(c / 5, 3 sqrt(c))) of the c particles with a finite
+        log-weight. +inf where no tail could be fitted (fewer than five distinct weights above the cutoff, all weights equal, a
+        tail that underflows). The definition is pp_is_psis_groups' header comment.
+
+        A device-backed Empirical is sorted by log-weight once (kept with the object); every call is then one operator call
+        without the smoothing launch and one copy of 8 doubles. Every other Empirical, and all of them under
+        PP_EMPIRICAL_DEVICE=0, computes the same definition in float64 numpy."""
+        self._check_finalized()
+        t = _psis_tail(tail)
+        if self.length == 0:
+            raise ValueError('pareto_k of an empty Empirical')
+        if self._device_backed():
+            from .ops import ops
+            lw_sorted, index, counted = self._device_lw_sorted()
+            row = ops.is_psis_groups(lw_sorted, index, counted, lw_sorted.numel(), self._group_stats_row(), t, False)[1].cpu().numpy()[0]
+        else:
+            row = _host_psis(self._lw, t, False)[1]
+        return float(row[0])
+
+    def psis(self, tail=None):
+        """A new Empirical with the same values and Pareto-smoothed log-weights: the `tail` largest weights (default as for pareto_k)
+        are replaced by the order statistics of the generalised Pareto distribution fitted to them, capped at the largest weight,
+        which stabilises every expectation taken afterwards; every other log-weight keeps its bits. `.fit` is a PsisFit (khat,
+        sigma, tail, grid, log_cutoff, count, ess_before, ess_after); the metadata says op='psis'. A UserWarning names a k-hat
+        above 0.7; where no tail could be fitted (k-hat = +inf) the weights are unchanged and the warning says so.
+
+        A device-backed Empirical stays on the device (pp_is_psis_groups over the particles sorted by log-weight, the statistics
+        reduced again by pp_is_stats). The posterior of a lock-step call is smoothed over ALL particles of the call and keeps its
+        statement log: marginal / joint / resample_joint / histogram2d of the result answer under the smoothed weights. Every
+        other Empirical, and all of them under PP_EMPIRICAL_DEVICE=0, computes the same definition in float64 numpy."""
+        self._check_finalized()
+        t = _psis_tail(tail)
+        if self.length == 0:
+            raise ValueError('psis of an empty Empirical')
+        if self._device_backed():
+            from .ops import ops
+            lw_sorted, index, counted = self._device_lw_sorted()
+            lw_out, out = ops.is_psis_groups(lw_sorted, index, counted, lw_sorted.numel(), self._group_stats_row(), t, True)
+            return self._psis_result(lw_out, out.cpu().numpy()[0])
+        new, row = _host_psis(self._lw, t, True)
+        ess = self.effective_sample_size
+        out = self._like(self._values, new, op='psis', length=self.length, khat=float(row[0]))
+        out.fit = _psis_fit(row, ess, out.effective_sample_size)
+        return out
+
+    def _psis_result(self, lw_out, row, stats=None):
+        """The smoothed posterior of psis() from the log-weights the kernel wrote for the call's particles and its row of `out`;
+        stats: pp_is_stats over the smoothed particles where the caller reduced them already (psis_batch: one copy for all)."""
+        own = self.__dict__
+        if '_all_log_weights' in own and own.get('_all_values') is not None:
+            all_values = own['_all_values']
+            if self._log_weights.numel() == lw_out.numel():      # (the call dropped no particle: the tensor the kernel wrote)
+                values, lw = self._values, lw_out
+            else:
+                from .model import _drop_non_finite
+                with warnings.catch_warnings():
+                    warnings.simplefilter('ignore')              # (the call said so already)
+                    values, lw = _drop_non_finite(all_values, lw_out)
+        else:
+            all_values, values, lw = None, self._values, lw_out
+        out = Empirical.from_device(values, lw, _device_stats(lw, values) if stats is None else stats, name=self.name)
+        if all_values is not None:
+            out._all_values, out._all_log_weights = all_values, lw_out
+            for k in ('statement_log', '_statement_rows_raw', 'statement_names', 'num_paths'):
+                if k in own:
+                    out.__dict__[k] = own[k]
+        out._metadata = dict(self._metadata)
+        out.add_metadata(op='psis', length=self.length, khat=float(row[0]))
+        out.fit = _psis_fit(row, self.effective_sample_size, out.effective_sample_size)
+        return out
+
     def argsort(self):
         """The indices of the counted particles (finite log-weight, value not NaN) in stable ascending order of value: a device
         int64 tensor for a device-backed Empirical - to gather the other latents of the statement log in value order - and an
@@ -1569,15 +1657,20 @@ class Empirical:
 _STATS_SCRATCH = {}
 
 
-def _device_stats(lw, x):
-    """pp_is_stats over (lw, x) as the dict Empirical.from_device takes (one small device-to-host copy)."""
+def _device_stats_row(lw, x):
+    """pp_is_stats over (lw, x): the row of doubles on the device (the scratch is kept per device)."""
     from . import lib as L
-    from .is_engine import DistRunner
     from .ops import ops
     scratch = _STATS_SCRATCH.get(lw.device)
     if scratch is None:
         scratch = _STATS_SCRATCH[lw.device] = torch.zeros(L.PP_IS_STATS_SCRATCH, dtype=torch.float64, device=lw.device)
-    return DistRunner._stats_dict(ops.is_stats(lw, x, scratch))
+    return ops.is_stats(lw, x, scratch)
+
+
+def _device_stats(lw, x):
+    """pp_is_stats over (lw, x) as the dict Empirical.from_device takes (one small device-to-host copy)."""
+    from .is_engine import DistRunner
+    return DistRunner._stats_dict(_device_stats_row(lw, x))
 
 
 class JointMoments:
@@ -2091,6 +2184,138 @@ def cdf_batch(posteriors, x, address=None, strict=False):
         cdf = ops.is_cdf_groups(lw_sorted, N, group_stats)
         out = ops.is_ecdf_groups(value, cdf, counted, N, torch.from_numpy(pts).to(lw.device), bool(strict))[0].cpu().numpy()
     return out.reshape(xs.shape)
+
+
+class PsisFit:
+    """What Empirical.psis fitted: khat (the shape of the generalised Pareto tail with the paper's weak prior; +inf: no fit), sigma
+    (its scale, in units of the largest weight), tail (the particles above the cutoff, ties with it excluded), grid (the points of
+    the profile), log_cutoff (the log-weight of the cutoff particle), count (the particles with a finite log-weight), ess_before
+    and ess_after."""
+
+    def __init__(self, khat, sigma, tail, grid, log_cutoff, count, ess_before, ess_after):
+        self.khat, self.sigma, self.tail, self.grid = float(khat), float(sigma), int(tail), int(grid)
+        self.log_cutoff, self.count = float(log_cutoff), int(count)
+        self.ess_before, self.ess_after = float(ess_before), float(ess_after)
+
+    def __repr__(self):
+        return 'PsisFit(khat:{}, sigma:{}, tail:{}, ess_before:{}, ess_after:{})'.format(self.khat, self.sigma, self.tail,
+                                                                                         self.ess_before, self.ess_after)
+
+
+PSIS_KHAT_THRESHOLD = 0.7
+
+
+def _psis_fit(row, ess_before, ess_after):
+    """The PsisFit of a row of pp_is_psis_groups' out, with psis()'s warning."""
+    fit = PsisFit(row[0], row[1], row[2], row[3], row[5], row[6], ess_before, ess_after)
+    if fit.khat == float('inf'):
+        warnings.warn('Pareto smoothing: no tail could be fitted to the {} particles with a finite log-weight (k-hat = inf): the '
+                      'weights are unchanged'.format(fit.count), UserWarning)
+    elif not fit.khat <= PSIS_KHAT_THRESHOLD:
+        warnings.warn('Pareto smoothing: k-hat = {:.3f} is above {}: the importance-sampling estimates of this posterior are '
+                      'unreliable (their variance is practically or literally infinite)'.format(fit.khat, PSIS_KHAT_THRESHOLD),
+                      UserWarning)
+    return fit
+
+
+def _psis_tail(tail):
+    """The `tail` argument of pp_is_psis_groups: 0 (the rule) for None, else a positive integer."""
+    if tail is None:
+        return 0
+    if isinstance(tail, bool) or not isinstance(tail, (int, np.integer)) or not 1 <= int(tail) <= 2 ** 31 - 1:
+        raise ValueError('tail must be a positive integer or None (the rule min(c / 5, 3 sqrt(c))), not %r' % (tail,))
+    return int(tail)
+
+
+def _host_psis(lw, tail, want_weights=True):
+    """pp_is_psis_groups' definition in float64 numpy for one particle set: (smoothed log-weights float64 [n] or None, the row of
+    PP_IS_PSIS_WIDTH doubles). The smoothed tail log-weights are rounded to float32 as the device stores them."""
+    lw = np.asarray(lw, np.float64)
+    fin = np.nonzero(np.isfinite(lw))[0]
+    order = fin[np.argsort(lw[fin], kind='stable')]
+    s = lw[order]
+    c = len(s)
+    row = np.array([np.inf, np.nan, 0.0, 0.0, 0.0, np.nan, float(c), np.nan])
+    new = lw.copy() if want_weights else None
+    if c == 0:
+        return new, row
+    Mg = row[7] = s[c - 1]
+    b = c - (tail if tail > 0 else int(math.ceil(min(c / 5.0, 3.0 * math.sqrt(float(c)))))) - 1
+    if b < 0:
+        return new, row
+    f = int(np.count_nonzero(s <= s[b]))
+    n = c - f
+    u = np.exp(s[b] - Mg)
+    row[2], row[4], row[5] = n, f, s[b]
+    if n <= 4:
+        return new, row
+    y = np.exp(s[f:] - Mg) - u
+    if not y[0] > 0:
+        return new, row
+    m = 30 + int(math.floor(math.sqrt(float(n))))
+    q = y[int(n / 4.0 + 0.5) - 1]
+    with np.errstate(all='ignore'):
+        theta = 1.0 / y[n - 1] + (1.0 - np.sqrt(m / (np.arange(1, m + 1) - 0.5))) / (3.0 * q)
+        kap = np.array([np.sum(np.log1p(-t * y)) / n for t in theta])
+        L = n * (np.log(-theta / kap) - kap - 1.0)
+        omega = np.array([1.0 / np.sum(np.exp(L - Lj)) for Lj in L])
+        that = np.sum(omega * theta)
+        kappa = np.sum(np.log1p(-that * y)) / n
+        sigma = -kappa / that
+        khat = (n * kappa + 5.0) / (n + 10.0)
+        row[0], row[1], row[3] = khat, sigma, m
+        if want_weights and np.isfinite(khat):
+            lp = np.log1p(-(np.arange(n) + 0.5) / n)
+            w = u - sigma * lp if khat == 0 else u + sigma * np.expm1(-khat * lp) / khat
+            new[order[f:]] = (np.minimum(np.log(w), 0.0) + Mg).astype(np.float32).astype(np.float64)
+    return new, row
+
+
+def _psis_batch_call(posteriors, tail, want_weights):
+    """(lw_out or None, out rows in numpy, N) from one sort by log-weight and ONE pp_is_psis_groups call where the posteriors are
+    the M groups of one Model.posterior_results_batch execution in order (as quantile_batch recognises them); else None."""
+    found = _batch_column(posteriors, None)
+    if found is None:
+        return None
+    from .ops import ops
+    lw, _, N, group_stats = found
+    _, lw_sorted, index, counted = ops.is_sort_groups(lw, lw, N, group_stats)
+    lw_out, out = ops.is_psis_groups(lw_sorted, index, counted, N, group_stats, tail, want_weights)
+    return lw_out, out.cpu().numpy(), N
+
+
+def pareto_k_batch(posteriors, tail=None):
+    """numpy.array([p.pareto_k(tail) for p in posteriors]) as float64 [M]: one k-hat per observation - the amortisation gap of the
+    trained network, observation by observation - and, where the posteriors are the M groups of ONE Model.posterior_results_batch
+    execution in order, the same numbers bit for bit from one pp_is_sort_groups call keyed on the log-weights, ONE
+    pp_is_psis_groups call (without the smoothing launch) and one device-to-host copy. Anything else is served by the loop."""
+    posteriors = list(posteriors)
+    t = _psis_tail(tail)
+    if not posteriors:
+        return np.zeros(0)
+    got = _psis_batch_call(posteriors, t, False)
+    if got is None:
+        return np.array([p.pareto_k(tail) for p in posteriors], np.float64)
+    return np.ascontiguousarray(got[1][:, 0])
+
+
+def psis_batch(posteriors, tail=None):
+    """[p.psis(tail) for p in posteriors] - and, where the posteriors are the M groups of ONE Model.posterior_results_batch execution
+    in order, the same log-weights and fits bit for bit from one sort, ONE pp_is_psis_groups call over all groups and one copy of
+    the rows of `out` (the statistics of each smoothed group are reduced by pp_is_stats as in the loop, and travel in one more copy)."""
+    posteriors = list(posteriors)
+    t = _psis_tail(tail)
+    if not posteriors:
+        return []
+    got = _psis_batch_call(posteriors, t, True)
+    if got is None:
+        return [p.psis(tail) for p in posteriors]
+    lw_out, rows, N = got
+    from .is_engine import DistRunner
+    parts = lw_out.split(N)
+    # (no particle was dropped in a recognised batch: the statistics of every smoothed group by the loop's call, ONE copy)
+    stats = torch.stack([_device_stats_row(part, p._values) for p, part in zip(posteriors, parts)]).cpu().numpy()
+    return [p._psis_result(part, rows[g], DistRunner._stats_dict(stats[g])) for g, (p, part) in enumerate(zip(posteriors, parts))]
 
 
 _GMM_MAX_K = 16      # PP_IS_GMM_MAX_K (include/pyprob_amd.h)

@@ -34,6 +34,7 @@ PP_IS_HIST_MAX_BINS = 2048   # bins_x * bins_y of one pp_is_hist_groups call (in
 PP_IS_SORT_TILE = 2048       # particles one workgroup of pp_is_sort_groups sorts in LDS (include/pyprob_amd.h)
 PP_IS_HPD_TILE = 2048        # starts one workgroup of pp_is_hpd_groups searches (include/pyprob_amd.h)
 PP_RESAMPLE_MULTINOMIAL, PP_RESAMPLE_STRATIFIED, PP_RESAMPLE_SYSTEMATIC = 0, 1, 2      # pp_is_resample_scheme_groups' schemes
+PP_IS_PSIS_WIDTH = 8         # doubles per group of pp_is_psis_groups' out (include/pyprob_amd.h)
 PP_IS_GMM_MAX_K = 16         # mixture components of one pp_is_gmm_groups call (include/pyprob_amd.h)
 
 
@@ -225,6 +226,8 @@ PROTOTYPES = {
     'pp_is_hpd_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
     'pp_is_hpd_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_ecdf_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+    'pp_is_psis_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
+    'pp_is_psis_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_gmm_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
     'pp_is_gmm_groups': (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),

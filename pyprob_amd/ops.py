@@ -34,6 +34,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_unique_groups    distinct values with fixed-point masses and counts (combine_duplicates)   pyprob/distributions/empirical.py:809-834
     is_hpd_groups       highest-posterior-density interval over the sorted particles (the reference has none)   pyprob/distributions/empirical.py:668-728
     is_ecdf_groups      the posterior cdf at points given per group (the reference has none)      pyprob/distributions/empirical.py:668-728
+    is_psis_groups      Pareto-smoothed importance weights and k-hat per group (the reference has none)   pyprob/distributions/empirical.py:758-766
     is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -100,6 +101,8 @@ _lib.define('is_unique_groups(Tensor value_sorted, Tensor lw_sorted, Tensor coun
 _lib.define('is_hpd_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor level) -> (Tensor, Tensor)')
 _lib.define('is_ecdf_groups(Tensor value_sorted, Tensor cdf_sorted, Tensor counted, int n_per, Tensor x, bool strict) -> '
             '(Tensor, Tensor)')
+_lib.define('is_psis_groups(Tensor lw_sorted, Tensor index_sorted, Tensor counted, int n_per, Tensor? stats, int tail, '
+            'bool want_weights) -> (Tensor?, Tensor)')
 _lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Tensor? stats, Tensor params_init, int max_iter, '
             'float tol, float reg_covar) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -964,6 +967,33 @@ def _is_ecdf_groups_hip(value_sorted, cdf_sorted, counted, n_per, x, strict):
     return out, rank
 
 
+def _is_psis_groups_hip(lw_sorted, index_sorted, counted, n_per, stats, tail, want_weights):
+    """(lw_out float32 [M n_per] in particle order or None, out float64 [M, PP_IS_PSIS_WIDTH]): the Pareto-smoothed log-weights and
+    the fit (k-hat, sigma, n, m, f, cutoff log-weight, c, maximum) of each of the M groups of n_per particles sorted by their
+    log-weight - is_sort_groups(lw, lw, ...) - (pp_is_psis_groups); tail: the tail length, 0 = min(c / 5, 3 sqrt(c)).
+    want_weights=False: the diagnostic alone, without the smoothing launch."""
+    lib = L.load()
+    _same_device(lw_sorted, index_sorted, counted, stats)
+    M = _groups_of(_f32(lw_sorted, 'lw_sorted'), n_per, 'is_psis_groups')
+    if index_sorted.dtype != torch.int32 or index_sorted.dim() != 1 or index_sorted.numel() != lw_sorted.numel() or \
+            not index_sorted.is_contiguous():
+        raise RuntimeError('pyprob_hip::is_psis_groups: index_sorted must be the contiguous int32 tensor of is_sort_groups '
+                           "(the log-weights' M * n_per elements)")
+    _counted_ok(counted, M, 'is_psis_groups')
+    _group_stats_ok(stats, M, 'is_psis_groups')
+    if int(tail) < 0:
+        raise RuntimeError('pyprob_hip::is_psis_groups: tail >= 0 (0: the rule)')
+    dev = lw_sorted.device
+    lw_out = torch.empty_like(lw_sorted) if want_weights else None
+    out = torch.empty((M, L.PP_IS_PSIS_WIDTH), dtype=torch.float64, device=dev)
+    ws, need = _workspace(lib.pp_is_psis_workspace_bytes, dev, M, int(n_per), int(tail))
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_psis_groups(lw_sorted.data_ptr(), index_sorted.data_ptr(), counted.data_ptr(), M, int(n_per), L.ptr(stats),
+                                   int(tail), L.ptr(lw_out), out.data_ptr(), ws.data_ptr(), need, _stream(lw_sorted))
+    L.check(rc, 'pp_is_psis_groups')
+    return lw_out, out
+
+
 def _is_unique_groups_hip(value_sorted, lw_sorted, counted, n_per, stats):
     """(value float32 [M, n_per], mass int64 [M, n_per], count int32 [M, n_per], runs int32 [M]): the runs of equal keys among the
     counted sorted particles of each group (pp_is_unique_groups); entries at or beyond runs[g] are not written."""
@@ -1050,6 +1080,7 @@ _lib.impl('is_quantile_groups', _is_quantile_groups_hip, 'CUDA')
 _lib.impl('is_unique_groups', _is_unique_groups_hip, 'CUDA')
 _lib.impl('is_hpd_groups', _is_hpd_groups_hip, 'CUDA')
 _lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
+_lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
