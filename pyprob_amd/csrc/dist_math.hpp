@@ -1,6 +1,8 @@
 // Log-densities and samplers of every pyprob distribution family (pyprob/distributions/*.py, v1.5.0), one particle per lane:
 // the device half of pp_dist_logweight / pp_dist_draw (dist_kernels.hip). The log-densities restate, operation for operation
-// in fp32, what the torch.distributions classes behind pyprob's wrappers compute; the samplers draw from a particle's own
+// in fp32, what the torch.distributions classes behind pyprob's wrappers compute - except where that arithmetic itself fails
+// (TruncatedNormal intervals inside one tail: kTruncTailFrom; lgamma differences at large counts: kLgammaFp64From; DESIGN.md
+// "Where the log-densities leave the reference's fp32 arithmetic") -; the samplers draw from a particle's own
 // Philox stream (counter = offset + particle, is_draw.hpp) and take a fresh block of four words per rejection round.
 #pragma once
 #include "common.hpp"
@@ -14,6 +16,12 @@ namespace pp {
 constexpr int kDistMaxRounds = 64;      // PP_DIST_MAX_ROUNDS
 constexpr float kLog2Pi = 1.83787706640934548356f;
 constexpr float kPi = 3.14159265358979323846f;
+// lgammaf carries half an ulp of its own value: 6e-5 at lgamma(256) = 1161, 4e-3 at lgamma(1e4), 6e-2 at lgamma(1e5). Poisson,
+// Binomial and Beta subtract such values from each other and from products of the same size, and what is left is a log-density of
+// a few units. From this count / concentration on, those terms are taken in fp64 and the result is rounded once (per lane; below
+// it every family keeps the reference's fp32 operations).
+constexpr float kLgammaFp64From = 256.0f;
+constexpr float kTruncTailFrom = 3.0f;      // lp_truncnormal: one-tail intervals from here on leave the reference's fp32 formula
 
 // torch.xlogy(a, x): 0 where a == 0 (x not NaN), a * log(x) otherwise
 __device__ __forceinline__ float xlogyf(float a, float x) { return (a == 0.0f && x == x) ? 0.0f : a * logf(x); }
@@ -35,9 +43,14 @@ __device__ __forceinline__ float lp_gamma(float a, float b, float x) {
 
 // 8 Beta(c1, c0, low, high) as pyprob's beta.py:38-40 scores it: torch Beta.log_prob (Dirichlet of (y, 1 - y)) at
 // y = (x - low) / (high - low), with no -log(high - low) Jacobian. Support y in [0, 1].
+__device__ __forceinline__ float lbeta_large(float c1, float c0) {
+#pragma clang fp contract(off)
+    return (float)(lgamma((double)c1 + (double)c0) - (lgamma((double)c1) + lgamma((double)c0)));
+}
 __device__ __forceinline__ float lp_beta(float c1, float c0, float low, float high, float x) {
     const float y = (x - low) / (high - low);
     if (!(y >= 0.0f && y <= 1.0f)) return -INFINITY;
+    if (c1 + c0 >= kLgammaFp64From) return (xlogyf(c1 - 1.0f, y) + xlogyf(c0 - 1.0f, 1.0f - y)) + lbeta_large(c1, c0);
     return (xlogyf(c1 - 1.0f, y) + xlogyf(c0 - 1.0f, 1.0f - y)) + lgammaf(c1 + c0) - (lgammaf(c1) + lgammaf(c0));
 }
 
@@ -59,8 +72,15 @@ __device__ __forceinline__ float lp_weibull(float l, float k, float x) {
 
 // 11 Binomial(total_count n, logits t): k t - lgamma(k + 1) - lgamma(n - k + 1) - (n max(t, 0) + n log1p(exp(-|t|)) -
 // lgamma(n + 1)), support the integers 0..n
+__device__ __forceinline__ float lp_binomial_large(float n, float t, float k) {
+#pragma clang fp contract(off)
+    const double dn = n, dt = t, dk = k;
+    const double norm = dn * fmax(dt, 0.0) + dn * log1p(exp(-fabs(dt))) - lgamma(dn + 1.0);
+    return (float)(dk * dt - lgamma(dk + 1.0) - lgamma(dn - dk + 1.0) - norm);
+}
 __device__ __forceinline__ float lp_binomial(float n, float t, float k) {
     if (!(k >= 0.0f && k <= n && k == floorf(k))) return -INFINITY;
+    if (n >= kLgammaFp64From) return lp_binomial_large(n, t, k);
     const float clamp0 = (fmaxf(t, 0.0f) + t - fminf(t, 0.0f)) * 0.5f;      // torch's _clamp_by_zero
     const float norm = n * clamp0 + n * log1pf(expf(-fabsf(t))) - lgammaf(n + 1.0f);
     return k * t - lgammaf(k + 1.0f) - lgammaf(n - k + 1.0f) - norm;
@@ -87,13 +107,37 @@ __device__ __forceinline__ float lp_vonmises(float loc, float k, float x) {
     return k * cosf(x - loc) - kLog2Pi - log_i0(k);
 }
 
+// An interval [ta, tb] inside one tail, 3 <= ta < tb in that tail's own coordinates, scored at zt in the same coordinates:
+// log phi(zt) - log Z with Z = Q(ta) - Q(tb), Q(t) = erfcx(t / sqrt 2) exp(-t^2 / 2) / 2. The exp(-ta^2 / 2) of Q(ta) is taken
+// out of Z and joined with phi's exponent, -(zt - ta)(zt + ta) / 2, so nothing underflows at any ta:
+//   log Z + ta^2 / 2 = log(erfcx(ta / sqrt 2) / 2) + log1p(-exp(-(tb - ta)(tb + ta) / 2) erfcx(tb / sqrt 2) / erfcx(ta / sqrt 2))
+// No contraction: the three log-weight kernels must give the same bits.
+__device__ __forceinline__ float truncnormal_tail_lp(float zt, float ta, float tb, float sd) {
+#pragma clang fp contract(off)
+    const float ea = erfcxf(ta * kInvSqrt2), eb = erfcxf(tb * kInvSqrt2);
+    const float ratio = expf(-0.5f * ((tb - ta) * (tb + ta))) * (eb / ea);
+    return -0.5f * ((zt - ta) * (zt + ta)) - kHalfLog2Pi - logf(sd) - logf(0.5f * ea) - log1pf(-ratio);
+}
+
 // 13 TruncatedNormal(mean, stddev, low, high) as truncated_normal.py:40-45 scores it: log(1[low <= x <= high]) +
-// N(0, 1).log_prob((x - mean) / stddev) - log(stddev Z), Z = Phi(beta) - Phi(alpha)
+// N(0, 1).log_prob((x - mean) / stddev) - log(stddev Z), Z = Phi(beta) - Phi(alpha) - except where the whole interval lies
+// beyond 3 standard deviations on one side (alpha >= 3 or beta <= -3). There Z <= 1.35e-3, the fp32 difference of two
+// 0.5 (1 + erf) carries ~1e-7 absolute - 7e-5 of Z at 3 sigma, 4e-2 at 5, all of it from 5.5 on (Z = 0, log-density +inf) -
+// and the log-density is taken in the tail's own coordinates instead (truncnormal_tail_lp). The branch is per lane.
 __device__ __forceinline__ float lp_truncnormal(float mu, float sd, float low, float high, float x) {
     if (!(x >= low && x <= high)) return -INFINITY;
     const float z = (x - mu) / sd;
-    const float Z = std_cdf((high - mu) / sd) - std_cdf((low - mu) / sd);
+    const float alpha = (low - mu) / sd, beta = (high - mu) / sd;
+    if (alpha >= kTruncTailFrom) return truncnormal_tail_lp(z, alpha, beta, sd);
+    if (beta <= -kTruncTailFrom) return truncnormal_tail_lp(-z, -beta, -alpha, sd);
+    const float Z = std_cdf(beta) - std_cdf(alpha);
     return -(z * z) / 2.0f - kHalfLog2Pi - logf(sd * Z);
+}
+
+// 3 Poisson(rate) at a count from kLgammaFp64From on (below it: poisson_lp of is_draw.hpp)
+__device__ __forceinline__ float lp_poisson_large(float rate, float v) {
+#pragma clang fp contract(off)
+    return (float)((double)v * log((double)rate) - (double)rate - lgamma((double)v + 1.0));
 }
 
 // log p(x) of a scalar family (kinds 0, 1, 3, 4, 6-13) from the parameter VALUES a..d = p0..p3 (the kinds with fewer parameters
@@ -103,7 +147,9 @@ __device__ __forceinline__ float scalar_log_prob_at(int kind, float a, float b, 
     switch (kind) {
         case 0: return normal_lp(a, b, x);
         case 1: return uniform_lp(a, b, x);
-        case 3: return (x >= 0.0f && x == floorf(x)) ? poisson_lp(a, x) : -INFINITY;      // (guarded here: is_draw.hpp)
+        case 3:      // (guarded here: is_draw.hpp)
+            if (!(x >= 0.0f && x == floorf(x))) return -INFINITY;
+            return x >= kLgammaFp64From ? lp_poisson_large(a, x) : poisson_lp(a, x);
         case 4: return (x == 0.0f || x == 1.0f) ? bernoulli_lp(a, x) : -INFINITY;
         case 6: return lp_exponential(a, x);
         case 7: return lp_gamma(a, b, x);

@@ -346,6 +346,17 @@ class Weibull(_Family):
     def _in_support(self, value):
         return value > 0
 
+    def log_prob(self, value, sum=False):
+        """log k - log l + (k - 1) log z - z^k with z^k = exp(k log z), z = x / l: lp_weibull of csrc/dist_math.hpp. torch's
+        transform chain takes z^k first and the Jacobian's log of it afterwards: -inf where z^k underflows (Weibull(1, 50) at 1e-6),
+        NaN where it overflows."""
+        l, k = self._p
+        value = _t(value).float().to(self._device())
+        lz = torch.log(value / l)
+        lp = torch.log(k) - torch.log(l) + (k - 1) * lz - torch.exp(k * lz)
+        lp = torch.where(value > 0, lp, torch.full_like(lp, float('-inf')))
+        return torch.sum(lp) if sum else lp
+
     @property
     def scale(self):
         return self._p[0]
@@ -433,15 +444,39 @@ class TruncatedNormal(_Family):
         mu, sd, low, high = self._p
         return (low - mu) / sd, (high - mu) / sd
 
+    def _tail(self, tail_from):
+        """(upper, lower, ta, tb, log Z + ta^2 / 2): where the whole interval lies beyond tail_from standard deviations on one side
+        (alpha >= tail_from / beta <= -tail_from) the mass Z is taken in that tail's own coordinates [ta, tb] as
+        Q(ta) - Q(tb), Q(t) = erfcx(t / sqrt 2) exp(-t^2 / 2) / 2, with exp(-ta^2 / 2) left out - lp_truncnormal of
+        csrc/dist_math.hpp. The fp32 difference of two 0.5 (1 + erf) is 0 from 5.5 sigma on. (Elements outside the tails carry
+        placeholders.)"""
+        a, b = self._ab()
+        upper, lower = a >= tail_from, b <= -tail_from
+        tail = upper | lower
+        ta = torch.where(tail, torch.where(upper, a, -b), torch.full_like(a, tail_from))
+        tb = torch.where(tail, torch.where(upper, b, -a), torch.full_like(a, tail_from + 1))
+        ea, eb = torch.special.erfcx(ta / math.sqrt(2)), torch.special.erfcx(tb / math.sqrt(2))
+        ratio = torch.exp(-0.5 * ((tb - ta) * (tb + ta))) * (eb / ea)
+        return upper, lower, ta, tb, torch.log(0.5 * ea) + torch.log1p(-ratio)
+
+    TAIL_FROM = 3.0             # log_prob: kTruncTailFrom of csrc/dist_math.hpp
+    MOMENTS_TAIL_FROM = 4.0     # _Z (mean, variance): the reference's own fp32 Z up to where the device sampler turns to Robert's tail
+                                # sampler - the reference's fp32 mean / stddev of a row such as (5, 1, 0, 2) are reproduced to 1e-5
+
     def _Z(self):
         a, b = self._ab()
-        return _std_cdf(b) - _std_cdf(a)
+        upper, lower, ta, _, lz = self._tail(self.MOMENTS_TAIL_FROM)
+        return torch.where(upper | lower, torch.exp(lz - 0.5 * ta * ta), _std_cdf(b) - _std_cdf(a))
 
     def log_prob(self, value, sum=False):
         mu, sd, low, high = self._p
         value = _t(value).float().to(self._device())
         z = (value - mu) / sd
-        lp = -(z * z) / 2 - 0.5 * math.log(2 * math.pi) - torch.log(sd * self._Z())
+        a, b = self._ab()
+        lp = -(z * z) / 2 - 0.5 * math.log(2 * math.pi) - torch.log(sd * (_std_cdf(b) - _std_cdf(a)))
+        upper, lower, ta, _, lz = self._tail(self.TAIL_FROM)
+        zt = torch.where(lower, -z, z)
+        lp = torch.where(upper | lower, -0.5 * ((zt - ta) * (zt + ta)) - 0.5 * math.log(2 * math.pi) - torch.log(sd) - lz, lp)
         lp = torch.where((value >= low) & (value <= high), lp, torch.full_like(lp, float('-inf')))
         return torch.sum(lp) if sum else lp
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from dist_edge_cases import lp64
 from helpers import chi2_p
 
 pytestmark = pytest.mark.gpu
@@ -55,52 +56,9 @@ def draw(ops, kind, p, n=N_DRAWS, seed=1234, offset=0, stream=7, rows=None, out=
     return out
 
 
-# ---- float64 restatements ----------------------------------------------------------------------------------------------
+# ---- float64 restatements: dist_edge_cases.lp64 (shared with tests/test_gpu_dist_edges.py) ----------------------------------
 def _lgamma(x):
     return np.vectorize(math.lgamma)(np.asarray(x, np.float64))
-
-
-def lp64(name, p, x):
-    x = np.asarray(x, np.float64)
-    p = [float(v) for v in p]
-    with np.errstate(all='ignore'):
-        if name == 'Exponential':
-            out = np.log(p[0]) - p[0] * x
-            ok = x >= 0
-        elif name == 'Gamma':
-            a, b = p[0], p[1]
-            out = a * np.log(b) + np.where((a - 1) == 0, 0.0, (a - 1) * np.log(x)) - b * x - math.lgamma(a)
-            ok = x >= 0
-        elif name == 'Beta':
-            y = (x - p[2]) / (p[3] - p[2])
-            out = (np.where(p[0] == 1, 0, (p[0] - 1) * np.log(y)) + np.where(p[1] == 1, 0, (p[1] - 1) * np.log1p(-y)) +
-                   math.lgamma(p[0] + p[1]) - math.lgamma(p[0]) - math.lgamma(p[1]))
-            ok = (y >= 0) & (y <= 1)
-        elif name == 'LogNormal':
-            ly = np.log(x)
-            out = -(ly - p[0]) ** 2 / (2 * p[1] ** 2) - math.log(p[1]) - 0.5 * math.log(2 * math.pi) - ly
-            ok = x > 0
-        elif name == 'Weibull':
-            z = x / p[0]
-            out = math.log(p[1]) - math.log(p[0]) + (p[1] - 1) * np.log(z) - z ** p[1]
-            ok = x > 0
-        elif name == 'Binomial':
-            n, t = p[0], p[1]
-            lq = -np.logaddexp(0, -t)       # log p
-            l1q = -np.logaddexp(0, t)       # log (1 - p)
-            ok = (x >= 0) & (x <= n) & (x == np.floor(x))
-            xs = np.where(ok, x, 0.0)
-            out = _lgamma(n + 1) - _lgamma(xs + 1) - _lgamma(n - xs + 1) + xs * lq + (n - xs) * l1q
-        elif name == 'VonMises':
-            out = p[1] * np.cos(x - p[0]) - math.log(2 * math.pi) - math.log(np.i0(p[1]))
-            ok = np.isfinite(x)
-        else:
-            mu, sd, lo, hi = p
-            Z = 0.5 * (math.erf((hi - mu) / sd / math.sqrt(2)) - math.erf((lo - mu) / sd / math.sqrt(2)))
-            z = (x - mu) / sd
-            out = -0.5 * z * z - 0.5 * math.log(2 * math.pi) - math.log(sd * Z)
-            ok = (x >= lo) & (x <= hi)
-    return np.where(ok, out, -np.inf)
 
 
 FAMILIES = ['Exponential', 'Gamma', 'Beta', 'LogNormal', 'Weibull', 'Binomial', 'VonMises', 'TruncatedNormal']
@@ -245,7 +203,8 @@ CONTINUOUS = [('Normal', (1.0, 2.0)), ('Uniform', (-1.0, 3.0)), ('Exponential', 
               ('Beta', (2.0, 3.0, 0.0, 1.0)), ('Beta', (0.5, 1.0, 1.0, 4.0)), ('Beta', (1.0, 0.2, 0.0, 1.0)),
               ('Beta', (0.05, 1.0, 0.0, 1.0)), ('LogNormal', (0.5, 0.7)), ('Weibull', (2.0, 0.7)), ('Weibull', (1.0, 5.0)),
               ('VonMises', (1.0, 1e-6)), ('VonMises', (0.5, 0.3)), ('VonMises', (-2.5, 8.0)), ('VonMises', (0.0, 300.0)),
-              ('TruncatedNormal', (0.0, 1.0, -1.0, 2.0)), ('TruncatedNormal', (3.0, 0.5, -1.0, 1.0))]
+              ('TruncatedNormal', (0.0, 1.0, -1.0, 2.0)), ('TruncatedNormal', (3.0, 0.5, -1.0, 1.0)),
+              ('TruncatedNormal', (0.0, 1.0, 3.99, 5.0))]      # (the last interval below the switch to Robert's tail sampler)
 
 
 @pytest.mark.parametrize('name,p', CONTINUOUS, ids=['%s%s' % c for c in CONTINUOUS])
@@ -275,6 +234,7 @@ def test_continuous_sampler_ks_and_moments(ops, name, p):
 
 
 DISCRETE = [('Poisson', (0.3,)), ('Poisson', (4.0,)), ('Poisson', (25.0,)), ('Poisson', (3000.0,)),
+            ('Poisson', (9.999,)), ('Poisson', (10.0,)), ('Binomial', (40.0, 0.25)),      # (either side of the regime switches)
             ('Binomial', (10.0, 0.3)), ('Binomial', (1000.0, 0.005)), ('Binomial', (200.0, 0.4)), ('Binomial', (5000.0, 0.97)),
             ('Bernoulli', (0.3,))]
 
@@ -358,7 +318,8 @@ def test_bad_parameters_give_nan_not_a_hang(ops):
 
 
 @pytest.mark.parametrize('p', [(0.0, 1.0, 30.0, 31.0), (0.0, 1.0, -31.0, -30.0), (2.0, 0.5, 4.5, 4.6), (1.0, 2.0, 10.0, 40.0),
-                               (-1.0, 1.0, -9.0, -5.0)])
+                               (-1.0, 1.0, -9.0, -5.0),
+                               (0.0, 1.0, 6.0, 6.1), (0.0, 1.0, -6.1, -6.0)])      # (narrower than 1 / lambda: the uniform proposal)
 def test_truncated_normal_far_tails(ops, p):
     """Intervals entirely beyond 4 standard deviations (Robert's tail sampler): finite draws inside [low, high] that follow
     the float64 CDF (written with erfc: the tail masses are ~1e-197 at 30 sigma)."""
