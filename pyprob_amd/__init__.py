@@ -3,6 +3,11 @@ API. Hand-written HIP (gfx950) behind a C ABI (include/pyprob_amd.h); PyTorch-RO
 streams and torch.distributed only."""
 __version__ = '0.1.0'
 
+# the posterior statistics over a list of posteriors and their result types (empirical_batch.py, empirical.py)
+_FROM_DISTRIBUTIONS = frozenset((
+    'resample_batch', 'joint_batch', 'histogram_batch', 'quantile_batch', 'hpd_batch', 'cdf_batch', 'pareto_k_batch', 'psis_batch',
+    'density_estimate_batch', 'Histogram', 'Histogram2D', 'MixtureFit', 'PsisFit'))
+
 
 def __getattr__(name):
     """Lazy pyprob-style top level: pyprob_amd.sample / observe / Model / InferenceEngine / PriorInflation ... (importing the package
@@ -17,16 +22,7 @@ def __getattr__(name):
         from .spec import ObserveEmbedding
         globals()[name] = ObserveEmbedding
         return ObserveEmbedding
-    if name == 'resample_batch':
-        from .distributions import resample_batch
-        globals()[name] = resample_batch
-        return resample_batch
-    if name == 'joint_batch':
-        from .distributions import joint_batch
-        globals()[name] = joint_batch
-        return joint_batch
-    if name in ('histogram_batch', 'Histogram', 'Histogram2D', 'quantile_batch', 'density_estimate_batch', 'MixtureFit',
-                'hpd_batch', 'cdf_batch', 'pareto_k_batch', 'psis_batch', 'PsisFit'):
+    if name in _FROM_DISTRIBUTIONS:
         from . import distributions
         value = getattr(distributions, name)
         globals()[name] = value

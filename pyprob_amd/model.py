@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from . import state
-from .distributions import Empirical
+from .empirical import Empirical
 from .nn import InferenceNetworkFeedForward, InferenceNetworkLSTM, OnlineDataset
 from .state import InferenceEngine, InferenceNetwork, Optimizer, PriorInflation, TraceMode
 from operator import is_ as _is

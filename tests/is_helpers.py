@@ -67,6 +67,27 @@ def rescore(case, meta, params, traces, observe, sigma):
     return lw
 
 
+def _batch_of(values, lw, M, N, second=None):
+    """M device-style Empiricals wired like the groups of one posterior_results_batch execution over [M N] columns: `values` is the
+    column forward() returned, logged as 'x__Normal__1'; `second`, where given, a further logged column 'y__Normal__2' that every
+    particle executed. A log-weight of -inf stays in its group, as it does where the call's statistics counted every particle."""
+    import torch
+    import order_stats_ref as R
+    from pyprob_amd.distributions import Empirical
+    stats = torch.zeros(M, 6, dtype=torch.float64)
+    stats[:, 0] = torch.from_numpy(R.group_max(lw.numpy().reshape(M, N)))
+    log = [{'x__Normal__1': (values, 0)}] + ([] if second is None else [{'y__Normal__2': (second, 1)}])
+    posts = []
+    for g in range(M):
+        p = Empirical.from_device(values[g * N:(g + 1) * N], lw[g * N:(g + 1) * N], None)
+        p._batch, p._batch_log = (values, lw, stats, g, N), log
+        if second is not None:      # (the group's own statement log: what address= and joint() read)
+            p.statement_log = [{a: (rec[0][g * N:(g + 1) * N], rec[1]) for a, rec in entry.items()} for entry in log]
+            p._statement_rows_raw, p.statement_names = [{a: None for a in entry} for entry in log], {}
+        posts.append(p)
+    return posts
+
+
 def lockstep_network(device='cpu'):
     """The golden GUMM network with its addresses renamed to the call sites of the lock-step variant of the program
     (`while s >= 1:` compiles to different instruction offsets than `while float(s) >= 1:`)."""

@@ -14,6 +14,7 @@ import pytest
 
 import gmm_ref as G
 import oracle_ops  # noqa: F401  registers the CPU kernels of pyprob_hip::*
+from is_helpers import _batch_of
 from pyprob_amd import lib as L
 from pyprob_amd.state import InferenceEngine
 
@@ -255,21 +256,6 @@ def test_device_style_empirical_through_the_cpu_double(device_style):
     assert G.calls['is_gmm_groups'] == 3
     torch.manual_seed(0)
     assert emp.density_estimate(2, num_samples=500).fit.count == 500 and G.calls['is_gmm_groups'] == 4
-
-
-def _batch_of(values, lw, M, N):
-    """M device-style Empiricals wired like the groups of one posterior_results_batch execution over [M N] columns."""
-    import order_stats_ref as R
-    from pyprob_amd.distributions import Empirical
-    stats = torch.zeros(M, 6, dtype=torch.float64)
-    stats[:, 0] = torch.from_numpy(R.group_max(lw.numpy().reshape(M, N)))
-    log = [{'x__Normal__1': (values, 0)}]
-    posts = []
-    for g in range(M):
-        p = Empirical.from_device(values[g * N:(g + 1) * N], lw[g * N:(g + 1) * N], None)
-        p._batch, p._batch_log = (values, lw, stats, g, N), log
-        posts.append(p)
-    return posts
 
 
 def test_density_estimate_batch_equals_the_loop(device_style):

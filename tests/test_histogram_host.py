@@ -137,7 +137,7 @@ def test_bad_arguments_are_rejected_without_a_device():
 
 
 def test_histogram_arithmetic_on_a_hand_made_row():
-    from pyprob_amd.distributions import Histogram, _histogram_rows
+    from pyprob_amd.empirical import Histogram, _histogram_rows
     edges = np.array([[0.0, 1.0, 3.0, 4.0, 6.0]])
     # slots: four bins, below, above, NaN - fixed-point masses 100, 300, 0, 400 | 50, 100, 50 (total 1000)
     row = np.array([[[100, 300, 0, 400, 50, 100, 50], [1, 3, 0, 2, 1, 1, 1]]], np.int64)

@@ -19,6 +19,7 @@ import interval_ref as I
 import order_stats_ref as R
 import resample_ref as RR
 import oracle_ops  # noqa: F401  registers the CPU kernels of pyprob_hip::*
+from is_helpers import _batch_of
 from pyprob_amd import lib as L
 from pyprob_amd.state import InferenceEngine
 
@@ -328,20 +329,6 @@ def test_scheme_reference_draws_in_order_and_close_to_the_expected_counts(n_out)
 
 
 # ---- 7. end to end through the CPU doubles ---------------------------------------------------------------------------------------------------
-def _batch_of(values, lw, M, N):
-    """M device-style Empiricals wired like the groups of one posterior_results_batch execution over [M N] columns."""
-    from pyprob_amd.distributions import Empirical
-    stats = torch.zeros(M, 6, dtype=torch.float64)
-    stats[:, 0] = torch.from_numpy(R.group_max(lw.numpy().reshape(M, N)))
-    log = [{'x__Normal__1': (values, 0)}]
-    posts = []
-    for g in range(M):
-        p = Empirical.from_device(values[g * N:(g + 1) * N], lw[g * N:(g + 1) * N], None)
-        p._batch, p._batch_log = (values, lw, stats, g, N), log
-        posts.append(p)
-    return posts
-
-
 def _reset():
     for c in (I.calls, R.calls, RR.calls):
         for k in c:

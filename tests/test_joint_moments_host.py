@@ -159,7 +159,7 @@ def test_empiricals_without_a_statement_log_refuse(monkeypatch):
 def test_operator_schema_and_column_blocks_through_the_cpu_double():
     """The operator's shape contract, and the host's assembly of more than 16 columns from calls over pairs of 8-column blocks."""
     from pyprob_amd import ops as P
-    from pyprob_amd.distributions import _moment_rows, joint_from_moments
+    from pyprob_amd.empirical import _moment_rows, joint_from_moments
     _register_cpu_double()
     rng = np.random.default_rng(1)
     M, N = 3, 70

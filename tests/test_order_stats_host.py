@@ -16,6 +16,7 @@ import histogram_ref as H
 import order_stats_ref as R
 import resample_ref as RR
 import oracle_ops  # noqa: F401  registers the CPU kernels of pyprob_hip::*
+from is_helpers import _batch_of
 from pyprob_amd import lib as L
 from pyprob_amd.state import InferenceEngine
 
@@ -279,20 +280,6 @@ def test_device_style_empirical_through_the_cpu_doubles(device_style):
     emp.add(0.25, 0.0)
     emp.finalize()
     assert '_dev_sorted' not in emp.__dict__ and emp.quantile(1.0) == float(v[keep].max()) and emp.length == n + 1
-
-
-def _batch_of(values, lw, M, N):
-    """M device-style Empiricals wired like the groups of one posterior_results_batch execution over [M N] columns."""
-    from pyprob_amd.distributions import Empirical
-    stats = torch.zeros(M, 6, dtype=torch.float64)
-    stats[:, 0] = torch.from_numpy(R.group_max(lw.numpy().reshape(M, N)))
-    log = [{'x__Normal__1': (values, 0)}]
-    posts = []
-    for g in range(M):
-        p = Empirical.from_device(values[g * N:(g + 1) * N], lw[g * N:(g + 1) * N], None)
-        p._batch, p._batch_log = (values, lw, stats, g, N), log
-        posts.append(p)
-    return posts
 
 
 def test_quantile_batch_fast_path_equals_the_loop(device_style):

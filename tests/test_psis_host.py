@@ -14,6 +14,7 @@ import order_stats_ref as R
 import psis_ref as PR
 import resample_ref as RR
 import oracle_ops  # noqa: F401  registers the CPU kernels of pyprob_hip::*
+from is_helpers import _batch_of
 from pyprob_amd import lib as L
 from pyprob_amd.state import InferenceEngine
 
@@ -216,20 +217,6 @@ def test_host_route_of_pareto_k_and_psis(monkeypatch):
 
 
 # ---- 4. the device route and the batch calls through the CPU doubles -------------------------------------------------------------------------
-def _batch_of(values, lw, M, N):
-    """M device-style Empiricals wired like the groups of one posterior_results_batch execution over [M N] columns."""
-    from pyprob_amd.distributions import Empirical
-    stats = torch.zeros(M, 6, dtype=torch.float64)
-    stats[:, 0] = torch.from_numpy(R.group_max(lw.numpy().reshape(M, N)))
-    log = [{'x__Normal__1': (values, 0)}]
-    posts = []
-    for g in range(M):
-        p = Empirical.from_device(values[g * N:(g + 1) * N], lw[g * N:(g + 1) * N], None)
-        p._batch, p._batch_log = (values, lw, stats, g, N), log
-        posts.append(p)
-    return posts
-
-
 def test_batch_calls_are_one_operator_call_each_and_equal_the_loop(device_style):
     import pyprob_amd
     rng = np.random.default_rng(44)

@@ -28,7 +28,8 @@ import torch  # noqa: E402
 
 import pyprob_amd  # noqa: E402
 from pyprob_amd import lib as L  # noqa: E402
-from pyprob_amd.distributions import Empirical, _host_gmm  # noqa: E402
+from pyprob_amd.distributions import Empirical  # noqa: E402
+from pyprob_amd.empirical_host import _host_gmm  # noqa: E402
 from pyprob_amd.ops import ops  # noqa: E402
 
 try:
@@ -191,7 +192,7 @@ def main():
         p = posterior(lw[sl], x[sl], host_stats[g])
         p._batch, p._batch_log = (x, lw, stats, g, Nb), whole_log
         posts.append(p)
-    from pyprob_amd.distributions import _batch_column
+    from pyprob_amd.empirical_batch import _batch_column
     assert _batch_column(posts, None) is not None, 'the posteriors must be recognised as one batched execution'
     fast = pyprob_amd.density_estimate_batch(posts, K)
     loop = [p.density_estimate(K) for p in posts]

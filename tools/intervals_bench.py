@@ -226,7 +226,7 @@ def main():
         p = posterior(lw[sl], x[sl], host_stats[g])
         p._batch, p._batch_log = (x, lw, stats, g, Nb), whole_log
         posts.append(p)
-    from pyprob_amd.distributions import _batch_column
+    from pyprob_amd.empirical_batch import _batch_column
     assert _batch_column(posts, None) is not None, 'the posteriors must be recognised as one batched execution'
     truths = torch.rand(M, 1, dtype=torch.float64, device=DEV) * 3.0
     host_truths = truths.cpu().numpy()[:, 0]

@@ -172,7 +172,7 @@ def main():
         p = posterior(lw[sl], x[sl], host_stats[g])
         p._batch, p._batch_log = (x, lw, stats, g, Nb), whole_log
         posts.append(p)
-    from pyprob_amd.distributions import _batch_column
+    from pyprob_amd.empirical_batch import _batch_column
     assert _batch_column(posts, None) is not None, 'the posteriors must be recognised as one batched execution'
     fast = pyprob_amd.quantile_batch(posts, qs)
     assert np.array_equal(fast, np.stack([p.quantile(qs) for p in posts])) and np.abs(fast - numpy_quantiles(lw, x, M, Nb, qs)).max() <= 0.05
