@@ -1169,6 +1169,42 @@ int pp_obs_logweight_groups(int32_t kind, const pp_obs_operand params[4], pp_obs
                             float scale, float* lw /*dev [n_groups * n_per]*/, float* lp_out, int32_t n_groups, int32_t n_per,
                             void* stream);
 
+/* Empirical.reobserve (pyprob/distributions/empirical.py:469-544): the n_per particles of ONE lock-step posterior call re-scored
+ * under n_groups new observations without running the program or the network again. Row i = g * n_per + j of `out` is particle j
+ * under observation g. A term is one re-scored observe statement: a scalar family (kinds 0, 1, 3, 4, 6-13, pp_obs_logweight's
+ * list), k values per observe, the program's parameters addressed with the PARTICLE j (params[q][j, e] =
+ * p[j * row_stride + e * elem_stride]: (0, 0) a scalar, (0, 1) one shared row, (1, 0) one value per particle, (k, 1) [n_per, k])
+ * and the new values addressed with the GROUP g (x[g, e] = p[g * row_stride + e * elem_stride]; row stride 0: one value / row for
+ * all groups). `lw` holds the call's log-weights, `old` the sum of the terms that are replaced (NULL: zero).
+ * THE FORMULA (fp32, no contraction), a contract:
+ *   lp_t(g, j) = the summed log-density of x_t[g, :] under params_t[j, :], with the bits pp_obs_logweight writes to lp_out for a
+ *                row with these element values (scalar_log_prob_at, the 256 slots, the butterfly: ONE compiled text,
+ *                csrc/obs_row.hpp); for k = 1 these are pp_dist_logweight's bits.
+ *   s_0 = +0,  s_t = s_{t-1} + (scale_t * lp_t): the product is rounded, then the sum, for t ascending - the chain the
+ *                accumulate route builds on a zeroed vector.
+ *   out[i] = lw[j]                     where lw[j] is not finite (the call dropped that particle; it stays dropped for every g)
+ *   out[i] = lw[j] + (s_T - old[j])    otherwise: the difference is rounded, then the sum.
+ * Consequences: re-scoring the original values at the original scales returns lw bit for bit (s_T == old); a new value outside
+ * a particle's support gives -inf for that (g, j) only; NaN parameters give NaN; a group's row does not depend on n_groups, on
+ * the other groups or on the grid; no atomics - the bits are equal from run to run. The per-particle operands are read from
+ * memory once per chunk of groups (a workgroup keeps lw[j] and old[j] in registers and walks the chunk), not once per group.
+ * All offsets are 64-bit (n_groups * n_per and j * row_stride may pass 2^31).
+ * Returns nonzero without a launch (pp_last_error names pp_is_reobserve_groups) for a kind outside the list, count outside
+ * 1..PP_REOBS_MAX_TERMS, k < 1, n_per < 1, n_groups < 0, a NULL pointer or a negative stride of an operand the kind needs or of
+ * x, terms, lw or out NULL. n_groups == 0 returns 0 without a launch. */
+#define PP_REOBS_MAX_TERMS 8
+typedef struct pp_reobs_term {
+    int32_t kind;
+    int32_t k;                  /* values per observe, >= 1 */
+    float   scale;              /* likelihood_importance of the NEW term */
+    int32_t _pad;
+    pp_obs_operand params[4];   /* rows indexed by the particle j */
+    pp_obs_operand x;           /* rows indexed by the group g */
+} pp_reobs_term;
+int pp_is_reobserve_groups(const pp_reobs_term* terms /*host*/, int32_t count, const float* lw /*dev [n_per]*/,
+                           const float* old /*dev [n_per] or NULL*/, float* out /*dev [n_groups * n_per]*/, int32_t n_groups,
+                           int32_t n_per, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * Individual kernels (used by the whole-path entry points; exported for unit parity tests and profiling)
  * ---------------------------------------------------------------------------------------------------- */

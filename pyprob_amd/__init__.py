@@ -6,7 +6,7 @@ __version__ = '0.1.0'
 # the posterior statistics over a list of posteriors and their result types (empirical_batch.py, empirical.py)
 _FROM_DISTRIBUTIONS = frozenset((
     'resample_batch', 'joint_batch', 'histogram_batch', 'quantile_batch', 'hpd_batch', 'cdf_batch', 'pareto_k_batch', 'psis_batch',
-    'density_estimate_batch', 'Histogram', 'Histogram2D', 'MixtureFit', 'PsisFit'))
+    'density_estimate_batch', 'reobserve_batch', 'Histogram', 'Histogram2D', 'MixtureFit', 'PsisFit'))
 
 
 def __getattr__(name):

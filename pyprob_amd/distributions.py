@@ -704,4 +704,4 @@ class Factor(Distribution):
 from .empirical import (PSIS_KHAT_THRESHOLD, Empirical, Histogram, Histogram2D, JointMoments, MixtureFit,  # noqa: E402,F401
                         PsisFit, joint_from_moments)
 from .empirical_batch import (cdf_batch, density_estimate_batch, histogram_batch, hpd_batch, joint_batch,  # noqa: E402,F401
-                              pareto_k_batch, psis_batch, quantile_batch, resample_batch)
+                              pareto_k_batch, psis_batch, quantile_batch, reobserve_batch, resample_batch)

@@ -1,6 +1,7 @@
 """Empirical, the weighted-sample container behind Model.prior / posterior (pyprob/distributions/empirical.py), the result types
 of its statistics and the decoders of the device kernels' output rows. The *_batch functions over the groups of one batched
 posterior call live in empirical_batch.py, the float64 numpy routes in empirical_host.py."""
+import contextlib
 import math
 import os
 import warnings
@@ -760,6 +761,165 @@ class Empirical:
         out.fit = _psis_fit(row, self.effective_sample_size, out.effective_sample_size)
         return out
 
+    # ---- re-scoring under new observations (csrc/is_reobserve.hip) ------------------------------------------------------
+    def _reobserve_weights(self, cols, M, likelihood_funcs, likelihood_importance):
+        """([M, N] log-weights of ALL particles of the call under the M new observations, the re-scored names, the origin): ONE
+        replay of the program over the statement log (state.ReobserveState), `old` by the accumulate route on a zeroed vector at
+        the original scale, ONE pp_is_reobserve_groups call. cols: {name: float32 array [M, k]} (a name that only gets a new
+        likelihood keeps its original value)."""
+        from . import state
+        from .is_engine import DistRunner, VecTerm
+        from .ops import ops
+        log = self.__dict__.get('statement_log')
+        self._latent_table()          # (no statement log, a stale one, PP_EMPIRICAL_DEVICE=0: refused as marginal / joint refuse)
+        origin = self.__dict__.get('_origin')
+        if origin is None and self.__dict__.get('_origin_lost'):
+            raise ValueError('reobserve: ' + self._origin_lost)
+        if origin is None:
+            raise AttributeError('this Empirical does not know the call that made it: reobserve serves the result of '
+                                 'posterior_results(..., lock_step=True) and the members of posterior_results_batch')
+        model, args, kwargs, observe0, scale0, engine = origin
+        if self.__dict__.get('num_paths', 1) != 1:
+            raise NotImplementedError('reobserve replays straight-line programs only: this posterior ran {} control-flow paths'
+                                      .format(self.num_paths))
+        if isinstance(observe0, tuple):      # a member of a batched call: row g of the call's observations
+            obs, g = observe0
+            observe0 = {k: v.as_subclass(torch.Tensor)[g].cpu() for k, v in obs.items()}
+        observe0 = dict(observe0 or {})
+        targets = list(dict.fromkeys(list(cols) + list(likelihood_funcs or {})))
+        if not targets:
+            raise ValueError('reobserve: name an observable in `observe` or `likelihood_funcs`')
+        lw = self._all_lw()
+        n, dev = int(lw.numel()), lw.device
+        runner = _REOBSERVE_RUNNERS.get(dev)
+        if runner is None:
+            runner = _REOBSERVE_RUNNERS[dev] = DistRunner(dev)
+        ls = state.ReobserveState(runner, n, log, targets, likelihood_funcs)
+        with (torch.cuda.device(dev) if dev.type == 'cuda' else contextlib.nullcontext()):
+            state._init_traces(func=model.forward, trace_mode=state.TraceMode.POSTERIOR,
+                               inference_engine=state.InferenceEngine.IMPORTANCE_SAMPLING, observe=observe0,
+                               likelihood_importance=scale0, lock_step=ls)
+            runner.begin(n)
+            try:
+                state._begin_trace()
+                model.forward(*args, **kwargs)
+            finally:
+                state._lock_step = None
+                state._current_trace = None
+                ls.memo = None
+            seen = [r[0] for r in ls.records]
+            unknown = [t for t in targets if t not in seen]
+            if unknown:
+                raise ValueError('reobserve: {} not among the named observes of the program: {}'.format(unknown, ls.observe_names))
+            if len(ls.records) > 8:
+                raise NotImplementedError('reobserve: at most 8 re-scored observe statements per call')
+            scale1 = float(scale0 if likelihood_importance is None else likelihood_importance)
+            old = torch.zeros(n, dtype=torch.float32, device=dev)
+            kinds, ks, scales, params, xs = [], [], [], [], []
+            for name, new, term0, v0, k in ls.records:
+                runner.accumulate(old, term0, v0, float(scale0))
+                if type(new) is VecTerm:
+                    kind, ps = new.kind, new.params
+                else:
+                    wide = new.wide()
+                    kind, ps = wide.kind, [p if p is None or p.numel() == 1 else p.reshape(n, 1) for p in wide.params]
+                if name in cols:
+                    c = np.ascontiguousarray(cols[name], np.float32).reshape(M, -1)
+                    if c.shape[1] != k:
+                        raise ValueError('reobserve: observable {!r} has {} values, the new observation {}'.format(name, k, c.shape[1]))
+                    x = torch.from_numpy(c).to(dev)
+                else:
+                    x = v0.reshape(1, k)
+                kinds.append(int(kind)); ks.append(k); scales.append(scale1); params += list(ps); xs.append(x)
+            out = ops.reobserve_groups(lw, old, kinds, ks, scales, params, xs, int(M))
+        # the scale a later reobserve takes the old terms out at: one number only where every weighted term carries it
+        scale = scale1 if (len(seen) == ls.n_weighted or scale1 == float(scale0)) else None
+        return out, seen, (model, args, kwargs, observe0, scale, engine)
+
+    def _reobserve_stats(self, origin, out):
+        """The [M, 6] statistics of out [M, N] over the call's values, on the device, and the values expanded to [M N]: ONE grouped
+        pass (pp_is_fused_groups without a draw or a term) where the model has an inference network on this device, else one
+        pp_is_stats launch per group. A group's row does not depend on M."""
+        all_values = self.__dict__.get('_all_values')
+        all_values = self._values if all_values is None else all_values
+        M, N = int(out.shape[0]), int(out.shape[1])
+        values = all_values if M == 1 else all_values.reshape(1, N).expand(M, N).reshape(-1)
+        runner = getattr(getattr(origin[0], '_inference_network', None), '_is', None)
+        if out.is_cuda and runner is not None and runner.dev == out.device and hasattr(runner, 'fused_groups'):
+            return runner.fused_groups(None, N, None, [], values, out.reshape(-1), False, stats=True), values, runner
+        return torch.stack([_device_stats_row(out[g], all_values)[:6] for g in range(M)]).contiguous(), values, None
+
+    def _reobserve_result(self, lw_new, stats, origin, observe, names):
+        """The Empirical of the call's particles under the new log-weights lw_new [N] (all particles): non-finite ones are
+        dropped as the call dropped them, the full vectors, the statement log and the origin (new values merged) stay."""
+        own = self.__dict__
+        all_values = own.get('_all_values')
+        all_values = self._values if all_values is None else all_values
+        values, lw = all_values, lw_new
+        if int(stats['count']) != lw_new.numel():
+            from .model import _drop_non_finite
+            values, lw = _drop_non_finite(all_values, lw_new)
+            if lw.numel() == 0:
+                raise ValueError('reobserve: no particle has a finite log-weight under the new observation')
+            stats = _device_stats(lw, values)
+        out = Empirical.from_device(values, lw, stats, name=self.name)
+        out._all_values, out._all_log_weights = all_values, lw_new
+        for k in ('statement_log', '_statement_rows_raw', 'statement_names', 'num_paths'):
+            if k in own:
+                out.__dict__[k] = own[k]
+        model, args, kwargs, observe0, scale, engine = origin
+        if scale is not None:
+            out._origin = (model, args, kwargs, dict(observe0, **observe), scale, engine)
+        else:       # the origin holds ONE likelihood_importance: the scale a later call takes the old terms out at
+            out._origin_lost = ('this posterior was re-observed for SOME of its observes at another likelihood_importance than the '
+                                'rest carry, so its terms no longer share one scale and it cannot be re-observed again - re-observe '
+                                'the original posterior, naming every observe, instead')
+        out._metadata = dict(self._metadata)
+        out.add_metadata(op='reobserve', length=self.length, length_after=out.length, observables=list(names),
+                         effective_sample_size=out.effective_sample_size)
+        return out
+
+    def reobserve(self, observe=None, likelihood_funcs=None, likelihood_importance=None):
+        """The posterior of the SAME particles under new observed values and / or new likelihoods, without running the inference
+        network or drawing anything again (pyprob/distributions/empirical.py:469-544): every name in `observe` or
+        `likelihood_funcs` is an observe statement of the program whose term leaves the log-weights (at the original call's
+        likelihood_importance) and enters again for the new value under `likelihood_funcs[name](v, trace)` - called ONCE: v has
+        name, address, distribution (the program's object, parameters per particle), value (the original one), observed; trace is
+        None, so `lambda v, trace: Normal(v.distribution.mean, 0.5)` works as in the reference - or, without a function, under
+        the program's own distribution. likelihood_importance scales the new terms (None: the original call's).
+
+        Returns a new device-backed Empirical over the same values tensor: log-weights for ALL particles of the call (one
+        pp_is_reobserve_groups call, include/pyprob_amd.h states its formula), particles whose new weight is not finite dropped
+        as the call drops them with the full vectors attached. It keeps the statement log - marginal / joint / resample_joint /
+        histogram2d / psis answer under the new weights - and its origin with the new values merged, so it can be re-observed
+        again. `pareto_k()` of the result says whether the reused particles still cover the new posterior.
+
+        Differences from the reference: it serves Empiricals of Trace objects only, this serves the device-backed result of a
+        lock-step posterior_results call (straight-line programs, scalar families; Categorical, Mixture and torch-route
+        likelihoods, and branching programs raise NotImplementedError). There a new value without a likelihood function keeps
+        the OLD log-prob (:515-527); here every name given is re-scored. As there: if any part of the program is conditional on
+        the observed value, the result is not the posterior of the new observation - the replay shows the program the ORIGINAL
+        values and nothing is drawn again."""
+        self._check_finalized()
+        observe = dict(observe or {})
+        cols = {k: np.asarray(torch.as_tensor(v, dtype=torch.float32).cpu().numpy(), np.float32).reshape(1, -1)
+                for k, v in observe.items()}
+        out, names, origin = self._reobserve_weights(cols, 1, likelihood_funcs, likelihood_importance)
+        from .is_engine import DistRunner
+        stats = DistRunner._stats_dict(self._reobserve_stats(origin, out)[0].cpu().numpy()[0])
+        return self._reobserve_result(out[0], stats, origin, observe, names)
+
+    def reweight(self, func, min_index=None, max_index=None):
+        """A new Empirical of the values [min_index, max_index) whose log-weights are func(value), one call per value
+        (pyprob/distributions/empirical.py:546-566). Host-backed."""
+        if self.length == 0:
+            return self
+        self._check_finalized()
+        lo = 0 if min_index is None else int(min_index)
+        hi = self.length if max_index is None else int(max_index)
+        values = [self._value(i) for i in range(lo, hi)]
+        return self._like(values, np.array([float(func(v)) for v in values], np.float64), op='reweight', length=self.length)
+
     def argsort(self):
         """The indices of the counted particles (finite log-weight, value not NaN) in stable ascending order of value: a device
         int64 tensor for a device-backed Empirical - to gather the other latents of the statement log in value order - and an
@@ -1066,6 +1226,7 @@ class Empirical:
 
 
 _STATS_SCRATCH = {}
+_REOBSERVE_RUNNERS = {}      # device -> the DistRunner of Empirical.reobserve's replays
 
 
 def _device_stats_row(lw, x):

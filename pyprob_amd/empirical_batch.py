@@ -209,6 +209,8 @@ def joint_batch(posteriors, addresses=None):
     lw, _, N, group_stats = found
     chosen, _ = posteriors[0]._joint_columns(addresses)
     whole = _log_columns(posteriors[0]._batch_log)
+    if any(a not in whole for a in chosen):      # (reobserve_batch: the members share the [N] columns of ONE posterior)
+        return [p.joint(addresses) for p in posteriors]
     return _joint_rows(chosen, _moment_rows(lw, [whole[a] for a in chosen], N, group_stats))
 
 
@@ -241,3 +243,39 @@ def resample_batch(posteriors, num_samples, seed=None, offset=0, scheme='multino
     d_parts, z_parts = drawn.split(n), zeros.split(n)
     return [p._resampled(d_parts[g], z_parts[g], runner._stats_dict(stats[g]), n, p.effective_sample_size, scheme)
             for g, p in enumerate(posteriors)]
+
+
+def reobserve_batch(post, observes, likelihood_funcs=None, likelihood_importance=None):
+    """[post.reobserve(observes[g], likelihood_funcs, likelihood_importance) for g in range(M)] - the posteriors of ONE set of
+    particles under M observations - bit for bit from ONE replay of the program, ONE pp_is_reobserve_groups call over all M N rows,
+    one grouped statistics pass (one pp_is_stats launch per group where the model has no inference network) and ONE
+    device-to-host copy of the statistics. `observes` as posterior_results_batch takes
+    them: a list of M observe dicts with equal keys, or one dict name -> tensor with a leading dimension M.
+
+    The members hold the call's [M, N] log-weights, the values expanded to [M, N] and the [M, 6] statistics (`_batch`), so with
+    address=None quantile_batch, hpd_batch, cdf_batch, histogram_batch, pareto_k_batch, psis_batch, density_estimate_batch and
+    (where the posterior came from an inference-network call) resample_batch recognise them as one execution; the address= forms
+    and joint_batch take their loop - every member's own marginal / joint answer from the shared [N] columns of the statement
+    log. `pareto_k_batch(reobserve_batch(post, observes))` says observation by observation whether the particles still cover the
+    new posterior."""
+    from .is_engine import DistRunner
+    from .model import Model
+    names, dicts, cols = Model._normalise_observes(observes)
+    M = len(dicts)
+    post._check_finalized()
+    out, seen, origin = post._reobserve_weights(cols, M, likelihood_funcs, likelihood_importance)
+    N = int(out.shape[1])
+    # (the values expanded to [M N]: what the grouped kernels behind the *_batch functions index; materialised once per call)
+    group_stats, values, runner = post._reobserve_stats(origin, out)
+    stats = group_stats.cpu().numpy()          # the one device-to-host copy
+    lw_all = out.reshape(-1)
+    log = []      # (the call's own [M N] columns do not exist: joint_batch and the address= forms take their loop)
+    members = []
+    for g in range(M):
+        emp = post._reobserve_result(out[g], DistRunner._stats_dict(stats[g]), origin, dicts[g], seen)
+        if emp.length == N:      # (no particle dropped) the call's whole tensors: the *_batch functions serve all groups at once
+            emp._batch, emp._batch_log = (values, lw_all, group_stats, g, N), log
+            if runner is not None:
+                emp._batch_runner = runner
+        members.append(emp)
+    return members

@@ -119,6 +119,14 @@ class pp_obs_operand(C.Structure):
     _fields_ = [('p', vp), ('row_stride', i64), ('elem_stride', i32), ('_pad', i32)]
 
 
+PP_REOBS_MAX_TERMS = 8
+
+
+class pp_reobs_term(C.Structure):
+    """One re-scored observe of pp_is_reobserve_groups: params rows by particle, x rows by group."""
+    _fields_ = [('kind', i32), ('k', i32), ('scale', C.c_float), ('_pad', i32), ('params', pp_obs_operand * 4), ('x', pp_obs_operand)]
+
+
 class pp_gemm_args(C.Structure):
     _fields_ = [('A', vp), ('lda', i64), ('a_idx', vp),
                 ('B', vp), ('ldb', i64), ('b_idx', vp),
@@ -243,6 +251,7 @@ PROTOTYPES = {
     'pp_mix_logweight': (C.c_int, [C.POINTER(pp_mixture), vp, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
     'pp_obs_logweight': (C.c_int, [i32, C.POINTER(pp_obs_operand), pp_obs_operand, i32, C.c_float, vp, vp, vp, i32, i32, vp]),
     'pp_obs_logweight_groups': (C.c_int, [i32, C.POINTER(pp_obs_operand), pp_obs_operand, i32, i32, C.c_float, vp, vp, i32, i32, vp]),
+    'pp_is_reobserve_groups': (C.c_int, [C.POINTER(pp_reobs_term), i32, vp, vp, vp, i32, i32, vp]),
     'pp_mix_draw': (C.c_int, [C.POINTER(pp_mixture), vp, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, vp, vp]),
     'pp_gemm_f32': (C.c_int, [C.POINTER(pp_gemm_args), vp]),
     'pp_gemm_f32_grouped': (C.c_int, [C.POINTER(pp_gemm_args), i32, vp]),

@@ -821,6 +821,10 @@ class Model:
             post = self._traces(num_traces, TraceMode.POSTERIOR, inference_engine, None, trace_result, observe,
                                 likelihood_importance, *args, **kwargs)
             post.rename('Posterior, IS, traces: {:,}, ESS: {:,.2f}'.format(post.length, post.effective_sample_size))
+        if 'statement_log' in post.__dict__:
+            # a lock-step route returned (a first call or a launch-plan replay, either engine): what Empirical.reobserve needs to
+            # replay the program. The observe dict is copied (no tensor is); the tuple keeps this model alive with the result.
+            post._origin = (self, args, kwargs, dict(observe or {}), likelihood_importance, inference_engine)
         return post
 
     # ---- batched posteriors: M observations in one call ------------------------------------------------------------------
@@ -1007,6 +1011,9 @@ class Model:
                 emp._batch, emp._batch_runner = (values, lw_all, ls.group_stats, g, N), runner
                 emp._batch_log = ls.log       # (the call's whole columns: joint_batch serves all groups in one launch)
             emp.num_paths = 1
+            # (the group's observe dict is row g of `obs`: resolved when Empirical.reobserve asks for it, nothing is copied here)
+            emp._origin = (self, args, kwargs, (obs, g), likelihood_importance,
+                           InferenceEngine.IMPORTANCE_SAMPLING_WITH_INFERENCE_NETWORK)
             emp.statement_log = [{a: (parts[g], addr_id) for a, parts, addr_id in entry} for entry in log_parts]
             emp._statement_rows_raw, emp.statement_names = ls.log_rows, names
             emp.rename('Posterior, IC, traces: {:,}, ESS: {:,.2f}'.format(emp.length, emp.effective_sample_size))

@@ -36,6 +36,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_ecdf_groups      the posterior cdf at points given per group (the reference has none)      pyprob/distributions/empirical.py:668-728
     is_psis_groups      Pareto-smoothed importance weights and k-hat per group (the reference has none)   pyprob/distributions/empirical.py:758-766
     is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
+    reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
 parameter buffer) is registered once per layer set with `register_net` and referenced by an integer handle; the
@@ -105,6 +106,8 @@ _lib.define('is_psis_groups(Tensor lw_sorted, Tensor index_sorted, Tensor counte
             'bool want_weights) -> (Tensor?, Tensor)')
 _lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Tensor? stats, Tensor params_init, int max_iter, '
             'float tol, float reg_covar) -> Tensor')
+_lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
+            'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
             'Tensor(b!)? lp_out, int n) -> ()')
 _lib.define('dist_draw(int kind, Tensor?[] params, int[] strides, Tensor? rows, Tensor(a!) out, int seed, int offset, '
@@ -554,6 +557,50 @@ def _obs_logweight_groups_hip(lw, kind, params, x, per_group, k, scale, lp_out, 
         rc = lib.pp_obs_logweight_groups(int(kind), arr, xo, per_group, k, float(scale), L.ptr(lw), L.ptr(lp_out), n_groups, n_per,
                                          _stream(ref))
     L.check(rc, 'pp_obs_logweight_groups')
+
+
+def _reobserve_groups_hip(lw, old, kinds, ks, scales, params, xs, n_groups):
+    """out [n_groups, N] of pp_is_reobserve_groups: term t has kind kinds[t], ks[t] values per observe, the parameter slots
+    params[4 t .. 4 t + 3] with rows by particle (a scalar, [k], [N] / [N, 1] or [N, k]: obs_draw_strides over N rows) and the new
+    values xs[t] with rows by group ([n_groups, k], or one element / [1, k]: the same for every group)."""
+    lib = L.load()
+    n_groups, T = int(n_groups), len(kinds)
+    N = int(_f32(lw, 'lw').numel())
+    if not 1 <= T <= L.PP_REOBS_MAX_TERMS or len(ks) != T or len(scales) != T or len(xs) != T or len(params) != 4 * T:
+        raise RuntimeError('pyprob_hip::reobserve_groups: 1..%d terms with a kind, k, scale, x and 4 parameter slots each'
+                           % L.PP_REOBS_MAX_TERMS)
+    if n_groups < 0 or N < 1 or lw.dim() != 1 or not lw.is_contiguous():
+        raise RuntimeError('pyprob_hip::reobserve_groups: n_groups >= 0 and a contiguous lw [N], N >= 1')
+    if old is not None and (_f32(old, 'old').numel() != N or not old.is_contiguous()):
+        raise RuntimeError('pyprob_hip::reobserve_groups: old must be a contiguous [N] like lw')
+    _same_device(lw, old, *params, *xs)
+    arr = (L.pp_reobs_term * T)()
+
+    def operand(o, t, rows, k, name):
+        if t.dtype != torch.float32:
+            raise RuntimeError('pyprob_hip: %s must be a float32 tensor' % name)
+        rs, es = obs_draw_strides(t, rows, k, name, 'obs_logweight')
+        o.p, o.row_stride, o.elem_stride = t.data_ptr(), int(rs), int(es)
+    for t in range(T):
+        k = int(ks[t])
+        if k < 1:
+            raise RuntimeError('pyprob_hip::reobserve_groups: k >= 1 values per observe, got %d' % k)
+        arr[t].kind, arr[t].k, arr[t].scale = int(kinds[t]), k, float(scales[t])
+        for q in range(4):
+            if params[4 * t + q] is not None:
+                operand(arr[t].params[q], params[4 * t + q], N, k, 'term %d p%d' % (t, q))
+        x = xs[t]
+        if x.dim() != 2 or x.shape[1] != k or x.shape[0] not in (1, n_groups):
+            raise RuntimeError('pyprob_hip::reobserve_groups: x of term %d must be [n_groups, k] or [1, k] (n_groups = %d, k = %d), '
+                               'got %s' % (t, n_groups, k, list(x.shape)))
+        operand(arr[t].x, x, int(x.shape[0]), k, 'term %d x' % t)
+        if x.shape[0] == 1:
+            arr[t].x.row_stride = 0
+    out = torch.empty((n_groups, N), dtype=torch.float32, device=lw.device)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_reobserve_groups(arr, T, lw.data_ptr(), L.ptr(old), out.data_ptr(), n_groups, N, _stream(lw))
+    L.check(rc, 'pp_is_reobserve_groups')
+    return out
 
 
 def _log_prob_hip(kind, p0, p0_stride, p1, p1_stride, x, n):
@@ -1066,6 +1113,7 @@ _lib.impl('prior_draw', _prior_draw_hip, 'CUDA')
 _lib.impl('obs_draw', _obs_draw_hip, 'CUDA')
 _lib.impl('obs_logweight', _obs_logweight_hip, 'CUDA')
 _lib.impl('obs_logweight_groups', _obs_logweight_groups_hip, 'CUDA')
+_lib.impl('reobserve_groups', _reobserve_groups_hip, 'CUDA')
 _lib.impl('log_prob', _log_prob_hip, 'CUDA')
 _lib.impl('logweight_terms', _logweight_terms_hip, 'CUDA')
 _lib.impl('is_stats', _is_stats_hip, 'CUDA')

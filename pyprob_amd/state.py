@@ -597,6 +597,87 @@ class PriorISState(LockStepState):
         return None
 
 
+class ReobservedVariable:
+    """What a likelihood function of Empirical.reobserve is handed for an observe statement (the reference hands it the trace's
+    Variable): the program's distribution object with its per-particle parameters and the value of the original call."""
+
+    def __init__(self, name, address, distribution, value):
+        self.name, self.address, self.distribution, self.value = name, address, distribution, value
+        self.observed = self.observable = True
+
+
+class ReobserveState(PriorISState):
+    """The replay behind Empirical.reobserve: forward() runs ONCE at the width of the original call and no statement draws -
+    `sample` at statement index j hands out the column the statement log holds for its address, an `observe` of a name that is
+    re-scored records the terms (the program's own distribution over ITS per-particle parameters, or what a likelihood function
+    makes of it) and returns the original value, every other observe and every factor is skipped: those terms are in the
+    log-weight already and do not change. Nothing is added to a log-weight here; Empirical.reobserve turns `records` into one
+    accumulate chain for the old terms and one pp_is_reobserve_groups call for the new ones."""
+    mode = 'reobserve'
+
+    def __init__(self, runner, n, log, targets, likelihood_funcs):
+        super().__init__(runner, n, 0, 0)
+        self.log = log
+        self.targets = set(targets)
+        self.likelihood_funcs = dict(likelihood_funcs or {})
+        self.records = []             # (name, new term, old term, old value as the accumulate route takes it, k)
+        self.observe_names = []       # the program's named observes, in order
+        self.n_weighted = 0           # observes and factors: the terms likelihood_importance scales
+
+    def branch(self, cond):
+        c = cond.reshape(-1) != 0
+        if bool(c.all()):
+            return True
+        if not bool(c.any()):
+            return False
+        raise NotImplementedError('reobserve replays straight-line programs only: the particles disagree at a branch')
+
+    def replay_statement(self, address, name):
+        j = self.statement
+        self.statement += 1
+        entry = self.log[j].get(address) if j < len(self.log) else None
+        if entry is None or not torch.is_tensor(entry[0]) or entry[0].numel() != self.n:
+            raise RuntimeError('reobserve: sample statement {} at address {!r} is not in the statement log of this posterior - '
+                               'the program no longer matches the call that made it'.format(j, address))
+        if name is not None:
+            self.names.setdefault(name, address)
+        return ParticleTensor.wrap(entry[0])
+
+    def _term(self, distribution, value):
+        """The device term of a likelihood over `value` (a scalar: dist_term, the route the call itself took; else vec_term)."""
+        family = getattr(distribution, 'name', type(distribution).__name__)
+        if family in ('Categorical', 'Mixture', 'Factor'):
+            raise NotImplementedError('reobserve: a {} likelihood is not re-scored on the device'.format(family))
+        if value.numel() == 1:
+            term = self.runner.dist_term(distribution)
+            if term is not None and type(term).__name__ != 'MixTerm' and int(term.kind) not in (2, 5):
+                return term
+        else:
+            term = self.runner.vec_term(distribution, tuple(value.shape), self.n)
+            if term is not None:
+                return term
+        raise NotImplementedError('reobserve: the {} likelihood of this observe takes the torch route of the lock-step '
+                                  'executor, which is not re-scored on the device'.format(family))
+
+    def observe_statement(self, name, address, distribution, value):
+        self.n_weighted += 1
+        if name is not None and getattr(distribution, 'name', None) != 'Factor':
+            self.observe_names.append(name)
+        if name is None or name not in self.targets:
+            return
+        if value is None:
+            raise ValueError('reobserve: observe {!r} had no value in the original call'.format(name))
+        if self.rows is not None:
+            raise NotImplementedError('reobserve: observe {!r} is reached under a row list (a branch); straight-line programs '
+                                      'only'.format(name))
+        value = torch.as_tensor(value, dtype=torch.float32)
+        old = self._term(distribution, value)
+        func = self.likelihood_funcs.get(name)
+        new = old if func is None else self._term(func(ReobservedVariable(name, address, distribution, value), None), value)
+        v = self.runner._const(float(value)) if value.numel() == 1 else value.reshape(-1).to(self.runner.dev)
+        self.records.append((name, new, old, v, int(value.numel())))
+
+
 class BatchUnsupported(Exception):
     """Internal: the program did something the batched fast path (Model.posterior_results_batch) does not serve; the caller
     falls back to one posterior_results call per observation."""
@@ -1314,6 +1395,11 @@ def observe(distribution, value=None, name=None, address=None):
         value = None
     if _lock_step is not None and _lock_step.mode == 'prior':
         return _lock_step.observe_statement(name, distribution, value)
+    if _lock_step is not None and _lock_step.mode == 'reobserve':      # (Empirical.reobserve: terms are recorded, nothing is scored)
+        _lock_step.observe_statement(name, addr, distribution, value)
+        _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
+                                    log_prob=None, log_importance_weight=None, observed=True, name=name))
+        return value
     if _coroutine is not None and value is not None and _trace_mode == TraceMode.POSTERIOR:
         _coroutine.observe(distribution, value)       # the weight term joins the next round's likelihood kernels
         _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
@@ -1362,6 +1448,15 @@ def sample(distribution, name=None, address=None, control=True):
         ls.history.append(entry)
         return wrapper
     base, addr, instance = _make_address(distribution, address)
+    if ls is not None and ls.mode == 'reobserve':      # (Empirical.reobserve: no statement draws)
+        if name in _current_trace_observed_variables:
+            value = torch.as_tensor(_current_trace_observed_variables[name], dtype=torch.float32)
+            ls.observe_statement(name, addr, distribution, value)
+        else:
+            value = ls.replay_statement(addr, name)
+        _current_trace.add(Variable(distribution=distribution, value=value, address_base=base, address=addr, instance=instance,
+                                    log_prob=None, control=control, name=name))
+        return value
     if name in _current_trace_observed_variables and _coroutine is not None and _trace_mode == TraceMode.POSTERIOR:
         value = torch.as_tensor(_current_trace_observed_variables[name], dtype=torch.float32)
         _coroutine.observe(distribution, value)
