@@ -1000,6 +1000,56 @@ int pp_is_gmm_groups(const float* lw /*dev [M n_per]*/, const float* x /*dev [M 
                      int32_t check_every, double* out /*dev double [M, PP_IS_GMM_WIDTH(K)]*/, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* Weighted EM for a mixture of K full-covariance Gaussians over J latents of a lock-step posterior call on the device: the JOINT
+ * density pp_is_gmm_groups cannot give (one latent, one variance per component). The reference has no counterpart. In fp64 (only the
+ * columns and lw are float32), over ALL particles of each of the M groups under their own weights, from the caller's parameters.
+ *   pp_is_gmm_joint_groups  cols: a HOST array of n_cols = J device pointers, each a column [M n_per] of float32 (as for
+ *                       pp_is_moments_groups). A particle counts where its lw is finite AND its J coordinates are finite; it weighs
+ *                       w_i = exp((double)lw_i - max_g), max_g = stats[6 g] or, without `stats`, the largest finite lw of the group
+ *                       (the same bits either way). Every other particle is skipped: its values are read but enter nothing.
+ *                       W = sum w_i. With pi_k, mu_k [J], Sigma_k [J, J] = L_k L_k^T (L_k the lower Cholesky factor) the current
+ *                       parameters of the group - at first params_init[g] - iteration t = 1 .. max_iter is
+ *                         E-step  l_ik = log pi_k - J/2 log 2 pi - sum_j log L_k,jj - 1/2 |L_k^-1 (x_i - mu_k)|^2,
+ *                                 L_i = logsumexp_k l_ik,  r_ik = w_i exp(l_ik - L_i),  lb_t = sum_i w_i L_i / W
+ *                         M-step  N_k = sum_i r_ik + 10 DBL_EPSILON,  d_k = sum_i r_ik (x_i - mu_k) / N_k,  mu'_k = mu_k + d_k,
+ *                                 Sigma'_k = sum_i r_ik (x_i - mu_k)(x_i - mu_k)^T / N_k - d_k d_k^T + reg_covar I,
+ *                                 pi'_k = N_k / sum_k N_k
+ *                         stop    |lb_t - lb_{t-1}| < tol (lb_0 = -inf): the group is converged, n_iter = t and the parameters are
+ *                                 those AFTER this M-step; tol = 0 runs exactly max_iter iterations.
+ *                       The M-step's sums are taken about the current mean, as in pp_is_gmm_groups. DEGENERATE: a Sigma'_k (or a
+ *                       Sigma_k of params_init) with a Cholesky pivot that is not positive. The group then keeps the parameters it
+ *                       had BEFORE this M-step, degenerate = 1, converged = 0, n_iter = t and the lower bound lb_t (0 and -inf for
+ *                       params_init), and is frozen like a converged group; no NaN reaches another group.
+ *                       Row g of `out`, PP_IS_GMM_JOINT_WIDTH(J, K) doubles: pi [K] | mu [K, J] | Sigma [K, J (J + 1) / 2], the upper
+ *                       triangle row by row | the last lower bound, n_iter, converged (0 / 1), degenerate (0 / 1), W, the count of
+ *                       particles that entered, max_g. params_init [M, K (1 + J + J (J + 1) / 2)] is the same layout without the
+ *                       seven trailing numbers; every pi_k must be positive. A group in which no particle counts: NaN parameters
+ *                       and lower bound, n_iter 0, converged 1, degenerate 0, W 0, count 0.
+ *                       Two dependent launches per iteration on the caller's stream: a workgroup of 256 threads per tile of 2048
+ *                       particles holds the group's constants (mu_k, the packed L_k^-1, log pi_k - sum_j log L_k,jj - J/2 log 2 pi)
+ *                       in LDS, finds L_i of its particles in a first sweep over the components and, in a second, the
+ *                       1 + J + J (J + 1) / 2 sums of one component at a time in registers; it stores a partial row of
+ *                       K (1 + J + J (J + 1) / 2) + 3 sums. One workgroup per group adds the rows in tile order, forms the new
+ *                       parameters, factorises the K matrices and writes its row of `out` and the next iteration's constants. No
+ *                       atomics, no workgroup waits for another. Every check_every iterations (< 1: 8) the host reads one word that
+ *                       says whether every group is converged or degenerate and stops enqueuing: this call SYNCHRONISES the stream
+ *                       there. The sums' order is a function of (n_per, J, K) alone: the result of a group does not depend on
+ *                       check_every, on M or on the other groups of the call, and a call repeated gives the same bits.
+ * Any n_per >= 1 and n_groups >= 0 (0: return 0 without a launch); nothing is written outside `out` and the workspace
+ * (pp_is_gmm_joint_workspace_bytes; PP_ENOSPACE when shorter). PP_EINVAL without a launch for a NULL required pointer (lw, cols, one
+ * of its n_cols entries, params_init, out, workspace), n_cols outside 1 .. PP_IS_GMM_JOINT_MAX_J, n_components outside
+ * 1 .. PP_IS_GMM_MAX_K, n_per < 1, n_groups < 0, M n_per above 2^31 - 1, max_iter < 1, tol < 0 or reg_covar < 0 (NaN included).
+ * pp_is_gmm_joint_workspace_bytes returns 0 outside that envelope. */
+#define PP_IS_GMM_JOINT_MAX_J 8
+#define PP_IS_GMM_JOINT_WIDTH(J, K) ((K) * (1 + (J) + (J) * ((J) + 1) / 2) + 7)
+size_t pp_is_gmm_joint_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_cols, int32_t n_components);
+int pp_is_gmm_joint_groups(const float* lw /*dev [M n_per]*/, const float* const* cols /*host [n_cols] of dev [M n_per]*/,
+                           int32_t n_cols, int32_t n_components, int32_t n_groups, int32_t n_per,
+                           const double* stats /*dev double [M, 6] or NULL*/,
+                           const double* params_init /*dev double [M, K (1 + J + J (J + 1) / 2)]*/, int32_t max_iter, double tol,
+                           double reg_covar, int32_t check_every, double* out /*dev double [M, PP_IS_GMM_JOINT_WIDTH(J, K)]*/,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

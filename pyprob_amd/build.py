@@ -8,8 +8,10 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libpyprob_amd.so')
-SOURCES = ['gemm_f32.hip', 'kernels.hip', 'engine.hip', 'panel.hip', 'panel16.hip', 'lstm_input.hip', 'wgrad_t1.hip', 'is_kernels.hip', 'is_step_fused.hip', 'is_step_small.hip', 'obs_embed.hip', 'pack.hip', 'train_loop.hip', 'lstm_tail.hip', 'dp.hip', 'optim.hip', 'dist_kernels.hip', 'cnn2d.hip', 'obs_draw.hip', 'obs_logweight.hip', 'is_batch.hip', 'is_resample.hip', 'is_moments.hip', 'is_hist.hip', 'is_sort.hip', 'is_gmm.hip', 'is_hpd.hip', 'is_psis.hip', 'is_reobserve.hip']
+SOURCES = ['gemm_f32.hip', 'kernels.hip', 'engine.hip', 'panel.hip', 'panel16.hip', 'lstm_input.hip', 'wgrad_t1.hip', 'is_kernels.hip', 'is_step_fused.hip', 'is_step_small.hip', 'obs_embed.hip', 'pack.hip', 'train_loop.hip', 'lstm_tail.hip', 'dp.hip', 'optim.hip', 'dist_kernels.hip', 'cnn2d.hip', 'obs_draw.hip', 'obs_logweight.hip', 'is_batch.hip', 'is_resample.hip', 'is_moments.hip', 'is_hist.hip', 'is_sort.hip', 'is_gmm.hip', 'is_hpd.hip', 'is_psis.hip', 'is_reobserve.hip', 'is_gmm_joint.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
+# Per-source additions. is_gmm_joint.hip: no packed fp32 arithmetic (its float work is loads and conversions to fp64 only).
+EXTRA_FLAGS = {'is_gmm_joint.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def _hipcc():
@@ -34,6 +36,11 @@ VGPR_LIMITS = {'gemm_f32_async_grouped_aux_kernel': 128, 'gemm_f32_async_grouped
                'gemm_f32_async_lstm_kernel': 256}   # (a 4-wave workgroup: two per CU up to 256 VGPRs)
 
 
+# Kernels that must not touch scratch memory: the joint mixture's tile kernel keeps up to 45 fp64 accumulators, eight particles of
+# J floats and their weights in registers (412 VGPRs + AGPRs at J = 8); a private array that lost its static indices would land there.
+NO_SCRATCH = ('joint_tile_kernel',)
+
+
 def _check_registers(remarks):
     name = None
     for line in remarks.splitlines():
@@ -44,6 +51,9 @@ def _check_registers(remarks):
             for key, limit in VGPR_LIMITS.items():
                 if key in name and n > limit:
                     raise RuntimeError('%s uses %d VGPRs (limit %d: two workgroups per CU)' % (name, n, limit))
+        elif 'ScratchSize' in line and name and any(key in name for key in NO_SCRATCH):
+            if int(line.split(':')[-1].split()[0]) != 0:
+                raise RuntimeError('%s uses scratch memory: %s' % (name, line.strip()))
 
 
 def build(force=False, verbose=False):
@@ -60,7 +70,7 @@ def build(force=False, verbose=False):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace('.hip', '.o'))
         if force or _stale(o, [s] + headers):
-            jobs.append([hipcc] + FLAGS + ['-Rpass-analysis=kernel-resource-usage', '-c', s, '-o', o])
+            jobs.append([hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ['-Rpass-analysis=kernel-resource-usage', '-c', s, '-o', o])
 
     def run(cmd):
         if verbose:

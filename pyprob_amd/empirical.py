@@ -1036,6 +1036,37 @@ class Empirical:
             rows = _host_gmm(lw, x, init[0], int(max_iter), float(tol), float(reg_covar))[None]
         return _mixtures_from_rows(rows, K, dict(self._metadata), self.length, tol, max_iter, reg_covar)[0]
 
+    def density_estimate_joint(self, num_mixture_components=1, addresses=None, tol=1e-3, max_iter=100, reg_covar=1e-6,
+                               weights_init=None, means_init=None, covariances_init=None):
+        """A mixture of num_mixture_components (K <= 16) Gaussians with FULL covariances fitted to several latents (J <= 8) of a
+        lock-step call at once, as a JointMixtureFit: the joint density behind joint()'s moments - ridges, and joint modes that
+        every marginal hides. Weighted expectation-maximisation over ALL particles under their own weights, in float64 on the
+        device, by the definition of pp_is_gmm_joint_groups (include/pyprob_amd.h): at most max_iter iterations, converged when
+        the weighted mean log-likelihood changes by less than tol; reg_covar is added to every covariance's diagonal. addresses:
+        as joint() takes them (default every address that ALL particles executed; an address of a branch raises ValueError). A
+        particle with a coordinate that is not finite is skipped like one without a finite log-weight.
+
+        The start needs no random numbers: weights 1 / K; mean k the particle - all J coordinates - at the exact weighted quantile
+        (k + 1/2) / K of the FIRST address (pp_is_sort_groups' order, the cumulative weights and a binary search, on the device);
+        every covariance joint().cov / K^(2 / J) + reg_covar I. weights_init [K], means_init [K, J] and covariances_init [K, J, J]
+        replace each of these. The same posterior therefore gives the same bits.
+
+        A fit that did not converge, or met a covariance that is not positive definite (degenerate: the parameters of the last
+        good iteration are returned), warns. One operator call and one copy of K (1 + J + J (J + 1) / 2) + 7 doubles. Only the
+        result of a lock-step posterior call has the statement log this needs: every other Empirical raises AttributeError."""
+        self._check_finalized()
+        K = _gmm_arguments(num_mixture_components, tol, max_iter, reg_covar)
+        chosen, cols = self._joint_columns(addresses)
+        lw = self._all_lw()
+        n, stats = lw.numel(), self._group_stats_row()
+        init = _joint_gmm_init_rows(K, len(cols), reg_covar, weights_init, means_init, covariances_init,
+                                    lambda: _joint_start_means(lw, cols, n, stats, K),
+                                    lambda: [_joint_rows(chosen, _moment_rows(lw, cols, n, stats))[0].cov])
+        from .ops import ops
+        rows = ops.is_gmm_joint_groups(lw, list(cols), K, n, stats, torch.from_numpy(init).to(lw.device), int(max_iter), float(tol),
+                                       float(reg_covar)).cpu().numpy()
+        return _joint_fits_from_rows(rows, chosen, K, dict(self._metadata), n, tol, max_iter, reg_covar)[0]
+
     # ---- transformations (each returns a new Empirical) ------------------------------------------------------
     def map(self, func, min_index=None, max_index=None):
         self._check_finalized()
@@ -1615,4 +1646,136 @@ def _mixtures_from_rows(rows, K, metadata, length, tol, max_iter, reg_covar):
         mix = Mixture([Normal(loc[g * K + k], scale[g * K + k]) for k in range(K)], probs[g])
         mix.fit = MixtureFit(pi[g], mu[g], sd[g], rows[g, 3 * K], rows[g, 3 * K + 1], rows[g, 3 * K + 2], rows[g, 3 * K + 4], meta)
         out.append(mix)
+    return out
+
+
+_GMM_JOINT_MAX_J = 8      # PP_IS_GMM_JOINT_MAX_J (include/pyprob_amd.h)
+
+
+class JointMixtureFit:
+    """What Empirical.density_estimate_joint fitted, in float64 numpy: addresses [J], weights [K], means [K, J], covariances
+    [K, J, J]; lower_bound (the weighted mean log-likelihood of the last E-step), n_iter, converged, degenerate (a covariance
+    lost positive definiteness: these are the parameters of the last good iteration), count (the particles that entered) and
+    metadata. log_prob and sample answer in numpy; marginal(address) is the Mixture of Normals of one coordinate."""
+
+    def __init__(self, addresses, weights, means, covariances, lower_bound, n_iter, converged, degenerate, count, metadata):
+        self.addresses = list(addresses)
+        self.weights, self.means, self.covariances = weights, means, covariances
+        self.lower_bound, self.n_iter, self.count = float(lower_bound), int(n_iter), int(count)
+        self.converged, self.degenerate = bool(converged), bool(degenerate)
+        self.metadata = metadata
+
+    def __repr__(self):
+        return 'JointMixtureFit(addresses:{}, components:{}, n_iter:{}, converged:{}, lower_bound:{})'.format(
+            self.addresses, len(self.weights), self.n_iter, self.converged, self.lower_bound)
+
+    def log_prob(self, x):
+        """log sum_k pi_k Normal(x; mu_k, Sigma_k) of x [..., J] as float64 numpy [...]."""
+        x = np.asarray(x, np.float64)
+        J = self.means.shape[1]
+        if x.shape[-1:] != (J,):
+            raise ValueError('x must end in the %d coordinates %s' % (J, self.addresses))
+        flat = x.reshape(-1, J)
+        ell = np.empty((flat.shape[0], len(self.weights)))
+        for k, (pi, mu, cov) in enumerate(zip(self.weights, self.means, self.covariances)):
+            L = np.linalg.cholesky(cov)
+            z = np.linalg.solve(L, (flat - mu).T)
+            ell[:, k] = np.log(pi) - 0.5 * J * math.log(2.0 * math.pi) - np.log(np.diag(L)).sum() - 0.5 * (z * z).sum(0)
+        peak = ell.max(1)
+        return (peak + np.log(np.exp(ell - peak[:, None]).sum(1))).reshape(x.shape[:-1])
+
+    def sample(self, n, seed=None):
+        """n draws [n, J] (float64 numpy) from the fitted mixture by numpy's Generator(seed)."""
+        rng = np.random.default_rng(seed)
+        k = rng.choice(len(self.weights), int(n), p=self.weights / self.weights.sum())
+        z = rng.standard_normal((int(n), self.means.shape[1]))
+        return self.means[k] + np.einsum('nij,nj->ni', np.linalg.cholesky(self.covariances)[k], z)
+
+    def marginal(self, address):
+        """The fitted density of ONE coordinate as a Mixture of Normals: `address` is one of `addresses`, or the address= its
+        statement was given where that begins one of them only."""
+        from .distributions import Mixture, Normal      # (the families' module re-exports this one: not at import time)
+        hits = [j for j, a in enumerate(self.addresses) if a == address] or \
+               [j for j, a in enumerate(self.addresses) if a.startswith(str(address) + '__')]
+        if len(hits) != 1:
+            raise KeyError('unknown address {!r}: this fit knows {}'.format(address, self.addresses))
+        j = hits[0]
+        sd = np.sqrt(self.covariances[:, j, j])
+        return Mixture([Normal(float(m), float(s)) for m, s in zip(self.means[:, j], sd)],
+                       torch.from_numpy(self.weights.astype(np.float32)))
+
+
+def _joint_start_means(lw, cols, n_per, stats, K):
+    """float64 numpy [M, K, J]: mean k of group g is the particle - all J columns - at the weighted quantile (k + 1/2) / K of the FIRST
+    column: the first position of pp_is_sort_groups' order whose cumulative weight reaches fl(q T) (Empirical.quantile's rule), found
+    by a binary search over the sorted cumulative weights, all on the device; one copy of M K J numbers."""
+    _, _, index, counted, cdf = _sorted_groups(lw, cols[0], n_per, stats)
+    M = lw.numel() // int(n_per)
+    cdf = cdf.view(M, n_per)
+    last = (counted.view(M, 2)[:, :1].long() - 1).clamp(min=0)
+    levels = torch.from_numpy((np.arange(K) + 0.5) / K).to(lw.device)
+    at = torch.minimum(torch.searchsorted(cdf, (cdf.gather(1, last) * levels[None, :]).contiguous()), last)
+    rows = index.view(M, n_per).long().gather(1, at) + torch.arange(M, device=lw.device)[:, None] * int(n_per)
+    return torch.stack([c[rows] for c in cols], -1).double().cpu().numpy()
+
+
+def _joint_gmm_init_rows(K, J, reg_covar, weights_init, means_init, covariances_init, means, covariances):
+    """The initial parameters [M, K (1 + J + J (J + 1) / 2)] (weights | means | upper triangles, float64) of density_estimate_joint:
+    the overrides where given (shared by the groups), else 1 / K, means() = [M, K, J] and covariances() = M matrices [J, J], each
+    divided by K^(2 / J) with reg_covar on the diagonal - each called only where its default is needed."""
+    if not 1 <= J <= _GMM_JOINT_MAX_J:
+        raise ValueError('density_estimate_joint takes 1 .. %d addresses, not %d' % (_GMM_JOINT_MAX_J, J))
+
+    def override(a, shape, name):
+        a = np.asarray(a, np.float64)
+        if a.shape != shape or not np.isfinite(a).all():
+            raise ValueError('%s must hold finite numbers of shape %s' % (name, list(shape)))
+        return a[None]
+    pi = override(weights_init, (K,), 'weights_init') if weights_init is not None else np.full((1, K), 1.0 / K)
+    if not (pi > 0).all():
+        raise ValueError('weights_init must be positive')
+    mu = override(means_init, (K, J), 'means_init') if means_init is not None else np.asarray(means(), np.float64).reshape(-1, K, J)
+    if covariances_init is not None:
+        cov = override(covariances_init, (K, J, J), 'covariances_init')
+        if not np.array_equal(cov, cov.transpose(0, 1, 3, 2)):
+            raise ValueError('covariances_init must be symmetric')
+    else:
+        cov = (np.stack(covariances()) / float(K) ** (2.0 / J) + float(reg_covar) * np.eye(J))[:, None]
+    if not (np.isfinite(mu).all() and np.isfinite(cov).all()):
+        raise ValueError('density_estimate_joint: the start is not finite (a coordinate that is not finite at a quantile of the first '
+                         'address, or no particle with a finite log-weight): give means_init / covariances_init')
+    M = max(mu.shape[0], cov.shape[0])
+    iu, ku = np.triu_indices(J)
+    parts = (np.broadcast_to(pi, (M, K)), np.broadcast_to(mu, (M, K, J)).reshape(M, -1),
+             np.broadcast_to(cov, (M, K, J, J))[:, :, iu, ku].reshape(M, -1))
+    return np.ascontiguousarray(np.concatenate(parts, 1))
+
+
+def _joint_fits_from_rows(rows, addresses, K, metadata, length, tol, max_iter, reg_covar):
+    """The output rows [M, PP_IS_GMM_JOINT_WIDTH(J, K)] of pp_is_gmm_joint_groups as M JointMixtureFits. metadata: one dict, or one
+    per row."""
+    J = len(addresses)
+    iu, ku = np.triu_indices(J)
+    off = K * (1 + J + len(iu))
+    rows = np.asarray(rows, np.float64).reshape(-1, off + 7)
+    if not (rows[:, off + 5] > 0).all():
+        raise ValueError('density_estimate_joint: no particle with a finite log-weight and finite coordinates')
+    out = []
+    for g, row in enumerate(rows):
+        lb, n_iter, converged, degenerate, _, count, _ = row[off:]
+        if degenerate:
+            warnings.warn('density_estimate_joint: a covariance lost positive definiteness at iteration {}: the parameters of the last '
+                          'good iteration are returned - raise reg_covar or lower num_mixture_components'.format(int(n_iter)),
+                          RuntimeWarning, stacklevel=3)
+        elif not converged:
+            warnings.warn('density_estimate_joint did not converge in {} iterations (last lower bound {}): raise max_iter or tol, '
+                          'or check the initial parameters'.format(int(n_iter), lb), RuntimeWarning, stacklevel=3)
+        cov = np.empty((K, J, J))
+        cov[:, iu, ku] = row[K + K * J:off].reshape(K, len(iu))
+        cov[:, ku, iu] = cov[:, iu, ku]
+        meta = dict(metadata if isinstance(metadata, dict) else metadata[g])
+        meta.update(op='density_estimate_joint', length=int(length), num_mixture_components=K, addresses=list(addresses),
+                    tol=float(tol), max_iter=int(max_iter), reg_covar=float(reg_covar))
+        out.append(JointMixtureFit(addresses, row[:K].copy(), row[K:K + K * J].reshape(K, J).copy(), cov, lb, n_iter, converged,
+                                   degenerate, count, meta))
     return out

@@ -4,8 +4,8 @@ import numpy as np
 import torch
 
 from .empirical import (_device_ecdf, _device_histograms, _device_hpd, _device_psis, _device_quantiles, _device_stats_row,
-                        _gmm_arguments, _gmm_init_rows, _hpd_levels, _joint_rows, _lw_sorted_groups, _mixtures_from_rows,
-                        _moment_rows, _philox_key, _psis_tail, _quantile_levels, _resample_op, _scheme_id, _sorted_groups)
+                        _gmm_arguments, _gmm_init_rows, _hpd_levels, _joint_fits_from_rows, _joint_gmm_init_rows, _joint_rows,
+                        _joint_start_means, _lw_sorted_groups, _mixtures_from_rows, _moment_rows, _philox_key, _psis_tail, _quantile_levels, _resample_op, _scheme_id, _sorted_groups)
 
 
 def _one_execution(posteriors, shared='_batch_log'):
@@ -194,6 +194,40 @@ def density_estimate_batch(posteriors, num_mixture_components=1, address=None, n
     rows = ops.is_gmm_groups(lw, column, K, N, group_stats, torch.from_numpy(init).to(lw.device), int(max_iter), float(tol),
                              float(reg_covar)).cpu().numpy()
     return _mixtures_from_rows(rows, K, [p._metadata for p in posteriors], N, tol, max_iter, reg_covar)
+
+
+def density_estimate_joint_batch(posteriors, num_mixture_components=1, addresses=None, tol=1e-3, max_iter=100, reg_covar=1e-6,
+                                 weights_init=None, means_init=None, covariances_init=None):
+    """[p.density_estimate_joint(num_mixture_components, addresses, ...) for p in posteriors] - and, where the posteriors are the M
+    groups of ONE Model.posterior_results_batch execution in order (recognised as joint_batch recognises them), the same
+    JointMixtureFits bit for bit from one sort of the first address for the initial means, one pp_is_moments_groups launch for the
+    initial covariances, ONE pp_is_gmm_joint_groups call over all groups (the maxima from the call's own [M, 6] statistics; groups
+    that converge early are frozen while the others go on) and one device-to-host copy of the rows. Anything else is served by
+    the loop."""
+    posteriors = list(posteriors)
+    K = _gmm_arguments(num_mixture_components, tol, max_iter, reg_covar)
+    if not posteriors:
+        return []
+    found = _batch_column(posteriors, None)
+    cols = None
+    if found is not None:
+        lw, _, N, group_stats = found
+        chosen, _ = posteriors[0]._joint_columns(addresses)
+        whole = _log_columns(posteriors[0]._batch_log)
+        cols = [whole.get(a) for a in chosen]
+        if any(c is None or c.dtype != torch.float32 or c.numel() != lw.numel() or not c.is_contiguous() for c in cols):
+            cols = None      # (reobserve_batch: the members share the [N] columns of ONE posterior)
+    if cols is None:
+        return [p.density_estimate_joint(K, addresses, tol, max_iter, reg_covar, weights_init, means_init, covariances_init)
+                for p in posteriors]
+    from .ops import ops
+    init = _joint_gmm_init_rows(K, len(cols), reg_covar, weights_init, means_init, covariances_init,
+                                lambda: _joint_start_means(lw, cols, N, group_stats, K),
+                                lambda: [j.cov for j in _joint_rows(chosen, _moment_rows(lw, cols, N, group_stats))])
+    init = np.array(np.broadcast_to(init, (len(posteriors), init.shape[1])))
+    rows = ops.is_gmm_joint_groups(lw, cols, K, N, group_stats, torch.from_numpy(init).to(lw.device), int(max_iter), float(tol),
+                                   float(reg_covar)).cpu().numpy()
+    return _joint_fits_from_rows(rows, chosen, K, [p._metadata for p in posteriors], N, tol, max_iter, reg_covar)
 
 
 def joint_batch(posteriors, addresses=None):

@@ -170,3 +170,75 @@ def _host_gmm(lw, x, init, max_iter, tol, reg_covar):
                 break
             before = lb
     return np.concatenate([pi, mu, v, [lb, float(n_iter), float(converged), W, float(fin.sum()), top]])
+
+
+def _cholesky_lower(cov):
+    """(the lower Cholesky factors [K, J, J] of the K matrices whose UPPER triangles are read from cov [K, J, J], whether every
+    pivot was positive) - all K matrices at once, column by column as pp_is_gmm_joint_groups factorises them."""
+    K, J, _ = cov.shape
+    L = np.zeros_like(cov)
+    for j in range(J):
+        for m in range(j + 1):
+            s = cov[:, m, j] - (L[:, j, :m] * L[:, m, :m]).sum(1)
+            if m < j:
+                L[:, j, m] = s / L[:, m, m]
+            elif not (s > 0).all():
+                return L, False
+            else:
+                L[:, j, j] = np.sqrt(s)
+    return L, True
+
+
+def _host_gmm_joint(lw, cols, init, K, max_iter, tol, reg_covar):
+    """pp_is_gmm_joint_groups' definition (include/pyprob_amd.h) in float64 numpy for one particle set: cols [J, n], init
+    [K (1 + J + J (J + 1) / 2)] = weights | means | covariances (upper triangles); its output row."""
+    lw, cols = np.asarray(lw, np.float64), np.asarray(cols, np.float64)
+    J = cols.shape[0]
+    iu, ku = np.triu_indices(J)
+    init = np.asarray(init, np.float64)
+    pi, mu = init[:K].copy(), init[K:K + K * J].reshape(K, J).copy()
+    cov = np.zeros((K, J, J))
+    cov[:, iu, ku] = init[K + K * J:].reshape(K, len(iu))
+    cov[:, ku, iu] = cov[:, iu, ku]
+
+    def row(pi, mu, cov, *tail):
+        return np.concatenate([pi, mu.reshape(-1), cov[:, iu, ku].reshape(-1), tail])
+    fin = np.isfinite(lw)
+    keep = fin & np.isfinite(cols).all(0)
+    top = lw[fin].max() if fin.any() else -np.inf
+    L, ok = _cholesky_lower(cov)
+    if not ok:
+        return row(pi, mu, cov, -np.inf, 0.0, 0.0, 1.0, 0.0, 0.0, -np.inf)
+    if not keep.any():
+        return row(pi * np.nan, mu * np.nan, cov * np.nan, np.nan, 0.0, 1.0, 0.0, 0.0, 0.0, top)
+    w, x = np.exp(lw[keep] - top), cols[:, keep].T
+    W, eye = w.sum(), np.eye(J)
+    before, lb, n_iter, converged = -np.inf, np.nan, 0, False
+    with np.errstate(all='ignore'):
+        for t in range(1, max_iter + 1):
+            l = np.empty((len(w), K))
+            for k in range(K):
+                z = np.linalg.solve(L[k], (x - mu[k]).T)
+                l[:, k] = np.log(pi[k]) - 0.5 * J * np.log(2.0 * np.pi) - np.log(np.diag(L[k])).sum() - 0.5 * (z * z).sum(0)
+            m = l.max(1)
+            Li = m + np.log(np.exp(l - m[:, None]).sum(1))
+            r = w[:, None] * np.exp(l - Li[:, None])
+            lb = float((w * Li).sum() / W)
+            N = r.sum(0) + 10.0 * np.finfo(np.float64).eps
+            new_mu, new_cov = np.empty_like(mu), np.empty_like(cov)
+            for k in range(K):
+                d = x - mu[k]
+                rd = r[:, k, None] * d
+                s = rd.sum(0) / N[k]
+                new_mu[k] = mu[k] + s
+                new_cov[k] = rd.T @ d / N[k] - np.outer(s, s) + reg_covar * eye
+            new_L, ok = _cholesky_lower(new_cov)
+            n_iter = t
+            if not ok:       # (degenerate: the parameters from before this M-step)
+                return row(pi, mu, cov, lb, float(t), 0.0, 1.0, W, float(keep.sum()), top)
+            pi, mu, cov, L = N / N.sum(), new_mu, new_cov, new_L
+            if abs(lb - before) < tol:
+                converged = True
+                break
+            before = lb
+    return row(pi, mu, cov, lb, float(n_iter), float(converged), 0.0, W, float(keep.sum()), top)

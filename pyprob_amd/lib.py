@@ -36,6 +36,7 @@ PP_IS_HPD_TILE = 2048        # starts one workgroup of pp_is_hpd_groups searches
 PP_RESAMPLE_MULTINOMIAL, PP_RESAMPLE_STRATIFIED, PP_RESAMPLE_SYSTEMATIC = 0, 1, 2      # pp_is_resample_scheme_groups' schemes
 PP_IS_PSIS_WIDTH = 8         # doubles per group of pp_is_psis_groups' out (include/pyprob_amd.h)
 PP_IS_GMM_MAX_K = 16         # mixture components of one pp_is_gmm_groups call (include/pyprob_amd.h)
+PP_IS_GMM_JOINT_MAX_J = 8    # columns of one pp_is_gmm_joint_groups call (include/pyprob_amd.h)
 
 
 def PP_IS_MOMENTS_WIDTH(n_cols):
@@ -49,6 +50,13 @@ def PP_IS_GMM_WIDTH(n_components):
     """Doubles per group of pp_is_gmm_groups' output (include/pyprob_amd.h): K weights, K means, K variances, the last lower bound,
     n_iter, converged, W, the count of finite log-weights and the group's maximum."""
     return 3 * int(n_components) + 6
+
+
+def PP_IS_GMM_JOINT_WIDTH(n_cols, n_components):
+    """Doubles per group of pp_is_gmm_joint_groups' output (include/pyprob_amd.h): K weights, K J means, K J (J + 1) / 2 covariance
+    entries (upper triangles), the last lower bound, n_iter, converged, degenerate, W, the count and the group's maximum."""
+    J, K = int(n_cols), int(n_components)
+    return K * (1 + J + J * (J + 1) // 2) + 7
 
 
 i32, i64, f32p, i32p, vp = C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p
@@ -238,6 +246,8 @@ PROTOTYPES = {
     'pp_is_psis_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_gmm_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
     'pp_is_gmm_groups': (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, C.c_size_t, vp]),
+    'pp_is_gmm_joint_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
+    'pp_is_gmm_joint_groups': (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

@@ -36,6 +36,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_ecdf_groups      the posterior cdf at points given per group (the reference has none)      pyprob/distributions/empirical.py:668-728
     is_psis_groups      Pareto-smoothed importance weights and k-hat per group (the reference has none)   pyprob/distributions/empirical.py:758-766
     is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
+    is_gmm_joint_groups weighted full-covariance Gaussian-mixture EM of several latents per group (density_estimate_joint)   -
     reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -106,6 +107,8 @@ _lib.define('is_psis_groups(Tensor lw_sorted, Tensor index_sorted, Tensor counte
             'bool want_weights) -> (Tensor?, Tensor)')
 _lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Tensor? stats, Tensor params_init, int max_iter, '
             'float tol, float reg_covar) -> Tensor')
+_lib.define('is_gmm_joint_groups(Tensor lw, Tensor[] cols, int n_components, int n_per, Tensor? stats, Tensor params_init, '
+            'int max_iter, float tol, float reg_covar) -> Tensor')
 _lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
             'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -1099,6 +1102,37 @@ def _is_gmm_groups_hip(lw, x, n_components, n_per, stats, params_init, max_iter,
     return out
 
 
+def _is_gmm_joint_groups_hip(lw, cols, n_components, n_per, stats, params_init, max_iter, tol, reg_covar):
+    """[M, PP_IS_GMM_JOINT_WIDTH(J, K)] (float64): weights, means, covariances (upper triangles) | last lower bound, n_iter, converged,
+    degenerate, W, count, max lw of the weighted EM for K full-covariance Gaussians over the J columns in each of the M groups of
+    n_per particles (pp_is_gmm_joint_groups), started from params_init (float64 [M, K (1 + J + J (J + 1) / 2)]: weights | means |
+    covariances). stats: as for is_cdf_groups."""
+    lib = L.load()
+    cols = list(cols)
+    _same_device(lw, stats, params_init, *cols)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_gmm_joint_groups')
+    J, K = len(cols), int(n_components)
+    if not 1 <= J <= L.PP_IS_GMM_JOINT_MAX_J or not 1 <= K <= L.PP_IS_GMM_MAX_K:
+        raise RuntimeError('pyprob_hip::is_gmm_joint_groups: 1 .. %d columns and 1 .. %d mixture components'
+                           % (L.PP_IS_GMM_JOINT_MAX_J, L.PP_IS_GMM_MAX_K))
+    for c in cols:
+        _particles_like(c, lw, 'every column', 'is_gmm_joint_groups')
+    _group_stats_ok(stats, M, 'is_gmm_joint_groups')
+    width = L.PP_IS_GMM_JOINT_WIDTH(J, K)
+    if params_init.dtype != torch.float64 or not params_init.is_contiguous() or params_init.numel() != M * (width - 7):
+        raise RuntimeError('pyprob_hip::is_gmm_joint_groups: params_init must be a contiguous float64 tensor of '
+                           '[M, K (1 + J + J (J + 1) / 2)]')
+    out = torch.empty((M, width), dtype=torch.float64, device=lw.device)
+    ws, need = _workspace(lib.pp_is_gmm_joint_workspace_bytes, lw.device, M, int(n_per), J, K)
+    ptrs = (C.c_void_p * J)(*[c.data_ptr() for c in cols])
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_gmm_joint_groups(lw.data_ptr(), C.cast(ptrs, C.c_void_p), J, K, M, int(n_per), L.ptr(stats),
+                                        params_init.data_ptr(), int(max_iter), float(tol), float(reg_covar), gmm_check_every(),
+                                        out.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_gmm_joint_groups')
+    return out
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -1130,6 +1164,7 @@ _lib.impl('is_hpd_groups', _is_hpd_groups_hip, 'CUDA')
 _lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
+_lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
