@@ -1050,6 +1050,48 @@ int pp_is_gmm_joint_groups(const float* lw /*dev [M n_per]*/, const float* const
                            double reg_covar, int32_t check_every, double* out /*dev double [M, PP_IS_GMM_JOINT_WIDTH(J, K)]*/,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Weighted Gaussian kernel density of one latent, or of a pair of latents on a rectangular grid, per group of an [M, n_per] block of
+ * a lock-step posterior call. The reference has no counterpart: the shape of a posterior is plot_histogram there
+ * (pyprob/distributions/empirical.py:889-914) or the 1000-sample density_estimate (:795-807).
+ *   pp_is_kde_groups    density[g, q] = sum_i wbar_i N(points[g, q]; x_i, h_g^2) over the particles that count - finite lw, x not
+ *                       NaN: what pp_is_sort_groups counts -, w_i = exp((double)lw_i - max_g) rounded to fp32, wbar_i = w_i / sum w
+ *                       with the sum taken here over the same particles and weights (max_g = stats[6 g] or, without `stats`, the
+ *                       largest finite lw of the group: the same bits; no other entry of `stats` is read). log_density = log
+ *                       (density), -inf where that is 0. Nothing counted: NaN. points (finite, within fp32's range): [n_x] shared
+ *                       (x_stride 0) or one row per group; bandwidth (finite, > 0): one shared (stride 0) or [M] (stride 1).
+ *                       One workgroup per (group, tile of 2048 particles, chunk of 256 P points; P = 1, 2, 4 from n_x): the tile is
+ *                       staged into LDS once as (x_i, w_i), every lane keeps P points as fp32 pairs hi + lo and evaluates
+ *                       v_exp_f32(-(((hi - x_i) + lo) s)^2), s = fp32(1 / (h sqrt(2 ln 2))) - the exponent from the difference,
+ *                       never from an expanded square -, fp32 sums over 256 particles in index order, flushed to fp64. A group of
+ *                       one tile is finished by that launch; a longer one stores a partial row per tile and a second launch adds
+ *                       them in tile order and scales.
+ *   pp_is_kde2d_groups  density[g, a, b] = sum_i wbar_i N(points_x[g, a]; x_i, hx_g^2) N(points_y[g, b]; y_i, hy_g^2); a particle counts
+ *                       where neither coordinate is NaN. A product over K = the particles on v_mfma_f32_32x32x2_f32 whose operands
+ *                       are computed in the fragment layout (two v_exp_f32 per lane and K-step), a wave per 32 x 32 block of the
+ *                       grid, fp32 accumulators flushed to fp64 once per tile of 2048 particles; sides up to PP_IS_KDE2D_MAX_SIDE.
+ * Error bounds: the head of csrc/is_kde.hip and DESIGN.md. No atomics, no workgroup waits for another; a group's bits depend on
+ * (n_per, n_x[, n_y]) and its own data, never on M or the other groups, and a call repeated gives the same bits. Nothing is written
+ * outside density, log_density and the workspace (pp_is_kde_workspace_bytes / pp_is_kde2d_workspace_bytes; PP_ENOSPACE when shorter).
+ * PP_EINVAL without a launch for a NULL pointer other than stats, n_per < 1, n_groups < 0, n_x outside 1 .. PP_IS_KDE_MAX_POINTS (2-D:
+ * a side outside 1 .. PP_IS_KDE2D_MAX_SIDE), a point stride that is neither 0 nor at least the row, a bandwidth stride other than 0
+ * or 1, or M n_per or the number of results above 2^31 - 1; the workspace functions return 0 outside that envelope. */
+#define PP_IS_KDE_MAX_POINTS 4096
+#define PP_IS_KDE2D_MAX_SIDE 256
+size_t pp_is_kde_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_x);
+int pp_is_kde_groups(const float* lw /*dev [M n_per]*/, const float* x /*dev [M n_per]*/, int32_t n_groups, int32_t n_per,
+                     const double* points /*dev [n_x] or [M, x_stride]*/, int32_t n_x, int64_t x_stride,
+                     const double* bandwidth /*dev [1] or [M]*/, int64_t bandwidth_stride, const double* stats /*dev double [M, 6] or NULL*/,
+                     double* density /*dev [M, n_x]*/, double* log_density /*dev [M, n_x]*/, void* workspace, size_t workspace_bytes,
+                     void* stream);
+size_t pp_is_kde2d_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_x, int32_t n_y);
+int pp_is_kde2d_groups(const float* lw /*dev [M n_per]*/, const float* x /*dev [M n_per]*/, const float* y /*dev [M n_per]*/,
+                       int32_t n_groups, int32_t n_per, const double* points_x /*dev [n_x] or [M, x_stride]*/, int32_t n_x,
+                       int64_t x_stride, const double* points_y /*dev [n_y] or [M, y_stride]*/, int32_t n_y, int64_t y_stride,
+                       const double* bandwidth_x /*dev [1] or [M]*/, int64_t bandwidth_x_stride, const double* bandwidth_y,
+                       int64_t bandwidth_y_stride, const double* stats /*dev double [M, 6] or NULL*/,
+                       double* density /*dev [M, n_x, n_y]*/, double* log_density /*dev [M, n_x, n_y]*/, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* Prior draws of vectorised trace generation (the per-trace generator: pyprob/nn/dataset.py:50-62 with state.sample's
  * prior branch pyprob/state.py:278-290): out[i] ~ Normal(p0, p1) (kind 0) | Uniform[p0, p1) (kind 1), parameters shared
  * (stride 0) or per trace (stride 1); Philox4x32-10, counter offset + i, key seed, `stream_id` distinguishes statements. */

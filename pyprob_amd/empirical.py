@@ -9,7 +9,7 @@ import warnings
 import numpy as np
 import torch
 
-from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_order, _host_psis,
+from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_kde, _host_order, _host_psis,
                              _host_quantiles)
 
 
@@ -588,6 +588,77 @@ class Empirical:
         row = ops.is_hist_groups(lw, cols[0], cols[1], n, torch.from_numpy(ex).to(lw.device), torch.from_numpy(ey).to(lw.device),
                                  self._group_stats_row()).cpu().numpy()[0]
         return _histogram2d_row(chosen, ex, ey, row)
+
+    # ---- kernel density (csrc/is_kde.hip) -------------------------------------------------------------------------------
+    def _counted_extent(self):
+        """(min, max, counted, NaN values) over the particles with a finite log-weight: pp_is_extent_groups' row, kept with a
+        device-backed object, or the same in numpy."""
+        if self._device_backed():
+            self._device_extent()
+            return self.__dict__['_dev_extent']
+        lw, v = self._host_scalars()
+        if v is None:
+            raise ValueError('kde needs scalar values')
+        return _host_extent(lw, v)
+
+    def kde(self, x=None, bandwidth=None, grid=512):
+        """The weighted Gaussian kernel density sum_i w_i N(x; x_i, h^2) of the values as a KernelDensity (x, density, log_density,
+        bandwidth, count, ess, mode): the smooth non-parametric curve of the posterior, where histogram resolves to a bin width and
+        density_estimate imposes K Gaussians. The particles that count are those quantile counts (finite log-weight, value not NaN),
+        w their normalised weights. x: a scalar or a sequence of at most 4096 points; None: `grid` uniform points from min - 3 h to
+        max + 3 h. bandwidth: h, finite and > 0; None: Silverman's rule under the weights, 0.9 min(stddev, IQR / 1.34)
+        ess^(-1/5) from the object's own stddev, quantile([0.25, 0.75]) and effective_sample_size (an IQR of 0: stddev alone; no
+        spread at all, fewer than two particles that count or a NaN value under a finite weight: ValueError - pass bandwidth=).
+
+        A device-backed Empirical (the result of a lock-step posterior call, post.marginal(address), a device resample, psis(),
+        reobserve()) is evaluated on the device: pp_is_kde_groups - one launch up to 2048 particles, two above - and one copy of
+        2 Q doubles; the error bound is DESIGN.md's. Every other Empirical, and all of them under PP_EMPIRICAL_DEVICE=0, computes
+        the same definition in float64 numpy."""
+        self._check_finalized()
+        if self.length == 0:
+            raise ValueError('kde of an empty Empirical')
+        ext = self._counted_extent()
+        h = _kde_bandwidth(bandwidth, lambda: _silverman(math.sqrt(self._skipping_variance()), self.quantile([0.25, 0.75]),
+                                                         self.effective_sample_size, int(ext[2])))
+        pts = _kde_points(x, grid, ext, h, _KDE_MAX_POINTS)
+        if self._device_backed():
+            from .ops import ops
+            dev = self._log_weights.device
+            out = ops.is_kde_groups(self._log_weights, self._values, self.length, torch.from_numpy(pts).to(dev),
+                                    torch.tensor([h], dtype=torch.float64, device=dev), self._group_stats_row()).cpu().numpy()[:, 0]
+        else:
+            out = _host_kde(*self._host_scalars(), pts, h)
+        return KernelDensity(pts, out[0], out[1], h, int(ext[2]), self.effective_sample_size)
+
+    def kde2d(self, x, y, grid=(64, 64), bandwidth=None, range=None):
+        """The weighted kernel density of TWO latents of a lock-step call on a rectangular grid as a KernelDensity2D (addresses, x [Qx],
+        y [Qy], density [Qx, Qy], log_density, bandwidth (hx, hy), count, ess, mode): sum_i w_i N(x; x_i, hx^2) N(y; y_i, hy^2), the
+        contours histogram2d shows in bins. x / y: addresses or statement names as joint() takes them (an address only some
+        particles executed raises joint()'s ValueError). grid: one number or (Qx, Qy), each side at most 256. range: ((xlo, xhi),
+        (ylo, yhi)); None: min - 3 h to max + 3 h per axis (pp_is_extent_groups). bandwidth: one number or (hx, hy); None:
+        Scott's rule per axis, stddev ess^(-1/6) with joint()'s numbers (no spread: ValueError - pass bandwidth=). count is
+        joint()'s: the particles with a finite log-weight. One pp_is_kde2d_groups call - the sum over the particles runs on the fp32
+        matrix pipe - and one copy. Only the result of a lock-step posterior call has the statement log this needs."""
+        self._check_finalized()
+        chosen, cols = self._joint_columns([x, y])
+        lw = self._all_lw()
+        n, stats = lw.numel(), self._group_stats_row()
+        sides = (grid, grid) if np.ndim(grid) == 0 else tuple(grid)
+        moments = _joint_rows(chosen, _moment_rows(lw, cols, n, stats))[0]
+        given = (None, None) if bandwidth is None else (bandwidth, bandwidth) if np.ndim(bandwidth) == 0 else tuple(bandwidth)
+        if len(sides) != 2 or len(given) != 2:
+            raise ValueError('grid and bandwidth are one number or a pair')
+        from .ops import ops
+        hs, pts = [], []
+        for j in (0, 1):
+            hs.append(_kde_bandwidth(given[j], lambda: _scott(moments.stddev[j], moments.ess, int(moments.count))))
+            ext = None if range is not None else ops.is_extent_groups(lw, cols[j], n).cpu().numpy()[0]
+            pts.append(_kde_points(None, sides[j], ext, hs[j], _KDE2D_MAX_SIDE, None if range is None else range[j]))
+        dev = lw.device
+        as_dev = lambda a: torch.from_numpy(np.asarray(a, np.float64).reshape(-1)).to(dev)      # noqa: E731
+        out = ops.is_kde2d_groups(lw, cols[0], cols[1], n, as_dev(pts[0]), as_dev(pts[1]), as_dev(hs[0]), as_dev(hs[1]),
+                                  stats).cpu().numpy()[:, 0]
+        return KernelDensity2D(chosen, pts[0], pts[1], out[0], out[1], (hs[0], hs[1]), int(moments.count), float(moments.ess))
 
     # ---- order statistics (csrc/is_sort.hip) ---------------------------------------------------------------------------
     def _device_sorted(self):
@@ -1527,6 +1598,89 @@ def _device_histograms(lw, x, n_per, bins, range, edges, stats):
     e = _hist_edges_for(bins, range, edges, lambda: ops.is_extent_groups(lw, x, int(n_per)).cpu().numpy())
     dev = torch.from_numpy(e if e.shape[0] > 1 else e[0]).to(lw.device)
     return _histogram_rows(e, ops.is_hist_groups(lw, x, None, int(n_per), dev, None, stats).cpu().numpy())
+
+
+_KDE_MAX_POINTS = 4096      # PP_IS_KDE_MAX_POINTS (include/pyprob_amd.h)
+_KDE2D_MAX_SIDE = 256       # PP_IS_KDE2D_MAX_SIDE
+_FLT_MAX = 3.4028234663852886e38
+
+
+class KernelDensity:
+    """A weighted Gaussian kernel density of one particle set (Empirical.kde), float64 numpy: x [Q] the points, density [Q],
+    log_density [Q] (-inf where the density is 0), bandwidth h, count (the particles with a finite log-weight and a value that is not
+    NaN), ess, and mode: the x of the largest density."""
+
+    def __init__(self, x, density, log_density, bandwidth, count, ess):
+        self.x, self.density, self.log_density = x, density, log_density
+        self.bandwidth, self.count, self.ess = float(bandwidth), int(count), float(ess)
+        self.mode = float(x[int(np.argmax(density))]) if count and not np.isnan(density).all() else float('nan')
+
+    def __repr__(self):
+        return 'KernelDensity(points:{}, bandwidth:{:.6g}, mode:{:.6g}, count:{})'.format(len(self.x), self.bandwidth, self.mode,
+                                                                                      self.count)
+
+
+class KernelDensity2D:
+    """A weighted product-Gaussian kernel density of two latents (Empirical.kde2d), float64 numpy: addresses, x [Qx], y [Qy], density
+    [Qx, Qy], log_density, bandwidth (hx, hy), count, ess, and mode: the (x, y) of the largest density."""
+
+    def __init__(self, addresses, x, y, density, log_density, bandwidth, count, ess):
+        self.addresses, self.x, self.y, self.density, self.log_density = list(addresses), x, y, density, log_density
+        self.bandwidth, self.count, self.ess = (float(bandwidth[0]), float(bandwidth[1])), int(count), float(ess)
+        a, b = np.unravel_index(int(np.argmax(density)), density.shape) if not np.isnan(density).all() else (None, None)
+        self.mode = (float('nan'), float('nan')) if a is None else (float(x[a]), float(y[b]))
+
+    def __repr__(self):
+        return 'KernelDensity2D(addresses:{}, grid:{}x{}, bandwidth:{})'.format(self.addresses, len(self.x), len(self.y), self.bandwidth)
+
+
+def _kde_bandwidth(bandwidth, rule):
+    """The bandwidth given (finite and > 0), or rule() where it is None."""
+    if bandwidth is None:
+        return rule()
+    h = float(bandwidth)
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError('bandwidth must be finite and > 0, not %r' % (bandwidth,))
+    return h
+
+
+def _rule_bandwidth(spread, ess, power, count):
+    if count < 2 or not (spread > 0 and np.isfinite(spread) and ess > 0):
+        raise ValueError('the particles have no spread to take a bandwidth from (fewer than two count, all values equal, or a '
+                         'value that is not finite under a finite weight): pass bandwidth=')
+    return float(spread * ess ** power)
+
+
+def _silverman(stddev, quartiles, ess, count):
+    """Silverman's rule under the weights: 0.9 min(stddev, IQR / 1.34) ess^(-1/5); an IQR of 0 leaves the stddev."""
+    iqr = float(quartiles[1]) - float(quartiles[0])
+    return _rule_bandwidth(0.9 * (min(stddev, iqr / 1.34) if iqr > 0 else stddev), ess, -0.2, count)
+
+
+def _scott(stddev, ess, count):
+    """Scott's rule for one axis of two: stddev ess^(-1/6)."""
+    return _rule_bandwidth(float(stddev), ess, -1.0 / 6.0, count)
+
+
+def _kde_points(x, grid, ext, h, most, span=None):
+    """The evaluation points float64 [Q], 1 <= Q <= most: x (a scalar or a sequence, finite, within fp32's range) or, x None, `grid`
+    uniform points over span = (lo, hi), default min - 3 h .. max + 3 h of the extent row `ext`."""
+    if x is not None:
+        pts = _flat_argument(x, 'x is a scalar or a sequence of finite points', lambda v: np.abs(v) <= _FLT_MAX)[0]
+        if not 1 <= len(pts) <= most:
+            raise ValueError('between 1 and %d points, not %d' % (most, len(pts)))
+        return pts
+    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or not 1 <= int(grid) <= most:
+        raise ValueError('grid must be an integer in 1 .. %d, not %r' % (most, grid))
+    if span is None:
+        if not ext[2] or not (np.isfinite(ext[0]) and np.isfinite(ext[1])):
+            raise ValueError('the extent of the values is not finite (nothing counted, or an infinite value under a finite weight): '
+                             'pass x= / range=')
+        span = (float(ext[0]) - 3.0 * h, float(ext[1]) + 3.0 * h)
+    lo, hi = (float(v) for v in span)
+    if not (abs(lo) <= _FLT_MAX and abs(hi) <= _FLT_MAX) or lo > hi:
+        raise ValueError('range must be finite with lo <= hi, not %r' % (span,))
+    return np.linspace(lo, hi, int(grid))
 
 
 class PsisFit:

@@ -3,7 +3,8 @@ Model.posterior_results_batch execution in order, the same result bit for bit fr
 import numpy as np
 import torch
 
-from .empirical import (_device_ecdf, _device_histograms, _device_hpd, _device_psis, _device_quantiles, _device_stats_row,
+from .empirical import (KernelDensity, _kde_bandwidth, _kde_points, _silverman, _KDE_MAX_POINTS,
+                        _device_ecdf, _device_histograms, _device_hpd, _device_psis, _device_quantiles, _device_stats_row,
                         _gmm_arguments, _gmm_init_rows, _hpd_levels, _joint_fits_from_rows, _joint_gmm_init_rows, _joint_rows,
                         _joint_start_means, _lw_sorted_groups, _mixtures_from_rows, _moment_rows, _philox_key, _psis_tail, _quantile_levels, _resample_op, _scheme_id, _sorted_groups)
 
@@ -122,6 +123,41 @@ def cdf_batch(posteriors, x, address=None, strict=False):
     else:
         out = _device_ecdf(_sorted_groups(*found), found[2], pts, strict)
     return out.reshape(xs.shape)
+
+
+def kde_batch(posteriors, x=None, bandwidth=None, grid=512, address=None):
+    """[p.kde(x[g], bandwidth[g], grid) for g, p in enumerate(posteriors)] as a list of M KernelDensity, or with address=
+    [p.marginal(address).kde(...) ...] - and, where the posteriors are the M groups of ONE Model.posterior_results_batch execution
+    in order (recognised as cdf_batch recognises them), the same results bit for bit from one pp_is_extent_groups launch (x=None:
+    every group gets the grid of its own extent), ONE pp_is_kde_groups call over all groups and one copy of the rows. x: [Q]
+    shared by the posteriors, [M, Q], or None; bandwidth: one number, [M], or None: Silverman's rule per group (one
+    quantile_batch call for the quartiles, each group's own stddev and ess)."""
+    posteriors = list(posteriors)
+    M = len(posteriors)
+    xs = None if x is None else np.asarray(x, np.float64)
+    if xs is not None and (xs.ndim not in (1, 2) or (xs.ndim == 2 and xs.shape[0] != M)):
+        raise ValueError('x is [Q] (shared by the posteriors) or [M, Q]: one row of points per posterior')
+    hs = None if bandwidth is None else np.asarray(bandwidth, np.float64)
+    if hs is not None and (hs.ndim > 1 or (hs.ndim == 1 and hs.shape[0] != M)):
+        raise ValueError('bandwidth is one number or [M]: one per posterior')
+    if not posteriors:
+        return []
+    x_of = lambda g: xs if (xs is None or xs.ndim == 1) else xs[g]            # noqa: E731
+    h_of = lambda g: hs if (hs is None or hs.ndim == 0) else hs[g]            # noqa: E731
+    found = _batch_column(posteriors, address)
+    if found is None:
+        return [_target(p, address).kde(x_of(g), h_of(g), grid) for g, p in enumerate(posteriors)]
+    from .ops import ops
+    lw, column, N, group_stats = found
+    ext = ops.is_extent_groups(lw, column, N).cpu().numpy()
+    targets = [_target(p, address) for p in posteriors]
+    quart = quantile_batch(posteriors, [0.25, 0.75], address) if hs is None else None
+    h = [_kde_bandwidth(h_of(g), lambda: _silverman(np.sqrt(t._skipping_variance()), quart[g], t.effective_sample_size, int(ext[g, 2])))
+         for g, t in enumerate(targets)]
+    pts = np.stack([_kde_points(x_of(g), grid, ext[g], h[g], _KDE_MAX_POINTS) for g in range(M)])
+    out = ops.is_kde_groups(lw, column, N, torch.from_numpy(pts).to(lw.device), torch.tensor(h, dtype=torch.float64, device=lw.device),
+                            group_stats).cpu().numpy()
+    return [KernelDensity(pts[g], out[0, g], out[1, g], h[g], int(ext[g, 2]), t.effective_sample_size) for g, t in enumerate(targets)]
 
 
 def _psis_batch_call(posteriors, tail, want_weights):

@@ -96,6 +96,41 @@ def _host_hist_row(lw, x, e):
     return np.stack([np.bincount(slot, weights=w, minlength=bins + 3), np.bincount(slot, minlength=bins + 3).astype(np.float64)])
 
 
+def _host_kde(lw, x, pts, h):
+    """pp_is_kde_groups' definition in float64 numpy for one particle set: [2, Q] (density | log density) at the points pts under the
+    bandwidth h, over the particles with a finite log-weight and a value that is not NaN. Nothing counted: NaN."""
+    keep = np.isfinite(lw) & ~np.isnan(x)
+    if not keep.any():
+        return np.full((2, len(pts)), np.nan)
+    v, w = x[keep], np.exp(lw[keep] - np.max(lw[np.isfinite(lw)]))
+    dens = np.empty(len(pts))
+    step = max(1, (1 << 22) // len(v))
+    for q in range(0, len(pts), step):
+        z = (pts[q:q + step, None] - v[None, :]) / h
+        dens[q:q + step] = np.exp(-0.5 * z * z) @ w
+    dens /= h * math.sqrt(2.0 * math.pi) * w.sum()
+    with np.errstate(divide='ignore'):
+        return np.stack([dens, np.log(dens)])
+
+
+def _host_kde2d(lw, x, y, px, py, hx, hy):
+    """pp_is_kde2d_groups' definition in float64 numpy for one particle set: [2, Qx, Qy] on the grid px x py (product kernel), over the
+    particles with a finite log-weight and neither coordinate NaN."""
+    keep = np.isfinite(lw) & ~np.isnan(x) & ~np.isnan(y)
+    if not keep.any():
+        return np.full((2, len(px), len(py)), np.nan)
+    u, v, w = x[keep], y[keep], np.exp(lw[keep] - np.max(lw[np.isfinite(lw)]))
+    dens = np.zeros((len(px), len(py)))
+    step = max(1, (1 << 22) // max(len(px), len(py)))
+    for i in range(0, len(u), step):
+        zx = (px[:, None] - u[None, i:i + step]) / hx
+        zy = (py[:, None] - v[None, i:i + step]) / hy
+        dens += (np.exp(-0.5 * zx * zx) * w[i:i + step]) @ np.exp(-0.5 * zy * zy).T
+    dens /= 2.0 * math.pi * hx * hy * w.sum()
+    with np.errstate(divide='ignore'):
+        return np.stack([dens, np.log(dens)])
+
+
 def _host_psis(lw, tail, want_weights=True):
     """pp_is_psis_groups' definition in float64 numpy for one particle set: (smoothed log-weights float64 [n] or None, the row of
     PP_IS_PSIS_WIDTH doubles). The smoothed tail log-weights are rounded to float32 as the device stores them."""

@@ -37,6 +37,8 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_psis_groups      Pareto-smoothed importance weights and k-hat per group (the reference has none)   pyprob/distributions/empirical.py:758-766
     is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
     is_gmm_joint_groups weighted full-covariance Gaussian-mixture EM of several latents per group (density_estimate_joint)   -
+    is_kde_groups       weighted Gaussian kernel density of a latent at points per group (the reference has none)   -
+    is_kde2d_groups     the same for two latents on a rectangular grid, on the fp32 matrix pipe (the reference has none)   -
     reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -109,6 +111,9 @@ _lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Ten
             'float tol, float reg_covar) -> Tensor')
 _lib.define('is_gmm_joint_groups(Tensor lw, Tensor[] cols, int n_components, int n_per, Tensor? stats, Tensor params_init, '
             'int max_iter, float tol, float reg_covar) -> Tensor')
+_lib.define('is_kde_groups(Tensor lw, Tensor x, int n_per, Tensor points, Tensor bandwidth, Tensor? stats) -> Tensor')
+_lib.define('is_kde2d_groups(Tensor lw, Tensor x, Tensor y, int n_per, Tensor points_x, Tensor points_y, Tensor bandwidth_x, '
+            'Tensor bandwidth_y, Tensor? stats) -> Tensor')
 _lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
             'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -1017,6 +1022,63 @@ def _is_ecdf_groups_hip(value_sorted, cdf_sorted, counted, n_per, x, strict):
     return out, rank
 
 
+def _kde_rows(t, M, most, name, what):
+    """(row length, stride) of a float64 tensor of points: [Q] shared by the groups (stride 0) or [M, Q], one row per group."""
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != M) or \
+            not 1 <= t.shape[-1] <= most:
+        raise RuntimeError('pyprob_hip::%s: %s must be a contiguous float64 tensor of [Q] or [M, Q], 1 <= Q <= %d' % (what, name, most))
+    return int(t.shape[-1]), (0 if t.dim() == 1 else int(t.shape[-1]))
+
+
+def _kde_bandwidth(t, M, name, what):
+    """The stride of a float64 bandwidth tensor: one element shared by the groups (0) or [M] (1)."""
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() not in (1, M):
+        raise RuntimeError('pyprob_hip::%s: %s must be a contiguous float64 tensor of 1 or M elements' % (what, name))
+    return 1 if (t.dim() == 1 and t.numel() == M and M > 1) else 0
+
+
+def _is_kde_groups_hip(lw, x, n_per, points, bandwidth, stats):
+    """[2, M, Q] (float64; density | log density): the weighted Gaussian kernel density of x at points ([Q] shared or [M, Q]) under
+    the bandwidth (one or [M]) for each of the M groups of n_per particles (pp_is_kde_groups). stats: as for is_cdf_groups."""
+    lib = L.load()
+    _same_device(lw, x, points, bandwidth, stats)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_kde_groups')
+    _particles_like(x, lw, 'x', 'is_kde_groups')
+    Q, sp = _kde_rows(points, M, L.PP_IS_KDE_MAX_POINTS, 'points', 'is_kde_groups')
+    sh = _kde_bandwidth(bandwidth, M, 'bandwidth', 'is_kde_groups')
+    _group_stats_ok(stats, M, 'is_kde_groups')
+    out = torch.empty((2, M, Q), dtype=torch.float64, device=lw.device)
+    ws, need = _workspace(lib.pp_is_kde_workspace_bytes, lw.device, M, int(n_per), Q)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_kde_groups(lw.data_ptr(), x.data_ptr(), M, int(n_per), points.data_ptr(), Q, sp, bandwidth.data_ptr(), sh,
+                                  L.ptr(stats), out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_kde_groups')
+    return out
+
+
+def _is_kde2d_groups_hip(lw, x, y, n_per, points_x, points_y, bandwidth_x, bandwidth_y, stats):
+    """[2, M, Qx, Qy] (float64; density | log density): the weighted product-Gaussian kernel density of (x, y) on the grid points_x
+    x points_y (each [Q] shared or [M, Q]) for each of the M groups of n_per particles (pp_is_kde2d_groups)."""
+    lib = L.load()
+    _same_device(lw, x, y, points_x, points_y, bandwidth_x, bandwidth_y, stats)
+    M = _groups_of(_f32(lw, 'lw'), n_per, 'is_kde2d_groups')
+    _particles_like(x, lw, 'x', 'is_kde2d_groups')
+    _particles_like(y, lw, 'y', 'is_kde2d_groups')
+    Qx, spx = _kde_rows(points_x, M, L.PP_IS_KDE2D_MAX_SIDE, 'points_x', 'is_kde2d_groups')
+    Qy, spy = _kde_rows(points_y, M, L.PP_IS_KDE2D_MAX_SIDE, 'points_y', 'is_kde2d_groups')
+    shx = _kde_bandwidth(bandwidth_x, M, 'bandwidth_x', 'is_kde2d_groups')
+    shy = _kde_bandwidth(bandwidth_y, M, 'bandwidth_y', 'is_kde2d_groups')
+    _group_stats_ok(stats, M, 'is_kde2d_groups')
+    out = torch.empty((2, M, Qx, Qy), dtype=torch.float64, device=lw.device)
+    ws, need = _workspace(lib.pp_is_kde2d_workspace_bytes, lw.device, M, int(n_per), Qx, Qy)
+    with torch.cuda.device(lw.device):
+        rc = lib.pp_is_kde2d_groups(lw.data_ptr(), x.data_ptr(), y.data_ptr(), M, int(n_per), points_x.data_ptr(), Qx, spx,
+                                    points_y.data_ptr(), Qy, spy, bandwidth_x.data_ptr(), shx, bandwidth_y.data_ptr(), shy,
+                                    L.ptr(stats), out[0].data_ptr(), out[1].data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_kde2d_groups')
+    return out
+
+
 def _is_psis_groups_hip(lw_sorted, index_sorted, counted, n_per, stats, tail, want_weights):
     """(lw_out float32 [M n_per] in particle order or None, out float64 [M, PP_IS_PSIS_WIDTH]): the Pareto-smoothed log-weights and
     the fit (k-hat, sigma, n, m, f, cutoff log-weight, c, maximum) of each of the M groups of n_per particles sorted by their
@@ -1165,6 +1227,8 @@ _lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
+_lib.impl('is_kde_groups', _is_kde_groups_hip, 'CUDA')
+_lib.impl('is_kde2d_groups', _is_kde2d_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')
 _lib.impl('dist_draw', _dist_draw_hip, 'CUDA')
 _lib.impl('mix_logweight', _mix_logweight_hip, 'CUDA')
