@@ -919,6 +919,51 @@ int pp_is_ecdf_groups(const float* value_sorted /*dev [M n_per]*/, const double*
                       int32_t n_x, int32_t strict, double* out /*dev [M, n_x]*/, int32_t* rank_out /*dev [M, n_x] or NULL*/,
                       void* stream);
 
+/* Two-sample distances between two lock-step posteriors of a scalar on the device: how far apart two weighted samples are. The
+ * reference compares a posterior with an analytic one by Distribution.kl_divergence (pyprob/distributions/distribution.py) and has
+ * no distance between two Empiricals. INPUTS per side, in the [M n_per] layout with a n_per of its own: pp_is_sort_groups' value_out
+ * and counted_out and pp_is_cdf_groups over its lw_out - what pp_is_quantile_groups takes. For group g let a[0..ca) and b[0..cb) be
+ * the counted particles of the two sides in sorted order (ca = counted_a[g, 0], clamped to [0, n_per_a]), WA and WB their cumulative
+ * weights, TA = WA[ca - 1], TB = WB[cb - 1], uA[i] = fl(WA[i] / TA), uB[j] = fl(WB[j] / TB). ca == 0, cb == 0, or a TA or TB that is
+ * not positive and finite: out[g, 0..4] and out[g, 7] are NaN (the two counts are written all the same).
+ *   VALUE WALK      Merge the two value sequences, stable, A before B on ties (-0.0 == +0.0). After consuming merged element k
+ *                   (k = 0 .. ca + cb - 1) with value z_k let i and j be the numbers consumed from each side,
+ *                   D_k = (i ? uA[i - 1] : 0) - (j ? uB[j - 1] : 0) (one fp64 subtraction) and next the smaller remaining head, if
+ *                   any. k is a STEP when next > z_k, and a run end when it is a step or nothing remains: there the counts of both
+ *                   sides are those of every value <= z_k.
+ *                     ks            = max |D_k| over the run ends, ks_location = (double)z_k of the first such maximum and
+ *                                     ks_position = its k.
+ *                     wasserstein1  = sum over the steps with D_k != 0 of |D_k| ((double)next - (double)z_k): int |F - G|.
+ *                     energy        = 2 sum over the same k of D_k^2 ((double)next - (double)z_k): the energy distance
+ *                                     2 E|X - Y| - E|X - X'| - E|Y - Y'| = 2 int (F - G)^2 of two samples of a scalar.
+ *                   Mass at -inf or +inf that the other side does not match gives +inf, never NaN: a term needs next > z_k.
+ *   QUANTILE WALK   Merge uA and uB the same way (A before B on ties). With (i, j) the numbers consumed BEFORE merged element k,
+ *                   u its key and prev the key consumed before it (0 for k = 0): where u > prev the element adds
+ *                   (u - prev) d^2, d = (double)a[min(i, ca - 1)] - (double)b[min(j, cb - 1)], d = 0 where the two values are equal
+ *                   (inf - inf); wasserstein2 = sqrt of the sum: (int_0^1 (F^-1 - G^-1)^2)^(1/2). Particles of weight 0 have
+ *                   u == prev and add nothing.
+ *   out[g]          { ks, ks_location, wasserstein1, wasserstein2, energy, ca, cb, ks_position }: PP_IS_TWOSAMPLE_WIDTH doubles.
+ * One kernel template over the key (value or u) runs twice as a merge-path split: a workgroup of 256 threads owns
+ * PP_IS_TWOSAMPLE_TILE consecutive MERGED positions of one group; two lanes find the tile's two diagonals by binary search in global
+ * memory; the tile's A range and B range (2048 elements together, one before and one after each) are staged into LDS once as fp32
+ * value and fp64 u; every thread finds its 8-position diagonal by binary search in LDS, merges its eight elements serially and keeps
+ * fp64 sums and the lexicographic maximum of (|D|, -k); the workgroup reduces by wave shuffles, then LDS in wave order. A pair of
+ * groups that fits one tile (n_per_a + n_per_b <= PP_IS_TWOSAMPLE_TILE) is finished by that launch; otherwise every tile stores a
+ * record of 32 bytes in the workspace and a second launch, one workgroup per group, adds them in tile order. Dependent launches on the
+ * caller's stream, no global atomics, no workgroup waits for another. The order of every sum is a function of (ca, cb) alone: two
+ * calls give the same bits, and group g of an M-group call equals the one-group call on its slices, whatever n_per_a and n_per_b.
+ * Any n_per_a, n_per_b >= 1 and n_groups >= 0 (0: return 0 without a launch; more than 65535 groups are split over launches);
+ * nothing is written outside out and the workspace (pp_is_twosample_workspace_bytes; PP_ENOSPACE when shorter). PP_EINVAL without a
+ * launch for a NULL pointer, n_per_a < 1, n_per_b < 1, n_groups < 0, or M n_per_a, M n_per_b or n_per_a + n_per_b above 2^31 - 1;
+ * pp_is_twosample_workspace_bytes returns 0 outside that envelope. */
+#define PP_IS_TWOSAMPLE_TILE 2048
+#define PP_IS_TWOSAMPLE_WIDTH 8
+size_t pp_is_twosample_workspace_bytes(int32_t n_groups, int32_t n_per_a, int32_t n_per_b);
+int pp_is_twosample_groups(const float* value_a /*dev [M n_per_a]*/, const double* cdf_a /*dev [M n_per_a]*/,
+                           const int32_t* counted_a /*dev [M, 2]*/, int32_t n_per_a, const float* value_b /*dev [M n_per_b]*/,
+                           const double* cdf_b /*dev [M n_per_b]*/, const int32_t* counted_b /*dev [M, 2]*/, int32_t n_per_b,
+                           int32_t n_groups, double* out /*dev [M, 8]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pareto-smoothed importance weights and the k-hat diagnostic of a lock-step posterior call on the device (PSIS: Vehtari, Simpson,
  * Gelman, Yao, Gabry, JMLR 2024). The reference has no counterpart: the only reliability figure of its Empirical is
  * effective_sample_size (pyprob/distributions/empirical.py:758-766), which looks healthy exactly when the proposal misses a heavy tail.

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_kde, _host_order, _host_psis,
-                             _host_quantiles)
+                             _host_quantiles, _host_twosample, _kolmogorov_sf)
 
 
 _NO_STATEMENT_LOG = ('this Empirical has no statement log: only the result of a lock-step posterior call '
@@ -104,6 +104,14 @@ def _device_ecdf(groups, n_per, pts, strict):
     return ops.is_ecdf_groups(value, cdf, counted, n_per, torch.from_numpy(pts).to(value.device), bool(strict))[0].cpu().numpy()
 
 
+def _device_twosample(groups_a, n_per_a, groups_b, n_per_b):
+    """float64 numpy [M, PP_IS_TWOSAMPLE_WIDTH] of pp_is_twosample_groups over _sorted_groups' results of the two sides: one operator
+    call, one copy."""
+    from .ops import ops
+    (va, _, _, ca, wa), (vb, _, _, cb, wb) = groups_a, groups_b
+    return ops.is_twosample_groups(va, wa, ca, n_per_a, vb, wb, cb, n_per_b).cpu().numpy()
+
+
 def _device_psis(groups, n_per, stats, tail, want_weights):
     """(the smoothed log-weights on the device or None, float64 numpy [M, PP_IS_PSIS_WIDTH]) of pp_is_psis_groups over
     _lw_sorted_groups' result."""
@@ -114,10 +122,10 @@ def _device_psis(groups, n_per, stats, tail, want_weights):
 
 # What an Empirical computes once on the device and keeps in its __dict__ (_device_cdf, _device_extent, _device_sorted,
 # _device_lw_sorted, combine_duplicates' masses, resample_joint's cdf over all particles) or is handed by its batched call (model.py:
-# _batch, _batch_log; resample_batch: _batch_cdf). All of it describes the particles as they are: add() drops every name listed
+# _batch, _batch_log; resample_batch: _batch_cdf; compare_batch: _batch_sorted). All of it describes the particles as they are: add() drops every name listed
 # here, so a new cache is registered by adding its name.
 _DEVICE_CACHES = ('_dev_cdf', '_dev_extent', '_dev_sorted', '_dev_lw_sorted', '_fixed_mass', '_all_cdf', '_batch', '_batch_cdf',
-                  '_batch_log')
+                  '_batch_log', '_batch_sorted')
 
 
 class Empirical:
@@ -747,6 +755,38 @@ class Empirical:
         out = self._order_statistic('cdf', lambda s: _device_ecdf(s, self.length, xs[None], strict),
                                     lambda lw, v: _host_ecdf(lw, v, xs, strict))
         return float(out[0]) if scalar else out
+
+    # ---- two-sample distances (csrc/is_twosample.hip) -----------------------------------------------------------------------
+    def compare(self, other, address=None):
+        """How far this posterior is from `other`, as a TwoSample (ks, ks_location, ks_pvalue, wasserstein1, wasserstein2, energy,
+        count, ess): the distances between the two weighted samples of a scalar - the amortised posterior against a long
+        prior-proposal run, this checkpoint against the last, reobserve() against a fresh call, psis() against the raw weights.
+        address=: the distances between self.marginal(address) and other.marginal(address), resolved as marginal resolves it.
+        With the counted particles of each side (finite log-weight, value not NaN) in ascending order of value and F, G their
+        weighted empirical cdfs: ks = max |F - G| over the distinct values and ks_location the first value where it is attained;
+        wasserstein1 = int |F - G|; energy = 2 int (F - G)^2, the energy distance of two samples of a scalar; wasserstein2 =
+        (int_0^1 (F^-1 - G^-1)^2)^(1/2), the quantile coupling. The definition, rounding by rounding, is pp_is_twosample_groups'
+        header comment. Nothing counted on a side, or a total that is not positive and finite: NaN.
+
+        Two device-backed Empiricals on one device (the result of a lock-step posterior call, post.marginal(address), a device
+        resample, psis(), reobserve()) are each sorted once (as for quantile, kept with the object); a call is then ONE operator
+        call (pp_is_twosample_groups: a merge-path split of the two sorted samples) and one copy of 8 doubles. Every other pair -
+        either side host-backed, and all of them under PP_EMPIRICAL_DEVICE=0 - computes the same definition in float64 numpy."""
+        if not isinstance(other, Empirical):
+            raise TypeError('compare takes another Empirical, not %r' % type(other).__name__)
+        a, b = (self, other) if address is None else (self.marginal(address), other.marginal(address))
+        for e in (a, b):
+            e._check_finalized()
+            if e.length == 0:
+                raise ValueError('compare of an empty Empirical')
+        if a._device_backed() and b._device_backed() and a._log_weights.device == b._log_weights.device:
+            row = _device_twosample(a._device_sorted(), a.length, b._device_sorted(), b.length)[0]
+        else:
+            (lw_a, x_a), (lw_b, x_b) = a._host_scalars(), b._host_scalars()
+            if x_a is None or x_b is None:
+                raise ValueError('compare needs scalar values')
+            row = _host_twosample(lw_a, x_a, lw_b, x_b)
+        return _two_sample(row, a.effective_sample_size, b.effective_sample_size)
 
     # ---- Pareto-smoothed importance sampling (csrc/is_psis.hip) -----------------------------------------------------------
     def _device_lw_sorted(self):
@@ -1681,6 +1721,33 @@ def _kde_points(x, grid, ext, h, most, span=None):
     if not (abs(lo) <= _FLT_MAX and abs(hi) <= _FLT_MAX) or lo > hi:
         raise ValueError('range must be finite with lo <= hi, not %r' % (span,))
     return np.linspace(lo, hi, int(grid))
+
+
+class TwoSample:
+    """The distances between two weighted samples of a scalar (Empirical.compare), floats: ks (the Kolmogorov-Smirnov statistic
+    max |F - G|), ks_location (the first value where it is attained), ks_pvalue, wasserstein1, wasserstein2, energy (the energy
+    distance 2 int (F - G)^2), and the pairs count (the particles with a finite log-weight and a value that is not NaN on each side)
+    and ess (the effective sample sizes).
+
+    ks_pvalue is ASYMPTOTIC and ESS-BASED: the Kolmogorov series Q(lambda) = 2 sum_k (-1)^(k-1) exp(-2 k^2 lambda^2) at lambda = ks
+    sqrt(ess_a ess_b / (ess_a + ess_b)), the large-sample law of the statistic for two independent unweighted samples with the
+    effective sample sizes standing in for the sample sizes. It is a guide for weighted particles, not an exact test."""
+
+    def __init__(self, ks, ks_location, wasserstein1, wasserstein2, energy, count, ess):
+        self.ks, self.ks_location = float(ks), float(ks_location)
+        self.wasserstein1, self.wasserstein2, self.energy = float(wasserstein1), float(wasserstein2), float(energy)
+        self.count, self.ess = (int(count[0]), int(count[1])), (float(ess[0]), float(ess[1]))
+        pooled = self.ess[0] * self.ess[1] / (self.ess[0] + self.ess[1]) if self.ess[0] + self.ess[1] > 0 else float('nan')
+        self.ks_pvalue = _kolmogorov_sf(self.ks * math.sqrt(pooled)) if pooled == pooled and pooled >= 0 else float('nan')
+
+    def __repr__(self):
+        return 'TwoSample(ks:{:.6g} at {:.6g}, p:{:.3g}, wasserstein1:{:.6g}, wasserstein2:{:.6g}, energy:{:.6g}, count:{})'.format(
+            self.ks, self.ks_location, self.ks_pvalue, self.wasserstein1, self.wasserstein2, self.energy, self.count)
+
+
+def _two_sample(row, ess_a, ess_b):
+    """The TwoSample of a row of pp_is_twosample_groups' out and the effective sample sizes of the two sides."""
+    return TwoSample(row[0], row[1], row[2], row[3], row[4], (row[5], row[6]), (ess_a, ess_b))
 
 
 class PsisFit:

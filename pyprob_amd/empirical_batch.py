@@ -3,7 +3,7 @@ Model.posterior_results_batch execution in order, the same result bit for bit fr
 import numpy as np
 import torch
 
-from .empirical import (KernelDensity, _kde_bandwidth, _kde_points, _silverman, _KDE_MAX_POINTS,
+from .empirical import (KernelDensity, _kde_bandwidth, _kde_points, _silverman, _KDE_MAX_POINTS, _device_twosample, _two_sample,
                         _device_ecdf, _device_histograms, _device_hpd, _device_psis, _device_quantiles, _device_stats_row,
                         _gmm_arguments, _gmm_init_rows, _hpd_levels, _joint_fits_from_rows, _joint_gmm_init_rows, _joint_rows,
                         _joint_start_means, _lw_sorted_groups, _mixtures_from_rows, _moment_rows, _philox_key, _psis_tail, _quantile_levels, _resample_op, _scheme_id, _sorted_groups)
@@ -158,6 +158,39 @@ def kde_batch(posteriors, x=None, bandwidth=None, grid=512, address=None):
     out = ops.is_kde_groups(lw, column, N, torch.from_numpy(pts).to(lw.device), torch.tensor(h, dtype=torch.float64, device=lw.device),
                             group_stats).cpu().numpy()
     return [KernelDensity(pts[g], out[0, g], out[1, g], h[g], int(ext[g, 2]), t.effective_sample_size) for g, t in enumerate(targets)]
+
+
+def _kept_sorted_groups(posteriors, address):
+    """(_sorted_groups' result over all M groups, N) where the posteriors are the M groups of one execution (as quantile_batch
+    recognises them), sorted once per column and kept with the call's first group; else None."""
+    found = _batch_column(posteriors, address)
+    if found is None:
+        return None
+    kept = posteriors[0].__dict__.setdefault('_batch_sorted', {})
+    key = None if address is None else posteriors[0]._latent(address)[0]
+    if key not in kept:
+        kept[key] = _sorted_groups(*found)
+    return kept[key], found[2]
+
+
+def compare_batch(posteriors_a, posteriors_b, address=None):
+    """[a.compare(b, address) for a, b in zip(posteriors_a, posteriors_b)] as a list of M TwoSample - and, where each side is the M
+    groups of ONE Model.posterior_results_batch (or reobserve_batch) execution in order (recognised as quantile_batch recognises
+    them; the two sides may have different num_traces), the same results bit for bit from the sort and the cumulative weights of
+    each side (one pp_is_sort_groups and one pp_is_cdf_groups call per side and column, kept with the call's first group), ONE
+    pp_is_twosample_groups call over all pairs and one copy of the [M, 8] rows. Anything else is served by the loop."""
+    posteriors_a, posteriors_b = list(posteriors_a), list(posteriors_b)
+    if len(posteriors_a) != len(posteriors_b):
+        raise ValueError('compare_batch pairs the posteriors: %d against %d' % (len(posteriors_a), len(posteriors_b)))
+    if not posteriors_a:
+        return []
+    side_a = _kept_sorted_groups(posteriors_a, address)
+    side_b = _kept_sorted_groups(posteriors_b, address) if side_a is not None else None
+    if side_b is None or side_a[0][0].device != side_b[0][0].device:
+        return [a.compare(b, address) for a, b in zip(posteriors_a, posteriors_b)]
+    rows = _device_twosample(*side_a, *side_b)
+    return [_two_sample(rows[g], _target(a, address).effective_sample_size, _target(b, address).effective_sample_size)
+            for g, (a, b) in enumerate(zip(posteriors_a, posteriors_b))]
 
 
 def _psis_batch_call(posteriors, tail, want_weights):

@@ -76,6 +76,63 @@ def _host_ecdf(lw, x, xs, strict):
     return np.where(np.isnan(xs), np.nan, out)
 
 
+def _host_twosample(lw_a, x_a, lw_b, x_b):
+    """pp_is_twosample_groups' definition (include/pyprob_amd.h) in float64 numpy for one pair of particle sets: its row of 8 - ks,
+    ks_location, wasserstein1, wasserstein2, energy, the two counts, the merged position of the ks maximum."""
+    ca, cb = len(_host_order(lw_a, x_a)), len(_host_order(lw_b, x_b))
+    a, wa = _host_sorted_cdf(lw_a, x_a)
+    b, wb = _host_sorted_cdf(lw_b, x_b)
+    row = np.array([np.nan, np.nan, np.nan, np.nan, np.nan, float(ca), float(cb), np.nan])
+    if a is None or b is None:
+        return row
+    ua, ub = wa / wa[-1], wb / wb[-1]
+    from_a = np.arange(ca + cb) < ca                    # (of the concatenation: a stable sort takes A before B on ties)
+
+    def merged(keys_a, keys_b):
+        """(the keys in merged order, how many of each side are consumed AFTER every merged element, whether it came from A)."""
+        keys = np.concatenate([keys_a, keys_b])
+        order = np.argsort(keys, kind='stable')
+        i = np.cumsum(from_a[order])
+        return keys[order], i, np.arange(1, ca + cb + 1) - i, from_a[order]
+    with np.errstate(invalid='ignore', over='ignore'):
+        # the value walk: F - G after every merged element, steps where the next value is larger
+        z, i, j, _ = merged(a, b)
+        D = np.where(i > 0, ua[np.maximum(i, 1) - 1], 0.0) - np.where(j > 0, ub[np.maximum(j, 1) - 1], 0.0)
+        step = np.append(z[1:] > z[:-1], False)
+        end = step.copy()
+        end[-1] = True
+        k = int(np.argmax(np.where(end, np.abs(D), -1.0)))          # (the first maximum)
+        term = step & (D != 0)
+        gap = np.append(z[1:], z[-1])[term] - z[term]
+        # the quantile walk: both quantile functions between two merged u, the heads BEFORE every element
+        u, i, j, was_a = merged(ua, ub)
+        prev = np.concatenate([[0.0], u[:-1]])
+        x, y = a[np.minimum(i - was_a, ca - 1)], b[np.minimum(j - ~was_a, cb - 1)]
+        d = np.where(x == y, 0.0, x - y)
+        wide = u > prev
+        row[:5] = (abs(D[k]), z[k], np.sum(np.abs(D[term]) * gap), math.sqrt(np.sum((u - prev)[wide] * d[wide] ** 2)),
+                   2.0 * np.sum(D[term] ** 2 * gap))
+    row[7] = k
+    return row
+
+
+def _kolmogorov_sf(lam):
+    """P(K > lam) of the Kolmogorov distribution: the series 2 sum_k (-1)^(k-1) exp(-2 k^2 lam^2), below lam = 1.18 its theta-function
+    form 1 - sqrt(2 pi) / lam sum_k exp(-(2 k - 1)^2 pi^2 / (8 lam^2)), which converges where the first does not."""
+    lam = float(lam)
+    if math.isnan(lam):
+        return float('nan')
+    if lam <= 0:
+        return 1.0
+    if lam < 1.18:
+        y = math.exp(-math.pi ** 2 / (8.0 * lam * lam))
+        p = 1.0 - math.sqrt(2.0 * math.pi) / lam * (y + y ** 9 + y ** 25 + y ** 49)
+    else:
+        x = math.exp(-2.0 * lam * lam)
+        p = 2.0 * (x - x ** 4 + x ** 9)
+    return min(max(p, 0.0), 1.0)
+
+
 def _host_extent(lw, x):
     """pp_is_extent_groups' row in numpy: min, max over the values with a finite log-weight that are not NaN, the two counts."""
     fin = np.isfinite(lw)

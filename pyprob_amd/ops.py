@@ -39,6 +39,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_gmm_joint_groups weighted full-covariance Gaussian-mixture EM of several latents per group (density_estimate_joint)   -
     is_kde_groups       weighted Gaussian kernel density of a latent at points per group (the reference has none)   -
     is_kde2d_groups     the same for two latents on a rectangular grid, on the fp32 matrix pipe (the reference has none)   -
+    is_twosample_groups KS, Wasserstein-1/2 and energy distance between two sorted groups, by merge path (the reference has none)   -
     reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -114,6 +115,8 @@ _lib.define('is_gmm_joint_groups(Tensor lw, Tensor[] cols, int n_components, int
 _lib.define('is_kde_groups(Tensor lw, Tensor x, int n_per, Tensor points, Tensor bandwidth, Tensor? stats) -> Tensor')
 _lib.define('is_kde2d_groups(Tensor lw, Tensor x, Tensor y, int n_per, Tensor points_x, Tensor points_y, Tensor bandwidth_x, '
             'Tensor bandwidth_y, Tensor? stats) -> Tensor')
+_lib.define('is_twosample_groups(Tensor value_a, Tensor cdf_a, Tensor counted_a, int n_per_a, Tensor value_b, Tensor cdf_b, '
+            'Tensor counted_b, int n_per_b) -> Tensor')
 _lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
             'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -1022,6 +1025,27 @@ def _is_ecdf_groups_hip(value_sorted, cdf_sorted, counted, n_per, x, strict):
     return out, rank
 
 
+def _is_twosample_groups_hip(value_a, cdf_a, counted_a, n_per_a, value_b, cdf_b, counted_b, n_per_b):
+    """[M, PP_IS_TWOSAMPLE_WIDTH] (float64): ks, ks_location, wasserstein1, wasserstein2, energy, the two counts and the merged
+    position of the ks maximum between group g of side a and group g of side b, each the sorted particles of M groups with a n_per of
+    its own (pp_is_twosample_groups); cdf_* = is_cdf_groups over the sorted log-weights."""
+    lib = L.load()
+    _same_device(value_a, cdf_a, counted_a, value_b, cdf_b, counted_b)
+    M = _sorted_ok(value_a, cdf_a, counted_a, n_per_a, 'is_twosample_groups')
+    if _sorted_ok(value_b, cdf_b, counted_b, n_per_b, 'is_twosample_groups') != M:
+        raise RuntimeError('pyprob_hip::is_twosample_groups: the two sides hold %d and %d groups' % (
+            M, value_b.numel() // int(n_per_b)))
+    dev = value_a.device
+    out = torch.empty((M, L.PP_IS_TWOSAMPLE_WIDTH), dtype=torch.float64, device=dev)
+    ws, need = _workspace(lib.pp_is_twosample_workspace_bytes, dev, M, int(n_per_a), int(n_per_b))
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_twosample_groups(value_a.data_ptr(), cdf_a.data_ptr(), counted_a.data_ptr(), int(n_per_a), value_b.data_ptr(),
+                                        cdf_b.data_ptr(), counted_b.data_ptr(), int(n_per_b), M, out.data_ptr(), ws.data_ptr(), need,
+                                        _stream(value_a))
+    L.check(rc, 'pp_is_twosample_groups')
+    return out
+
+
 def _kde_rows(t, M, most, name, what):
     """(row length, stride) of a float64 tensor of points: [Q] shared by the groups (stride 0) or [M, Q], one row per group."""
     if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != M) or \
@@ -1224,6 +1248,7 @@ _lib.impl('is_quantile_groups', _is_quantile_groups_hip, 'CUDA')
 _lib.impl('is_unique_groups', _is_unique_groups_hip, 'CUDA')
 _lib.impl('is_hpd_groups', _is_hpd_groups_hip, 'CUDA')
 _lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
+_lib.impl('is_twosample_groups', _is_twosample_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
