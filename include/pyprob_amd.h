@@ -964,6 +964,44 @@ int pp_is_twosample_groups(const float* value_a /*dev [M n_per_a]*/, const doubl
                            const double* cdf_b /*dev [M n_per_b]*/, const int32_t* counted_b /*dev [M, 2]*/, int32_t n_per_b,
                            int32_t n_groups, double* out /*dev [M, 8]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Pair sums between the JOINT particles of two lock-step posteriors on the device: what the Gaussian-kernel MMD^2 and the
+ * multivariate energy distance of two weighted samples of J latents are made of (Empirical.compare_joint). The reference has no
+ * distance between two Empiricals. INPUTS per side, in the [M n_per] layout with a n_per of its own: the log-weights, a HOST array
+ * of n_cols device column pointers (as pp_is_moments_groups takes them) and the [M, 6] statistics or NULL (only the maximum, entry
+ * 0 of a row, is read; NULL: found here, the same bits). Per group, device doubles: center [M, J], inv_scale [M, J] and the
+ * bandwidth h [M] (bandwidth_stride 1) or one number shared by the groups (0), in standardised units.
+ *   z_j = fp32(((double)x_j - center[g, j]) inv_scale[g, j]). A particle COUNTS where its log-weight is finite, its group has a finite
+ *   maximum and every z_j is finite with |z_j| sqrt(log2 e) / h < 2^30 (a NaN coordinate drops the particle; beyond the last limit
+ *   fp32 exponents would overflow). It weighs exp(lw - max) in fp64; w and v below are those weights over their sum on side a and b.
+ *   out[g] = { k_aa, k_bb, k_ab, d_aa, d_bb, d_ab, sum w^2, sum v^2, count_a, count_b }: PP_IS_PAIRS_WIDTH doubles, with
+ *     k_ab = sum_ij w_i v_j exp(-|z_i - z'_j|^2 / (2 h^2)),  d_ab = sum_ij w_i v_j |z_i - z'_j|  (Euclidean), aa and bb likewise
+ *     within a side, the diagonal included. A side without a counted particle: its count is 0, its sum of squares and the
+ *     sums it enters are NaN.
+ * Launches, dependent on the caller's stream: per side (the tile maxima where stats is NULL and a group has more than 2048
+ * particles, then) one operand pass - per particle the image (alpha z, q, 1), alpha = sqrt(log2 e) / h, q = log2(e) (lw - max) -
+ * alpha^2 |z|^2 / 2, whose inner product with another particle's (alpha z', 1, q') is log2 of w_i v_j k - then the Gaussian sums on
+ * v_mfma_f32_32x32x2_f32 (four waves own 128 rows of one of the products aa, bb, ab and sweep one of at most 16 strips of column
+ * chunks of 256 staged through LDS; 16 v_exp_f32 per lane and 32 x 32 block; fp32 sums of at most 128 terms, flushed to fp64), the
+ * distance sums on the VALU over the same tiling (a thread owns a row, the column comes in scalar registers; the distance is taken
+ * from the difference), and one workgroup per group that adds the stored partial sums in a fixed order. aa and bb visit what lies on
+ * or above the diagonal and count what lies above it twice. No atomics, no workgroup waits for another; the order of every sum is a
+ * function of (n_per_a, n_per_b, n_cols) alone: two calls give the same bits, and group g of an M-group call equals the one-group
+ * call on its slices. The derived error bound is at the head of csrc/is_pairs.hip.
+ * Any n_per_a, n_per_b >= 1, n_cols in 1 .. PP_IS_PAIRS_MAX_COLS and n_groups >= 0 (0: return 0 without a launch; more than 21845
+ * groups are split over launches); nothing is written outside out and the workspace (pp_is_pairs_workspace_bytes: about 76 bytes
+ * per particle at n_cols = 8; PP_ENOSPACE when shorter). PP_EINVAL without a launch for a NULL pointer (stats_a and stats_b may be
+ * NULL), n_cols outside 1 .. 8, n_per_a < 1, n_per_b < 1, n_groups < 0, M n_per_a or M n_per_b above 2^31 - 1 or a
+ * bandwidth_stride other than 0 or 1; pp_is_pairs_workspace_bytes returns 0 outside that envelope. */
+#define PP_IS_PAIRS_MAX_COLS 8
+#define PP_IS_PAIRS_WIDTH 10
+size_t pp_is_pairs_workspace_bytes(int32_t n_groups, int32_t n_per_a, int32_t n_per_b, int32_t n_cols);
+int pp_is_pairs_groups(const float* lw_a /*dev [M n_per_a]*/, const float* const* cols_a /*host array of J dev pointers*/,
+                       const double* stats_a /*dev [M, 6] or NULL*/, int32_t n_per_a, const float* lw_b /*dev [M n_per_b]*/,
+                       const float* const* cols_b /*host array of J dev pointers*/, const double* stats_b /*dev [M, 6] or NULL*/,
+                       int32_t n_per_b, int32_t n_cols, int32_t n_groups, const double* center /*dev [M, J]*/,
+                       const double* inv_scale /*dev [M, J]*/, const double* bandwidth /*dev [M] or [1]*/, int64_t bandwidth_stride,
+                       double* out /*dev [M, 10]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pareto-smoothed importance weights and the k-hat diagnostic of a lock-step posterior call on the device (PSIS: Vehtari, Simpson,
  * Gelman, Yao, Gabry, JMLR 2024). The reference has no counterpart: the only reliability figure of its Empirical is
  * effective_sample_size (pyprob/distributions/empirical.py:758-766), which looks healthy exactly when the proposal misses a heavy tail.

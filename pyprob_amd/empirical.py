@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_kde, _host_order, _host_psis,
-                             _host_quantiles, _host_twosample, _kolmogorov_sf)
+                             _host_quantiles, _host_twosample, _host_twosample_joint, _kolmogorov_sf, _pairs_bandwidth,
+                             _pairs_standardise)
 
 
 _NO_STATEMENT_LOG = ('this Empirical has no statement log: only the result of a lock-step posterior call '
@@ -110,6 +111,17 @@ def _device_twosample(groups_a, n_per_a, groups_b, n_per_b):
     from .ops import ops
     (va, _, _, ca, wa), (vb, _, _, cb, wb) = groups_a, groups_b
     return ops.is_twosample_groups(va, wa, ca, n_per_a, vb, wb, cb, n_per_b).cpu().numpy()
+
+
+def _device_pairs(side_a, side_b, center, scale, bandwidth):
+    """float64 numpy [M, PP_IS_PAIRS_WIDTH] of pp_is_pairs_groups between two sides (lw, cols, n_per, stats) under center / scale
+    [M, J] and bandwidth [M] or [1] (numpy): one operator call, one copy."""
+    from .ops import ops
+    dev = side_a[0].device
+    as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)      # noqa: E731
+    (lw_a, cols_a, n_a, stats_a), (lw_b, cols_b, n_b, stats_b) = side_a, side_b
+    return ops.is_pairs_groups(lw_a, list(cols_a), int(n_a), stats_a, lw_b, list(cols_b), int(n_b), stats_b, as_dev(center),
+                               as_dev(1.0 / scale), as_dev(bandwidth)).cpu().numpy()
 
 
 def _device_psis(groups, n_per, stats, tail, want_weights):
@@ -380,7 +392,7 @@ class Empirical:
         return self._value(int(self._draw_indices(1, min_index, max_index)[0]))
 
     # ---- the other latents of a lock-step call (csrc/is_moments.hip) ------------------------------------------------
-    def _latent_table(self):
+    def _latent_table(self, host_ok=False):
         """{address: (values [n] of ALL particles of the call, rows that executed it or None)} in the order the statement log
         first meets each address - the statement log of a lock-step posterior call. Every other Empirical has none.
 
@@ -393,7 +405,7 @@ class Empirical:
             raise AttributeError(_NO_STATEMENT_LOG)
         if self.__dict__.get('_log_stale'):
             raise AttributeError(_STALE_STATEMENT_LOG)
-        if os.environ.get('PP_EMPIRICAL_DEVICE', '1') == '0':
+        if os.environ.get('PP_EMPIRICAL_DEVICE', '1') == '0' and not host_ok:      # (compare_joint reads the columns on its host route)
             raise ValueError('PP_EMPIRICAL_DEVICE=0 keeps every Empirical on the host route: the statement log is not served '
                              '(addresses / marginal / joint / resample_joint need the device route)')
         table = self.__dict__.get('_latents')
@@ -436,8 +448,8 @@ class Empirical:
         """The addresses of the statement log in statement order."""
         return list(self._latent_table())
 
-    def _latent(self, address):
-        table = self._latent_table()
+    def _latent(self, address, host_ok=False):
+        table = self._latent_table(host_ok)
         if address not in table:
             address = self.__dict__.get('statement_names', {}).get(address, address)
         if address not in table:       # the address= of a sample statement: the one full address it begins ('a' -> 'a__Normal__1')
@@ -489,14 +501,14 @@ class Empirical:
         out.add_metadata(op='marginal', address=address, length=self.length, length_after=out.length)
         return out
 
-    def _joint_columns(self, addresses):
-        table = self._latent_table()
+    def _joint_columns(self, addresses, host_ok=False):
+        table = self._latent_table(host_ok)
         if addresses is None:
             chosen = [a for a, (_, rows) in table.items() if rows is None]
         else:
             chosen = []
             for a in addresses:
-                a, _, rows = self._latent(a)
+                a, _, rows = self._latent(a, host_ok)
                 if rows is not None:
                     raise ValueError('address {!r} was executed by {} of the particles only (a branch): joint() takes addresses '
                                      'that every particle executed - see marginal()'.format(a, int(rows.numel())))
@@ -787,6 +799,76 @@ class Empirical:
                 raise ValueError('compare needs scalar values')
             row = _host_twosample(lw_a, x_a, lw_b, x_b)
         return _two_sample(row, a.effective_sample_size, b.effective_sample_size)
+
+    # ---- two-sample distances of the joint particles (csrc/is_pairs.hip) ----------------------------------------------------
+    def _pair_columns(self, addresses):
+        """(names, log-weights of ALL particles, the J columns, the statistics row or None) of the joint particles compare_joint
+        takes: the statement log's columns as joint() resolves them or - an Empirical without a statement log whose values are
+        J-vectors - the components of the values (addresses: None or component indices)."""
+        if self.__dict__.get('statement_log') is not None or self.__dict__.get('_log_stale'):
+            names, cols = self._joint_columns(addresses, host_ok=True)
+            return names, self._all_lw(), cols, self._group_stats_row()
+        v = self.__dict__.get('_values')
+        try:
+            x = v.detach().cpu().double().numpy() if torch.is_tensor(v) else np.asarray([np.asarray(t, np.float64) for t in v])
+        except (TypeError, ValueError, RuntimeError):
+            x = None
+        if x is None or x.ndim != 2 or x.shape[0] == 0:
+            raise AttributeError(_NO_STATEMENT_LOG)
+        names = list(range(x.shape[1])) if addresses is None else [int(a) for a in addresses]
+        if any(not 0 <= a < x.shape[1] for a in names):
+            raise KeyError('the values of this Empirical have components 0 .. %d' % (x.shape[1] - 1))
+        return names, np.asarray(self._lw, np.float64), [x[:, a] for a in names], None
+
+    def compare_joint(self, other, addresses=None, bandwidth=None, scale=None, num_samples=None, seed=None):
+        """How far the JOINT posterior of several latents is from `other`'s, as a TwoSampleJoint: the Gaussian-kernel MMD^2 (mmd2, the
+        V-statistic k_aa + k_bb - 2 k_ab; mmd2_unbiased without the diagonals; mmd) and the multivariate energy distance (energy =
+        2 d_ab - d_aa - d_bb) of the two weighted particle sets - what compare() cannot see: two posteriors that agree in every
+        marginal and differ jointly. addresses: as joint() takes them, resolved on BOTH objects (None: every address of this
+        posterior that all particles executed); 1 .. 8 of them. A particle counts where its log-weight is finite and none of its
+        requested coordinates is NaN or infinite (kde2d's rule). Coordinates are standardised, z = (x - center) / scale, with center
+        the mean and scale the per-address standard deviation of the equal mixture of the two sides (one joint() each); scale=: J
+        positive numbers instead (needed where an address has no spread: ValueError). bandwidth: h of the kernel exp(-|z - z'|^2 /
+        (2 h^2)) in standardised units, default sqrt(J). num_samples: first draw that many joint particles from each side
+        (resample_joint, scheme='systematic', keyed by seed), weights uniform afterwards; None: all particles.
+
+        Two sides whose columns are float32 tensors on one device take ONE pp_is_pairs_groups call (the Gaussian sums on the fp32
+        matrix pipe, the distances on the VALU; derived error bound in DESIGN.md) and one copy of 10 doubles. Every other pair, and
+        all of them under PP_EMPIRICAL_DEVICE=0, takes the same definitions in chunked float64 numpy
+        (empirical_host._host_twosample_joint; num_samples is not served there)."""
+        if not isinstance(other, Empirical):
+            raise TypeError('compare_joint takes another Empirical, not %r' % type(other).__name__)
+        for e in (self, other):
+            e._check_finalized()
+        names, lw_a, cols_a, stats_a = self._pair_columns(addresses)
+        _, lw_b, cols_b, stats_b = other._pair_columns(names if addresses is None else addresses)
+        J = len(names)
+        if not 1 <= J <= 8:
+            raise ValueError('compare_joint takes 1 .. 8 addresses, not %d' % J)
+        h = _pairs_bandwidth(bandwidth, J)
+        tensors = [lw_a, lw_b] + list(cols_a) + list(cols_b)
+        device = os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0' and all(
+            torch.is_tensor(t) and t.is_cuda and t.device == lw_a.device and t.dtype == torch.float32 and t.dim() == 1 and
+            t.is_contiguous() for t in tensors)
+        if not device:
+            if num_samples is not None:
+                raise ValueError('num_samples needs two posteriors whose columns are on one device')
+            to_np = lambda t: t.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(t) else np.asarray(t, np.float64)  # noqa: E731
+            row, center, s, h = _host_twosample_joint(to_np(lw_a), np.stack([to_np(c) for c in cols_a], 1), to_np(lw_b),
+                                                      np.stack([to_np(c) for c in cols_b], 1), h, scale)
+            return _two_sample_joint(row, names, h, s, center)
+        if num_samples is not None:
+            key = _philox_key(seed)
+            drawn_a = self.resample_joint(num_samples, names, seed=key, scheme='systematic')
+            drawn_b = other.resample_joint(num_samples, names if addresses is None else addresses, seed=key, offset=1,
+                                           scheme='systematic')
+            cols_a, cols_b = [drawn_a[a] for a in names], [c for a, c in drawn_b.items() if a != 'index']
+            lw_a, lw_b, stats_a, stats_b = torch.zeros_like(cols_a[0]), torch.zeros_like(cols_b[0]), None, None
+        sides = (lw_a, cols_a, lw_a.numel(), stats_a), (lw_b, cols_b, lw_b.numel(), stats_b)
+        ja, jb = (_joint_rows(names, _moment_rows(*side)) for side in sides)
+        center, s = _pairs_standardise(ja[0].mean, ja[0].stddev ** 2, jb[0].mean, jb[0].stddev ** 2, scale)
+        row = _device_pairs(sides[0], sides[1], center[None], s[None], np.array([h]))[0]
+        return _two_sample_joint(row, names, h, s, center)
 
     # ---- Pareto-smoothed importance sampling (csrc/is_psis.hip) -----------------------------------------------------------
     def _device_lw_sorted(self):
@@ -1748,6 +1830,36 @@ class TwoSample:
 def _two_sample(row, ess_a, ess_b):
     """The TwoSample of a row of pp_is_twosample_groups' out and the effective sample sizes of the two sides."""
     return TwoSample(row[0], row[1], row[2], row[3], row[4], (row[5], row[6]), (ess_a, ess_b))
+
+
+class TwoSampleJoint:
+    """The distances between two weighted samples of J latents (Empirical.compare_joint), floats: k_aa, k_bb, k_ab (the weighted means
+    of the Gaussian kernel within and between the sides, diagonals included), mmd2 = k_aa + k_bb - 2 k_ab (the V-statistic),
+    mmd2_unbiased (the diagonals removed: (k_aa - sum w^2) / (1 - sum w^2) and likewise for b, minus 2 k_ab; NaN for a side of one
+    particle), mmd = sqrt(max(mmd2, 0)), d_aa, d_bb, d_ab (the weighted mean Euclidean distances), energy = 2 d_ab - d_aa - d_bb; and
+    bandwidth, scale [J], center [J] (the standardisation: z = (x - center) / scale), addresses, count (the particles that count on
+    each side) and ess (1 / sum w^2 of each side). The combinations are host float64 arithmetic on the six sums."""
+
+    def __init__(self, sums, sum_w2, count, addresses, bandwidth, scale, center):
+        self.k_aa, self.k_bb, self.k_ab, self.d_aa, self.d_bb, self.d_ab = (float(v) for v in sums)
+        self.mmd2 = self.k_aa + self.k_bb - 2.0 * self.k_ab
+        off = [(k - q) / (1.0 - q) if q < 1.0 else float('nan') for k, q in zip((self.k_aa, self.k_bb), map(float, sum_w2))]
+        self.mmd2_unbiased = off[0] + off[1] - 2.0 * self.k_ab
+        self.mmd = math.sqrt(max(self.mmd2, 0.0)) if self.mmd2 == self.mmd2 else float('nan')
+        self.energy = 2.0 * self.d_ab - self.d_aa - self.d_bb
+        self.addresses, self.bandwidth = list(addresses), float(bandwidth)
+        self.scale, self.center = np.array(scale, np.float64), np.array(center, np.float64)
+        self.count = (int(count[0]), int(count[1]))
+        self.ess = tuple(1.0 / float(q) if q > 0 else 0.0 for q in sum_w2)
+
+    def __repr__(self):
+        return 'TwoSampleJoint(addresses:{}, mmd2:{:.6g}, mmd2_unbiased:{:.6g}, energy:{:.6g}, bandwidth:{:.4g}, count:{})'.format(
+            self.addresses, self.mmd2, self.mmd2_unbiased, self.energy, self.bandwidth, self.count)
+
+
+def _two_sample_joint(row, addresses, bandwidth, scale, center):
+    """The TwoSampleJoint of a row of pp_is_pairs_groups' out and the standardisation it was computed under."""
+    return TwoSampleJoint(row[:6], row[6:8], row[8:10], addresses, bandwidth, scale, center)
 
 
 class PsisFit:

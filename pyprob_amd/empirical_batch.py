@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from .empirical import (KernelDensity, _kde_bandwidth, _kde_points, _silverman, _KDE_MAX_POINTS, _device_twosample, _two_sample,
+                        _device_pairs, _pairs_bandwidth, _pairs_standardise, _two_sample_joint,
                         _device_ecdf, _device_histograms, _device_hpd, _device_psis, _device_quantiles, _device_stats_row,
                         _gmm_arguments, _gmm_init_rows, _hpd_levels, _joint_fits_from_rows, _joint_gmm_init_rows, _joint_rows,
                         _joint_start_means, _lw_sorted_groups, _mixtures_from_rows, _moment_rows, _philox_key, _psis_tail, _quantile_levels, _resample_op, _scheme_id, _sorted_groups)
@@ -191,6 +192,46 @@ def compare_batch(posteriors_a, posteriors_b, address=None):
     rows = _device_twosample(*side_a, *side_b)
     return [_two_sample(rows[g], _target(a, address).effective_sample_size, _target(b, address).effective_sample_size)
             for g, (a, b) in enumerate(zip(posteriors_a, posteriors_b))]
+
+
+def _batch_joint_columns(posteriors, addresses):
+    """(names, lw, the J whole columns, N, group statistics) where the posteriors are the M groups of one execution in order and
+    every requested address is a whole [M N] column of the call's statement log (as joint_batch recognises them); else None."""
+    found = _batch_column(posteriors, None)
+    if found is None:
+        return None
+    lw, _, N, group_stats = found
+    names, _ = posteriors[0]._joint_columns(addresses)
+    whole = _log_columns(posteriors[0]._batch_log)
+    cols = [whole.get(a) for a in names]
+    if any(c is None or c.dtype != torch.float32 or c.numel() != lw.numel() or not c.is_contiguous() for c in cols):
+        return None      # (reobserve_batch: the members share the [N] columns of ONE posterior)
+    return names, lw, cols, N, group_stats
+
+
+def compare_joint_batch(posteriors_a, posteriors_b, addresses=None, bandwidth=None, scale=None):
+    """[a.compare_joint(b, addresses, bandwidth, scale) for a, b in zip(posteriors_a, posteriors_b)] as a list of M TwoSampleJoint -
+    and, where each side is the M groups of ONE Model.posterior_results_batch execution in order (recognised as joint_batch
+    recognises them; the two sides may have different num_traces), the same results bit for bit from one pp_is_moments_groups launch
+    sequence per side, ONE pp_is_pairs_groups call over all pairs and one copy of the [M, 10] rows. Anything else is served by the
+    loop."""
+    posteriors_a, posteriors_b = list(posteriors_a), list(posteriors_b)
+    if len(posteriors_a) != len(posteriors_b):
+        raise ValueError('compare_joint_batch pairs the posteriors: %d against %d' % (len(posteriors_a), len(posteriors_b)))
+    if not posteriors_a:
+        return []
+    side_a = _batch_joint_columns(posteriors_a, addresses)
+    side_b = _batch_joint_columns(posteriors_b, side_a[0] if addresses is None else addresses) if side_a is not None else None
+    if side_b is None or side_a[1].device != side_b[1].device or not 1 <= len(side_a[0]) <= 8:
+        return [a.compare_joint(b, addresses, bandwidth, scale) for a, b in zip(posteriors_a, posteriors_b)]
+    names = side_a[0]
+    h = _pairs_bandwidth(bandwidth, len(names))
+    ja, jb = (_joint_rows(names, _moment_rows(lw, cols, N, stats)) for _, lw, cols, N, stats in (side_a, side_b))
+    stack = lambda js, f: np.stack([f(j) for j in js])      # noqa: E731
+    center, s = _pairs_standardise(stack(ja, lambda j: j.mean), stack(ja, lambda j: j.stddev ** 2), stack(jb, lambda j: j.mean),
+                                   stack(jb, lambda j: j.stddev ** 2), scale)
+    rows = _device_pairs(side_a[1:], side_b[1:], center, s, np.array([h]))
+    return [_two_sample_joint(rows[g], names, h, s[g], center[g]) for g in range(len(posteriors_a))]
 
 
 def _psis_batch_call(posteriors, tail, want_weights):

@@ -116,6 +116,79 @@ def _host_twosample(lw_a, x_a, lw_b, x_b):
     return row
 
 
+def _pairs_standardise(mean_a, var_a, mean_b, var_b, scale):
+    """(center, scale) [.., J] of compare_joint from the means and variances of the two sides: the mean and the standard deviation of
+    their equal mixture, or the caller's J positive numbers in place of the latter."""
+    mean_a, mean_b = np.asarray(mean_a, np.float64), np.asarray(mean_b, np.float64)
+    center = 0.5 * (mean_a + mean_b)
+    if scale is None:
+        s = np.sqrt(0.5 * (np.asarray(var_a, np.float64) + np.asarray(var_b, np.float64)) + 0.25 * (mean_a - mean_b) ** 2)
+    else:
+        s = np.asarray(scale, np.float64).reshape(-1)
+        if s.shape[0] != center.shape[-1] or not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError('scale= takes %d finite positive numbers, one per address' % center.shape[-1])
+        s = np.array(np.broadcast_to(s, center.shape))
+    if not np.isfinite(center).all() or not np.isfinite(s).all():
+        raise ValueError('the joint moments of a side are not finite (no particle with a weight, or a NaN or infinite coordinate '
+                         'under a finite weight): nothing to standardise by')
+    if (s == 0).any():
+        raise ValueError('an address has no spread on either side: pass scale= (J positive numbers)')
+    return center, s
+
+
+def _pairs_bandwidth(bandwidth, J):
+    h = math.sqrt(J) if bandwidth is None else float(bandwidth)
+    if not (math.isfinite(h) and h > 0):
+        raise ValueError('bandwidth must be a finite positive number (standardised units)')
+    return h
+
+
+def _host_twosample_joint(lw_a, x_a, lw_b, x_b, bandwidth=None, scale=None, chunk=1024):
+    """pp_is_pairs_groups' row of 10 (include/pyprob_amd.h) for one pair of particle sets in chunked float64 numpy, with the
+    standardisation of compare_joint in front: (row, center, scale, bandwidth). x_*: [n, J]; a particle counts where its log-weight is
+    finite and its J coordinates are. The moments are joint()'s: over the particles with a finite log-weight."""
+    sides = []
+    for lw, x in ((lw_a, x_a), (lw_b, x_b)):
+        lw, x = np.asarray(lw, np.float64).reshape(-1), np.asarray(x, np.float64)
+        x = x.reshape(len(lw), -1)
+        fin = np.isfinite(lw)
+        w = np.where(fin, np.exp(lw - (lw[fin].max() if fin.any() else 0.0)), 0.0)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            mean = (w[fin, None] * x[fin]).sum(0) / w.sum()
+            var = np.maximum((w[fin, None] * (x[fin] - mean) ** 2).sum(0) / w.sum(), 0.0)
+        sides.append((w, x, mean, var))
+    J = sides[0][1].shape[1]
+    if sides[1][1].shape[1] != J or not 1 <= J <= 8:
+        raise ValueError('compare_joint takes 1 .. 8 addresses, the same on both sides')
+    h = _pairs_bandwidth(bandwidth, J)
+    center, s = _pairs_standardise(sides[0][2], sides[0][3], sides[1][2], sides[1][3], scale)
+    parts = []
+    for (w, x, _, _), lw in zip(sides, (lw_a, lw_b)):
+        with np.errstate(invalid='ignore'):
+            z = (x - center) * (1.0 / s)
+        keep = np.isfinite(z).all(1) & np.isfinite(np.asarray(lw, np.float64).reshape(-1))
+        parts.append((z[keep], w[keep]))
+    row = np.full(10, np.nan)
+    row[8], row[9] = len(parts[0][1]), len(parts[1][1])
+
+    def sums(p, q):
+        (zp, wp), (zq, wq) = p, q
+        k = d = 0.0
+        for i in range(0, len(wp), chunk):
+            diff = zp[i:i + chunk, None, :] - zq[None, :, :]
+            r2 = (diff * diff).sum(-1)
+            ww = wp[i:i + chunk, None] * wq[None, :]
+            k += (ww * np.exp(r2 * (-0.5 / (h * h)))).sum()
+            d += (ww * np.sqrt(r2)).sum()
+        with np.errstate(invalid='ignore', divide='ignore'):
+            norm = wp.sum() * wq.sum()
+            return np.float64(k) / norm, np.float64(d) / norm
+    (row[0], row[3]), (row[1], row[4]), (row[2], row[5]) = sums(parts[0], parts[0]), sums(parts[1], parts[1]), sums(parts[0], parts[1])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        row[6], row[7] = [np.float64((w * w).sum()) / np.float64(w.sum()) ** 2 for _, w in parts]
+    return row, center, s, h
+
+
 def _kolmogorov_sf(lam):
     """P(K > lam) of the Kolmogorov distribution: the series 2 sum_k (-1)^(k-1) exp(-2 k^2 lam^2), below lam = 1.18 its theta-function
     form 1 - sqrt(2 pi) / lam sum_k exp(-(2 k - 1)^2 pi^2 / (8 lam^2)), which converges where the first does not."""

@@ -41,6 +41,8 @@ PP_IS_KDE_MAX_POINTS = 4096  # points per group of one pp_is_kde_groups call (in
 PP_IS_KDE2D_MAX_SIDE = 256   # points per grid side of one pp_is_kde2d_groups call (include/pyprob_amd.h)
 PP_IS_TWOSAMPLE_TILE = 2048  # merged positions one workgroup of pp_is_twosample_groups walks (include/pyprob_amd.h)
 PP_IS_TWOSAMPLE_WIDTH = 8    # doubles per group of pp_is_twosample_groups' out (include/pyprob_amd.h)
+PP_IS_PAIRS_MAX_COLS = 8     # columns of one pp_is_pairs_groups call (include/pyprob_amd.h)
+PP_IS_PAIRS_WIDTH = 10       # doubles per group of pp_is_pairs_groups' out (include/pyprob_amd.h)
 
 
 def PP_IS_MOMENTS_WIDTH(n_cols):
@@ -258,6 +260,8 @@ PROTOTYPES = {
     'pp_is_kde2d_groups': (C.c_int, [vp, vp, vp, i32, i32, vp, i32, i64, vp, i32, i64, vp, i64, vp, i64, vp, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_twosample_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
     'pp_is_twosample_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, C.c_size_t, vp]),
+    'pp_is_pairs_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
+    'pp_is_pairs_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_copy_rows': (C.c_int, [vp, i32, vp, vp, i32, vp]),

@@ -40,6 +40,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_kde_groups       weighted Gaussian kernel density of a latent at points per group (the reference has none)   -
     is_kde2d_groups     the same for two latents on a rectangular grid, on the fp32 matrix pipe (the reference has none)   -
     is_twosample_groups KS, Wasserstein-1/2 and energy distance between two sorted groups, by merge path (the reference has none)   -
+    is_pairs_groups     Gaussian-kernel and Euclidean-distance pair sums between two groups of joint particles (the reference has none)   -
     reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -117,6 +118,8 @@ _lib.define('is_kde2d_groups(Tensor lw, Tensor x, Tensor y, int n_per, Tensor po
             'Tensor bandwidth_y, Tensor? stats) -> Tensor')
 _lib.define('is_twosample_groups(Tensor value_a, Tensor cdf_a, Tensor counted_a, int n_per_a, Tensor value_b, Tensor cdf_b, '
             'Tensor counted_b, int n_per_b) -> Tensor')
+_lib.define('is_pairs_groups(Tensor lw_a, Tensor[] cols_a, int n_per_a, Tensor? stats_a, Tensor lw_b, Tensor[] cols_b, int n_per_b, '
+            'Tensor? stats_b, Tensor center, Tensor inv_scale, Tensor bandwidth) -> Tensor')
 _lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
             'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -1046,6 +1049,42 @@ def _is_twosample_groups_hip(value_a, cdf_a, counted_a, n_per_a, value_b, cdf_b,
     return out
 
 
+def _is_pairs_groups_hip(lw_a, cols_a, n_per_a, stats_a, lw_b, cols_b, n_per_b, stats_b, center, inv_scale, bandwidth):
+    """[M, PP_IS_PAIRS_WIDTH] (float64): k_aa, k_bb, k_ab, d_aa, d_bb, d_ab, sum w^2, sum v^2 and the two counts between group g of side
+    a and group g of side b, each M groups of joint particles (J columns) with a n_per of its own (pp_is_pairs_groups). center and
+    inv_scale: float64 [M, J]; bandwidth: float64 [M] or [1] (shared); stats_*: as for is_cdf_groups."""
+    lib = L.load()
+    cols_a, cols_b = list(cols_a), list(cols_b)
+    _same_device(lw_a, stats_a, lw_b, stats_b, center, inv_scale, bandwidth, *cols_a, *cols_b)
+    M = _groups_of(_f32(lw_a, 'lw_a'), n_per_a, 'is_pairs_groups')
+    J = len(cols_a)
+    if _groups_of(_f32(lw_b, 'lw_b'), n_per_b, 'is_pairs_groups') != M or len(cols_b) != J:
+        raise RuntimeError('pyprob_hip::is_pairs_groups: the two sides hold the same number of groups and of columns')
+    if not 1 <= J <= L.PP_IS_PAIRS_MAX_COLS:
+        raise RuntimeError('pyprob_hip::is_pairs_groups: 1 .. %d columns per call' % L.PP_IS_PAIRS_MAX_COLS)
+    for lw, cols, stats in ((lw_a, cols_a, stats_a), (lw_b, cols_b, stats_b)):
+        for c in cols:
+            _particles_like(c, lw, 'every column', 'is_pairs_groups')
+        _group_stats_ok(stats, M, 'is_pairs_groups')
+    for t, shape, name in ((center, (M, J), 'center'), (inv_scale, (M, J), 'inv_scale')):
+        if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError('pyprob_hip::is_pairs_groups: %s must be a contiguous float64 tensor of [M, J]' % name)
+    if bandwidth.dtype != torch.float64 or not bandwidth.is_contiguous() or bandwidth.dim() != 1 or bandwidth.numel() not in (1, M):
+        raise RuntimeError('pyprob_hip::is_pairs_groups: bandwidth must be a contiguous float64 tensor of [1] or [M]')
+    dev = lw_a.device
+    out = torch.empty((M, L.PP_IS_PAIRS_WIDTH), dtype=torch.float64, device=dev)
+    ws, need = _workspace(lib.pp_is_pairs_workspace_bytes, dev, M, int(n_per_a), int(n_per_b), J)
+    pa = (C.c_void_p * J)(*[c.data_ptr() for c in cols_a])
+    pb = (C.c_void_p * J)(*[c.data_ptr() for c in cols_b])
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_pairs_groups(lw_a.data_ptr(), C.cast(pa, C.c_void_p), L.ptr(stats_a), int(n_per_a), lw_b.data_ptr(),
+                                    C.cast(pb, C.c_void_p), L.ptr(stats_b), int(n_per_b), J, M, center.data_ptr(), inv_scale.data_ptr(),
+                                    bandwidth.data_ptr(), 1 if (bandwidth.numel() == M and M > 1) else 0, out.data_ptr(),
+                                    ws.data_ptr(), need, _stream(lw_a))
+    L.check(rc, 'pp_is_pairs_groups')
+    return out
+
+
 def _kde_rows(t, M, most, name, what):
     """(row length, stride) of a float64 tensor of points: [Q] shared by the groups (stride 0) or [M, Q], one row per group."""
     if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != M) or \
@@ -1249,6 +1288,7 @@ _lib.impl('is_unique_groups', _is_unique_groups_hip, 'CUDA')
 _lib.impl('is_hpd_groups', _is_hpd_groups_hip, 'CUDA')
 _lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
 _lib.impl('is_twosample_groups', _is_twosample_groups_hip, 'CUDA')
+_lib.impl('is_pairs_groups', _is_pairs_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
