@@ -1133,6 +1133,40 @@ int pp_is_gmm_joint_groups(const float* lw /*dev [M n_per]*/, const float* const
                            double reg_covar, int32_t check_every, double* out /*dev double [M, PP_IS_GMM_JOINT_WIDTH(J, K)]*/,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Draws from, and the density of, a fitted joint mixture q_g = sum_k pi_k N(mu_k, Sigma_k) over J latents per group: the proposal of
+ * the next importance-sampling call (adaptive IS). The reference has no counterpart.
+ *   pp_is_proposal_groups  fit_rows: device doubles, row g at fit_rows + g ld_fit; its leading K (1 + J + J (J + 1) / 2) doubles are those
+ *                       of a pp_is_gmm_joint_groups output row - weights | means | upper triangles - so such rows are fed as they
+ *                       are (ld_fit = PP_IS_GMM_JOINT_WIDTH(J, K)). The weights need not sum to 1: they are normalised here.
+ *                       cols: a HOST array of n_cols = J device pointers, each a column [M n_per] of float32.
+ *                         mode 0 (draw)   particle i of group g: Philox4x32-10 with key = seed, counter = offset + g n_per + i (the
+ *                                         contract of the batched posterior calls) and stream id PP_IS_PROPOSAL_STREAM; its first
+ *                                         word picks component k - the first whose cumulative weight exceeds the uniform -, the next
+ *                                         2 ceil(J / 2) give J standard normals z (Box-Muller, both branches);
+ *                                         x = mu_k + L_k z in fp64 (L_k the lower Cholesky factor), ROUNDED to float32 into cols;
+ *                                         neg_log_q[g n_per + i] = -log q_g(x) AT THE FLOAT32 VALUE.
+ *                         mode 1 (score)  cols are read; neg_log_q as above. Scoring the columns a draw wrote returns its bits.
+ *                       log q_g(x) = logsumexp_k (log pi_k - J/2 log 2 pi - sum_j log L_k,jj - 1/2 |L_k^-1 (x - mu_k)|^2) in fp64 - the
+ *                       difference x - mu_k is formed first, so a narrow component far from the origin keeps its digits - and is
+ *                       rounded once to float32. status[g] = 0, or 1 + the first component whose weight is not positive and
+ *                       finite or whose covariance has a Cholesky pivot that is not positive (a NaN included): every output of that
+ *                       group is NaN, the other groups are not touched, and the call still returns 0.
+ *                       Two dependent launches on the caller's stream: one workgroup per group factorises the K covariances and
+ *                       writes a packed block (per component mu, L^-1, the constant, L; the cumulative weights) to the workspace;
+ *                       a workgroup of 256 threads per tile of 2048 particles stages the block in LDS and holds eight particles
+ *                       per thread in registers. No atomics, no workgroup waits for another. A particle's outputs are a function of
+ *                       (seed, offset + g n_per + i, fit_rows[g]) alone: not of M, and not of how a call is split.
+ * n_groups = 0 or n_per = 0: return 0 without a launch (status is not written). PP_EINVAL without a launch - pp_last_error names
+ * the operator - for n_cols outside 1 .. PP_IS_GMM_JOINT_MAX_J, n_components outside 1 .. PP_IS_GMM_MAX_K, a NULL pointer (fit_rows,
+ * cols, one of its n_cols entries, neg_log_q, status, workspace), mode outside {0, 1}, n_groups < 0, n_per < 0, ld_fit below the
+ * length of a row, a workspace shorter than pp_is_proposal_workspace_bytes (which returns 0 outside the envelope). */
+#define PP_IS_PROPOSAL_STREAM 0x20000u   /* taken elsewhere: statement indices j, 0x1C, 0x52, 0x53, 0x4000 + i, 0x10000 + j, the top bit */
+size_t pp_is_proposal_workspace_bytes(int32_t n_groups, int32_t n_cols, int32_t n_components);
+int pp_is_proposal_groups(const double* fit_rows /*dev [M, ld_fit]*/, int64_t ld_fit, int32_t n_groups, int32_t n_cols,
+                          int32_t n_components, int64_t n_per, int32_t mode, uint64_t seed, uint64_t offset,
+                          float* const* cols /*host [n_cols] of dev [M n_per]*/, float* neg_log_q /*dev [M n_per]*/,
+                          int32_t* status /*dev [M]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Weighted Gaussian kernel density of one latent, or of a pair of latents on a rectangular grid, per group of an [M, n_per] block of
  * a lock-step posterior call. The reference has no counterpart: the shape of a posterior is plot_histogram there
  * (pyprob/distributions/empirical.py:889-914) or the 1000-sample density_estimate (:795-807).

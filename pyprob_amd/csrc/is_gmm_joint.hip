@@ -28,6 +28,7 @@
 // of a wave meet by lane exchanges in a fixed pattern (wave_sum_dpp), the four waves in LDS as ((0 + 1) + 2) + 3, the tiles in index
 // order, the components in the order of k. The order is a function of (n_per, J, K) alone: group g of an M-group call carries the bits
 // of the one-group call on the same particles, whatever the other groups do and whatever check_every is.
+#include "gmm_factor.hpp"
 #include "is_groups.hpp"
 
 #include <float.h>
@@ -40,21 +41,12 @@ constexpr int PER_THREAD = 8;
 static_assert(TILE == 256 * PER_THREAD, "a tile is 256 threads of eight particles");
 constexpr int MAXK = PP_IS_GMM_MAX_K;
 constexpr int MAXJ = PP_IS_GMM_JOINT_MAX_J;
-constexpr double LOG_2PI = 1.8378770664093454835606594728112;
 
-__host__ __device__ constexpr int tri_of(int J) { return J * (J + 1) / 2; }
-// Parameters of one component: pi | mu [J] | Sigma, upper triangle row-major. The sums of one component have the same shape.
-__host__ __device__ constexpr int params_of(int J) { return 1 + J + tri_of(J); }
-// Constants of one component: mu [J] | L^-1, lower triangle row-major | c
-__host__ __device__ constexpr int consts_of(int J) { return J + tri_of(J) + 1; }
 // A partial row: component k's sums R | S [J] | Q [tri] at k params_of(J) | sum w L, W, count, the group's maximum
 __host__ __device__ constexpr int slots_of(int J, int K) { return K * params_of(J) + 4; }
 // A row of `out`: pi [K] | mu [K, J] | Sigma [K, tri] | lower bound, n_iter, converged, degenerate, W, count, the group's maximum
 __host__ __device__ constexpr int width_of(int J, int K) { return PP_IS_GMM_JOINT_WIDTH(J, K); }
 constexpr int MAXTRI = tri_of(MAXJ), MAXP = params_of(MAXJ);
-// (j, m), j <= m, of an upper triangle stored row by row; (j, m), m <= j, of a lower triangle stored row by row
-__host__ __device__ constexpr int upper_at(int J, int j, int m) { return j * J - j * (j - 1) / 2 + (m - j); }
-__host__ __device__ constexpr int lower_at(int j, int m) { return j * (j + 1) / 2 + m; }
 
 struct JointCols {
     const float* p[MAXJ];
@@ -78,37 +70,6 @@ void joint_carve(int M, int n_per, int J, int K, void* p, JointWorkspace& w) {
     w.cons = c.take<double>(groups * K * consts_of(J) * 8);
     w.all_done = c.take<int>(4);
     w.bytes = c.bytes();
-}
-
-// Thread k of a workgroup: the Cholesky factor of the J x J matrix whose upper triangle is `cov` into lf, the factor's inverse into
-// li (both lower triangles, row by row, in LDS: the indices are run-time values) and sum_j log L_jj. False where a pivot is not
-// positive (a NaN included): lf and li are then incomplete.
-__device__ bool factorise(const double* cov, int J, double* lf, double* li, double* logdet) {
-    double ld = 0.0;
-    for (int j = 0; j < J; ++j) {
-        for (int m = 0; m <= j; ++m) {
-            double s = cov[upper_at(J, m, j)];
-            for (int q = 0; q < m; ++q) s -= lf[lower_at(j, q)] * lf[lower_at(m, q)];
-            if (m < j) {
-                lf[lower_at(j, m)] = s / lf[lower_at(m, m)];
-            } else {
-                if (!(s > 0.0)) return false;
-                lf[lower_at(j, j)] = sqrt(s);
-                ld += log(lf[lower_at(j, j)]);
-            }
-        }
-    }
-    for (int j = 0; j < J; ++j) {
-        const double inv = 1.0 / lf[lower_at(j, j)];
-        li[lower_at(j, j)] = inv;
-        for (int m = 0; m < j; ++m) {
-            double s = 0.0;
-            for (int q = m; q < j; ++q) s += lf[lower_at(j, q)] * li[lower_at(q, m)];
-            li[lower_at(j, m)] = -s * inv;
-        }
-    }
-    *logdet = ld;
-    return true;
 }
 
 // The constants of a group from its parameters `par` (pi | mu | Sigma, any address space), the inverse factors and log-determinants:
@@ -139,22 +100,6 @@ __global__ __launch_bounds__(64) void joint_init_kernel(const double* __restrict
     for (int s = tid; s < off; s += 64) state[s] = par[s];
     if (tid < 7) state[off + tid] = (tid == 0 || tid == 6) ? (double)-INFINITY : (tid == 3 && degenerate) ? 1.0 : 0.0;
     if (!degenerate) publish_constants(par, li, ld, J, K, 64, cons + g * K * consts_of(J));
-}
-
-// l_ik = c_k - 1/2 |L_k^-1 (x - mu_k)|^2 with the constants of component k at ck (LDS); d <- x - mu_k.
-template <int J>
-__device__ __forceinline__ double log_density(const float (&x)[J], const double* ck, double (&d)[J]) {
-#pragma unroll
-    for (int j = 0; j < J; ++j) d[j] = (double)x[j] - ck[j];
-    double q = 0.0;
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        double z = ck[J + lower_at(j, 0)] * d[0];
-#pragma unroll
-        for (int m = 1; m <= j; ++m) z += ck[J + lower_at(j, m)] * d[m];
-        q += z * z;
-    }
-    return ck[J + tri_of(J)] - 0.5 * q;
 }
 
 // Step 1 of an iteration: workgroup (tile blockIdx.x, group g0 + blockIdx.y) stores its partial row.

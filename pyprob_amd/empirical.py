@@ -2024,6 +2024,44 @@ class JointMixtureFit:
         z = rng.standard_normal((int(n), self.means.shape[1]))
         return self.means[k] + np.einsum('nij,nj->ni', np.linalg.cholesky(self.covariances)[k], z)
 
+    def fit_row(self, device):
+        """The parameters as pp_is_proposal_groups reads them: float64 [1, K (1 + J + J (J + 1) / 2)] on `device`, weights | means |
+        upper triangles row by row - the leading part of the pp_is_gmm_joint_groups row this fit was read from."""
+        iu, ku = np.triu_indices(self.means.shape[1])
+        row = np.concatenate([np.ravel(self.weights), np.ravel(self.means), np.ravel(self.covariances[:, iu, ku])])
+        return torch.from_numpy(np.ascontiguousarray(row, np.float64)[None]).to(device)
+
+    def _check_status(self, status):
+        k = int(status)
+        if k:
+            raise ValueError('JointMixtureFit: component {} is no density (a weight that is not positive and finite, or a covariance '
+                             'that is not positive definite)'.format(k - 1))
+
+    def sample_device(self, n, seed=None, offset=0, device=None):
+        """(x [n, J] float32, log_q [n] float32) on the device: n draws from the fitted mixture and the log-density AT the float32
+        values, one pp_is_proposal_groups call (csrc/is_proposal.hip). Draw i is a function of (seed, offset + i, the fit) alone;
+        seed=None keys from torch's generator as resample does."""
+        from .ops import ops
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        K, J = self.means.shape
+        cols, neg, status = ops.is_proposal_groups(self.fit_row(dev), J, K, int(n), [], _philox_key(seed), int(offset))
+        if int(n) > 0:
+            self._check_status(status[0])
+        return torch.stack(list(cols), 1), neg.neg_()
+
+    def log_prob_device(self, x):
+        """log q of x [n, J] (a float32 device tensor) as float32 [n] on the device: the score mode of pp_is_proposal_groups -
+        evaluated in fp64 and rounded once, the bits sample_device returns for its own draws."""
+        from .ops import ops
+        K, J = self.means.shape
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != J or x.dtype != torch.float32:
+            raise ValueError('x must be a float32 tensor [n, %d] of the coordinates %s' % (J, self.addresses))
+        cols = list(x.t().contiguous().unbind(0))
+        _, neg, status = ops.is_proposal_groups(self.fit_row(x.device), J, K, int(x.shape[0]), cols, 0, 0)
+        if x.shape[0] > 0:
+            self._check_status(status[0])
+        return neg.neg_()
+
     def marginal(self, address):
         """The fitted density of ONE coordinate as a Mixture of Normals: `address` is one of `addresses`, or the address= its
         statement was given where that begins one of them only."""

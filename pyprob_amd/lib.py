@@ -254,6 +254,8 @@ PROTOTYPES = {
     'pp_is_gmm_groups': (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, C.c_size_t, vp]),
     'pp_is_gmm_joint_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
     'pp_is_gmm_joint_groups': (C.c_int, [vp, vp, i32, i32, i32, i32, vp, vp, i32, C.c_double, C.c_double, i32, vp, vp, C.c_size_t, vp]),
+    'pp_is_proposal_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
+    'pp_is_proposal_groups': (C.c_int, [vp, i64, i32, i32, i32, i64, i32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_kde_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
     'pp_is_kde_groups': (C.c_int, [vp, vp, i32, i32, vp, i32, i64, vp, i64, vp, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_kde2d_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),

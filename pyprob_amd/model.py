@@ -159,13 +159,22 @@ class Model:
         from its prior (pp_dist_draw, counter = offset + particle: a particle's values do not depend on how the call is
         split), every observe / factor a device log-weight term; control flow diverges into paths as in
         _traces_lockstep_on_device. The weight of a particle is its likelihood."""
+        runner = self._prior_is_runner_on(device)
+        return self._run_prior_lockstep(state.PriorISState(runner, num_traces, seed, offset), runner, num_traces, observe, offset,
+                                        likelihood_importance, args, kwargs)
+
+    def _prior_is_runner_on(self, device):
+        """The network-free runner of the prior-proposal engine on `device` (None: the current GPU, else the CPU), kept per model."""
         from .is_engine import DistRunner
         dev = torch.device(device) if device is not None else (
             torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu'))
         runner = self.__dict__.get('_prior_is_runner')
         if runner is None or runner.dev != dev:
             runner = self._prior_is_runner = DistRunner(dev)
-        ls = state.PriorISState(runner, num_traces, seed, offset)
+        return runner
+
+    def _run_prior_lockstep(self, ls, runner, num_traces, observe, offset, likelihood_importance, args, kwargs):
+        """forward() over every control-flow path of the lock-step state `ls` (a PriorISState); the call's Empirical."""
         state._init_traces(func=self.forward, trace_mode=TraceMode.POSTERIOR, inference_engine=InferenceEngine.IMPORTANCE_SAMPLING,
                            observe=observe, likelihood_importance=likelihood_importance, lock_step=ls)
         runner.begin(num_traces, offset=offset)
@@ -198,7 +207,27 @@ class Model:
             state._lock_step = None
             state._current_trace = None
             ls.memo = None
+        if hasattr(ls, 'finish'):
+            ls.finish()
         return self._lockstep_empirical(runner, ls, values, runner.stats(ls.lw, values), num_traces, n_paths)
+
+    def posterior_results_from_proposal(self, num_traces, proposal, observe=None, seed=None, offset=0, *args, device=None, **kwargs):
+        """Importance sampling with the latents of `proposal` - the JointMixtureFit of an earlier posterior's density_estimate_joint -
+        drawn from the fit instead of their priors (adaptive importance sampling: run, fit, run again from the fit). All particles
+        in lock step (state.ProposalISState): the [num_traces, J] block and - log q are ONE pp_is_proposal_groups call (Philox key =
+        seed, counter = offset + particle; seed=None keys from torch's generator), a statement at a fitted address takes its
+        column and adds its prior's log-density, every other statement draws from its prior, observes and factors add their
+        likelihood. Straight-line programs in the fitted addresses. The device-backed Empirical carries the statement log like any
+        lock-step result. On the CPU device and under PP_EMPIRICAL_DEVICE=0 the block comes from proposal.sample / log_prob."""
+        from .empirical import _philox_key
+        runner = self._prior_is_runner_on(device)
+        ls = state.ProposalISState(runner, int(num_traces), _philox_key(seed), int(offset), proposal)
+        post = self._run_prior_lockstep(ls, runner, int(num_traces), observe, int(offset), 1., args, kwargs)
+        post.rename('Posterior, IS from a fitted proposal, traces: {:,}, ESS: {:,.2f}'.format(post.length, post.effective_sample_size))
+        post.add_metadata(op='proposal_is', num_traces=int(num_traces), addresses=list(proposal.addresses),
+                          num_mixture_components=len(proposal.weights), effective_sample_size=post.effective_sample_size)
+        post._origin = (self, args, kwargs, dict(observe or {}), 1., InferenceEngine.IMPORTANCE_SAMPLING)
+        return post
 
     @staticmethod
     def _lockstep_empirical(runner, ls, values, stats, num_traces, n_paths):

@@ -37,6 +37,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_psis_groups      Pareto-smoothed importance weights and k-hat per group (the reference has none)   pyprob/distributions/empirical.py:758-766
     is_gmm_groups       weighted Gaussian-mixture EM of a latent per group (density_estimate)     pyprob/distributions/empirical.py:795-807
     is_gmm_joint_groups weighted full-covariance Gaussian-mixture EM of several latents per group (density_estimate_joint)   -
+    is_proposal_groups  draws from a fitted joint mixture and its log-density per group (sample_device, proposal IS)   -
     is_kde_groups       weighted Gaussian kernel density of a latent at points per group (the reference has none)   -
     is_kde2d_groups     the same for two latents on a rectangular grid, on the fp32 matrix pipe (the reference has none)   -
     is_twosample_groups KS, Wasserstein-1/2 and energy distance between two sorted groups, by merge path (the reference has none)   -
@@ -113,6 +114,8 @@ _lib.define('is_gmm_groups(Tensor lw, Tensor x, int n_components, int n_per, Ten
             'float tol, float reg_covar) -> Tensor')
 _lib.define('is_gmm_joint_groups(Tensor lw, Tensor[] cols, int n_components, int n_per, Tensor? stats, Tensor params_init, '
             'int max_iter, float tol, float reg_covar) -> Tensor')
+_lib.define('is_proposal_groups(Tensor fit_rows, int n_cols, int n_components, int n_per, Tensor[] cols, int seed, int offset) -> '
+            '(Tensor[], Tensor, Tensor)')
 _lib.define('is_kde_groups(Tensor lw, Tensor x, int n_per, Tensor points, Tensor bandwidth, Tensor? stats) -> Tensor')
 _lib.define('is_kde2d_groups(Tensor lw, Tensor x, Tensor y, int n_per, Tensor points_x, Tensor points_y, Tensor bandwidth_x, '
             'Tensor bandwidth_y, Tensor? stats) -> Tensor')
@@ -1258,6 +1261,43 @@ def _is_gmm_joint_groups_hip(lw, cols, n_components, n_per, stats, params_init, 
     return out
 
 
+def _is_proposal_groups_hip(fit_rows, n_cols, n_components, n_per, cols, seed, offset):
+    """(cols: J float32 columns [M n_per], neg_log_q float32 [M n_per], status int32 [M]) of the M fitted joint mixtures in fit_rows
+    (float64 [M, ld >= K (1 + J + J (J + 1) / 2)]: weights | means | upper triangles - rows of is_gmm_joint_groups as they are)
+    (pp_is_proposal_groups). cols empty: DRAW n_per particles per group (Philox key `seed`, counter offset + g n_per + i) into the
+    rows of one new [J, M n_per] block; else SCORE the caller's J columns (the first result is then empty). neg_log_q is -log q at the float32 values; status[g] != 0:
+    1 + the first component of group g that is no density (its outputs are NaN)."""
+    lib = L.load()
+    cols = list(cols)
+    _same_device(fit_rows, *cols)
+    J, K, n_per = int(n_cols), int(n_components), int(n_per)
+    if not 1 <= J <= L.PP_IS_GMM_JOINT_MAX_J or not 1 <= K <= L.PP_IS_GMM_MAX_K:
+        raise RuntimeError('pyprob_hip::is_proposal_groups: 1 .. %d columns and 1 .. %d mixture components'
+                           % (L.PP_IS_GMM_JOINT_MAX_J, L.PP_IS_GMM_MAX_K))
+    if fit_rows.dtype != torch.float64 or fit_rows.dim() != 2 or not fit_rows.is_contiguous() or \
+            fit_rows.shape[1] < K * (1 + J + J * (J + 1) // 2) or n_per < 0:
+        raise RuntimeError('pyprob_hip::is_proposal_groups: fit_rows must be a contiguous float64 tensor of '
+                           '[M, >= K (1 + J + J (J + 1) / 2)] and n_per >= 0')
+    M, dev = int(fit_rows.shape[0]), fit_rows.device
+    mode = 1 if cols else 0
+    if mode == 0:
+        cols = list(torch.empty((J, M * n_per), dtype=torch.float32, device=dev).unbind(0))
+    elif len(cols) != J or any(_f32(c, 'every column').dim() != 1 or c.numel() != M * n_per for c in cols):
+        raise RuntimeError('pyprob_hip::is_proposal_groups: n_cols contiguous float32 columns of M * n_per elements')
+    neg_log_q = torch.empty(M * n_per, dtype=torch.float32, device=dev)
+    status = torch.zeros(M, dtype=torch.int32, device=dev)
+    ws, need = _workspace(lib.pp_is_proposal_workspace_bytes, dev, M, J, K)
+    if M * n_per == 0:      # (nothing to launch: an empty tensor has no address to pass)
+        return (cols if mode == 0 else []), neg_log_q, status
+    ptrs = (C.c_void_p * J)(*[c.data_ptr() for c in cols])
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_proposal_groups(fit_rows.data_ptr(), int(fit_rows.shape[1]), M, J, K, n_per, mode, int(seed), int(offset),
+                                       C.cast(ptrs, C.c_void_p), neg_log_q.data_ptr(), status.data_ptr(), ws.data_ptr(), need,
+                                       _stream(fit_rows))
+    L.check(rc, 'pp_is_proposal_groups')
+    return (cols if mode == 0 else []), neg_log_q, status      # (a score hands none of its inputs back)
+
+
 _lib.impl('ic_loss', _ic_loss_hip, 'CUDA')
 _lib.impl('adam_step', _adam_step_hip, 'CUDA')
 _lib.impl('sgd_step', _sgd_step_hip, 'CUDA')
@@ -1292,6 +1332,7 @@ _lib.impl('is_pairs_groups', _is_pairs_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
+_lib.impl('is_proposal_groups', _is_proposal_groups_hip, 'CUDA')
 _lib.impl('is_kde_groups', _is_kde_groups_hip, 'CUDA')
 _lib.impl('is_kde2d_groups', _is_kde2d_groups_hip, 'CUDA')
 _lib.impl('dist_logweight', _dist_logweight_hip, 'CUDA')

@@ -597,6 +597,72 @@ class PriorISState(LockStepState):
         return None
 
 
+class ProposalISState(PriorISState):
+    """Lock-step importance sampling with the latents of a JointMixtureFit proposed from the fit (Model.posterior_results_from_proposal):
+    the [n, J] block is drawn ONCE, before the program runs - pp_is_proposal_groups, Philox key = seed, counter = offset + particle -
+    and the log-weight starts as -log q(x). A sample statement at one of fit.addresses is handed its column, recorded in the
+    statement log like a draw, and adds + log prior(x) - a value outside the prior's support drops the particle; every other
+    statement is PriorISState's draw from the prior. Straight-line use only: a fitted address under a row list (inside a branch) or
+    reached twice is refused. On the CPU device and under PP_EMPIRICAL_DEVICE=0 the block is fit.sample's and the density
+    fit.log_prob's at the float32 values (numpy: another stream of the same distribution)."""
+
+    def __init__(self, runner, n, seed, offset, fit):
+        super().__init__(runner, n, seed, offset)
+        import os
+        K, J = fit.means.shape
+        if len(fit.addresses) != J or len(set(fit.addresses)) != J:
+            raise ValueError('the proposal needs one distinct address per coordinate')
+        if runner.dev.type == 'cuda' and os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0':
+            from .ops import ops
+            cols, neg_log_q, status = ops.is_proposal_groups(fit.fit_row(runner.dev), J, K, int(n), [], int(seed), int(offset))
+            if int(n) > 0:
+                fit._check_status(status[0])
+            self._lw = neg_log_q
+        else:
+            import numpy as np
+            for k, (w, cov) in enumerate(zip(fit.weights, fit.covariances)):
+                try:
+                    ok = np.isfinite(w) and w > 0 and np.linalg.cholesky(cov) is not None
+                except np.linalg.LinAlgError:
+                    ok = False
+                if not ok:
+                    fit._check_status(k + 1)
+            x = fit.sample(int(n), seed=[int(seed), int(offset)]).astype(np.float32)
+            cols = list(torch.from_numpy(np.ascontiguousarray(x.T)).to(runner.dev).unbind(0))
+            self._lw = torch.from_numpy(-fit.log_prob(x.astype(np.float64))).to(runner.dev, torch.float32)
+        self._lw_valid = True
+        self.fit_columns = dict(zip(fit.addresses, cols))
+        self.fit_reached = set()
+
+    def prior_statement(self, address, distribution):
+        col = self.fit_columns.get(address)
+        if col is None or self.statement < self.replay_statements:
+            return super().prior_statement(address, distribution)
+        if self.rows is not None or self.active is not None:
+            raise NotImplementedError('proposal IS: the fitted address {!r} is reached inside a branch; straight-line programs '
+                                      'only'.format(address))
+        if address in self.fit_reached:
+            raise NotImplementedError('proposal IS: the fitted address {!r} is reached twice'.format(address))
+        term = self.runner.dist_term(distribution)
+        if term is None or (type(term).__name__ == 'DistTerm' and term.kind == 2):
+            raise NotImplementedError('proposal IS: no device log-density for the {} prior at {!r}'.format(distribution.name, address))
+        j = self.statement
+        self.statement += 1
+        while len(self.log) <= j:
+            self.log.append({})
+        self.log[j][address] = (col, None)
+        self.runner.accumulate(self.lw, term, col, 1.0)      # + log prior(x); - log q(x) is where the log-weight started
+        self.fit_reached.add(address)
+        w = self.wrappers[id(col)] = (col, ParticleTensor.wrap(col))
+        return w[1]
+
+    def finish(self):
+        missing = [a for a in self.fit_columns if a not in self.fit_reached]
+        if missing:
+            raise RuntimeError('proposal IS: the program never reached the fitted address(es) {}: its weights would miss their '
+                               'prior terms'.format(missing))
+
+
 class ReobservedVariable:
     """What a likelihood function of Empirical.reobserve is handed for an observe statement (the reference hands it the trace's
     Variable): the program's distribution object with its per-particle parameters and the value of the original call."""
