@@ -1002,6 +1002,62 @@ int pp_is_pairs_groups(const float* lw_a /*dev [M n_per_a]*/, const float* const
                        const double* inv_scale /*dev [M, J]*/, const double* bandwidth /*dev [M] or [1]*/, int64_t bandwidth_stride,
                        double* out /*dev [M, 10]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The product-Gaussian kernel density of the JOINT particles of a lock-step posterior at query points, and the mean-shift map that
+ * climbs it to the joint modes (Empirical.kde_joint, Empirical.modes). The reference has neither. INPUTS as pp_is_pairs_groups takes
+ * one side: the log-weights [M n_per], a HOST array of n_cols device column pointers, the [M, 6] statistics or NULL, center [M, J],
+ * inv_scale [M, J] and the bandwidth h [M] (bandwidth_stride 1) or one shared number (0), in standardised units. The particles are
+ * standardised and COUNTED by pp_is_pairs_groups' rule, z_j = fp32(((double)x_j - center[g, j]) inv_scale[g, j]); w below are their
+ * weights exp(lw - max) over their sum.
+ *   pp_is_kde_joint_groups  points [M, Q, J] (device doubles) in the ORIGINAL coordinates, standardised exactly as the particles are.
+ *       log_density[g, q] = log sum_i w_i N_J(z_q; z_i, h_g^2 I)   (the density of z: the caller adds sum_j log inv_scale for x)
+ *       mean[g, q, :]     = sum_i w_i k_qi z_i / sum_i w_i k_qi, k_qi = exp(-|z_q - z_i|^2 / (2 h^2)), in STANDARDISED coordinates;
+ *                           NULL: not computed (and the second matrix product is not issued)
+ *       count[g]          = the counted particles (NULL: not written)
+ *     A query far from every particle keeps a finite log-density and a defined mean (a running maximum over the exponents) as long as
+ *     the exponent's products stay in fp32 range; beyond it (|alpha z_q| |alpha z_i| near 2^127, alpha = sqrt(log2 e) / h, or a query
+ *     coordinate that is not finite) log_density is -inf or NaN and the mean NaN. A group without a counted particle: NaN rows, count 0.
+ *   pp_is_meanshift_groups  seeds [M, S, J] in STANDARDISED coordinates; x <- mean(x) by the kernels above, fed back on the device. A
+ *       seed is frozen once a step is shorter than tol h (converged 1) or its mean is NaN (converged 0); the call ends when no seed is
+ *       open - the host reads one word every check_every iterations (< 1: 8); a frozen seed never moves, so the results do not depend on
+ *       check_every - or after max_iter iterations. points [M, S, J]: the final points (standardised), log_density [M, S] theirs,
+ *       n_iter [M, S] the steps a seed took, converged [M, S], count [M] or NULL.
+ * Launches, dependent on the caller's stream: (the tile maxima, then) one operand pass writing pp_is_pairs_groups' Gaussian image; per
+ * evaluation the main kernel - four waves own PP_IS_KDEJ_QUERY_TILE queries and one strip of the particles staged through LDS in
+ * chunks of PP_IS_KDEJ_CHUNK; per PP_IS_KDEJ_PARTICLE_BLOCK x PP_IS_KDEJ_QUERY_BLOCK block the exponents come out of
+ * v_mfma_f32_32x32x2_f32, the running maximum is an integer (rescaling is exact), and the v_exp_f32 values feed mean-sum += P Z as
+ * MFMA operands straight from the accumulator registers - and a combine kernel that merges the strips' (max, sum, mean-sum[J]) in
+ * strip order. The number of strips, pp_is_kde_joint_strips(n_per, n_points) <= PP_IS_KDEJ_MAX_STRIPS, is a function of those two
+ * alone (about PP_IS_KDEJ_TARGET_WORKGROUPS workgroups per group). No atomics, no workgroup waits for another, no scratch; fp32 sums of
+ * at most 256 terms flushed to fp64; two calls give the same bits, and group g of an M-group call equals the one-group call on its
+ * slices. The derived error bound is at the head of csrc/is_kde_joint.hip.
+ * Any n_per >= 1, n_cols in 1 .. PP_IS_KDEJ_MAX_J, n_points (n_seeds) in 1 .. PP_IS_KDEJ_MAX_Q and n_groups >= 0 (0: return 0 without a
+ * launch). PP_EINVAL without a launch for a NULL pointer (stats, mean and count may be NULL), a shape outside that envelope, M n_per
+ * or M n_points above 2^31 - 1, a bandwidth_stride other than 0 or 1, max_iter < 1 or tol < 0; PP_ENOSPACE for a short workspace;
+ * pp_is_kde_joint_workspace_bytes (meanshift != 0: for pp_is_meanshift_groups) returns 0 outside the envelope. */
+#define PP_IS_KDEJ_QUERY_BLOCK 32
+#define PP_IS_KDEJ_QUERY_TILE 128
+#define PP_IS_KDEJ_PARTICLE_BLOCK 32
+#define PP_IS_KDEJ_CHUNK 256
+#define PP_IS_KDEJ_MAX_STRIPS 128
+#define PP_IS_KDEJ_TARGET_WORKGROUPS 1024
+#define PP_IS_KDEJ_MAX_Q 65536
+#define PP_IS_KDEJ_MAX_J 8
+size_t pp_is_kde_joint_workspace_bytes(int32_t n_groups, int32_t n_per, int32_t n_cols, int32_t n_points, int32_t meanshift);
+int32_t pp_is_kde_joint_strips(int32_t n_per, int32_t n_points);
+int pp_is_kde_joint_groups(const float* lw /*dev [M n_per]*/, const float* const* cols /*host array of J dev pointers*/,
+                           const double* stats /*dev [M, 6] or NULL*/, int32_t n_per, int32_t n_cols, int32_t n_groups,
+                           const double* center /*dev [M, J]*/, const double* inv_scale /*dev [M, J]*/,
+                           const double* bandwidth /*dev [M] or [1]*/, int64_t bandwidth_stride, const double* points /*dev [M, Q, J]*/,
+                           int32_t n_points, double* log_density /*dev [M, Q]*/, double* mean /*dev [M, Q, J] or NULL*/,
+                           double* count /*dev [M] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+int pp_is_meanshift_groups(const float* lw /*dev [M n_per]*/, const float* const* cols /*host array of J dev pointers*/,
+                           const double* stats /*dev [M, 6] or NULL*/, int32_t n_per, int32_t n_cols, int32_t n_groups,
+                           const double* center /*dev [M, J]*/, const double* inv_scale /*dev [M, J]*/,
+                           const double* bandwidth /*dev [M] or [1]*/, int64_t bandwidth_stride, const double* seeds /*dev [M, S, J]*/,
+                           int32_t n_seeds, double tol, int32_t max_iter, int32_t check_every, double* points /*dev [M, S, J]*/,
+                           double* log_density /*dev [M, S]*/, int32_t* n_iter /*dev [M, S]*/, int32_t* converged /*dev [M, S]*/,
+                           double* count /*dev [M] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pareto-smoothed importance weights and the k-hat diagnostic of a lock-step posterior call on the device (PSIS: Vehtari, Simpson,
  * Gelman, Yao, Gabry, JMLR 2024). The reference has no counterpart: the only reliability figure of its Empirical is
  * effective_sample_size (pyprob/distributions/empirical.py:758-766), which looks healthy exactly when the proposal misses a heavy tail.

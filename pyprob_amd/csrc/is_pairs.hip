@@ -56,25 +56,14 @@
 // that and v_sqrt_f32 adds 1 ulp: (J / 2 + 3) u relative; fp32(v_j) and fp32(w_i): 2 u; the fp32 sum of 128 fma: 128 u:
 //   |d_sum - exact| <= sum_ij w_i v_j (d_ij (J / 2 + 133) u + (|z_i| + |z'_j|) u) + (n_a + n_b + 64) 2^-53 d_sum
 // (v_sqrt_f32 flushes an argument below 2^-126: 2^-63 absolute on d, far below the second term).
-#include "is_groups.hpp"
+#include "is_pair_image.hpp"      // (pass 1, the images and their constants: shared with is_kde_joint.hip)
 
 namespace pp {
 namespace {
 
-constexpr int OP_TILE = 2048, THREADS = 256, PER_THREAD = 8;
-constexpr int ROWS = 128, CHUNK = 256, HALF = 128, MAX_STRIPS = 16, MAXJ = PP_IS_PAIRS_MAX_COLS;
+constexpr int ROWS = 128, HALF = 128, MAX_STRIPS = 16;
 constexpr int GROUPS_PER_LAUNCH = 65535 / 3;       // (three products per group ride on grid dimension z)
-constexpr double LOG2E = 1.4426950408889634;
-static_assert(OP_TILE == THREADS * PER_THREAD && OP_TILE % CHUNK == 0 && HALF == ROWS && 2 * HALF == CHUNK, "tiling");
-
-__host__ __device__ constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
-__host__ __device__ constexpr int image_k(int J) { return (J + 3) & ~1; }
-__host__ __device__ constexpr int dist_stride(int J) { return (J + 4) & ~3; }
-__host__ __device__ constexpr int64_t pad_of(int n) { return (int64_t)ceil_div(n, CHUNK) * CHUNK; }
-
-struct PairCols {
-    const float* p[MAXJ];
-};
+static_assert(HALF == ROWS && 2 * HALF == CHUNK, "tiling");
 
 // The three products of a group: 0 = aa, 1 = bb, 2 = ab. Rows, columns, row blocks, column chunks, chunks per strip, strips.
 struct Shape {
@@ -121,89 +110,6 @@ void pairs_carve(int M, int na, int nb, int J, void* p, PairsWorkspace& w) {
 }
 bool pairs_shape_ok(int M, int na, int nb, int J) {
     return J >= 1 && J <= MAXJ && groups_shape_ok(M, na) && groups_shape_ok(M, nb);
-}
-
-// The workgroup's total of v in a fixed order: lanes by DPP, then the four waves in wave order. sh: 4 doubles.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = wave_sum_dpp(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-// ---- 1. operands ----------------------------------------------------------------------------------------------------------------
-// Workgroup (tile blockIdx.x, group g0 + blockIdx.y) of one side: particles tile 2048 + tid + 256 k.
-template <int J>
-__global__ __launch_bounds__(THREADS) void pairs_operand_kernel(const float* __restrict__ lw, PairCols cols, int n_per, int T, int g0,
-                                                                const double* __restrict__ center, const double* __restrict__ inv_scale,
-                                                                const double* __restrict__ h, int64_t sh_, const double* __restrict__ stats,
-                                                                const float* __restrict__ tmax, float* __restrict__ img,
-                                                                float* __restrict__ dimg, double* __restrict__ wsum) {
-    constexpr int K = image_k(J), DS = dist_stride(J);
-    __shared__ float shmax[THREADS / 64];
-    __shared__ double shsum[THREADS / 64];
-    const int tid = threadIdx.x, tile = blockIdx.x;
-    const int64_t g = (int64_t)g0 + blockIdx.y, base = g * n_per, pad = pad_of(n_per);
-    const int64_t first = (int64_t)tile * OP_TILE + tid;
-    float a[PER_THREAD];
-#pragma unroll
-    for (int k = 0; k < PER_THREAD; ++k) {
-        const int64_t i = first + THREADS * k;
-        a[k] = i < n_per ? lw[base + i] : -INFINITY;
-    }
-    const double M = group_max<THREADS>(stats, tmax, g, T, a, shmax);
-    const bool any = group_any(M);
-    const double hg = h[g * sh_];
-    const double alpha = sqrt(LOG2E) / hg, half_alpha2 = 0.5 * LOG2E / (hg * hg);
-    double c[J], is[J];
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        c[j] = center[g * J + j];
-        is[j] = inv_scale[g * J + j];
-    }
-    float* gi = img + g * K * pad;
-    float* di = dimg + g * DS * pad;
-    double W = 0.0, W2 = 0.0, cnt = 0.0;
-#pragma unroll
-    for (int k = 0; k < PER_THREAD; ++k) {
-        const int64_t i = first + THREADS * k;
-        if (i >= pad) continue;
-        float z[J];
-        bool ok = particle_counted(a[k], any);
-        double r2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            z[j] = i < n_per ? (float)(((double)cols.p[j][base + i] - c[j]) * is[j]) : 0.0f;
-            ok = ok && fabs(alpha * (double)z[j]) < 0x1p30;      // (false for NaN and inf; beyond it fp32 exponents overflow)
-            r2 += (double)z[j] * (double)z[j];
-        }
-        const double w = ok ? particle_weight(a[k], M, any) : 0.0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            gi[j * pad + i] = ok ? (float)(alpha * (double)z[j]) : 0.0f;
-            di[i * DS + j] = ok ? z[j] : 0.0f;
-        }
-#pragma unroll
-        for (int f = J; f < K - 2; ++f) gi[f * pad + i] = 0.0f;
-        gi[(K - 2) * pad + i] = ok ? (float)(LOG2E * ((double)a[k] - M) - half_alpha2 * r2) : -INFINITY;
-        gi[(K - 1) * pad + i] = 1.0f;
-        di[i * DS + J] = (float)w;
-#pragma unroll
-        for (int f = J + 1; f < DS; ++f) di[i * DS + f] = 0.0f;
-        W += w;
-        W2 += w * w;
-        cnt += ok ? 1.0 : 0.0;
-    }
-    W = block_sum(W, shsum);
-    W2 = block_sum(W2, shsum);
-    cnt = block_sum(cnt, shsum);
-    if (tid == 0) {
-        double* o = wsum + (g * T + tile) * 3;
-        o[0] = W;
-        o[1] = W2;
-        o[2] = cnt;
-    }
 }
 
 // ---- 2. pair sums ---------------------------------------------------------------------------------------------------------------
@@ -389,7 +295,7 @@ void launch_pairs(hipStream_t st, const PairSide (&side)[2], int g0, int groups,
         const int T = tiles_of(side[s].n_per, OP_TILE);
         if (T > 1 && !side[s].stats)
             hipLaunchKernelGGL(group_tile_max_kernel, dim3(T, groups), dim3(256), 0, st, side[s].lw, side[s].n_per, OP_TILE, T, g0, w.tmax[s]);
-        hipLaunchKernelGGL(pairs_operand_kernel<J>, dim3(T, groups), dim3(THREADS), 0, st, side[s].lw, side[s].cols, side[s].n_per, T, g0,
+        hipLaunchKernelGGL((pairs_operand_kernel<J, true>), dim3(T, groups), dim3(THREADS), 0, st, side[s].lw, side[s].cols, side[s].n_per, T, g0,
                            center, inv_scale, h, sh, side[s].stats, (const float*)w.tmax[s], w.img[s], w.dimg[s], w.wsum[s]);
     }
     int S = 0;

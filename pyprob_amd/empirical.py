@@ -9,8 +9,9 @@ import warnings
 import numpy as np
 import torch
 
-from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_kde, _host_order, _host_psis,
-                             _host_quantiles, _host_twosample, _host_twosample_joint, _kolmogorov_sf, _pairs_bandwidth,
+from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_joint_moments, _host_kde,
+                             _host_kde_joint, _host_meanshift, _host_order, _host_psis, _host_quantiles, _host_twosample,
+                             _host_twosample_joint, _kdej_standardise, _kolmogorov_sf, _merge_modes, _pairs_bandwidth,
                              _pairs_standardise)
 
 
@@ -869,6 +870,97 @@ class Empirical:
         center, s = _pairs_standardise(ja[0].mean, ja[0].stddev ** 2, jb[0].mean, jb[0].stddev ** 2, scale)
         row = _device_pairs(sides[0], sides[1], center[None], s[None], np.array([h]))[0]
         return _two_sample_joint(row, names, h, s, center)
+
+    # ---- joint kernel density and its modes (csrc/is_kde_joint.hip) -------------------------------------------------------
+    def _kdej_setup(self, what, addresses, bandwidth, scale):
+        """What kde_joint and modes share: (names, log-weights, columns, statistics row, on the device?, center, scale, h, count, ess)."""
+        self._check_finalized()
+        names, lw, cols, stats = self._pair_columns(addresses)
+        J = len(names)
+        if not 1 <= J <= 8:
+            raise ValueError('%s takes 1 .. 8 addresses, not %d' % (what, J))
+        tensors = [lw] + list(cols)
+        device = os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0' and all(
+            torch.is_tensor(t) and t.is_cuda and t.device == lw.device and t.dtype == torch.float32 and t.dim() == 1 and
+            t.is_contiguous() for t in tensors)
+        if device:
+            m = _joint_rows(names, _moment_rows(lw, cols, lw.numel(), stats))[0]
+            mean, std, ess, count = m.mean, m.stddev, float(m.ess), int(m.count)
+        else:
+            to_np = lambda t: t.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(t) else np.asarray(t, np.float64)  # noqa: E731
+            lw, cols = to_np(lw), np.stack([to_np(c) for c in cols], 1)
+            mean, std, ess, count = _host_joint_moments(lw, cols)
+        center, s = _kdej_standardise(mean, std, scale)
+        h = _kde_bandwidth(bandwidth, lambda: _rule_bandwidth(1.0, ess, -1.0 / (J + 4), count))
+        return names, lw, cols, stats, device, center, s, h, count, ess
+
+    def kde_joint(self, x, addresses=None, bandwidth=None, scale=None):
+        """The weighted product-Gaussian kernel density of SEVERAL latents at the points x [Q, J] as a KernelDensityJoint (x,
+        log_density, density, bandwidth, center, scale, addresses, count, ess): sum_i w_i N_J(z; z_i, h^2 I) / prod_j scale_j with z =
+        (x - center) / scale - a density of x, in the ORIGINAL coordinates - where kde2d's tensor-product grid stops at two.
+        addresses: as joint() takes them (None: every address that all particles executed; an address of a branch raises as it does
+        there); 1 .. 8 of them. center and scale: the object's own joint() mean and per-address standard deviation; scale=: J positive
+        numbers instead (needed where an address has no spread: ValueError). bandwidth: h in standardised units, default Scott's rule
+        ess^(-1 / (J + 4)). A particle counts where its log-weight is finite and none of its coordinates is NaN or infinite. A point
+        far from every particle keeps a finite log_density (its density may underflow to 0).
+
+        Columns that are float32 tensors on one device (a lock-step posterior call, its psis(), reobserve() and
+        posterior_results_from_proposal results) take ONE pp_is_kde_joint_groups call - the exponents on the fp32 matrix pipe under a
+        running maximum; derived error bound in DESIGN.md - and one copy of Q doubles. Every other object, and all of them under
+        PP_EMPIRICAL_DEVICE=0, takes the same definition in chunked float64 numpy (empirical_host._host_kde_joint)."""
+        names, lw, cols, stats, device, center, s, h, count, ess = self._kdej_setup('kde_joint', addresses, bandwidth, scale)
+        pts = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, len(names)))
+        if not 1 <= len(pts) <= _KDEJ_MAX_POINTS:
+            raise ValueError('kde_joint takes 1 .. %d points of %d coordinates' % (_KDEJ_MAX_POINTS, len(names)))
+        if device:
+            from .ops import ops
+            as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(lw.device)      # noqa: E731
+            logd = ops.is_kde_joint_groups(lw, list(cols), lw.numel(), stats, as_dev(center[None]), as_dev(1.0 / s[None]),
+                                           as_dev(np.array([h])), as_dev(pts[None]), False)[0].cpu().numpy()[0]
+        else:
+            logd = _host_kde_joint(lw, cols, center, s, h, pts)[0]
+        return KernelDensityJoint(names, pts, logd - np.log(s).sum(), h, center, s, count, ess)
+
+    def modes(self, addresses=None, bandwidth=None, scale=None, num_seeds=256, tol=1e-3, max_iter=200, seed=None):
+        """The joint modes of several latents as a JointModes (modes [R, J] in the original coordinates by descending density - modes[0]
+        is the joint MAP estimate -, log_density [R], share [R], n_iter, converged, bandwidth, addresses, count, ess): mean shift on
+        kde_joint's density. num_seeds (at most 4096) joint particles drawn with resample_joint(scheme='systematic', seed=seed) climb x
+        <- sum_i w_i k_i z_i / sum_i w_i k_i until their step is below tol h or max_iter; the end points are merged on the host in
+        float64 - two seeds are one mode if they end within h / 2 of each other, the one with the highest density represents it - and
+        share is the fraction of the seeds that ended in each mode: the draws being systematic, an estimate of the mass of its basin.
+        addresses, bandwidth, scale: as kde_joint takes them. A seed that did not converge warns. The metadata says op='modes'.
+
+        On the device ONE pp_is_meanshift_groups call iterates without a host round trip (the host reads one word every eighth
+        iteration); the host route (empirical_host._host_meanshift) is the same definition in float64 numpy."""
+        names, lw, cols, stats, device, center, s, h, count, ess = self._kdej_setup('modes', addresses, bandwidth, scale)
+        S = int(num_seeds)
+        if not 1 <= S <= _MODES_MAX_SEEDS:
+            raise ValueError('num_seeds in 1 .. %d' % _MODES_MAX_SEEDS)
+        if not (tol >= 0 and int(max_iter) >= 1):
+            raise ValueError('tol >= 0 and max_iter >= 1')
+        if device:
+            from .ops import ops
+            as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(lw.device)      # noqa: E731
+            drawn = self.resample_joint(S, names, seed=_philox_key(seed), scheme='systematic')
+            seeds = (torch.stack([drawn[a].double() for a in names], 1) - as_dev(center)) * as_dev(1.0 / s)
+            out = ops.is_meanshift_groups(lw, list(cols), lw.numel(), stats, as_dev(center[None]), as_dev(1.0 / s[None]),
+                                          as_dev(np.array([h])), seeds[None].contiguous(), float(tol), int(max_iter), 8)
+            pts, logd, n_iter, conv = (t.cpu().numpy()[0] for t in out[:4])
+        else:
+            fin = np.isfinite(lw)
+            cdf = np.cumsum(np.where(fin, np.exp(lw - (lw[fin].max() if fin.any() else 0.0)), 0.0))
+            u = (np.arange(S) + np.random.default_rng(seed).random()) / S * cdf[-1]
+            index = np.minimum(np.searchsorted(cdf, u, side='right'), len(cdf) - 1)
+            pts, logd, n_iter, conv, _ = _host_meanshift(lw, cols, center, s, h, (cols[index] - center) / s, float(tol), int(max_iter))
+        if not np.all(conv):
+            warnings.warn('modes: %d of %d seeds did not converge within %d iterations (tol %g)' % (
+                int(S - np.sum(conv != 0)), S, int(max_iter), tol))
+        reps, label = _merge_modes(pts, logd, h)
+        share = np.bincount(label[label >= 0], minlength=len(reps)) / float(S)
+        meta = dict(self._metadata)
+        meta.update(op='modes', length=self.length, num_seeds=S, tol=float(tol), max_iter=int(max_iter))
+        return JointModes(names, center + pts[reps] * s, logd[reps] - np.log(s).sum(), share, n_iter, np.asarray(conv) != 0, h,
+                          center, s, count, ess, meta)
 
     # ---- Pareto-smoothed importance sampling (csrc/is_psis.hip) -----------------------------------------------------------
     def _device_lw_sorted(self):
@@ -1754,6 +1846,42 @@ class KernelDensity2D:
 
     def __repr__(self):
         return 'KernelDensity2D(addresses:{}, grid:{}x{}, bandwidth:{})'.format(self.addresses, len(self.x), len(self.y), self.bandwidth)
+
+
+_KDEJ_MAX_POINTS = 65536    # PP_IS_KDEJ_MAX_Q
+_MODES_MAX_SEEDS = 4096
+
+
+class KernelDensityJoint:
+    """A weighted product-Gaussian kernel density of several latents at points (Empirical.kde_joint), float64 numpy: addresses, x [Q,
+    J] the points, log_density [Q] and density [Q] in the ORIGINAL coordinates, bandwidth h (standardised units), center [J] and
+    scale [J] of the standardisation, count (joint()'s: the particles with a finite log-weight) and ess."""
+
+    def __init__(self, addresses, x, log_density, bandwidth, center, scale, count, ess):
+        self.addresses, self.x, self.log_density = list(addresses), x, log_density
+        with np.errstate(under='ignore'):
+            self.density = np.exp(log_density)
+        self.bandwidth, self.center, self.scale, self.count, self.ess = float(bandwidth), center, scale, int(count), float(ess)
+
+    def __repr__(self):
+        return 'KernelDensityJoint(addresses:{}, points:{}, bandwidth:{:.6g}, count:{})'.format(self.addresses, len(self.x),
+                                                                                               self.bandwidth, self.count)
+
+
+class JointModes:
+    """The joint modes of several latents (Empirical.modes), float64 numpy: addresses, modes [R, J] in the original coordinates by
+    descending density (modes[0]: the joint MAP estimate), log_density [R] (of the original coordinates), share [R] the fraction of
+    the seeds that ended in each mode, n_iter [S] and converged [S] per seed, bandwidth h (standardised units), center, scale, count,
+    ess and metadata (op='modes')."""
+
+    def __init__(self, addresses, modes, log_density, share, n_iter, converged, bandwidth, center, scale, count, ess, metadata):
+        self.addresses, self.modes, self.log_density, self.share = list(addresses), modes, log_density, share
+        self.n_iter, self.converged, self.bandwidth = n_iter, converged, float(bandwidth)
+        self.center, self.scale, self.count, self.ess, self.metadata = center, scale, int(count), float(ess), metadata
+
+    def __repr__(self):
+        return 'JointModes(addresses:{}, modes:{}, bandwidth:{:.6g}, share:{})'.format(self.addresses, len(self.modes), self.bandwidth,
+                                                                                       np.round(self.share, 3).tolist())
 
 
 def _kde_bandwidth(bandwidth, rule):

@@ -189,6 +189,118 @@ def _host_twosample_joint(lw_a, x_a, lw_b, x_b, bandwidth=None, scale=None, chun
     return row, center, s, h
 
 
+def _kdej_standardise(mean, stddev, scale):
+    """(center, scale) [J] of kde_joint / modes: the object's own joint() mean and per-address standard deviation, or the caller's J
+    positive numbers in place of the latter."""
+    center = np.asarray(mean, np.float64).reshape(-1)
+    if scale is None:
+        s = np.asarray(stddev, np.float64).reshape(-1)
+    else:
+        s = np.asarray(scale, np.float64).reshape(-1)
+        if s.shape != center.shape or not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError('scale= takes %d finite positive numbers, one per address' % center.shape[0])
+    if not np.isfinite(center).all() or not np.isfinite(s).all():
+        raise ValueError('the joint moments are not finite (no particle with a weight, or a NaN or infinite coordinate under a '
+                         'finite weight): nothing to standardise by')
+    if (s == 0).any():
+        raise ValueError('an address has no spread: pass scale= (J positive numbers)')
+    return center, s
+
+
+def _host_joint_moments(lw, x):
+    """(mean [J], stddev [J], ess, count) of joint(): over the particles with a finite log-weight, in float64 numpy."""
+    lw, x = np.asarray(lw, np.float64).reshape(-1), np.asarray(x, np.float64)
+    fin = np.isfinite(lw)
+    w = np.where(fin, np.exp(lw - (lw[fin].max() if fin.any() else 0.0)), 0.0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = (w[fin, None] * x[fin]).sum(0) / w.sum()
+        std = np.sqrt(np.maximum((w[fin, None] * (x[fin] - mean) ** 2).sum(0) / w.sum(), 0.0))
+        ess = float(w.sum() ** 2 / (w * w).sum())
+    return mean, std, ess, int(fin.sum())
+
+
+def _kdej_counted(lw, x, center, scale):
+    """(z [c, J], log of the normalised weights [c]) of the particles pp_is_kde_joint_groups counts: a finite log-weight and J finite
+    standardised coordinates."""
+    lw, x = np.asarray(lw, np.float64).reshape(-1), np.asarray(x, np.float64)
+    with np.errstate(invalid='ignore'):
+        z = (x.reshape(len(lw), -1) - center) * (1.0 / scale)
+    keep = np.isfinite(lw) & np.isfinite(z).all(1)
+    z, lw = z[keep], lw[keep]
+    if len(lw):
+        lw = lw - lw.max()
+        lw = lw - math.log(np.exp(lw).sum())
+    return z, lw
+
+
+def _kdej_at(z, logw, zq, h, want_mean, chunk=64):
+    """log sum_i w_i N_J(zq; z_i, h^2 I) [Q] and the mean-shift mean [Q, J] (or None) in chunked float64 numpy, the maximum of the
+    exponents taken out before the exponential as the device does."""
+    Q, J = zq.shape
+    logd, mean = np.full(Q, np.nan), (np.full((Q, J), np.nan) if want_mean else None)
+    if len(logw) == 0:
+        return logd, mean
+    norm = J * (math.log(h) + 0.5 * math.log(2.0 * math.pi))
+    for a in range(0, Q, chunk):
+        with np.errstate(invalid='ignore', over='ignore'):
+            diff = zq[a:a + chunk, None, :] - z[None, :, :]
+            e = logw[None, :] - (diff * diff).sum(-1) * (0.5 / (h * h))
+            m = np.nanmax(np.where(np.isnan(e), -np.inf, e), axis=1)
+            p = np.exp(e - m[:, None])
+            S = p.sum(1)
+            logd[a:a + chunk] = m + np.log(S) - norm
+            if want_mean:
+                mean[a:a + chunk] = (p @ z) / S[:, None]
+    return logd, mean
+
+
+def _host_kde_joint(lw, x, center, scale, h, points, want_mean=False):
+    """pp_is_kde_joint_groups' definition (include/pyprob_amd.h) for one particle set: x [n, J], points [Q, J] in the ORIGINAL
+    coordinates. (log_density [Q] of the standardised coordinates, mean [Q, J] standardised or None, count)."""
+    z, logw = _kdej_counted(lw, x, center, scale)
+    with np.errstate(invalid='ignore'):
+        zq = (np.asarray(points, np.float64).reshape(-1, len(center)) - center) * (1.0 / scale)
+    logd, mean = _kdej_at(z, logw, zq, float(h), want_mean)
+    return logd, mean, len(logw)
+
+
+def _host_meanshift(lw, x, center, scale, h, seeds, tol, max_iter):
+    """pp_is_meanshift_groups' definition for one particle set, seeds [S, J] STANDARDISED: (points [S, J], log_density [S], n_iter
+    [S], converged [S], count)."""
+    z, logw = _kdej_counted(lw, x, center, scale)
+    pts = np.array(seeds, np.float64).reshape(-1, len(center))
+    S = len(pts)
+    state, n_iter = np.zeros(S, np.int64), np.zeros(S, np.int32)
+    for it in range(1, int(max_iter) + 1):
+        live = np.flatnonzero(state == 0)
+        if len(live) == 0:
+            break
+        mean = _kdej_at(z, logw, pts[live], float(h), True)[1]
+        step2 = ((mean - pts[live]) ** 2).sum(1)
+        pts[live], n_iter[live] = mean, it
+        state[live] = np.where(np.isnan(step2), 2, np.where(step2 < (tol * h) ** 2, 1, 0))
+    return pts, _kdej_at(z, logw, pts, float(h), False)[0], n_iter, state == 1, len(logw)
+
+
+def _merge_modes(points, log_density, h):
+    """The end points of mean shift merged in float64: in descending order of density, a point within h / 2 of a mode's
+    representative joins it, else it opens a mode. (the representatives' indices, the mode of every point or -1 for a NaN point)."""
+    order = [int(i) for i in np.argsort(-np.where(np.isnan(log_density), -np.inf, log_density), kind='stable')]
+    reps, label = [], np.full(len(points), -1, np.int64)
+    for i in order:
+        if not (np.isfinite(points[i]).all() and np.isfinite(log_density[i])):
+            continue
+        if reps:
+            d2 = ((points[reps] - points[i]) ** 2).sum(1)
+            k = int(np.argmin(d2))
+            if d2[k] < 0.25 * h * h:
+                label[i] = k
+                continue
+        label[i] = len(reps)
+        reps.append(i)
+    return np.asarray(reps, np.int64), label
+
+
 def _kolmogorov_sf(lam):
     """P(K > lam) of the Kolmogorov distribution: the series 2 sum_k (-1)^(k-1) exp(-2 k^2 lam^2), below lam = 1.18 its theta-function
     form 1 - sqrt(2 pi) / lam sum_k exp(-(2 k - 1)^2 pi^2 / (8 lam^2)), which converges where the first does not."""

@@ -43,6 +43,10 @@ PP_IS_TWOSAMPLE_TILE = 2048  # merged positions one workgroup of pp_is_twosample
 PP_IS_TWOSAMPLE_WIDTH = 8    # doubles per group of pp_is_twosample_groups' out (include/pyprob_amd.h)
 PP_IS_PAIRS_MAX_COLS = 8     # columns of one pp_is_pairs_groups call (include/pyprob_amd.h)
 PP_IS_PAIRS_WIDTH = 10       # doubles per group of pp_is_pairs_groups' out (include/pyprob_amd.h)
+# pp_is_kde_joint_groups / pp_is_meanshift_groups (include/pyprob_amd.h): the queries of a 32 x 32 block and of a workgroup, the
+# particles of a block and of a staged chunk, the most strips and the workgroups aimed at per group, the largest Q and J
+PP_IS_KDEJ_QUERY_BLOCK, PP_IS_KDEJ_QUERY_TILE, PP_IS_KDEJ_PARTICLE_BLOCK, PP_IS_KDEJ_CHUNK = 32, 128, 32, 256
+PP_IS_KDEJ_MAX_STRIPS, PP_IS_KDEJ_TARGET_WORKGROUPS, PP_IS_KDEJ_MAX_Q, PP_IS_KDEJ_MAX_J = 128, 1024, 65536, 8
 
 
 def PP_IS_MOMENTS_WIDTH(n_cols):
@@ -263,6 +267,11 @@ PROTOTYPES = {
     'pp_is_twosample_workspace_bytes': (C.c_size_t, [i32, i32, i32]),
     'pp_is_twosample_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, C.c_size_t, vp]),
     'pp_is_pairs_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
+    'pp_is_kde_joint_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32, i32]),
+    'pp_is_kde_joint_strips': (i32, [i32, i32]),
+    'pp_is_kde_joint_groups': (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    'pp_is_meanshift_groups': (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp,
+                                         vp, C.c_size_t, vp]),
     'pp_is_pairs_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),

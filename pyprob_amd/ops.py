@@ -42,6 +42,8 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_kde2d_groups     the same for two latents on a rectangular grid, on the fp32 matrix pipe (the reference has none)   -
     is_twosample_groups KS, Wasserstein-1/2 and energy distance between two sorted groups, by merge path (the reference has none)   -
     is_pairs_groups     Gaussian-kernel and Euclidean-distance pair sums between two groups of joint particles (the reference has none)   -
+    is_kde_joint_groups product-Gaussian kernel density and mean-shift mean of joint particles at points (the reference has none)   -
+    is_meanshift_groups mean shift from seeds to the joint modes, iterated on the device (the reference has none)   -
     reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -123,6 +125,10 @@ _lib.define('is_twosample_groups(Tensor value_a, Tensor cdf_a, Tensor counted_a,
             'Tensor counted_b, int n_per_b) -> Tensor')
 _lib.define('is_pairs_groups(Tensor lw_a, Tensor[] cols_a, int n_per_a, Tensor? stats_a, Tensor lw_b, Tensor[] cols_b, int n_per_b, '
             'Tensor? stats_b, Tensor center, Tensor inv_scale, Tensor bandwidth) -> Tensor')
+_lib.define('is_kde_joint_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? stats, Tensor center, Tensor inv_scale, Tensor bandwidth, '
+            'Tensor points, bool want_mean) -> (Tensor, Tensor, Tensor)')
+_lib.define('is_meanshift_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? stats, Tensor center, Tensor inv_scale, Tensor bandwidth, '
+            'Tensor seeds, float tol, int max_iter, int check_every) -> (Tensor, Tensor, Tensor, Tensor, Tensor)')
 _lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
             'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -1088,6 +1094,76 @@ def _is_pairs_groups_hip(lw_a, cols_a, n_per_a, stats_a, lw_b, cols_b, n_per_b, 
     return out
 
 
+def _kdej_args(what, lw, cols, n_per, stats, center, inv_scale, bandwidth, points):
+    """(M, J, Q) of a pp_is_kde_joint_groups / pp_is_meanshift_groups call after its argument checks."""
+    _same_device(lw, stats, center, inv_scale, bandwidth, points, *cols)
+    M = _groups_of(_f32(lw, 'lw'), n_per, what)
+    J = len(cols)
+    if not 1 <= J <= L.PP_IS_KDEJ_MAX_J:
+        raise RuntimeError('pyprob_hip::%s: 1 .. %d columns per call' % (what, L.PP_IS_KDEJ_MAX_J))
+    for c in cols:
+        _particles_like(c, lw, 'every column', what)
+    _group_stats_ok(stats, M, what)
+    for t, name in ((center, 'center'), (inv_scale, 'inv_scale')):
+        if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != (M, J):
+            raise RuntimeError('pyprob_hip::%s: %s must be a contiguous float64 tensor of [M, J]' % (what, name))
+    if bandwidth.dtype != torch.float64 or not bandwidth.is_contiguous() or bandwidth.dim() != 1 or bandwidth.numel() not in (1, M):
+        raise RuntimeError('pyprob_hip::%s: bandwidth must be a contiguous float64 tensor of [1] or [M]' % what)
+    if points.dtype != torch.float64 or not points.is_contiguous() or points.dim() != 3 or points.shape[0] != M or \
+            points.shape[2] != J or not 1 <= points.shape[1] <= L.PP_IS_KDEJ_MAX_Q:
+        raise RuntimeError('pyprob_hip::%s: the points must be a contiguous float64 tensor of [M, Q, J], 1 <= Q <= %d'
+                           % (what, L.PP_IS_KDEJ_MAX_Q))
+    return M, J, int(points.shape[1])
+
+
+def _is_kde_joint_groups_hip(lw, cols, n_per, stats, center, inv_scale, bandwidth, points, want_mean):
+    """(log_density [M, Q], mean [M, Q, J] or an empty tensor, count [M]) in float64: the product-Gaussian kernel density of the M
+    groups of joint particles (J columns) at points [M, Q, J] given in the ORIGINAL coordinates, in standardised units, and where
+    want_mean the mean-shift mean in standardised coordinates (pp_is_kde_joint_groups). center, inv_scale: float64 [M, J];
+    bandwidth: float64 [M] or [1] (shared); stats: as for is_cdf_groups."""
+    lib = L.load()
+    cols = list(cols)
+    M, J, Q = _kdej_args('is_kde_joint_groups', lw, cols, n_per, stats, center, inv_scale, bandwidth, points)
+    dev = lw.device
+    log_density = torch.empty((M, Q), dtype=torch.float64, device=dev)
+    mean = torch.empty((M, Q, J) if want_mean else (0,), dtype=torch.float64, device=dev)
+    count = torch.empty((M,), dtype=torch.float64, device=dev)
+    ws, need = _workspace(lib.pp_is_kde_joint_workspace_bytes, dev, M, int(n_per), J, Q, 0)
+    ptrs = (C.c_void_p * J)(*[c.data_ptr() for c in cols])
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_kde_joint_groups(lw.data_ptr(), C.cast(ptrs, C.c_void_p), L.ptr(stats), int(n_per), J, M, center.data_ptr(),
+                                        inv_scale.data_ptr(), bandwidth.data_ptr(), 1 if (bandwidth.numel() == M and M > 1) else 0,
+                                        points.data_ptr(), Q, log_density.data_ptr(), mean.data_ptr() if want_mean else None,
+                                        count.data_ptr(), ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_kde_joint_groups')
+    return log_density, mean, count
+
+
+def _is_meanshift_groups_hip(lw, cols, n_per, stats, center, inv_scale, bandwidth, seeds, tol, max_iter, check_every):
+    """(points float64 [M, S, J], log_density float64 [M, S], n_iter int32 [M, S], converged int32 [M, S], count float64 [M]): mean
+    shift of the seeds [M, S, J] (STANDARDISED coordinates, as the points returned) on the kernel density of the M groups of joint
+    particles, iterated on the device until every seed's step is below tol h or max_iter (pp_is_meanshift_groups)."""
+    lib = L.load()
+    cols = list(cols)
+    M, J, S = _kdej_args('is_meanshift_groups', lw, cols, n_per, stats, center, inv_scale, bandwidth, seeds)
+    dev = lw.device
+    points = torch.empty((M, S, J), dtype=torch.float64, device=dev)
+    log_density = torch.empty((M, S), dtype=torch.float64, device=dev)
+    n_iter = torch.empty((M, S), dtype=torch.int32, device=dev)
+    converged = torch.empty((M, S), dtype=torch.int32, device=dev)
+    count = torch.empty((M,), dtype=torch.float64, device=dev)
+    ws, need = _workspace(lib.pp_is_kde_joint_workspace_bytes, dev, M, int(n_per), J, S, 1)
+    ptrs = (C.c_void_p * J)(*[c.data_ptr() for c in cols])
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_meanshift_groups(lw.data_ptr(), C.cast(ptrs, C.c_void_p), L.ptr(stats), int(n_per), J, M, center.data_ptr(),
+                                        inv_scale.data_ptr(), bandwidth.data_ptr(), 1 if (bandwidth.numel() == M and M > 1) else 0,
+                                        seeds.data_ptr(), S, float(tol), int(max_iter), int(check_every), points.data_ptr(),
+                                        log_density.data_ptr(), n_iter.data_ptr(), converged.data_ptr(), count.data_ptr(),
+                                        ws.data_ptr(), need, _stream(lw))
+    L.check(rc, 'pp_is_meanshift_groups')
+    return points, log_density, n_iter, converged, count
+
+
 def _kde_rows(t, M, most, name, what):
     """(row length, stride) of a float64 tensor of points: [Q] shared by the groups (stride 0) or [M, Q], one row per group."""
     if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != M) or \
@@ -1329,6 +1405,8 @@ _lib.impl('is_hpd_groups', _is_hpd_groups_hip, 'CUDA')
 _lib.impl('is_ecdf_groups', _is_ecdf_groups_hip, 'CUDA')
 _lib.impl('is_twosample_groups', _is_twosample_groups_hip, 'CUDA')
 _lib.impl('is_pairs_groups', _is_pairs_groups_hip, 'CUDA')
+_lib.impl('is_kde_joint_groups', _is_kde_joint_groups_hip, 'CUDA')
+_lib.impl('is_meanshift_groups', _is_meanshift_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
