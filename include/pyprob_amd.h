@@ -1058,6 +1058,63 @@ int pp_is_meanshift_groups(const float* lw /*dev [M n_per]*/, const float* const
                            double* log_density /*dev [M, S]*/, int32_t* n_iter /*dev [M, S]*/, int32_t* converged /*dev [M, S]*/,
                            double* count /*dev [M] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The entropic optimal-transport cost and the debiased Sinkhorn divergence between the JOINT particles of two lock-step posteriors on
+ * the device (Empirical.sinkhorn). The reference has no distance between two Empiricals. INPUTS as pp_is_pairs_groups takes them: per
+ * side, with a n_per of its own, the log-weights [M n_per], a HOST array of n_cols device column pointers and the [M, 6] statistics or
+ * NULL; center [M, J], inv_scale [M, J] and epsilon [M] (device doubles, standardised units, > 0). The particles are standardised and
+ * COUNTED by pp_is_pairs_groups' rule with alpha = sqrt(log2 e / epsilon) in place of sqrt(log2 e) / h; a, b below are the weights
+ * exp(lw - max) of the counted particles of side a and b over their sums, C_ij = |z_i - z'_j|^2 / 2.
+ *   problem (a, b)   potentials f [n_a], g [n_b] from 0; one iteration is the g update, then the f update:
+ *                      g_j <- -eps log sum_i a_i exp((f_i - C_ij) / eps),   f_i <- -eps log sum_j b_j exp((g_j - C_ij) / eps)
+ *                    residual = max(max_i |f_new - f_old|, max_j |g_new - g_old|) / eps
+ *   problems (a, a), (b, b)   one potential p from 0; one iteration is p_i <- (p_i + T(p)_i) / 2,
+ *                      T(p)_i = -eps log sum_j a_j exp((p_j - C_ij) / eps);   residual = max_i |p_new - p_old| / eps
+ *   A problem is frozen after the first iteration whose residual is below tol (converged) and stops at max_iter otherwise; tol = 0 runs
+ *   exactly max_iter iterations. The host reads one word every check_every iterations (< 1: 8); a frozen problem's potentials never
+ *   move again, so no result depends on check_every.
+ *   out[g] = { ot_ab, ot_aa, ot_bb, n_iter_ab, n_iter_aa, n_iter_bb, residual_ab, residual_aa, residual_bb, count_a, count_b, status }:
+ *     PP_IS_SINKHORN_WIDTH doubles, ot_ab = sum a_i f_i + sum b_j g_j, ot_aa = 2 sum a_i p_i, ot_bb likewise (the caller forms
+ *     divergence = ot_ab - (ot_aa + ot_bb) / 2); status = the sum of 1, 2, 4 for a problem ab, aa, bb that max_iter stopped and 8 where
+ *     a side has no counted particle (the costs, residuals and potentials are then NaN).
+ *   f [M, n_a], g [M, n_b] (or NULL): the potentials of problem (a, b); p_a [M, n_a], p_b [M, n_b] (or NULL): those of (a, a) and
+ *     (b, b); NaN where a particle does not count.
+ * Launches, dependent on the caller's stream: per side (the tile maxima, then) one operand pass writing pp_is_pairs_groups' Gaussian
+ * image, whose q column alone carries a potential: q = fp32(log2(e) (lw - max + pot / eps) - alpha^2 |z|^2 / 2); per iteration two
+ * half-step launches (the g, aa and bb updates of all groups on grid dimension z, then the f updates) - four waves own
+ * PP_IS_SINKHORN_QUERY_TILE queries (the OTHER side's particles, any number of tiles) and one strip of the summed side staged through
+ * LDS in chunks of PP_IS_SINKHORN_CHUNK; the exponents of a PP_IS_SINKHORN_PARTICLE_BLOCK x PP_IS_SINKHORN_QUERY_BLOCK block come out
+ * of v_mfma_f32_32x32x2_f32 under an integer running maximum - each followed by an update launch (a thread per query merges the
+ * strips in strip order, writes the new potential and its q column and leaves a per-workgroup maximum of |new - old|), and one fold
+ * launch (a workgroup per problem: residual, iteration count, frozen flag). The strips of a half-step,
+ * pp_is_sinkhorn_strips(n_sum, n_query) <= PP_IS_SINKHORN_MAX_STRIPS, are a function of those two alone (about
+ * PP_IS_SINKHORN_TARGET_WORKGROUPS workgroups). No atomics, no workgroup waits for another, no scratch in the half-step kernel; the
+ * order of every sum is a function of (n_per_a, n_per_b, n_cols) alone: two calls give the same bits, and group g of an M-group call
+ * equals the one-group call on its slices. Memory is O(M (n_per_a + n_per_b)): no n_a x n_b matrix is stored. The derived error bound
+ * is at the head of csrc/is_sinkhorn.hip.
+ * Any n_per_a, n_per_b >= 1, n_cols in 1 .. PP_IS_SINKHORN_MAX_J and 0 <= n_groups <= 16383 (0: return 0 without a launch).
+ * PP_EINVAL without a launch for a NULL pointer (stats_a, stats_b, f, g, p_a and p_b may be NULL), a shape outside that envelope, M n_per_a or
+ * M n_per_b above 2^31 - 1, max_iter < 1 or tol < 0; PP_ENOSPACE for a short workspace; pp_is_sinkhorn_workspace_bytes returns 0
+ * outside the envelope. */
+#define PP_IS_SINKHORN_QUERY_BLOCK 32
+#define PP_IS_SINKHORN_QUERY_TILE 128
+#define PP_IS_SINKHORN_PARTICLE_BLOCK 32
+#define PP_IS_SINKHORN_CHUNK 256
+#define PP_IS_SINKHORN_MAX_STRIPS 16
+#define PP_IS_SINKHORN_TARGET_WORKGROUPS 1024
+#define PP_IS_SINKHORN_MAX_J 8
+#define PP_IS_SINKHORN_MAX_GROUPS 16383
+#define PP_IS_SINKHORN_WIDTH 12
+size_t pp_is_sinkhorn_workspace_bytes(int32_t n_groups, int32_t n_per_a, int32_t n_per_b, int32_t n_cols);
+int32_t pp_is_sinkhorn_strips(int32_t n_sum, int32_t n_query);
+int pp_is_sinkhorn_groups(const float* lw_a /*dev [M n_per_a]*/, const float* const* cols_a /*host array of J dev pointers*/,
+                          const double* stats_a /*dev [M, 6] or NULL*/, int32_t n_per_a, const float* lw_b /*dev [M n_per_b]*/,
+                          const float* const* cols_b /*host array of J dev pointers*/, const double* stats_b /*dev [M, 6] or NULL*/,
+                          int32_t n_per_b, int32_t n_cols, int32_t n_groups, const double* center /*dev [M, J]*/,
+                          const double* inv_scale /*dev [M, J]*/, const double* epsilon /*dev [M]*/, double tol, int32_t max_iter,
+                          int32_t check_every, double* out /*dev [M, 12]*/, double* f /*dev [M, n_per_a] or NULL*/,
+                          double* g /*dev [M, n_per_b] or NULL*/, double* p_a /*dev [M, n_per_a] or NULL*/,
+                          double* p_b /*dev [M, n_per_b] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pareto-smoothed importance weights and the k-hat diagnostic of a lock-step posterior call on the device (PSIS: Vehtari, Simpson,
  * Gelman, Yao, Gabry, JMLR 2024). The reference has no counterpart: the only reliability figure of its Empirical is
  * effective_sample_size (pyprob/distributions/empirical.py:758-766), which looks healthy exactly when the proposal misses a heavy tail.

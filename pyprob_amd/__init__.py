@@ -8,7 +8,7 @@ _FROM_DISTRIBUTIONS = frozenset((
     'resample_batch', 'joint_batch', 'histogram_batch', 'quantile_batch', 'hpd_batch', 'cdf_batch', 'pareto_k_batch', 'psis_batch',
     'density_estimate_batch', 'density_estimate_joint_batch', 'reobserve_batch', 'Histogram', 'Histogram2D', 'MixtureFit',
     'JointMixtureFit', 'PsisFit', 'kde_batch', 'KernelDensity', 'KernelDensity2D', 'compare_batch', 'TwoSample',
-    'compare_joint_batch', 'TwoSampleJoint', 'KernelDensityJoint', 'JointModes'))
+    'compare_joint_batch', 'TwoSampleJoint', 'KernelDensityJoint', 'JointModes', 'TwoSampleTransport'))
 
 
 def __getattr__(name):

@@ -702,7 +702,8 @@ class Factor(Distribution):
 
 # The weighted-sample container and its batch calls live in modules of their own; their public names stay importable from here.
 from .empirical import (PSIS_KHAT_THRESHOLD, Empirical, Histogram, Histogram2D, JointMixtureFit, JointMoments,  # noqa: E402,F401
-                        JointModes, KernelDensity, KernelDensity2D, KernelDensityJoint, MixtureFit, PsisFit, TwoSample, TwoSampleJoint, joint_from_moments)
+                        JointModes, KernelDensity, KernelDensity2D, KernelDensityJoint, MixtureFit, PsisFit, TwoSample, TwoSampleJoint, TwoSampleTransport,
+                        joint_from_moments)
 from .empirical_batch import (cdf_batch, compare_batch, compare_joint_batch, density_estimate_batch, density_estimate_joint_batch, histogram_batch,  # noqa: E402,F401
                               hpd_batch, joint_batch, kde_batch, pareto_k_batch, psis_batch, quantile_batch, reobserve_batch,
                               resample_batch)

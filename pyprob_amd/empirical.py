@@ -11,8 +11,8 @@ import torch
 
 from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_joint_moments, _host_kde,
                              _host_kde_joint, _host_meanshift, _host_order, _host_psis, _host_quantiles, _host_twosample,
-                             _host_twosample_joint, _kdej_standardise, _kolmogorov_sf, _merge_modes, _pairs_bandwidth,
-                             _pairs_standardise)
+                             _host_sinkhorn, _host_twosample_joint, _kdej_standardise, _kolmogorov_sf, _merge_modes, _pairs_bandwidth,
+                             _pairs_standardise, _sinkhorn_epsilon)
 
 
 _NO_STATEMENT_LOG = ('this Empirical has no statement log: only the result of a lock-step posterior call '
@@ -870,6 +870,64 @@ class Empirical:
         center, s = _pairs_standardise(ja[0].mean, ja[0].stddev ** 2, jb[0].mean, jb[0].stddev ** 2, scale)
         row = _device_pairs(sides[0], sides[1], center[None], s[None], np.array([h]))[0]
         return _two_sample_joint(row, names, h, s, center)
+
+    # ---- entropic optimal transport between the joint particles (csrc/is_sinkhorn.hip) -------------------------------------
+    def sinkhorn(self, other, addresses=None, epsilon=None, scale=None, num_samples=None, seed=None, tol=1e-3, max_iter=1000):
+        """The entropic optimal-transport distance between the JOINT posterior of several latents and `other`'s, as a
+        TwoSampleTransport: the debiased Sinkhorn divergence ot_ab - (ot_aa + ot_bb) / 2 of the two weighted particle sets under the
+        cost |z - z'|^2 / 2 and wasserstein2 = sqrt(2 max(divergence, 0)), in standardised units. The importance weights are the
+        marginals: nothing is resampled. addresses, scale, num_samples, seed: as compare_joint takes them (the same resolution,
+        standardisation by the equal mixture of the two sides, and systematic resampling). epsilon: the regularisation in
+        standardised units squared, default 0.05 J (a twentieth of compare_joint's default h^2). The three problems iterate in the log
+        domain (include/pyprob_amd.h states the updates) until their residual - the largest move of a potential over epsilon - is
+        below tol, or max_iter: a problem that max_iter stopped raises a UserWarning.
+
+        Two sides whose columns are float32 tensors on one device take ONE pp_is_sinkhorn_groups call: no n_a x n_b matrix is stored,
+        a half-step is a log-sum-exp on the fp32 matrix pipe under a running maximum, the host reads one word every eighth iteration.
+        Every other pair, and all of them under PP_EMPIRICAL_DEVICE=0, takes the same definition in chunked float64 numpy
+        (empirical_host._host_sinkhorn; num_samples is not served there)."""
+        if not isinstance(other, Empirical):
+            raise TypeError('sinkhorn takes another Empirical, not %r' % type(other).__name__)
+        for e in (self, other):
+            e._check_finalized()
+        names, lw_a, cols_a, stats_a = self._pair_columns(addresses)
+        _, lw_b, cols_b, stats_b = other._pair_columns(names if addresses is None else addresses)
+        J = len(names)
+        if not 1 <= J <= 8:
+            raise ValueError('sinkhorn takes 1 .. 8 addresses, not %d' % J)
+        eps = _sinkhorn_epsilon(epsilon, J)
+        if not (float(tol) >= 0.0 and int(max_iter) >= 1):
+            raise ValueError('sinkhorn takes tol >= 0 and max_iter >= 1')
+        tensors = [lw_a, lw_b] + list(cols_a) + list(cols_b)
+        device = os.environ.get('PP_EMPIRICAL_DEVICE', '1') != '0' and all(
+            torch.is_tensor(t) and t.is_cuda and t.device == lw_a.device and t.dtype == torch.float32 and t.dim() == 1 and
+            t.is_contiguous() for t in tensors)
+        if not device:
+            if num_samples is not None:
+                raise ValueError('num_samples needs two posteriors whose columns are on one device')
+            to_np = lambda t: t.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(t) else np.asarray(t, np.float64)  # noqa: E731
+            (lw_a, x_a), (lw_b, x_b) = ((to_np(lw), np.stack([to_np(c) for c in cols], 1)) for lw, cols in ((lw_a, cols_a), (lw_b, cols_b)))
+            ma, mb = _host_joint_moments(lw_a, x_a), _host_joint_moments(lw_b, x_b)
+            center, s = _pairs_standardise(ma[0], ma[1] ** 2, mb[0], mb[1] ** 2, scale)
+            row, f, g = _host_sinkhorn(lw_a, x_a, lw_b, x_b, center, s, eps, tol, max_iter)[:3]
+            return _two_sample_transport(row, f, g, names, eps, s, center, (ma[2], mb[2]), max_iter)
+        if num_samples is not None:
+            key = _philox_key(seed)
+            drawn_a = self.resample_joint(num_samples, names, seed=key, scheme='systematic')
+            drawn_b = other.resample_joint(num_samples, names if addresses is None else addresses, seed=key, offset=1,
+                                           scheme='systematic')
+            cols_a, cols_b = [drawn_a[a] for a in names], [c for a, c in drawn_b.items() if a != 'index']
+            lw_a, lw_b, stats_a, stats_b = torch.zeros_like(cols_a[0]), torch.zeros_like(cols_b[0]), None, None
+        sides = (lw_a, cols_a, lw_a.numel(), stats_a), (lw_b, cols_b, lw_b.numel(), stats_b)
+        ja, jb = (_joint_rows(names, _moment_rows(*side)) for side in sides)
+        center, s = _pairs_standardise(ja[0].mean, ja[0].stddev ** 2, jb[0].mean, jb[0].stddev ** 2, scale)
+        from .ops import ops
+        as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(lw_a.device)      # noqa: E731
+        out, f, g = ops.is_sinkhorn_groups(lw_a, list(cols_a), lw_a.numel(), stats_a, lw_b, list(cols_b), lw_b.numel(), stats_b,
+                                           as_dev(center[None]), as_dev(1.0 / s[None]), as_dev(np.array([eps])), float(tol),
+                                           int(max_iter), 8)[:3]
+        return _two_sample_transport(out[0].cpu().numpy(), f[0], g[0], names, eps, s, center, (float(ja[0].ess), float(jb[0].ess)),
+                                     max_iter)
 
     # ---- joint kernel density and its modes (csrc/is_kde_joint.hip) -------------------------------------------------------
     def _kdej_setup(self, what, addresses, bandwidth, scale):
@@ -1988,6 +2046,41 @@ class TwoSampleJoint:
 def _two_sample_joint(row, addresses, bandwidth, scale, center):
     """The TwoSampleJoint of a row of pp_is_pairs_groups' out and the standardisation it was computed under."""
     return TwoSampleJoint(row[:6], row[6:8], row[8:10], addresses, bandwidth, scale, center)
+
+
+class TwoSampleTransport:
+    """The entropic optimal-transport distance between two weighted samples of J latents (Empirical.sinkhorn): ot_ab, ot_aa, ot_bb
+    (the dual values sum a f + sum b g of the three problems under the cost |z - z'|^2 / 2), divergence = ot_ab - (ot_aa + ot_bb) / 2
+    (the debiased Sinkhorn divergence), wasserstein2 = sqrt(2 max(divergence, 0)) in standardised units; epsilon, scale [J], center
+    [J] (z = (x - center) / scale), addresses, count and ess of each side; n_iter, converged and residual of the problems (ab, aa,
+    bb); f [n_a], g [n_b]: the potentials of problem (a, b) - device tensors from the device route, numpy arrays from the host's -
+    NaN where a particle does not count."""
+
+    def __init__(self, row, f, g, addresses, epsilon, scale, center, ess):
+        self.ot_ab, self.ot_aa, self.ot_bb = (float(v) for v in row[:3])
+        self.divergence = self.ot_ab - 0.5 * (self.ot_aa + self.ot_bb)
+        self.wasserstein2 = math.sqrt(2.0 * max(self.divergence, 0.0)) if self.divergence == self.divergence else float('nan')
+        self.n_iter = tuple(int(v) for v in row[3:6])
+        self.residual = tuple(float(v) for v in row[6:9])
+        self.converged = tuple(not (int(row[11]) >> p) & 1 and not int(row[11]) & 8 for p in range(3))
+        self.count = (int(row[9]), int(row[10]))
+        self.addresses, self.epsilon = list(addresses), float(epsilon)
+        self.scale, self.center = np.array(scale, np.float64), np.array(center, np.float64)
+        self.ess, self.f, self.g = tuple(ess), f, g
+
+    def __repr__(self):
+        return 'TwoSampleTransport(addresses:{}, divergence:{:.6g}, wasserstein2:{:.6g}, epsilon:{:.4g}, n_iter:{}, count:{})'.format(
+            self.addresses, self.divergence, self.wasserstein2, self.epsilon, self.n_iter, self.count)
+
+
+def _two_sample_transport(row, f, g, addresses, epsilon, scale, center, ess, max_iter):
+    """The TwoSampleTransport of a row of pp_is_sinkhorn_groups' out; a problem that max_iter stopped warns."""
+    r = TwoSampleTransport(row, f, g, addresses, epsilon, scale, center, ess)
+    stopped = [name for name, ok in zip(('(a, b)', '(a, a)', '(b, b)'), r.converged) if not ok]
+    if stopped and not int(row[11]) & 8:
+        warnings.warn('sinkhorn: problem %s did not converge within max_iter=%d (residual %s)'
+                      % (', '.join(stopped), int(max_iter), ', '.join('%.3g' % v for v in r.residual)), UserWarning, stacklevel=3)
+    return r
 
 
 class PsisFit:

@@ -189,6 +189,82 @@ def _host_twosample_joint(lw_a, x_a, lw_b, x_b, bandwidth=None, scale=None, chun
     return row, center, s, h
 
 
+def _sinkhorn_epsilon(epsilon, J):
+    eps = 0.05 * J if epsilon is None else float(epsilon)
+    if not (math.isfinite(eps) and eps > 0):
+        raise ValueError('epsilon must be a finite positive number (standardised units squared)')
+    return eps
+
+
+def _sinkhorn_softmin(z_s, logw_s, pot_s, z_q, eps, chunk=256):
+    """-eps log sum_i w_i exp((pot_i - |z_i - zq|^2 / 2) / eps) per query [Q] in chunked float64 numpy, the maximum of the exponents
+    taken out before the exponential."""
+    out = np.empty(len(z_q))
+    for a in range(0, len(z_q), chunk):
+        r2 = np.zeros((len(z_q[a:a + chunk]), len(z_s)))
+        for j in range(z_s.shape[1]):
+            r2 += (z_q[a:a + chunk, j, None] - z_s[None, :, j]) ** 2
+        e = logw_s[None, :] + (pot_s[None, :] - 0.5 * r2) / eps
+        m = e.max(1)
+        out[a:a + chunk] = -eps * (m + np.log(np.exp(e - m[:, None]).sum(1)))
+    return out
+
+
+def _host_sinkhorn(lw_a, x_a, lw_b, x_b, center, scale, epsilon, tol=1e-3, max_iter=1000):
+    """pp_is_sinkhorn_groups' definition (include/pyprob_amd.h) for one pair of particle sets in chunked float64 numpy: (row of 12, f
+    [n_a], g [n_b], p_a [n_a], p_b [n_b], peak [3]), the potentials NaN where a particle does not count and peak the largest |potential|
+    any iteration of problem ab, aa, bb saw (what the device's error bound takes). x_*: [n, J]."""
+    eps, tol, max_iter = float(epsilon), float(tol), int(max_iter)
+    sides, full = [], []
+    for lw, x in ((lw_a, x_a), (lw_b, x_b)):
+        lw, x = np.asarray(lw, np.float64).reshape(-1), np.asarray(x, np.float64)
+        with np.errstate(invalid='ignore'):
+            z = (x.reshape(len(lw), -1) - center) * (1.0 / scale)
+        keep = np.isfinite(lw) & np.isfinite(z).all(1)
+        sides.append(_kdej_counted(lw, x, center, scale))
+        full.append(keep)
+    (za, la), (zb, lb) = sides
+    row = np.full(12, np.nan)
+    row[3:6], row[9], row[10] = 0.0, len(la), len(lb)
+
+    def spread(pot, keep):
+        out = np.full(len(keep), np.nan)
+        out[keep] = pot
+        return out
+    if len(la) == 0 or len(lb) == 0:
+        row[11] = 8.0
+        return (row,) + tuple(np.full(len(k), np.nan) for k in (full[0], full[1], full[0], full[1])) + (np.full(3, np.nan),)
+    status, peak = 0, np.zeros(3)
+    f, g = np.zeros(len(la)), np.zeros(len(lb))
+    for it in range(1, max_iter + 1):
+        g_new = _sinkhorn_softmin(za, la, f, zb, eps)
+        f_new = _sinkhorn_softmin(zb, lb, g_new, za, eps)
+        row[6] = max(np.abs(f_new - f).max(), np.abs(g_new - g).max()) / eps
+        f, g, row[3] = f_new, g_new, it
+        peak[0] = max(peak[0], np.abs(f).max(), np.abs(g).max())
+        if row[6] < tol:
+            break
+    else:
+        status |= 1
+    row[0] = (np.exp(la) * f).sum() + (np.exp(lb) * g).sum()
+    pots = []
+    for k, (z, l) in enumerate(sides):
+        p = np.zeros(len(l))
+        for it in range(1, max_iter + 1):
+            p_new = 0.5 * (p + _sinkhorn_softmin(z, l, p, z, eps))
+            row[7 + k] = np.abs(p_new - p).max() / eps
+            p, row[4 + k] = p_new, it
+            peak[1 + k] = max(peak[1 + k], np.abs(p).max())
+            if row[7 + k] < tol:
+                break
+        else:
+            status |= 2 << k
+        row[1 + k] = 2.0 * (np.exp(l) * p).sum()
+        pots.append(p)
+    row[11] = status
+    return row, spread(f, full[0]), spread(g, full[1]), spread(pots[0], full[0]), spread(pots[1], full[1]), peak
+
+
 def _kdej_standardise(mean, stddev, scale):
     """(center, scale) [J] of kde_joint / modes: the object's own joint() mean and per-address standard deviation, or the caller's J
     positive numbers in place of the latter."""

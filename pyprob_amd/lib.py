@@ -47,6 +47,10 @@ PP_IS_PAIRS_WIDTH = 10       # doubles per group of pp_is_pairs_groups' out (inc
 # particles of a block and of a staged chunk, the most strips and the workgroups aimed at per group, the largest Q and J
 PP_IS_KDEJ_QUERY_BLOCK, PP_IS_KDEJ_QUERY_TILE, PP_IS_KDEJ_PARTICLE_BLOCK, PP_IS_KDEJ_CHUNK = 32, 128, 32, 256
 PP_IS_KDEJ_MAX_STRIPS, PP_IS_KDEJ_TARGET_WORKGROUPS, PP_IS_KDEJ_MAX_Q, PP_IS_KDEJ_MAX_J = 128, 1024, 65536, 8
+# pp_is_sinkhorn_groups (include/pyprob_amd.h): the same tiling of a half-step, its strips, the groups of a call, doubles per out row
+PP_IS_SINKHORN_QUERY_BLOCK, PP_IS_SINKHORN_QUERY_TILE, PP_IS_SINKHORN_PARTICLE_BLOCK, PP_IS_SINKHORN_CHUNK = 32, 128, 32, 256
+PP_IS_SINKHORN_MAX_STRIPS, PP_IS_SINKHORN_TARGET_WORKGROUPS, PP_IS_SINKHORN_MAX_J = 16, 1024, 8
+PP_IS_SINKHORN_MAX_GROUPS, PP_IS_SINKHORN_WIDTH = 16383, 12
 
 
 def PP_IS_MOMENTS_WIDTH(n_cols):
@@ -272,6 +276,10 @@ PROTOTYPES = {
     'pp_is_kde_joint_groups': (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, i32, vp, vp, vp, vp, C.c_size_t, vp]),
     'pp_is_meanshift_groups': (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, i32, C.c_double, i32, i32, vp, vp, vp, vp, vp,
                                          vp, C.c_size_t, vp]),
+    'pp_is_sinkhorn_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
+    'pp_is_sinkhorn_strips': (i32, [i32, i32]),
+    'pp_is_sinkhorn_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, vp, vp, vp,
+                                        vp, C.c_size_t, vp]),
     'pp_is_pairs_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
