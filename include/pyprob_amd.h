@@ -1115,6 +1115,43 @@ int pp_is_sinkhorn_groups(const float* lw_a /*dev [M n_per_a]*/, const float* co
                           double* g /*dev [M, n_per_b] or NULL*/, double* p_a /*dev [M, n_per_a] or NULL*/,
                           double* p_b /*dev [M, n_per_b] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The barycentric projection of the entropic plan of problem (a, b), in both directions, on the device
+ * (Empirical.sinkhorn(transport=True)). INPUTS: pp_is_sinkhorn_groups' per-side arguments, n_cols, n_groups, center, inv_scale and
+ * epsilon, with the same standardisation and COUNTING rule, then the potentials f [M, n_a] and g [M, n_b] (device doubles): plain
+ * inputs - the operator does not care whether they are converged; NaN is allowed at particles that do not count. With a, b, C_ij as
+ * above and P_ij = a_i b_j exp((f_i + g_j - C_ij) / eps):
+ *   map_ab [M, n_a, J]   map_ab[g, i, :] = center + scale (sum_j b_j exp((g_j - C_ij) / eps) z'_j / sum_j b_j exp((g_j - C_ij) / eps))
+ *                        = center + scale sum_j P_ij z'_j / sum_j P_ij: the query's own potential and weight cancel; scale = 1 / inv_scale
+ *   map_ba [M, n_b, J]   the mirror, with a, f and z
+ *   log_mass_a [M, n_a]  f_i / eps + log sum_j b_j exp((g_j - C_ij) / eps) = log(sum_j P_ij / a_i): 0 where the marginal constraint
+ *                        holds - how far an unconverged plan is from its marginals, particle by particle
+ *   log_mass_b [M, n_b]  the mirror
+ * Each of the four may be NULL; a direction with both of its outputs NULL is not launched. Rows of particles that do not count are
+ * NaN, and so is a whole group with a side without a counted particle.
+ * Launches, dependent on the caller's stream: per side (the tile maxima, then) one operand pass writing pp_is_pairs_groups' Gaussian
+ * image with the side's potential in its q column, q = fp32(log2(e) (lw - max + pot / eps) - alpha^2 |z|^2 / 2); ONE main launch for
+ * both directions of all groups (grid dimension z) with pp_is_sinkhorn_groups' tiling (PP_IS_SINKHORN_QUERY_TILE queries and one of
+ * pp_is_sinkhorn_strips(n_sum, n_query) strips of the summed side per workgroup, staged through LDS in chunks of PP_IS_SINKHORN_CHUNK):
+ * the exponents of a block from v_mfma_f32_32x32x2_f32 under an integer running maximum, v_exp_f32, and a second product on the same
+ * instruction, fed from the accumulator registers, whose A rows are the summed side's alpha z and a row of ones - the normaliser comes
+ * off the matrix pipe; one combine launch (a thread per query merges the strips in strip order). No atomics, no workgroup waits for
+ * another, no scratch in the main kernel; the order of every sum is a function of (n_per_a, n_per_b, n_cols) alone: two calls give
+ * the same bits, and group g of an M-group call equals the one-group call on its slices. Memory is O(M (n_per_a + n_per_b) n_cols): no
+ * n_a x n_b matrix is stored. The derived error bound is at the head of csrc/is_sinkhorn_map.hip.
+ * The envelope is pp_is_sinkhorn_groups'. PP_EINVAL without a launch for a NULL pointer (stats_a, stats_b and the four outputs may be
+ * NULL), a shape outside the envelope, M n_per_a or M n_per_b above 2^31 - 1; PP_ENOSPACE for a short workspace;
+ * pp_is_sinkhorn_map_workspace_bytes returns 0 outside the envelope. */
+size_t pp_is_sinkhorn_map_workspace_bytes(int32_t n_groups, int32_t n_per_a, int32_t n_per_b, int32_t n_cols);
+int pp_is_sinkhorn_map_groups(const float* lw_a /*dev [M n_per_a]*/, const float* const* cols_a /*host array of J dev pointers*/,
+                              const double* stats_a /*dev [M, 6] or NULL*/, int32_t n_per_a, const float* lw_b /*dev [M n_per_b]*/,
+                              const float* const* cols_b /*host array of J dev pointers*/, const double* stats_b /*dev [M, 6] or NULL*/,
+                              int32_t n_per_b, int32_t n_cols, int32_t n_groups, const double* center /*dev [M, J]*/,
+                              const double* inv_scale /*dev [M, J]*/, const double* epsilon /*dev [M]*/,
+                              const double* f /*dev [M, n_per_a]*/, const double* g /*dev [M, n_per_b]*/,
+                              double* map_ab /*dev [M, n_per_a, J] or NULL*/, double* map_ba /*dev [M, n_per_b, J] or NULL*/,
+                              double* log_mass_a /*dev [M, n_per_a] or NULL*/, double* log_mass_b /*dev [M, n_per_b] or NULL*/,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Pareto-smoothed importance weights and the k-hat diagnostic of a lock-step posterior call on the device (PSIS: Vehtari, Simpson,
  * Gelman, Yao, Gabry, JMLR 2024). The reference has no counterpart: the only reliability figure of its Empirical is
  * effective_sample_size (pyprob/distributions/empirical.py:758-766), which looks healthy exactly when the proposal misses a heavy tail.

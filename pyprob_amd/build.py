@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libpyprob_amd.so')
-SOURCES = ['gemm_f32.hip', 'kernels.hip', 'engine.hip', 'panel.hip', 'panel16.hip', 'lstm_input.hip', 'wgrad_t1.hip', 'is_kernels.hip', 'is_step_fused.hip', 'is_step_small.hip', 'obs_embed.hip', 'pack.hip', 'train_loop.hip', 'lstm_tail.hip', 'dp.hip', 'optim.hip', 'dist_kernels.hip', 'cnn2d.hip', 'obs_draw.hip', 'obs_logweight.hip', 'is_batch.hip', 'is_resample.hip', 'is_moments.hip', 'is_hist.hip', 'is_sort.hip', 'is_gmm.hip', 'is_hpd.hip', 'is_psis.hip', 'is_reobserve.hip', 'is_gmm_joint.hip', 'is_kde.hip', 'is_twosample.hip', 'is_pairs.hip', 'is_proposal.hip', 'is_kde_joint.hip', 'is_sinkhorn.hip']
+SOURCES = ['gemm_f32.hip', 'kernels.hip', 'engine.hip', 'panel.hip', 'panel16.hip', 'lstm_input.hip', 'wgrad_t1.hip', 'is_kernels.hip', 'is_step_fused.hip', 'is_step_small.hip', 'obs_embed.hip', 'pack.hip', 'train_loop.hip', 'lstm_tail.hip', 'dp.hip', 'optim.hip', 'dist_kernels.hip', 'cnn2d.hip', 'obs_draw.hip', 'obs_logweight.hip', 'is_batch.hip', 'is_resample.hip', 'is_moments.hip', 'is_hist.hip', 'is_sort.hip', 'is_gmm.hip', 'is_hpd.hip', 'is_psis.hip', 'is_reobserve.hip', 'is_gmm_joint.hip', 'is_kde.hip', 'is_twosample.hip', 'is_pairs.hip', 'is_proposal.hip', 'is_kde_joint.hip', 'is_sinkhorn.hip', 'is_sinkhorn_map.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-inline-asm']
 # Per-source additions. is_gmm_joint.hip: no packed fp32 arithmetic (its float work is loads and conversions to fp64 only).
 # is_kde.hip: the same - the P chains of a lane stay scalar fp32 operations, whose roundings the error bound counts one by one.
@@ -50,9 +50,11 @@ VGPR_LIMITS = {'gemm_f32_async_grouped_aux_kernel': 128, 'gemm_f32_async_grouped
 # The proposal's particle kernel keeps eight particles of J floats, their Philox words and deviates in registers; its component is LDS's.
 # The joint density's main kernel keeps a query's fragments, a staged particle, two 32 x 32 accumulator blocks and five fp64 sums per lane.
 # The Sinkhorn half-step keeps a query's fragments, a staged particle, one 32 x 32 accumulator block and one fp64 sum per lane.
+# The transport map's main kernel keeps the same with a second accumulator block and five fp64 sums per lane.
 NO_SCRATCH = ('joint_tile_kernel', 'kde_tile_kernel', 'kde2d_tile_kernel', 'twosample_tile_kernel', 'pairs_gauss_kernel',
               'pairs_dist_kernel', 'pairs_operand_kernel', 'proposal_particle_kernel', 'proposal_prepare_kernel', 'kdej_main_kernel',
-              'kdej_combine_kernel', 'kdej_shift_kernel', 'sink_main_kernel', 'sink_update_kernel')
+              'kdej_combine_kernel', 'kdej_shift_kernel', 'sink_main_kernel', 'sink_update_kernel', 'map_main_kernel',
+              'map_combine_kernel')
 
 
 def _check_registers(remarks):

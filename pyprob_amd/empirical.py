@@ -11,7 +11,7 @@ import torch
 
 from .empirical_host import (_host_ecdf, _host_extent, _host_gmm, _host_hist_row, _host_hpd, _host_joint_moments, _host_kde,
                              _host_kde_joint, _host_meanshift, _host_order, _host_psis, _host_quantiles, _host_twosample,
-                             _host_sinkhorn, _host_twosample_joint, _kdej_standardise, _kolmogorov_sf, _merge_modes, _pairs_bandwidth,
+                             _host_sinkhorn, _host_sinkhorn_map, _host_twosample_joint, _kdej_standardise, _kolmogorov_sf, _merge_modes, _pairs_bandwidth,
                              _pairs_standardise, _sinkhorn_epsilon)
 
 
@@ -872,7 +872,8 @@ class Empirical:
         return _two_sample_joint(row, names, h, s, center)
 
     # ---- entropic optimal transport between the joint particles (csrc/is_sinkhorn.hip) -------------------------------------
-    def sinkhorn(self, other, addresses=None, epsilon=None, scale=None, num_samples=None, seed=None, tol=1e-3, max_iter=1000):
+    def sinkhorn(self, other, addresses=None, epsilon=None, scale=None, num_samples=None, seed=None, tol=1e-3, max_iter=1000,
+                 transport=False):
         """The entropic optimal-transport distance between the JOINT posterior of several latents and `other`'s, as a
         TwoSampleTransport: the debiased Sinkhorn divergence ot_ab - (ot_aa + ot_bb) / 2 of the two weighted particle sets under the
         cost |z - z'|^2 / 2 and wasserstein2 = sqrt(2 max(divergence, 0)), in standardised units. The importance weights are the
@@ -885,7 +886,14 @@ class Empirical:
         Two sides whose columns are float32 tensors on one device take ONE pp_is_sinkhorn_groups call: no n_a x n_b matrix is stored,
         a half-step is a log-sum-exp on the fp32 matrix pipe under a running maximum, the host reads one word every eighth iteration.
         Every other pair, and all of them under PP_EMPIRICAL_DEVICE=0, takes the same definition in chunked float64 numpy
-        (empirical_host._host_sinkhorn; num_samples is not served there)."""
+        (empirical_host._host_sinkhorn; num_samples is not served there).
+
+        transport=True adds the barycentric projection of the plan of problem (a, b) at the returned f, g: map_ab [n_a, J], where the
+        plan sends each particle of this posterior (the plan-weighted mean of `other`'s particles, original coordinates), map_ba [n_b,
+        J] the mirror, and log_mass_a, log_mass_b, the log of every particle's plan mass over its weight (0 where the marginal holds);
+        displacement() is (map_ab - x_a, map_ba - x_b). One more operator call (pp_is_sinkhorn_map_groups) on the device route, the
+        same definition in numpy (empirical_host._host_sinkhorn_map) on the host's; with num_samples the maps belong to the drawn
+        particles. Without it the four fields are None and nothing else changes."""
         if not isinstance(other, Empirical):
             raise TypeError('sinkhorn takes another Empirical, not %r' % type(other).__name__)
         for e in (self, other):
@@ -910,7 +918,10 @@ class Empirical:
             ma, mb = _host_joint_moments(lw_a, x_a), _host_joint_moments(lw_b, x_b)
             center, s = _pairs_standardise(ma[0], ma[1] ** 2, mb[0], mb[1] ** 2, scale)
             row, f, g = _host_sinkhorn(lw_a, x_a, lw_b, x_b, center, s, eps, tol, max_iter)[:3]
-            return _two_sample_transport(row, f, g, names, eps, s, center, (ma[2], mb[2]), max_iter)
+            r = _two_sample_transport(row, f, g, names, eps, s, center, (ma[2], mb[2]), max_iter)
+            if transport:
+                r._set_transport(_host_sinkhorn_map(lw_a, x_a, lw_b, x_b, center, s, eps, f, g), x_a, x_b)
+            return r
         if num_samples is not None:
             key = _philox_key(seed)
             drawn_a = self.resample_joint(num_samples, names, seed=key, scheme='systematic')
@@ -923,11 +934,15 @@ class Empirical:
         center, s = _pairs_standardise(ja[0].mean, ja[0].stddev ** 2, jb[0].mean, jb[0].stddev ** 2, scale)
         from .ops import ops
         as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(lw_a.device)      # noqa: E731
-        out, f, g = ops.is_sinkhorn_groups(lw_a, list(cols_a), lw_a.numel(), stats_a, lw_b, list(cols_b), lw_b.numel(), stats_b,
-                                           as_dev(center[None]), as_dev(1.0 / s[None]), as_dev(np.array([eps])), float(tol),
-                                           int(max_iter), 8)[:3]
-        return _two_sample_transport(out[0].cpu().numpy(), f[0], g[0], names, eps, s, center, (float(ja[0].ess), float(jb[0].ess)),
-                                     max_iter)
+        setup = (lw_a, list(cols_a), lw_a.numel(), stats_a, lw_b, list(cols_b), lw_b.numel(), stats_b, as_dev(center[None]),
+                 as_dev(1.0 / s[None]), as_dev(np.array([eps])))
+        out, f, g = ops.is_sinkhorn_groups(*setup, float(tol), int(max_iter), 8)[:3]
+        r = _two_sample_transport(out[0].cpu().numpy(), f[0], g[0], names, eps, s, center, (float(ja[0].ess), float(jb[0].ess)),
+                                  max_iter)
+        if transport:
+            r._set_transport([t[0] for t in ops.is_sinkhorn_map_groups(*setup, f, g, True, True)],
+                             *(torch.stack(list(cols), 1).double() for cols in (cols_a, cols_b)))
+        return r
 
     # ---- joint kernel density and its modes (csrc/is_kde_joint.hip) -------------------------------------------------------
     def _kdej_setup(self, what, addresses, bandwidth, scale):
@@ -2054,7 +2069,11 @@ class TwoSampleTransport:
     (the debiased Sinkhorn divergence), wasserstein2 = sqrt(2 max(divergence, 0)) in standardised units; epsilon, scale [J], center
     [J] (z = (x - center) / scale), addresses, count and ess of each side; n_iter, converged and residual of the problems (ab, aa,
     bb); f [n_a], g [n_b]: the potentials of problem (a, b) - device tensors from the device route, numpy arrays from the host's -
-    NaN where a particle does not count."""
+    NaN where a particle does not count. From sinkhorn(transport=True) also map_ab [n_a, J], map_ba [n_b, J] - the barycentric
+    projection of the plan of problem (a, b) at f, g: where each particle's mass goes, in the original coordinates - and log_mass_a
+    [n_a], log_mass_b [n_b], the log of a particle's plan mass over its weight (0 where the marginal holds), with NaN rows where a
+    particle does not count; displacement() is (map_ab - x_a, map_ba - x_b). Without transport the four are None."""
+    map_ab = map_ba = log_mass_a = log_mass_b = None
 
     def __init__(self, row, f, g, addresses, epsilon, scale, center, ess):
         self.ot_ab, self.ot_aa, self.ot_bb = (float(v) for v in row[:3])
@@ -2067,6 +2086,17 @@ class TwoSampleTransport:
         self.addresses, self.epsilon = list(addresses), float(epsilon)
         self.scale, self.center = np.array(scale, np.float64), np.array(center, np.float64)
         self.ess, self.f, self.g = tuple(ess), f, g
+
+    def _set_transport(self, maps, x_a, x_b):
+        """maps: pp_is_sinkhorn_map_groups' four outputs of this pair; x_a [n_a, J], x_b [n_b, J]: the particles they belong to."""
+        self.map_ab, self.map_ba, self.log_mass_a, self.log_mass_b = maps
+        self._x = (x_a, x_b)
+
+    def displacement(self):
+        """(map_ab - x_a [n_a, J], map_ba - x_b [n_b, J]): where the plan moves every particle, in the original coordinates."""
+        if self.map_ab is None:
+            raise ValueError('displacement needs sinkhorn(..., transport=True)')
+        return self.map_ab - self._x[0], self.map_ba - self._x[1]
 
     def __repr__(self):
         return 'TwoSampleTransport(addresses:{}, divergence:{:.6g}, wasserstein2:{:.6g}, epsilon:{:.4g}, n_iter:{}, count:{})'.format(

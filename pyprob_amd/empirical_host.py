@@ -265,6 +265,36 @@ def _host_sinkhorn(lw_a, x_a, lw_b, x_b, center, scale, epsilon, tol=1e-3, max_i
     return row, spread(f, full[0]), spread(g, full[1]), spread(pots[0], full[0]), spread(pots[1], full[1]), peak
 
 
+def _host_sinkhorn_map(lw_a, x_a, lw_b, x_b, center, scale, epsilon, f, g, chunk=256):
+    """pp_is_sinkhorn_map_groups' definition (include/pyprob_amd.h) for one pair of particle sets in chunked float64 numpy: (map_ab [n_a,
+    J], map_ba [n_b, J], log_mass_a [n_a], log_mass_b [n_b]) from the potentials f [n_a], g [n_b] (NaN allowed where a particle does
+    not count), NaN rows where a particle does not count or a side has no counted particle. x_*: [n, J]."""
+    eps, center, scale = float(epsilon), np.asarray(center, np.float64), np.asarray(scale, np.float64)
+    sides = []
+    for lw, x, pot in ((lw_a, x_a, f), (lw_b, x_b, g)):
+        lw, x = np.asarray(lw, np.float64).reshape(-1), np.asarray(x, np.float64)
+        with np.errstate(invalid='ignore'):
+            keep = np.isfinite(lw) & np.isfinite((x.reshape(len(lw), -1) - center) * (1.0 / scale)).all(1)
+        sides.append(_kdej_counted(lw, x, center, scale) + (np.asarray(pot, np.float64).reshape(-1)[keep], keep))
+    out = []
+    for (zq, _, pq, keep_q), (zs, ls, ps, _) in ((sides[0], sides[1]), (sides[1], sides[0])):
+        T, mass = np.full((len(keep_q), zq.shape[1]), np.nan), np.full(len(keep_q), np.nan)
+        if len(ls) and len(pq):
+            mean, lm = np.empty_like(zq), np.empty(len(zq))
+            for a in range(0, len(zq), chunk):
+                r2 = np.zeros((len(zq[a:a + chunk]), len(zs)))
+                for j in range(zs.shape[1]):
+                    r2 += (zq[a:a + chunk, j, None] - zs[None, :, j]) ** 2
+                e = ls[None, :] + (ps[None, :] - 0.5 * r2) / eps
+                m = e.max(1)
+                p = np.exp(e - m[:, None])
+                mean[a:a + chunk] = (p @ zs) / p.sum(1)[:, None]
+                lm[a:a + chunk] = pq[a:a + chunk] / eps + (m + np.log(p.sum(1)))
+            T[keep_q], mass[keep_q] = center + scale * mean, lm
+        out.append((T, mass))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
 def _kdej_standardise(mean, stddev, scale):
     """(center, scale) [J] of kde_joint / modes: the object's own joint() mean and per-address standard deviation, or the caller's J
     positive numbers in place of the latter."""

@@ -280,6 +280,9 @@ PROTOTYPES = {
     'pp_is_sinkhorn_strips': (i32, [i32, i32]),
     'pp_is_sinkhorn_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.c_double, i32, i32, vp, vp, vp, vp, vp,
                                         vp, C.c_size_t, vp]),
+    'pp_is_sinkhorn_map_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
+    'pp_is_sinkhorn_map_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                            C.c_size_t, vp]),
     'pp_is_pairs_groups': (C.c_int, [vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, C.c_size_t, vp]),
     'pp_logweight_accumulate': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),
     'pp_logweight_accumulate_rows': (C.c_int, [i32, vp, i32, vp, i32, vp, i32, C.c_float, vp, vp, i32, vp]),

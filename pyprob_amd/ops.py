@@ -45,6 +45,7 @@ kernels for these operators from tests/, to execute the host logic above them wi
     is_kde_joint_groups product-Gaussian kernel density and mean-shift mean of joint particles at points (the reference has none)   -
     is_meanshift_groups mean shift from seeds to the joint modes, iterated on the device (the reference has none)   -
     is_sinkhorn_groups  entropic OT costs of the debiased Sinkhorn divergence between two groups of joint particles (the reference has none)   -
+    is_sinkhorn_map_groups  barycentric transport maps and row masses of an entropic plan, both directions, from given potentials (the reference has none)   -
     reobserve_groups    the particles of one call re-scored under M new observations (reobserve)  pyprob/distributions/empirical.py:469-544
 
 Non-tensor state travels as follows: the network description (`pp_net`, host struct with offsets into the flat
@@ -133,6 +134,9 @@ _lib.define('is_meanshift_groups(Tensor lw, Tensor[] cols, int n_per, Tensor? st
 _lib.define('is_sinkhorn_groups(Tensor lw_a, Tensor[] cols_a, int n_per_a, Tensor? stats_a, Tensor lw_b, Tensor[] cols_b, int n_per_b, '
             'Tensor? stats_b, Tensor center, Tensor inv_scale, Tensor epsilon, float tol, int max_iter, int check_every) '
             '-> (Tensor, Tensor, Tensor, Tensor, Tensor)')
+_lib.define('is_sinkhorn_map_groups(Tensor lw_a, Tensor[] cols_a, int n_per_a, Tensor? stats_a, Tensor lw_b, Tensor[] cols_b, '
+            'int n_per_b, Tensor? stats_b, Tensor center, Tensor inv_scale, Tensor epsilon, Tensor f, Tensor g, bool want_ab, '
+            'bool want_ba) -> (Tensor, Tensor, Tensor, Tensor)')
 _lib.define('reobserve_groups(Tensor lw, Tensor? old, int[] kinds, int[] ks, float[] scales, Tensor?[] params, Tensor[] xs, '
             'int n_groups) -> Tensor')
 _lib.define('dist_logweight(Tensor(a!)? lw, int[] kinds, Tensor?[] params, int[] strides, Tensor[] x, float[] scales, Tensor? rows, '
@@ -1216,6 +1220,52 @@ def _is_sinkhorn_groups_hip(lw_a, cols_a, n_per_a, stats_a, lw_b, cols_b, n_per_
     return out, f, g, p_a, p_b
 
 
+def _is_sinkhorn_map_groups_hip(lw_a, cols_a, n_per_a, stats_a, lw_b, cols_b, n_per_b, stats_b, center, inv_scale, epsilon, f, g,
+                                want_ab, want_ba):
+    """(map_ab float64 [M, n_per_a, J], map_ba [M, n_per_b, J], log_mass_a [M, n_per_a], log_mass_b [M, n_per_b]): the barycentric
+    projection of the entropic plan P_ij = a_i b_j exp((f_i + g_j - C_ij) / eps) between group g of side a and of side b in both
+    directions, in the original coordinates, and the log of every row's (column's) mass over its marginal; NaN rows where a particle
+    does not count (pp_is_sinkhorn_map_groups). The sides, center, inv_scale and epsilon as is_sinkhorn_groups takes them; f [M,
+    n_per_a], g [M, n_per_b]: float64 potentials, converged or not. A direction that is not wanted is not launched and comes back as
+    two empty tensors."""
+    what = 'is_sinkhorn_map_groups'
+    lib = L.load()
+    cols_a, cols_b = list(cols_a), list(cols_b)
+    _same_device(lw_a, stats_a, lw_b, stats_b, center, inv_scale, epsilon, f, g, *cols_a, *cols_b)
+    M = _groups_of(_f32(lw_a, 'lw_a'), n_per_a, what)
+    J = len(cols_a)
+    if _groups_of(_f32(lw_b, 'lw_b'), n_per_b, what) != M or len(cols_b) != J:
+        raise RuntimeError('pyprob_hip::%s: the two sides hold the same number of groups and of columns' % what)
+    if not 1 <= J <= L.PP_IS_SINKHORN_MAX_J:
+        raise RuntimeError('pyprob_hip::%s: 1 .. %d columns per call' % (what, L.PP_IS_SINKHORN_MAX_J))
+    if M > L.PP_IS_SINKHORN_MAX_GROUPS:
+        raise RuntimeError('pyprob_hip::%s: at most %d groups per call' % (what, L.PP_IS_SINKHORN_MAX_GROUPS))
+    for lw, cols, stats in ((lw_a, cols_a, stats_a), (lw_b, cols_b, stats_b)):
+        for c in cols:
+            _particles_like(c, lw, 'every column', what)
+        _group_stats_ok(stats, M, what)
+    for t, name, shape in ((center, 'center', (M, J)), (inv_scale, 'inv_scale', (M, J)), (epsilon, 'epsilon', (M,)),
+                           (f, 'f', (M, int(n_per_a))), (g, 'g', (M, int(n_per_b)))):
+        if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise RuntimeError('pyprob_hip::%s: %s must be a contiguous float64 tensor of %s' % (what, name, list(shape)))
+    if M and not bool((torch.isfinite(epsilon) & (epsilon > 0)).all()):
+        raise RuntimeError('pyprob_hip::%s: every epsilon must be a finite positive number' % what)
+    dev = lw_a.device
+    out = [torch.empty(shape if want else (0,), dtype=torch.float64, device=dev)
+           for want, shape in ((want_ab, (M, int(n_per_a), J)), (want_ba, (M, int(n_per_b), J)), (want_ab, (M, int(n_per_a))),
+                               (want_ba, (M, int(n_per_b))))]
+    ws, need = _workspace(lib.pp_is_sinkhorn_map_workspace_bytes, dev, M, int(n_per_a), int(n_per_b), J)
+    pa = (C.c_void_p * J)(*[c.data_ptr() for c in cols_a])
+    pb = (C.c_void_p * J)(*[c.data_ptr() for c in cols_b])
+    with torch.cuda.device(dev):
+        rc = lib.pp_is_sinkhorn_map_groups(lw_a.data_ptr(), C.cast(pa, C.c_void_p), L.ptr(stats_a), int(n_per_a), lw_b.data_ptr(),
+                                           C.cast(pb, C.c_void_p), L.ptr(stats_b), int(n_per_b), J, M, center.data_ptr(),
+                                           inv_scale.data_ptr(), epsilon.data_ptr(), f.data_ptr(), g.data_ptr(),
+                                           *[t.data_ptr() if t.numel() else None for t in out], ws.data_ptr(), need, _stream(lw_a))
+    L.check(rc, 'pp_is_sinkhorn_map_groups')
+    return tuple(out)
+
+
 def _kde_rows(t, M, most, name, what):
     """(row length, stride) of a float64 tensor of points: [Q] shared by the groups (stride 0) or [M, Q], one row per group."""
     if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[0] != M) or \
@@ -1460,6 +1510,7 @@ _lib.impl('is_pairs_groups', _is_pairs_groups_hip, 'CUDA')
 _lib.impl('is_kde_joint_groups', _is_kde_joint_groups_hip, 'CUDA')
 _lib.impl('is_meanshift_groups', _is_meanshift_groups_hip, 'CUDA')
 _lib.impl('is_sinkhorn_groups', _is_sinkhorn_groups_hip, 'CUDA')
+_lib.impl('is_sinkhorn_map_groups', _is_sinkhorn_map_groups_hip, 'CUDA')
 _lib.impl('is_psis_groups', _is_psis_groups_hip, 'CUDA')
 _lib.impl('is_gmm_groups', _is_gmm_groups_hip, 'CUDA')
 _lib.impl('is_gmm_joint_groups', _is_gmm_joint_groups_hip, 'CUDA')
